@@ -338,17 +338,101 @@ def guarded_region(region, store, rank, world, timeout_s, report, exit_fn=os._ex
     return value
 
 
-def claim_stdout():
+LINE_BYTES = 8192              # the stdout line stays below this: a longer line is not parsed by the tools that read it
+DETAIL_ONLY = ("rooflines", "traffic_detail", "per_rank", "kernels_in_class")     # keys left to the detail line
+_DROP = object()
+
+
+def compact_line(obj, depth=0):
+    """The stdout line: `obj` without its lists, the keys of DETAIL_ONLY, strings over 80 characters (an "error" keeps its first
+    1000) and dictionaries nested more than two deep (the whole object is the detail line).  Should that still not fit LINE_BYTES,
+    the largest top-level entries go until it does (metric, value, unit and the other scalars always stay)."""
+    if isinstance(obj, dict):
+        if depth >= 3:
+            return _DROP
+        out = {}
+        for k, v in obj.items():
+            if k == "error" and isinstance(v, str):
+                c = v[:1000]
+            else:
+                c = _DROP if k in DETAIL_ONLY else compact_line(v, depth + 1)
+            if c is not _DROP:
+                out[k] = c
+        if depth == 0:
+            while len(json.dumps(out)) >= LINE_BYTES:
+                big = max((k for k in out if isinstance(out[k], dict)), key=lambda k: len(json.dumps(out[k])), default=None)
+                if big is None:
+                    break
+                del out[big]
+        return out
+    if isinstance(obj, str):
+        return obj if len(obj) <= 80 else _DROP
+    if isinstance(obj, (list, tuple)):
+        return _DROP
+    return obj
+
+
+def claim_stdout(detail_path=None):
     """ONE JSON line on stdout: libraries below this process write to file descriptor 1 on their own (RCCL prints a version banner when
     a communicator is made, gloo its connection lines), so from here on everything written to fd 1 -- by them or by print() -- goes to
-    stderr, and the returned function writes an object as one line to the real stdout."""
+    stderr, and the returned function writes an object as one line to the real stdout: compact_line(obj), below LINE_BYTES.  The
+    whole object (rooflines of every class, traffic detail, per-rank figures, prose) goes as one line to `detail_path`, or to stderr."""
     real_stdout = os.dup(1)
     sys.stdout.flush()
     os.dup2(2, 1)
 
     def emit(obj):
-        os.write(real_stdout, (json.dumps(obj) + "\n").encode())
+        full = json.dumps(obj)
+        if detail_path:
+            with open(detail_path, "w") as f:
+                f.write(full + "\n")
+        else:
+            log("detail line: " + full)
+        os.write(real_stdout, (json.dumps(compact_line(obj)) + "\n").encode())
     return emit
+
+
+DUMP_BYTES = 64 << 20          # --dump-outputs: at most this many bytes of .npy files in all
+DUMP_SEED = 20240601           # seed of the fixed sample drawn from an output too large to be written whole
+
+
+def dump_outputs(res, out_dir):
+    """--dump-outputs: what the timed path returned in its last step -- the arrays vlg_result_fetch hands a caller (per-query match
+    counts, offsets into the match list, first position of every match, tuples when materialised) -- as DIR/<name>.npy in float64
+    (every value is an integer below 2^53, so the conversion is exact).  An array longer than its share of DUMP_BYTES is replaced by a
+    fixed, seeded sample of its elements, written as <name>.npy with the sampled element numbers beside it as <name>_index.npy.
+    summary.npy holds the batch's totals (the 64-bit checksum as two 32-bit halves)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    s = res.summary
+    counts = np.zeros(max(s["n_queries"], 1), dtype=np.uint64)
+    offsets = np.zeros(s["n_queries"] + 1, dtype=np.uint64)
+    first = np.zeros(max(s["n_matches"], 1), dtype=np.uint64)
+    tuples = np.zeros(max(s["n_tuple_values"], 1), dtype=np.uint64)
+    res.fetch_into(counts.ctypes.data, offsets.ctypes.data, first.ctypes.data, tuples.ctypes.data if s["n_tuple_values"] else None)
+    counts, first, tuples = counts[: s["n_queries"]], first[: s["n_matches"]], tuples[: s["n_tuple_values"]]
+    chk = s["checksum"] % (1 << 64)
+    arrays = {"summary": np.array([s["n_queries"], s["n_matches"], s["located_occurrences"], s["n_tuple_values"],
+                                   chk & 0xFFFFFFFF, chk >> 32], dtype=np.float64)}
+    # 8 B values: an array is written whole up to its cap, else as cap / 2 sampled values + their element numbers, so at most
+    # 8 + 8 + 16 + 16 MB in all, under DUMP_BYTES with the .npy headers
+    caps = {"counts": 1 << 20, "offsets": 1 << 20, "first_positions": 1 << 21, "tuples": 1 << 21}
+    written = 0
+    for name, a in (("counts", counts), ("offsets", offsets), ("first_positions", first), ("tuples", tuples)):
+        if name == "tuples" and not s["n_tuple_values"]:
+            continue
+        if a.size <= caps[name]:
+            arrays[name] = a.astype(np.float64)
+        else:
+            pick = np.unique(np.random.default_rng(DUMP_SEED).integers(0, a.size, caps[name] // 2, dtype=np.int64))
+            arrays[name] = a[pick].astype(np.float64)
+            arrays[name + "_index"] = pick.astype(np.float64)
+    for name, a in arrays.items():
+        path = os.path.join(out_dir, name + ".npy")
+        np.save(path, a)
+        written += os.path.getsize(path)
+    assert written <= DUMP_BYTES, written
+    log("outputs of the last timed step written to %s: %s (%d bytes)" % (out_dir, ", ".join(sorted(arrays)), written))
 
 
 def other_config(name, steps, warmup, workspace_gb, tuples):
@@ -454,12 +538,20 @@ def main():
                          "(default: RCCL through torch) or vlg_index_broadcast over a communicator made through the C-ABI (the product's "
                          "own RCCL binding).  With the default the product's broadcast runs -- and is timed and checked -- inside the "
                          "guarded strong-scaling region instead, where a failure of the so far one-rank-only path cannot cost the metric")
+    ap.add_argument("--detail", metavar="FILE", default=None,
+                    help="write the whole result object (every class roofline, traffic detail, per-rank figures, prose) as one JSON "
+                         "line to FILE instead of stderr; stdout carries the compact line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (rank 0's batch) as DIR/<name>.npy, float64, "
+                         "<= 64 MB in all (a fixed seeded sample of a longer output)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args)                                     # does not return
 
-    emit = claim_stdout()
+    emit = claim_stdout(args.detail)
     # (the host driver of this pool only supports dmabuf IPC: without this RCCL fails with hipIpcGetMemHandle: invalid argument;
     # set before anything initialises HIP, kept if the launcher already chose a value)
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
@@ -608,6 +700,8 @@ def main():
     kstats = ws.kernel_stats()
     ws.profile(False)
     per_rank = gather_per_rank([my_dt / args.steps * 1e3, s["located_occurrences"], s["n_matches"]])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(res, args.dump_outputs)
 
     # ---- end to end, as SURVEY.md 8(d) words it: parse + H2D of the query batch, search, D2H of counts and first positions
     #      (pinned host buffers; the index upload is separate, as `load` is in gm_search.cpp:68-83) ---------------------------
@@ -919,7 +1013,7 @@ def main():
         for name in [c for c in args.other_configs.split(",") if c]:
             t0 = time.perf_counter()
             try:
-                out["other_configs"][name] = other_config(name, max(2, min(args.steps, 5)), 1, args.workspace_gb, bool(args.tuples))
+                out["other_configs"][name] = other_config(name, args.steps, 1, args.workspace_gb, bool(args.tuples))
             except Exception as e:                                 # noqa: BLE001 -- reported in the line
                 import traceback
                 traceback.print_exc()

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Markdown table of the per-class rooflines of a bench.py line (what DESIGN.md section 6 shows): design_table.py <bench json>"""
+"""Markdown table of the per-class rooflines of a bench.py result (what DESIGN.md section 6 shows): design_table.py <file written by bench.py --detail>"""
 import json
 import sys
 
