@@ -500,6 +500,15 @@ vlg_status vlg_workspace_profile(vlg_workspace* ws, int enable);
 vlg_status vlg_workspace_set_option(vlg_workspace* ws, const char* name, int64_t value);
 vlg_status vlg_workspace_kernel_stats(vlg_workspace* ws, vlg_kernel_stat* out, uint32_t cap, uint32_t* n);
 
+/* The build-time constants the library was compiled with: the tile, run and chunk sizes of the kernels and the switches between
+ * kept alternates (the VLG_* macros of csrc/, set with -D at build time), one {name, value} per constant, name = the macro's name
+ * ("VLG_LINK_RUN", "VLG_RESOLVE_HOPS", ...).  *n = how many there are; at most cap are written.  Needs no device. */
+typedef struct {
+    char name[32];
+    int64_t value;
+} vlg_build_constant;
+vlg_status vlg_build_constants(vlg_build_constant* out, uint32_t cap, uint32_t* n);
+
 /* ------------------------------------------------------------------------------------------
  * Collective search (one process per GPU): ONE batch answered by all ranks of a communicator.
  * Every rank passes the same index image and the same query batch to vlg_search_batch, with a workspace of the same cap.  A batch

@@ -1410,6 +1410,10 @@ def test_k4_list_sort_stand_alone(torch_cuda, V, case):
     want = np.concatenate([np.sort(x) for x in lists])
     L = V.lib()
     import ctypes as C
+    # the windows (and with them the flagging of clustered lists) can be off in the build or, at run time, by VLG_WINDOW_SORT=0
+    windows = os.environ["VLG_WINDOW_SORT"][:1] != "0" if "VLG_WINDOW_SORT" in os.environ else V.capi.build_constants()["VLG_WINDOW_SORT"] != 0
+    if not windows and want_clustered is not None:
+        want_clustered = 0
     for mode in (1, 2):
         d = torch.from_numpy(flat.view(np.int32).copy()).cuda()
         nc = C.c_uint64(99)

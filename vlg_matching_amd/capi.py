@@ -58,6 +58,10 @@ class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("launches", C.c_uint64), ("total_ms", C.c_double), ("algorithmic_bytes", C.c_uint64)]
 
 
+class BuildConstant(C.Structure):
+    _fields_ = [("name", C.c_char * 32), ("value", C.c_int64)]
+
+
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.c_uint32, C.c_int, C.c_int, C.c_void_p)
 ALLTOALL_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p, C.POINTER(C.c_uint64), C.c_uint32, C.c_int, C.c_int,
                           C.c_void_p)
@@ -151,6 +155,7 @@ SYMBOLS = [
     ("vlg_workspace_profile", _I, [_P, _I]),
     ("vlg_workspace_set_option", _I, [_P, C.c_char_p, C.c_int64]),
     ("vlg_workspace_kernel_stats", _I, [_P, C.POINTER(KernelStat), C.c_uint32, C.POINTER(C.c_uint32)]),
+    ("vlg_build_constants", _I, [C.POINTER(BuildConstant), C.c_uint32, C.POINTER(C.c_uint32)]),
     ("vlg_workspace_set_comm", _I, [_P, _P]),
     ("vlg_workspace_set_exchange", _I, [_P, _I, _I, _P, _P]),
     ("vlg_workspace_set_exchange_alltoall", _I, [_P, _I, _I, _P, _P]),
@@ -182,6 +187,15 @@ def lib():
             f.argtypes = args
         _LIB = L
     return _LIB
+
+
+def build_constants():
+    """{macro name: value} of the build-time constants the loaded library was compiled with (vlg_build_constants)."""
+    n = C.c_uint32()
+    check(lib().vlg_build_constants(None, 0, C.byref(n)))
+    arr = (BuildConstant * n.value)()
+    check(lib().vlg_build_constants(arr, n.value, C.byref(n)))
+    return {arr[i].name.decode(): int(arr[i].value) for i in range(n.value)}
 
 
 def check(status):

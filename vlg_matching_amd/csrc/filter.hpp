@@ -212,6 +212,7 @@ __global__ void __launch_bounds__(256) filter_pass_kernel(const pos_t* __restric
 #define VLG_PIVOT_GROUPS 2
 #endif
 constexpr uint32_t kPivotGroups = VLG_PIVOT_GROUPS;
+static_assert(kPivotGroups >= 1, "VLG_PIVOT_GROUPS: at least one group of 64 pivot elements per wave");
 template <typename pos_t>
 __device__ __forceinline__ void pivot_ranges(const pos_t* __restrict__ P, const pos_t* __restrict__ F, uint32_t pbegin, uint32_t pend, const uint64_t (&a)[kPivotGroups],
                                              const uint64_t (&b)[kPivotGroups], bool (&on)[kPivotGroups], uint32_t (&i0)[kPivotGroups],
@@ -496,6 +497,7 @@ constexpr uint32_t kPivotRun = 64 * kPivotGroups;     // pivot elements per wave
 #ifndef VLG_PIVOT_TURNS
 #define VLG_PIVOT_TURNS 1
 #endif
+static_assert(VLG_PIVOT_TURNS >= 1, "VLG_PIVOT_TURNS: at least one run per wave");
 constexpr uint32_t kPivotTurns = VLG_PIVOT_TURNS;     // runs a wave takes one after the other (round 4, C3: 1 -> 21.9 ms, 4 -> 24.1 ms: the task
                                                       // look-up in front of a run is not what the kernel waits for; more, shorter waves win)
 
@@ -651,9 +653,11 @@ __global__ void filter_gather_counts_kernel(const uint32_t* __restrict__ task_ci
 #define VLG_COMPACT_RUNS 16
 #endif
 constexpr uint32_t kCompactRuns = VLG_COMPACT_RUNS;
+static_assert(kCompactRuns >= 1 && kCompactRuns <= 64, "VLG_COMPACT_RUNS: 1 .. 64 (a ballot over the lanes picks the runs with survivors)");
 #ifndef VLG_SPARSE_TURN
 #define VLG_SPARSE_TURN 8
 #endif
+static_assert(VLG_SPARSE_TURN >= 1 && VLG_SPARSE_TURN <= 32, "VLG_SPARSE_TURN: 1 .. 32 (a half word holds 32 survivors at most)");
 constexpr uint32_t kSparseTurn = VLG_SPARSE_TURN;      // survivors of a lane's half word moved per turn of the sparse path: their loads are in flight
                                                        // together (round 4, C3, the class: 2 -> 15.7 ms, 4 -> 13.6, 8 -> 13.3)
 template <typename pos_t>

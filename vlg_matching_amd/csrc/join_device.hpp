@@ -87,6 +87,9 @@ __global__ void fence_build_kernel(const pos_t* __restrict__ P, uint64_t g0, uin
 #endif
 constexpr uint32_t kRungShift = VLG_RUNG_SHIFT, kRungFan = 1u << kRungShift;
 constexpr uint32_t kMaxRungs = 32 / kRungShift;         // f^kMaxRungs elements: more than any index here (32-bit)
+// >= 2: a level's group of f entries is read as f / 4 aligned quads (pivot_ranges_rungs); <= 8: every lane holds 2 x kPivotGroups
+// groups of f entries in registers
+static_assert(kRungShift >= 2 && kRungShift <= 8, "VLG_RUNG_SHIFT: 2 .. 8");
 struct RungLayout { uint64_t off[kMaxRungs + 1]; uint32_t levels; uint64_t entries; };
 inline RungLayout rung_layout(uint64_t total)
 {
@@ -211,6 +214,7 @@ __device__ __forceinline__ uint32_t wave_lower_bound(const pos_t* __restrict__ P
 #ifndef VLG_COOP_WINDOWS2
 #define VLG_COOP_WINDOWS2 4
 #endif
+static_assert(VLG_COOP_WINDOWS2 >= 1, "VLG_COOP_WINDOWS2: at least one window before the far search");
 constexpr uint32_t kCoopWindows2 = VLG_COOP_WINDOWS2;      // round 3, link class on C3: 3 -> 22.2, 4 -> 21.9, 6 -> 22.5, 9 -> 22.8 ms (flat: the
                                                              // far search is about as cheap per key as a window); round 2:            // measured on C3: 2 -> 35.2, 3 -> 33.8, 4 -> 33.2, 6 -> 31.9, 8..16 -> 33..34 ms
 template <typename pos_t>
@@ -403,6 +407,8 @@ constexpr uint32_t kRun = 2048;
 #ifndef VLG_LINK_RUN
 #define VLG_LINK_RUN 2048
 #endif
+// a multiple of 64: runs start on a word of the feasibility bitmap, and a step writes that word whole
+static_assert(VLG_LINK_RUN >= 64 && VLG_LINK_RUN % 64 == 0 && VLG_LINK_RUN <= (1u << 24), "VLG_LINK_RUN: a multiple of 64 slots");
 constexpr uint32_t kLinkRun = VLG_LINK_RUN;      // slots a wave of the link pass takes (round 4, C3: 2048 -> 21.3 ms, 4096 -> 21.9 ms: what stands in front of
                                                  // a run -- segment, metadata, the first fence -- is not what the pass waits for; it is issue-bound)
 

@@ -644,6 +644,7 @@ __global__ void sweep_init_kernel(const uint64_t* __restrict__ l, const uint64_t
 #define VLG_STAGE_LISTS 1
 #endif
 constexpr bool kStageLists = VLG_STAGE_LISTS != 0;
+static_assert(VLG_STAGE_LISTS == 0 || VLG_STAGE_LISTS == 1, "VLG_STAGE_LISTS: 0 or 1");
 constexpr uint32_t kListStage = 256;
 struct ListStage { uint64_t off[kListStage + 1]; uint64_t l[kListStage]; };
 __device__ __forceinline__ bool stage_lists(ListStage& ls, const uint64_t* __restrict__ out_off, const uint64_t* __restrict__ l, uint64_t n_pat,
@@ -785,6 +786,7 @@ __device__ __forceinline__ void sweep_element(const IndexView& iv, const WalkLds
 #define VLG_SWEEP_PAIRS 1
 #endif
 constexpr bool kSweepPairs = VLG_SWEEP_PAIRS != 0;
+static_assert(VLG_SWEEP_PAIRS == 0 || VLG_SWEEP_PAIRS == 1, "VLG_SWEEP_PAIRS: 0 or 1");
 template <class BV, typename pos_t, bool kTrail, bool kWide, bool kTextOrder>
 __global__ void __launch_bounds__(256) sweep_step_kernel(IndexView iv, uint64_t* __restrict__ val, uint16_t* __restrict__ key, uint64_t count,
                                                          uint32_t step, pos_t* __restrict__ out,
@@ -978,7 +980,14 @@ __global__ void __launch_bounds__(256) sweep_first_kernel(IndexView iv, const ui
 // stopped elements in (the per-round tails of its buffers, last round first, then first to last): 35.5 instead of 17.7 ms --
 // neighbours in SA order are not neighbours in slot order; (3) following the chains on a second stream beside the sweep's late rounds:
 // this kernel 18.0 -> 13.3 ms, but the rounds and their partitions slow down by 7 ms: the requests are conserved, not hidden.
-constexpr uint32_t kResolveHops = 4096;       // (64 left 2·10⁵ of C3's 6·10⁸ pointers open -- runs of more than 64 occurrences side by side in the text -- and cost a second pass over all records: 1 ms)
+#ifndef VLG_RESOLVE_HOPS
+#define VLG_RESOLVE_HOPS 4096                 // (64 left 2·10⁵ of C3's 6·10⁸ pointers open -- runs of more than 64 occurrences side by side in the text -- and cost a second pass over all records: 1 ms)
+#endif
+constexpr uint32_t kResolveHops = VLG_RESOLVE_HOPS;
+// A record only ever moves further along its chain, and every hop adds the reach of the record it reads: a round of h hops multiplies
+// the reach of every open record by at least h + 1 >= 2, so a chain of at most 2^33 records closes within 34 rounds -- inside the cap
+// of 64 rounds in run_locate_sweep for any h >= 1.
+static_assert(kResolveHops >= 1, "VLG_RESOLVE_HOPS: at least one hop per round (the reach of a record doubles per round at least)");
 // A workgroup takes kResolveChunk CONSECUTIVE records per turn (not every gridDim-th group of 256): consecutive elements of a list
 // that read the same symbol in front of them follow consecutive elements of another list, so the lines a wave fetches for its hops
 // are the lines the next waves of the same chunk need -- through the CU's own L1 when they belong to one workgroup.
@@ -986,6 +995,7 @@ constexpr uint32_t kResolveHops = 4096;       // (64 left 2·10⁵ of C3's 6·10
 #define VLG_RESOLVE_CHUNK 4096
 #endif
 constexpr uint32_t kResolveChunk = VLG_RESOLVE_CHUNK;
+static_assert(kResolveChunk >= 256 && kResolveChunk % 256 == 0, "VLG_RESOLVE_CHUNK: whole turns of the 256-thread workgroup");
 // The first pass, regrouped.  The 64 consecutive elements a wave holds have ~20 different symbols in front of them, so the records they
 // follow lie in ~20 other lists, three side by side in each: ~40 lines per wave-wide hop (VLG_RESOLVE_STATS).  Elements with the SAME
 // symbol in front follow CONSECUTIVE records (LF restricted to a symbol is monotone), so a workgroup sorts its kGroupChunk records by that
@@ -998,6 +1008,9 @@ constexpr uint32_t kResolveChunk = VLG_RESOLVE_CHUNK;
 #define VLG_GROUP_CHUNK 2048
 #endif
 constexpr uint32_t kGroupChunk = VLG_GROUP_CHUNK;
+static_assert(kGroupChunk >= 256 && kGroupChunk % 256 == 0, "VLG_GROUP_CHUNK: kGroupChunk / 256 records per thread");
+static_assert(kGroupChunk <= 65536, "VLG_GROUP_CHUNK: s_idx holds a record's place in the chunk in 16 bits");
+static_assert(kGroupChunk * (8 + 2) + 258 * 4 <= 160 * 1024, "VLG_GROUP_CHUNK: s_rec + s_idx + s_bin must fit the 160 KiB of LDS a gfx950 workgroup may take");
 template <typename pos_t, bool kWide>
 __global__ void __launch_bounds__(256) trail_resolve_grouped_kernel(uint64_t* __restrict__ rec, uint64_t count, pos_t* __restrict__ out,
                                                                     const uint8_t* __restrict__ front, unsigned long long* __restrict__ n_open)
@@ -1449,7 +1462,9 @@ vlg_status run_locate_sweep(const SweepKernels& K, const uint64_t* d_l, const ui
     for (uint64_t t0 = 0; t0 < total; t0 += batch_max) {
         const uint64_t t1 = std::min(total, t0 + batch_max);
         // (a sweep too short for a single round hands its elements to the stragglers' kernel, which reads their words)
-        const bool fused_first = t1 - t0 > tail_threshold && [] { const char* e = getenv("VLG_NO_FUSED_FIRST_ROUND"); return !(e && e[0] == '1'); }();
+        // (rounds always start with the fused first round: the switch VLG_NO_FUSED_FIRST_ROUND that ran them behind sweep_init_kernel
+        // returned wrong positions and was removed -- DESIGN.md section 5)
+        const bool fused_first = t1 - t0 > tail_threshold;
         if (!fused_first) front_valid = false;                   // (front[] is written by the fused first round only)
         static const bool ahead = [] { const char* e = getenv("VLG_SWEEP_LOOKAHEAD"); return !(e && e[0] == '0'); }();
         if (!fused_first) {
@@ -1708,6 +1723,12 @@ vlg_status launch_widen(const T* d_in, uint64_t* d_out, uint64_t count, hipStrea
     return VLG_OK;
 }
 template vlg_status launch_widen<uint32_t>(const uint32_t*, uint64_t*, uint64_t, hipStream_t);
+
+// the build-time constants of this translation unit (vlg_build_constants)
+KernelConstants kernel_constants()
+{
+    return KernelConstants{VLG_RESOLVE_HOPS, VLG_RESOLVE_CHUNK, VLG_GROUP_CHUNK, VLG_STAGE_LISTS, VLG_SWEEP_PAIRS};
+}
 
 }  // namespace vlg
 

@@ -13,6 +13,10 @@ vlg_status launch_expand(const uint64_t* d_l, const uint64_t* d_out_off, uint64_
 template <typename pos_t>
 vlg_status launch_locate(const IndexView& iv, pos_t* d_io, uint64_t total, unsigned long long* d_stats, hipStream_t stream);
 
+// the build-time constants kernels.hip was compiled with (VLG_RESOLVE_HOPS, ...; reported by vlg_build_constants)
+struct KernelConstants { int64_t resolve_hops, resolve_chunk, group_chunk, stage_lists, sweep_pairs; };
+KernelConstants kernel_constants();
+
 // Optional per-launch timing hooks (HIP events on the stream), implemented by the workspace.
 struct LaunchTimer {
     virtual ~LaunchTimer() {}

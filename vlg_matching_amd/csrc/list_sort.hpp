@@ -31,6 +31,7 @@ constexpr uint32_t kSortChunk = 32;           // tiles per chunk of the histogra
 #ifndef VLG_BUCKET_SORT
 #define VLG_BUCKET_SORT 1
 #endif
+static_assert(VLG_BUCKET_SORT == 0 || VLG_BUCKET_SORT == 1, "VLG_BUCKET_SORT: 0 or 1");
 constexpr uint32_t kBucketMaxOcc = 24;
 __device__ __forceinline__ uint32_t bin_at(uint32_t j) { return j + (j >> 5); }      // counters padded: thread t scans bins [t*k, t*k + k)
 
@@ -185,6 +186,7 @@ struct BucketSort {
             if (!kInlineFallback) return false;
         }
         if constexpr (kInlineFallback) radix(src, dst, len, bits, st.r);
+        else return false;                                                   // (VLG_BUCKET_SORT=0: the caller's radix pass sorts it)
         return true;
     }
 };
@@ -379,6 +381,9 @@ __global__ void __launch_bounds__(256) list_sort_scatter_kernel(const uint32_t* 
 #ifndef VLG_WINDOW_ITEMS
 #define VLG_WINDOW_ITEMS 12
 #endif
+static_assert(VLG_WINDOW_SORT == 0 || VLG_WINDOW_SORT == 1, "VLG_WINDOW_SORT: 0 or 1");
+static_assert(VLG_WINDOW_RANK_LOOP == 0 || VLG_WINDOW_RANK_LOOP == 1, "VLG_WINDOW_RANK_LOOP: 0 or 1");
+static_assert(VLG_WINDOWS_PER_TILE >= 1, "VLG_WINDOWS_PER_TILE: at least one window per tile");
 constexpr uint32_t kWinPerTile = VLG_WINDOWS_PER_TILE, kWinSpan = kSortTile / kWinPerTile;       // a window: kWinSpan keys before its borders move
 constexpr uint32_t kWinThreads = VLG_WINDOW_THREADS, kWinItems = VLG_WINDOW_ITEMS, kWinCap = kWinThreads * kWinItems, kWinReach = kWinCap - kWinSpan;
 static_assert(kWinCap > kWinSpan && kSortTile % kWinPerTile == 0, "a window holds its span and the group it reaches back for");

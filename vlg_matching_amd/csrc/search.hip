@@ -441,6 +441,7 @@ namespace {
 #ifndef VLG_FETCH_THREADS
 #define VLG_FETCH_THREADS 16
 #endif
+static_assert(VLG_FETCH_THREADS >= 1, "VLG_FETCH_THREADS: at least one copy thread");
 constexpr uint32_t kFetchThreads = VLG_FETCH_THREADS;
 constexpr uint64_t kFetchBlock = 8ull << 20;                 // bytes per staging block
 struct FetchLane { void* blk[2] = {nullptr, nullptr}; hipStream_t st = nullptr; hipEvent_t ev[2] = {nullptr, nullptr}; int device = -1; };
@@ -2295,3 +2296,27 @@ extern "C" vlg_status vlg_join_batch(const uint64_t* d_lists, const uint64_t* h_
 
 #include "wtsa.hpp"
 #include "int_index.hpp"
+
+// ---- the build-time constants this library was compiled with (include/vlg_hip.h) -------------------------------------------------
+extern "C" vlg_status vlg_build_constants(vlg_build_constant* out, uint32_t cap, uint32_t* n)
+{
+    if (!n) return fail(VLG_E_INVALID, "null argument");
+    const vlg::KernelConstants kc = vlg::kernel_constants();
+    const struct { const char* name; int64_t value; } all[] = {
+        {"VLG_LINK_RUN", VLG_LINK_RUN}, {"VLG_COOP_WINDOWS2", VLG_COOP_WINDOWS2}, {"VLG_RUNG_SHIFT", VLG_RUNG_SHIFT},
+        {"VLG_RESOLVE_HOPS", kc.resolve_hops}, {"VLG_RESOLVE_CHUNK", kc.resolve_chunk}, {"VLG_GROUP_CHUNK", kc.group_chunk},
+        {"VLG_STAGE_LISTS", kc.stage_lists}, {"VLG_SWEEP_PAIRS", kc.sweep_pairs},
+        {"VLG_PIVOT_GROUPS", VLG_PIVOT_GROUPS}, {"VLG_PIVOT_TURNS", VLG_PIVOT_TURNS}, {"VLG_COMPACT_RUNS", VLG_COMPACT_RUNS},
+        {"VLG_SPARSE_TURN", VLG_SPARSE_TURN}, {"VLG_SORT_CLASSES", VLG_SORT_CLASSES}, {"VLG_BUCKET_SORT", VLG_BUCKET_SORT},
+        {"VLG_WINDOW_SORT", VLG_WINDOW_SORT}, {"VLG_WINDOWS_PER_TILE", VLG_WINDOWS_PER_TILE}, {"VLG_WINDOW_RANK_LOOP", VLG_WINDOW_RANK_LOOP},
+        {"VLG_WINDOW_THREADS", VLG_WINDOW_THREADS}, {"VLG_WINDOW_ITEMS", VLG_WINDOW_ITEMS}, {"VLG_FETCH_THREADS", VLG_FETCH_THREADS},
+    };
+    const uint32_t count = (uint32_t)(sizeof(all) / sizeof(all[0]));
+    *n = count;
+    for (uint32_t i = 0; i < count && i < cap && out; ++i) {
+        memset(out[i].name, 0, sizeof(out[i].name));
+        strncpy(out[i].name, all[i].name, sizeof(out[i].name) - 1);
+        out[i].value = all[i].value;
+    }
+    return VLG_OK;
+}
