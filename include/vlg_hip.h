@@ -145,7 +145,13 @@ vlg_status vlg_index_compress(const vlg_index* src, int bv_kind, vlg_index** out
  * (csa_wt<wt_huff<>, 1, .>: 4 B per text character up to 4 GiB of text, 8 B beyond): csa[i] is one read (csa_wt.hpp:335-348 with
  * zero LF steps), vlg_search_batch's locate stage becomes a coalesced copy of the SA intervals and keeps no trail table;
  * for a text-order index vlg_index_export_parts' sa_samples receives the condensed values SA / d, vlg_index_export_marked the
- * marks (bit i = h_words[i >> 6] >> (i & 63), ceil(n / 64) words). */
+ * marks (bit i = h_words[i >> 6] >> (i & 63), ceil(n / 64) words).
+ * An integer-alphabet index (vlg_index_build_int, plain or compressed) is resampled under the same rules and statuses --
+ * csa_wt<wt_int<>, d, ., text_order_sa_sampling<>, ., int_alphabet<>> (test/csa_int_test.cpp:34), or SA order at another density; its
+ * samples stay 4 bytes wide, its suffix array is expanded on the device by LF walks on the wavelet matrix, and at SA order d = 1 its
+ * locate stage is the same copy of SA intervals whatever the alphabet size.  A text-order integer index is not compressed
+ * (VLG_E_INVALID: compress first, then resample); vlg_index_export_marked gives its marks, vlg_index_info reports its sampling.
+ * vlg_index_export_marked refuses an SA-order index of either alphabet (VLG_E_INVALID). */
 #define VLG_SAMPLING_SA_ORDER 0
 #define VLG_SAMPLING_TEXT_ORDER 1
 vlg_status vlg_index_resample(const vlg_index* src, int sampling, uint32_t sa_sample_dens, vlg_index** out);
@@ -158,7 +164,9 @@ vlg_status vlg_index_get_info(const vlg_index* idx, vlg_index_info* info);
  * symbols: one super-block read per level), LF / csa[i] / backward_search as for bytes.  h_text: n_symbols uint32_t, none of them 0
  * (VLG_E_ZERO_BYTE: construct.hpp:36-45); n_symbols < 2^32 / 5.  The handle is a vlg_index: vlg_search_batch (with a batch parsed
  * by vlg_queries_parse_int), vlg_queries_intervals / _occurrences, vlg_backward_search_batch (patterns = little-endian uint32_t
- * symbols), vlg_sa_batch, vlg_locate_batch, blob export / attach / broadcast take it; the byte-only entry points refuse it. */
+ * symbols), vlg_sa_batch, vlg_locate_batch, blob export / attach / broadcast take it; the byte-only entry points refuse it.
+ * vlg_index_compress (rrr-63 levels), vlg_index_resample (text-order sampling, other densities, the resident suffix array at d = 1),
+ * vlg_index_export_marked and vlg_index_isa_samples take it too, under the byte index's rules. */
 vlg_status vlg_index_build_int(const uint32_t* h_text, uint64_t n_symbols, uint32_t sa_sample_dens, vlg_index** out);
 /* 64-bit symbols.  gapped_pattern_query<int_alphabet_tag> reads uint64_t tokens (vlg_index.hpp:57-69) and int_vector<64> texts hold
  * 64-bit symbols; the device indexes (vlg_index_build_int, vlg_wtsa_build_int) hold uint32_t.  A symbol map carries the sorted
@@ -183,7 +191,8 @@ void vlg_index_destroy(vlg_index* idx);
  * receives n_text + 1 entries, d_sa[0] = n_text.  The same prefix-doubling sorter the index builder uses; n_text < 2^32 - 1. */
 vlg_status vlg_suffix_array_device(const uint8_t* d_text, uint64_t n_text, uint32_t* d_sa, void* stream);
 /* ISA samples as csa_wt keeps them (include/sdsl/csa_sampling_strategy.hpp:626-642): h_out[j] = the SA index i with SA[i] = j * inv_dens,
- * count = (n-1)/inv_dens + 1.  Computed from the index alone by walking LF from every SA sample. */
+ * count = (n-1)/inv_dens + 1.  Computed from the index alone by walking LF from every SA sample: the byte index on its wavelet tree, the
+ * integer-alphabet index (plain or rrr) on its wavelet matrix.  The index must be SA-order sampled (a text-order one: VLG_E_UNSUPPORTED). */
 vlg_status vlg_index_isa_samples(const vlg_index* idx, uint32_t inv_dens, uint64_t* h_out, uint64_t count);
 /* Store the index in the reference's on-disk format of csa_wt<wt_huff<>,32,64> (csa_wt.hpp:374-393) so that stock sdsl
  * can load_from_file() it: wavelet tree with rank_support_v and both select_support_mcl, SA samples, ISA samples (density

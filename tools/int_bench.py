@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """f-4 on the clock: (1) a word-level integer text through the integer-alphabet FM-index (vlg_index_build_int: wavelet
-matrix, one lane per occurrence in locate), (2) BASELINE config 3's batch on a text_order_sa_sampling index (vlg_index_resample).
+matrix, one lane per occurrence in locate), (1b) the same batch on the integer index resampled to text order d = 32 and to SA order d = 1
+(vlg_index_resample), (2) BASELINE config 3's batch on a text_order_sa_sampling index (vlg_index_resample).
 Prints one JSON line per part; development / profiling tool, not the metric.
 
     python tools/int_bench.py [n_tokens_log2=27] [steps=3]"""
@@ -70,6 +71,26 @@ def main():
                         "words (seed 3), %d queries x k=%d, m=%d tokens, gap .{%d,%d}? tokens" % (lg, nq, k, m, gap[0], gap[1]),
                 "index": idx.info(), "index_build_s": t_build})
     print(json.dumps(out), flush=True)
+    # ---- (1b) the same batch on two indexes vlg_index_resample makes from it: text order d = 32, and the resident suffix array (SA order,
+    # d = 1); each line carries the SA-order d = 32 time of the same run, and its checksum must be the SA-order index's ----------------------
+    for text_order, dens, what in ((True, 32, "csa_wt<wt_int<>, 32, ., text_order_sa_sampling<>, ., int_alphabet<>>"),
+                                   (False, 1, "csa_wt<wt_int<>, 1, ., sa_order_sa_sampling<>, ., int_alphabet<>> (the suffix array resident in HBM)")):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        rs = idx.resample(text_order=text_order, dens=dens)
+        torch.cuda.synchronize()
+        t_rs = time.perf_counter() - t0
+        a = timed(idx, q, ws, steps)
+        b = timed(rs, q, ws, steps)
+        if (b["checksum"], b["matches_per_step"], b["located_occ_per_step"]) != (a["checksum"], a["matches_per_step"], a["located_occ_per_step"]):
+            raise SystemExit("resampled integer index (text_order=%s, dens=%d): results differ from the SA-order index" % (text_order, dens))
+        b.update({"what": "the word-level batch of the line above on %s, made by vlg_index_resample: same matches and checksum as the SA-order "
+                          "d = 32 index" % what, "resample_s": t_rs, "hbm_bytes": rs.info()["hbm_bytes"], "index": rs.info(),
+                  "sa_order_ms_per_step_same_run": a["ms_per_step"], "sa_order_checksum": a["checksum"],
+                  "sa_order_kernels_ms_per_step_same_run": a["kernels_ms_per_step"]})
+        print(json.dumps(b), flush=True)
+        del rs
+        torch.cuda.empty_cache()
     del idx, q, ws, text
     torch.cuda.empty_cache()
     # ---- (2) C3 on text-order sampling ---------------------------------------------------------------------------------------------------

@@ -98,21 +98,27 @@ struct IntHeader {
     // rrr-63 levels (vlg_index_compress of an integer index; all zero in a plain one -- the header is followed by zeros up to 256 bytes,
     // so blobs written before these fields existed read as plain): the layout of the byte index's rrr variant, one "node" per level
     uint64_t bv_kind, n_sb /* super-blocks of 32 x 63 bits per level */, rrr_words, off_rrr_hdr, off_rrr_stream, off_binom;
+    // SA sampling (vlg_index_resample of an integer index; zero in blobs written before these fields existed: SA order): kSamplingSaOrder
+    // keeps SA[0], SA[dens], ...; kSamplingTextOrder keeps SA[i] / dens of the marked i (SA[i] % dens == 0) in ascending i, and the marks
+    // at off_marked as the byte index keeps them (n / 224 + 1 super-blocks {224 marks, ones before} over the SA indices)
+    uint64_t sampling, off_marked;
 };
+static_assert(sizeof(IntHeader) <= 256, "the integer header is zero-padded to 256 bytes");
 struct IntView {
     const Block* blocks;                              // plain: [n_levels][nb] wavelet matrix of the BWT over compact symbols
     const uint4* rrr_hdr;                             // rrr-63: [n_levels][n_sb] headers, the offset stream and the block code's tables
     const uint64_t* rrr_stream;                       //         (the members the bit-vector policies of device_rank.hpp read)
     const struct RrrTables* rrr_tables;
     uint64_t stride;                                  // super-blocks per level: nb (plain) or n_sb (rrr)
-    uint32_t bv_kind, pad_;
+    uint32_t bv_kind, sampling;                       // kBvPlain / kBvRrr63; kSamplingSaOrder / kSamplingTextOrder
     const uint64_t* Z;                                // zeros per level
     const uint64_t* D;                                // C[c] - first position of c in the last arrangement
     const uint64_t* C;                                // [sigma + 1]
     const uint32_t* comp2char;                        // [sigma] ascending
-    const uint32_t* samples;                          // SA[0], SA[dens], ...
+    const uint32_t* samples;                          // SA[0], SA[dens], ... (SA order) or SA[i] / dens of the marked i (text order)
     uint64_t n, nb, sigma, n_samples;
     uint32_t n_levels, dens;
+    const Block* marked;                              // text order: the marks over the SA indices (null in SA order)
 };
 
 constexpr uint32_t kBvPlain = 0, kBvRrr63 = 1;

@@ -204,6 +204,9 @@ struct TextOrderSampling {
     const sample_t* samples;
     __device__ __forceinline__ explicit TextOrderSampling(const IndexView& iv)
         : dens(iv.dens), marked(iv.marked), samples(reinterpret_cast<const sample_t*>(iv.samples)) {}
+    // the integer index's (int_index.hpp: the same marks and condensed samples, 4-byte values)
+    __device__ __forceinline__ explicit TextOrderSampling(const IntView& iv)
+        : dens(iv.dens), marked(iv.marked), samples(reinterpret_cast<const sample_t*>(iv.samples)) {}
     __device__ __forceinline__ bool probe(uint64_t i, uint64_t& value) const
     {
         uint32_t blk, off;

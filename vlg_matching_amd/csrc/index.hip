@@ -7,6 +7,7 @@
 #include "common.hpp"
 #include <functional>
 #include "device_rank.hpp"
+#include "kernels.hpp"
 #include "rrr_code.hpp"
 #include <rocprim/rocprim.hpp>
 
@@ -653,6 +654,7 @@ vlg_status compress_int(const vlg_index* src, vlg_index** out)
 {
     const IntHeader& sh = src->ihdr;
     if (sh.bv_kind != kBvPlain) return fail(VLG_E_INVALID, "source index must use plain bit-vectors");
+    if (sh.sampling != kSamplingSaOrder) return fail(VLG_E_INVALID, "compress the SA-order index first, then resample it (vlg_index_resample)");
     IntHeader h = sh;
     h.bv_kind = kBvRrr63;
     h.n_sb = sh.n / kRrrSuperBits + 1;
@@ -900,6 +902,65 @@ vlg_status resample_run(const vlg_index* src, int sampling, uint32_t dens, vlg_i
     bind_view(idx);
     return VLG_OK;
 }
+
+// The integer index (int_index.hpp): the suffix array from the SA-order samples by LF walks on the wavelet matrix (int_sa_expand_kernel),
+// then the samples -- and the marks -- of the new strategy by the kernels above.  Everything in front of the samples (levels or rrr
+// streams, Z, D, C, comp2char) has the same size and place in both images and is copied as it is.
+vlg_status resample_int(const vlg_index* src, int sampling, uint32_t dens, vlg_index** out)
+{
+    const IntHeader& sh = src->ihdr;
+    if (sh.sampling != kSamplingSaOrder) return fail(VLG_E_INVALID, "the source index must be sampled in SA order");
+    hipStream_t stream = nullptr;
+    const uint64_t n = sh.n;
+    IntHeader h = sh;
+    h.dens = dens;
+    h.sampling = (uint64_t)sampling;
+    h.n_samples = (n + dens - 1) / dens;
+    layout_int_blob(h);
+    if (h.off_samples != sh.off_samples) return fail(VLG_E_INTERNAL, "integer index: sections in front of the samples moved");
+    DevBuf d_sa, d_pops, d_tmp;
+    VLG_HIP_TRY(d_sa.alloc(n * 4));
+    if (vlg_status s = launch_int_sa_expand(src->iview, d_sa.as<uint32_t>(), stream)) return s;
+    void* d_blob = nullptr;
+    auto run = [&]() -> vlg_status {
+        VLG_HIP_TRY(hipMalloc(&d_blob, h.total_bytes));
+        uint8_t* b = reinterpret_cast<uint8_t*>(d_blob);
+        const uint8_t* sb = reinterpret_cast<const uint8_t*>(src->d_blob);
+        VLG_HIP_TRY(hipMemsetAsync(b, 0, h.off_levels, stream));
+        VLG_HIP_TRY(hipMemcpyAsync(b, &h, sizeof h, hipMemcpyHostToDevice, stream));
+        VLG_HIP_TRY(hipMemcpyAsync(b + h.off_levels, sb + sh.off_levels, sh.off_samples - sh.off_levels, hipMemcpyDeviceToDevice, stream));
+        uint32_t* samples = reinterpret_cast<uint32_t*>(b + h.off_samples);
+        if (sampling == VLG_SAMPLING_SA_ORDER) {
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(sa_order_samples_kernel<uint32_t>), dim3((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((h.n_samples + 255) / 256, 8192))),
+                               dim3(256), 0, stream, d_sa.as<uint32_t>(), h.n_samples, dens, samples);
+        } else {
+            const uint64_t nb = n / kBlockBits + 1;
+            Block* mk = reinterpret_cast<Block*>(b + h.off_marked);
+            VLG_HIP_TRY(d_pops.alloc((nb + 1) * 4));
+            const dim3 gb((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((nb + 255) / 256, 8192)));
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(marked_pack_kernel<uint32_t>), gb, dim3(256), 0, stream, d_sa.as<uint32_t>(), n, dens, mk, nb, d_pops.as<uint32_t>());
+            size_t tb = 0;
+            VLG_HIP_TRY(rocprim::exclusive_scan(nullptr, tb, d_pops.as<uint32_t>(), d_pops.as<uint32_t>(), 0u, nb, rocprim::plus<uint32_t>(), stream));
+            VLG_HIP_TRY(d_tmp.alloc(tb + 16));
+            VLG_HIP_TRY(rocprim::exclusive_scan(d_tmp.p, tb, d_pops.as<uint32_t>(), d_pops.as<uint32_t>(), 0u, nb, rocprim::plus<uint32_t>(), stream));
+            hipLaunchKernelGGL(marked_counts_kernel, gb, dim3(256), 0, stream, mk, d_pops.as<uint32_t>(), nb);
+            VLG_HIP_TRY(hipMemsetAsync(samples, 0, h.n_samples * 4, stream));
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(text_order_samples_kernel<uint32_t>), dim3((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, 16384))), dim3(256), 0,
+                               stream, d_sa.as<uint32_t>(), n, dens, mk, samples);
+        }
+        VLG_HIP_TRY(hipGetLastError());
+        VLG_HIP_TRY(hipStreamSynchronize(stream));
+        return VLG_OK;
+    };
+    vlg_status st = run();
+    if (st) { if (d_blob) (void)hipFree(d_blob); return st; }
+    vlg_index* idx = new vlg_index();
+    st = attach_int_blob(d_blob, h.total_bytes, idx);
+    if (st) { (void)hipFree(d_blob); delete idx; return st; }
+    idx->owns_blob = true;
+    *out = idx;
+    return VLG_OK;
+}
 }  // namespace
 
 extern "C" vlg_status vlg_index_resample(const vlg_index* src, int sampling, uint32_t dens, vlg_index** out)
@@ -909,8 +970,8 @@ extern "C" vlg_status vlg_index_resample(const vlg_index* src, int sampling, uin
     *out = nullptr;
     if (sampling != VLG_SAMPLING_SA_ORDER && sampling != VLG_SAMPLING_TEXT_ORDER) return fail(VLG_E_INVALID, "unknown sampling strategy");
     if (!dens) dens = 32;
-    if (src->is_int) return fail(VLG_E_UNSUPPORTED, "resampling is built for byte-alphabet indexes");
     if (src->hdr.sampling != kSamplingSaOrder) return fail(VLG_E_INVALID, "the source index must be sampled in SA order");
+    if (src->is_int) return resample_int(src, sampling, dens, out);
     if (src->hdr.sample_bytes != 4 && src->hdr.sample_bytes != 8) return fail(VLG_E_INTERNAL, "unknown sample width");
     vlg_index* idx = new vlg_index();
     idx->tree = src->tree;
@@ -929,7 +990,8 @@ extern "C" vlg_status vlg_index_export_marked(const vlg_index* idx, uint64_t* h_
     const uint64_t n = idx->hdr.n, nw = (n + 63) / 64;
     DevBuf d;
     VLG_HIP_TRY(d.alloc(nw * 8));
-    hipLaunchKernelGGL(marked_words_kernel, dim3((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((nw + 255) / 256, 8192))), dim3(256), 0, nullptr, idx->view.marked, n,
+    hipLaunchKernelGGL(marked_words_kernel, dim3((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((nw + 255) / 256, 8192))), dim3(256), 0, nullptr,
+                       idx->is_int ? idx->iview.marked : idx->view.marked, n,
                        d.as<uint64_t>(), nw);
     VLG_HIP_TRY(hipGetLastError());
     VLG_HIP_TRY(hipMemcpy(h_words, d.p, nw * 8, hipMemcpyDeviceToHost));

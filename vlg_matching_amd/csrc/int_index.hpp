@@ -16,6 +16,8 @@
 //   Z       levels words; D[c] = C[c] - (first position of symbol c in the last arrangement), so that
 //           C[c] + rank_c(i) = D[c] + walk(i, c)  and  LF(i) = D[c] + walk(i) with c read off the bits on the way;
 //   C       sigma + 1 words; comp2char: sigma symbols ascending (queries are mapped by binary search); samples: SA[0], SA[d], ...
+//   marked  (text_order_sa_sampling only, made by vlg_index_resample: csa_sampling_strategy.hpp:127-246) the byte index's marks over the
+//           SA indices; samples are then SA[i] / d of the marked i in ascending i
 // Limits: symbols are uint32_t, none of them 0 (construct() refuses a 0 symbol: include/sdsl/construct.hpp:36-45); n <= 2^32 / 5
 // (the suffix sorter sees five bytes per symbol).
 #pragma once
@@ -27,7 +29,7 @@ void bind_int_view(vlg_index* idx)
     const uint8_t* b = reinterpret_cast<const uint8_t*>(idx->d_blob);
     const IntHeader& h = idx->ihdr;
     IntView& v = idx->iview;
-    v.bv_kind = (uint32_t)h.bv_kind; v.pad_ = 0;
+    v.bv_kind = (uint32_t)h.bv_kind; v.sampling = (uint32_t)h.sampling;
     v.blocks = h.bv_kind == kBvPlain ? reinterpret_cast<const Block*>(b + h.off_levels) : nullptr;
     v.rrr_hdr = h.bv_kind == kBvRrr63 ? reinterpret_cast<const uint4*>(b + h.off_rrr_hdr) : nullptr;
     v.rrr_stream = h.bv_kind == kBvRrr63 ? reinterpret_cast<const uint64_t*>(b + h.off_rrr_stream) : nullptr;
@@ -39,6 +41,7 @@ void bind_int_view(vlg_index* idx)
     v.comp2char = reinterpret_cast<const uint32_t*>(b + h.off_c2c);
     v.samples = reinterpret_cast<const uint32_t*>(b + h.off_samples);
     v.n = h.n; v.nb = h.nb; v.sigma = h.sigma; v.n_samples = h.n_samples; v.n_levels = h.levels; v.dens = h.dens;
+    v.marked = h.sampling == kSamplingTextOrder ? reinterpret_cast<const Block*>(b + h.off_marked) : nullptr;
     // what the generic entry points read from the byte header
     BlobHeader& g = idx->hdr;
     memset(&g, 0, sizeof g);
@@ -46,6 +49,7 @@ void bind_int_view(vlg_index* idx)
     g.dens = h.dens; g.n_samples = h.n_samples; g.sample_bytes = 4; g.bv_kind = h.bv_kind == kBvRrr63 ? VLG_BV_INT_MATRIX_RRR63 : VLG_BV_INT_MATRIX;
     g.n_blocks = (h.bv_kind == kBvRrr63 ? h.n_sb : h.nb) * h.levels; g.n_rrr_sb = h.n_sb * h.levels; g.rrr_stream_words = h.rrr_words;
     g.max_code_len = h.levels; g.wt_bits = h.n * h.levels;
+    g.sampling = (uint32_t)h.sampling; g.off_marked = h.off_marked;
     idx->is_int = true;
 }
 
@@ -119,13 +123,30 @@ __global__ void __launch_bounds__(256) int_backward_search_kernel(IntView v, con
     }
 }
 
+// SA sampling policies of the locate kernels: is SA index i sampled, and if so what is SA[i].  SA order (csa_sampling_strategy.hpp:102-111)
+// is the arithmetic these kernels always had; text order is the byte index's TextOrderSampling on the IntView (device_rank.hpp: the mark
+// and the rank that addresses the sample come out of one 32-byte read).
+struct IntSaOrderSampling {
+    uint32_t dens;
+    const uint32_t* samples;
+    __device__ __forceinline__ explicit IntSaOrderSampling(const IntView& v) : dens(v.dens), samples(v.samples) {}
+    __device__ __forceinline__ bool probe(uint64_t i, uint64_t& value) const
+    {
+        if (i % dens) return false;
+        value = samples[i / dens];
+        return true;
+    }
+};
+using IntTextOrderSampling = TextOrderSampling<uint32_t>;
+
 // csa[i] (csa_wt.hpp:335-348) for the SA indices in io[], in place; the lanes of a wave refill from the wave's slice like K3's
-template <class BV>
+template <class BV, class Sampling>
 __global__ void __launch_bounds__(256) int_locate_kernel(IntView v, uint32_t* __restrict__ io, uint64_t total, uint32_t per_wave,
                                                          unsigned long long* __restrict__ stats)
 {
     __shared__ IntLds<BV> sZ;
     stage_int(sZ, v);
+    const Sampling sampling(v);
     const uint32_t lane = threadIdx.x & 63;
     const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     uint64_t next = wave * per_wave;
@@ -147,8 +168,9 @@ __global__ void __launch_bounds__(256) int_locate_kernel(IntView v, uint32_t* __
         }
         if (!__any(active)) break;
         if (active) {
-            if (lvl == 0 && i % v.dens == 0) {                       // csa_sampling_strategy.hpp:102-111
-                uint64_t r = (uint64_t)v.samples[i / v.dens] + off;
+            uint64_t sv;
+            if (lvl == 0 && sampling.probe(i, sv)) {                 // csa_sampling_strategy.hpp:102-111 / :185-194
+                uint64_t r = sv + off;
                 if (r >= v.n) r -= v.n;
                 io[t] = (uint32_t)r;
                 need = true;
@@ -199,15 +221,16 @@ __device__ __forceinline__ void int_counters_add(unsigned long long a, unsigned 
     if ((threadIdx.x & 63) == 0) { if (a) atomicAdd(&stats[0], a); if (b) atomicAdd(&stats[1], b); if (c && n_done) atomicAdd(n_done, c); }
 }
 
-template <class BV, bool kTrail, bool kFirst, bool kAhead>
-__device__ __forceinline__ void int_sweep_element(const IntView& v, const IntLds<BV>& sZ, uint64_t e, uint64_t v64, uint64_t* __restrict__ val,
+template <class BV, class Sampling, bool kTrail, bool kFirst, bool kAhead>
+__device__ __forceinline__ void int_sweep_element(const IntView& v, const IntLds<BV>& sZ, const Sampling& sampling, uint64_t e, uint64_t v64, uint64_t* __restrict__ val,
                                                   uint16_t* __restrict__ key, uint32_t step, uint32_t* __restrict__ out, const Block* __restrict__ member,
                                                   uint64_t* __restrict__ rec, uint64_t slot0, bool probed, uint32_t& n_lv, uint32_t& n_lf, uint32_t& n_fin)
 {
     const uint64_t i = v64 & 0xFFFFFFFFull, slot = v64 >> 32;
     uint32_t owner = 0;
-    if (i % v.dens == 0) {                                           // csa_sampling_strategy.hpp:102-111
-        uint64_t r = (uint64_t)v.samples[i / v.dens] + step;
+    uint64_t sv;
+    if (sampling.probe(i, sv)) {                                     // csa_sampling_strategy.hpp:102-111 / :185-194
+        uint64_t r = sv + step;
         if (r >= v.n) r -= v.n;                                      // csa_wt.hpp:343-347
         if (kTrail) rec[slot0 + slot] = r; else out[slot] = (uint32_t)r;
         key[e] = (uint16_t)v.sigma;
@@ -238,20 +261,21 @@ __device__ __forceinline__ void int_sweep_element(const IntView& v, const IntLds
     }
 }
 
-template <class BV, bool kTrail>
+template <class BV, class Sampling, bool kTrail>
 __global__ void __launch_bounds__(256) int_sweep_step_kernel(IntView v, uint64_t* __restrict__ val, uint16_t* __restrict__ key, uint64_t count, uint32_t step,
                                                              uint32_t* __restrict__ out, unsigned long long* __restrict__ stats, unsigned long long* __restrict__ n_done,
                                                              const Block* __restrict__ member, uint64_t* __restrict__ rec, uint64_t slot0, bool probed)
 {
     __shared__ IntLds<BV> sZ;
     stage_int(sZ, v);
+    const Sampling sampling(v);
     uint32_t n_lv = 0, n_lf = 0, n_fin = 0;
     for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < count; e += (uint64_t)gridDim.x * blockDim.x)
-        int_sweep_element<BV, kTrail, false, false>(v, sZ, e, val[e], val, key, step, out, member, rec, slot0, probed, n_lv, n_lf, n_fin);
+        int_sweep_element<BV, Sampling, kTrail, false, false>(v, sZ, sampling, e, val[e], val, key, step, out, member, rec, slot0, probed, n_lv, n_lf, n_fin);
     int_counters_add(n_lf, n_lv, n_fin, stats, n_done);
 }
 
-template <class BV, bool kTrail, bool kAhead>
+template <class BV, class Sampling, bool kTrail, bool kAhead>
 __global__ void __launch_bounds__(256) int_sweep_first_kernel(IntView v, const uint64_t* __restrict__ l, const uint64_t* __restrict__ out_off, uint64_t n_pat, uint64_t t0,
                                                               uint64_t total, uint64_t* __restrict__ val, uint16_t* __restrict__ key, uint32_t* __restrict__ out,
                                                               unsigned long long* __restrict__ stats, unsigned long long* __restrict__ n_done,
@@ -261,6 +285,7 @@ __global__ void __launch_bounds__(256) int_sweep_first_kernel(IntView v, const u
     constexpr uint32_t kPer = kSweepChunk / 256;
     __shared__ IntLds<BV> sZ;
     stage_int(sZ, v);
+    const Sampling sampling(v);
     uint32_t n_lv = 0, n_lf = 0, n_fin = 0;
     for (uint64_t base = t0 + (uint64_t)blockIdx.x * kSweepChunk; base < total; base += (uint64_t)gridDim.x * kSweepChunk) {
         uint64_t p = chunk_list[(base - t0) / kSweepChunk];         // the list of the chunk's first element (sweep_chunk_lists_kernel)
@@ -270,7 +295,7 @@ __global__ void __launch_bounds__(256) int_sweep_first_kernel(IntView v, const u
             if (t < total) {
                 while (out_off[p + 1] <= t) ++p;
                 const uint64_t v64 = ((t - t0) << 32) | (l[p] + (t - out_off[p]));
-                int_sweep_element<BV, kTrail, true, kAhead>(v, sZ, t - t0, v64, val, key, 0u, out, member, rec, t0, false, n_lv, n_lf, n_fin);
+                int_sweep_element<BV, Sampling, kTrail, true, kAhead>(v, sZ, sampling, t - t0, v64, val, key, 0u, out, member, rec, t0, false, n_lv, n_lf, n_fin);
             }
         }
     }
@@ -278,13 +303,14 @@ __global__ void __launch_bounds__(256) int_sweep_first_kernel(IntView v, const u
 }
 
 // the stragglers: int_locate_kernel's refilling lanes on the elements val[] = slot << 32 | SA index that have walked `step` steps
-template <class BV>
+template <class BV, class Sampling>
 __global__ void __launch_bounds__(256) int_sweep_tail_kernel(IntView v, uint32_t* __restrict__ out, uint64_t total, uint32_t per_wave, unsigned long long* __restrict__ stats,
                                                              const uint64_t* __restrict__ val, uint32_t step, uint64_t* __restrict__ rec, uint64_t slot0,
                                                              const Block* __restrict__ member)
 {
     __shared__ IntLds<BV> sZ;
     stage_int(sZ, v);
+    const Sampling sampling(v);
     const uint32_t lane = threadIdx.x & 63;
     const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     uint64_t next = wave * per_wave;
@@ -307,8 +333,9 @@ __global__ void __launch_bounds__(256) int_sweep_tail_kernel(IntView v, uint32_t
         if (!__any(active)) break;
         if (active) {
             uint32_t owner = 0;
-            if (i % v.dens == 0) {
-                uint64_t r = (uint64_t)v.samples[i / v.dens] + off;
+            uint64_t sv = 0;
+            if (sampling.probe(i, sv)) {
+                uint64_t r = sv + off;
                 if (r >= v.n) r -= v.n;
                 if (rec) rec[slot0 + t] = r; else out[t] = (uint32_t)r;
                 need = true;
@@ -418,7 +445,45 @@ inline void layout_int(IntHeader& h)
     h.off_C = off;       off = align_up(off + (h.sigma + 1) * 8, 256);
     h.off_c2c = off;     off = align_up(off + h.sigma * 4, 256);
     h.off_samples = off; off = align_up(off + h.n_samples * 4, 256);
+    h.off_marked = 0;
+    if (h.sampling == kSamplingTextOrder) { h.off_marked = off; off = align_up(off + (h.n / kBlockBits + 1) * sizeof(Block), 256); }
     h.total_bytes = off;
+}
+
+// ---- resampling and ISA samples (vlg_index_resample in index.hip, vlg_index_isa_samples in kernels.hip) --------------------------------
+// every SA value from the SA-order samples: a lane starts at one sample (j * d, SA[j * d]) and walks LF on the matrix -- (LF(i), SA[i] - 1)
+// -- up to the next sampled index, so that every SA index is visited exactly once with its value (index.hip: sa_expand_kernel on the tree).
+// (a walk is at most n steps long: a damaged image ends the loop instead of spinning)
+template <class BV, class Visit>
+__device__ __forceinline__ void int_walk_from_samples(const IntView& v, const IntLds<BV>& sZ, const Visit& visit)
+{
+    uint32_t n_lv = 0;
+    for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < v.n_samples; j += (uint64_t)gridDim.x * blockDim.x) {
+        uint64_t i = j * v.dens, x = v.samples[j];
+        for (uint64_t k = 0; k < v.n && i < v.n; ++k) {
+            visit(i, x);
+            uint32_t c;
+            i = v.n_levels ? int_lf(v, sZ, i, c, n_lv) : 0;
+            x = x ? x - 1 : v.n - 1;
+            if (i % v.dens == 0) break;
+        }
+    }
+}
+// sa[i] = SA[i] for every i (the resampler's input)
+template <class BV>
+__global__ void __launch_bounds__(256) int_sa_expand_kernel(IntView v, uint32_t* __restrict__ sa)
+{
+    __shared__ IntLds<BV> sZ;
+    stage_int(sZ, v);
+    int_walk_from_samples(v, sZ, [&](uint64_t i, uint64_t x) { sa[i] = (uint32_t)x; });
+}
+// isa_sample[SA[i] / inv_dens] = i for every i with SA[i] % inv_dens == 0 (csa_sampling_strategy.hpp:626-642)
+template <class BV>
+__global__ void __launch_bounds__(256) int_isa_samples_kernel(IntView v, uint32_t inv_dens, uint64_t* __restrict__ out)
+{
+    __shared__ IntLds<BV> sZ;
+    stage_int(sZ, v);
+    int_walk_from_samples(v, sZ, [&](uint64_t i, uint64_t x) { if (x % inv_dens == 0) out[x / inv_dens] = i; });
 }
 
 }  // namespace
@@ -433,6 +498,9 @@ vlg_status attach_int_blob(const void* d_blob, uint64_t bytes, vlg_index* idx)
     const IntHeader& h = idx->ihdr;
     if (h.magic != kIntBlobMagic || h.total_bytes > bytes || h.levels > kMaxIntLevels || h.bv_kind > kBvRrr63)
         return fail(VLG_E_INVALID, "not a VLG integer-index blob");
+    if (h.sampling > kSamplingTextOrder || !h.dens || h.n_samples != (h.n + h.dens - 1) / h.dens ||
+        (h.sampling == kSamplingTextOrder && (h.off_marked < h.off_samples + h.n_samples * 4 || h.off_marked + (h.n / kBlockBits + 1) * sizeof(Block) > h.total_bytes)))
+        return fail(VLG_E_INVALID, "integer-index blob: inconsistent sampling fields");
     idx->d_blob = const_cast<void*>(d_blob);
     idx->owns_blob = false;
     bind_int_view(idx);
@@ -631,7 +699,7 @@ vlg_status launch_int_backward_search(const IntView& v, const uint8_t* d_blob, c
 }
 
 // the integer index in the sorted sweep (sigma <= 65534: the partition key is 16 bits wide)
-template <class BV>
+template <class BV, class Sampling>
 static vlg_status launch_int_locate_sweep_bv(const IntView& v, const uint64_t* d_l, const uint64_t* d_out_off, uint64_t n_pat, uint64_t total, uint32_t* d_out,
                                    uint64_t* val_a, uint64_t* val_b, uint16_t* key_a, uint16_t* key_b, void* temp, size_t temp_bytes, unsigned long long* d_counter,
                                    unsigned long long* d_stats, uint64_t tail_threshold, hipStream_t stream, LaunchTimer* timer, Block* member,
@@ -647,18 +715,18 @@ static vlg_status launch_int_locate_sweep_bv(const IntView& v, const uint64_t* d
         launch_sweep_chunk_lists(d_out_off, n_pat, t0, t1, chunk_list, stream);
         const dim3 g = grid_of((t1 - t0 + 7) / 8, 8192);
         uint32_t* o = static_cast<uint32_t*>(out);
-        if (mem && ahead) hipLaunchKernelGGL(HIP_KERNEL_NAME(int_sweep_first_kernel<BV, true, true>), g, dim3(256), 0, stream, v, d_l, d_out_off, n_pat, t0, t1, val, key, o, d_stats, counter, mem, rc, chunk_list);
-        else if (mem) hipLaunchKernelGGL(HIP_KERNEL_NAME(int_sweep_first_kernel<BV, true, false>), g, dim3(256), 0, stream, v, d_l, d_out_off, n_pat, t0, t1, val, key, o, d_stats, counter, mem, rc, chunk_list);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(int_sweep_first_kernel<BV, false, false>), g, dim3(256), 0, stream, v, d_l, d_out_off, n_pat, t0, t1, val, key, o, d_stats, counter, mem, rc, chunk_list);
+        if (mem && ahead) hipLaunchKernelGGL(HIP_KERNEL_NAME(int_sweep_first_kernel<BV, Sampling, true, true>), g, dim3(256), 0, stream, v, d_l, d_out_off, n_pat, t0, t1, val, key, o, d_stats, counter, mem, rc, chunk_list);
+        else if (mem) hipLaunchKernelGGL(HIP_KERNEL_NAME(int_sweep_first_kernel<BV, Sampling, true, false>), g, dim3(256), 0, stream, v, d_l, d_out_off, n_pat, t0, t1, val, key, o, d_stats, counter, mem, rc, chunk_list);
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(int_sweep_first_kernel<BV, Sampling, false, false>), g, dim3(256), 0, stream, v, d_l, d_out_off, n_pat, t0, t1, val, key, o, d_stats, counter, mem, rc, chunk_list);
     };
     K.step = [&](uint64_t* val, uint16_t* key, uint64_t alive, uint32_t step, void* out, unsigned long long* counter, const Block* mem, uint64_t* rc, uint64_t t0, bool probed) {
         const dim3 g = grid_of(alive, 4096);
         uint32_t* o = static_cast<uint32_t*>(out);
-        if (mem) hipLaunchKernelGGL(HIP_KERNEL_NAME(int_sweep_step_kernel<BV, true>), g, dim3(256), 0, stream, v, val, key, alive, step, o, d_stats, counter, mem, rc, t0, probed);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(int_sweep_step_kernel<BV, false>), g, dim3(256), 0, stream, v, val, key, alive, step, o, d_stats, counter, mem, rc, t0, probed);
+        if (mem) hipLaunchKernelGGL(HIP_KERNEL_NAME(int_sweep_step_kernel<BV, Sampling, true>), g, dim3(256), 0, stream, v, val, key, alive, step, o, d_stats, counter, mem, rc, t0, probed);
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(int_sweep_step_kernel<BV, Sampling, false>), g, dim3(256), 0, stream, v, val, key, alive, step, o, d_stats, counter, mem, rc, t0, probed);
     };
     K.tail = [&](void* out, uint64_t alive, uint32_t per_wave, const uint64_t* val, uint32_t step, uint64_t* rc, uint64_t t0, const Block* mem, uint32_t blocks) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(int_sweep_tail_kernel<BV>), dim3(blocks), dim3(256), 0, stream, v, static_cast<uint32_t*>(out), alive, per_wave, d_stats, val, step, rc, t0, mem);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(int_sweep_tail_kernel<BV, Sampling>), dim3(blocks), dim3(256), 0, stream, v, static_cast<uint32_t*>(out), alive, per_wave, d_stats, val, step, rc, t0, mem);
     };
     return run_locate_sweep<uint32_t, false>(K, d_l, d_out_off, n_pat, total, d_out, val_a, val_b, key_a, key_b, temp, temp_bytes, d_counter, tail_threshold, stream, timer,
                                              member, n_member_lists, rec, while_first_step);
@@ -669,11 +737,27 @@ vlg_status launch_int_locate_sweep(const IntView& v, const uint64_t* d_l, const 
                                    unsigned long long* d_stats, uint64_t tail_threshold, hipStream_t stream, LaunchTimer* timer, Block* member,
                                    uint32_t n_member_lists, uint64_t* rec, const std::function<vlg_status()>* while_first_step)
 {
-    return v.bv_kind == kBvRrr63
-               ? launch_int_locate_sweep_bv<RrrBV>(v, d_l, d_out_off, n_pat, total, d_out, val_a, val_b, key_a, key_b, temp, temp_bytes, d_counter, d_stats, tail_threshold,
-                                                   stream, timer, member, n_member_lists, rec, while_first_step)
-               : launch_int_locate_sweep_bv<PlainBV>(v, d_l, d_out_off, n_pat, total, d_out, val_a, val_b, key_a, key_b, temp, temp_bytes, d_counter, d_stats, tail_threshold,
-                                                     stream, timer, member, n_member_lists, rec, while_first_step);
+    if (v.dens == 1 && v.sampling == kSamplingSaOrder && total) {     // the resident suffix array: no walk, no trails, no records
+        if (timer) timer->begin(0);
+        const vlg_status s = launch_int_dense_copy(v, d_l, d_out_off, n_pat, total, d_out, stream);
+        if (timer) timer->end(0);
+        if (s) return s;
+        if (while_first_step) if (vlg_status hs = (*while_first_step)()) return hs;
+        return VLG_OK;
+    }
+#define VLG_INT_SWEEP(BV, S) launch_int_locate_sweep_bv<BV, S>(v, d_l, d_out_off, n_pat, total, d_out, val_a, val_b, key_a, key_b, temp, temp_bytes, d_counter, \
+                                                              d_stats, tail_threshold, stream, timer, member, n_member_lists, rec, while_first_step)
+    const bool rrr = v.bv_kind == kBvRrr63;
+    if (v.sampling == kSamplingTextOrder) return rrr ? VLG_INT_SWEEP(RrrBV, IntTextOrderSampling) : VLG_INT_SWEEP(PlainBV, IntTextOrderSampling);
+    return rrr ? VLG_INT_SWEEP(RrrBV, IntSaOrderSampling) : VLG_INT_SWEEP(PlainBV, IntSaOrderSampling);
+#undef VLG_INT_SWEEP
+}
+
+// SA-order density 1: the samples are the suffix array, and locate copies SA intervals (kernels.hip: sa_dense_copy_kernel)
+vlg_status launch_int_dense_copy(const IntView& v, const uint64_t* d_l, const uint64_t* d_out_off, uint64_t n_pat, uint64_t total, uint32_t* d_out, hipStream_t stream)
+{
+    if (v.dens != 1 || v.sampling != kSamplingSaOrder) return fail(VLG_E_INTERNAL, "integer index: the copy needs SA-order samples of density 1");
+    return launch_sa_dense_copy(v.samples, d_l, d_out_off, n_pat, total, d_out, stream);
 }
 
 vlg_status launch_int_locate(const IntView& v, uint32_t* d_io, uint64_t total, unsigned long long* d_stats, hipStream_t st)
@@ -683,10 +767,34 @@ vlg_status launch_int_locate(const IntView& v, uint32_t* d_io, uint64_t total, u
     uint64_t per_wave = (total + target_waves - 1) / target_waves;
     per_wave = std::min<uint64_t>(std::max<uint64_t>(per_wave, 64 * 16), 1u << 20);
     const uint64_t waves = (total + per_wave - 1) / per_wave;
-    if (v.bv_kind == kBvRrr63)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(int_locate_kernel<RrrBV>), dim3((uint32_t)((waves + 3) / 4)), dim3(256), 0, st, v, d_io, total, (uint32_t)per_wave, d_stats);
-    else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(int_locate_kernel<PlainBV>), dim3((uint32_t)((waves + 3) / 4)), dim3(256), 0, st, v, d_io, total, (uint32_t)per_wave, d_stats);
+    const dim3 grid((uint32_t)((waves + 3) / 4));
+#define VLG_INT_LOCATE(BV, S) hipLaunchKernelGGL(HIP_KERNEL_NAME(int_locate_kernel<BV, S>), grid, dim3(256), 0, st, v, d_io, total, (uint32_t)per_wave, d_stats)
+    const bool rrr = v.bv_kind == kBvRrr63;
+    if (v.sampling == kSamplingTextOrder) { if (rrr) VLG_INT_LOCATE(RrrBV, IntTextOrderSampling); else VLG_INT_LOCATE(PlainBV, IntTextOrderSampling); }
+    else { if (rrr) VLG_INT_LOCATE(RrrBV, IntSaOrderSampling); else VLG_INT_LOCATE(PlainBV, IntSaOrderSampling); }
+#undef VLG_INT_LOCATE
+    VLG_HIP_TRY(hipGetLastError());
+    return VLG_OK;
+}
+
+// every SA value of an SA-order integer index into d_sa (n words): the input of vlg_index_resample
+vlg_status launch_int_sa_expand(const IntView& v, uint32_t* d_sa, hipStream_t st)
+{
+    if (v.sampling != kSamplingSaOrder) return fail(VLG_E_INTERNAL, "integer index: expanding the suffix array needs SA-order samples");
+    const dim3 grid(grid_for(v.n_samples, 8192));
+    if (v.bv_kind == kBvRrr63) hipLaunchKernelGGL(HIP_KERNEL_NAME(int_sa_expand_kernel<RrrBV>), grid, dim3(256), 0, st, v, d_sa);
+    else hipLaunchKernelGGL(HIP_KERNEL_NAME(int_sa_expand_kernel<PlainBV>), grid, dim3(256), 0, st, v, d_sa);
+    VLG_HIP_TRY(hipGetLastError());
+    return VLG_OK;
+}
+
+// isa_sample of an SA-order integer index into d_out ((n - 1) / inv_dens + 1 words): vlg_index_isa_samples
+vlg_status launch_int_isa_samples(const IntView& v, uint32_t inv_dens, uint64_t* d_out, hipStream_t st)
+{
+    if (v.sampling != kSamplingSaOrder || !inv_dens) return fail(VLG_E_INTERNAL, "integer index: ISA samples need SA-order samples");
+    const dim3 grid(grid_for(v.n_samples, 8192));
+    if (v.bv_kind == kBvRrr63) hipLaunchKernelGGL(HIP_KERNEL_NAME(int_isa_samples_kernel<RrrBV>), grid, dim3(256), 0, st, v, inv_dens, d_out);
+    else hipLaunchKernelGGL(HIP_KERNEL_NAME(int_isa_samples_kernel<PlainBV>), grid, dim3(256), 0, st, v, inv_dens, d_out);
     VLG_HIP_TRY(hipGetLastError());
     return VLG_OK;
 }

@@ -1695,6 +1695,17 @@ template vlg_status launch_unsample<true>(const IndexView&, const uint64_t*, con
                                           uint16_t*, uint16_t*, void*, size_t, unsigned long long*, unsigned long long*, unsigned long long*, uint64_t, hipStream_t,
                                           LaunchTimer*, const std::function<vlg_status()>*);
 
+// the copy on its own, for the integer index (int_index.hpp: an SA-order index of density 1 keeps the suffix array as its samples)
+vlg_status launch_sa_dense_copy(const uint32_t* sa, const uint64_t* d_l, const uint64_t* d_out_off, uint64_t n_pat, uint64_t total, uint32_t* d_out,
+                                hipStream_t stream)
+{
+    if (!total) return VLG_OK;
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(sa_dense_copy_kernel<uint32_t, uint32_t>), dim3(grid_for((total + 7) / 8, 32768)), dim3(256), 0, stream,
+                       sa, d_l, d_out_off, n_pat, total, d_out);
+    VLG_HIP_TRY(hipGetLastError());
+    return VLG_OK;
+}
+
 #define VLG_SWEEP_INST(P, W)                                                                                                          \
     template vlg_status launch_locate_sweep<P, W>(const IndexView&, const uint64_t*, const uint64_t*, uint64_t, uint64_t, P*, uint64_t*, \
                                                   uint64_t*, uint16_t*, uint16_t*, void*, size_t, unsigned long long*, unsigned long long*, \
@@ -1807,13 +1818,15 @@ extern "C" vlg_status vlg_index_isa_samples(const vlg_index* idx, uint32_t inv_d
     const uint64_t n = idx->hdr.n;
     if (count != (n - 1) / inv_dens + 1) return fail(VLG_E_INVALID, "ISA sample count must be (n-1)/inv_dens + 1");
     if (idx->hdr.sampling != kSamplingSaOrder) return fail(VLG_E_UNSUPPORTED, "ISA samples are computed from an SA-order index");
-    if (idx->is_int) return fail(VLG_E_UNSUPPORTED, "ISA samples of an integer-alphabet index are not built");
     uint64_t* d_out = nullptr;
     VLG_HIP_TRY(hipMalloc((void**)&d_out, count * 8));
     VLG_HIP_TRY(hipMemset(d_out, 0, count * 8));
     const dim3 grid(grid_for(idx->view.n_samples, 8192));
     const bool rrr = idx->view.bv_kind == kBvRrr63, wide = idx->hdr.sample_bytes == 8;
-    if (rrr && wide) hipLaunchKernelGGL(HIP_KERNEL_NAME(isa_samples_kernel<RrrBV, uint64_t>), grid, dim3(256), 0, nullptr, idx->view, inv_dens, d_out);
+    if (idx->is_int) {                                             // the walk on the wavelet matrix (int_index.hpp), plain or rrr levels
+        const vlg_status s = launch_int_isa_samples(idx->iview, inv_dens, d_out, nullptr);
+        if (s) { (void)hipFree(d_out); return s; }
+    } else if (rrr && wide) hipLaunchKernelGGL(HIP_KERNEL_NAME(isa_samples_kernel<RrrBV, uint64_t>), grid, dim3(256), 0, nullptr, idx->view, inv_dens, d_out);
     else if (rrr) hipLaunchKernelGGL(HIP_KERNEL_NAME(isa_samples_kernel<RrrBV, uint32_t>), grid, dim3(256), 0, nullptr, idx->view, inv_dens, d_out);
     else if (wide) hipLaunchKernelGGL(HIP_KERNEL_NAME(isa_samples_kernel<PlainBV, uint64_t>), grid, dim3(256), 0, nullptr, idx->view, inv_dens, d_out);
     else hipLaunchKernelGGL(HIP_KERNEL_NAME(isa_samples_kernel<PlainBV, uint32_t>), grid, dim3(256), 0, nullptr, idx->view, inv_dens, d_out);

@@ -84,6 +84,13 @@ vlg_status launch_int_locate_sweep(const IntView& v, const uint64_t* d_l, const 
                                    uint64_t* val_a, uint64_t* val_b, uint16_t* key_a, uint16_t* key_b, void* temp, size_t temp_bytes, unsigned long long* d_counter,
                                    unsigned long long* d_stats, uint64_t tail_threshold, hipStream_t stream, LaunchTimer* timer, Block* member,
                                    uint32_t n_member_lists, uint64_t* rec, const std::function<vlg_status()>* while_first_step = nullptr);
+// SA-order density 1 (vlg_index_resample): locate copies SA intervals of the samples, which are the suffix array (sa_dense_copy_kernel)
+vlg_status launch_sa_dense_copy(const uint32_t* sa, const uint64_t* d_l, const uint64_t* d_out_off, uint64_t n_pat, uint64_t total, uint32_t* d_out,
+                                hipStream_t stream);
+vlg_status launch_int_dense_copy(const IntView& v, const uint64_t* d_l, const uint64_t* d_out_off, uint64_t n_pat, uint64_t total, uint32_t* d_out, hipStream_t stream);
+// every SA value of an SA-order integer index (n words), and its ISA samples ((n - 1) / inv_dens + 1 words): LF walks from the samples
+vlg_status launch_int_sa_expand(const IntView& v, uint32_t* d_sa, hipStream_t st);
+vlg_status launch_int_isa_samples(const IntView& v, uint32_t inv_dens, uint64_t* d_out, hipStream_t st);
 // can this index's occurrences be located by the sorted sweep at all (the byte index always; the integer index with a 16-bit key)
 inline bool int_sweep_possible(const IntView& v) { return v.sigma < 0xFFFFu && v.n_levels >= 1 && v.n <= (1ull << 32); }
 

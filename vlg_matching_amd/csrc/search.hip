@@ -951,17 +951,24 @@ vlg_status build_physical(const vlg_index* idx, vlg_workspace* ws, vlg_result* r
         res->sum.locate_mode = idx->hdr.dens == 1 && idx->hdr.sampling == kSamplingSaOrder ? VLG_LOCATE_COPY : VLG_LOCATE_SWEEP;
         bt.mark("  physical: sweep");
     } else if (idx->is_int) {
-        // integer-alphabet index (int_index.hpp): one lane per occurrence on the wavelet matrix of the BWT
+        // integer-alphabet index (int_index.hpp): one lane per occurrence on the wavelet matrix of the BWT -- or, with the suffix array
+        // resident (SA order, density 1), a copy of the SA intervals whatever the alphabet or the size of the batch
+        const bool dense = idx->iview.dens == 1 && idx->iview.sampling == kSamplingSaOrder;
         ws->sample_reads += acc;
-        res->sum.locate_mode = VLG_LOCATE_WALKS;
+        res->sum.locate_mode = dense ? VLG_LOCATE_COPY : VLG_LOCATE_WALKS;
         if (vlg_status s = plan_sort()) return s;
         if constexpr (sizeof(pos_t) == 4) {
-            {
-                Timed t(ws, KS_EXPAND, 0);
-                if (vlg_status s = launch_expand<uint32_t>(d_lh, d_off64, nd, acc, Pa, nullptr, st)) return s;
+            if (dense) {
+                Timed t(ws, KS_LOCATE, 0);
+                if (vlg_status s = launch_int_dense_copy(idx->iview, d_lh, d_off64, nd, acc, Pa, st)) return s;
+            } else {
+                {
+                    Timed t(ws, KS_EXPAND, 0);
+                    if (vlg_status s = launch_expand<uint32_t>(d_lh, d_off64, nd, acc, Pa, nullptr, st)) return s;
+                }
+                Timed t(ws, KS_LOCATE, 0);
+                if (vlg_status s = launch_int_locate(idx->iview, Pa, acc, d_stats, st)) return s;
             }
-            Timed t(ws, KS_LOCATE, 0);
-            if (vlg_status s = launch_int_locate(idx->iview, Pa, acc, d_stats, st)) return s;
         } else return fail(VLG_E_INTERNAL, "integer-alphabet index with 64-bit positions");
     } else if (wide && sizeof(pos_t) == 4) {
         // few occurrences, 33-bit SA indices, 32-bit positions: the in-place kernel walks in 64-bit words of the scratch, then narrows

@@ -380,7 +380,8 @@ class VlgIndex:
         check(lib().vlg_index_save_sdsl(self._h, str(path).encode()))
 
     def isa_samples(self, inv_dens=64):
-        """isa_sample of csa_wt: out[j] = SA index of text position j * inv_dens."""
+        """isa_sample of csa_wt: out[j] = SA index of text position j * inv_dens.  Byte or integer alphabet, plain or rrr; the index
+        must be SA-order sampled (a text-order one raises VLG_E_UNSUPPORTED)."""
         n = self.info()["n"]
         out = np.zeros((n - 1) // inv_dens + 1, dtype=np.uint64)
         check(lib().vlg_index_isa_samples(self._h, inv_dens, out.ctypes.data, len(out)))
@@ -413,13 +414,15 @@ class VlgIndex:
         return VlgIndex(h)
 
     def resample(self, text_order=True, dens=32):
-        """A second index over the same BWT with text_order_sa_sampling (or SA-order sampling of another density); same answers."""
+        """A second index over the same BWT with text_order_sa_sampling (or SA-order sampling of another density; dens=1 keeps the suffix
+        array resident); same answers.  Byte or integer alphabet, plain or rrr; this index must be SA-order sampled (VLG_E_INVALID)."""
         h = C.c_void_p()
         check(lib().vlg_index_resample(self._h, 1 if text_order else 0, int(dens), C.byref(h)))
         return VlgIndex(h)
 
     def marked(self):
-        """text-order sampling: the marks over the SA indices -> uint8 array of n zeros / ones"""
+        """text-order sampling: the marks over the SA indices -> uint8 array of n zeros / ones (byte or integer alphabet; an SA-order
+        index raises VLG_E_INVALID)"""
         n = self.info()["n"]
         w = np.zeros((n + 63) // 64, dtype=np.uint64)
         check(lib().vlg_index_export_marked(self._h, w.ctypes.data))
