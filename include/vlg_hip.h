@@ -196,7 +196,8 @@ vlg_status vlg_suffix_array_device(const uint8_t* d_text, uint64_t n_text, uint3
 vlg_status vlg_index_isa_samples(const vlg_index* idx, uint32_t inv_dens, uint64_t* h_out, uint64_t count);
 /* Store the index in the reference's on-disk format of csa_wt<wt_huff<>,32,64> (csa_wt.hpp:374-393) so that stock sdsl
  * can load_from_file() it: wavelet tree with rank_support_v and both select_support_mcl, SA samples, ISA samples (density
- * 64), byte_alphabet.  The index must be a plain one with SA sample density 32. */
+ * 64), byte_alphabet.  The index must be a plain one with SA sample density 32.  An integer-alphabet index is stored as
+ * csa_wt<wt_int<>, d, 64, ., ., int_alphabet<>> instead (vlg_index_save_sdsl_int below). */
 vlg_status vlg_index_save_sdsl(const vlg_index* idx, const char* path);
 /* Load an index stored by stock sdsl: the file written by `store_to_file(csa, file)` / `csa.serialize(out)` for
  * csa_wt<wt_huff<>, t_dens, t_inv_dens> with the default sampling strategies and byte_alphabet
@@ -216,6 +217,51 @@ vlg_status vlg_index_load_sdsl(const char* path, uint32_t sa_sample_dens, vlg_in
  * device in this library's block numbering (vlg_index_compress): same sizes, same answers.  VLG_BV_PLAIN = vlg_index_load_sdsl. */
 vlg_status vlg_sdsl_file_open_kind(const char* path, uint32_t sa_sample_dens, int bv_kind, vlg_sdsl_file** out);
 vlg_status vlg_index_load_sdsl_kind(const char* path, uint32_t sa_sample_dens, int bv_kind, vlg_index** out);
+
+/* Integer-alphabet indexes on disk: the file of csa_wt<wt_int<>, t_dens, t_inv_dens, sa_order_sa_sampling<>, isa_sampling<>,
+ * int_alphabet<>> (test/csa_int_test.cpp:29-33), written by `store_to_file(csa, file)` (csa_wt.hpp:374-393):
+ *   wt_int        size, sigma (distinct values), tree (int_vector<1> of size * max_level bits), rank_support_v<1>,
+ *                 select_support_mcl<1>, select_support_mcl<0>, u32 max_level = hi(max(largest symbol, 1)) + 1   (wt_int.hpp:708-732)
+ *   SA samples    int_vector<> of width hi(n)+1: SA[0], SA[d], ...;  ISA samples: the same width, (n-1)/t_inv_dens + 1 of them
+ *   int_alphabet  m_char (sd_vector<> over largest symbol + 1 bits, EMPTY when the symbols are exactly 0..sigma-1), its rank / select
+ *                 supports (sd: nothing stored), m_C (int_vector<> of width hi(n)+1, sigma + 1 entries), u64 m_sigma
+ *                 (csa_alphabet_strategy.hpp:470-590; sd_vector.hpp:192-230, 404-416, 538-541, 643-646)
+ * The reference's wt_int<> keeps the BWT over the ORIGINAL symbols, level l (of max_level) being the arrangement stably sorted by the
+ * symbols' top l bits, one node per prefix (wt_int.hpp:182-262); the device index keeps a wavelet matrix over the compact symbols.
+ * Saving and loading convert between the two on the device, one level step at a time (csrc/int_index.hpp).
+ *
+ * vlg_index_save_sdsl(idx, path) on an integer index (plain or rrr, SA order, any density d) writes the plain type above with
+ * t_inv_dens = 64; vlg_index_save_sdsl_int chooses t_inv_dens (0 = 64).  A text-order integer index: VLG_E_UNSUPPORTED (resample it to
+ * SA order first); a byte index given to vlg_index_save_sdsl_int: VLG_E_INVALID.
+ * vlg_index_load_sdsl_int reads such a file: bv_kind VLG_BV_PLAIN for wt_int<>, VLG_BV_RRR63 for wt_int<rrr_vector<63>> (its blocks
+ * decoded on the host, the index then compressed by vlg_index_compress).  t_dens is not stored: pass it (0 = 32).  The ISA samples'
+ * count is checked against n, their values are not used.  Malformed files (truncated, trailing bytes, a sample count other than
+ * ceil(n / t_dens), wt size != C[sigma], max_level inconsistent with the largest symbol, C not increasing, a tree inconsistent with C)
+ * give VLG_E_INVALID; a symbol >= 2^32 gives VLG_E_UNSUPPORTED (the device index holds uint32_t symbols: INTEGRATION.md, symbol map).
+ * A loaded index is byte for byte the one vlg_index_build_int makes of the same text.
+ * vlg_sdsl_int_file_* parse on the host only (no GPU needed); vlg_index_load_sdsl_int = open + parts + vlg_index_from_int_parts. */
+typedef struct {
+    uint64_t n;                   /* csa.size() = |text| + 1                                                                  */
+    uint64_t sigma;               /* distinct symbols, the sentinel 0 included                                                */
+    uint32_t max_level;           /* levels of the reference's wt_int<>: hi(max(largest symbol, 1)) + 1                       */
+    uint32_t sa_sample_dens;
+    const uint64_t* comp2char;    /* [sigma] ascending, comp2char[0] = 0                                                      */
+    const uint64_t* C;            /* [sigma + 1]                                                                              */
+    const uint64_t* tree_words;   /* wt_int::tree: level l = bits [l * n, (l + 1) * n), bit i = word[i >> 6] >> (i & 63)      */
+    uint64_t tree_bits;           /* n * max_level                                                                            */
+    const uint64_t* sa_samples;   /* [n_samples] unpacked: SA[0], SA[dens], ...                                               */
+    uint64_t n_samples;
+} vlg_int_index_parts;
+typedef struct vlg_sdsl_int_file vlg_sdsl_int_file;
+vlg_status vlg_sdsl_int_file_open(const char* path, uint32_t sa_sample_dens, int bv_kind, vlg_sdsl_int_file** out);
+vlg_status vlg_sdsl_int_file_parts(const vlg_sdsl_int_file* f, vlg_int_index_parts* parts);   /* pointers stay valid until close */
+void vlg_sdsl_int_file_close(vlg_sdsl_int_file* f);
+vlg_status vlg_index_from_int_parts(const vlg_int_index_parts* h_parts, vlg_index** out);
+vlg_status vlg_index_load_sdsl_int(const char* path, uint32_t sa_sample_dens, int bv_kind, vlg_index** out);
+vlg_status vlg_index_save_sdsl_int(const vlg_index* idx, const char* path, uint32_t isa_inv_dens);
+/* wt_int::tree of an integer index (plain or rrr), converted on the device (two-phase: a null h_words gives *max_level only):
+ * h_words receives ceil(n * max_level / 64) words in the layout of vlg_int_index_parts.tree_words. */
+vlg_status vlg_index_export_int_tree(const vlg_index* idx, uint32_t* max_level, uint64_t* h_words);
 
 /* One contiguous device image of the read-only index, for replication across the GPUs of a node
  * (SURVEY.md 8e): the owner exports it into caller-provided HBM, the caller moves it with RCCL

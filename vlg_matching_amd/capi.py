@@ -27,6 +27,12 @@ class IndexParts(C.Structure):
                 ("n_nodes", C.c_uint32), ("sa_samples", C.c_void_p), ("n_samples", C.c_uint64)]
 
 
+class IntIndexParts(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("sigma", C.c_uint64), ("max_level", C.c_uint32), ("sa_sample_dens", C.c_uint32),
+                ("comp2char", C.c_void_p), ("C", C.c_void_p), ("tree_words", C.c_void_p), ("tree_bits", C.c_uint64),
+                ("sa_samples", C.c_void_p), ("n_samples", C.c_uint64)]
+
+
 class IndexPartsOut(C.Structure):
     _fields_ = [("char2comp", C.c_void_p), ("C", C.c_void_p), ("bv_words", C.c_void_p), ("nodes", C.c_void_p),
                 ("sa_samples", C.c_void_p)]
@@ -92,6 +98,13 @@ SYMBOLS = [
     ("vlg_sdsl_file_open_kind", _I, [C.c_char_p, C.c_uint32, _I, C.POINTER(_P)]),
     ("vlg_index_load_sdsl_kind", _I, [C.c_char_p, C.c_uint32, _I, C.POINTER(_P)]),
     ("vlg_index_save_sdsl", _I, [_P, C.c_char_p]),
+    ("vlg_sdsl_int_file_open", _I, [C.c_char_p, C.c_uint32, _I, C.POINTER(_P)]),
+    ("vlg_sdsl_int_file_parts", _I, [_P, C.POINTER(IntIndexParts)]),
+    ("vlg_sdsl_int_file_close", None, [_P]),
+    ("vlg_index_from_int_parts", _I, [C.POINTER(IntIndexParts), C.POINTER(_P)]),
+    ("vlg_index_load_sdsl_int", _I, [C.c_char_p, C.c_uint32, _I, C.POINTER(_P)]),
+    ("vlg_index_save_sdsl_int", _I, [_P, C.c_char_p, C.c_uint32]),
+    ("vlg_index_export_int_tree", _I, [_P, C.POINTER(C.c_uint32), _P]),
     ("vlg_suffix_array_device", _I, [_P, _U64, _P, _P]),
     ("vlg_index_isa_samples", _I, [_P, C.c_uint32, _P, _U64]),
     ("vlg_index_blob_bytes", _I, [_P, C.POINTER(_U64)]),

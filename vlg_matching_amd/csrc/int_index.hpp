@@ -429,6 +429,111 @@ __global__ void int_zero_check_kernel(const uint32_t* __restrict__ text, uint64_
     for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += (uint64_t)gridDim.x * blockDim.x) if (text[j] == 0) *flag = 1;
 }
 
+// ---- the reference's level-wise tree <-> the compact BWT (vlg_index_save_sdsl_int / vlg_index_from_int_parts) ----------------------------
+// wt_int<> (wt_int.hpp:182-262) keeps L = max_level levels over the ORIGINAL symbols: level l is bit L-1-l of every symbol in the
+// arrangement sorted stably by the symbols' top l bits, and a node is the run of one such prefix.  comp2char is ascending, so a node
+// starts at C[f], f = the first comp whose symbol has that prefix, and its one-child at C[sp], sp = its first comp whose bit l is 1.
+// One LEVEL STEP moves the element at p of level l (R = ones of the level before a position, s = C[f]) to
+//     bit ? C[sp] + (R(p) - R(s)) : p - (R(p) - R(s))
+// of level l + 1 and makes its node's first comp  bit ? sp : f.  Each lane carries (payload, f): the origin of the element when decoding
+// (after the last step f is its compact symbol: bwt[origin] = f), its compact symbol when encoding (the bit is read off comp2char).
+// Ranks come from the tree words and an exclusive scan of their popcounts, counted from the level's first word g0 (only differences of
+// two ranks inside the level are used, so the bits of neighbouring levels that share a word cancel).  Tree bit offsets are 64-bit.
+
+// per level, for every comp f that starts a node: split[f] = sp and end[f] = the first comp after the node (sigma for the last); shift = L - l
+__global__ void int_tree_split_kernel(const uint32_t* __restrict__ c2c, uint64_t sigma, uint32_t shift, uint32_t* __restrict__ split,
+                                      uint32_t* __restrict__ end)
+{
+    for (uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; c <= sigma; c += (uint64_t)gridDim.x * blockDim.x) {
+        if (c == sigma) { split[c] = end[c] = (uint32_t)sigma; continue; }
+        const uint64_t pre = (uint64_t)c2c[c] >> shift;
+        if (c > 0 && ((uint64_t)c2c[c - 1] >> shift) == pre) continue;          // not the first comp of its node
+        uint64_t lo = c, hi = sigma;
+        while (lo < hi) { const uint64_t mid = (lo + hi) >> 1; if (((uint64_t)c2c[mid] >> (shift - 1)) < 2 * pre + 1) lo = mid + 1; else hi = mid; }
+        split[c] = (uint32_t)lo;
+        hi = sigma;
+        while (lo < hi) { const uint64_t mid = (lo + hi) >> 1; if (((uint64_t)c2c[mid] >> shift) < pre + 1) lo = mid + 1; else hi = mid; }
+        end[c] = (uint32_t)lo;
+    }
+}
+// ones of tree bits [64 g0, q): pre = exclusive scan of the popcounts of words g0, g0 + 1, ...
+__device__ __forceinline__ uint64_t int_tree_rank(const uint64_t* __restrict__ tree, const uint32_t* __restrict__ pre, uint64_t g0, uint64_t q)
+{
+    const uint64_t g = q >> 6;
+    const uint32_t o = (uint32_t)(q & 63);
+    return pre[g - g0] + (o ? (uint64_t)__popcll(tree[g] & ((1ull << o) - 1)) : 0ull);
+}
+// decode: popcounts of the words g0 .. g0 + nw - 1 as the file holds them
+__global__ void int_tree_pops_kernel(const uint64_t* __restrict__ tree, uint64_t g0, uint64_t nw, uint32_t* __restrict__ pops)
+{
+    for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < nw; k += (uint64_t)gridDim.x * blockDim.x) pops[k] = (uint32_t)__popcll(tree[g0 + k]);
+}
+// encode: level l's bits as whole words, one wave per word (64 consecutive tree bits, __ballot), and the popcounts of the words as they
+// now stand.  A word the level shares with its neighbours is OR-ed in (the previous level's part is already there, the next one's is not).
+__global__ void __launch_bounds__(256) int_tree_emit_kernel(const uint32_t* __restrict__ cur, const uint32_t* __restrict__ c2c, uint64_t base, uint64_t n,
+                                                            uint32_t bit, uint64_t g0, uint64_t nw, uint64_t* __restrict__ tree, uint32_t* __restrict__ pops)
+{
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x >> 6);
+    for (uint64_t k = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; k < nw; k += waves) {
+        const uint64_t g = g0 + k, q = (g << 6) + lane;
+        const bool in = q >= base && q < base + n;
+        const uint32_t b = in ? (c2c[cur[q - base]] >> bit) & 1u : 0u;
+        const uint64_t m = __ballot(b);
+        if (lane == 0) {
+            uint64_t word = m;
+            if ((g << 6) >= base && (g << 6) + 64 <= base + n) tree[g] = m;
+            else word |= atomicOr(reinterpret_cast<unsigned long long*>(tree + g), (unsigned long long)m);
+            pops[k] = (uint32_t)__popcll(word);
+        }
+    }
+}
+// one level step (see above).  Every destination is checked against its child node, so a tree that disagrees with C flags *bad instead
+// of writing: with the checks each step is a bijection of [0, n).  kLast (decode): bwt[payload] = the leaf's comp instead of moving on.
+template <bool kLast>
+__global__ void int_tree_step_kernel(const uint64_t* __restrict__ tree, const uint32_t* __restrict__ pre, uint64_t base, uint64_t g0, uint64_t n,
+                                     const uint64_t* __restrict__ C, const uint32_t* __restrict__ split, const uint32_t* __restrict__ end,
+                                     const uint32_t* __restrict__ pay, const uint32_t* __restrict__ first, uint32_t* __restrict__ pay_out,
+                                     uint32_t* __restrict__ first_out, uint32_t* __restrict__ bad)
+{
+    for (uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t f = first[p];
+        const uint64_t s = C[f], q = base + p;
+        if (s > p) { *bad = 1; continue; }
+        const uint32_t b = (uint32_t)(tree[q >> 6] >> (q & 63)) & 1u;
+        const uint64_t r = int_tree_rank(tree, pre, g0, q) - int_tree_rank(tree, pre, g0, base + s);
+        const uint32_t sp = split[f];
+        const uint32_t nf = b ? sp : f;
+        const uint64_t dst = b ? C[sp] + r : p - r;
+        if (dst >= C[b ? end[f] : sp]) { *bad = 1; continue; }
+        if (kLast) pay_out[pay[p]] = nf;
+        else { pay_out[dst] = pay[p]; first_out[dst] = nf; }
+    }
+}
+// the compact BWT out of the wavelet matrix: one lane per position walks the levels (plain or rrr, the BV policies of device_rank.hpp)
+template <class BV>
+__global__ void __launch_bounds__(256) int_bwt_extract_kernel(IntView v, uint32_t* __restrict__ bwt)
+{
+    __shared__ IntLds<BV> sZ;
+    stage_int(sZ, v);
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < v.n; i += (uint64_t)gridDim.x * blockDim.x) {
+        uint64_t p = i;
+        uint32_t c = 0;
+        for (uint32_t l = 0; l < v.n_levels; ++l) {
+            uint32_t b;
+            uint64_t r1;
+            BV::rank_bit(v, sZ.sh, (uint32_t)(l * v.stride), p, r1, b);
+            p = b ? sZ.Z[l] + r1 : p - r1;
+            c = (c << 1) | b;
+        }
+        bwt[i] = c;
+    }
+}
+__global__ void int_iota_kernel(uint32_t* __restrict__ a, uint64_t n)
+{
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) a[i] = (uint32_t)i;
+}
+
 inline void layout_int(IntHeader& h)
 {
     uint64_t off = align_up(sizeof(IntHeader), 256);
@@ -508,6 +613,81 @@ vlg_status attach_int_blob(const void* d_blob, uint64_t bytes, vlg_index* idx)
 }
 }  // namespace vlg
 
+namespace {
+
+// a fresh SA-order integer blob for (n, sigma, dens), every byte zero but the header, its view bound: C, comp2char, the matrix and the
+// samples are the caller's to fill (zeroing the whole image also makes the padding between its arrays, and so every blob, deterministic)
+vlg_status int_alloc_blob(vlg_index* idx, uint64_t n, uint64_t sigma, uint32_t dens)
+{
+    IntHeader& h = idx->ihdr;
+    memset(&h, 0, sizeof h);
+    h.magic = kIntBlobMagic; h.n = n; h.sigma = sigma; h.dens = dens; h.n_samples = (n + dens - 1) / dens; h.nb = n / kBlockBits + 1;
+    h.levels = sigma > 1 ? bit_width64(sigma - 1) : 0;
+    if (h.levels > kMaxIntLevels || (uint64_t)h.levels * h.nb >= 0xFFFFFFF0ull) return fail(VLG_E_UNSUPPORTED, "integer index too large for 32-bit block numbers");
+    layout_int(h);
+    VLG_HIP_TRY(hipMalloc(&idx->d_blob, h.total_bytes));
+    idx->owns_blob = true;
+    VLG_HIP_TRY(hipMemset(idx->d_blob, 0, h.total_bytes));
+    VLG_HIP_TRY(hipMemcpy(idx->d_blob, &h, sizeof h, hipMemcpyHostToDevice));
+    bind_int_view(idx);
+    return VLG_OK;
+}
+
+// The tail every integer index shares (vlg_index_build_int, vlg_index_from_int_parts): the BWT in compact symbols in d_cur (n words) ->
+// the wavelet matrix level by level, Z and D, in the blob of int_alloc_blob whose C and comp2char are filled.  d_other, d_ka, d_kb: n-word
+// scratch; d_tmp: rocPRIM scratch of tmp_bytes (allocated here when smaller than the stable partition needs).
+vlg_status int_matrix_from_bwt(vlg_index* idx, uint32_t* d_cur, uint32_t* d_other, uint32_t* d_ka, uint32_t* d_kb, void* d_tmp, size_t tmp_bytes)
+{
+    const IntHeader& h = idx->ihdr;
+    const uint64_t n = h.n;
+    auto grid = [](uint64_t m) { return dim3((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((m + 255) / 256, 16384))); };
+    uint8_t* b = reinterpret_cast<uint8_t*>(idx->d_blob);
+    Block* lv = reinterpret_cast<Block*>(b + h.off_levels);
+    uint64_t* d_Z = reinterpret_cast<uint64_t*>(b + h.off_Z);
+    std::vector<uint64_t> Z(kMaxIntLevels, 0);
+    uint32_t* cur = d_cur;
+    uint32_t* other = d_other;
+    uint32_t* d_pops = nullptr;
+    void *d_tmp2 = nullptr, *d_own = nullptr;
+    size_t pops_tb = 0, pair_tb = 0;
+    auto run = [&]() -> vlg_status {
+        VLG_HIP_TRY(rocprim::radix_sort_pairs(nullptr, pair_tb, d_ka, d_kb, cur, other, n, 0, 1, nullptr));
+        if (tmp_bytes < pair_tb) { VLG_HIP_TRY(hipMalloc(&d_own, pair_tb + 16)); d_tmp = d_own; }
+        VLG_HIP_TRY(hipMalloc((void**)&d_pops, (h.nb + 1) * 4));
+        VLG_HIP_TRY(rocprim::exclusive_scan(nullptr, pops_tb, d_pops, d_pops, 0u, h.nb + 1, rocprim::plus<uint32_t>(), nullptr));
+        VLG_HIP_TRY(hipMalloc(&d_tmp2, pops_tb + 16));
+        for (uint32_t l = 0; l < h.levels; ++l) {
+            const uint32_t bit = h.levels - 1 - l;
+            Block* lb = lv + (uint64_t)l * h.nb;
+            VLG_HIP_TRY(hipMemsetAsync(d_pops, 0, (h.nb + 1) * 4, nullptr));
+            hipLaunchKernelGGL(wtsa_emit_kernel, grid(h.nb * 7), dim3(256), 0, nullptr, cur, n, bit, lb, h.nb, d_pops);
+            size_t tb = pops_tb;
+            VLG_HIP_TRY(rocprim::exclusive_scan(d_tmp2, tb, d_pops, d_pops, 0u, h.nb + 1, rocprim::plus<uint32_t>(), nullptr));
+            hipLaunchKernelGGL(wtsa_counts_kernel, grid(h.nb), dim3(256), 0, nullptr, lb, d_pops, h.nb);
+            uint32_t ones = 0;
+            VLG_HIP_TRY(hipMemcpy(&ones, d_pops + h.nb, 4, hipMemcpyDeviceToHost));
+            Z[l] = n - ones;
+            if (l + 1 < h.levels) {                                    // next arrangement: stable by this bit, zeros first
+                hipLaunchKernelGGL(int_bit_keys_kernel, grid(n), dim3(256), 0, nullptr, cur, n, bit, d_ka);
+                tb = pair_tb;
+                VLG_HIP_TRY(rocprim::radix_sort_pairs(d_tmp, tb, d_ka, d_kb, cur, other, n, 0, 1, nullptr));
+                std::swap(cur, other);
+            }
+            VLG_HIP_TRY(hipGetLastError());
+        }
+        VLG_HIP_TRY(hipMemcpy(d_Z, Z.data(), kMaxIntLevels * 8, hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(int_D_kernel, grid(h.sigma), dim3(256), 0, nullptr, idx->iview, reinterpret_cast<uint64_t*>(b + h.off_D));
+        VLG_HIP_TRY(hipGetLastError());
+        VLG_HIP_TRY(hipDeviceSynchronize());
+        return VLG_OK;
+    };
+    const vlg_status st = run();
+    for (void* p : {(void*)d_pops, d_tmp2, d_own}) if (p) (void)hipFree(p);
+    return st;
+}
+
+}  // namespace
+
 extern "C" vlg_status vlg_index_build_int(const uint32_t* h_text, uint64_t n_symbols, uint32_t dens, vlg_index** out)
 {
     if (!out || (n_symbols && !h_text)) return fail(VLG_E_INVALID, "null argument");
@@ -521,7 +701,7 @@ extern "C" vlg_status vlg_index_build_int(const uint32_t* h_text, uint64_t n_sym
     const uint64_t n = n_symbols + 1;
     vlg_index* idx = new vlg_index();
     uint32_t *d_text = nullptr, *d_sa5 = nullptr, *d_flag = nullptr, *d_pos = nullptr, *d_sa = nullptr, *d_a = nullptr, *d_b = nullptr, *d_ka = nullptr,
-             *d_kb = nullptr, *d_pops = nullptr, *d_c2c = nullptr;
+             *d_kb = nullptr, *d_c2c = nullptr;
     uint8_t* d_bytes = nullptr;
     uint64_t* d_C = nullptr;
     void* d_tmp = nullptr;
@@ -582,73 +762,24 @@ extern "C" vlg_status vlg_index_build_int(const uint32_t* h_text, uint64_t n_sym
             VLG_HIP_TRY(hipMemcpy(&distinct, d_kb + (n_symbols - 1), 4, hipMemcpyDeviceToHost));
             sigma = (uint64_t)distinct + 1;
         }
-        IntHeader& h = idx->ihdr;
-        memset(&h, 0, sizeof h);
-        h.magic = kIntBlobMagic; h.n = n; h.sigma = sigma; h.dens = dens; h.n_samples = (n + dens - 1) / dens; h.nb = n / kBlockBits + 1;
-        h.levels = sigma > 1 ? bit_width64(sigma - 1) : 0;
-        if (h.levels > kMaxIntLevels || (uint64_t)h.levels * h.nb >= 0xFFFFFFF0ull) return fail(VLG_E_UNSUPPORTED, "integer index too large for 32-bit block numbers");
-        layout_int(h);
-        VLG_HIP_TRY(hipMalloc(&idx->d_blob, h.total_bytes));
-        idx->owns_blob = true;
+        if (vlg_status s = int_alloc_blob(idx, n, sigma, dens)) return s;
+        const IntHeader& h = idx->ihdr;
         uint8_t* b = reinterpret_cast<uint8_t*>(idx->d_blob);
-        VLG_HIP_TRY(hipMemset(b, 0, h.off_levels));
-        VLG_HIP_TRY(hipMemcpy(b, &h, sizeof h, hipMemcpyHostToDevice));
-        bind_int_view(idx);
         d_c2c = reinterpret_cast<uint32_t*>(b + h.off_c2c);
         d_C = reinterpret_cast<uint64_t*>(b + h.off_C);
-        VLG_HIP_TRY(hipMemset(d_c2c, 0, sigma * 4));                       // comp 0 = the sentinel, C[0] = 0
-        VLG_HIP_TRY(hipMemset(d_C, 0, (sigma + 1) * 8));
-        if (n_symbols) hipLaunchKernelGGL(int_alphabet_kernel, grid(n_symbols), dim3(256), 0, nullptr, d_b, d_kb, n_symbols, d_c2c, d_C);
+        if (n_symbols) hipLaunchKernelGGL(int_alphabet_kernel, grid(n_symbols), dim3(256), 0, nullptr, d_b, d_kb, n_symbols, d_c2c, d_C);   // comp 0 = the sentinel, C[0] = 0
         VLG_HIP_TRY(hipMemcpy(d_C + sigma, &n, 8, hipMemcpyHostToDevice));
         // ---- BWT in compact symbols, then the wavelet matrix level by level ----------------------------------------------------------------
         hipLaunchKernelGGL(int_bwt_kernel, grid(n), dim3(256), 0, nullptr, d_text, d_sa, n, d_c2c, sigma, d_a);
         VLG_HIP_TRY(hipGetLastError());
-        VLG_HIP_TRY(hipMalloc((void**)&d_pops, (h.nb + 1) * 4));
-        Block* lv = reinterpret_cast<Block*>(b + h.off_levels);
-        uint64_t* d_Z = reinterpret_cast<uint64_t*>(b + h.off_Z);
-        std::vector<uint64_t> Z(kMaxIntLevels, 0);
-        uint32_t* cur = d_a;
-        uint32_t* other = d_b;
-        size_t pops_tb = 0;
-        VLG_HIP_TRY(rocprim::exclusive_scan(nullptr, pops_tb, d_pops, d_pops, 0u, h.nb + 1, rocprim::plus<uint32_t>(), nullptr));
-        void* d_tmp2 = nullptr;
-        VLG_HIP_TRY(hipMalloc(&d_tmp2, pops_tb + 16));
-        vlg_status lst = VLG_OK;
-        for (uint32_t l = 0; l < h.levels && !lst; ++l) {
-            const uint32_t bit = h.levels - 1 - l;
-            Block* lb = lv + (uint64_t)l * h.nb;
-            auto step = [&]() -> vlg_status {
-                VLG_HIP_TRY(hipMemsetAsync(d_pops, 0, (h.nb + 1) * 4, nullptr));
-                hipLaunchKernelGGL(wtsa_emit_kernel, grid(h.nb * 7), dim3(256), 0, nullptr, cur, n, bit, lb, h.nb, d_pops);
-                size_t tb = pops_tb;
-                VLG_HIP_TRY(rocprim::exclusive_scan(d_tmp2, tb, d_pops, d_pops, 0u, h.nb + 1, rocprim::plus<uint32_t>(), nullptr));
-                hipLaunchKernelGGL(wtsa_counts_kernel, grid(h.nb), dim3(256), 0, nullptr, lb, d_pops, h.nb);
-                uint32_t ones = 0;
-                VLG_HIP_TRY(hipMemcpy(&ones, d_pops + h.nb, 4, hipMemcpyDeviceToHost));
-                Z[l] = n - ones;
-                if (l + 1 < h.levels) {                                // next arrangement: stable by this bit, zeros first
-                    hipLaunchKernelGGL(int_bit_keys_kernel, grid(n), dim3(256), 0, nullptr, cur, n, bit, d_ka);
-                    tb = pair_tb;
-                    VLG_HIP_TRY(rocprim::radix_sort_pairs(d_tmp, tb, d_ka, d_kb, cur, other, n, 0, 1, nullptr));
-                    std::swap(cur, other);
-                }
-                VLG_HIP_TRY(hipGetLastError());
-                return VLG_OK;
-            };
-            lst = step();
-        }
-        (void)hipFree(d_tmp2);
-        if (lst) return lst;
-        VLG_HIP_TRY(hipMemcpy(d_Z, Z.data(), kMaxIntLevels * 8, hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(int_D_kernel, grid(sigma), dim3(256), 0, nullptr, idx->iview, reinterpret_cast<uint64_t*>(b + h.off_D));
+        if (vlg_status s = int_matrix_from_bwt(idx, d_a, d_b, d_ka, d_kb, d_tmp, std::max(std::max(sort_tb, scan_tb), pair_tb))) return s;
         hipLaunchKernelGGL(int_samples_kernel, grid(h.n_samples), dim3(256), 0, nullptr, d_sa, h.n_samples, dens, reinterpret_cast<uint32_t*>(b + h.off_samples));
         VLG_HIP_TRY(hipGetLastError());
         VLG_HIP_TRY(hipDeviceSynchronize());
         return VLG_OK;
     };
     const vlg_status st = run();
-    for (void* p : {(void*)d_text, (void*)d_sa5, (void*)d_flag, (void*)d_pos, (void*)d_sa, (void*)d_a, (void*)d_b, (void*)d_ka, (void*)d_kb, (void*)d_pops,
-                    (void*)d_bytes, d_tmp})
+    for (void* p : {(void*)d_text, (void*)d_sa5, (void*)d_flag, (void*)d_pos, (void*)d_sa, (void*)d_a, (void*)d_b, (void*)d_ka, (void*)d_kb, (void*)d_bytes, d_tmp})
         if (p) (void)hipFree(p);
     if (st) { vlg_index_destroy(idx); return st; }
     *out = idx;
@@ -800,3 +931,192 @@ vlg_status launch_int_isa_samples(const IntView& v, uint32_t inv_dens, uint64_t*
 }
 
 }  // namespace vlg
+
+// ---- the reference's wt_int<> and the device index (vlg_hip.h: vlg_index_from_int_parts, vlg_index_export_int_tree) ---------------------
+namespace {
+
+inline uint32_t int_max_level(uint64_t largest) { return (uint32_t)bit_width64(std::max<uint64_t>(largest, 1)); }   // hi(max(x, 1)) + 1
+
+// device scratch of the level steps: the tree, (payload, first comp) twice, the per-node tables and the popcount scan of one level
+struct TreeScratch {
+    uint64_t* tree = nullptr;
+    uint32_t *pay[2] = {nullptr, nullptr}, *first[2] = {nullptr, nullptr}, *split = nullptr, *end = nullptr, *pops = nullptr, *bad = nullptr;
+    void* tmp = nullptr;
+    size_t tmp_bytes = 0;
+    uint64_t words = 0, max_nw = 0;
+    vlg_status alloc(uint64_t n, uint64_t sigma, uint32_t L)
+    {
+        words = (n * L + 63) / 64;
+        max_nw = n / 64 + 2;                                            // words one level of n bits touches
+        VLG_HIP_TRY(hipMalloc((void**)&tree, (words + 1) * 8));
+        for (int k = 0; k < 2; ++k) {
+            VLG_HIP_TRY(hipMalloc((void**)&pay[k], n * 4));
+            VLG_HIP_TRY(hipMalloc((void**)&first[k], n * 4));
+        }
+        VLG_HIP_TRY(hipMalloc((void**)&split, (sigma + 1) * 4));
+        VLG_HIP_TRY(hipMalloc((void**)&end, (sigma + 1) * 4));
+        VLG_HIP_TRY(hipMalloc((void**)&pops, (max_nw + 1) * 4));
+        VLG_HIP_TRY(hipMalloc((void**)&bad, 4));
+        VLG_HIP_TRY(hipMemset(bad, 0, 4));
+        VLG_HIP_TRY(rocprim::exclusive_scan(nullptr, tmp_bytes, pops, pops, 0u, max_nw, rocprim::plus<uint32_t>(), nullptr));
+        VLG_HIP_TRY(hipMalloc(&tmp, tmp_bytes + 16));
+        return VLG_OK;
+    }
+    void release()
+    {
+        for (void* p : {(void*)tree, (void*)pay[0], (void*)pay[1], (void*)first[0], (void*)first[1], (void*)split, (void*)end, (void*)pops, (void*)bad, tmp})
+            if (p) (void)hipFree(p);
+        *this = TreeScratch();
+    }
+};
+
+inline dim3 int_grid(uint64_t m) { return dim3((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((m + 255) / 256, 16384))); }
+
+// level l of the tree: first word g0 and the number of words nw it touches
+inline void tree_level_words(uint64_t n, uint32_t l, uint64_t& base, uint64_t& g0, uint64_t& nw)
+{
+    base = (uint64_t)l * n;
+    g0 = base >> 6;
+    nw = ((base + n - 1) >> 6) - g0 + 1;
+}
+
+// encode: compact BWT in s.pay[0] -> the level-wise tree over comp2char (d_c2c) in s.tree, L levels
+vlg_status int_tree_encode(TreeScratch& s, uint64_t n, uint64_t sigma, uint32_t L, const uint32_t* d_c2c, const uint64_t* d_C)
+{
+    VLG_HIP_TRY(hipMemset(s.tree, 0, (s.words + 1) * 8));
+    VLG_HIP_TRY(hipMemset(s.first[0], 0, n * 4));
+    int cur = 0;
+    for (uint32_t l = 0; l < L; ++l) {
+        uint64_t base, g0, nw;
+        tree_level_words(n, l, base, g0, nw);
+        const uint32_t waves_per_block = 4;
+        const dim3 eg((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((nw + waves_per_block - 1) / waves_per_block, 16384)));
+        hipLaunchKernelGGL(int_tree_emit_kernel, eg, dim3(256), 0, nullptr, s.pay[cur], d_c2c, base, n, L - 1 - l, g0, nw, s.tree, s.pops);
+        if (l + 1 == L) break;                                         // the last level's bits are all the file needs
+        size_t tb = s.tmp_bytes;
+        VLG_HIP_TRY(rocprim::exclusive_scan(s.tmp, tb, s.pops, s.pops, 0u, nw, rocprim::plus<uint32_t>(), nullptr));
+        hipLaunchKernelGGL(int_tree_split_kernel, int_grid(sigma + 1), dim3(256), 0, nullptr, d_c2c, sigma, L - l, s.split, s.end);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(int_tree_step_kernel<false>), int_grid(n), dim3(256), 0, nullptr, s.tree, s.pops, base, g0, n, d_C, s.split, s.end,
+                           s.pay[cur], s.first[cur], s.pay[cur ^ 1], s.first[cur ^ 1], s.bad);
+        VLG_HIP_TRY(hipGetLastError());
+        cur ^= 1;
+    }
+    VLG_HIP_TRY(hipGetLastError());
+    uint32_t bad = 0;
+    VLG_HIP_TRY(hipMemcpy(&bad, s.bad, 4, hipMemcpyDeviceToHost));
+    if (bad) return fail(VLG_E_INTERNAL, "integer index: the level-wise tree does not agree with the alphabet");
+    return VLG_OK;
+}
+
+// decode: the level-wise tree in s.tree -> compact BWT in *bwt (one of s's payload arrays); C and comp2char on the device
+vlg_status int_tree_decode(TreeScratch& s, uint64_t n, uint64_t sigma, uint32_t L, const uint32_t* d_c2c, const uint64_t* d_C, uint32_t** bwt)
+{
+    hipLaunchKernelGGL(int_iota_kernel, int_grid(n), dim3(256), 0, nullptr, s.pay[0], n);
+    VLG_HIP_TRY(hipMemset(s.first[0], 0, n * 4));
+    int cur = 0;
+    for (uint32_t l = 0; l < L; ++l) {
+        uint64_t base, g0, nw;
+        tree_level_words(n, l, base, g0, nw);
+        hipLaunchKernelGGL(int_tree_pops_kernel, int_grid(nw), dim3(256), 0, nullptr, s.tree, g0, nw, s.pops);
+        size_t tb = s.tmp_bytes;
+        VLG_HIP_TRY(rocprim::exclusive_scan(s.tmp, tb, s.pops, s.pops, 0u, nw, rocprim::plus<uint32_t>(), nullptr));
+        hipLaunchKernelGGL(int_tree_split_kernel, int_grid(sigma + 1), dim3(256), 0, nullptr, d_c2c, sigma, L - l, s.split, s.end);
+        if (l + 1 < L)
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(int_tree_step_kernel<false>), int_grid(n), dim3(256), 0, nullptr, s.tree, s.pops, base, g0, n, d_C, s.split, s.end,
+                               s.pay[cur], s.first[cur], s.pay[cur ^ 1], s.first[cur ^ 1], s.bad);
+        else
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(int_tree_step_kernel<true>), int_grid(n), dim3(256), 0, nullptr, s.tree, s.pops, base, g0, n, d_C, s.split, s.end,
+                               s.pay[cur], s.first[cur], s.pay[cur ^ 1], nullptr, s.bad);
+        VLG_HIP_TRY(hipGetLastError());
+        uint32_t bad = 0;                                              // a step that flagged left holes: the next one must not read them
+        VLG_HIP_TRY(hipMemcpy(&bad, s.bad, 4, hipMemcpyDeviceToHost));
+        if (bad) return fail(VLG_E_INVALID, "wt_int tree does not agree with the alphabet's C (level " + std::to_string(l) + ")");
+        cur ^= 1;
+    }
+    *bwt = s.pay[cur];
+    return VLG_OK;
+}
+
+}  // namespace
+
+extern "C" vlg_status vlg_index_export_int_tree(const vlg_index* idx, uint32_t* max_level, uint64_t* h_words)
+{
+    if (!idx || !max_level) return fail(VLG_E_INVALID, "null argument");
+    if (!idx->is_int) return fail(VLG_E_INVALID, "not an integer-alphabet index");
+    const IntView& v = idx->iview;
+    const uint64_t n = v.n, sigma = v.sigma;
+    uint32_t largest = 0;
+    VLG_HIP_TRY(hipMemcpy(&largest, v.comp2char + (sigma - 1), 4, hipMemcpyDeviceToHost));
+    const uint32_t L = int_max_level(largest);
+    *max_level = L;
+    if (!h_words) return VLG_OK;
+    release_cached_device_memory();
+    TreeScratch s;
+    auto run = [&]() -> vlg_status {
+        if (vlg_status st = s.alloc(n, sigma, L)) return st;
+        if (v.bv_kind == kBvRrr63) hipLaunchKernelGGL(HIP_KERNEL_NAME(int_bwt_extract_kernel<RrrBV>), int_grid(n), dim3(256), 0, nullptr, v, s.pay[0]);
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(int_bwt_extract_kernel<PlainBV>), int_grid(n), dim3(256), 0, nullptr, v, s.pay[0]);
+        VLG_HIP_TRY(hipGetLastError());
+        if (vlg_status st = int_tree_encode(s, n, sigma, L, v.comp2char, v.C)) return st;
+        VLG_HIP_TRY(hipMemcpy(h_words, s.tree, s.words * 8, hipMemcpyDeviceToHost));
+        return VLG_OK;
+    };
+    const vlg_status st = run();
+    s.release();
+    return st;
+}
+
+extern "C" vlg_status vlg_index_from_int_parts(const vlg_int_index_parts* p, vlg_index** out)
+{
+    if (!p || !out) return fail(VLG_E_INVALID, "null argument");
+    *out = nullptr;
+    const uint64_t n = p->n, sigma = p->sigma;
+    if (!n || !sigma || sigma > n || !p->C || !p->comp2char || !p->sa_sample_dens || (p->tree_bits && !p->tree_words) || (p->n_samples && !p->sa_samples))
+        return fail(VLG_E_INVALID, "integer index parts: missing or empty members");
+    if (n > 0xFFFFFFFFull) return fail(VLG_E_UNSUPPORTED, "integer index parts: n >= 2^32 (SA samples and positions are 32-bit)");
+    if (p->C[0] != 0 || p->C[sigma] != n || p->comp2char[0] != 0) return fail(VLG_E_INVALID, "integer index parts: C[0] = 0, C[sigma] = n and comp2char[0] = 0 are required");
+    for (uint64_t c = 0; c < sigma; ++c) {
+        if (p->C[c + 1] <= p->C[c]) return fail(VLG_E_INVALID, "integer index parts: C does not increase");
+        if (c && p->comp2char[c] <= p->comp2char[c - 1]) return fail(VLG_E_INVALID, "integer index parts: comp2char does not increase");
+    }
+    if (p->comp2char[sigma - 1] > 0xFFFFFFFFull) return fail(VLG_E_UNSUPPORTED, "integer index parts: a symbol >= 2^32 (the device index holds uint32_t symbols)");
+    const uint32_t L = int_max_level(p->comp2char[sigma - 1]);
+    if (p->max_level != L || p->tree_bits != n * L) return fail(VLG_E_INVALID, "integer index parts: max_level or the tree size disagree with the largest symbol");
+    if (p->n_samples != (n + p->sa_sample_dens - 1) / p->sa_sample_dens) return fail(VLG_E_INVALID, "integer index parts: SA sample count is not ceil(n / dens)");
+    std::vector<uint32_t> c2c(sigma), smp(std::max<uint64_t>(p->n_samples, 1));
+    for (uint64_t c = 0; c < sigma; ++c) c2c[c] = (uint32_t)p->comp2char[c];
+    for (uint64_t j = 0; j < p->n_samples; ++j) {
+        if (p->sa_samples[j] >= n) return fail(VLG_E_INVALID, "integer index parts: an SA sample is not below n");
+        smp[j] = (uint32_t)p->sa_samples[j];
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(VLG_E_NO_DEVICE, "no HIP device available (the VLG library has no CPU fallback)");
+    release_cached_device_memory();
+    vlg_index* idx = new vlg_index();
+    TreeScratch s;
+    auto run = [&]() -> vlg_status {
+        if (vlg_status st = int_alloc_blob(idx, n, sigma, p->sa_sample_dens)) return st;
+        const IntHeader& h = idx->ihdr;
+        uint8_t* b = reinterpret_cast<uint8_t*>(idx->d_blob);
+        uint32_t* d_c2c = reinterpret_cast<uint32_t*>(b + h.off_c2c);
+        uint64_t* d_C = reinterpret_cast<uint64_t*>(b + h.off_C);
+        VLG_HIP_TRY(hipMemcpy(d_C, p->C, (sigma + 1) * 8, hipMemcpyHostToDevice));
+        VLG_HIP_TRY(hipMemcpy(d_c2c, c2c.data(), sigma * 4, hipMemcpyHostToDevice));
+        VLG_HIP_TRY(hipMemcpy(b + h.off_samples, smp.data(), p->n_samples * 4, hipMemcpyHostToDevice));
+        if (vlg_status st = s.alloc(n, sigma, L)) return st;
+        VLG_HIP_TRY(hipMemset(s.tree + s.words, 0, 8));
+        VLG_HIP_TRY(hipMemcpy(s.tree, p->tree_words, s.words * 8, hipMemcpyHostToDevice));
+        uint32_t* bwt = nullptr;
+        if (vlg_status st = int_tree_decode(s, n, sigma, L, d_c2c, d_C, &bwt)) return st;
+        // the tree, the tables and the scan go; the four n-word arrays are the matrix builder's scratch
+        for (void* q : {(void*)s.tree, (void*)s.split, (void*)s.end, (void*)s.pops, (void*)s.bad, s.tmp}) (void)hipFree(q);
+        s.tree = nullptr; s.split = s.end = s.pops = s.bad = nullptr; s.tmp = nullptr;
+        uint32_t* other = bwt == s.pay[0] ? s.pay[1] : s.pay[0];
+        return int_matrix_from_bwt(idx, bwt, other, s.first[0], s.first[1], nullptr, 0);
+    };
+    const vlg_status st = run();
+    s.release();
+    if (st) { vlg_index_destroy(idx); return st; }
+    *out = idx;
+    return VLG_OK;
+}

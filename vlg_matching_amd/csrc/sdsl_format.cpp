@@ -10,6 +10,8 @@
 //   rrr_vector<63>         include/sdsl/rrr_vector.hpp:349-372 (csa_wt<wt_huff<rrr_vector<63>>>, BASELINE config 5: the stock image is
 //                          decoded block by block on the host and re-coded on the device, vlg_index_load_sdsl_kind)
 // Host-only: nothing here touches the GPU.
+// The same for csa_wt<wt_int<>, t_dens, t_inv_dens, sa_order_sa_sampling<>, isa_sampling<>, int_alphabet<>> (end of the file): the
+// reader is host-only as well; the writer asks the device for the level-wise tree (vlg_index_export_int_tree, int_index.hpp).
 #include <cstdio>
 #include <cstring>
 #include <memory>
@@ -374,6 +376,7 @@ extern "C" vlg_status vlg_index_save_sdsl(const vlg_index* idx, const char* path
 {
     using namespace vlg;
     if (!idx || !path) return fail(VLG_E_INVALID, "null argument");
+    if (idx->is_int) return vlg_index_save_sdsl_int(idx, path, 64);      // csa_wt<wt_int<>, d, 64, ., ., int_alphabet<>>
     vlg_index_parts sz;
     if (vlg_status st = vlg_index_export_parts(idx, &sz, nullptr)) return st;
     if (sz.sa_sample_dens != 32) return fail(VLG_E_UNSUPPORTED, "the reference type csa_wt<wt_huff<>,32,64> has SA sample density 32");
@@ -429,4 +432,271 @@ extern "C" vlg_status vlg_index_save_sdsl(const vlg_index* idx, const char* path
     const bool ok = out.ok;
     if (fclose(fp) != 0 || !ok) return fail(VLG_E_INVALID, std::string("write failed: ") + path);
     return VLG_OK;
+}
+
+// =============================================================================================
+// Integer alphabet: csa_wt<wt_int<[rrr_vector<63>]>, t_dens, t_inv_dens, sa_order_sa_sampling<>, isa_sampling<>, int_alphabet<>>
+// (test/csa_int_test.cpp:29-33), member by member:
+//   csa_wt::serialize       include/sdsl/csa_wt.hpp:374-393        wavelet tree, SA samples, ISA samples, alphabet
+//   wt_int::serialize       include/sdsl/wt_int.hpp:708-732        size, sigma, tree, rank_support_v<1>, select_support_mcl<1>,
+//                                                                  select_support_mcl<0>, u32 max_level (tree layout: :182-262)
+//   int_alphabet            include/sdsl/csa_alphabet_strategy.hpp:470-590   m_char (empty when the symbols are 0..sigma-1),
+//                                                                  m_char_rank, m_char_select, m_C, u64 m_sigma
+//   sd_vector<>             include/sdsl/sd_vector.hpp:192-230, 404-416     size, wl, low, high, select_support_mcl<1>, <0>; its rank
+//                                                                  and select supports store nothing (:538-541, 643-646)
+// =============================================================================================
+struct vlg_sdsl_int_file {
+    std::vector<uint8_t> raw;
+    uint64_t n = 0, sigma = 0, tree_bits = 0;
+    uint32_t max_level = 0, dens = 0;
+    std::vector<uint64_t> tree, comp2char, C, samples;
+};
+
+namespace {
+
+// a status with its message; ok() while none was set
+struct IntParse {
+    vlg_status st = VLG_OK;
+    std::string msg;
+    vlg_status bad(vlg_status s, const std::string& what) { st = s; msg = what; return s; }
+};
+
+vlg_status sdsl_int_file_open_impl(const char* path, uint32_t sa_sample_dens, int bv_kind, vlg_sdsl_int_file** out)
+{
+    using namespace vlg;
+    FILE* fp = fopen(path, "rb");
+    if (!fp) return fail(VLG_E_INVALID, std::string("cannot open ") + path);
+    std::unique_ptr<FILE, int (*)(FILE*)> fp_guard(fp, fclose);
+    std::unique_ptr<vlg_sdsl_int_file> holder(new vlg_sdsl_int_file());
+    vlg_sdsl_int_file* f = holder.get();
+    fseek(fp, 0, SEEK_END);
+    long sz = ftell(fp);
+    fseek(fp, 0, SEEK_SET);
+    f->raw.resize(sz > 0 ? (size_t)sz : 0);
+    size_t got = f->raw.empty() ? 0 : fread(f->raw.data(), 1, f->raw.size(), fp);
+    fp_guard.reset();
+    auto bad = [&](const std::string& what) { return fail(VLG_E_INVALID, "not a csa_wt<wt_int<>, ., ., ., ., int_alphabet<>> file (" + what + ")"); };
+    if (got != f->raw.size()) return bad("short read");
+    Cursor c{f->raw.data(), f->raw.data() + f->raw.size()};
+    // ---- wt_int (wt_int.hpp:708-732) ----------------------------------------------------------------------------------------------
+    const uint64_t wt_size = c.get<uint64_t>();
+    const uint64_t wt_sigma = c.get<uint64_t>();
+    if (!c.ok) return bad("wavelet tree header");
+    if (bv_kind == VLG_BV_RRR63) {
+        // wt_int<rrr_vector<63>>: the tree is an rrr_vector, its rank / select supports store nothing (rrr_vector.hpp:511-522)
+        if (!rrr63_to_plain(c, f->tree_bits, f->tree)) return bad("rrr_vector<63> tree");
+    } else {
+        uint8_t w;
+        const uint8_t* tw = c.int_vector(1, f->tree_bits, w);
+        if (!c.ok) return bad("tree");
+        f->tree.assign((f->tree_bits + 63) / 64 + 1, 0);
+        if (f->tree_bits) memcpy(f->tree.data(), tw, ((f->tree_bits + 63) / 64) * 8);
+        c.skip_int_vector(64);                                    // rank_support_v (the device counts its own)
+        c.skip_select_mcl();                                      // select_1
+        c.skip_select_mcl();                                      // select_0
+    }
+    f->max_level = c.get<uint32_t>();
+    if (!c.ok) return bad("wavelet tree");
+    f->n = wt_size;
+    const uint64_t n = f->n;
+    if (n == 0) return bad("empty wavelet tree: a csa holds at least the sentinel");
+    // ---- SA samples, ISA samples: int_vector<0> (csa_sampling_strategy.hpp:64-112, 626-642) ---------------------------------------------
+    uint64_t sbits; uint8_t sw;
+    const uint8_t* sw_words = c.int_vector(0, sbits, sw);
+    if (!c.ok || sw == 0 || sbits % sw) return bad("SA samples");
+    const uint64_t n_samples = sbits / sw;
+    uint64_t ibits; uint8_t iw;
+    c.int_vector(0, ibits, iw);
+    if (!c.ok || iw == 0 || ibits % iw) return bad("ISA samples");
+    // ---- int_alphabet<sd_vector<>> (csa_alphabet_strategy.hpp:578-587) ---------------------------------------------------------------
+    const uint64_t char_size = c.get<uint64_t>();                 // sd_vector: m_size, m_wl, m_low, m_high, two select_support_mcl
+    const uint8_t wl = c.get<uint8_t>();
+    uint64_t low_bits; uint8_t low_w;
+    const uint8_t* low = c.int_vector(0, low_bits, low_w);
+    uint64_t high_bits; uint8_t hw;
+    const uint8_t* high = c.int_vector(1, high_bits, hw);
+    c.skip_select_mcl();
+    c.skip_select_mcl();
+    uint64_t cbits; uint8_t cw;
+    const uint8_t* Cw = c.int_vector(0, cbits, cw);
+    const uint64_t sigma = c.get<uint64_t>();
+    if (!c.ok) return bad("alphabet: truncated");
+    if (c.p != c.e) return bad(std::to_string(c.e - c.p) + " trailing bytes after the alphabet");
+    if (cw == 0 || cbits != (sigma + 1) * cw || sigma == 0) return bad("alphabet: m_C does not hold sigma + 1 entries");
+    if (wt_sigma != sigma) return bad("wavelet tree sigma != alphabet sigma");
+    f->sigma = sigma;
+    f->C.resize(sigma + 1);
+    for (uint64_t i = 0; i <= sigma; ++i) f->C[i] = read_packed(Cw, i, cw);
+    if (f->C[sigma] != wt_size) return bad("wavelet tree size != C[sigma]");
+    if (f->C[0] != 0) return bad("C[0] != 0");
+    for (uint64_t i = 0; i < sigma; ++i) if (f->C[i + 1] <= f->C[i]) return bad("C does not increase");
+    f->comp2char.resize(sigma);
+    if (char_size == 0) {                                         // continuous alphabet: comp2char is the identity
+        for (uint64_t i = 0; i < sigma; ++i) f->comp2char[i] = i;
+    } else {
+        // sd_vector: the j-th one sits at ((its position in high) - j) << wl | low[j] (sd_vector.hpp:192-230)
+        if (wl == 0 || low_w != wl || low_bits != sigma * (uint64_t)wl) return bad("alphabet: sd_vector low part");
+        uint64_t j = 0;
+        for (uint64_t i = 0; i < high_bits; ++i) {
+            if (!((high[i >> 3] >> (i & 7)) & 1)) continue;
+            if (j == sigma) return bad("alphabet: sd_vector holds more ones than sigma");
+            const uint64_t hi_part = i - j;
+            if (wl < 64 && hi_part >> (64 - wl)) return bad("alphabet: sd_vector position overflows");
+            f->comp2char[j] = (hi_part << wl) | read_packed(low, j, wl);
+            ++j;
+        }
+        if (j != sigma) return bad("alphabet: sd_vector holds fewer ones than sigma");
+        for (uint64_t i = 1; i < sigma; ++i) if (f->comp2char[i] <= f->comp2char[i - 1]) return bad("alphabet: symbols do not increase");
+        if (f->comp2char[sigma - 1] >= char_size) return bad("alphabet: a symbol beyond the sd_vector's size");
+    }
+    if (f->comp2char[0] != 0) return bad("alphabet: the sentinel 0 is missing");
+    const uint64_t largest = f->comp2char[sigma - 1];
+    const uint32_t want_levels = bit_width64(largest ? largest : 1);
+    if (f->max_level != want_levels) return bad("max_level " + std::to_string(f->max_level) + " does not match the largest symbol (" + std::to_string(want_levels) + " levels)");
+    if (f->tree_bits / f->max_level != n || f->tree_bits % f->max_level) return bad("tree size != size * max_level");
+    if (largest > 0xFFFFFFFFull) return fail(VLG_E_UNSUPPORTED, "symbol " + std::to_string(largest) + " >= 2^32: the device index holds uint32_t symbols (map the text first: vlg_symbol_map_*)");
+    // density: t_dens is a template parameter, not stored; n_samples = ceil(n / dens) must hold for the given value
+    f->dens = sa_sample_dens ? sa_sample_dens : 32;
+    if (n_samples != (n + f->dens - 1) / f->dens) return bad("SA sample density does not match the file");
+    f->samples.resize(n_samples);
+    for (uint64_t i = 0; i < n_samples; ++i) {
+        f->samples[i] = read_packed(sw_words, i, sw);
+        if (f->samples[i] >= n) return bad("an SA sample is not below n");
+    }
+    // ISA samples: (n - 1) / t_inv_dens + 1 of them for some t_inv_dens >= 1 (their values are not used)
+    const uint64_t isa = ibits / iw;
+    const uint64_t k = isa > 1 ? (n - 1) / (isa - 1) : n;
+    if (isa == 0 || isa > n || k == 0 || (n - 1) / k + 1 != isa) return bad("ISA sample count fits no density for n = " + std::to_string(n));
+    *out = holder.release();
+    return VLG_OK;
+}
+
+}  // namespace
+
+extern "C" vlg_status vlg_sdsl_int_file_open(const char* path, uint32_t sa_sample_dens, int bv_kind, vlg_sdsl_int_file** out)
+{
+    using namespace vlg;
+    if (!path || !out) return fail(VLG_E_INVALID, "null argument");
+    *out = nullptr;
+    if (bv_kind != VLG_BV_PLAIN && bv_kind != VLG_BV_RRR63) return fail(VLG_E_INVALID, "unknown bit-vector kind");
+    try { return sdsl_int_file_open_impl(path, sa_sample_dens, bv_kind, out); }
+    catch (const std::bad_alloc&) { return fail(VLG_E_OOM, "out of host memory while reading the index file"); }
+    catch (const std::exception& e) { return fail(VLG_E_INVALID, std::string("not a csa_wt<wt_int<>> file (") + e.what() + ")"); }
+}
+
+extern "C" vlg_status vlg_sdsl_int_file_parts(const vlg_sdsl_int_file* f, vlg_int_index_parts* p)
+{
+    using namespace vlg;
+    if (!f || !p) return fail(VLG_E_INVALID, "null argument");
+    p->n = f->n; p->sigma = f->sigma; p->max_level = f->max_level; p->sa_sample_dens = f->dens;
+    p->comp2char = f->comp2char.data(); p->C = f->C.data();
+    p->tree_words = f->tree.data(); p->tree_bits = f->tree_bits;
+    p->sa_samples = f->samples.data(); p->n_samples = f->samples.size();
+    return VLG_OK;
+}
+
+extern "C" void vlg_sdsl_int_file_close(vlg_sdsl_int_file* f) { delete f; }
+
+extern "C" vlg_status vlg_index_load_sdsl_int(const char* path, uint32_t sa_sample_dens, int bv_kind, vlg_index** out)
+{
+    if (!out) return vlg::fail(VLG_E_INVALID, "null argument");
+    *out = nullptr;
+    vlg_sdsl_int_file* f = nullptr;
+    if (vlg_status st = vlg_sdsl_int_file_open(path, sa_sample_dens, bv_kind, &f)) return st;
+    vlg_int_index_parts p;
+    vlg_sdsl_int_file_parts(f, &p);
+    vlg_index* plain = nullptr;
+    vlg_status st = vlg_index_from_int_parts(&p, &plain);
+    vlg_sdsl_int_file_close(f);
+    if (st || bv_kind == VLG_BV_PLAIN) { *out = plain; return st; }
+    // a stock wt_int<rrr_vector<63>>: its blocks were decoded on the host; the device index keeps its levels rrr-coded in its own numbering
+    st = vlg_index_compress(plain, VLG_BV_RRR63, out);
+    vlg_index_destroy(plain);
+    return st;
+}
+
+namespace {
+
+// sd_vector<>(bit_vector with ones at the sorted symbols), sd_vector.hpp:192-230: m = sigma ones in largest + 1 bits
+void write_sd_vector(Sink& out, const std::vector<uint64_t>& sym)
+{
+    const uint64_t size = sym.back() + 1, m = sym.size();
+    uint8_t logm = (uint8_t)(hi_bit(m) + 1);
+    const uint8_t logn = (uint8_t)(hi_bit(size) + 1);
+    if (logm == logn) --logm;
+    const uint8_t wl = logn - logm;
+    std::vector<uint64_t> lowv(m), high((m + (1ull << logm) + 63) / 64 + 1, 0);
+    for (uint64_t j = 0; j < m; ++j) {
+        lowv[j] = sym[j] & ((1ull << wl) - 1);
+        const uint64_t pos = (sym[j] >> wl) + j;
+        high[pos >> 6] |= 1ull << (pos & 63);
+    }
+    const uint64_t high_bits = m + (1ull << logm);
+    out.put<uint64_t>(size);
+    out.put<uint8_t>(wl);
+    out.int_vector_packed(lowv, wl, true);
+    out.bit_vector_words(high.data(), high_bits);
+    write_select_mcl(out, high.data(), high_bits, true);
+    write_select_mcl(out, high.data(), high_bits, false);
+}
+
+}  // namespace
+
+extern "C" vlg_status vlg_index_save_sdsl_int(const vlg_index* idx, const char* path, uint32_t isa_inv_dens)
+{
+    using namespace vlg;
+    if (!idx || !path) return fail(VLG_E_INVALID, "null argument");
+    if (!idx->is_int) return fail(VLG_E_INVALID, "vlg_index_save_sdsl_int needs an integer-alphabet index (vlg_index_save_sdsl stores a byte index)");
+    if (idx->ihdr.sampling != kSamplingSaOrder)
+        return fail(VLG_E_UNSUPPORTED, "the file type has sa_order_sa_sampling: resample the text-order index to SA order first (vlg_index_resample)");
+    if (!isa_inv_dens) isa_inv_dens = 64;
+    try {
+        const uint64_t n = idx->ihdr.n, dens = idx->ihdr.dens, n_samples = idx->ihdr.n_samples;
+        uint64_t sigma = 0;
+        if (vlg_status st = vlg_index_export_int_alphabet(idx, &sigma, nullptr, nullptr)) return st;
+        std::vector<uint64_t> C(sigma + 1), c2c(sigma);
+        if (vlg_status st = vlg_index_export_int_alphabet(idx, &sigma, C.data(), c2c.data())) return st;
+        uint32_t L = 0;
+        if (vlg_status st = vlg_index_export_int_tree(idx, &L, nullptr)) return st;
+        const uint64_t tree_bits = n * L;
+        std::vector<uint64_t> tree((tree_bits + 63) / 64 + 1, 0);
+        if (vlg_status st = vlg_index_export_int_tree(idx, &L, tree.data())) return st;
+        std::vector<uint32_t> s32(n_samples);
+        VLG_HIP_TRY(hipMemcpy(s32.data(), idx->iview.samples, n_samples * 4, hipMemcpyDeviceToHost));
+        std::vector<uint64_t> samples(s32.begin(), s32.end());
+        std::vector<uint64_t> isa((n - 1) / isa_inv_dens + 1);
+        if (vlg_status st = vlg_index_isa_samples(idx, isa_inv_dens, isa.data(), isa.size())) return st;
+        (void)dens;
+        FILE* fp = fopen(path, "wb");
+        if (!fp) return fail(VLG_E_INVALID, std::string("cannot create ") + path);
+        Sink out{fp};
+        // ---- wt_int::serialize (wt_int.hpp:708-732) -------------------------------------------------------------------------------
+        out.put<uint64_t>(n);
+        out.put<uint64_t>(sigma);                                  // distinct values = leaves of the tree
+        out.bit_vector_words(tree.data(), tree_bits);
+        write_rank_support_v(out, tree.data(), tree_bits);
+        write_select_mcl(out, tree.data(), tree_bits, true);
+        write_select_mcl(out, tree.data(), tree_bits, false);
+        out.put<uint32_t>(L);
+        // ---- SA samples, ISA samples: int_vector<0> of width hi(n)+1 (csa_sampling_strategy.hpp:85-98, 626-642) ------------------------
+        const uint8_t w = (uint8_t)(hi_bit(n) + 1);
+        out.int_vector_packed(samples, w, true);
+        out.int_vector_packed(isa, w, true);
+        // ---- int_alphabet<sd_vector<>> (csa_alphabet_strategy.hpp:578-587) ---------------------------------------------------------
+        if (c2c.back() + 1 == sigma) {                             // continuous: m_char stays a default sd_vector<>
+            out.put<uint64_t>(0);                                  // size
+            out.put<uint8_t>(0);                                   // wl
+            out.put<uint64_t>(0); out.put<uint8_t>(64);            // low: an empty int_vector<> has width 64 (int_vector.hpp:147-154)
+            out.put<uint64_t>(0);                                  // high
+            out.put<uint64_t>(0); out.put<uint64_t>(0);            // select_1, select_0 of no ones / zeros
+        } else {
+            write_sd_vector(out, c2c);
+        }
+        out.int_vector_packed(C, w, true);                         // m_C: width hi(n)+1 (:520)
+        out.put<uint64_t>(sigma);
+        const bool ok = out.ok;
+        if (fclose(fp) != 0 || !ok) return fail(VLG_E_INVALID, std::string("write failed: ") + path);
+        return VLG_OK;
+    }
+    catch (const std::bad_alloc&) { return fail(VLG_E_OOM, "out of host memory while writing the index file"); }
 }

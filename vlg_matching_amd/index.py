@@ -115,6 +115,26 @@ def read_sdsl_file(path, dens=32, rrr=False):
         lib().vlg_sdsl_file_close(f)
 
 
+def read_sdsl_int_file(path, dens=32, rrr=False):
+    """Host-only parse of a stock sdsl csa_wt<wt_int<>, dens, ., sa_order_sa_sampling<>, isa_sampling<>, int_alphabet<>> file (rrr: over
+    wt_int<rrr_vector<63>>, its blocks decoded back to plain bits) -> dict: n, sigma, max_level, dens, comp2char, C, tree_bits,
+    tree_words (wt_int::tree, level l = bits [l * n, (l + 1) * n)), samples."""
+    f = C.c_void_p()
+    check(lib().vlg_sdsl_int_file_open(str(path).encode(), dens, 1 if rrr else 0, C.byref(f)))
+    try:
+        p = capi.IntIndexParts()
+        check(lib().vlg_sdsl_int_file_parts(f, C.byref(p)))
+        nw = (p.tree_bits + 63) // 64
+
+        def u64(ptr, count):
+            return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint64)), shape=(max(count, 1),))[:count].copy()
+        return {"n": int(p.n), "sigma": int(p.sigma), "max_level": int(p.max_level), "dens": int(p.sa_sample_dens),
+                "comp2char": u64(p.comp2char, p.sigma), "C": u64(p.C, p.sigma + 1), "tree_bits": int(p.tree_bits),
+                "tree_words": u64(p.tree_words, nw), "samples": u64(p.sa_samples, p.n_samples)}
+    finally:
+        lib().vlg_sdsl_int_file_close(f)
+
+
 class Workspace:
     def __init__(self, max_hbm_bytes=0, stream=None):
         h = C.c_void_p()
@@ -375,9 +395,45 @@ class VlgIndex:
         check(lib().vlg_index_load_sdsl_kind(str(path).encode(), dens, 1 if rrr else 0, C.byref(h)))
         return cls(h)
 
-    def save_sdsl(self, path):
-        """Store in the reference's on-disk format of csa_wt<wt_huff<>,32,64> (stock sdsl can load_from_file it)."""
-        check(lib().vlg_index_save_sdsl(self._h, str(path).encode()))
+    @classmethod
+    def load_sdsl_int(cls, path, dens=32, rrr=False):
+        """An integer index stored by stock sdsl: a csa_wt<wt_int<>, dens, ., ., ., int_alphabet<>> file, or (rrr) one over
+        wt_int<rrr_vector<63>>; the level-wise tree is converted to this library's wavelet matrix on the device."""
+        h = C.c_void_p()
+        check(lib().vlg_index_load_sdsl_int(str(path).encode(), dens, 1 if rrr else 0, C.byref(h)))
+        return cls(h)
+
+    @classmethod
+    def from_int_parts(cls, p):
+        """An integer index from the members of a csa_wt<wt_int<>> file (dict as read_sdsl_int_file returns it)."""
+        c2c = np.ascontiguousarray(p["comp2char"], dtype=np.uint64)
+        Cc = np.ascontiguousarray(p["C"], dtype=np.uint64)
+        tw = np.ascontiguousarray(p["tree_words"], dtype=np.uint64)
+        smp = np.ascontiguousarray(p["samples"], dtype=np.uint64)
+        parts = capi.IntIndexParts(int(p["n"]), int(p["sigma"]), int(p["max_level"]), int(p.get("dens", 32)), c2c.ctypes.data, Cc.ctypes.data,
+                                   tw.ctypes.data if len(tw) else None, int(p["tree_bits"]), smp.ctypes.data if len(smp) else None, len(smp))
+        h = C.c_void_p()
+        check(lib().vlg_index_from_int_parts(C.byref(parts), C.byref(h)))
+        return cls(h)
+
+    def save_sdsl(self, path, isa_dens=64):
+        """Store in the reference's on-disk format (stock sdsl can load_from_file it): csa_wt<wt_huff<>,32,64> for a byte index,
+        csa_wt<wt_int<>, dens, isa_dens, ., ., int_alphabet<>> for an integer one (plain or rrr, SA order, any dens)."""
+        if self.info()["bv_kind"] in (2, 3):
+            check(lib().vlg_index_save_sdsl_int(self._h, str(path).encode(), int(isa_dens)))
+        else:
+            if isa_dens != 64:
+                raise ValueError("a byte index is stored as csa_wt<wt_huff<>,32,64>: its ISA density is 64")
+            check(lib().vlg_index_save_sdsl(self._h, str(path).encode()))
+
+    def int_tree(self):
+        """wt_int::tree of an integer index, converted on the device -> (max_level, uint64 words of n * max_level bits)"""
+        L = C.c_uint32()
+        check(lib().vlg_index_export_int_tree(self._h, C.byref(L), None))
+        n = self.info()["n"]
+        w = np.zeros((n * L.value + 63) // 64 + 1, np.uint64)
+        check(lib().vlg_index_export_int_tree(self._h, C.byref(L), w.ctypes.data))
+        return int(L.value), w[: (n * L.value + 63) // 64]
 
     def isa_samples(self, inv_dens=64):
         """isa_sample of csa_wt: out[j] = SA index of text position j * inv_dens.  Byte or integer alphabet, plain or rrr; the index
