@@ -345,6 +345,28 @@ vlg_status vlg_locate_batch(const vlg_index* idx, const uint64_t* d_l, const uin
                             const uint64_t* d_out_off, uint64_t n_patterns, uint64_t total,
                             uint64_t* d_out, void* stream);
 
+/* Text access: the index keeps no text, but a self-index can give it back.  A vlg_text_access holds, in HBM, the ISA samples of one
+ * index -- isa_sample of csa_wt (m_isa_sample, t_inv_dens: include/sdsl/csa_wt.hpp:145-151; csa_sampling_strategy.hpp:626-642):
+ * ISA[0], ISA[d], ISA[2d], ..., 4 bytes each when n < 2^32, else 8 -- computed on the device like vlg_index_isa_samples.  It does not
+ * change idx, which must outlive it.  SA-order indexes only (byte or integer, plain or rrr, any SA density including 1); a text-order
+ * index gives VLG_E_UNSUPPORTED (the reference derives its ISA through the marks, which needs a select structure).
+ * inv_dens = 0 means 64, the reference's t_inv_dens default.  Creation walks n LF steps in all and synchronises `stream`. */
+typedef struct vlg_text_access vlg_text_access;
+vlg_status vlg_text_access_create(const vlg_index* idx, uint32_t inv_dens, void* stream, vlg_text_access** out);
+void vlg_text_access_destroy(vlg_text_access* t);
+/* sdsl::extract(csa, begin, end) (include/sdsl/suffix_array_algorithm.hpp:645-745, the lf_tag specialisation; csa.text[i] --
+ * text_of_csa, suffix_array_helper.hpp:641 -- is the range [i, i]) for every range r: inclusive ends, begin[r] <= end[r] < n (n = |text| + 1: position n - 1 is the sentinel and extracts
+ * as 0).  Range r is written to d_out from d_out_off[r] on (the exclusive prefix sum of the lengths end - begin + 1; every range must
+ * end within `total` elements).  d_out holds uint8_t for a byte index, uint32_t ORIGINAL symbols (comp2char applied) for an integer
+ * one.  Each range is cut at the multiples of d and one lane walks each piece backward from an ISA sample: at most d LF steps per
+ * lane, however long the range.  The ranges are checked on the device first: any bad range gives VLG_E_INVALID and nothing is
+ * written.  Synchronises `stream`. */
+vlg_status vlg_extract_batch(const vlg_text_access* t, const uint64_t* d_begin, const uint64_t* d_end, const uint64_t* d_out_off,
+                             uint64_t n_ranges, uint64_t total, void* d_out, void* stream);
+/* csa.isa[i] (include/sdsl/csa_wt.hpp:149; isa_of_csa_wt::operator[], suffix_array_helper.hpp:500-514, from
+ * isa_sample.sample_qeq, csa_sampling_strategy.hpp:650-663): d_out[j] = ISA[d_i[j]], fewer than d LF steps from the next sample.  A position >= n gives VLG_E_INVALID (d_out is then undefined).  Synchronises `stream`. */
+vlg_status vlg_isa_batch(const vlg_text_access* t, const uint64_t* d_i, uint64_t* d_out, uint64_t count, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Query batches.  Parsing mirrors the reference's two dialects:
  *   VLG_DIALECT_LIBRARY   gapped_pattern_query(const std::string&)   include/sdsl/vlg_index.hpp:54-105

@@ -132,6 +132,10 @@ SYMBOLS = [
     ("vlg_backward_search_batch", _I, [_P, _P, _P, _U64, _P, _P, _P]),
     ("vlg_sa_batch", _I, [_P, _P, _P, _U64, _P]),
     ("vlg_locate_batch", _I, [_P, _P, _P, _P, _U64, _U64, _P, _P]),
+    ("vlg_text_access_create", _I, [_P, C.c_uint32, _P, C.POINTER(_P)]),
+    ("vlg_text_access_destroy", None, [_P]),
+    ("vlg_extract_batch", _I, [_P, _P, _P, _P, _U64, _U64, _P, _P]),
+    ("vlg_isa_batch", _I, [_P, _P, _P, _U64, _P]),
     ("vlg_parse_query", _I, [C.c_char_p, _U64, _I, C.POINTER(ParsedQuery)]),
     ("vlg_queries_parse", _I, [C.c_char_p, _P, _U64, _I, _P, C.POINTER(_P)]),
     ("vlg_queries_create", _I, [_P, _P, _P, _P, _P, _P, _U64, C.POINTER(_P)]),

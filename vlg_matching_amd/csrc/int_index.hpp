@@ -21,6 +21,7 @@
 // Limits: symbols are uint32_t, none of them 0 (construct() refuses a 0 symbol: include/sdsl/construct.hpp:36-45); n <= 2^32 / 5
 // (the suffix sorter sees five bytes per symbol).
 #pragma once
+#include "extract.hpp"
 
 namespace {
 
@@ -582,13 +583,42 @@ __global__ void __launch_bounds__(256) int_sa_expand_kernel(IntView v, uint32_t*
     stage_int(sZ, v);
     int_walk_from_samples(v, sZ, [&](uint64_t i, uint64_t x) { sa[i] = (uint32_t)x; });
 }
-// isa_sample[SA[i] / inv_dens] = i for every i with SA[i] % inv_dens == 0 (csa_sampling_strategy.hpp:626-642)
+// isa_sample[SA[i] / inv_dens] = i for every i with SA[i] % inv_dens == 0 (csa_sampling_strategy.hpp:626-642); n < 2^32: 4-byte samples
 template <class BV>
-__global__ void __launch_bounds__(256) int_isa_samples_kernel(IntView v, uint32_t inv_dens, uint64_t* __restrict__ out)
+__global__ void __launch_bounds__(256) int_isa_samples_kernel(IntView v, uint32_t inv_dens, uint32_t* __restrict__ out)
 {
     __shared__ IntLds<BV> sZ;
     stage_int(sZ, v);
-    int_walk_from_samples(v, sZ, [&](uint64_t i, uint64_t x) { if (x % inv_dens == 0) out[x / inv_dens] = i; });
+    int_walk_from_samples(v, sZ, [&](uint64_t i, uint64_t x) { if (x % inv_dens == 0) out[x / inv_dens] = (uint32_t)i; });
+}
+
+// ---- text access (extract.hpp): sdsl::extract and csa.isa[i] on the wavelet matrix ---------------------------------------------------
+template <class BV>
+struct IntWalk {
+    const IntView& v;
+    const IntLds<BV>& sZ;
+    __device__ __forceinline__ uint64_t lf(uint64_t i, uint32_t& c) const
+    {
+        uint32_t n_lv = 0;
+        if (!v.n_levels) { c = 0; return 0; }                // degenerate: only the sentinel exists (n = 1)
+        return int_lf(v, sZ, i, c, n_lv);
+    }
+    __device__ __forceinline__ uint32_t sym(uint32_t c) const { return v.comp2char[c]; }      // (sigma up to 2^32: not staged)
+};
+template <class BV>
+__global__ void __launch_bounds__(256) int_extract_kernel(IntView v, ExtractJob job, const uint32_t* __restrict__ isa, uint32_t* __restrict__ out)
+{
+    __shared__ IntLds<BV> sZ;
+    stage_int(sZ, v);
+    extract_segments(job, isa, out, IntWalk<BV>{v, sZ});
+}
+template <class BV>
+__global__ void __launch_bounds__(256) int_isa_kernel(IntView v, uint32_t d, const uint32_t* __restrict__ isa, const uint64_t* __restrict__ p,
+                                                      uint64_t* __restrict__ out, uint64_t count, unsigned long long* __restrict__ bad)
+{
+    __shared__ IntLds<BV> sZ;
+    stage_int(sZ, v);
+    isa_queries(p, out, count, v.n, d, isa, IntWalk<BV>{v, sZ}, bad);
 }
 
 }  // namespace
@@ -920,12 +950,31 @@ vlg_status launch_int_sa_expand(const IntView& v, uint32_t* d_sa, hipStream_t st
 }
 
 // isa_sample of an SA-order integer index into d_out ((n - 1) / inv_dens + 1 words): vlg_index_isa_samples
-vlg_status launch_int_isa_samples(const IntView& v, uint32_t inv_dens, uint64_t* d_out, hipStream_t st)
+vlg_status launch_int_isa_samples(const IntView& v, uint32_t inv_dens, uint32_t* d_out, hipStream_t st)
 {
     if (v.sampling != kSamplingSaOrder || !inv_dens) return fail(VLG_E_INTERNAL, "integer index: ISA samples need SA-order samples");
     const dim3 grid(grid_for(v.n_samples, 8192));
     if (v.bv_kind == kBvRrr63) hipLaunchKernelGGL(HIP_KERNEL_NAME(int_isa_samples_kernel<RrrBV>), grid, dim3(256), 0, st, v, inv_dens, d_out);
     else hipLaunchKernelGGL(HIP_KERNEL_NAME(int_isa_samples_kernel<PlainBV>), grid, dim3(256), 0, st, v, inv_dens, d_out);
+    VLG_HIP_TRY(hipGetLastError());
+    return VLG_OK;
+}
+
+vlg_status launch_int_extract(const IntView& v, const ExtractJob& job, const uint32_t* d_isa, uint32_t* d_out, hipStream_t st)
+{
+    const dim3 grid(grid_for(job.n_segs, 8192));
+    if (v.bv_kind == kBvRrr63) hipLaunchKernelGGL(HIP_KERNEL_NAME(int_extract_kernel<RrrBV>), grid, dim3(256), 0, st, v, job, d_isa, d_out);
+    else hipLaunchKernelGGL(HIP_KERNEL_NAME(int_extract_kernel<PlainBV>), grid, dim3(256), 0, st, v, job, d_isa, d_out);
+    VLG_HIP_TRY(hipGetLastError());
+    return VLG_OK;
+}
+
+vlg_status launch_int_isa(const IntView& v, uint32_t d, const uint32_t* d_isa, const uint64_t* d_i, uint64_t* d_out, uint64_t count,
+                          unsigned long long* d_bad, hipStream_t st)
+{
+    const dim3 grid(grid_for(count, 8192));
+    if (v.bv_kind == kBvRrr63) hipLaunchKernelGGL(HIP_KERNEL_NAME(int_isa_kernel<RrrBV>), grid, dim3(256), 0, st, v, d, d_isa, d_i, d_out, count, d_bad);
+    else hipLaunchKernelGGL(HIP_KERNEL_NAME(int_isa_kernel<PlainBV>), grid, dim3(256), 0, st, v, d, d_isa, d_i, d_out, count, d_bad);
     VLG_HIP_TRY(hipGetLastError());
     return VLG_OK;
 }

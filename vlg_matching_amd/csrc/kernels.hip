@@ -6,6 +6,7 @@
 #include "common.hpp"
 #include "device_rank.hpp"
 #include "kernels.hpp"
+#include "extract.hpp"
 #include <rocprim/rocprim.hpp>
 
 using namespace vlg;
@@ -1308,8 +1309,8 @@ __global__ void __launch_bounds__(256) unsample_tail_kernel(IndexView iv, const 
 // ISA samples (csa_sampling_strategy.hpp:626-642: isa_sample[SA[i] / d'] = i for every i with SA[i] % d' == 0), computed from the
 // index alone: a lane starts at one SA sample (i, SA[i]) and walks LF -- (LF(i), SA[i] - 1) -- until the next sampled
 // index, so every SA index is visited exactly once and every text position passes by with its SA index.
-template <class BV, typename pos_t>
-__global__ void __launch_bounds__(256) isa_samples_kernel(IndexView iv, uint32_t inv_dens, uint64_t* __restrict__ out)
+template <class BV, typename pos_t, typename out_t>
+__global__ void __launch_bounds__(256) isa_samples_kernel(IndexView iv, uint32_t inv_dens, out_t* __restrict__ out)
 {
     __shared__ WalkLds<BV> s;
     stage_walk(s, iv);
@@ -1317,7 +1318,7 @@ __global__ void __launch_bounds__(256) isa_samples_kernel(IndexView iv, uint32_t
     for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < iv.n_samples; j += (uint64_t)gridDim.x * blockDim.x) {
         uint64_t i = j * iv.dens, v = samples[j];
         do {
-            if (v % inv_dens == 0) out[v / inv_dens] = i;
+            if (v % inv_dens == 0) out[v / inv_dens] = (out_t)i;
             uint32_t node = 0, c;
             uint64_t pos = i;
             for (;;) {                                       // inverse_select: wt_pc.hpp:385-402
@@ -1333,6 +1334,62 @@ __global__ void __launch_bounds__(256) isa_samples_kernel(IndexView iv, uint32_t
             i = s.C[c] + pos;                                // LF
             v = v ? v - 1 : iv.n - 1;
         } while (i % iv.dens);
+    }
+}
+
+// ---- text access (extract.hpp): sdsl::extract and csa.isa[i] on the Huffman-shaped tree -----------------------------------------------
+template <class BV, bool kWide>
+struct ByteWalk {
+    const IndexView& iv;
+    const WalkLds<BV>& s;
+    const uint8_t* c2c;                                      // comp2char in LDS
+    __device__ __forceinline__ uint64_t lf(uint64_t i, uint32_t& c) const
+    {
+        if (iv.sigma == 1) { c = 0; return 0; }              // degenerate: only the sentinel exists (n = 1)
+        uint32_t n_lv = 0;
+        return lf_step<BV, kWide>(iv, s, i, c, n_lv);
+    }
+    __device__ __forceinline__ uint8_t sym(uint32_t c) const { return c2c[c]; }
+};
+
+template <class BV, bool kWide, typename isa_t>
+__global__ void __launch_bounds__(256) extract_kernel(IndexView iv, ExtractJob job, const isa_t* __restrict__ isa, const uint8_t* __restrict__ comp2char,
+                                                      uint8_t* __restrict__ out)
+{
+    __shared__ WalkLds<BV> s;
+    __shared__ uint8_t c2c[256];
+    c2c[threadIdx.x] = comp2char[threadIdx.x];             // (256 threads; stage_walk's barrier covers it)
+    stage_walk(s, iv);
+    extract_segments(job, isa, out, ByteWalk<BV, kWide>{iv, s, c2c});
+}
+
+template <class BV, bool kWide, typename isa_t>
+__global__ void __launch_bounds__(256) isa_kernel(IndexView iv, uint32_t d, const isa_t* __restrict__ isa, const uint64_t* __restrict__ p,
+                                                  uint64_t* __restrict__ out, uint64_t count, unsigned long long* __restrict__ bad)
+{
+    __shared__ WalkLds<BV> s;
+    stage_walk(s, iv);
+    isa_queries(p, out, count, iv.n, d, isa, ByteWalk<BV, kWide>{iv, s, nullptr}, bad);
+}
+
+// comp2char of a byte index from its char2comp (comp 0 is the sentinel; absent characters map to 0 and are skipped)
+__global__ void comp2char_kernel(const uint8_t* __restrict__ char2comp, uint8_t* __restrict__ c2c)
+{
+    const uint32_t ch = threadIdx.x, c = char2comp[ch];
+    if (ch == 0 || c != 0) c2c[c] = (uint8_t)ch;
+}
+
+// segment counts of the ranges of an extract batch (a bad range counts 0 and raises *bad): seg[r] = e / d - b / d + 1, seg[n_ranges] = 0
+__global__ void extract_check_kernel(const uint64_t* __restrict__ begin, const uint64_t* __restrict__ end, const uint64_t* __restrict__ out_off,
+                                     uint64_t n_ranges, uint64_t n, uint64_t total, uint32_t d, uint64_t* __restrict__ seg,
+                                     unsigned long long* __restrict__ bad)
+{
+    for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r <= n_ranges; r += (uint64_t)gridDim.x * blockDim.x) {
+        if (r == n_ranges) { seg[r] = 0; continue; }
+        const uint64_t b = begin[r], e = end[r], o = out_off[r];
+        const bool ok = b <= e && e < n && o <= total && e - b + 1 <= total - o;
+        seg[r] = ok ? e / d - b / d + 1 : 0;
+        if (!ok) atomicAdd(bad, 1ull);
     }
 }
 
@@ -1812,27 +1869,197 @@ extern "C" vlg_status vlg_locate_batch(const vlg_index* idx, const uint64_t* d_l
     return VLG_OK;
 }
 
+namespace {
+// ISA samples of an SA-order index into d_out: (n - 1) / inv_dens + 1 entries of isa_sample_bytes(n) bytes
+vlg_status isa_samples_device(const vlg_index* idx, uint32_t inv_dens, void* d_out, hipStream_t st)
+{
+    const uint64_t n = idx->hdr.n;
+    if (idx->hdr.sampling != kSamplingSaOrder) return fail(VLG_E_UNSUPPORTED, "ISA samples are computed from an SA-order index");
+    const uint64_t count = (n - 1) / inv_dens + 1;
+    const uint32_t w = isa_sample_bytes(n);
+    VLG_HIP_TRY(hipMemsetAsync(d_out, 0, count * w, st));
+    if (idx->is_int)                                               // the walk on the wavelet matrix (int_index.hpp), plain or rrr levels
+        return launch_int_isa_samples(idx->iview, inv_dens, (uint32_t*)d_out, st);
+    const dim3 grid(grid_for(idx->view.n_samples, 8192));
+    const bool rrr = idx->view.bv_kind == kBvRrr63, wide = idx->hdr.sample_bytes == 8;
+#define VLG_ISA_SAMPLES(BV_, POS_, OUT_) \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(isa_samples_kernel<BV_, POS_, OUT_>), grid, dim3(256), 0, st, idx->view, inv_dens, (OUT_*)d_out)
+    if (w == 8) {
+        if (rrr && wide) VLG_ISA_SAMPLES(RrrBV, uint64_t, uint64_t);
+        else if (rrr) VLG_ISA_SAMPLES(RrrBV, uint32_t, uint64_t);
+        else if (wide) VLG_ISA_SAMPLES(PlainBV, uint64_t, uint64_t);
+        else VLG_ISA_SAMPLES(PlainBV, uint32_t, uint64_t);
+    } else {
+        if (rrr && wide) VLG_ISA_SAMPLES(RrrBV, uint64_t, uint32_t);
+        else if (rrr) VLG_ISA_SAMPLES(RrrBV, uint32_t, uint32_t);
+        else if (wide) VLG_ISA_SAMPLES(PlainBV, uint64_t, uint32_t);
+        else VLG_ISA_SAMPLES(PlainBV, uint32_t, uint32_t);
+    }
+#undef VLG_ISA_SAMPLES
+    VLG_HIP_TRY(hipGetLastError());
+    return VLG_OK;
+}
+}  // namespace
+
 extern "C" vlg_status vlg_index_isa_samples(const vlg_index* idx, uint32_t inv_dens, uint64_t* h_out, uint64_t count)
 {
     if (!idx || !h_out || !inv_dens) return fail(VLG_E_INVALID, "null argument");
     const uint64_t n = idx->hdr.n;
     if (count != (n - 1) / inv_dens + 1) return fail(VLG_E_INVALID, "ISA sample count must be (n-1)/inv_dens + 1");
     if (idx->hdr.sampling != kSamplingSaOrder) return fail(VLG_E_UNSUPPORTED, "ISA samples are computed from an SA-order index");
+    const uint32_t w = isa_sample_bytes(n);
     uint64_t* d_out = nullptr;
-    VLG_HIP_TRY(hipMalloc((void**)&d_out, count * 8));
-    VLG_HIP_TRY(hipMemset(d_out, 0, count * 8));
-    const dim3 grid(grid_for(idx->view.n_samples, 8192));
-    const bool rrr = idx->view.bv_kind == kBvRrr63, wide = idx->hdr.sample_bytes == 8;
-    if (idx->is_int) {                                             // the walk on the wavelet matrix (int_index.hpp), plain or rrr levels
-        const vlg_status s = launch_int_isa_samples(idx->iview, inv_dens, d_out, nullptr);
-        if (s) { (void)hipFree(d_out); return s; }
-    } else if (rrr && wide) hipLaunchKernelGGL(HIP_KERNEL_NAME(isa_samples_kernel<RrrBV, uint64_t>), grid, dim3(256), 0, nullptr, idx->view, inv_dens, d_out);
-    else if (rrr) hipLaunchKernelGGL(HIP_KERNEL_NAME(isa_samples_kernel<RrrBV, uint32_t>), grid, dim3(256), 0, nullptr, idx->view, inv_dens, d_out);
-    else if (wide) hipLaunchKernelGGL(HIP_KERNEL_NAME(isa_samples_kernel<PlainBV, uint64_t>), grid, dim3(256), 0, nullptr, idx->view, inv_dens, d_out);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(isa_samples_kernel<PlainBV, uint32_t>), grid, dim3(256), 0, nullptr, idx->view, inv_dens, d_out);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpy(h_out, d_out, count * 8, hipMemcpyDeviceToHost);
+    VLG_HIP_TRY(hipMalloc((void**)&d_out, count * (8 + w)));          // the samples as the device keeps them, then widened
+    void* d_smp = d_out + count;
+    vlg_status s = isa_samples_device(idx, inv_dens, d_smp, nullptr);
+    if (!s) s = w == 8 ? (hipMemcpyAsync(d_out, d_smp, count * 8, hipMemcpyDeviceToDevice, nullptr) == hipSuccess ? VLG_OK : VLG_E_NO_DEVICE)
+                       : launch_widen<uint32_t>((const uint32_t*)d_smp, d_out, count, nullptr);
+    hipError_t e = s ? hipSuccess : hipMemcpy(h_out, d_out, count * 8, hipMemcpyDeviceToHost);
     (void)hipFree(d_out);
+    if (s) return s == VLG_E_NO_DEVICE ? fail(s, "ISA samples: device copy failed") : s;
     VLG_HIP_TRY(e);
+    return VLG_OK;
+}
+
+// ---- text access: sdsl::extract, csa.text[i], csa.isa[i] (extract.hpp) ----------------------------------------------------------------
+struct vlg_text_access {
+    const vlg_index* idx = nullptr;
+    uint32_t d = 0;
+    uint32_t isa_bytes = 0;                                        // isa_sample_bytes(n)
+    void* d_isa = nullptr;                                         // ISA[0], ISA[d], ... ((n - 1) / d + 1 entries)
+    uint8_t* d_c2c = nullptr;                                      // byte index: comp2char[256]
+};
+
+extern "C" vlg_status vlg_text_access_create(const vlg_index* idx, uint32_t inv_dens, void* stream, vlg_text_access** out)
+{
+    if (!idx || !out) return fail(VLG_E_INVALID, "null argument");
+    *out = nullptr;
+    if (idx->hdr.sampling != kSamplingSaOrder)
+        return fail(VLG_E_UNSUPPORTED, "text access needs an SA-order index (a text-order index derives its ISA through the marks)");
+    const uint32_t d = inv_dens ? inv_dens : 64;
+    hipStream_t st = (hipStream_t)stream;
+    vlg_text_access* t = new (std::nothrow) vlg_text_access;
+    if (!t) return fail(VLG_E_OOM, "text access handle");
+    t->idx = idx;
+    t->d = d;
+    t->isa_bytes = isa_sample_bytes(idx->hdr.n);
+    const uint64_t count = (idx->hdr.n - 1) / d + 1;
+    vlg_status s = VLG_OK;
+    if (hipMalloc(&t->d_isa, count * t->isa_bytes) != hipSuccess) { t->d_isa = nullptr; s = fail(VLG_E_OOM, "text access: ISA samples"); }
+    if (!s) s = isa_samples_device(idx, d, t->d_isa, st);
+    if (!s && !idx->is_int) {
+        if (hipMalloc((void**)&t->d_c2c, 256) != hipSuccess) { t->d_c2c = nullptr; s = fail(VLG_E_OOM, "text access: comp2char"); }
+        else if (hipMemsetAsync(t->d_c2c, 0, 256, st) != hipSuccess) s = fail(VLG_E_NO_DEVICE, "text access: comp2char");
+        else hipLaunchKernelGGL(comp2char_kernel, dim3(1), dim3(256), 0, st, idx->view.char2comp, t->d_c2c);
+    }
+    if (!s) {
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) s = fail(VLG_E_NO_DEVICE, std::string("text access: ") + hipGetErrorString(e));
+    }
+    if (s) { vlg_text_access_destroy(t); return s; }
+    *out = t;
+    return VLG_OK;
+}
+
+extern "C" void vlg_text_access_destroy(vlg_text_access* t)
+{
+    if (!t) return;
+    if (t->d_isa) (void)hipFree(t->d_isa);
+    if (t->d_c2c) (void)hipFree(t->d_c2c);
+    delete t;
+}
+
+extern "C" vlg_status vlg_extract_batch(const vlg_text_access* t, const uint64_t* d_begin, const uint64_t* d_end, const uint64_t* d_out_off,
+                                        uint64_t n_ranges, uint64_t total, void* d_out, void* stream)
+{
+    if (!t || (n_ranges && (!d_begin || !d_end || !d_out_off || !d_out))) return fail(VLG_E_INVALID, "null argument");
+    if (!n_ranges) return VLG_OK;
+    const vlg_index* idx = t->idx;
+    hipStream_t st = (hipStream_t)stream;
+    // scratch: [0, n_ranges] segment counts scanned in place, then the bad-range counter
+    size_t tb = 0;
+    uint64_t* seg = nullptr;
+    VLG_HIP_TRY(rocprim::exclusive_scan(nullptr, tb, seg, seg, (uint64_t)0, n_ranges + 1, rocprim::plus<uint64_t>(), st));
+    const size_t seg_bytes = align_up((n_ranges + 1) * 8 + 8, 256);
+    VLG_HIP_TRY(hipMalloc((void**)&seg, seg_bytes + tb));
+    unsigned long long* d_bad = reinterpret_cast<unsigned long long*>(seg + n_ranges + 1);
+    void* temp = reinterpret_cast<uint8_t*>(seg) + seg_bytes;
+    uint64_t h[2] = {0, 0};                                        // bad ranges, segments
+    hipError_t e = hipMemsetAsync(d_bad, 0, 8, st);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(extract_check_kernel, dim3(grid_for(n_ranges + 1, 4096)), dim3(256), 0, st, d_begin, d_end, d_out_off, n_ranges, idx->hdr.n,
+                           total, t->d, seg, d_bad);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = rocprim::exclusive_scan(temp, tb, seg, seg, (uint64_t)0, n_ranges + 1, rocprim::plus<uint64_t>(), st);
+    if (e == hipSuccess) e = hipMemcpyAsync(&h[0], d_bad, 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(&h[1], seg + n_ranges, 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    vlg_status s = VLG_OK;
+    if (e != hipSuccess) s = fail(VLG_E_NO_DEVICE, std::string("extract: ") + hipGetErrorString(e));
+    else if (h[0]) s = fail(VLG_E_INVALID, std::to_string(h[0]) + " extract range(s) with begin > end, end >= n, or output beyond total");
+    if (!s) {
+        const ExtractJob job{d_begin, d_end, d_out_off, seg, n_ranges, h[1], idx->hdr.n, t->d};
+        const dim3 grid(grid_for(h[1], 8192));
+        if (idx->is_int) s = launch_int_extract(idx->iview, job, (const uint32_t*)t->d_isa, (uint32_t*)d_out, st);
+        else {
+            const bool rrr = idx->view.bv_kind == kBvRrr63, wide = idx->hdr.sample_bytes == 8, w8 = t->isa_bytes == 8;
+#define VLG_EXTRACT(BV_, W_, ISA_) \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(extract_kernel<BV_, W_, ISA_>), grid, dim3(256), 0, st, idx->view, job, (const ISA_*)t->d_isa, t->d_c2c, (uint8_t*)d_out)
+            if (w8) {                                              // n >= 2^32: SA indices are wide too
+                if (rrr) VLG_EXTRACT(RrrBV, true, uint64_t);
+                else VLG_EXTRACT(PlainBV, true, uint64_t);
+            } else if (rrr && wide) VLG_EXTRACT(RrrBV, true, uint32_t);
+            else if (rrr) VLG_EXTRACT(RrrBV, false, uint32_t);
+            else if (wide) VLG_EXTRACT(PlainBV, true, uint32_t);
+            else VLG_EXTRACT(PlainBV, false, uint32_t);
+#undef VLG_EXTRACT
+            e = hipGetLastError();
+            if (e != hipSuccess) s = fail(VLG_E_NO_DEVICE, std::string("extract: ") + hipGetErrorString(e));
+        }
+        e = hipStreamSynchronize(st);                              // the scratch is freed below
+        if (!s && e != hipSuccess) s = fail(VLG_E_NO_DEVICE, std::string("extract: ") + hipGetErrorString(e));
+    }
+    (void)hipFree(seg);
+    return s;
+}
+
+extern "C" vlg_status vlg_isa_batch(const vlg_text_access* t, const uint64_t* d_i, uint64_t* d_out, uint64_t count, void* stream)
+{
+    if (!t || (count && (!d_i || !d_out))) return fail(VLG_E_INVALID, "null argument");
+    if (!count) return VLG_OK;
+    const vlg_index* idx = t->idx;
+    hipStream_t st = (hipStream_t)stream;
+    unsigned long long* d_bad = nullptr;
+    VLG_HIP_TRY(hipMalloc((void**)&d_bad, 8));
+    unsigned long long h_bad = 0;
+    vlg_status s = VLG_OK;
+    hipError_t e = hipMemsetAsync(d_bad, 0, 8, st);
+    if (e == hipSuccess) {
+        if (idx->is_int) s = launch_int_isa(idx->iview, t->d, (const uint32_t*)t->d_isa, d_i, d_out, count, d_bad, st);
+        else {
+            const dim3 grid(grid_for(count, 8192));
+            const bool rrr = idx->view.bv_kind == kBvRrr63, wide = idx->hdr.sample_bytes == 8, w8 = t->isa_bytes == 8;
+#define VLG_ISA(BV_, W_, ISA_) \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(isa_kernel<BV_, W_, ISA_>), grid, dim3(256), 0, st, idx->view, t->d, (const ISA_*)t->d_isa, d_i, d_out, count, d_bad)
+            if (w8) {
+                if (rrr) VLG_ISA(RrrBV, true, uint64_t);
+                else VLG_ISA(PlainBV, true, uint64_t);
+            } else if (rrr && wide) VLG_ISA(RrrBV, true, uint32_t);
+            else if (rrr) VLG_ISA(RrrBV, false, uint32_t);
+            else if (wide) VLG_ISA(PlainBV, true, uint32_t);
+            else VLG_ISA(PlainBV, false, uint32_t);
+#undef VLG_ISA
+            e = hipGetLastError();
+        }
+    }
+    if (e == hipSuccess && !s) e = hipMemcpyAsync(&h_bad, d_bad, 8, hipMemcpyDeviceToHost, st);
+    const hipError_t e2 = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = e2;
+    (void)hipFree(d_bad);
+    if (s) return s;
+    if (e != hipSuccess) return fail(VLG_E_NO_DEVICE, std::string("isa: ") + hipGetErrorString(e));
+    if (h_bad) return fail(VLG_E_INVALID, std::to_string(h_bad) + " ISA position(s) >= n");
     return VLG_OK;
 }

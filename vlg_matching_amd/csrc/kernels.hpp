@@ -90,7 +90,12 @@ vlg_status launch_sa_dense_copy(const uint32_t* sa, const uint64_t* d_l, const u
 vlg_status launch_int_dense_copy(const IntView& v, const uint64_t* d_l, const uint64_t* d_out_off, uint64_t n_pat, uint64_t total, uint32_t* d_out, hipStream_t stream);
 // every SA value of an SA-order integer index (n words), and its ISA samples ((n - 1) / inv_dens + 1 words): LF walks from the samples
 vlg_status launch_int_sa_expand(const IntView& v, uint32_t* d_sa, hipStream_t st);
-vlg_status launch_int_isa_samples(const IntView& v, uint32_t inv_dens, uint64_t* d_out, hipStream_t st);
+vlg_status launch_int_isa_samples(const IntView& v, uint32_t inv_dens, uint32_t* d_out, hipStream_t st);
+// text access on an integer index (extract.hpp): extract of the job's segments into original symbols, ISA[d_i[j]] (a bad position raises *d_bad)
+struct ExtractJob;
+vlg_status launch_int_extract(const IntView& v, const ExtractJob& job, const uint32_t* d_isa, uint32_t* d_out, hipStream_t st);
+vlg_status launch_int_isa(const IntView& v, uint32_t d, const uint32_t* d_isa, const uint64_t* d_i, uint64_t* d_out, uint64_t count,
+                          unsigned long long* d_bad, hipStream_t st);
 // can this index's occurrences be located by the sorted sweep at all (the byte index always; the integer index with a 16-bit key)
 inline bool int_sweep_possible(const IntView& v) { return v.sigma < 0xFFFFu && v.n_levels >= 1 && v.n <= (1ull << 32); }
 

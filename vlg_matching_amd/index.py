@@ -443,6 +443,11 @@ class VlgIndex:
         check(lib().vlg_index_isa_samples(self._h, inv_dens, out.ctypes.data, len(out)))
         return out
 
+    def text_access(self, inv_dens=64, stream=None):
+        """A TextAccess over this index: extract(csa, b, e), csa.text[i] and csa.isa[i] from ISA samples of density inv_dens kept in
+        HBM.  SA-order indexes only (a text-order one raises VLG_E_UNSUPPORTED)."""
+        return TextAccess(self, inv_dens, stream)
+
     @classmethod
     def attach_blob(cls, d_ptr, nbytes, keep=None):
         h = C.c_void_p()
@@ -557,6 +562,129 @@ class VlgIndex:
         h = C.c_void_p()
         check(lib().vlg_search_batch(self._h, q._h, ws._h, C.byref(h)))
         return SearchResult(h, q.ks)
+
+
+def _u64_index_array(a, name):
+    """a host array / scalar of non-negative integers as uint64 (negative values and non-integers raise ValueError)"""
+    arr = np.asarray(a)
+    if arr.size == 0:
+        return np.zeros(0, np.uint64)
+    if arr.dtype.kind not in "iu":
+        raise ValueError("%s: integer values expected, got %s" % (name, arr.dtype))
+    if arr.dtype.kind == "i" and arr.size and int(arr.min()) < 0:
+        raise ValueError("%s: negative value" % name)
+    return np.ascontiguousarray(arr.reshape(-1), dtype=np.uint64)
+
+
+class TextAccess:
+    """The text of an SA-order index given back on the device (vlg_text_access): extract = sdsl::extract(csa, begin, end)
+    (inclusive end), isa = csa.isa[i].  Byte indexes give bytes, integer indexes np.uint32 arrays of the original symbols.  Position
+    n - 1 (n = |text| + 1) is the sentinel and reads as 0."""
+
+    def __init__(self, index, inv_dens=64, stream=None):
+        inv_dens = int(inv_dens)
+        if inv_dens < 1 or inv_dens >= 1 << 32:
+            raise ValueError("inv_dens must be in [1, 2^32)")
+        self.index = index                        # the handle refers to the index: keep it alive
+        info = index.info()
+        self.n = info["n"]
+        self.is_int = info["bv_kind"] in (2, 3)
+        self.inv_dens = inv_dens
+        self._h = None
+        h = C.c_void_p()
+        check(lib().vlg_text_access_create(index._h, inv_dens, stream, C.byref(h)))
+        self._h = h
+
+    def __del__(self):
+        try:
+            if self._h:
+                lib().vlg_text_access_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    @property
+    def symbol_dtype(self):
+        return np.uint32 if self.is_int else np.uint8
+
+    def extract_device(self, d_begin_ptr, d_end_ptr, d_out_off_ptr, n_ranges, total, d_out_ptr, stream=None):
+        """vlg_extract_batch on device pointers"""
+        check(lib().vlg_extract_batch(self._h, d_begin_ptr, d_end_ptr, d_out_off_ptr, int(n_ranges), int(total), d_out_ptr, stream))
+
+    def isa_device(self, d_i_ptr, d_out_ptr, count, stream=None):
+        """vlg_isa_batch on device pointers"""
+        check(lib().vlg_isa_batch(self._h, d_i_ptr, d_out_ptr, int(count), stream))
+
+    def extract_batch(self, begins, ends):
+        """T[begins[r] .. ends[r]] for every r -> (concatenated symbols, offsets[n_ranges + 1]).  Host arrays give a numpy array (uint8
+        or uint32) and numpy offsets; device tensors (torch, int64 / uint64) give a device tensor (uint8 or int32 holding the uint32
+        symbols) and device offsets."""
+        import torch
+        if isinstance(begins, torch.Tensor) or isinstance(ends, torch.Tensor):
+            return self._extract_batch_device(begins, ends)
+        b, e = _u64_index_array(begins, "begins"), _u64_index_array(ends, "ends")
+        if len(b) != len(e):
+            raise ValueError("begins and ends differ in length")
+        if len(b) and ((b > e).any() or int(e.max()) >= self.n):
+            raise ValueError("every range needs begin <= end < n (n = %d)" % self.n)
+        off = np.zeros(len(b) + 1, dtype=np.uint64)
+        np.cumsum(e - b + 1, out=off[1:])
+        total = int(off[-1])
+        if not len(b):
+            return np.zeros(0, self.symbol_dtype), off
+        d_b = torch.from_numpy(b.view(np.int64)).cuda()
+        d_e = torch.from_numpy(e.view(np.int64)).cuda()
+        d_off = torch.from_numpy(off.view(np.int64)).cuda()
+        d_out = torch.empty(max(total, 1), dtype=torch.int32 if self.is_int else torch.uint8, device="cuda")
+        self.extract_device(d_b.data_ptr(), d_e.data_ptr(), d_off.data_ptr(), len(b), total, d_out.data_ptr())
+        out = d_out[:total].cpu().numpy()
+        return (out.view(np.uint32) if self.is_int else out), off
+
+    def _extract_batch_device(self, begins, ends):
+        import torch
+        for name, t in (("begins", begins), ("ends", ends)):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype not in (torch.int64, getattr(torch, "uint64", torch.int64)) or t.dim() != 1:
+                raise ValueError("%s: a 1-d int64 / uint64 device tensor expected" % name)
+        if begins.numel() != ends.numel():
+            raise ValueError("begins and ends differ in length")
+        b, e = begins.contiguous().to(torch.int64), ends.contiguous().to(torch.int64)
+        off = torch.zeros(b.numel() + 1, dtype=torch.int64, device=b.device)
+        torch.cumsum(e - b + 1, 0, out=off[1:])
+        total = int(off[-1].item()) if b.numel() else 0
+        d_out = torch.empty(max(total, 1), dtype=torch.int32 if self.is_int else torch.uint8, device=b.device)
+        if total < 0:
+            raise ValueError("every range needs begin <= end < n (n = %d)" % self.n)
+        if b.numel():                                 # (a bad range among them: the device check refuses the batch, VLG_E_INVALID)
+            self.extract_device(b.data_ptr(), e.data_ptr(), off.data_ptr(), b.numel(), total, d_out.data_ptr())
+        return d_out[:total], off
+
+    def extract(self, begin, end):
+        """sdsl::extract(csa, begin, end): T[begin .. end] (inclusive) -> bytes (byte index) or np.uint32 array (integer index)"""
+        begin, end = int(begin), int(end)
+        if begin < 0 or begin > end or end >= self.n:
+            raise ValueError("extract needs 0 <= begin <= end < n (n = %d)" % self.n)
+        out, _ = self.extract_batch(np.array([begin], np.uint64), np.array([end], np.uint64))
+        return out if self.is_int else out.tobytes()
+
+    def text(self, i):
+        """csa.text[i]"""
+        r = self.extract(i, i)
+        return int(r[0])
+
+    def isa(self, i):
+        """csa.isa[i] for a scalar (-> int) or an array (-> np.uint64 array) of positions < n"""
+        import torch
+        scalar = np.ndim(i) == 0
+        p = _u64_index_array(i, "i")
+        if len(p) and int(p.max()) >= self.n:
+            raise ValueError("isa needs positions < n (n = %d)" % self.n)
+        if not len(p):
+            return np.zeros(0, np.uint64)
+        d_i = torch.from_numpy(p.view(np.int64)).cuda()
+        d_o = torch.empty_like(d_i)
+        self.isa_device(d_i.data_ptr(), d_o.data_ptr(), len(p))
+        out = d_o.cpu().numpy().view(np.uint64)
+        return int(out[0]) if scalar else out
 
 
 class WtsaIndex:
