@@ -472,7 +472,7 @@ typedef struct {
 /* csa[i] = iterated LF to a sampled index (csa_wt.hpp:335-348), organised per batch as
  *   WALKS     one walk per occurrence (few occurrences; integer alphabets; workspace option "sweep" = 0)
  *   SWEEP     all occurrences advance together in SA order, walks that meet share their LF steps ("trail" = 1)
- *   UNSAMPLE  a batch that locates a large part of all text positions ("unsample_pct" per cent, default 40): one walker per SA
+ *   UNSAMPLE  a batch that locates a large part of all text positions ("unsample_pct" per cent; default 0, off): one walker per SA
  *             sample rebuilds the whole suffix array -- n LF steps whatever the batch, each SA index visited once -- and the
  *             lists are copied out of it; recomputed for every batch, nothing is kept
  *   COPY      an index that keeps every SA value (sa_sample_dens = 1): no LF step at all                               */

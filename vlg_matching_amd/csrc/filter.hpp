@@ -823,10 +823,11 @@ inline uint64_t filter_bytes(const vlg_queries* q, const Plan& pl, const vlg_wor
 
 template <typename pos_t>
 vlg_status filter_group(uint64_t n_positions /* every list element is smaller */, const vlg_queries* q, vlg_workspace* ws, const Plan& pl,
-                        const std::vector<uint32_t>& poff /* per sub-pattern: its list inside P */, const pos_t* P,
-                        Arena& A /* advanced past the state the join chunks still need */, FilterGroup& fg, pos_t* Pc /* survivors go here */)
+                        const Lists<pos_t>& L, Arena& A /* advanced past the state the join chunks still need */, FilterGroup& fg)
 {
     hipStream_t st = ws->stream;
+    const pos_t* P = L.P;
+    pos_t* Pc = L.Pc;                                 // survivors go here
     PhaseTrace ft(st);
     const uint32_t g = filter_block_shift(n_positions);
     const uint64_t nblocks = (n_positions >> g) + 1, nbw = (nblocks + 63) / 64;
@@ -862,7 +863,7 @@ vlg_status filter_group(uint64_t n_positions /* every list element is smaller */
         for (uint32_t i = 0; i < k; ++i) {
             RSeg r;
             memset(&r, 0, sizeof r);
-            r.pbegin = poff[s0 + i];
+            r.pbegin = L.off[s0 + i];
             r.pend = r.pbegin + (uint32_t)pl.occ[s0 + i];
             r.lo = q->lo[s0 + i]; r.hi = q->hi[s0 + i];
             if (i + 1 < k) { r.nlo = q->lo[s0 + i + 1]; r.nhi = q->hi[s0 + i + 1]; }
@@ -927,13 +928,13 @@ vlg_status filter_group(uint64_t n_positions /* every list element is smaller */
         uint64_t probes = 0;                                      // (pivot element, level) pairs: two lower bounds of 8 bytes each
         for (const PTask& pt : ptasks) probes += (uint64_t)(segs[pt.seg0 + pt.p].pend - segs[pt.seg0 + pt.p].pbegin) * (pt.k >= 2 ? pt.k - 2 + (pt.p + 1 == pt.k ? 1 : 0) : 0);
         Timed t(ws, KS_FILTER_PIVOT, 16 * probes);
-        if (ws->rungs && ws->pivot_rungs)
+        if (L.R && ws->pivot_rungs)
             hipLaunchKernelGGL(HIP_KERNEL_NAME(filter_pivot_kernel<pos_t, true>), dim3((uint32_t)((prun0.back() + 4 * kPivotTurns - 1) / (4 * kPivotTurns))), dim3(256), 0, st, P,
-                               static_cast<const pos_t*>(ws->fences), static_cast<const pos_t*>(ws->rungs), ws->rung_off, fg.d_segs, d_ptasks, d_prun0,
+                               L.F, L.R, L.roff, fg.d_segs, d_ptasks, d_prun0,
                                (uint32_t)ptasks.size(), fg.d_abits);
         else
             hipLaunchKernelGGL(HIP_KERNEL_NAME(filter_pivot_kernel<pos_t, false>), dim3((uint32_t)((prun0.back() + 4 * kPivotTurns - 1) / (4 * kPivotTurns))), dim3(256), 0, st, P,
-                               static_cast<const pos_t*>(ws->fences), (const pos_t*)nullptr, (const uint64_t*)nullptr, fg.d_segs, d_ptasks, d_prun0,
+                               L.F, (const pos_t*)nullptr, (const uint64_t*)nullptr, fg.d_segs, d_ptasks, d_prun0,
                                (uint32_t)ptasks.size(), fg.d_abits);
         VLG_HIP_TRY(hipGetLastError());
     }
@@ -1024,10 +1025,9 @@ vlg_status filter_group(uint64_t n_positions /* every list element is smaller */
         if (fg.speculated) {
             ws->stats[KS_FILTER_COMPACT].algorithmic_bytes += 2 * fg.cpre.back() * sizeof(pos_t);
             // fences of the survivors' lists: whole blocks of [Pc, Pc + total) (Pc starts on a block)
-            if (ws->fences && fg.cpre.back() >= 64) {
+            if (L.F && fg.cpre.back() >= 64) {
                 const uint64_t g0 = (uint64_t)(Pc - P) / 64;
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(fence_build_kernel<pos_t>), dim3(grid_for(fg.cpre.back() / 64, 8192)), dim3(256), 0, st, P, g0, g0 + fg.cpre.back() / 64,
-                                   static_cast<pos_t*>(ws->fences));
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(fence_build_kernel<pos_t>), dim3(grid_for(fg.cpre.back() / 64, 8192)), dim3(256), 0, st, P, g0, g0 + fg.cpre.back() / 64, L.F);
                 VLG_HIP_TRY(hipGetLastError());
             }
         }

@@ -64,13 +64,9 @@ struct vlg_workspace {
     uint64_t filter_pivot_ratio = 3;    // ... i.e. when all lists together are at least this many times longer (C3, ms per batch, with the
                                         // ladder: 8 -> 173.2, 6 -> 171.1, 4 -> 169.0, 3 -> 168.9, 2 -> 168.8; with bracket + bisection it was
                                         // 24 -> 262, 12 -> 251, 6 -> 246.6, 4 -> 246.4, <= 3 -> 248): the descents win wherever a list is the shortest
-    void* fences = nullptr;     // F[g] = P[64 g + 63] over the lists of the super-chunk in work (join_device.hpp), or null
-    void* rungs = nullptr;      // the 4-ary ladder over the same lists (join_device.hpp), or null
-    uint64_t* rung_off = nullptr;   // device: first entry of every level
     uint32_t compact_dense_min = 256;        // compaction: runs with fewer survivors move them half a word per lane, fuller ones word by word
                                              // (C3, ms for the class: 0 18.2, 64 18.3, 256 16.6, 512 16.8, 1024 19.2, always half words 31.5)
-    uint32_t pivot_rungs = 1;   // the pivot filter searches through the ladder: 0 never (fences + bisection), 1 when it pays, 2 always
-    bool want_rungs = false;    // ... and the super-chunk in work has enough pivot searches to pay for building it
+    uint32_t pivot_rungs = 1;   // the pivot filter searches through the ladder (join_device.hpp): 0 never (fences + bisection), 1 when it pays, 2 always
     int list_sort = 1;          // 32-bit positions: every list sorted inside itself (list_sort.hpp; 2: without the window passes); 0: the two rocPRIM paths below
     uint64_t global_sort_min = 1ull << 20;  // at least this many occurrences: all lists are sorted by one radix sort of (list, position) keys
     uint64_t sweep_min = 1ull << 22;    // below this many occurrences the persistent random-access kernel is used
@@ -623,6 +619,18 @@ struct Plan {                       // host view of the batch after backward sea
     rvec<uint64_t> dl, docc;        // per distinct interval: left border, size
 };
 
+template <typename pos_t>
+struct Lists {                      // the sorted occurrence lists the joins read, and the search aids over them (join_device.hpp)
+    pos_t* P = nullptr;             // the lists, one after the other
+    pos_t* Pc = nullptr;            // room for the survivors of filtered lists, inside the allocation of P (or null)
+    uint64_t pc_cap = 0;
+    std::vector<uint32_t> off;      // per sub-pattern: its list inside P
+    std::vector<uint32_t> doff;     // (vlg_search_batch) per distinct interval: its list inside P
+    pos_t* F = nullptr;             // fences: F[g] = P[64 g + 63] over the lists and the survivors behind them, or null
+    pos_t* R = nullptr;             // the 4-ary ladder over the lists, or null
+    uint64_t* roff = nullptr;       // device: first entry of every level of R
+};
+
 template <typename pos_t> constexpr uint64_t kPhysScratchPerElem() { return 20; }   // sweep scratch; the sorted lists reuse it
 constexpr uint64_t kJoinBytesPerSlot = 4 + 8 + 1;      // link, endp(<=8), feasibility bits + summaries (any slot)
 constexpr uint64_t kJoinBytesPerSlot0 = 4 + 4 + 8 + 1; // jump, mlist, (exit,hops), chain records (slots of list 0)
@@ -773,40 +781,90 @@ __global__ void __launch_bounds__(256) segments_copy_kernel(pos_t* __restrict__ 
     }
 }
 
-// K3u (kernels.hip): does a share of `acc` occurrences of this index's text pay for rebuilding the whole suffix array?
-inline bool unsample_applies(const vlg_index* idx, const vlg_workspace* ws, uint64_t acc)
+// ---- what the physical pass of a super-chunk does: decided once, for the plan of the arena and for the pass itself -------------
+struct PhysChoice {
+    uint32_t locate = VLG_LOCATE_WALKS; // VLG_LOCATE_WALKS / _SWEEP / _UNSAMPLE / _COPY: what the result reports
+    bool sweep = false;                 // the sorted sweep locates (also with COPY on a byte index: it copies the resident suffix array)
+    bool share_steps = false;           // ... and its walks stop at elements of the batch (room for the member bit-vector and the records)
+    bool list_sort = false;             // 32-bit positions: every list sorted inside itself first (list_sort.hpp), when its tables fit
+    bool global_sort = false;           // otherwise one radix sort of (list, position) keys; false: a segmented one
+    unsigned pos_bits = 1;              // bits of the largest position, n - 2 (n - 1 is the sentinel)
+};
+
+// `elems` occurrences in `n_lists` lists.  K3u (kernels.hip: the whole suffix array rebuilt from the samples -- n LF steps, no trails,
+// no records) is judged on `unsample_elems` and needs its arrays (n x 4 B + 20 B per sample) inside the sweep scratch of
+// `scratch_elems` (0: not tested).  `sized` is the choice the arena was planned for (null: this is that plan): the pass unsamples and
+// shares LF steps only where the plan made room for it.
+template <typename pos_t>
+PhysChoice choose_physical(const vlg_index* idx, const vlg_workspace* ws, uint64_t elems, uint64_t n_lists, bool wide, uint64_t unsample_elems,
+                           uint64_t scratch_elems, const PhysChoice* sized)
 {
-    if (!ws->unsample_pct || !ws->sweep || !ws->trail || !ws->dedup || idx->is_int) return false;
-    if (idx->hdr.sampling != kSamplingSaOrder || idx->hdr.dens < 2 || idx->hdr.n > (1ull << 32) + 1 || idx->hdr.sigma >= 0x7FFFu) return false;
-    return acc >= ws->sweep_min && acc >= ws->unsample_min && (__uint128_t)acc * 100 >= (__uint128_t)idx->hdr.n * ws->unsample_pct;
+    const BlobHeader& h = idx->hdr;
+    const bool dense = h.dens == 1 && h.sampling == kSamplingSaOrder;     // the index keeps the whole suffix array: nothing to walk
+    PhysChoice c;
+    c.pos_bits = std::max(1u, bit_width64(h.n >= 2 ? h.n - 2 : 0));
+    c.sweep = ws->sweep && elems >= ws->sweep_min && h.n <= (1ull << (wide ? 33 : 32)) &&
+              (!idx->is_int || (int_sweep_possible(idx->iview) && sizeof(pos_t) == 4 && !wide));
+    // K3u needs dedup + trail (the options that let the walks of a batch share LF steps at all) and SA-order samples
+    const uint64_t n_walkers = idx->is_int ? 0 : idx->view.n_samples;
+    const bool unsample = c.sweep && sizeof(pos_t) == 4 && ws->unsample_pct && ws->trail && ws->dedup && !idx->is_int && h.sampling == kSamplingSaOrder &&
+                          h.dens >= 2 && h.n <= (1ull << 32) + 1 && h.sigma < 0x7FFFu && unsample_elems >= ws->sweep_min && unsample_elems >= ws->unsample_min &&
+                          (__uint128_t)unsample_elems * 100 >= (__uint128_t)h.n * ws->unsample_pct &&
+                          (!scratch_elems || align_up(h.n * 4, 256) + n_walkers * 20 + 1024 <= scratch_elems * kPhysScratchPerElem<pos_t>()) &&
+                          (!sized || sized->locate == VLG_LOCATE_UNSAMPLE);
+    c.locate = !c.sweep ? (idx->is_int && dense ? VLG_LOCATE_COPY : VLG_LOCATE_WALKS) : unsample ? VLG_LOCATE_UNSAMPLE : dense ? VLG_LOCATE_COPY : VLG_LOCATE_SWEEP;
+    c.share_steps = c.sweep && !unsample && ws->trail && ws->dedup && !dense && elems <= 0xFFFFFF00ull && (!sized || sized->share_steps);
+    c.list_sort = sizeof(pos_t) == 4 && ws->list_sort;
+    c.global_sort = elems >= ws->global_sort_min && c.pos_bits + bit_width64(n_lists) <= 64;
+    return c;
 }
 
-// ---- physical pass: locate + sort every distinct interval used by queries [Q0,Q1) -------------------
+struct SuperChunk {                 // a run of queries [Q0, Q1) whose distinct occurrence lists fit the physical budget
+    uint64_t Q0 = 0, Q1 = 0, phys = 0;
+    std::vector<uint32_t> dlist;    // their distinct lists, in ascending id order
+};
+
+struct ChunkPlan {                  // the arena of a super-chunk: physical lists first, filter state and join scratch behind them
+    PhysChoice c;                   // choose_physical over the whole super-chunk
+    size_t sort_tmp = 0;            // temporary storage of the sorts and of the sweep
+    bool want_rungs = false;        // the pivot filter has enough searches in the super-chunk to pay for the ladder
+    uint64_t phys_bytes = 0, join_budget = 0;
+    bool launch_first = false;      // the arena holds whatever a plan can ask for: locate + sort are launched before the joins are planned
+};
+
+// ---- physical pass: locate + sort every distinct interval used by the queries of a super-chunk -------------------
+// The stages run one after the other and do what the plan and choose_physical over this rank's share decided.
 template <typename pos_t>
-vlg_status build_physical(const vlg_index* idx, vlg_workspace* ws, vlg_result* res, const std::vector<uint32_t>& dlist_in /* distinct ids */,
-                          const Plan& pl, Arena& A, pos_t*& P_out, std::vector<uint32_t>& poff /* per distinct id -> offset (size dl) */,
-                          uint64_t& Tphys, size_t sort_tmp, unsigned long long* d_stats, pos_t*& Pc_out, uint64_t& pc_cap,
-                          bool share_steps /* the sweep's walks stop at elements of the batch (room for the member bit-vector and the records) */,
-                          bool wide /* SA indices need 33 bits / 64-bit samples (always so for 64-bit positions) */,
-                          bool allow_unsample /* the caller planned the workspace for K3u (no trail table) */,
-                          const vlg_queries* q = nullptr, const std::vector<uint64_t>* xq = nullptr /* collective search: the ranks' query cuts */,
-                          Agreement* ag = nullptr /* collective search: settled here, right before the exchange */)
-{
+struct PhysicalPass {
+    const vlg_index* idx; vlg_workspace* ws; vlg_result* res; const Plan& pl; const ChunkPlan& cp; bool wide; Arena& A;
+    unsigned long long* d_stats; Lists<pos_t>& L;
     hipStream_t st = ws->stream;
-    PhaseTrace bt(st);
+    PhaseTrace bt{st};
+    std::vector<uint32_t> dlist, cut;   // layout order of the lists; collective search: the lists [cut[r], cut[r + 1]) are rank r's share
+    std::vector<uint64_t> xcounts;      // ... and their occurrences
+    uint32_t gnd = 0, n_outer = 0, sl = 0, nd = 0;
+    uint64_t gacc = 0, acc = 0;
+    svec<uint64_t> goff64, off64, lh; svec<uint32_t> off32;
+    PhysChoice c;                       // for this rank's share
+    pos_t* Pg = nullptr; pos_t* Pa = nullptr; pos_t* Pb = nullptr; uint8_t* scratch = nullptr; void* d_tmp = nullptr;
+    uint64_t* d_goff64 = nullptr; uint64_t* d_off64 = nullptr; uint32_t* d_off32 = nullptr; uint64_t* d_lh = nullptr; unsigned long long* d_counter = nullptr;
+    uint64_t* rec = nullptr; Block* member = nullptr; uint8_t* front = nullptr;
+    uint64_t sort_mark = 0; ListSortPlan lsp;
+    bool pairwise = false;              // the exchange moved needed lists only: each rank checks its own share
+
     // all lists of the super-chunk ("g": global), laid out one after the other in SA order of their intervals -- first the ones that
     // are pairwise disjoint ("outer"), then the ones nested inside another list of the chunk (the interval of a pattern that continues
     // another pattern; SA intervals of patterns nest or are disjoint, they never overlap in part).  With the outer lists in SA order
     // at the front, the slot of an SA index inside one of them is the number of such indices before it: what the sweep's member
     // bit-vector returns (kernels.hip: sweep_element).
-    const uint32_t gnd = (uint32_t)dlist_in.size();
-    std::vector<uint32_t> dlist(dlist_in);
-    bool ascending = true;
-    for (uint32_t i = 1; i < gnd && ascending; ++i) ascending = pl.dl[dlist[i - 1]] <= pl.dl[dlist[i]];
-    if (!ascending)                                                        // (a plan made on the host numbers the intervals as they come)
-        std::sort(dlist.begin(), dlist.end(), [&](uint32_t a, uint32_t b) { return pl.dl[a] != pl.dl[b] ? pl.dl[a] < pl.dl[b] : pl.docc[a] < pl.docc[b]; });
-    uint32_t n_outer = gnd;
+    void layout(const std::vector<uint32_t>& dlist_in)
     {
+        gnd = (uint32_t)dlist_in.size();
+        dlist = dlist_in;
+        bool ascending = true;
+        for (uint32_t i = 1; i < gnd && ascending; ++i) ascending = pl.dl[dlist[i - 1]] <= pl.dl[dlist[i]];
+        if (!ascending)                                                    // (a plan made on the host numbers the intervals as they come)
+            std::sort(dlist.begin(), dlist.end(), [&](uint32_t a, uint32_t b) { return pl.dl[a] != pl.dl[b] ? pl.dl[a] < pl.dl[b] : pl.docc[a] < pl.docc[b]; });
         std::vector<uint32_t> inner;
         uint64_t cover_end = 0;
         uint32_t w = 0;
@@ -823,229 +881,202 @@ vlg_status build_physical(const vlg_index* idx, vlg_workspace* ws, vlg_result* r
         }
         n_outer = w;
         for (uint32_t d : inner) dlist[w++] = d;
-    }
-    svec<uint64_t> goff64(gnd + 1);
-    uint64_t gacc = 0;
-    for (uint32_t i = 0; i < gnd; ++i) {
-        goff64[i] = gacc;
-        poff[dlist[i]] = (uint32_t)gacc;
-        gacc += pl.docc[dlist[i]];
-    }
-    goff64[gnd] = gacc;
-    Tphys = gacc;
-    P_out = nullptr;
-    Pc_out = nullptr;
-    pc_cap = 0;
-    ws->fences = nullptr;
-    ws->rungs = nullptr;
-    if (!gacc) return ag ? ag->settle(VLG_OK) : VLG_OK;              // (every rank sees the same empty plan and settles too)
-    // Collective search: this rank locates and sorts a contiguous share [sl, sh) of the lists -- cut so that every rank gets the
-    // same number of occurrences, identically on every rank -- and the ranks exchange their sorted pieces afterwards.
-    uint32_t sl = 0, sh = gnd;
-    std::vector<uint64_t> xcounts;
-    std::vector<uint32_t> cut(ws->x_ranks + 1, gnd);
-    if (ws->x_ranks > 1) {
-        cut[0] = 0;
-        for (int r = 1; r < ws->x_ranks; ++r) {
-            const uint64_t target = gacc / (uint64_t)ws->x_ranks * (uint64_t)r;
-            const uint32_t c = (uint32_t)(std::lower_bound(goff64.begin(), goff64.end(), target) - goff64.begin());
-            cut[r] = std::max(cut[r - 1], std::min(c, gnd));
+        goff64.resize(gnd + 1);
+        for (uint32_t i = 0; i < gnd; ++i) {
+            goff64[i] = gacc;
+            L.doff[dlist[i]] = (uint32_t)gacc;
+            gacc += pl.docc[dlist[i]];
         }
-        xcounts.resize(ws->x_ranks);
-        for (int r = 0; r < ws->x_ranks; ++r) xcounts[r] = goff64[cut[r + 1]] - goff64[cut[r]];
-        sl = cut[ws->x_rank]; sh = cut[ws->x_rank + 1];
+        goff64[gnd] = gacc;
+        // Collective search: this rank locates and sorts a contiguous share [sl, sh) of the lists -- cut so that every rank gets the
+        // same number of occurrences, identically on every rank -- and the ranks exchange their sorted pieces afterwards.
+        uint32_t sh = gnd;
+        cut.assign(ws->x_ranks + 1, gnd);
+        if (ws->x_ranks > 1) {
+            cut[0] = 0;
+            for (int r = 1; r < ws->x_ranks; ++r) {
+                const uint64_t target = gacc / (uint64_t)ws->x_ranks * (uint64_t)r;
+                const uint32_t at = (uint32_t)(std::lower_bound(goff64.begin(), goff64.end(), target) - goff64.begin());
+                cut[r] = std::max(cut[r - 1], std::min(at, gnd));
+            }
+            xcounts.resize(ws->x_ranks);
+            for (int r = 0; r < ws->x_ranks; ++r) xcounts[r] = goff64[cut[r + 1]] - goff64[cut[r]];
+            sl = cut[ws->x_rank]; sh = cut[ws->x_rank + 1];
+        }
+        nd = sh - sl;                                                      // from here to the sort: this rank's share
+        off64.resize(nd + 1); lh.resize(std::max<uint32_t>(nd, 1)); off32.resize(nd + 1);
+        for (uint32_t i = 0; i <= nd; ++i) { off64[i] = goff64[sl + i] - goff64[sl]; off32[i] = (uint32_t)off64[i]; }
+        for (uint32_t i = 0; i < nd; ++i) lh[i] = pl.dl[dlist[sl + i]];
+        acc = off64[nd];
+        c = choose_physical<pos_t>(idx, ws, acc, nd, wide, acc, gacc, &cp.c);
     }
-    const uint32_t nd = sh - sl;                                       // from here to the sort: this rank's share
-    svec<uint64_t> off64(nd + 1), lh(std::max<uint32_t>(nd, 1));
-    svec<uint32_t> off32(nd + 1);
-    for (uint32_t i = 0; i <= nd; ++i) { off64[i] = goff64[sl + i] - goff64[sl]; off32[i] = (uint32_t)off64[i]; }
-    for (uint32_t i = 0; i < nd; ++i) lh[i] = pl.dl[dlist[sl + i]];
-    const uint64_t acc = off64[nd];
-    const bool use_sweep = ws->sweep && acc >= ws->sweep_min && idx->hdr.n <= (1ull << (wide ? 33 : 32)) && (!idx->is_int || (int_sweep_possible(idx->iview) && sizeof(pos_t) == 4 && !wide));
-    // K3u: the whole suffix array from the samples, inside the sweep's scratch (n x 4 B + 20 B per sample <= 20 B per occurrence)
-    const uint64_t n_walkers = idx->is_int ? 0 : idx->view.n_samples;
-    const bool use_unsample = allow_unsample && use_sweep && sizeof(pos_t) == 4 && unsample_applies(idx, ws, acc) &&
-                              align_up(idx->hdr.n * 4, 256) + n_walkers * 20 + 1024 <= gacc * kPhysScratchPerElem<pos_t>();
-    pos_t* Pg = A.take<pos_t>(gacc);
-    // scratch of the sweep (20 B per element); the sorted lists Pb reuse it once locate is done
-    uint8_t* scratch = A.take<uint8_t>(gacc * kPhysScratchPerElem<pos_t>());
-    pos_t* Pa = Pg ? Pg + goff64[sl] : nullptr;
-    uint64_t* d_goff64 = (ws->x_ranks > 1) ? A.take<uint64_t>(gnd + 1) : nullptr;
-    uint64_t* d_off64 = A.take<uint64_t>(nd + 1);
-    uint32_t* d_off32 = A.take<uint32_t>(nd + 1);
-    uint64_t* d_lh = A.take<uint64_t>(nd);
-    unsigned long long* d_counter = A.take<unsigned long long>(4);     // [0] the sweep's counter, [1..3] diagnostics (VLG_RESOLVE_STATS)
-    void* d_tmp = A.take<uint8_t>(sort_tmp + 256);
-    if (A.failed) return fail(VLG_E_INTERNAL, "arena carve failed (physical)");
-    pos_t* Pb = reinterpret_cast<pos_t*>(scratch);
-    VLG_HIP_TRY(hipMemcpyAsync(d_off64, off64.data(), (nd + 1) * 8, hipMemcpyHostToDevice, st));
-    VLG_HIP_TRY(hipMemcpyAsync(d_off32, off32.data(), (nd + 1) * 4, hipMemcpyHostToDevice, st));
-    if (nd) VLG_HIP_TRY(hipMemcpyAsync(d_lh, lh.data(), nd * 8, hipMemcpyHostToDevice, st));
-    if (d_goff64) VLG_HIP_TRY(hipMemcpyAsync(d_goff64, goff64.data(), (gnd + 1) * 8, hipMemcpyHostToDevice, st));
-    uint64_t* rec = nullptr;
-    Block* member = nullptr;
-    uint8_t* front = nullptr;
-    const uint32_t n_member_lists = n_outer > sl ? std::min(n_outer - sl, nd) : 0u;      // this rank's outer lists: a prefix of its share
-    if (use_sweep && !use_unsample && share_steps && acc <= 0xFFFFFF00ull) {
-        rec = A.take<uint64_t>(acc);
-        member = A.take<Block>(member_blocks(idx->hdr.n));
-        if (!idx->is_int) front = A.take<uint8_t>(acc);             // the symbol in front of every element that stops on its first step (kernels.hpp: SweepKernels)
-        if (A.failed) return fail(VLG_E_INTERNAL, "arena carve failed (member bit-vector, records)");
+
+    vlg_status carve()
+    {
+        Pg = A.take<pos_t>(gacc);
+        scratch = A.take<uint8_t>(gacc * kPhysScratchPerElem<pos_t>());   // the sweep's scratch (20 B per element); the sorted lists Pb reuse it
+        Pa = Pg ? Pg + goff64[sl] : nullptr;
+        d_goff64 = (ws->x_ranks > 1) ? A.take<uint64_t>(gnd + 1) : nullptr;
+        d_off64 = A.take<uint64_t>(nd + 1);
+        d_off32 = A.take<uint32_t>(nd + 1);
+        d_lh = A.take<uint64_t>(nd);
+        d_counter = A.take<unsigned long long>(4);                        // [0] the sweep's counter, [1..3] diagnostics (VLG_RESOLVE_STATS)
+        d_tmp = A.take<uint8_t>(cp.sort_tmp + 256);
+        if (A.failed) return fail(VLG_E_INTERNAL, "arena carve failed (physical)");
+        Pb = reinterpret_cast<pos_t*>(scratch);
+        VLG_HIP_TRY(hipMemcpyAsync(d_off64, off64.data(), (nd + 1) * 8, hipMemcpyHostToDevice, st));
+        VLG_HIP_TRY(hipMemcpyAsync(d_off32, off32.data(), (nd + 1) * 4, hipMemcpyHostToDevice, st));
+        if (nd) VLG_HIP_TRY(hipMemcpyAsync(d_lh, lh.data(), nd * 8, hipMemcpyHostToDevice, st));
+        if (d_goff64) VLG_HIP_TRY(hipMemcpyAsync(d_goff64, goff64.data(), (gnd + 1) * 8, hipMemcpyHostToDevice, st));
+        if (c.share_steps) {
+            rec = A.take<uint64_t>(acc);
+            member = A.take<Block>(member_blocks(idx->hdr.n));
+            if (!idx->is_int) front = A.take<uint8_t>(acc);             // the symbol in front of every element that stops on its first step (kernels.hpp: SweepKernels)
+            if (A.failed) return fail(VLG_E_INTERNAL, "arena carve failed (member bit-vector, records)");
+        }
+        sort_mark = A.used;
+        return VLG_OK;
     }
+
     // the sort's tables only depend on the list lengths: they are built and uploaded while the first step of locate runs
-    const uint64_t sort_mark = A.used;
-    ListSortPlan lsp;
-    const unsigned bits = std::max(1u, bit_width64(idx->hdr.n >= 2 ? idx->hdr.n - 2 : 0));   // the largest position is n - 2 (n - 1 is the sentinel)
-    const std::function<vlg_status()> plan_sort = [&]() -> vlg_status {
-        if (sizeof(pos_t) != 4 || !ws->list_sort) return VLG_OK;
+    vlg_status plan_sort()
+    {
+        if (!c.list_sort) return VLG_OK;
         const vlg_status ls = list_sort_prepare(off64, nd, A, st, lsp);
         if (ls != VLG_OK && ls != VLG_E_WORKSPACE) return ls;      // no room for its tables: the device-wide sort below
         if (ls != VLG_OK) A.used = sort_mark;
         return VLG_OK;
-    };
-    if (!acc) {
-        // (a rank without a share: nothing to locate or sort, the exchange below still takes place)
-    } else if (use_unsample) {
-        uint32_t* sa_full = reinterpret_cast<uint32_t*>(scratch);
-        uint64_t* val_a = reinterpret_cast<uint64_t*>(scratch + align_up(idx->hdr.n * 4, 256));
-        uint64_t* val_b = val_a + n_walkers;
-        uint16_t* key_a = reinterpret_cast<uint16_t*>(val_b + n_walkers);
-        uint16_t* key_b = key_a + n_walkers;
-        svec<unsigned long long> h_done(1, 0);
-        SweepTimer timer(ws);
-        bt.mark("  physical: tables + sort plan");
+    }
+
+    // this rank's share into Pa (a rank without a share locates nothing; the exchange still takes place)
+    vlg_status locate(const std::function<vlg_status()>& hook /* plan_sort, run by the sweep while its first step runs */)
+    {
+        if (!acc) return VLG_OK;
+        const uint64_t n_walkers = idx->is_int ? 0 : idx->view.n_samples;
         vlg_status s = VLG_OK;
-        if constexpr (sizeof(pos_t) == 4) {
-            if (wide) s = launch_unsample<true>(idx->view, d_lh, d_off64, nd, acc, Pa, sa_full, val_a, val_b, key_a, key_b, d_tmp, sort_tmp, d_counter, h_done.data(),
-                                                d_stats, ws->unsample_tail, st, &timer, &plan_sort);
-            else s = launch_unsample<false>(idx->view, d_lh, d_off64, nd, acc, Pa, sa_full, val_a, val_b, key_a, key_b, d_tmp, sort_tmp, d_counter, h_done.data(),
-                                            d_stats, ws->unsample_tail, st, &timer, &plan_sort);
-        }
-        if (s) return s;
-        ws->sample_reads += n_walkers;
-        res->sum.locate_mode = VLG_LOCATE_UNSAMPLE;
-        bt.mark("  physical: unsampling");
-    } else if (use_sweep) {
-        const uint64_t cap = std::min<uint64_t>(acc, wide ? sweep_batch_max<true>() : sweep_batch_max<false>());
-        uint64_t* val_a = reinterpret_cast<uint64_t*>(scratch);
-        uint64_t* val_b = val_a + cap;
-        uint16_t* key_a = reinterpret_cast<uint16_t*>(val_b + cap);
-        uint16_t* key_b = key_a + cap;
-        SweepTimer timer(ws);
-        bt.mark("  physical: tables + sort plan");
-        vlg_status s = VLG_OK;
-        if (idx->is_int) {
-            if constexpr (sizeof(pos_t) == 4)
-                s = launch_int_locate_sweep(idx->iview, d_lh, d_off64, nd, acc, Pa, val_a, val_b, key_a, key_b, d_tmp, sort_tmp, d_counter, d_stats, ws->sweep_tail, st,
-                                            &timer, member, n_member_lists, rec, &plan_sort);
-            else s = fail(VLG_E_INTERNAL, "integer-alphabet index with 64-bit positions");
-        } else if (wide)
-            s = launch_locate_sweep<pos_t, true>(idx->view, d_lh, d_off64, nd, acc, Pa, val_a, val_b, key_a, key_b, d_tmp, sort_tmp, d_counter, d_stats,
-                                                 ws->sweep_tail, st, &timer, member, n_member_lists, rec, &plan_sort, front);
-        else if constexpr (sizeof(pos_t) == 4)                      // (a 64-bit position type always comes with wide indices)
-            s = launch_locate_sweep<uint32_t, false>(idx->view, d_lh, d_off64, nd, acc, Pa, val_a, val_b, key_a, key_b, d_tmp, sort_tmp, d_counter, d_stats,
-                                                     ws->sweep_tail, st, &timer, member, n_member_lists, rec, &plan_sort, front);
-        else s = fail(VLG_E_INTERNAL, "64-bit positions with 32-bit SA indices");
-        if (s) return s;
-        ws->sample_reads += acc;
-        res->sum.locate_mode = idx->hdr.dens == 1 && idx->hdr.sampling == kSamplingSaOrder ? VLG_LOCATE_COPY : VLG_LOCATE_SWEEP;
-        bt.mark("  physical: sweep");
-    } else if (idx->is_int) {
-        // integer-alphabet index (int_index.hpp): one lane per occurrence on the wavelet matrix of the BWT -- or, with the suffix array
-        // resident (SA order, density 1), a copy of the SA intervals whatever the alphabet or the size of the batch
-        const bool dense = idx->iview.dens == 1 && idx->iview.sampling == kSamplingSaOrder;
-        ws->sample_reads += acc;
-        res->sum.locate_mode = dense ? VLG_LOCATE_COPY : VLG_LOCATE_WALKS;
-        if (vlg_status s = plan_sort()) return s;
-        if constexpr (sizeof(pos_t) == 4) {
-            if (dense) {
-                Timed t(ws, KS_LOCATE, 0);
-                if (vlg_status s = launch_int_dense_copy(idx->iview, d_lh, d_off64, nd, acc, Pa, st)) return s;
-            } else {
-                {
-                    Timed t(ws, KS_EXPAND, 0);
-                    if (vlg_status s = launch_expand<uint32_t>(d_lh, d_off64, nd, acc, Pa, nullptr, st)) return s;
-                }
-                Timed t(ws, KS_LOCATE, 0);
-                if (vlg_status s = launch_int_locate(idx->iview, Pa, acc, d_stats, st)) return s;
+        if (c.locate == VLG_LOCATE_UNSAMPLE) {
+            // K3u: the whole suffix array from the samples, inside the sweep's scratch (n x 4 B + 20 B per sample <= 20 B per occurrence)
+            uint32_t* sa_full = reinterpret_cast<uint32_t*>(scratch);
+            uint64_t* val_a = reinterpret_cast<uint64_t*>(scratch + align_up(idx->hdr.n * 4, 256));
+            uint64_t* val_b = val_a + n_walkers;
+            uint16_t* key_a = reinterpret_cast<uint16_t*>(val_b + n_walkers);
+            uint16_t* key_b = key_a + n_walkers;
+            svec<unsigned long long> h_done(1, 0);
+            SweepTimer timer(ws);
+            bt.mark("  physical: tables + sort plan");
+            if constexpr (sizeof(pos_t) == 4) {
+                if (wide) s = launch_unsample<true>(idx->view, d_lh, d_off64, nd, acc, Pa, sa_full, val_a, val_b, key_a, key_b, d_tmp, cp.sort_tmp, d_counter, h_done.data(),
+                                                    d_stats, ws->unsample_tail, st, &timer, &hook);
+                else s = launch_unsample<false>(idx->view, d_lh, d_off64, nd, acc, Pa, sa_full, val_a, val_b, key_a, key_b, d_tmp, cp.sort_tmp, d_counter, h_done.data(),
+                                                d_stats, ws->unsample_tail, st, &timer, &hook);
             }
-        } else return fail(VLG_E_INTERNAL, "integer-alphabet index with 64-bit positions");
-    } else if (wide && sizeof(pos_t) == 4) {
-        // few occurrences, 33-bit SA indices, 32-bit positions: the in-place kernel walks in 64-bit words of the scratch, then narrows
-        ws->sample_reads += acc;
-        res->sum.locate_mode = VLG_LOCATE_WALKS;
+            if (!s) bt.mark("  physical: unsampling");
+        } else if (c.sweep) {
+            const uint64_t cap = std::min<uint64_t>(acc, wide ? sweep_batch_max<true>() : sweep_batch_max<false>());
+            uint64_t* val_a = reinterpret_cast<uint64_t*>(scratch);
+            uint64_t* val_b = val_a + cap;
+            uint16_t* key_a = reinterpret_cast<uint16_t*>(val_b + cap);
+            uint16_t* key_b = key_a + cap;
+            const uint32_t n_member_lists = n_outer > sl ? std::min(n_outer - sl, nd) : 0u;      // this rank's outer lists: a prefix of its share
+            SweepTimer timer(ws);
+            bt.mark("  physical: tables + sort plan");
+            if (idx->is_int) {
+                if constexpr (sizeof(pos_t) == 4)
+                    s = launch_int_locate_sweep(idx->iview, d_lh, d_off64, nd, acc, Pa, val_a, val_b, key_a, key_b, d_tmp, cp.sort_tmp, d_counter, d_stats, ws->sweep_tail, st,
+                                                &timer, member, n_member_lists, rec, &hook);
+                else s = fail(VLG_E_INTERNAL, "integer-alphabet index with 64-bit positions");
+            } else if (wide)
+                s = launch_locate_sweep<pos_t, true>(idx->view, d_lh, d_off64, nd, acc, Pa, val_a, val_b, key_a, key_b, d_tmp, cp.sort_tmp, d_counter, d_stats,
+                                                     ws->sweep_tail, st, &timer, member, n_member_lists, rec, &hook, front);
+            else if constexpr (sizeof(pos_t) == 4)                      // (a 64-bit position type always comes with wide indices)
+                s = launch_locate_sweep<uint32_t, false>(idx->view, d_lh, d_off64, nd, acc, Pa, val_a, val_b, key_a, key_b, d_tmp, cp.sort_tmp, d_counter, d_stats,
+                                                         ws->sweep_tail, st, &timer, member, n_member_lists, rec, &hook, front);
+            else s = fail(VLG_E_INTERNAL, "64-bit positions with 32-bit SA indices");
+            if (!s) bt.mark("  physical: sweep");
+        } else if (idx->is_int) {
+            // integer-alphabet index (int_index.hpp): one lane per occurrence on the wavelet matrix of the BWT -- or, with the suffix array
+            // resident (SA order, density 1), a copy of the SA intervals whatever the alphabet or the size of the batch
+            if ((s = plan_sort())) return s;
+            if constexpr (sizeof(pos_t) == 4) {
+                if (c.locate == VLG_LOCATE_COPY) {
+                    Timed t(ws, KS_LOCATE, 0);
+                    s = launch_int_dense_copy(idx->iview, d_lh, d_off64, nd, acc, Pa, st);
+                } else {
+                    {
+                        Timed t(ws, KS_EXPAND, 0);
+                        if ((s = launch_expand<uint32_t>(d_lh, d_off64, nd, acc, Pa, nullptr, st))) return s;
+                    }
+                    Timed t(ws, KS_LOCATE, 0);
+                    s = launch_int_locate(idx->iview, Pa, acc, d_stats, st);
+                }
+            } else s = fail(VLG_E_INTERNAL, "integer-alphabet index with 64-bit positions");
+        } else if (wide && sizeof(pos_t) == 4) s = walks(reinterpret_cast<uint64_t*>(scratch));   // 33-bit SA indices: 64-bit words of the scratch
+        else s = walks(Pa);
+        if (s) return s;
+        ws->sample_reads += c.locate == VLG_LOCATE_UNSAMPLE ? n_walkers : acc;
+        res->sum.locate_mode = c.locate;
+        return VLG_OK;
+    }
+
+    // few occurrences: one walk per occurrence in place, in words of word_t -- narrowed into Pa when they are wider than a position
+    template <typename word_t>
+    vlg_status walks(word_t* io)
+    {
         if (vlg_status s = plan_sort()) return s;
-        uint64_t* io64 = reinterpret_cast<uint64_t*>(scratch);
         {
             Timed t(ws, KS_EXPAND, 0);
-            if (vlg_status s = launch_expand<uint64_t>(d_lh, d_off64, nd, acc, io64, nullptr, st)) return s;
+            if (vlg_status s = launch_expand<word_t>(d_lh, d_off64, nd, acc, io, nullptr, st)) return s;
         }
-        {
-            Timed t(ws, KS_LOCATE, 0);
-            if (vlg_status s = launch_locate<uint64_t>(idx->view, io64, acc, d_stats, st)) return s;
-            if (vlg_status s = launch_narrow<uint32_t>(io64, reinterpret_cast<uint32_t*>(Pa), acc, st)) return s;
-        }
-    } else {
-        ws->sample_reads += acc;
-        res->sum.locate_mode = VLG_LOCATE_WALKS;
-        if (vlg_status s = plan_sort()) return s;
-        {
-            Timed t(ws, KS_EXPAND, 0);
-            if (vlg_status s = launch_expand<pos_t>(d_lh, d_off64, nd, acc, Pa, nullptr, st)) return s;
-        }
-        {
-            Timed t(ws, KS_LOCATE, 0);
-            if (vlg_status s = launch_locate<pos_t>(idx->view, Pa, acc, d_stats, st)) return s;
-        }
+        Timed t(ws, KS_LOCATE, 0);
+        if (vlg_status s = launch_locate<word_t>(idx->view, io, acc, d_stats, st)) return s;
+        if constexpr (sizeof(word_t) != sizeof(pos_t)) return launch_narrow<pos_t>(io, Pa, acc, st);
+        return VLG_OK;
     }
-    // sort every occurrence list ascending (std::sort, index_sasearch.hpp:80)
-    const unsigned list_bits = bit_width64(nd);
-    const bool global_sort = acc >= ws->global_sort_min && bits + list_bits <= 64;
-    uint64_t dead_bytes = 0;                              // free bytes behind the sorted lists (the survivors of the window filter go there)
-    bool sorted = false;
-    if (!acc) {
-        sorted = true;
-        P_out = Pa;
-    } else if (lsp.ready) {
-        // 32-bit positions: sorted inside every list (list_sort.hpp) -- 4 passes of 8 B per element instead of 6 of 16 B
-        Timed t(ws, KS_SORT, 2ull * acc * sizeof(pos_t));
-        if (vlg_status ls = list_sort_enqueue(lsp, reinterpret_cast<uint32_t*>(Pa), reinterpret_cast<uint32_t*>(scratch), d_off64, bits, st, ws->list_sort == 1)) return ls;
-        A.used = sort_mark;                               // its tables are dead once its kernels have run (stream order)
-        sorted = true;
-        P_out = Pa;
-    }
-    if (sorted) {
-    } else if (global_sort) {
-        // one radix sort of (list, position) keys: the passes stream the whole batch whatever the list sizes are
-        uint64_t* ka = reinterpret_cast<uint64_t*>(scratch);
-        uint64_t* kb = ka + acc;
-        Timed t(ws, KS_SORT, 2ull * acc * sizeof(pos_t));
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(sort_compose_kernel<pos_t>), dim3(grid_for((acc + 7) / 8, 32768)), dim3(256), 0, st, Pa, d_off64, (uint64_t)nd, acc, bits, ka);
-        rocprim::double_buffer<uint64_t> keys(ka, kb);
-        size_t tb = sort_tmp;
-        VLG_HIP_TRY(rocprim::radix_sort_keys(d_tmp, tb, keys, acc, 0, bits + list_bits, st));
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(sort_narrow_kernel<pos_t>), dim3(grid_for(acc, 32768)), dim3(256), 0, st, keys.current(), acc, bits, Pa);
-        VLG_HIP_TRY(hipGetLastError());
-        P_out = Pa;
-    } else {
-        Timed t(ws, KS_SORT, 2ull * acc * sizeof(pos_t));
-        size_t tb = sort_tmp;
-        VLG_HIP_TRY(rocprim::segmented_radix_sort_keys(d_tmp, tb, Pa, Pb, (unsigned)acc, nd, d_off32, d_off32 + 1, 0, bits, st));
-        P_out = Pb;
-        if (ws->x_ranks > 1) {                                // the pieces of all ranks meet in ONE array: back to the share's place
-            VLG_HIP_TRY(hipMemcpyAsync(Pa, Pb, acc * sizeof(pos_t), hipMemcpyDeviceToDevice, st));
-            P_out = Pa;
+
+    // every occurrence list ascending (std::sort, index_sasearch.hpp:80); -> where the sorted share lies
+    vlg_status sort(pos_t*& P)
+    {
+        P = Pa;
+        if (!acc) return VLG_OK;
+        if (lsp.ready) {
+            // 32-bit positions: sorted inside every list (list_sort.hpp) -- 4 passes of 8 B per element instead of 6 of 16 B
+            Timed t(ws, KS_SORT, 2ull * acc * sizeof(pos_t));
+            if (vlg_status ls = list_sort_enqueue(lsp, reinterpret_cast<uint32_t*>(Pa), reinterpret_cast<uint32_t*>(scratch), d_off64, c.pos_bits, st, ws->list_sort == 1)) return ls;
+            A.used = sort_mark;                               // its tables are dead once its kernels have run (stream order)
+        } else if (c.global_sort) {
+            // one radix sort of (list, position) keys: the passes stream the whole batch whatever the list sizes are
+            const unsigned bits = c.pos_bits, list_bits = bit_width64(nd);
+            uint64_t* ka = reinterpret_cast<uint64_t*>(scratch);
+            uint64_t* kb = ka + acc;
+            Timed t(ws, KS_SORT, 2ull * acc * sizeof(pos_t));
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(sort_compose_kernel<pos_t>), dim3(grid_for((acc + 7) / 8, 32768)), dim3(256), 0, st, Pa, d_off64, (uint64_t)nd, acc, bits, ka);
+            rocprim::double_buffer<uint64_t> keys(ka, kb);
+            size_t tb = cp.sort_tmp;
+            VLG_HIP_TRY(rocprim::radix_sort_keys(d_tmp, tb, keys, acc, 0, bits + list_bits, st));
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(sort_narrow_kernel<pos_t>), dim3(grid_for(acc, 32768)), dim3(256), 0, st, keys.current(), acc, bits, Pa);
+            VLG_HIP_TRY(hipGetLastError());
+        } else {
+            Timed t(ws, KS_SORT, 2ull * acc * sizeof(pos_t));
+            size_t tb = cp.sort_tmp;
+            VLG_HIP_TRY(rocprim::segmented_radix_sort_keys(d_tmp, tb, Pa, Pb, (unsigned)acc, nd, d_off32, d_off32 + 1, 0, c.pos_bits, st));
+            P = Pb;
+            if (ws->x_ranks > 1) {                                // the pieces of all ranks meet in ONE array: back to the share's place
+                VLG_HIP_TRY(hipMemcpyAsync(Pa, Pb, acc * sizeof(pos_t), hipMemcpyDeviceToDevice, st));
+                P = Pa;
+            }
         }
+        return VLG_OK;
     }
-    // ---- the exchange step: the ranks' sorted shares meet ----------------------------------------------------------------------------------
-    const uint64_t* d_check_off = d_off64;
-    uint64_t check_nd = nd, check_acc = acc;
-    const pos_t* check_base = nullptr;                                  // (null: P_out)
-    if (ws->x_ranks > 1) {
+
+    // ---- the exchange step: the ranks' sorted shares meet in Pg ------------------------------------------------------------------------
+    vlg_status exchange(pos_t*& P, const vlg_queries* q, const std::vector<uint64_t>* xq, Agreement* ag)
+    {
+        if (ws->x_ranks <= 1) return VLG_OK;
         // every rank has come this far, or says so now (Agreement): nothing moves unless all of them are ready
         if (ag) if (vlg_status as = ag->settle(VLG_OK)) return as;
         const int n = ws->x_ranks, me = ws->x_rank;
-        const bool pairwise = !ws->exchange_all && !ws->x_fn && (ws->x_a2a || ws->x_comm) && q && xq && (int)xq->size() == n + 1;
+        pairwise = !ws->exchange_all && !ws->x_fn && (ws->x_a2a || ws->x_comm) && q && xq && (int)xq->size() == n + 1;
+        P = Pg;
         if (!pairwise) {
             // every list to every rank: one in-place all-gather of the shares
             Timed t(ws, KS_EXCHANGE, (gacc - acc) * sizeof(pos_t));
@@ -1054,107 +1085,103 @@ vlg_status build_physical(const vlg_index* idx, vlg_workspace* ws, vlg_result* r
             else if (ws->x_comm) rc = (int)vlg_comm_allgatherv(ws->x_comm, Pa, xcounts.data(), (uint32_t)sizeof(pos_t), Pg, st);
             else return fail(VLG_E_INTERNAL, "collective search without a communicator (or an all-to-all callback with \"exchange_all\")");
             if (rc) return ws->x_fn ? fail(VLG_E_INTERNAL, "the exchange callback failed with code " + std::to_string(rc)) : (vlg_status)rc;
-            d_check_off = d_goff64; check_nd = gnd; check_acc = gacc;
-        } else {
-            // needed lists only, pairwise.  Every rank computes the same table: need[r] = the lists the queries of rank r use; rank s
-            // owes rank r the lists of ITS share among them.  Lists that follow each other in the layout travel as one segment.
-            std::vector<uint32_t> place(pl.dl.size(), 0);               // distinct id -> place in the layout
-            for (uint32_t i = 0; i < gnd; ++i) place[dlist[i]] = i;
-            std::vector<uint8_t> need((size_t)n * gnd, 0);
-            for (int r = 0; r < n; ++r) {
-                uint8_t* nr = need.data() + (size_t)r * gnd;
-                for (uint64_t qi = (*xq)[r]; qi < (*xq)[r + 1]; ++qi)
-                    for (uint64_t sidx = q->qsub[qi]; sidx < q->qsub[qi + 1]; ++sidx)
-                        if (pl.occ[sidx]) nr[place[pl.did[sidx]]] = 1;
-            }
-            // segments (first element in Pg, length) of what `from` owes `to`, in layout order
-            auto segments = [&](int from, int to, svec<uint64_t>& src, svec<uint64_t>& dst, uint64_t& at) {
-                const uint8_t* nt = need.data() + (size_t)to * gnd;
-                for (uint32_t i = cut[from]; i < cut[from + 1];) {
-                    if (!nt[i] || goff64[i + 1] == goff64[i]) { ++i; continue; }
-                    uint32_t j = i;
-                    while (j < cut[from + 1] && nt[j]) ++j;
-                    src.push_back(goff64[i]);
-                    dst.push_back(at);
-                    at += goff64[j] - goff64[i];
-                    i = j;
-                }
-            };
-            svec<uint64_t> s_src, s_dst, r_src, r_dst;
-            std::vector<uint64_t> scount((size_t)n, 0), rcount((size_t)n, 0);
-            uint64_t s_at = 0, r_at = 0;
-            for (int r = 0; r < n; ++r) {
-                if (r == me) continue;                                   // (a rank's own lists are where they belong already)
-                uint64_t b = s_at;
-                segments(me, r, s_src, s_dst, s_at);
-                scount[r] = s_at - b;
-                b = r_at;
-                segments(r, me, r_src, r_dst, r_at);
-                rcount[r] = r_at - b;
-            }
-            s_dst.push_back(s_at);
-            r_dst.push_back(r_at);
-            const uint64_t ns = s_src.size(), nr_ = r_src.size();
-            pos_t* d_send = A.take<pos_t>(s_at + 1);
-            pos_t* d_recv = A.take<pos_t>(r_at + 1);
-            uint64_t* d_seg = A.take<uint64_t>(2 * (ns + nr_) + 4);
-            if (A.failed) return fail(VLG_E_WORKSPACE, "collective search: no room for the exchange buffers");
-            uint64_t* d_s_src = d_seg; uint64_t* d_s_dst = d_s_src + ns; uint64_t* d_r_src = d_s_dst + ns + 1; uint64_t* d_r_dst = d_r_src + nr_;
-            if (ns) VLG_HIP_TRY(hipMemcpyAsync(d_s_src, s_src.data(), ns * 8, hipMemcpyHostToDevice, st));
-            VLG_HIP_TRY(hipMemcpyAsync(d_s_dst, s_dst.data(), (ns + 1) * 8, hipMemcpyHostToDevice, st));
-            if (nr_) VLG_HIP_TRY(hipMemcpyAsync(d_r_src, r_src.data(), nr_ * 8, hipMemcpyHostToDevice, st));
-            VLG_HIP_TRY(hipMemcpyAsync(d_r_dst, r_dst.data(), (nr_ + 1) * 8, hipMemcpyHostToDevice, st));
-            Timed t(ws, KS_EXCHANGE, r_at * sizeof(pos_t));
-            if (s_at) hipLaunchKernelGGL(HIP_KERNEL_NAME(segments_copy_kernel<pos_t, true>), dim3(grid_for((s_at + 7) / 8, 16384)), dim3(256), 0, st, Pg, d_send, d_s_src, d_s_dst, ns, s_at);
-            VLG_HIP_TRY(hipGetLastError());
-            int rc = 0;
-            if (ws->x_a2a) rc = ws->x_a2a(ws->x_ctx, d_send, scount.data(), d_recv, rcount.data(), (uint32_t)sizeof(pos_t), n, me, st);
-            else rc = (int)vlg_comm_alltoallv(ws->x_comm, d_send, scount.data(), d_recv, rcount.data(), (uint32_t)sizeof(pos_t), st);
-            if (rc) return ws->x_a2a ? fail(VLG_E_INTERNAL, "the exchange callback failed with code " + std::to_string(rc)) : (vlg_status)rc;
-            if (r_at) hipLaunchKernelGGL(HIP_KERNEL_NAME(segments_copy_kernel<pos_t, false>), dim3(grid_for((r_at + 7) / 8, 16384)), dim3(256), 0, st, Pg, d_recv, d_r_src, d_r_dst, nr_, r_at);
-            VLG_HIP_TRY(hipGetLastError());
-            check_base = Pa;                                           // (lists no query of this rank uses hold nothing: only the own share is checked)
+            return VLG_OK;
         }
-        P_out = Pg;
+        // needed lists only, pairwise.  Every rank computes the same table: need[r] = the lists the queries of rank r use; rank s
+        // owes rank r the lists of ITS share among them.  Lists that follow each other in the layout travel as one segment.
+        std::vector<uint32_t> place(pl.dl.size(), 0);               // distinct id -> place in the layout
+        for (uint32_t i = 0; i < gnd; ++i) place[dlist[i]] = i;
+        std::vector<uint8_t> need((size_t)n * gnd, 0);
+        for (int r = 0; r < n; ++r) {
+            uint8_t* nr = need.data() + (size_t)r * gnd;
+            for (uint64_t qi = (*xq)[r]; qi < (*xq)[r + 1]; ++qi)
+                for (uint64_t sidx = q->qsub[qi]; sidx < q->qsub[qi + 1]; ++sidx)
+                    if (pl.occ[sidx]) nr[place[pl.did[sidx]]] = 1;
+        }
+        // segments (first element in Pg, length) of what `from` owes `to`, in layout order
+        auto segments = [&](int from, int to, svec<uint64_t>& src, svec<uint64_t>& dst, uint64_t& at) {
+            const uint8_t* nt = need.data() + (size_t)to * gnd;
+            for (uint32_t i = cut[from]; i < cut[from + 1];) {
+                if (!nt[i] || goff64[i + 1] == goff64[i]) { ++i; continue; }
+                uint32_t j = i;
+                while (j < cut[from + 1] && nt[j]) ++j;
+                src.push_back(goff64[i]);
+                dst.push_back(at);
+                at += goff64[j] - goff64[i];
+                i = j;
+            }
+        };
+        svec<uint64_t> s_src, s_dst, r_src, r_dst;
+        std::vector<uint64_t> scount((size_t)n, 0), rcount((size_t)n, 0);
+        uint64_t s_at = 0, r_at = 0;
+        for (int r = 0; r < n; ++r) {
+            if (r == me) continue;                                   // (a rank's own lists are where they belong already)
+            uint64_t b = s_at;
+            segments(me, r, s_src, s_dst, s_at);
+            scount[r] = s_at - b;
+            b = r_at;
+            segments(r, me, r_src, r_dst, r_at);
+            rcount[r] = r_at - b;
+        }
+        s_dst.push_back(s_at);
+        r_dst.push_back(r_at);
+        const uint64_t ns = s_src.size(), nr_ = r_src.size();
+        pos_t* d_send = A.take<pos_t>(s_at + 1);
+        pos_t* d_recv = A.take<pos_t>(r_at + 1);
+        uint64_t* d_seg = A.take<uint64_t>(2 * (ns + nr_) + 4);
+        if (A.failed) return fail(VLG_E_WORKSPACE, "collective search: no room for the exchange buffers");
+        uint64_t* d_s_src = d_seg; uint64_t* d_s_dst = d_s_src + ns; uint64_t* d_r_src = d_s_dst + ns + 1; uint64_t* d_r_dst = d_r_src + nr_;
+        if (ns) VLG_HIP_TRY(hipMemcpyAsync(d_s_src, s_src.data(), ns * 8, hipMemcpyHostToDevice, st));
+        VLG_HIP_TRY(hipMemcpyAsync(d_s_dst, s_dst.data(), (ns + 1) * 8, hipMemcpyHostToDevice, st));
+        if (nr_) VLG_HIP_TRY(hipMemcpyAsync(d_r_src, r_src.data(), nr_ * 8, hipMemcpyHostToDevice, st));
+        VLG_HIP_TRY(hipMemcpyAsync(d_r_dst, r_dst.data(), (nr_ + 1) * 8, hipMemcpyHostToDevice, st));
+        Timed t(ws, KS_EXCHANGE, r_at * sizeof(pos_t));
+        if (s_at) hipLaunchKernelGGL(HIP_KERNEL_NAME(segments_copy_kernel<pos_t, true>), dim3(grid_for((s_at + 7) / 8, 16384)), dim3(256), 0, st, Pg, d_send, d_s_src, d_s_dst, ns, s_at);
+        VLG_HIP_TRY(hipGetLastError());
+        int rc = 0;
+        if (ws->x_a2a) rc = ws->x_a2a(ws->x_ctx, d_send, scount.data(), d_recv, rcount.data(), (uint32_t)sizeof(pos_t), n, me, st);
+        else rc = (int)vlg_comm_alltoallv(ws->x_comm, d_send, scount.data(), d_recv, rcount.data(), (uint32_t)sizeof(pos_t), st);
+        if (rc) return ws->x_a2a ? fail(VLG_E_INTERNAL, "the exchange callback failed with code " + std::to_string(rc)) : (vlg_status)rc;
+        if (r_at) hipLaunchKernelGGL(HIP_KERNEL_NAME(segments_copy_kernel<pos_t, false>), dim3(grid_for((r_at + 7) / 8, 16384)), dim3(256), 0, st, Pg, d_recv, d_r_src, d_r_dst, nr_, r_at);
+        VLG_HIP_TRY(hipGetLastError());
+        return VLG_OK;
     }
-    if (P_out == Pb) dead_bytes = gacc * kPhysScratchPerElem<pos_t>() - gacc * sizeof(pos_t);
-    else dead_bytes = (uint64_t)(scratch - reinterpret_cast<uint8_t*>(Pg)) + gacc * kPhysScratchPerElem<pos_t>() - gacc * sizeof(pos_t);
-    if (ws->x_ranks == 1 && P_out == Pa) P_out = Pg;          // (the same place: the one share starts at the beginning)
+
     // VLG_CHECK_SORT=1 (set by the tests): every list is verified ascending on the device after the sort -- list_sort.hpp leans on
     // the key order of rocPRIM's block_radix_rank, which a library upgrade could change silently
-    if (check_sort_enabled() && P_out) {
+    vlg_status check_sort()
+    {
+        if (!check_sort_enabled()) return VLG_OK;
+        const bool all = ws->x_ranks > 1 && !pairwise;     // (pairwise: lists no query of this rank uses hold nothing, only the own share is checked)
         unsigned long long* d_flags = A.take<unsigned long long>(2);
         if (!d_flags) return fail(VLG_E_INTERNAL, "arena carve failed (sort check)");
         unsigned long long flags[2] = {0, 0};
         VLG_HIP_TRY(hipMemsetAsync(d_flags, 0, 16, st));
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(lists_check_kernel<pos_t>), dim3(grid_for((check_acc + 7) / 8, 8192)), dim3(256), 0, st, check_base ? check_base : P_out, d_check_off, check_nd, check_acc, d_flags);
+        const uint64_t n = all ? gacc : acc;
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(lists_check_kernel<pos_t>), dim3(grid_for((n + 7) / 8, 8192)), dim3(256), 0, st, pairwise ? Pa : L.P, all ? d_goff64 : d_off64,
+                           (uint64_t)(all ? gnd : nd), n, d_flags);
         VLG_HIP_TRY(hipGetLastError());
         VLG_HIP_TRY(hipMemcpyAsync(flags, d_flags, 16, hipMemcpyDeviceToHost, st));
         VLG_HIP_TRY(hipStreamSynchronize(st));
         if (flags[0]) return fail(VLG_E_INTERNAL, "an occurrence list is not ascending after the sort (VLG_CHECK_SORT)");
+        return VLG_OK;
     }
-    // no wait here: the staging vectors live in the workspace's pinned pool until the batch ends, so the caller plans the
-    // window filter while the sort runs
+
+    // room for the survivors of the window filter behind the sorted lists (the dead scratch), the fences of both and the ladder
+    vlg_status fences_and_ladder()
     {
+        const uint64_t dead_bytes = (L.P == Pb ? 0 : (uint64_t)(scratch - reinterpret_cast<uint8_t*>(Pg))) + gacc * kPhysScratchPerElem<pos_t>() - gacc * sizeof(pos_t);
         const uint64_t pc_first = align_up(gacc, 64);
         if (dead_bytes > (pc_first - gacc + 64) * sizeof(pos_t) && pc_first < 0xFFFFFF00ull) {
-            Pc_out = P_out + pc_first;
-            pc_cap = std::min<uint64_t>(dead_bytes / sizeof(pos_t) - (pc_first - gacc) - 64, 0xFFFFFF00ull - pc_first);
+            L.Pc = L.P + pc_first;
+            L.pc_cap = std::min<uint64_t>(dead_bytes / sizeof(pos_t) - (pc_first - gacc) - 64, 0xFFFFFF00ull - pc_first);
         }
-    }
-    // fences of the sorted lists (and room for those of the survivors' lists behind them)
-    ws->fences = nullptr;
-    ws->rungs = nullptr;
-    if (P_out) {
-        const uint64_t cover = Pc_out ? (uint64_t)(Pc_out - P_out) + pc_cap : gacc;
+        const uint64_t cover = L.Pc ? (uint64_t)(L.Pc - L.P) + L.pc_cap : gacc;
         const uint64_t entries = cover / 64 + 2;
-        if (!A.failed && A.size - A.used > entries * sizeof(pos_t) + 4096) {
-            pos_t* F = A.take<pos_t>(entries);
-            ws->fences = F;
-        }
+        if (!A.failed && A.size - A.used > entries * sizeof(pos_t) + 4096) L.F = A.take<pos_t>(entries);
         // the ladder for the pivot filter (a third of the lists' size): only when the window filter will run on these lists
         bool fences_written = false;
-        if (ws->fences && ws->want_rungs && gacc >= 64) {
+        if (L.F && cp.want_rungs && gacc >= 64) {
             const RungLayout rl = rung_layout(gacc);
             if (A.size - A.used > rl.entries * sizeof(pos_t) + 8192) {
                 pos_t* R = A.take<pos_t>(rl.entries);
@@ -1164,21 +1191,43 @@ vlg_status build_physical(const vlg_index* idx, vlg_workspace* ws, vlg_result* r
                 fences_written = kRungsHoldFences && rl.levels >= 6 / kRungShift;      // the fences are one of its levels: written on the way
                 {
                     Timed t(ws, KS_FILTER_LADDER, gacc * sizeof(pos_t));
-                    hipLaunchKernelGGL(HIP_KERNEL_NAME(rung_build_kernel<pos_t>), dim3(grid_for(gacc >> kRungShift, 16384)), dim3(256), 0, st, P_out, gacc, R, d_off,
-                                       rl.levels, fences_written ? static_cast<pos_t*>(ws->fences) : (pos_t*)nullptr);
+                    hipLaunchKernelGGL(HIP_KERNEL_NAME(rung_build_kernel<pos_t>), dim3(grid_for(gacc >> kRungShift, 16384)), dim3(256), 0, st, L.P, gacc, R, d_off,
+                                       rl.levels, fences_written ? L.F : (pos_t*)nullptr);
                 }
                 VLG_HIP_TRY(hipGetLastError());
-                ws->rungs = R;
-                ws->rung_off = d_off;
+                L.R = R;
+                L.roff = d_off;
             }
         }
-        if (ws->fences && !fences_written && gacc >= 64) {
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(fence_build_kernel<pos_t>), dim3(grid_for(gacc / 64, 8192)), dim3(256), 0, st, P_out, (uint64_t)0, gacc / 64,
-                               static_cast<pos_t*>(ws->fences));
+        if (L.F && !fences_written && gacc >= 64) {
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(fence_build_kernel<pos_t>), dim3(grid_for(gacc / 64, 8192)), dim3(256), 0, st, L.P, (uint64_t)0, gacc / 64, L.F);
             VLG_HIP_TRY(hipGetLastError());
         }
+        return VLG_OK;
     }
-    res->sum.located_occurrences += acc;
+};
+
+// -> L: the sorted lists of the super-chunk (L.doff: where every distinct list of it starts), the room behind them, fences and ladder.
+// q, xq, ag: collective search (the ranks' query cuts; the agreement, settled right before the exchange).
+template <typename pos_t>
+vlg_status build_physical(const vlg_index* idx, vlg_workspace* ws, vlg_result* res, const Plan& pl, const SuperChunk& sc, const ChunkPlan& cp, bool wide,
+                          Arena& A, unsigned long long* d_stats, Lists<pos_t>& L, const vlg_queries* q = nullptr, const std::vector<uint64_t>* xq = nullptr,
+                          Agreement* ag = nullptr)
+{
+    L.P = L.Pc = L.F = L.R = nullptr; L.pc_cap = 0; L.roff = nullptr;
+    PhysicalPass<pos_t> pp{idx, ws, res, pl, cp, wide, A, d_stats, L};
+    pp.layout(sc.dlist);
+    if (!pp.gacc) return ag ? ag->settle(VLG_OK) : VLG_OK;              // (every rank sees the same empty plan and settles too)
+    const std::function<vlg_status()> plan_sort = [&pp]() { return pp.plan_sort(); };
+    if (vlg_status s = pp.carve()) return s;
+    if (vlg_status s = pp.locate(plan_sort)) return s;
+    if (vlg_status s = pp.sort(L.P)) return s;
+    if (vlg_status s = pp.exchange(L.P, q, xq, ag)) return s;
+    if (vlg_status s = pp.check_sort()) return s;
+    // no wait here: the staging vectors live in the workspace's pinned pool until the batch ends, so the caller plans the
+    // window filter while the sort runs
+    if (vlg_status s = pp.fences_and_ladder()) return s;
+    res->sum.located_occurrences += pp.acc;
     return VLG_OK;
 }
 
@@ -1190,12 +1239,13 @@ namespace {
 
 // ---- join of the queries [q0,q1) against the physical lists -------------------------------------------
 template <typename pos_t>
-vlg_status run_join_chunk(const vlg_queries* q, vlg_workspace* ws, vlg_result* res, uint64_t q0, uint64_t q1,
-                          const Plan& pl, const std::vector<uint32_t>& poff /* per sub-pattern: its list inside P */, const pos_t* P,
-                          Arena A /* by value: scratch past P */,
-                          unsigned long long* d_stats, const FilterGroup* fg, pos_t* Pc /* survivors of filtered lists go here */)
+vlg_status run_join_chunk(const vlg_queries* q, vlg_workspace* ws, vlg_result* res, uint64_t q0, uint64_t q1, const Plan& pl, const Lists<pos_t>& L,
+                          Arena A /* by value: scratch past the lists */, unsigned long long* d_stats, const FilterGroup* fg)
 {
     hipStream_t st = ws->stream;
+    const pos_t* P = L.P;
+    pos_t* Pc = L.Pc;                   // survivors of filtered lists go here
+    const std::vector<uint32_t>& poff = L.off;
     PhaseTrace jt(st);
     // list lengths as the join sees them: the survivors of the window filter where it ran
     auto eo = [&](uint64_t s) -> uint64_t { return fg ? fg->eff[s - fg->sub0] : pl.occ[s]; };
@@ -1255,14 +1305,13 @@ vlg_status run_join_chunk(const vlg_queries* q, vlg_workspace* ws, vlg_result* r
                                dim3(256), 0, st, P, fg->d_segs, d_tseg, d_trun0, (uint32_t)t_seg.size(), fg->d_abits, d_cnt, d_off, Pc, ~0ull, ws->compact_dense_min);
         }
         // fences of the survivors' lists: whole blocks of [Pc, Pc + pc_total) (Pc starts on a block)
-        if (ws->fences && pc_total >= 64) {
+        if (L.F && pc_total >= 64) {
             const uint64_t g0 = (uint64_t)(Pc - P) / 64;
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(fence_build_kernel<pos_t>), dim3(grid_for(pc_total / 64, 8192)), dim3(256), 0, st, P, g0, g0 + pc_total / 64,
-                               static_cast<pos_t*>(ws->fences));
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(fence_build_kernel<pos_t>), dim3(grid_for(pc_total / 64, 8192)), dim3(256), 0, st, P, g0, g0 + pc_total / 64, L.F);
         }
         VLG_HIP_TRY(hipGetLastError());
     }
-    const pos_t* F = static_cast<const pos_t*>(ws->fences);
+    const pos_t* F = L.F;
     jt.mark("  chunk: compaction launched");
     std::vector<uint32_t> cls_count(kmax + 1, 0), cls_first(kmax + 2, 0);   // segments per dist class
     for (uint64_t qi = q0; qi < q1; ++qi) {
@@ -1573,14 +1622,14 @@ vlg_status plan_joins(const vlg_queries* q, const Plan& pl, const vlg_workspace*
     return VLG_OK;
 }
 
-// groups of queries that share one run of the filter; join chunks inside a group.  A = arena behind the lists; Pc / pc_cap = where
-// (inside the allocation of P) the survivors of filtered lists may go.
+// groups of queries that share one run of the filter; join chunks inside a group.  A = arena behind the lists; L.Pc / L.pc_cap = where
+// (inside the allocation of L.P) the survivors of filtered lists may go.
 template <typename pos_t>
-vlg_status run_joins(uint64_t n_positions, const vlg_queries* q, vlg_workspace* ws, vlg_result* res, const Plan& pl,
-                     const std::vector<uint32_t>& poff, const pos_t* P, const Arena& A, pos_t* Pc, uint64_t pc_cap, uint64_t Q0, uint64_t Q1,
-                     const JoinPlan& jp, unsigned long long* d_stats, PhaseTrace& tr)
+vlg_status run_joins(uint64_t n_positions, const vlg_queries* q, vlg_workspace* ws, vlg_result* res, const Plan& pl, const Lists<pos_t>& L,
+                     const Arena& A, uint64_t Q0, uint64_t Q1, const JoinPlan& jp, unsigned long long* d_stats, PhaseTrace& tr)
 {
     const uint64_t max_chunk_slots = 0xF0000000ull;
+    const uint64_t pc_cap = L.pc_cap;
     uint64_t g0 = Q0;
     while (g0 < Q1) {
         Arena GA = A;
@@ -1597,7 +1646,7 @@ vlg_status run_joins(uint64_t n_positions, const vlg_queries* q, vlg_workspace* 
         fg.g1 = g1;
         const FilterGroup* fgp = nullptr;
         if (fb) {
-            if (vlg_status s = filter_group<pos_t>(n_positions, q, ws, pl, poff, P, GA, fg, Pc)) return s;
+            if (vlg_status s = filter_group<pos_t>(n_positions, q, ws, pl, L, GA, fg)) return s;
             if (fg.any) fgp = &fg;
             tr.mark("filter group");
         }
@@ -1628,7 +1677,7 @@ vlg_status run_joins(uint64_t n_positions, const vlg_queries* q, vlg_workspace* 
                 T += t; S += sl; C += pc;
                 ++q1;
             }
-            vlg_status s = run_join_chunk<pos_t>(q, ws, res, q0, q1, pl, poff, P, GA, d_stats, fgp, Pc);
+            vlg_status s = run_join_chunk<pos_t>(q, ws, res, q0, q1, pl, L, GA, d_stats, fgp);
             if (s) return s;
             tr.mark("join chunk");
             q0 = q1;
@@ -1636,6 +1685,150 @@ vlg_status run_joins(uint64_t n_positions, const vlg_queries* q, vlg_workspace* 
         g0 = g1;
     }
     return VLG_OK;
+}
+
+// The next super-chunk from query Q0 on: whole queries while their distinct lists fit phys_cap.  stamp[d] == epoch marks the lists
+// taken into the super-chunk in work (epoch counts the super-chunks).
+vlg_status next_super_chunk(const vlg_queries* q, const Plan& pl, bool dedup, uint64_t phys_cap, uint64_t Q0, std::vector<uint32_t>& stamp, uint32_t& epoch,
+                            SuperChunk& sc)
+{
+    std::vector<uint32_t>& dlist = sc.dlist;
+    dlist.reserve(pl.dl.size());
+    uint64_t phys = 0, Q1 = Q0;
+    if (Q0 == 0 && dedup) {
+        // the usual case, without a walk over the sub-patterns: every distinct list of the batch fits one super-chunk
+        // (with dedup every id belongs to a live sub-pattern; the ids are already in ascending order)
+        uint64_t all = 0;
+        for (uint64_t d = 0; d < pl.docc.size() && all <= phys_cap; ++d) all += pl.docc[d];
+        if (all <= phys_cap) {
+            phys = all;
+            Q1 = q->nq;
+            dlist.resize(pl.dl.size());
+            for (uint32_t d = 0; d < (uint32_t)pl.dl.size(); ++d) dlist[d] = d;
+            std::fill(stamp.begin(), stamp.end(), epoch);
+        }
+    }
+    while (Q1 < q->nq) {
+        uint64_t add = 0;
+        size_t mark = dlist.size();
+        for (uint64_t s = q->qsub[Q1]; s < q->qsub[Q1 + 1]; ++s)
+            if (pl.occ[s] && stamp[pl.did[s]] != epoch) { stamp[pl.did[s]] = epoch; dlist.push_back(pl.did[s]); add += pl.occ[s]; }
+        if (phys + add > phys_cap) {
+            for (size_t i = mark; i < dlist.size(); ++i) stamp[dlist[i]] = 0xFFFFFFFFu;
+            dlist.resize(mark);
+            if (Q1 == Q0)
+                return fail(VLG_E_WORKSPACE, "query " + std::to_string(Q1) + " needs " + std::to_string(add) +
+                                                 " occurrence slots; workspace cap allows " + std::to_string(phys_cap));
+            break;
+        }
+        phys += add;
+        ++Q1;
+    }
+    ++epoch;
+    // distinct lists in ascending id order: SA order when the plan came from the device (ids are ranks of the intervals), which is
+    // the order the sorted sweep wants to start in
+    if (dlist.size() > 1) {
+        if (dlist.size() * 8 >= pl.dl.size()) {               // most ids are used: walk the stamps instead of sorting
+            size_t w = 0;
+            for (uint32_t d = 0; d < (uint32_t)pl.dl.size(); ++d) if (stamp[d] == epoch - 1) dlist[w++] = d;
+        } else std::sort(dlist.begin(), dlist.end());
+    }
+    sc.Q0 = Q0; sc.Q1 = Q1; sc.phys = phys;
+    return VLG_OK;
+}
+
+// The arena of a super-chunk: what the physical pass does and needs (sort temporaries, shared LF steps, ladder), and the join budget
+// that leaves.  budget: the workspace cap less `fixed` (alignment slack + per-chunk metadata).
+template <typename pos_t>
+vlg_status plan_super_chunk(const vlg_index* idx, const vlg_queries* q, const Plan& pl, vlg_workspace* ws, const SuperChunk& sc, bool wide,
+                            uint64_t budget, uint64_t fixed, bool trace, ChunkPlan& cp)
+{
+    const uint64_t phys = sc.phys, Q0 = sc.Q0, Q1 = sc.Q1;
+    const std::vector<uint32_t>& dlist = sc.dlist;
+    // (K3u is judged on one rank's share: the pass decides on the share it got)
+    cp.c = choose_physical<pos_t>(idx, ws, phys, dlist.size(), wide, phys / (uint64_t)std::max(1, ws->x_ranks), 0, nullptr);
+    // (the library's size queries are not free -- a few hundred microseconds each -- and batches repeat: the last answer is kept)
+    const uint64_t tmp_key[6] = {phys, dlist.size(), idx->hdr.n, ((uint64_t)idx->hdr.sigma << 8) | ((uint64_t)ws->sweep << 1) | (uint64_t)idx->is_int | (sizeof(pos_t) << 4),
+                                 ws->global_sort_min, ws->sweep_min};
+    if (phys && !memcmp(tmp_key, ws->tmp_key, sizeof tmp_key)) cp.sort_tmp = ws->tmp_bytes;
+    else if (phys) {
+        if (cp.c.global_sort) {
+            rocprim::double_buffer<uint64_t> nk(nullptr, nullptr);
+            VLG_HIP_TRY(rocprim::radix_sort_keys(nullptr, cp.sort_tmp, nk, phys, 0, 64, ws->stream));
+        } else {
+            pos_t* np = nullptr; uint32_t* nu = nullptr;
+            VLG_HIP_TRY(rocprim::segmented_radix_sort_keys(nullptr, cp.sort_tmp, np, np, (unsigned)phys, (unsigned)dlist.size(), nu, nu, 0,
+                                                           cp.c.pos_bits, ws->stream));
+        }
+        if (cp.c.sweep) cp.sort_tmp = std::max(cp.sort_tmp, sweep_temp_bytes(phys, idx->hdr.sigma, ws->stream));
+        memcpy(ws->tmp_key, tmp_key, sizeof tmp_key);
+        ws->tmp_bytes = cp.sort_tmp;
+    }
+    // per query: the largest join, and how many pivot elements the window filter will search from (for the ladder, below)
+    uint64_t logical_max_query = 0, pivot_elems = 0;
+    {
+        uint64_t part_max[kHostThreads] = {0}, part_piv[kHostThreads] = {0};
+        const bool count_pivots = ws->filter && ws->filter_pivot && ws->pivot_rungs;
+        parallel_slices(Q0, Q1, 1u << 16, [&](uint64_t a, uint64_t b, uint32_t t) {
+            uint64_t mx = 0, pv_sum = 0;
+            for (uint64_t qi = a; qi < b; ++qi) {
+                mx = std::max(mx, join_bytes_of(q, qi, [&](uint64_t s) -> uint64_t { return pl.occ[s]; }));
+                uint32_t pv = 0;
+                if (count_pivots && filter_mode(q, pl, ws, qi, &pv) == 2) pv_sum += pl.occ[q->qsub[qi] + pv];
+            }
+            part_max[t] = mx; part_piv[t] = pv_sum;
+        });
+        for (uint32_t t = 0; t < kHostThreads; ++t) { logical_max_query = std::max(logical_max_query, part_max[t]); pivot_elems += part_piv[t]; }
+    }
+    // the member bit-vector (32 B per 224 SA indices) and the records (8 B per occurrence) must leave room for the joins
+    uint64_t trail_bytes = cp.c.share_steps ? member_blocks(idx->hdr.n) * sizeof(Block) + phys * 9 + 2048 : 0;
+    // (+ fences: < 1 B per element; + the pivot filter's ladder, a third of the lists, when its searches outweigh building it:
+    // one pass over the lists against two descents per pivot element)
+    cp.want_rungs = pivot_elems && (ws->pivot_rungs == 2 || (pivot_elems >= phys / 16 && pivot_elems >= 4096));
+    const uint64_t rung_bytes = cp.want_rungs ? rung_layout(phys).entries * sizeof(pos_t) + 8192 : 0;
+    const uint64_t phys_plain = phys * (sizeof(pos_t) + kPhysScratchPerElem<pos_t>()) + cp.sort_tmp + (dlist.size() + 2) * 24 + (8ull << 20) + phys + rung_bytes;
+    if (trail_bytes) {
+        const uint64_t left = budget > phys_plain + trail_bytes ? budget - phys_plain - trail_bytes : 0;
+        if (left < std::max<uint64_t>(2 * logical_max_query, budget / 8)) trail_bytes = 0;
+    }
+    cp.c.share_steps = trail_bytes != 0;
+    if (trace) {
+        fprintf(stderr, "[vlg trace] super-chunk: %llu occurrences, %.1f GB physical, LF steps %s (%.1f GB), budget %.1f GB, largest join %.1f GB\n",
+                (unsigned long long)phys, phys_plain / 1e9, cp.c.share_steps ? "shared" : "not shared",
+                (member_blocks(idx->hdr.n) * sizeof(Block) + phys * 8) / 1e9, budget / 1e9, logical_max_query / 1e9);
+        uint64_t cnt[40] = {0}, sum[40] = {0};                                // where the occurrences are: distinct lists by size class
+        for (uint32_t d : dlist) { const unsigned b = bit_width64(pl.docc[d]); cnt[b]++; sum[b] += pl.docc[d]; }
+        fprintf(stderr, "[vlg trace] distinct lists by size (2^b: lists/occurrences):");
+        for (unsigned b = 0; b < 40; ++b) if (cnt[b]) fprintf(stderr, " %u:%llu/%llu", b, (unsigned long long)cnt[b], (unsigned long long)sum[b]);
+        fprintf(stderr, "\n");
+    }
+    cp.phys_bytes = phys_plain + trail_bytes;
+    cp.join_budget = budget > cp.phys_bytes ? budget - cp.phys_bytes : 0;
+    // When the arena already holds whatever a plan can ask for (the caller reserved the whole cap), locate + sort are launched
+    // first and the joins are planned while the GPU works; otherwise the plan decides how much to allocate.
+    const uint64_t meta_upper = (q->qsub[Q1] - q->qsub[Q0] + 4) * (sizeof(SegMeta) + 48) + (Q1 - Q0 + 4) * (sizeof(QueryMeta) + 96) +
+                                (budget / 8192 + (Q1 - Q0) + 8) * 48 + (1ull << 20);
+    cp.launch_first = ws->arena_bytes >= budget + meta_upper + 2 * fixed;
+    return VLG_OK;
+}
+
+// collective search: the queries [Q0, Q1) cut into one contiguous piece per rank of equal join work (slots of the non-final lists,
+// from the list lengths every rank knows): rank r filters and joins [xq[r], xq[r + 1]) only
+std::vector<uint64_t> cut_queries(const vlg_queries* q, const Plan& pl, uint64_t Q0, uint64_t Q1, int n_ranks)
+{
+    std::vector<uint64_t> cum(Q1 - Q0 + 1, 0);
+    for (uint64_t qi = Q0; qi < Q1; ++qi)
+        cum[qi - Q0 + 1] = cum[qi - Q0] + 1 + (pl.occ[q->qsub[qi]] ? join_slots_of(q, qi, [&](uint64_t sidx) -> uint64_t { return pl.occ[sidx]; }) : 0);
+    auto cut_at = [&](int r) -> uint64_t {
+        if (r <= 0) return Q0;
+        if (r >= n_ranks) return Q1;
+        const uint64_t target = cum.back() / (uint64_t)n_ranks * (uint64_t)r;
+        return Q0 + (uint64_t)(std::lower_bound(cum.begin(), cum.end(), target) - cum.begin());
+    };
+    std::vector<uint64_t> xq(n_ranks + 1);
+    xq[0] = Q0;
+    for (int r = 1; r <= n_ranks; ++r) xq[r] = std::max(xq[r - 1], std::min(cut_at(r), Q1));
+    return xq;
 }
 
 // A super-chunk = a run of queries whose distinct occurrence lists fit the physical budget; inside it
@@ -1648,171 +1841,37 @@ vlg_status run_batch(const vlg_index* idx, const vlg_queries* q, vlg_workspace* 
     if (ws->cap_bytes <= 2 * fixed) return fail(VLG_E_WORKSPACE, "workspace cap too small");
     const uint64_t budget = ws->cap_bytes - fixed;
     // physical lists take at most half of the budget (two buffers during the sort)
-    const uint64_t phys_per = sizeof(pos_t) + kPhysScratchPerElem<pos_t>();
-    const uint64_t phys_cap = std::min<uint64_t>(budget / 2 / (phys_per + 1), 0xFFFFFF00ull);
+    const uint64_t phys_cap = std::min<uint64_t>(budget / 2 / (sizeof(pos_t) + kPhysScratchPerElem<pos_t>() + 1), 0xFFFFFF00ull);
     std::vector<uint32_t> stamp(pl.dl.size(), 0xFFFFFFFFu);
-    std::vector<uint32_t> poff(pl.dl.size(), 0);
-    std::vector<uint32_t> poff_sub(q->nsub, 0);
-    uint64_t Q0 = 0;
+    Lists<pos_t> L;
+    L.doff.assign(pl.dl.size(), 0);
+    L.off.assign(q->nsub, 0);
     uint32_t epoch = 0;
     PhaseTrace tr(ws->stream);
-    while (Q0 < q->nq) {
-        // ---- choose the super-chunk ----------------------------------------------------------------
-        std::vector<uint32_t> dlist;
-        dlist.reserve(pl.dl.size());
-        uint64_t phys = 0, Q1 = Q0;
-        if (Q0 == 0 && ws->dedup) {
-            // the usual case, without a walk over the sub-patterns: every distinct list of the batch fits one super-chunk
-            // (with dedup every id belongs to a live sub-pattern; the ids are already in ascending order)
-            uint64_t all = 0;
-            for (uint64_t d = 0; d < pl.docc.size() && all <= phys_cap; ++d) all += pl.docc[d];
-            if (all <= phys_cap) {
-                phys = all;
-                Q1 = q->nq;
-                dlist.resize(pl.dl.size());
-                for (uint32_t d = 0; d < (uint32_t)pl.dl.size(); ++d) dlist[d] = d;
-                std::fill(stamp.begin(), stamp.end(), epoch);
-            }
-        }
-        while (Q1 < q->nq) {
-            uint64_t add = 0;
-            size_t mark = dlist.size();
-            for (uint64_t s = q->qsub[Q1]; s < q->qsub[Q1 + 1]; ++s)
-                if (pl.occ[s] && stamp[pl.did[s]] != epoch) { stamp[pl.did[s]] = epoch; dlist.push_back(pl.did[s]); add += pl.occ[s]; }
-            if (phys + add > phys_cap) {
-                for (size_t i = mark; i < dlist.size(); ++i) stamp[dlist[i]] = 0xFFFFFFFFu;
-                dlist.resize(mark);
-                if (Q1 == Q0)
-                    return fail(VLG_E_WORKSPACE, "query " + std::to_string(Q1) + " needs " + std::to_string(add) +
-                                                     " occurrence slots; workspace cap allows " + std::to_string(phys_cap));
-                break;
-            }
-            phys += add;
-            ++Q1;
-        }
-        ++epoch;
-        // distinct lists in ascending id order: SA order when the plan came from the device (ids are ranks of the intervals), which is
-        // the order the sorted sweep wants to start in
-        if (dlist.size() > 1) {
-            if (dlist.size() * 8 >= pl.dl.size()) {               // most ids are used: walk the stamps instead of sorting
-                size_t w = 0;
-                for (uint32_t d = 0; d < (uint32_t)pl.dl.size(); ++d) if (stamp[d] == epoch - 1) dlist[w++] = d;
-            } else std::sort(dlist.begin(), dlist.end());
-        }
-        // ---- arena: physical lists first, filter state and join scratch behind them ---------------------
-        size_t sort_tmp = 0;
-        // (the library's size queries are not free -- a few hundred microseconds each -- and batches repeat: the last answer is kept)
-        const uint64_t tmp_key[6] = {phys, dlist.size(), idx->hdr.n, ((uint64_t)idx->hdr.sigma << 8) | ((uint64_t)ws->sweep << 1) | (uint64_t)idx->is_int | (sizeof(pos_t) << 4),
-                                     ws->global_sort_min, ws->sweep_min};
-        if (phys && !memcmp(tmp_key, ws->tmp_key, sizeof tmp_key)) sort_tmp = ws->tmp_bytes;
-        else if (phys) {
-            // the sort build_physical will choose (same condition there): one radix sort of (list, position) keys, or a segmented one
-            const unsigned pos_bits = std::max(1u, bit_width64(idx->hdr.n >= 2 ? idx->hdr.n - 2 : 0));
-            if (phys >= ws->global_sort_min && pos_bits + bit_width64(dlist.size()) <= 64) {
-                rocprim::double_buffer<uint64_t> nk(nullptr, nullptr);
-                VLG_HIP_TRY(rocprim::radix_sort_keys(nullptr, sort_tmp, nk, phys, 0, 64, ws->stream));
-            } else {
-                pos_t* np = nullptr; uint32_t* nu = nullptr;
-                VLG_HIP_TRY(rocprim::segmented_radix_sort_keys(nullptr, sort_tmp, np, np, (unsigned)phys, (unsigned)dlist.size(), nu, nu, 0,
-                                                               pos_bits, ws->stream));
-            }
-            if (ws->sweep && phys >= ws->sweep_min && (!idx->is_int || int_sweep_possible(idx->iview)))
-                sort_tmp = std::max(sort_tmp, sweep_temp_bytes(phys, idx->hdr.sigma, ws->stream));
-            memcpy(ws->tmp_key, tmp_key, sizeof tmp_key);
-            ws->tmp_bytes = sort_tmp;
-        }
-        const bool will_sweep = ws->sweep && phys >= ws->sweep_min && (!idx->is_int || int_sweep_possible(idx->iview));
-        // per query: the largest join, and how many pivot elements the window filter will search from (for the ladder, below)
-        uint64_t logical_max_query = 0, pivot_elems = 0;
-        {
-            uint64_t part_max[kHostThreads] = {0}, part_piv[kHostThreads] = {0};
-            const bool count_pivots = ws->filter && ws->filter_pivot && ws->pivot_rungs;
-            parallel_slices(Q0, Q1, 1u << 16, [&](uint64_t a, uint64_t b, uint32_t t) {
-                uint64_t mx = 0, pv_sum = 0;
-                for (uint64_t qi = a; qi < b; ++qi) {
-                    mx = std::max(mx, join_bytes_of(q, qi, [&](uint64_t s) -> uint64_t { return pl.occ[s]; }));
-                    uint32_t pv = 0;
-                    if (count_pivots && filter_mode(q, pl, ws, qi, &pv) == 2) pv_sum += pl.occ[q->qsub[qi] + pv];
-                }
-                part_max[t] = mx; part_piv[t] = pv_sum;
-            });
-            for (uint32_t t = 0; t < kHostThreads; ++t) { logical_max_query = std::max(logical_max_query, part_max[t]); pivot_elems += part_piv[t]; }
-        }
-        // the member bit-vector (32 B per 224 SA indices) and the records (8 B per occurrence) must leave room for the joins
-        // (an index that keeps the whole suffix array -- SA-order samples of density 1 -- walks nothing: no shared steps, no records)
-        const bool dense_sa = idx->hdr.dens == 1 && idx->hdr.sampling == kSamplingSaOrder;
-        // (nor does a batch dense enough to rebuild the whole suffix array, K3u: its arrays fit the sweep's scratch)
-        const bool will_unsample = will_sweep && !dense_sa && sizeof(pos_t) == 4 && unsample_applies(idx, ws, phys / (uint64_t)std::max(1, ws->x_ranks));
-        uint64_t trail_bytes = will_sweep && ws->trail && ws->dedup && !dense_sa && !will_unsample ? member_blocks(idx->hdr.n) * sizeof(Block) + phys * 9 + 2048 : 0;
-        // (+ fences: < 1 B per element; + the pivot filter's ladder, a third of the lists, when its searches outweigh building it:
-        // one pass over the lists against two descents per pivot element)
-        ws->want_rungs = pivot_elems && (ws->pivot_rungs == 2 || (pivot_elems >= phys / 16 && pivot_elems >= 4096));
-        const uint64_t rung_bytes = ws->want_rungs ? rung_layout(phys).entries * sizeof(pos_t) + 8192 : 0;
-        const uint64_t phys_plain = phys * phys_per + sort_tmp + (dlist.size() + 2) * 24 + (8ull << 20) + phys + rung_bytes;
-        if (trail_bytes) {
-            const uint64_t left = budget > phys_plain + trail_bytes ? budget - phys_plain - trail_bytes : 0;
-            if (left < std::max<uint64_t>(2 * logical_max_query, budget / 8)) trail_bytes = 0;
-        }
-        const bool share_trails = trail_bytes != 0;
-        if (tr.on) fprintf(stderr, "[vlg trace] super-chunk: %llu occurrences, %.1f GB physical, LF steps %s (%.1f GB), budget %.1f GB, largest join %.1f GB\n",
-                           (unsigned long long)phys, phys_plain / 1e9, share_trails ? "shared" : "not shared",
-                           (member_blocks(idx->hdr.n) * sizeof(Block) + phys * 8) / 1e9, budget / 1e9, logical_max_query / 1e9);
-        if (tr.on) {                                                          // where the occurrences are: distinct lists by size class
-            uint64_t cnt[40] = {0}, sum[40] = {0};
-            for (uint32_t d : dlist) { const unsigned b = bit_width64(pl.docc[d]); cnt[b]++; sum[b] += pl.docc[d]; }
-            fprintf(stderr, "[vlg trace] distinct lists by size (2^b: lists/occurrences):");
-            for (unsigned b = 0; b < 40; ++b) if (cnt[b]) fprintf(stderr, " %u:%llu/%llu", b, (unsigned long long)cnt[b], (unsigned long long)sum[b]);
-            fprintf(stderr, "\n");
-        }
-        const uint64_t phys_bytes = phys_plain + trail_bytes;
-        const uint64_t join_budget = budget > phys_bytes ? budget - phys_bytes : 0;
-        // When the arena already holds whatever a plan can ask for (the caller reserved the whole cap), locate + sort are launched
-        // first and the joins are planned while the GPU works; otherwise the plan decides how much to allocate.
-        const uint64_t meta_upper = (q->qsub[Q1] - q->qsub[Q0] + 4) * (sizeof(SegMeta) + 48) + (Q1 - Q0 + 4) * (sizeof(QueryMeta) + 96) +
-                                    (budget / 8192 + (Q1 - Q0) + 8) * 48 + (1ull << 20);
-        const bool launch_first = ws->arena_bytes >= budget + meta_upper + 2 * fixed;
-        // collective search: the queries of the super-chunk are cut into one contiguous piece per rank of equal join work (slots of the
-        // non-final lists, from the list lengths every rank knows); this rank filters and joins its piece [qa, qb) only
-        uint64_t qa = Q0, qb = Q1;
-        std::vector<uint64_t> xq;
+    for (uint64_t Q0 = 0; Q0 < q->nq;) {
+        SuperChunk sc;
+        if (vlg_status s = next_super_chunk(q, pl, ws->dedup, phys_cap, Q0, stamp, epoch, sc)) return s;
+        ChunkPlan cp;
+        if (vlg_status s = plan_super_chunk<pos_t>(idx, q, pl, ws, sc, wide, budget, fixed, tr.on, cp)) return s;
+        const std::vector<uint64_t> xq = ws->x_ranks > 1 ? cut_queries(q, pl, sc.Q0, sc.Q1, ws->x_ranks) : std::vector<uint64_t>{sc.Q0, sc.Q1};
+        const uint64_t qa = xq[ws->x_rank], qb = xq[ws->x_rank + 1];             // the queries this rank filters and joins
+        if (ws->x_ranks > 1) { res->owned.push_back(qa); res->owned.push_back(qb); }
         Agreement ag(ws);
-        if (ws->x_ranks > 1) {
-            std::vector<uint64_t> cum(Q1 - Q0 + 1, 0);
-            for (uint64_t qi = Q0; qi < Q1; ++qi)
-                cum[qi - Q0 + 1] = cum[qi - Q0] + 1 + (pl.occ[q->qsub[qi]] ? join_slots_of(q, qi, [&](uint64_t sidx) -> uint64_t { return pl.occ[sidx]; }) : 0);
-            auto cut_at = [&](int r) -> uint64_t {
-                if (r <= 0) return Q0;
-                if (r >= ws->x_ranks) return Q1;
-                const uint64_t target = cum.back() / (uint64_t)ws->x_ranks * (uint64_t)r;
-                return Q0 + (uint64_t)(std::lower_bound(cum.begin(), cum.end(), target) - cum.begin());
-            };
-            xq.resize(ws->x_ranks + 1);
-            xq[0] = Q0;
-            for (int r = 1; r <= ws->x_ranks; ++r) xq[r] = std::max(xq[r - 1], std::min(cut_at(r), Q1));
-            qa = xq[ws->x_rank];
-            qb = xq[ws->x_rank + 1];
-            res->owned.push_back(qa);
-            res->owned.push_back(qb);
-        }
         JoinPlan jp;
-        if (!launch_first) {
-            if (vlg_status s = plan_joins(q, pl, ws, qa, qb, join_budget, idx->hdr.n, jp)) { ag.mine = s; return s; }
-            if (vlg_status s = ws_reserve(ws, phys_bytes + jp.filter_need + jp.want_bytes + jp.meta + fixed)) { ag.mine = s; return s; }
+        if (!cp.launch_first) {
+            if (vlg_status s = plan_joins(q, pl, ws, qa, qb, cp.join_budget, idx->hdr.n, jp)) { ag.mine = s; return s; }
+            if (vlg_status s = ws_reserve(ws, cp.phys_bytes + jp.filter_need + jp.want_bytes + jp.meta + fixed)) { ag.mine = s; return s; }
         }
         Arena A{ws->arena, ws->arena_bytes};
-        pos_t* P = nullptr;
-        uint64_t Tphys = 0;
         tr.mark("plan super-chunk");
-        pos_t* Pc = nullptr;
-        uint64_t pc_cap = 0;
-        if (vlg_status s = build_physical<pos_t>(idx, ws, res, dlist, pl, A, P, poff, Tphys, sort_tmp, d_stats, Pc, pc_cap, share_trails, wide, will_unsample, q,
-                                                   ws->x_ranks > 1 ? &xq : nullptr, ws->x_ranks > 1 ? &ag : nullptr)) return s;
-        if (launch_first)
-            if (vlg_status s = plan_joins(q, pl, ws, qa, qb, join_budget, idx->hdr.n, jp)) return s;
+        if (vlg_status s = build_physical<pos_t>(idx, ws, res, pl, sc, cp, wide, A, d_stats, L, q, ws->x_ranks > 1 ? &xq : nullptr,
+                                                   ws->x_ranks > 1 ? &ag : nullptr)) return s;
+        if (cp.launch_first)
+            if (vlg_status s = plan_joins(q, pl, ws, qa, qb, cp.join_budget, idx->hdr.n, jp)) return s;
         tr.mark("locate + sort");
-        for (uint64_t s = q->qsub[Q0]; s < q->qsub[Q1]; ++s) poff_sub[s] = pl.occ[s] ? poff[pl.did[s]] : 0;
-        if (vlg_status s = run_joins<pos_t>(idx->hdr.n, q, ws, res, pl, poff_sub, P, A, Pc, pc_cap, qa, qb, jp, d_stats, tr)) return s;
-        Q0 = Q1;
+        for (uint64_t s = q->qsub[sc.Q0]; s < q->qsub[sc.Q1]; ++s) L.off[s] = pl.occ[s] ? L.doff[pl.did[s]] : 0;
+        if (vlg_status s = run_joins<pos_t>(idx->hdr.n, q, ws, res, pl, L, A, qa, qb, jp, d_stats, tr)) return s;
+        Q0 = sc.Q1;
     }
     return VLG_OK;
 }
@@ -1944,6 +2003,58 @@ vlg_status plan_on_device(const vlg_queries* q, vlg_workspace* ws, const uint64_
     return run();
 }
 
+// The same plan made on the host (no dedup, texts beyond 2^33 or an interval too long for its key on the device): the intervals are
+// copied back and numbered as they come.
+vlg_status plan_on_host(const vlg_queries* q, vlg_workspace* ws, const uint64_t* d_l, const uint64_t* d_r, Plan& pl, uint64_t& logical)
+{
+    hipStream_t st = ws->stream;
+    const uint64_t nsub = q->nsub;
+    svec<uint64_t> l(nsub), r(nsub);
+    if (nsub) {
+        VLG_HIP_TRY(hipMemcpyAsync(l.data(), d_l, nsub * 8, hipMemcpyDeviceToHost, st));
+        VLG_HIP_TRY(hipMemcpyAsync(r.data(), d_r, nsub * 8, hipMemcpyDeviceToHost, st));
+    }
+    VLG_HIP_TRY(hipStreamSynchronize(st));
+    // a query with an empty occurrence list has no match: none of its lists is materialised
+    // (vlg_index.hpp:315-316 returns at the first empty range)
+    pl.occ.assign(nsub, 0);
+    pl.did.assign(nsub, 0);
+    for (uint64_t qi = 0; qi < q->nq; ++qi) {
+        bool live = q->qsub[qi + 1] > q->qsub[qi];
+        for (uint64_t s = q->qsub[qi]; s < q->qsub[qi + 1] && live; ++s) live = (r[s] + 1 - l[s]) > 0;
+        if (live) for (uint64_t s = q->qsub[qi]; s < q->qsub[qi + 1]; ++s) pl.occ[s] = r[s] + 1 - l[s];
+    }
+    // identical SA intervals are the same occurrence list: locate + sort each distinct one once per
+    // super-chunk and let every query that uses it share the sorted list.
+    std::vector<uint64_t> order;
+    order.reserve(nsub);
+    for (uint64_t s = 0; s < nsub; ++s) if (pl.occ[s]) { order.push_back(s); logical += pl.occ[s]; }
+    if (ws->dedup) {
+        // open-addressing table keyed by the interval; ids in order of first appearance
+        uint64_t cap = 16;
+        while (cap < 2 * order.size()) cap <<= 1;
+        std::vector<uint32_t> table(cap, 0xFFFFFFFFu);
+        for (uint64_t s : order) {
+            uint64_t h = (l[s] * 0x9E3779B97F4A7C15ull) ^ (r[s] * 0xC2B2AE3D27D4EB4Full);
+            h ^= h >> 29;
+            uint64_t at = h & (cap - 1);
+            for (;; at = (at + 1) & (cap - 1)) {
+                const uint32_t d = table[at];
+                if (d == 0xFFFFFFFFu) {
+                    table[at] = (uint32_t)pl.dl.size();
+                    pl.did[s] = (uint32_t)pl.dl.size();
+                    pl.dl.push_back(l[s]); pl.docc.push_back(pl.occ[s]);
+                    break;
+                }
+                if (pl.dl[d] == l[s] && pl.docc[d] == pl.occ[s]) { pl.did[s] = d; break; }      // same l and same length = same interval
+            }
+        }
+    } else {
+        for (uint64_t s : order) { pl.did[s] = (uint32_t)pl.dl.size(); pl.dl.push_back(l[s]); pl.docc.push_back(pl.occ[s]); }
+    }
+    return VLG_OK;
+}
+
 }  // namespace
 
 extern "C" vlg_status vlg_search_batch(const vlg_index* idx, const vlg_queries* q, vlg_workspace* ws, vlg_result** out)
@@ -1996,53 +2107,8 @@ extern "C" vlg_status vlg_search_batch(const vlg_index* idx, const vlg_queries* 
             if (vlg_status s = plan_on_device(q, ws, d_l, d_r, idx->hdr.n, pl, res->sum.logical_occurrences, &fallback, plan_mem, plan_bytes)) return s;
             if (fallback) { device_plan = false; pl = Plan(); res->sum.logical_occurrences = 0; }
         }
-        if (!device_plan) {
-        svec<uint64_t> l(nsub), r(nsub);
-        if (nsub) {
-            VLG_HIP_TRY(hipMemcpyAsync(l.data(), d_l, nsub * 8, hipMemcpyDeviceToHost, st));
-            VLG_HIP_TRY(hipMemcpyAsync(r.data(), d_r, nsub * 8, hipMemcpyDeviceToHost, st));
-        }
-        VLG_HIP_TRY(hipStreamSynchronize(st));
-        // a query with an empty occurrence list has no match: none of its lists is materialised
-        // (vlg_index.hpp:315-316 returns at the first empty range)
-        pl.occ.assign(nsub, 0);
-        pl.did.assign(nsub, 0);
-        for (uint64_t qi = 0; qi < q->nq; ++qi) {
-            bool live = q->qsub[qi + 1] > q->qsub[qi];
-            for (uint64_t s = q->qsub[qi]; s < q->qsub[qi + 1] && live; ++s) live = (r[s] + 1 - l[s]) > 0;
-            if (live) for (uint64_t s = q->qsub[qi]; s < q->qsub[qi + 1]; ++s) pl.occ[s] = r[s] + 1 - l[s];
-        }
-        // identical SA intervals are the same occurrence list: locate + sort each distinct one once per
-        // super-chunk and let every query that uses it share the sorted list.
-        {
-            std::vector<uint64_t> order;
-            order.reserve(nsub);
-            for (uint64_t s = 0; s < nsub; ++s) if (pl.occ[s]) { order.push_back(s); res->sum.logical_occurrences += pl.occ[s]; }
-            if (ws->dedup) {
-                // open-addressing table keyed by the interval; ids in order of first appearance
-                uint64_t cap = 16;
-                while (cap < 2 * order.size()) cap <<= 1;
-                std::vector<uint32_t> table(cap, 0xFFFFFFFFu);
-                for (uint64_t s : order) {
-                    uint64_t h = (l[s] * 0x9E3779B97F4A7C15ull) ^ (r[s] * 0xC2B2AE3D27D4EB4Full);
-                    h ^= h >> 29;
-                    uint64_t at = h & (cap - 1);
-                    for (;; at = (at + 1) & (cap - 1)) {
-                        const uint32_t d = table[at];
-                        if (d == 0xFFFFFFFFu) {
-                            table[at] = (uint32_t)pl.dl.size();
-                            pl.did[s] = (uint32_t)pl.dl.size();
-                            pl.dl.push_back(l[s]); pl.docc.push_back(pl.occ[s]);
-                            break;
-                        }
-                        if (pl.dl[d] == l[s] && pl.docc[d] == pl.occ[s]) { pl.did[s] = d; break; }      // same l and same length = same interval
-                    }
-                }
-            } else {
-                for (uint64_t s : order) { pl.did[s] = (uint32_t)pl.dl.size(); pl.dl.push_back(l[s]); pl.docc.push_back(pl.occ[s]); }
-            }
-        }
-        }
+        if (!device_plan)
+            if (vlg_status s = plan_on_host(q, ws, d_l, d_r, pl, res->sum.logical_occurrences)) return s;
         tr.mark("intervals to host + plan");
         // SA indices are wide (33 bits, 64-bit samples) for n > 2^32; text positions still fit 32 bits up to n = 2^32 + 1 (the largest
         // one is n - 2), and then everything behind locate -- sort, fences, filter, join -- runs on 32-bit positions.
@@ -2211,7 +2277,8 @@ extern "C" vlg_status vlg_join_batch(const uint64_t* d_lists, const uint64_t* h_
         Plan pl;
         pl.occ.assign(qq.nsub, 0);
         pl.did.assign(qq.nsub, 0);
-        std::vector<uint32_t> poff(qq.nsub, 0);
+        Lists<uint64_t> L;
+        L.off.assign(qq.nsub, 0);
         for (uint64_t j = 0; j < n_joins; ++j) {
             if (qq.qsub[j + 1] < qq.qsub[j] || qq.qsub[j + 1] - qq.qsub[j] > VLG_MAX_SUBPATTERNS) return fail(VLG_E_INVALID, "bad join offsets");
             const uint32_t k = (uint32_t)(qq.qsub[j + 1] - qq.qsub[j]);
@@ -2226,7 +2293,7 @@ extern "C" vlg_status vlg_join_batch(const uint64_t* d_lists, const uint64_t* h_
                 live = live && h_list_off[s + 1] > h_list_off[s];
             }
             // a join with an empty list has no match: none of its lists is looked at (vlg_index.hpp:315-316)
-            if (live) for (uint64_t s = qq.qsub[j]; s < qq.qsub[j + 1]; ++s) { pl.occ[s] = h_list_off[s + 1] - h_list_off[s]; poff[s] = (uint32_t)h_list_off[s]; }
+            if (live) for (uint64_t s = qq.qsub[j]; s < qq.qsub[j + 1]; ++s) { pl.occ[s] = h_list_off[s + 1] - h_list_off[s]; L.off[s] = (uint32_t)h_list_off[s]; }
         }
         if (qq.kmin == 0xFFFFFFFFu) qq.kmin = 0;
         for (uint64_t s = 0; s < qq.nsub; ++s) res->sum.logical_occurrences += pl.occ[s];
@@ -2266,22 +2333,21 @@ extern "C" vlg_status vlg_join_batch(const uint64_t* d_lists, const uint64_t* h_
         JoinPlan jp;
         if (vlg_status s = plan_joins(&qq, pl, ws, 0, n_joins, budget - list_bytes, n_positions, jp)) return s;
         if (vlg_status s = ws_reserve(ws, list_bytes + jp.filter_need + jp.want_bytes + jp.meta + fixed)) return s;
-        ws->fences = nullptr;
-        ws->rungs = nullptr;
         Arena A{ws->arena, ws->arena_bytes};
-        uint64_t* P = A.take<uint64_t>(pc_first + pc_cap + 64);
+        L.P = A.take<uint64_t>(pc_first + pc_cap + 64);
         uint64_t* F = A.take<uint64_t>(fence_entries);
         if (A.failed) return fail(VLG_E_INTERNAL, "arena carve failed (join lists)");
         if (total) {
-            VLG_HIP_TRY(hipMemcpyAsync(P, d_lists, total * 8, hipMemcpyDeviceToDevice, st));
+            VLG_HIP_TRY(hipMemcpyAsync(L.P, d_lists, total * 8, hipMemcpyDeviceToDevice, st));
             if (total >= 64)
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(fence_build_kernel<uint64_t>), dim3(grid_for(total / 64, 8192)), dim3(256), 0, st, P, (uint64_t)0, total / 64, F);
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(fence_build_kernel<uint64_t>), dim3(grid_for(total / 64, 8192)), dim3(256), 0, st, L.P, (uint64_t)0, total / 64, F);
             VLG_HIP_TRY(hipGetLastError());
-            ws->fences = F;
+            L.F = F;
         }
+        L.Pc = pc_cap ? L.P + pc_first : nullptr;
+        L.pc_cap = pc_cap;
         tr.mark("join lists copied + checked");
-        if (vlg_status s = run_joins<uint64_t>(n_positions, &qq, ws, res, pl, poff, P, A, pc_cap ? P + pc_first : nullptr, pc_cap, 0, n_joins, jp,
-                                               d_stats, tr)) return s;
+        if (vlg_status s = run_joins<uint64_t>(n_positions, &qq, ws, res, pl, L, A, 0, n_joins, jp, d_stats, tr)) return s;
         unsigned long long hs[kStatsWords];
         VLG_HIP_TRY(hipMemcpyAsync(hs, d_stats, sizeof hs, hipMemcpyDeviceToHost, st));
         VLG_HIP_TRY(hipStreamSynchronize(st));
