@@ -528,6 +528,57 @@ vlg_status vlg_wtsa_range_walk_batch(const vlg_wtsa* idx, const uint64_t* d_l, c
 /* Level `level` of the tree as plain words (bit i = h_words[i >> 6] >> (i & 63), ceil(n / 64) words): bits [level * n, (level + 1) * n)
  * of wt_int::tree (include/sdsl/wt_int.hpp:162, 215-255) -- what m_wt.serialize stores (vlg_index.hpp:181-190). */
 vlg_status vlg_wtsa_export_level(const vlg_wtsa* idx, uint32_t level, uint64_t* h_words);
+/* The paper's index on disk: the file of vlg_index<alphabet_tag, wt_int<bit_vector_il<>, rank_support_il<>>> (the reference's default
+ * tree type, include/sdsl/vlg_index.hpp:116-119), what `store_to_file(idx, file)` writes (vlg_index.hpp:181-198: m_text, then m_wt):
+ *   m_text        int_vector<8> (byte_alphabet_tag): u64 size in bits, the bytes packed into u64 words; int_vector<0> (int_alphabet_tag):
+ *                 u64 size in bits, u8 width, the packed words (include/sdsl/sdsl_concepts.hpp:48-49, int_vector.hpp:584-600)
+ *   m_wt          wt_int::serialize (wt_int.hpp:708-732): u64 size n = |text| + 1, u64 sigma = n (one leaf per suffix-array value),
+ *                 the tree, three supports that store nothing (bit_vector_il.hpp:339-346, 509-516), u32 max_level
+ *                 L = hi(max(n - 1, 1)) + 1 (wt_int.hpp:194-204)
+ *   the tree      bit_vector_il<512>::serialize (bit_vector_il.hpp:201-213) of S = n * L bits, level l = bits [l * n, (l + 1) * n):
+ *                 u64 size S, u64 block_num = (S + 64) / 64 + (S + 512) / 512 + 1, u64 superblocks = (S + 512) / 512, u64 block_shift 9,
+ *                 m_data (int_vector<64>: a cumulative count word before every 8 data words, data word i at i + i / 8 + 1, the total
+ *                 ones last: :113-150) and m_rank_samples (int_vector<64>, empty unless block_num > 65536, then
+ *                 min(1024, 1 << hi(superblocks)) count words in the BFS order of init_rank_samples, :87-104).
+ * vlg_sdsl_wtsa_file_* parse such a file on the host only (no GPU needed); symbol_bytes 1 reads the byte tag, 4 the int tag.  Every
+ * header field is checked against n and L (text size n - 1, max_level, sigma, the il sizes, block_shift, the data and rank-sample
+ * lengths, a text width in 1..64), and a truncated file or trailing bytes are refused: VLG_E_INVALID -- which is also what a file
+ * stored with the other alphabet tag gives, and a path that is not a regular file (a directory, a pipe).  The rank samples are
+ * checked against the count words they copy.
+ * vlg_wtsa_from_parts converts on the device: the data words are gathered into the device tree, an integer text is unpacked to
+ * uint32_t.  Before a handle is returned the device checks that every cumulative count word and the final word equal the running
+ * popcount, that the bits past S are zero, that level l holds as many ones as there are values v in [0, n) with bit L - 1 - l set
+ * (true of every suffix-array tree), and that a byte text has no 0 byte; a failed check gives VLG_E_INVALID (VLG_E_ZERO_BYTE for the
+ * 0 byte) and no handle, an integer symbol >= 2^32 VLG_E_UNSUPPORTED, n > 2^32 - 16 VLG_E_UNSUPPORTED.  Whether the tree is the suffix
+ * array of the text is NOT checked, as the reference's load does not check it (vlg_index.hpp:193-197).  A loaded index equals the one
+ * vlg_wtsa_build makes of the same text: the same device tree, the same text.
+ * vlg_wtsa_load_sdsl = open + parts + from_parts.
+ * vlg_wtsa_save_sdsl writes the file; text_width is the width of m_text: a byte index takes 0 or 8; an integer index takes 0 (the width
+ * of the file it was loaded from, or hi(largest symbol) + 1, at least 1, for a built index) or 1..64 literally (VLG_E_INVALID when a
+ * symbol does not fit) -- the reference keeps whatever width its text had (construct_im of an int_vector<> stores 64 bits a symbol).
+ * vlg_wtsa_il_device assembles m_data (block_num words) of the tree into device memory d_words: what the save writes.  It is
+ * asynchronous on `stream`, like the other entry points that take one: synchronise before reading d_words. */
+typedef struct {
+    uint64_t n;                   /* wt.size() = |text| + 1                                                                   */
+    uint32_t symbol_bytes;        /* 1: byte_alphabet_tag, 4: int_alphabet_tag                                                */
+    uint32_t levels;              /* wt.max_level = L                                                                         */
+    const uint64_t* text_words;   /* m_text as stored: symbol i = bits [i * text_width, (i + 1) * text_width)                  */
+    uint64_t text_count;          /* n - 1 symbols                                                                            */
+    uint32_t text_width;          /* 8 for the byte tag, 1..64 for the int tag                                                */
+    uint32_t reserved;
+    const uint64_t* data;         /* bit_vector_il<512>::m_data                                                               */
+    uint64_t data_words;          /* its block_num                                                                            */
+    const uint64_t* rank_samples; /* bit_vector_il<512>::m_rank_samples                                                       */
+    uint64_t n_rank_samples;
+} vlg_wtsa_parts;
+typedef struct vlg_sdsl_wtsa_file vlg_sdsl_wtsa_file;
+vlg_status vlg_sdsl_wtsa_file_open(const char* path, uint32_t symbol_bytes, vlg_sdsl_wtsa_file** out);
+vlg_status vlg_sdsl_wtsa_file_parts(const vlg_sdsl_wtsa_file* f, vlg_wtsa_parts* parts);   /* pointers stay valid until close */
+void vlg_sdsl_wtsa_file_close(vlg_sdsl_wtsa_file* f);
+vlg_status vlg_wtsa_from_parts(const vlg_wtsa_parts* h_parts, vlg_wtsa** out);
+vlg_status vlg_wtsa_load_sdsl(const char* path, uint32_t symbol_bytes, vlg_wtsa** out);
+vlg_status vlg_wtsa_save_sdsl(const vlg_wtsa* idx, const char* path, uint32_t text_width);
+vlg_status vlg_wtsa_il_device(const vlg_wtsa* idx, uint64_t* d_words, uint64_t n_words, void* stream);
 /* forward_search(text.begin(), text.end(), wt, 0, wt.size()-1, pat.begin(), pat.end(), sp, ep)
  * (include/sdsl/suffix_array_algorithm.hpp:48-112) for every sub-pattern of the batch: h_sp/h_ep receive the suffix-array
  * range [sp, ep] (sp = ep + 1: no occurrence). */

@@ -60,6 +60,12 @@ class WtsaInfo(C.Structure):
                 ("hbm_bytes", C.c_uint64)]
 
 
+class WtsaParts(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("symbol_bytes", C.c_uint32), ("levels", C.c_uint32), ("text_words", C.c_void_p),
+                ("text_count", C.c_uint64), ("text_width", C.c_uint32), ("reserved", C.c_uint32), ("data", C.c_void_p),
+                ("data_words", C.c_uint64), ("rank_samples", C.c_void_p), ("n_rank_samples", C.c_uint64)]
+
+
 class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("launches", C.c_uint64), ("total_ms", C.c_double), ("algorithmic_bytes", C.c_uint64)]
 
@@ -161,6 +167,13 @@ SYMBOLS = [
     ("vlg_wtsa_ranges", _I, [_P, _P, _P, _P, _P]),
     ("vlg_wtsa_range_walk_batch", _I, [_P, _P, _P, _P, _I, _P, _U64, _P]),
     ("vlg_wtsa_export_level", _I, [_P, C.c_uint32, _P]),
+    ("vlg_sdsl_wtsa_file_open", _I, [C.c_char_p, C.c_uint32, C.POINTER(_P)]),
+    ("vlg_sdsl_wtsa_file_parts", _I, [_P, C.POINTER(WtsaParts)]),
+    ("vlg_sdsl_wtsa_file_close", None, [_P]),
+    ("vlg_wtsa_from_parts", _I, [C.POINTER(WtsaParts), C.POINTER(_P)]),
+    ("vlg_wtsa_load_sdsl", _I, [C.c_char_p, C.c_uint32, C.POINTER(_P)]),
+    ("vlg_wtsa_save_sdsl", _I, [_P, C.c_char_p, C.c_uint32]),
+    ("vlg_wtsa_il_device", _I, [_P, _P, _U64, _P]),
     ("vlg_queries_parse_int", _I, [C.c_char_p, _P, _U64, _P, C.POINTER(_P)]),
     ("vlg_queries_parse_int_mapped", _I, [_P, _P, _P, _U64, _P, C.POINTER(_P)]),
     ("vlg_symbol_map_create", _I, [_P, _U64, C.POINTER(_P)]),

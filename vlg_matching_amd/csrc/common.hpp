@@ -187,6 +187,34 @@ template <class T> using rvec = std::vector<T, StageAllocRaw<T>>;
 inline uint64_t align_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
 inline uint32_t bit_width64(uint64_t x) { return x ? 64u - (uint32_t)__builtin_clzll(x) : 0u; }
 
+// bit_vector_il<512> of the paper's index tree (include/sdsl/bit_vector_il.hpp:113-150): sizes of a tree of n values and L levels
+struct IlShape {
+    uint64_t bits, data_words, superblocks, block_num, rank_samples;
+};
+inline IlShape il_shape(uint64_t n, uint32_t levels)
+{
+    IlShape s;
+    s.bits = n * levels;
+    s.data_words = (s.bits + 64) / 64;
+    s.superblocks = (s.bits + 512) / 512;
+    s.block_num = s.data_words + s.superblocks + 1;
+    const uint64_t top = 1ull << (bit_width64(s.superblocks) - 1);                 // 1 << bits::hi(superblocks)
+    s.rank_samples = s.block_num > 1024 * 64 ? (top < 1024 ? top : 1024) : 0;
+    return s;
+}
+// m_rank_samples (init_rank_samples, bit_vector_il.hpp:87-104): count words of the superblocks met in the BFS order of a bisection
+inline void il_rank_samples(const uint64_t* data, uint64_t superblocks, uint64_t count, uint64_t* out)
+{
+    std::vector<uint64_t> lbs{0}, rbs{superblocks};
+    uint64_t idx = 0;
+    for (size_t q = 0; q < lbs.size() && idx < count; ++q) {
+        const uint64_t lb = lbs[q], rb = rbs[q], mid = lb + (rb - lb) / 2;
+        out[idx++] = data[mid * 9];
+        lbs.push_back(lb); rbs.push_back(mid);
+        lbs.push_back(mid + 1); rbs.push_back(rb);
+    }
+}
+
 // Host-side description of the tree, shared by from_parts and the device builder.
 struct HostTree {
     uint32_t n_nodes = 0;
@@ -224,6 +252,10 @@ struct vlg_index {
 };
 
 namespace vlg {
+// the paper's index on disk (wtsa_sdsl.hpp): m_text packed to `width` bits (in: 0 = the index's own width; out: the width used), and
+// bit_vector_il<512>::m_data of the tree, both converted on the device and copied to the host
+vlg_status wtsa_text_words(const vlg_wtsa* idx, uint32_t& width, std::vector<uint64_t>& words);
+vlg_status wtsa_il_words(const vlg_wtsa* idx, std::vector<uint64_t>& words);
 vlg_status attach_int_blob(const void* d_blob, uint64_t bytes, vlg_index* idx);   // int_index.hpp
 void layout_int_blob(IntHeader& h);                                               // int_index.hpp: offsets and total_bytes from the sizes
 }

@@ -12,6 +12,7 @@
 // Host-only: nothing here touches the GPU.
 // The same for csa_wt<wt_int<>, t_dens, t_inv_dens, sa_order_sa_sampling<>, isa_sampling<>, int_alphabet<>> (end of the file): the
 // reader is host-only as well; the writer asks the device for the level-wise tree (vlg_index_export_int_tree, int_index.hpp).
+#include <sys/stat.h>
 #include <cstdio>
 #include <cstring>
 #include <memory>
@@ -699,4 +700,170 @@ extern "C" vlg_status vlg_index_save_sdsl_int(const vlg_index* idx, const char* 
         return VLG_OK;
     }
     catch (const std::bad_alloc&) { return fail(VLG_E_OOM, "out of host memory while writing the index file"); }
+}
+
+// =============================================================================================
+// The paper's index: vlg_index<alphabet_tag, wt_int<bit_vector_il<>, rank_support_il<>>> (vlg_hip.h: vlg_sdsl_wtsa_file_*,
+// vlg_wtsa_load_sdsl, vlg_wtsa_save_sdsl).  The file is parsed here, on the host; the tree image is converted on the device
+// (wtsa_sdsl.hpp).
+//   vlg_index::serialize        include/sdsl/vlg_index.hpp:181-198          m_text, m_wt
+//   int_vector<8> / <0>         include/sdsl/int_vector.hpp:584-600         u64 size in bits [, u8 width], the packed words
+//   wt_int::serialize           include/sdsl/wt_int.hpp:708-732             size, sigma, tree, rank / select supports, u32 max_level
+//   bit_vector_il<512>          include/sdsl/bit_vector_il.hpp:201-213      size, block_num, superblocks, block_shift, m_data,
+//                                                                           m_rank_samples; rank_support_il / select_support_il
+//                                                                           store nothing (:339-346, 509-516)
+// =============================================================================================
+struct vlg_sdsl_wtsa_file {
+    std::vector<uint64_t> raw;              // the file, placed so that its word arrays are 8-byte aligned
+    vlg_wtsa_parts parts;
+};
+
+namespace {
+
+vlg_status sdsl_wtsa_file_open_impl(const char* path, uint32_t symbol_bytes, vlg_sdsl_wtsa_file** out)
+{
+    using namespace vlg;
+    FILE* fp = fopen(path, "rb");
+    if (!fp) return fail(VLG_E_INVALID, std::string("cannot open ") + path);
+    std::unique_ptr<FILE, int (*)(FILE*)> fp_guard(fp, fclose);
+    // a directory opens on some file systems and reports a size of LLONG_MAX: only a regular file is read, and only its real size
+    struct stat sb;
+    if (fstat(fileno(fp), &sb) != 0 || !S_ISREG(sb.st_mode)) return fail(VLG_E_INVALID, std::string("not a regular file: ") + path);
+    std::unique_ptr<vlg_sdsl_wtsa_file> holder(new vlg_sdsl_wtsa_file());
+    vlg_sdsl_wtsa_file* f = holder.get();
+    if (fseek(fp, 0, SEEK_END) != 0) return fail(VLG_E_INVALID, std::string("cannot seek in ") + path);
+    const long sz = ftell(fp);
+    if (sz < 0 || (uint64_t)sz != (uint64_t)sb.st_size || fseek(fp, 0, SEEK_SET) != 0) return fail(VLG_E_INVALID, std::string("cannot size ") + path);
+    const uint64_t bytes = (uint64_t)sz;
+    // int_vector<0> puts a width byte after the text's size: 7 bytes of lead make the words behind it aligned
+    const uint64_t lead = symbol_bytes == 4 ? 7 : 0;
+    f->raw.resize((lead + bytes + 7) / 8 + 1);
+    uint8_t* base = reinterpret_cast<uint8_t*>(f->raw.data()) + lead;
+    const size_t got = bytes ? fread(base, 1, bytes, fp) : 0;
+    fp_guard.reset();
+    const char* tag = symbol_bytes == 1 ? "vlg_index<byte_alphabet_tag>" : "vlg_index<int_alphabet_tag>";
+    auto bad = [&](const std::string& what) { return fail(VLG_E_INVALID, std::string("not a ") + tag + " file (" + what + ")"); };
+    if (got != bytes) return bad("short read");
+    Cursor c{base, base + bytes};
+    // ---- m_text -------------------------------------------------------------------------------------------------------------------
+    uint64_t text_bits; uint8_t width;
+    const uint8_t* text = c.int_vector(symbol_bytes == 1 ? 8 : 0, text_bits, width);
+    if (!c.ok) return bad("text: truncated");
+    if (width < 1 || width > 64) return bad("text width " + std::to_string(width) + " is not in 1..64");
+    // ---- m_wt: wt_int ----------------------------------------------------------------------------------------------------------------
+    const uint64_t n = c.get<uint64_t>();
+    const uint64_t sigma = c.get<uint64_t>();
+    if (!c.ok) return bad("wavelet tree: truncated");
+    if (n == 0 || n > (1ull << 40)) return bad("wavelet tree size " + std::to_string(n));
+    if (text_bits % width || text_bits / width != n - 1)
+        return bad("the text holds " + std::to_string(text_bits / width) + " symbols, the wavelet tree " + std::to_string(n) + " = |text| + 1 values");
+    if (sigma != n) return bad("wavelet tree sigma " + std::to_string(sigma) + " != its size (one leaf per suffix-array value)");
+    const uint32_t L = bit_width64(std::max<uint64_t>(n - 1, 1));
+    const IlShape s = il_shape(n, L);
+    const uint64_t il_size = c.get<uint64_t>(), block_num = c.get<uint64_t>(), superblocks = c.get<uint64_t>(), block_shift = c.get<uint64_t>();
+    if (!c.ok) return bad("bit_vector_il: truncated");
+    if (il_size != s.bits) return bad("tree size " + std::to_string(il_size) + " != size * max_level = " + std::to_string(s.bits));
+    if (block_num != s.block_num) return bad("bit_vector_il block_num " + std::to_string(block_num) + " != " + std::to_string(s.block_num));
+    if (superblocks != s.superblocks) return bad("bit_vector_il superblocks " + std::to_string(superblocks) + " != " + std::to_string(s.superblocks));
+    if (block_shift != 9) return bad("bit_vector_il block_shift " + std::to_string(block_shift) + " != 9 (bit_vector_il<512>)");
+    uint64_t data_bits, rs_bits; uint8_t w64;
+    const uint8_t* data = c.int_vector(64, data_bits, w64);
+    if (!c.ok) return bad("bit_vector_il m_data: truncated");
+    if (data_bits != 64 * s.block_num) return bad("bit_vector_il m_data holds " + std::to_string(data_bits / 64) + " words, not block_num");
+    const uint8_t* rs = c.int_vector(64, rs_bits, w64);
+    if (!c.ok) return bad("bit_vector_il m_rank_samples: truncated");
+    if (rs_bits != 64 * s.rank_samples)
+        return bad("bit_vector_il holds " + std::to_string(rs_bits / 64) + " rank samples, not " + std::to_string(s.rank_samples));
+    const uint32_t max_level = c.get<uint32_t>();
+    if (!c.ok) return bad("wavelet tree max_level: truncated");
+    if (max_level != L) return bad("max_level " + std::to_string(max_level) + " != hi(max(size - 1, 1)) + 1 = " + std::to_string(L));
+    if (c.p != c.e) return bad(std::to_string(c.e - c.p) + " trailing bytes after the wavelet tree");
+    vlg_wtsa_parts& p = f->parts;
+    p.n = n; p.symbol_bytes = symbol_bytes; p.levels = L;
+    p.text_words = reinterpret_cast<const uint64_t*>(text); p.text_count = n - 1; p.text_width = width; p.reserved = 0;
+    p.data = reinterpret_cast<const uint64_t*>(data); p.data_words = s.block_num;
+    p.rank_samples = reinterpret_cast<const uint64_t*>(rs); p.n_rank_samples = s.rank_samples;
+    if (s.rank_samples) {
+        std::vector<uint64_t> want(s.rank_samples);
+        il_rank_samples(p.data, s.superblocks, s.rank_samples, want.data());
+        if (memcmp(want.data(), p.rank_samples, s.rank_samples * 8)) return bad("the rank samples are not the count words they copy");
+    }
+    *out = holder.release();
+    return VLG_OK;
+}
+
+}  // namespace
+
+extern "C" vlg_status vlg_sdsl_wtsa_file_open(const char* path, uint32_t symbol_bytes, vlg_sdsl_wtsa_file** out)
+{
+    using namespace vlg;
+    if (!path || !out) return fail(VLG_E_INVALID, "null argument");
+    *out = nullptr;
+    if (symbol_bytes != 1 && symbol_bytes != 4) return fail(VLG_E_INVALID, "symbol_bytes must be 1 (byte_alphabet_tag) or 4 (int_alphabet_tag)");
+    try { return sdsl_wtsa_file_open_impl(path, symbol_bytes, out); }
+    catch (const std::bad_alloc&) { return fail(VLG_E_OOM, "out of host memory while reading the index file"); }
+    catch (const std::exception& e) { return fail(VLG_E_INVALID, std::string("not a vlg_index<> file (") + e.what() + ")"); }
+}
+
+extern "C" vlg_status vlg_sdsl_wtsa_file_parts(const vlg_sdsl_wtsa_file* f, vlg_wtsa_parts* p)
+{
+    if (!f || !p) return vlg::fail(VLG_E_INVALID, "null argument");
+    *p = f->parts;
+    return VLG_OK;
+}
+
+extern "C" void vlg_sdsl_wtsa_file_close(vlg_sdsl_wtsa_file* f) { delete f; }
+
+extern "C" vlg_status vlg_wtsa_load_sdsl(const char* path, uint32_t symbol_bytes, vlg_wtsa** out)
+{
+    if (!out) return vlg::fail(VLG_E_INVALID, "null argument");
+    *out = nullptr;
+    vlg_sdsl_wtsa_file* f = nullptr;
+    if (vlg_status st = vlg_sdsl_wtsa_file_open(path, symbol_bytes, &f)) return st;
+    vlg_wtsa_parts p;
+    vlg_sdsl_wtsa_file_parts(f, &p);
+    vlg_status st = vlg_wtsa_from_parts(&p, out);
+    vlg_sdsl_wtsa_file_close(f);
+    return st;
+}
+
+extern "C" vlg_status vlg_wtsa_save_sdsl(const vlg_wtsa* idx, const char* path, uint32_t text_width)
+{
+    using namespace vlg;
+    if (!idx || !path) return fail(VLG_E_INVALID, "null argument");
+    vlg_wtsa_info info;
+    if (vlg_status st = vlg_wtsa_get_info(idx, &info)) return st;
+    try {
+        const uint64_t n = info.n;
+        const uint32_t L = info.levels;
+        const IlShape s = il_shape(n, L);
+        uint32_t width = text_width;
+        std::vector<uint64_t> text, data;
+        if (vlg_status st = wtsa_text_words(idx, width, text)) return st;
+        if (vlg_status st = wtsa_il_words(idx, data)) return st;
+        std::vector<uint64_t> rs(s.rank_samples);
+        if (s.rank_samples) il_rank_samples(data.data(), s.superblocks, s.rank_samples, rs.data());
+        FILE* fp = fopen(path, "wb");
+        if (!fp) return fail(VLG_E_INVALID, std::string("cannot create ") + path);
+        Sink out{fp};
+        // ---- m_text: int_vector<8> / int_vector<0> (int_vector.hpp:584-600) ----------------------------------------------------------
+        out.put<uint64_t>((n - 1) * width);
+        if (info.symbol_bytes == 4) out.put<uint8_t>((uint8_t)width);
+        out.raw(text.data(), (((n - 1) * width + 63) / 64) * 8);
+        // ---- m_wt: wt_int::serialize (wt_int.hpp:708-732), its tree bit_vector_il<512>::serialize (bit_vector_il.hpp:201-213) --------
+        out.put<uint64_t>(n);
+        out.put<uint64_t>(n);                                      // sigma: one leaf per suffix-array value
+        out.put<uint64_t>(s.bits);
+        out.put<uint64_t>(s.block_num);
+        out.put<uint64_t>(s.superblocks);
+        out.put<uint64_t>(9);                                      // block_shift = hi(512)
+        out.bit_vector_words(data.data(), 64 * s.block_num);      // m_data: int_vector<64>
+        out.bit_vector_words(rs.data(), 64 * s.rank_samples);     // m_rank_samples
+        out.put<uint32_t>(L);                                      // rank_support_il, select_support_il<1>, <0> write nothing
+        const bool ok = out.ok;
+        if (fclose(fp) != 0 || !ok) return fail(VLG_E_INVALID, std::string("write failed: ") + path);
+        return VLG_OK;
+    }
+    catch (const std::bad_alloc&) { return fail(VLG_E_OOM, "out of host memory while writing the index file"); }
+    catch (const std::exception& e) { return fail(VLG_E_INTERNAL, std::string("while writing the index file: ") + e.what()); }
 }

@@ -2368,6 +2368,7 @@ extern "C" vlg_status vlg_join_batch(const uint64_t* d_lists, const uint64_t* h_
 }
 
 #include "wtsa.hpp"
+#include "wtsa_sdsl.hpp"
 #include "int_index.hpp"
 
 // ---- the build-time constants this library was compiled with (include/vlg_hip.h) -------------------------------------------------

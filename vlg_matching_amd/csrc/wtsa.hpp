@@ -1,6 +1,7 @@
 // The paper's index on the device: text + wavelet tree over the suffix array, searched lazily.
 // Internal to search.hip's translation unit (results, workspace and timers live there); included exactly once, at its end.
-//   vlg_index<alphabet_tag, wt_int<>>   include/sdsl/vlg_index.hpp:109-198, construct :375-392
+//   vlg_index<alphabet_tag, wt_int<bit_vector_il<>, rank_support_il<>>>   include/sdsl/vlg_index.hpp:109-198 (default tree type :116-119),
+//                                       construct :375-392; on disk: wtsa_sdsl.hpp
 //   wt_int                              include/sdsl/wt_int.hpp:215-255 (level-wise layout), :339-361 (operator[]), :824-939 (expand / ranges)
 //   vlg_iterator                        include/sdsl/vlg_index.hpp:209-373 (relax / next / pull_forward)
 //   forward_search                      include/sdsl/suffix_array_algorithm.hpp:48-112
@@ -24,6 +25,8 @@ struct vlg_wtsa {
     uint64_t nb = 0;                       // super-blocks per level
     vlg::Block* d_blocks = nullptr;        // [levels][nb]
     void* d_text = nullptr;                // n_text symbols
+    uint32_t file_width = 0;               // width of m_text in the file it was loaded from (0: built; wtsa_sdsl.hpp)
+    uint64_t* d_level_prefix = nullptr;    // [levels + 1]: ones of the levels before each, all of them last (wtsa_sdsl.hpp)
 };
 
 namespace {
@@ -314,6 +317,7 @@ __global__ void wtsa_compact_kernel(const WQuery* __restrict__ from, const uint6
 }
 
 WtsaView wtsa_view(const vlg_wtsa* x) { return WtsaView{x->d_blocks, x->d_text, x->nb, x->n_vals, x->n_text, x->levels, x->sym_bytes}; }
+vlg_status wtsa_level_prefix(vlg_wtsa* x);                          // wtsa_sdsl.hpp
 
 }  // namespace
 
@@ -322,6 +326,7 @@ extern "C" void vlg_wtsa_destroy(vlg_wtsa* x)
     if (!x) return;
     if (x->d_blocks) (void)hipFree(x->d_blocks);
     if (x->d_text) (void)hipFree(x->d_text);
+    if (x->d_level_prefix) (void)hipFree(x->d_level_prefix);
     delete x;
 }
 
@@ -406,6 +411,7 @@ extern "C" vlg_status vlg_wtsa_build(const void* h_text, uint64_t n_symbols, uin
                 std::swap(cur, other);
             }
         }
+        if (vlg_status st = wtsa_level_prefix(x)) return st;
         VLG_HIP_TRY(hipDeviceSynchronize());
         return VLG_OK;
     };

@@ -3,6 +3,8 @@
 //   construct / construct_im             :375-392, construct.hpp
 //   locate(idx, query) -> container<vlg_iterator>   :394-401; iterator surface :293-373 (operator*, operator[], size(), is_end(), ++)
 //   count(idx, query)                    :403-411
+//   store_to_file / load_from_file       the file of vlg_index<alphabet_tag, wt_int<bit_vector_il<>, rank_support_il<>>>
+//                                        (serialize / load :181-198; vlg_wtsa_save_sdsl / vlg_wtsa_load_sdsl)
 // The iterator is lazy like the reference's: it asks the device for the first matches only and, when the caller walks past them,
 // for four times as many (vlg_wtsa_search_batch's max_matches_per_query) -- a caller that stops early never pays for the rest.
 #pragma once
@@ -41,6 +43,18 @@ class vlg_index_gpu
         check(vlg_workspace_create(0, nullptr, &h->ws));
         m_h = h;
     }
+    // take over an index made elsewhere (vlg_wtsa_load_sdsl, vlg_wtsa_from_parts); its alphabet must be this one's
+    void adopt(vlg_wtsa* idx)
+    {
+        std::shared_ptr<handles> h(new handles());
+        h->idx = idx;
+        vlg_wtsa_info i;
+        check(vlg_wtsa_get_info(idx, &i));
+        if (i.symbol_bytes != (byte_symbols ? 1u : 4u)) throw std::runtime_error("vlg_index_gpu: the index has the other alphabet");
+        check(vlg_workspace_create(0, nullptr, &h->ws));
+        m_h = h;
+    }
+    const vlg_wtsa* handle() const { return m_h ? m_h->idx : nullptr; }
     bool empty() const { return !m_h; }
     size_type size() const
     {
@@ -143,6 +157,22 @@ inline void construct(vlg_index_gpu<byte_alphabet_tag>& idx, const std::string& 
     if (!in) throw std::runtime_error("cannot open " + file);
     std::string text((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
     idx.build(text.data(), text.size());
+}
+
+// store_to_file(idx, file) / load_from_file(idx, file) (include/sdsl/io.hpp:668, 741): true on success, like sdsl's
+template <typename alphabet_tag>
+bool store_to_file(const vlg_index_gpu<alphabet_tag>& idx, const std::string& file)
+{
+    return idx.handle() && vlg_wtsa_save_sdsl(idx.handle(), file.c_str(), 0) == VLG_OK;
+}
+template <typename alphabet_tag>
+bool load_from_file(vlg_index_gpu<alphabet_tag>& idx, const std::string& file)
+{
+    vlg_wtsa* x = nullptr;
+    if (vlg_wtsa_load_sdsl(file.c_str(), vlg_index_gpu<alphabet_tag>::byte_symbols ? 1 : 4, &x) != VLG_OK) return false;
+    try { idx.adopt(x); }
+    catch (const std::exception&) { return false; }
+    return true;
 }
 
 template <typename type_index>

@@ -135,6 +135,44 @@ def read_sdsl_int_file(path, dens=32, rrr=False):
         lib().vlg_sdsl_int_file_close(f)
 
 
+def _wtsa_parts_dict(p):
+    def u64(ptr, count):
+        return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint64)), shape=(max(count, 1),))[:count].copy() if count else np.zeros(0, np.uint64)
+    count, width = int(p.text_count), int(p.text_width)
+    words = u64(p.text_words, (count * width + 63) // 64)
+    return {"n": int(p.n), "symbol_bytes": int(p.symbol_bytes), "levels": int(p.levels), "text_width": width, "text_count": count,
+            "text_words": words, "text": _unpack_symbols(words, count, width, int(p.symbol_bytes)),
+            "data": u64(p.data, p.data_words), "rank_samples": u64(p.rank_samples, p.n_rank_samples)}
+
+
+def _unpack_symbols(words, count, width, symbol_bytes):
+    """int_vector words -> the symbols (uint8 for the byte tag, uint64 for the int tag)"""
+    if symbol_bytes == 1:
+        return words.view(np.uint8)[:count].copy()
+    i = np.arange(count, dtype=np.uint64) * np.uint64(width)
+    w, o = (i >> np.uint64(6)).astype(np.int64), i & np.uint64(63)
+    ext = np.concatenate([words, np.zeros(1, np.uint64)])
+    lo = ext[w] >> o
+    sh = (np.uint64(64) - o) & np.uint64(63)
+    hi = np.where(o + np.uint64(width) > np.uint64(64), ext[w + 1] << sh, np.uint64(0))
+    v = lo | hi
+    return v if width == 64 else v & np.uint64((1 << width) - 1)
+
+
+def read_sdsl_wtsa_file(path, int_alphabet=False):
+    """Host-only parse of a stock sdsl vlg_index<byte_alphabet_tag> file (int_alphabet: vlg_index<int_alphabet_tag>), tree type
+    wt_int<bit_vector_il<>, rank_support_il<>> -> dict: n, symbol_bytes, levels, text_width, text_count, text_words (m_text as stored),
+    text (its symbols), data (bit_vector_il<512>::m_data), rank_samples."""
+    f = C.c_void_p()
+    check(lib().vlg_sdsl_wtsa_file_open(str(path).encode(), 4 if int_alphabet else 1, C.byref(f)))
+    try:
+        p = capi.WtsaParts()
+        check(lib().vlg_sdsl_wtsa_file_parts(f, C.byref(p)))
+        return _wtsa_parts_dict(p)
+    finally:
+        lib().vlg_sdsl_wtsa_file_close(f)
+
+
 class Workspace:
     def __init__(self, max_hbm_bytes=0, stream=None):
         h = C.c_void_p()
@@ -702,6 +740,43 @@ class WtsaIndex:
         check(lib().vlg_wtsa_build(t.ctypes.data if len(t) else None, len(t), self.symbol_bytes, C.byref(h)))
         self._h = h
         self._ws = None
+
+    @classmethod
+    def _adopt(cls, h):
+        self = cls.__new__(cls)
+        self._h, self._ws = h, None
+        self.symbol_bytes = self.info()["symbol_bytes"]
+        return self
+
+    @classmethod
+    def load_sdsl(cls, path, int_alphabet=False):
+        """An index stored by stock sdsl: `store_to_file(idx, file)` of vlg_index<byte_alphabet_tag> (int_alphabet:
+        vlg_index<int_alphabet_tag>) with the default tree wt_int<bit_vector_il<>, rank_support_il<>>."""
+        h = C.c_void_p()
+        check(lib().vlg_wtsa_load_sdsl(str(path).encode(), 4 if int_alphabet else 1, C.byref(h)))
+        return cls._adopt(h)
+
+    @classmethod
+    def from_parts(cls, p):
+        """An index from the members of such a file (dict as read_sdsl_wtsa_file returns it), converted and checked on the device."""
+        tw = np.ascontiguousarray(p["text_words"], dtype=np.uint64)
+        data = np.ascontiguousarray(p["data"], dtype=np.uint64)
+        rs = np.ascontiguousarray(p["rank_samples"], dtype=np.uint64)
+        parts = capi.WtsaParts(int(p["n"]), int(p["symbol_bytes"]), int(p["levels"]), tw.ctypes.data if len(tw) else None,
+                               int(p["text_count"]), int(p["text_width"]), 0, data.ctypes.data if len(data) else None, len(data),
+                               rs.ctypes.data if len(rs) else None, len(rs))
+        h = C.c_void_p()
+        check(lib().vlg_wtsa_from_parts(C.byref(parts), C.byref(h)))
+        return cls._adopt(h)
+
+    def save_sdsl(self, path, text_width=0):
+        """Store as stock sdsl's vlg_index<alphabet_tag> file.  text_width: the width of m_text -- 0 or 8 for a byte index; for an
+        integer index 0 (the width of the file it was loaded from, or that of its largest symbol) or 1..64."""
+        check(lib().vlg_wtsa_save_sdsl(self._h, str(path).encode(), int(text_width)))
+
+    def il_device(self, d_words_ptr, n_words, stream=None):
+        """bit_vector_il<512>::m_data of the tree into device memory (block_num words)"""
+        check(lib().vlg_wtsa_il_device(self._h, d_words_ptr, int(n_words), stream))
 
     def __del__(self):
         try:
