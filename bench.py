@@ -9,12 +9,17 @@ N GPUs = N processes, one per GPU: launched by `python -m torch.distributed.run 
 this script itself when it is started plainly with --gpus N > 1 (the parent then only spawns and waits: it never touches a
 GPU).  The read-only index is built on rank 0 and broadcast over RCCL (vlg_matching_amd.dist.replicate_index), then
   * weak scaling (the printed `value`): every rank runs its own 100k-query batch;
-  * strong scaling (reported beside it as `strong_scaling`): THE batch of rank 0 is cut into contiguous slices of equal
-    work (sum of SA-interval sizes from one backward-search pass, vlg_matching_amd.dist.shard_by_work) -- the query loop of
+  * strong scaling (reported beside it as `strong_scaling`, with --full): THE batch of rank 0 is cut into contiguous slices of
+    equal work (sum of SA-interval sizes from one backward-search pass, vlg_matching_amd.dist.shard_by_work) -- the query loop of
     gm_search.cpp:91-121 sharded.
 No collective on the data path; the timed regions are bracketed by barrier + synchronize and the max over ranks is reported.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3] [--scale 1.0]
+A plain run does what the headline figure needs and nothing more: set-up, warm-up, the timed steps, --dump-outputs, the line.
+--full adds everything else the line can carry, each behind the metric's region: the end-to-end region (`e2e`), the same batch on
+the index that keeps the whole suffix array (`hbm_resident_sa`), the CPU baselines (`cpu_baseline`), BASELINE's other configs
+(`other_configs`) and, at N > 1, the strong-scaling region; the --no-* options below leave single ones out of a --full run.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3] [--scale 1.0] [--full]
 """
 import argparse
 import json
@@ -499,7 +504,8 @@ def other_config(name, steps, warmup, workspace_gb, tuples):
                                      "algorithmic_bytes_are": CLASSES["locate"][2]}}
 
 
-def main():
+def parse_args(argv=None):
+    """The command line; without --full every region the headline figure does not need is switched off here."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2)
@@ -511,13 +517,16 @@ def main():
     ap.add_argument("--sa-dens", type=int, default=32,
                     help="suffix-array sample density t_dens of csa_wt<> (default 32 = the benchmark's index; 1 keeps the whole suffix "
                          "array resident in HBM: 4 B x n, no LF walk in locate). Not the headline config unless 32.")
-    ap.add_argument("--no-dense-sa", action="store_true", help="N = 1: skip the secondary run on the index that keeps the whole suffix array")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need (end-to-end region, suffix array resident, CPU "
+                         "baselines, other configs, strong scaling), each after the metric's region; a plain run leaves all of them out")
+    ap.add_argument("--no-dense-sa", action="store_true", help="--full, N = 1: skip the secondary run on the index that keeps the whole suffix array")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
     ap.add_argument("--other-configs", default="C2,C5,C4",
-                    help="N = 1, default config only: BASELINE's other single-GPU configs measured behind the metric's regions and reported in "
-                         "`other_configs` (each: ms per batch, matches / checksum checked against the constants the full-size tests assert, "
-                         "roofline of its rank kernel); '' = none")
-    ap.add_argument("--no-strong", action="store_true", help="N > 1: skip the strong-scaling region")
+                    help="--full, N = 1, default config only: BASELINE's other single-GPU configs measured behind the metric's regions and "
+                         "reported in `other_configs` (each: ms per batch, matches / checksum checked against the constants the full-size tests "
+                         "assert, roofline of its rank kernel); '' = none")
+    ap.add_argument("--no-strong", action="store_true", help="--full, N > 1: skip the strong-scaling region")
     ap.add_argument("--strong-timeout", type=float, default=120.0,
                     help="N > 1: seconds the strong-scaling region may take before the weak-scaling line is printed without it")
     ap.add_argument("--strong-sharding", choices=["lists", "affinity", "work"], default="lists",
@@ -526,7 +535,7 @@ def main():
     ap.add_argument("--exchange", choices=["needed", "allgather"], default="needed",
                     help="strong-scaling region with --strong-sharding lists: 'needed' = a sorted list travels only to the ranks whose queries "
                          "use it, pairwise (vlg_comm_alltoallv); 'allgather' = every list to every rank (vlg_comm_allgatherv)")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end (parse + H2D + search + D2H) region")
+    ap.add_argument("--no-e2e", action="store_true", help="--full: skip the end-to-end (parse + H2D + search + D2H) region")
     ap.add_argument("--tuples", action="store_true", help="also materialise every sub-pattern position of every match (sdsl::locate output)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only to rehearse N>1 on one GPU)")
     ap.add_argument("--single-device", action="store_true", help="rehearsal: every rank uses cuda:0")
@@ -537,17 +546,25 @@ def main():
                     help="N > 1: how the index gets to the ranks BEFORE the metric's region: torch.distributed.broadcast of its image "
                          "(default: RCCL through torch) or vlg_index_broadcast over a communicator made through the C-ABI (the product's "
                          "own RCCL binding).  With the default the product's broadcast runs -- and is timed and checked -- inside the "
-                         "guarded strong-scaling region instead, where a failure of the so far one-rank-only path cannot cost the metric")
+                         "guarded strong-scaling region of a --full run instead, where a failure of the so far one-rank-only path cannot cost "
+                         "the metric")
     ap.add_argument("--detail", metavar="FILE", default=None,
                     help="write the whole result object (every class roofline, traffic detail, per-rank figures, prose) as one JSON "
                          "line to FILE instead of stderr; stdout carries the compact line")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one returned (rank 0's batch) as DIR/<name>.npy, float64, "
                          "<= 64 MB in all (a fixed seeded sample of a longer output)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:                                         # the headline figure alone
+        args.no_e2e = args.no_dense_sa = args.no_cpu_baseline = args.no_strong = True
+        args.other_configs = ""
+    return args
 
+
+def main():
+    args = parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args)                                     # does not return
 

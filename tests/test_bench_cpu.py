@@ -1,7 +1,8 @@
 """bench.py's output on CPU.  The stdout line: built from a recorded full-size result (profiles/), it must stay below
 bench.LINE_BYTES and still carry the metric, the rooflines and the baselines.  --dump-outputs: a stand-in result (no GPU) goes
 through bench.dump_outputs; the files must hold what the result hands a caller, exactly, within the size cap, and the sample drawn
-from a long output must be the same from run to run."""
+from a long output must be the same from run to run.  The command line: a plain run switches off every region the headline
+figure does not need, --full switches them on again, and the --no-* options still leave single ones out of a --full run."""
 import ctypes as C
 import json
 import os
@@ -103,3 +104,16 @@ def test_stdout_line_keeps_errors_and_stays_under_the_limit_whatever_comes():
     c = json.loads(json.dumps(bench.compact_line(huge)))
     assert len(json.dumps(c)) < bench.LINE_BYTES
     assert c["metric"] == "m" and c["value"] == 1.0 and c["strong_scaling"]["error"] == msg
+
+
+def test_plain_run_leaves_out_what_the_headline_does_not_need():
+    bench = _bench()
+    extras = ("no_e2e", "no_dense_sa", "no_cpu_baseline", "no_strong")
+    plain = bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "2"])
+    assert not plain.full and (plain.steps, plain.warmup, plain.gpus) == (3, 2, 1)
+    assert all(getattr(plain, k) for k in extras) and plain.other_configs == ""
+    assert bench.parse_args(["--other-configs", "C2", "--dump-outputs", "d"]).other_configs == ""
+    full = bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "2", "--full"])
+    assert not any(getattr(full, k) for k in extras) and full.other_configs == "C2,C5,C4"
+    some = bench.parse_args(["--full", "--no-e2e", "--other-configs", "C2"])
+    assert some.no_e2e and not some.no_dense_sa and not some.no_cpu_baseline and some.other_configs == "C2"

@@ -13,7 +13,7 @@ cd $R
 B="python3 bench.py --no-cpu-baseline --no-e2e --no-dense-sa --other-configs="
 step() { date +"%T $1" >> $O/log; }
 step start
-python3 bench.py > $O/bench_C3_default.json 2> $O/bench_C3_default.err || exit 1
+python3 bench.py --full > $O/bench_C3_default.json 2> $O/bench_C3_default.err || exit 1
 step "default line"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/r04_stats -o r04 -- $B --steps 2 --warmup 1 > $O/bench_C3_under_rocprof.json 2> $O/stats.err || exit 1
 for f in $(find /tmp/r04_stats -name "*kernel_stats.csv"); do cp $f $O/kernel_stats_bench_C3.csv; done
@@ -27,12 +27,12 @@ for f in $(find /tmp/r04_write -name "*counter_collection.csv"); do cp $f $O/pmc
 step "WRITE_SIZE pass"
 python3 tools/pmc_summary.py $O/pmc_FETCH_SIZE_bench_C3.csv $O/pmc_WRITE_SIZE_bench_C3.csv r04 2 $COMMIT > $O/pmc_summary.txt 2>&1 && cp profiles/pmc_traffic.json $O/pmc_traffic.json
 step "pmc summary"
-python3 bench.py --gpus 1 --dist-at-1 --steps 2 --warmup 1 --no-cpu-baseline --no-e2e --no-dense-sa --other-configs= > $O/bench_C3_one_rank_rccl.json 2> $O/bench_C3_one_rank_rccl.err || exit 1
+python3 bench.py --full --gpus 1 --dist-at-1 --steps 2 --warmup 1 --no-cpu-baseline --no-e2e --no-dense-sa --other-configs= > $O/bench_C3_one_rank_rccl.json 2> $O/bench_C3_one_rank_rccl.err || exit 1
 step "one-rank RCCL line"
 for X in needed allgather; do
-python3 bench.py --gpus 2 --single-device --backend gloo --scale 0.25 --workspace-gb 60 --steps 2 --warmup 1 --exchange $X --no-cpu-baseline --no-e2e --no-dense-sa > $O/rehearse_2ranks_one_device_C3x0.25_$X.json 2> $O/rehearse_2_$X.err || exit 1
+python3 bench.py --full --gpus 2 --single-device --backend gloo --scale 0.25 --workspace-gb 60 --steps 2 --warmup 1 --exchange $X --no-cpu-baseline --no-e2e --no-dense-sa > $O/rehearse_2ranks_one_device_C3x0.25_$X.json 2> $O/rehearse_2_$X.err || exit 1
 step "two-rank rehearsal ($X)"
-python3 bench.py --gpus 4 --single-device --backend gloo --scale 0.25 --workspace-gb 40 --steps 2 --warmup 1 --exchange $X --no-cpu-baseline --no-e2e --no-dense-sa > $O/rehearse_4ranks_one_device_C3x0.25_$X.json 2> $O/rehearse_4_$X.err || exit 1
+python3 bench.py --full --gpus 4 --single-device --backend gloo --scale 0.25 --workspace-gb 40 --steps 2 --warmup 1 --exchange $X --no-cpu-baseline --no-e2e --no-dense-sa > $O/rehearse_4ranks_one_device_C3x0.25_$X.json 2> $O/rehearse_4_$X.err || exit 1
 step "four-rank rehearsal ($X)"
 done
 python3 tools/int_bench.py 27 3 > $O/int_bench.jsonl 2> $O/int_bench.err || exit 1
