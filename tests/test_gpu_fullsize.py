@@ -3,9 +3,14 @@ index in seconds, but it can adopt the device-built parts and answer a bounded s
   * every tuple obeys its gap bounds, tuples are ascending and non-overlapping (SURVEY.md Appendix C);
   * every reported position really is an occurrence of its sub-pattern in the text;
   * interval sharing on/off, sorted-sweep vs random-access locate, the window filter on/off all give identical results;
-  * a random sample of queries equals the CPU oracle tuple for tuple."""
+  * a random sample of queries equals the CPU oracle tuple for tuple.
+Every config's index is also checked against its text alone: the device suffix array (at C4, the csa[i] of a dens-1 resample) is
+certified exactly (tests/sa_certificate.py), and C, char2comp, the SA samples and wavelet-tree ranks are derived from it on the
+device and compared (C2: the whole index against the oracle built from the certified SA)."""
 import numpy as np
 import pytest
+
+from sa_certificate import bwt_from_sa, certify_suffix_array, check_index_against_sa, hbm_used
 
 pytestmark = pytest.mark.gpu
 
@@ -20,7 +25,8 @@ class _Lap:
         if self.on:
             import sys
             t1 = self.clock()
-            print("[lap] %s: %-40s %7.1f s" % (self.name, what, t1 - self.t0), file=sys.stderr, flush=True)
+            print("[lap] %s: %-40s %7.1f s   HBM in use %6.1f GiB" % (self.name, what, t1 - self.t0, hbm_used() / 2 ** 30),
+                  file=sys.stderr, flush=True)
             self.t0 = t1
 
 
@@ -102,19 +108,44 @@ def test_c2_sample_equals_oracle(c2, oracle):
         assert o.sa(i) == sa
 
 
-def _check_device_suffix_array(text, sa, rng, samples=20000):
+def test_c2_whole_index_equals_oracle_from_certified_sa(c2, oracle):
+    """The device-built C2 index against one built from the text alone: the device SA, certified against the text, gives the BWT; the
+    oracle builds its index from that BWT and SA on the CPU; the two are compared part by part (wavelet-tree bits, tree shape, C,
+    char2comp, samples), and the wavelet tree is probed for ranks against exact counts."""
+    import torch
+    from test_gpu_parity import assert_parts_equal
+    V, text, idx, queries, parts, cfg = c2
+    lap = _Lap("C2")
+    d_text = torch.from_numpy(text).cuda()
+    d_sa = _device_suffix_array(V, d_text)
+    certify_suffix_array(d_text, d_sa)
+    lap("device SA + certificate")
+    bwt = bwt_from_sa(d_text, d_sa).cpu().numpy()
+    sa = d_sa.cpu().numpy().view(np.uint64)
+    want = oracle.Index.from_bwt(bwt, sa, 32).parts()
+    del bwt, sa
+    lap("oracle index from the certified SA (CPU)")
+    assert_parts_equal(idx.export_parts(), want)
+    lap("whole index equal")
+    n_pos, n_probes = check_index_against_sa(V, d_text, d_sa, [idx], seed=2)
+    lap("C, samples, %d rank positions, %d probes" % (n_pos, n_probes[0]))
+
+
+def _device_suffix_array(V, d_text):
+    """the device sorter's suffix array of a device text (+ sentinel) -> int64 tensor on the device"""
+    import torch
+    d_sa = torch.empty(d_text.numel() + 1, dtype=torch.int32, device="cuda")
+    V.capi.check(V.lib().vlg_suffix_array_device(d_text.data_ptr(), d_text.numel(), d_sa.data_ptr(), None))
+    torch.cuda.synchronize()
+    return d_sa.to(torch.int64) & 0xFFFFFFFF
+
+
+def _check_device_suffix_array(d_text, d_sa):
     """The suffix array the SASEARCH restatement runs on comes from the device sorter: it must be a permutation of [0, n] whose
-    neighbouring suffixes ascend (sampled; csa_byte_test.cpp:136-147 checks csa[j] == SA[j] the same way)."""
-    n = len(text) + 1
-    assert len(sa) == n and int(sa[0]) == n - 1                              # the sentinel suffix sorts first
-    seen = np.zeros(n, dtype=bool)
-    seen[sa] = True
-    assert seen.all()
-    del seen
-    for i in rng.integers(1, n - 1, samples):
-        a, b = int(sa[i]), int(sa[i + 1])
-        x, y = text[a: a + 96].tobytes(), text[b: b + 96].tobytes()          # a proper prefix (suffix at the text end) sorts first
-        assert x < y or (x == y and len(x) == 96), (i, a, b)
+    neighbouring suffixes ascend -- certified exactly, every pair, against the text (tests/sa_certificate.py)."""
+    n = d_text.numel() + 1
+    assert d_sa.numel() == n and int(d_sa[0]) == n - 1                       # the sentinel suffix sorts first
+    certify_suffix_array(d_text, d_sa)                                       # a permutation, every neighbouring pair ascends
 
 
 def test_c3_headline_config_modes_and_oracle_sample(oracle):
@@ -200,14 +231,17 @@ def test_c3_headline_config_modes_and_oracle_sample(oracle):
     occ_sub, _ = idx.occurrences(q)
     occ_q = occ_sub.reshape(-1, cfg["k"]).astype(np.int64)
     assert (occ_q.sum(axis=1)[occ_q.min(axis=1) > 0]).sum() == sa["logical_occurrences"]
+    lap = _Lap("C3")
     d_text = torch.from_numpy(text).cuda()
-    d_sa = torch.empty(len(text) + 1, dtype=torch.int32, device="cuda")
-    V.capi.check(V.lib().vlg_suffix_array_device(d_text.data_ptr(), len(text), d_sa.data_ptr(), None))
-    torch.cuda.synchronize()
-    sarr = d_sa.cpu().numpy().view(np.uint32)
+    d_sa = _device_suffix_array(V, d_text)
+    lap("device suffix array")
+    _check_device_suffix_array(d_text, d_sa)
+    lap("SA certificate")
+    n_pos, n_probes = check_index_against_sa(V, d_text, d_sa, [idx], seed=3)
+    lap("C, samples, %d rank positions, %d probes" % (n_pos, n_probes[0]))
+    sarr = d_sa.to(torch.int32).cpu().numpy().view(np.uint32)
     del d_text, d_sa
     torch.cuda.empty_cache()
-    _check_device_suffix_array(text, sarr, rng)
     sas = oracle.SaSearch(np.concatenate([text, np.zeros(1, dtype=np.uint8)]), sarr)
     heavy = [int(qi) for qi in rng.permutation(cfg["nq"]) if occ_q[qi].min() > 0 and 100000 < occ_q[qi].sum() <= 4000000][:220]
     assert len(heavy) >= 200
@@ -302,6 +336,18 @@ def test_c5_one_gib_dna_rrr_full_size(oracle):
         nonempty += len(want) > 0
     assert nonempty >= 2                                                     # (the two heavy ones at least)
     lap("oracle sample")
+    # ---- the index against its text alone: certified SA, C / samples, ranks of the plain and the rrr wavelet tree ------------------
+    import torch
+    del o
+    d_text = torch.from_numpy(text).cuda()
+    d_sa = _device_suffix_array(V, d_text)
+    lap("device suffix array")
+    certify_suffix_array(d_text, d_sa)
+    lap("SA certificate")
+    n_pos, n_probes = check_index_against_sa(V, d_text, d_sa, [plain, rrr], seed=5)
+    lap("C, samples, %d rank positions, %r probes (plain, rrr)" % (n_pos, n_probes))
+    del d_text, d_sa
+    torch.cuda.empty_cache()
 
 
 def test_c4_four_gib_text_64bit_positions(oracle):
@@ -350,10 +396,38 @@ def test_c4_four_gib_text_64bit_positions(oracle):
     del full
     res = idx.search(queries, workspace=Workspace(100 << 30))
     # bounded oracle sample on the device-built parts (CPU algorithm, reference layout)
-    o = oracle.Index.from_parts(idx.export_parts())
+    parts = idx.export_parts()
+    o = oracle.Index.from_parts(parts)
     done = 0
     for qi in rng.permutation(nq)[:200]:
         want = o.search(queries[qi])
         assert res.tuples(int(qi)).tolist() == want.tolist()
         done += 1
     assert done == 200
+    # ---- the index against its text alone.  The device sorter cannot emit 2^32 + 1 entries, so csa[i] of a dens-1 resample (the whole
+    #      SA resident) is read for every i and certified; then samples, C and ranks (positions beyond 2^32 included) follow from it ----
+    import gc
+    del res, o
+    gc.collect()
+    torch.cuda.empty_cache()
+    lap = _Lap("C4")
+    n = info["n"]
+    d_text = torch.from_numpy(text).cuda()
+    whole = idx.resample(text_order=False, dens=1)
+    d_sa = torch.empty(n, dtype=torch.int64, device="cuda")
+    step = 1 << 28
+    for s in range(0, n, step):
+        e = min(n, s + step)
+        d_sa[s:e] = torch.arange(s, e, dtype=torch.int64, device="cuda")
+        V.capi.check(V.lib().vlg_sa_batch(whole._h, d_sa[s:e].data_ptr(), d_sa[s:e].data_ptr(), e - s, None))   # in place
+    torch.cuda.synchronize()
+    stats = {"hbm_peak": hbm_used()}
+    lap("dens-1 resample, csa[i] for every i")
+    del whole
+    torch.cuda.empty_cache()
+    certify_suffix_array(d_text, d_sa, stats=stats)
+    lap("SA certificate (HBM peak %.1f GiB)" % (stats["hbm_peak"] / 2 ** 30))
+    n_pos, n_probes = check_index_against_sa(V, d_text, d_sa, [idx], seed=4, parts=parts)
+    lap("C, samples, %d rank positions, %d probes" % (n_pos, n_probes[0]))
+    del d_text, d_sa, parts
+    torch.cuda.empty_cache()
