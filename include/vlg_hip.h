@@ -397,7 +397,11 @@ vlg_status vlg_queries_parse(const char* h_text, const uint64_t* h_off, uint64_t
                              int* h_status, vlg_queries** out);
 /* Already-parsed form: sub-pattern bytes + per-gap start-to-start bounds (lo,hi) + non-overlap length.
  * Query q has sub-patterns [h_qsub[q], h_qsub[q+1]); sub-pattern s = h_blob[h_suboff[s], h_suboff[s+1]);
- * h_lo/h_hi are indexed by sub-pattern (entry of a query's first sub-pattern is ignored). */
+ * h_lo/h_hi are indexed by sub-pattern (entry of a query's first sub-pattern is ignored).
+ * Accepted: at most VLG_MAX_SUBPATTERNS non-empty sub-patterns per query, lo <= hi < 2^63 for every gap (lo may be smaller than
+ * the previous sub-pattern's length, down to 0: two sub-patterns at the same position), and 1 <= end_len < 2^63 for every query
+ * with a sub-pattern -- after a match the search restarts at its last position + end_len, and with 0 it would not advance.
+ * Anything else is VLG_E_INVALID, decided on the host before a device is asked for. */
 vlg_status vlg_queries_create(const uint8_t* h_blob, const uint64_t* h_suboff, const uint64_t* h_qsub,
                               const uint64_t* h_lo, const uint64_t* h_hi, const uint64_t* h_end_len,
                               uint64_t n_queries, vlg_queries** out);

@@ -249,3 +249,41 @@ def test_symbol_map_is_dense_and_order_preserving(V):
     got = mb.apply(big)
     assert (mb.symbols()[got.astype(np.int64) - 1] == big).all()
     assert V.SymbolMap(np.zeros(0, dtype=np.uint64)).sigma == 0
+
+
+def test_queries_create_refuses_bad_batches_before_it_asks_for_a_device(V):
+    """vlg_queries_create (Queries.from_arrays) takes a batch the parser never saw, so it checks it itself -- on the host, before
+    anything is uploaded or launched: every refusal is VLG_E_INVALID, with or without a GPU (never VLG_E_NO_DEVICE).  A zero end_len
+    is the one that matters most: the lazy search restarts at `match end + end_len` and would report the same match for ever.
+    (Nothing is asserted about valid batches here: they need a device.)"""
+    L = V.lib()
+    B63 = 1 << 63
+
+    def create(subs_per_query, lo, hi, end_len, qsub=None, suboff=None, blob=True):
+        flat = [s for q in subs_per_query for s in q]
+        so = np.array(suboff if suboff is not None else np.concatenate([[0], np.cumsum([len(s) for s in flat])]), dtype=np.uint64)
+        qs = np.array(qsub if qsub is not None else np.concatenate([[0], np.cumsum([len(q) for q in subs_per_query])]), dtype=np.uint64)
+        b = np.frombuffer(b"".join(flat) + b"\0" * 16, dtype=np.uint8)
+        a = [np.array(list(x) + [0], dtype=np.uint64) for x in (lo, hi, end_len)]
+        h = C.c_void_p()
+        st = L.vlg_queries_create(b.ctypes.data if blob else None, so.ctypes.data, qs.ctypes.data, a[0].ctypes.data, a[1].ctypes.data,
+                                  a[2].ctypes.data, len(qs) - 1, C.byref(h))
+        if st == 0:
+            L.vlg_queries_destroy(h)
+        return st
+
+    two = [[b"ab", b"c"]]
+    refused = {
+        "end_len 0, k = 1": create([[b"a"]], [0], [0], [0]),
+        "end_len 0, k = 2": create(two, [0, 2], [0, 5], [0]),
+        "end_len 0 in the second query": create([[b"a"], [b"b"]], [0, 0], [0, 0], [1, 0]),
+        "end_len 2^63": create(two, [0, 2], [0, 5], [B63]),
+        "end_len 2^64 - 1": create(two, [0, 2], [0, 5], [2 * B63 - 1]),
+        "lo > hi": create(two, [0, 6], [0, 5], [1]),
+        "hi = 2^63": create(two, [0, 2], [0, B63], [1]),
+        "k = 65": create([[b"a"] * 65], [0] + [1] * 64, [0] + [2] * 64, [1]),
+        "decreasing qsub": create([[b"a"], [b"b"], [b"c"]], [0, 0, 0], [0, 0, 0], [1, 1], qsub=[0, 2, 1]),
+        "empty sub-pattern": create(two, [0, 2], [0, 5], [1], suboff=[0, 2, 2]),
+        "null blob with nsub > 0": create(two, [0, 2], [0, 5], [1], blob=False),
+    }
+    assert refused == {name: V.capi.E_INVALID for name in refused}

@@ -65,3 +65,50 @@ def reference_semantics_join(lists, lo, hi, end_len):
         while p[0] < len(lists[0]) and lists[0][p[0]] < end:
             p[0] += 1
     return out
+
+
+I63 = (1 << 63) - 1
+ARRAY_KS = (1, 2, 3, 8, 9, 31, 32, 33, 40, 64)
+
+
+def array_queries(text, seed, n=150, absent=b"\xfe"):
+    """Query shapes only vlg_queries_create can express (the parser always adds |s_{i-1}| to a gap, stops at 2^62 and sets end_len to a
+    sub-pattern's length): [(sub-patterns, lo[k-1], hi[k-1], end_len)] over sub-patterns of 1..3 symbols cut from `text` -- k from
+    ARRAY_KS, a different gap for every sub-pattern: lo = 0 behind an equal sub-pattern, lo below the previous length, lo == hi,
+    hi = 2^63 - 1, lo = hi = 2^63 - 1 (no match), end_len in {1, |s_0|, |s_last|, 1000, 2^63 - 1}, and a sub-pattern that does not
+    occur in the first, a middle and the last place."""
+    rng = np.random.default_rng(seed)
+    text = bytes(text)
+    out = []
+    for qi in range(n):
+        k = ARRAY_KS[qi % len(ARRAY_KS)]
+        subs, lo, hi = [], [], []
+        for i in range(k):
+            s = int(rng.integers(0, len(text) - 3))
+            sub = text[s:s + (1 if k >= 31 and rng.integers(0, 4) else int(rng.integers(1, 4)))]   # (deep queries: mostly single symbols, so that some match)
+            if i:
+                kind = int(rng.integers(0, 6 if k < 31 else 5))            # (deep queries keep a chance to match: no exact distances)
+                if kind == 0:                                               # the same sub-pattern again, maybe at the same position
+                    sub, a, b = subs[-1], 0, int(rng.integers(0, 20))
+                elif kind == 1:                                             # overlapping the previous sub-pattern
+                    a = int(rng.integers(0, len(subs[-1])))
+                    b = a + int(rng.integers(0, 30))
+                elif kind == 2:
+                    a, b = int(rng.integers(0, 12)), I63
+                elif kind in (3, 4):
+                    a = int(rng.integers(0, 25))
+                    b = a + int(rng.integers(4, 60))
+                else:
+                    a = b = int(rng.integers(1, 30))
+                lo.append(a)
+                hi.append(b)
+            subs.append(sub)
+        special = qi // len(ARRAY_KS) % 8
+        if k > 1 and special == 5:
+            j = int(rng.integers(0, k - 1))
+            lo[j] = hi[j] = I63
+        if special == 6:
+            subs[(0, k // 2, k - 1)[qi % 3]] = absent
+        end_len = (1, len(subs[0]), len(subs[-1]), 1000, I63)[int(rng.integers(0, 5))]
+        out.append((subs, lo, hi, end_len))
+    return out

@@ -394,6 +394,12 @@ extern "C" vlg_status vlg_queries_create(const uint8_t* h_blob, const uint64_t* 
         for (uint64_t sidx = q->qsub[i] + 1; sidx < q->qsub[i + 1]; ++sidx)
             if (q->lo[sidx] > q->hi[sidx] || q->hi[sidx] >= (1ull << 63)) { delete q; return fail(VLG_E_INVALID, "bad gap bounds"); }
     q->end_len.assign(h_end_len, h_end_len + n_queries);
+    for (uint64_t i = 0; i < n_queries; ++i) {
+        // as vlg_join_batch: after a match the search restarts at its end + end_len, and with a zero length neither the lazy search
+        // (wtsa.hpp) nor the join chain would advance (index_sasearch.hpp:113) -- such a batch would never finish on the device
+        if (q->qsub[i + 1] > q->qsub[i] && q->end_len[i] == 0) { delete q; return fail(VLG_E_INVALID, "end_len must be at least 1"); }
+        if (q->end_len[i] >= (1ull << 63)) { delete q; return fail(VLG_E_INVALID, "end_len out of range"); }
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { delete q; return fail(VLG_E_NO_DEVICE, "no HIP device available"); }
     if (vlg_status st = upload_queries(q)) { vlg_queries_destroy(q); return st; }
