@@ -265,3 +265,71 @@ def test_int_sampling_moderate_size(torch_cuda, V, oracle):
         assert (res.counts == ref.counts).all() and res.summary["checksum"] == ref.summary["checksum"], idx.info()
         for i in pick:
             assert res.tuples(i).tolist() == want[i], qs[i]
+
+
+SWEEP_CHUNK = 2048              # elements a workgroup of the sweep's round 0 takes per turn (kSweepChunk)
+LIST_STAGE = 256                # lists a turn may span and still keep them in LDS (kListStage)
+
+
+def _staging_case():
+    """A text of 9 800 symbols whose single-symbol lists, laid out in SA order (= symbol order), put every way round 0 looks its lists
+    up side by side: 600 symbols four times each (the first turn of 2 048 elements spans 512 lists: walked in the global arrays), ten
+    symbols 500 times each (a turn spans a handful of lists: staged in LDS; 500 does not divide 2 048, so lists straddle the turns'
+    borders), and 2 400 tokens of twenty symbols no query asks for, so that not every SA index is an element of the batch and walks
+    are of every length.  Queries for symbols the text does not hold stand between the others: their (empty) lists are dropped by the
+    planner -- vlg_search_batch hands the sweep non-empty lists only -- and their queries must come back empty."""
+    rng = np.random.default_rng(5)
+    small = np.repeat(np.arange(1, 601, dtype=np.uint32), 4)
+    large = np.repeat(np.arange(1001, 1011, dtype=np.uint32), 500)
+    filler = rng.integers(5001, 5021, 2400).astype(np.uint32)
+    text = rng.permutation(np.concatenate([small, large, filler]))
+    asked = list(range(1, 601)) + list(range(1001, 1011))
+    absent = [700 + 7 * j for j in range(20)] + [2000, 4000]
+    syms = sorted(asked + absent)
+    qs = [str(c) for c in syms]
+    sizes = np.array([int((text == c).sum()) for c in asked])      # the lists of the sweep, in layout order
+    return text, qs, sizes
+
+
+def test_int_sweep_staging_layout_is_what_the_test_needs():
+    """the layout the case above promises, from the text itself: which turns of round 0 are staged, and that lists straddle borders"""
+    _, _, sizes = _staging_case()
+    off = np.concatenate([[0], np.cumsum(sizes)])
+    total = int(off[-1])
+    assert total == 7400
+    spans = []
+    for base in range(0, total, SWEEP_CHUNK):
+        end = min(base + SWEEP_CHUNK, total)
+        first = int(np.searchsorted(off, base, side="right")) - 1
+        last = int(np.searchsorted(off, end - 1, side="right")) - 1
+        spans.append(last - first + 1)
+    assert spans[0] > LIST_STAGE and max(spans[1:]) <= LIST_STAGE, spans          # one turn walks the global arrays, the others are staged
+    straddled = [border for border in range(SWEEP_CHUNK, total, SWEEP_CHUNK) if border not in set(off.tolist())]
+    assert len(straddled) >= 2, off                                                # borders that lie inside a list
+
+
+_STAGING = {}
+
+
+@pytest.mark.parametrize("trail", [1, 0], ids=["trail", "notrail"])
+@pytest.mark.parametrize("rrr", [False, True], ids=["plain", "rrr"])
+def test_int_sweep_first_round_staged_lists(V, oracle, rrr, trail):
+    """Round 0 of the sorted sweep on the wavelet matrix with its lists staged in LDS and not (sweep_first_kernel, the byte index's
+    kernel: VLG_STAGE_LISTS = 0 in the `alternates` variant never stages): every position equals the restated reference's, with the
+    sweep run to a few stragglers, to the end, and not at all (the stragglers' kernel alone)."""
+    if "case" not in _STAGING:
+        text, qs, _ = _staging_case()
+        o = oracle.IntIndex(text.astype(np.uint64), dens=32)
+        _STAGING["case"] = (text, qs, [o.search(q).tolist() for q in qs])
+    text, qs, want = _STAGING["case"]
+    assert sum(len(w) for w in want) == 7400 and sum(1 for w in want if not w) == 22
+    if rrr not in _STAGING:
+        base = V.VlgIndex.build_int(text)
+        _STAGING[rrr] = base.compress() if rrr else base
+    idx = _STAGING[rrr]
+    for tail in (4, 0, SORTED_SWEEP_OFF):
+        opts = {"sweep_min": 1, "sweep_tail": tail, "trail": trail}
+        res = idx.search(qs, workspace=_workspace(opts))
+        assert res.summary["locate_mode"] == V.capi.LOCATE_SWEEP and res.summary["located_occurrences"] == 7400, (opts, res.summary)
+        for i in range(len(qs)):
+            assert res.tuples(i).tolist() == want[i], (qs[i], opts)

@@ -40,7 +40,7 @@ CHILD_TESTS = ["tests/test_gpu_variants.py::test_loaded_library_has_the_expected
         "test_integer_alphabet_rrr_index",
         "test_pivot_filter_through_the_ladder",
         "test_search_chunked_equals_unchunked",
-    )] + ["tests/test_gpu_boundaries.py"]
+    )] + ["tests/test_gpu_int_sampling.py::test_int_sweep_first_round_staged_lists", "tests/test_gpu_boundaries.py"]
 
 EXPECT_ENV = "VLG_EXPECT_CONSTANTS"      # set by the runner for its child: the constants the loaded library must report
 

@@ -68,7 +68,7 @@ __device__ __forceinline__ uint64_t node_rank1(const Block* blocks, uint32_t bas
     return block_rank(r, off);
 }
 
-// the sweep's member bit-vector (kernels.hip: sweep_element): is SA index i an element of the batch, and which -- its slot is the
+// the sweep's member bit-vector (sweep_kernels.hpp: sweep_element): is SA index i an element of the batch, and which -- its slot is the
 // number of member bits before it
 __device__ __forceinline__ bool member_probe(const Block* __restrict__ member, uint64_t i, uint32_t& slot)
 {
@@ -184,6 +184,10 @@ struct SaOrderSampling {
     bool pow2;
     const sample_t* samples;
     __device__ __forceinline__ explicit SaOrderSampling(const IndexView& iv)
+        : dens(iv.dens), dmask(iv.dens - 1), dshift(31 - __clz(iv.dens)), pow2((iv.dens & (iv.dens - 1)) == 0),
+          samples(reinterpret_cast<const sample_t*>(iv.samples)) {}
+    // the integer index's (int_index.hpp: SA[0], SA[dens], ... in 4-byte values)
+    __device__ __forceinline__ explicit SaOrderSampling(const IntView& iv)
         : dens(iv.dens), dmask(iv.dens - 1), dshift(31 - __clz(iv.dens)), pow2((iv.dens & (iv.dens - 1)) == 0),
           samples(reinterpret_cast<const sample_t*>(iv.samples)) {}
     __device__ __forceinline__ bool probe(uint64_t i, uint64_t& value) const

@@ -1,7 +1,7 @@
 // Text access on the device (vlg_hip.h: vlg_text_access_create, vlg_extract_batch, vlg_isa_batch): the walks behind
 // sdsl::extract(csa, begin, end) (include/sdsl/suffix_array_algorithm.hpp:645-745, lf_tag) and csa.isa[i] (csa_wt.hpp:145-151), from
-// ISA samples ISA[0], ISA[d], ISA[2d], ... kept in HBM.  The bodies are generic in the LF step: kernels.hip instantiates them with
-// lf_step on the Huffman-shaped tree (ByteWalk), int_index.hpp with int_lf on the wavelet matrix (IntWalk).
+// ISA samples ISA[0], ISA[d], ISA[2d], ... kept in HBM.  The bodies are generic in the LF step (lf_walk.hpp): kernels.hip instantiates
+// them with ByteWalk on the Huffman-shaped tree, int_index.hpp with IntWalk on the wavelet matrix.
 //
 // Extract: a range [b, e] is cut at the multiples of d into segments, segment s = [s d, (s + 1) d) & [b, e], and one lane owns one
 // segment.  It starts at ISA[(s + 1) d] -- or at ISA[0] when (s + 1) d >= n, which stands for ISA[n] because the text is cyclic:

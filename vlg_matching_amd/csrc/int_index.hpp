@@ -22,6 +22,7 @@
 // (the suffix sorter sees five bytes per symbol).
 #pragma once
 #include "extract.hpp"
+#include "sweep_kernels.hpp"
 
 namespace {
 
@@ -60,21 +61,6 @@ __device__ __forceinline__ uint32_t int_char2comp(const IntView& v, uint32_t sym
     uint64_t lo = 0, hi = v.sigma;
     while (lo < hi) { const uint64_t mid = (lo + hi) >> 1; if (v.comp2char[mid] < sym) lo = mid + 1; else hi = mid; }
     return lo < v.sigma && v.comp2char[lo] == sym ? (uint32_t)lo : 0u;
-}
-
-// what every workgroup that walks the matrix keeps in LDS: the zeros per level and whatever the bit-vector policy needs (BV: PlainBV or
-// RrrBV of device_rank.hpp, reading the IntView as they read the byte index's IndexView; level l is "node" l * stride)
-template <class BV>
-struct IntLds {
-    uint64_t Z[kMaxIntLevels];
-    typename BV::Shared sh;
-};
-template <class BV>
-__device__ __forceinline__ void stage_int(IntLds<BV>& s, const IntView& v)
-{
-    if (threadIdx.x < v.n_levels) s.Z[threadIdx.x] = v.Z[threadIdx.x];
-    BV::stage(s.sh, v);
-    __syncthreads();
 }
 
 // position of (the first i symbols' share of) symbol c in the last arrangement: D[c] + this = C[c] + rank_c(i)
@@ -124,243 +110,11 @@ __global__ void __launch_bounds__(256) int_backward_search_kernel(IntView v, con
     }
 }
 
-// SA sampling policies of the locate kernels: is SA index i sampled, and if so what is SA[i].  SA order (csa_sampling_strategy.hpp:102-111)
-// is the arithmetic these kernels always had; text order is the byte index's TextOrderSampling on the IntView (device_rank.hpp: the mark
-// and the rank that addresses the sample come out of one 32-byte read).
-struct IntSaOrderSampling {
-    uint32_t dens;
-    const uint32_t* samples;
-    __device__ __forceinline__ explicit IntSaOrderSampling(const IntView& v) : dens(v.dens), samples(v.samples) {}
-    __device__ __forceinline__ bool probe(uint64_t i, uint64_t& value) const
-    {
-        if (i % dens) return false;
-        value = samples[i / dens];
-        return true;
-    }
-};
-using IntTextOrderSampling = TextOrderSampling<uint32_t>;
-
-// csa[i] (csa_wt.hpp:335-348) for the SA indices in io[], in place; the lanes of a wave refill from the wave's slice like K3's
-template <class BV, class Sampling>
-__global__ void __launch_bounds__(256) int_locate_kernel(IntView v, uint32_t* __restrict__ io, uint64_t total, uint32_t per_wave,
-                                                         unsigned long long* __restrict__ stats)
-{
-    __shared__ IntLds<BV> sZ;
-    stage_int(sZ, v);
-    const Sampling sampling(v);
-    const uint32_t lane = threadIdx.x & 63;
-    const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    uint64_t next = wave * per_wave;
-    const uint64_t slice_end = next + per_wave < total ? next + per_wave : total;
-    uint64_t t = 0, i = 0;
-    uint32_t lvl = 0, c = 0, off = 0, n_lf = 0, n_lv = 0;
-    bool active = false, need = true;
-    for (;;) {
-        const unsigned long long m = __ballot(need);
-        if (m) {
-            const uint32_t before = __popcll(m & ((1ull << lane) - 1ull));
-            if (need) {
-                const uint64_t cand = next + before;
-                if (cand < slice_end) { t = cand; i = io[cand]; off = 0; lvl = 0; c = 0; active = true; }
-                else active = false;
-                need = false;
-            }
-            next += __popcll(m);
-        }
-        if (!__any(active)) break;
-        if (active) {
-            uint64_t sv;
-            if (lvl == 0 && sampling.probe(i, sv)) {                 // csa_sampling_strategy.hpp:102-111 / :185-194
-                uint64_t r = sv + off;
-                if (r >= v.n) r -= v.n;
-                io[t] = (uint32_t)r;
-                need = true;
-                active = false;
-            } else if (v.n_levels == 0) {                            // only the sentinel exists
-                i = 0; ++off;
-            } else {
-                uint32_t bit;
-                uint64_t r1;
-                BV::rank_bit(v, sZ.sh, (uint32_t)(lvl * v.stride), i, r1, bit);
-                ++n_lv;
-                i = bit ? sZ.Z[lvl] + r1 : i - r1;
-                c = (c << 1) | bit;
-                if (++lvl == v.n_levels) { i = v.D[c] + i; lvl = 0; c = 0; ++off; ++n_lf; }      // LF: suffix_array_helper.hpp:341-348
-            }
-        }
-    }
-    if (stats) {
-        unsigned long long a = n_lf, b = n_lv;
-        for (int o = 32; o > 0; o >>= 1) { a += __shfl_down(a, o); b += __shfl_down(b, o); }
-        if (lane == 0) { if (a) atomicAdd(&stats[0], a); if (b) atomicAdd(&stats[1], b); }
-    }
-}
-
-// ---- the sorted sweep on the wavelet matrix (round 4; kernels.hip: K3s explains the sweep, sweep_element the records) ---------------
-// An LF step reads one super-block per matrix level and the symbol's D entry; the symbol read (its compact number, < sigma <= 65534) is
-// the partition key.  Everything else -- rounds, partition, member bit-vector, records, resolution -- is run_locate_sweep's.
-template <class BV>
-__device__ __forceinline__ uint64_t int_lf(const IntView& v, const IntLds<BV>& sZ, uint64_t i, uint32_t& c, uint32_t& n_lv)
-{
-    uint64_t p = i;
-    c = 0;
-    for (uint32_t l = 0; l < v.n_levels; ++l) {
-        uint32_t bit;
-        uint64_t r1;
-        BV::rank_bit(v, sZ.sh, (uint32_t)(l * v.stride), p, r1, bit);
-        ++n_lv;
-        p = bit ? sZ.Z[l] + r1 : p - r1;
-        c = (c << 1) | bit;
-    }
-    return v.D[c] + p;                                               // LF: suffix_array_helper.hpp:341-348
-}
-
-__device__ __forceinline__ void int_counters_add(unsigned long long a, unsigned long long b, unsigned long long c, unsigned long long* __restrict__ stats,
-                                                 unsigned long long* __restrict__ n_done)
-{
-    for (int o = 32; o > 0; o >>= 1) { a += __shfl_down(a, o); b += __shfl_down(b, o); c += __shfl_down(c, o); }
-    if ((threadIdx.x & 63) == 0) { if (a) atomicAdd(&stats[0], a); if (b) atomicAdd(&stats[1], b); if (c && n_done) atomicAdd(n_done, c); }
-}
-
-template <class BV, class Sampling, bool kTrail, bool kFirst, bool kAhead>
-__device__ __forceinline__ void int_sweep_element(const IntView& v, const IntLds<BV>& sZ, const Sampling& sampling, uint64_t e, uint64_t v64, uint64_t* __restrict__ val,
-                                                  uint16_t* __restrict__ key, uint32_t step, uint32_t* __restrict__ out, const Block* __restrict__ member,
-                                                  uint64_t* __restrict__ rec, uint64_t slot0, bool probed, uint32_t& n_lv, uint32_t& n_lf, uint32_t& n_fin)
-{
-    const uint64_t i = v64 & 0xFFFFFFFFull, slot = v64 >> 32;
-    uint32_t owner = 0;
-    uint64_t sv;
-    if (sampling.probe(i, sv)) {                                     // csa_sampling_strategy.hpp:102-111 / :185-194
-        uint64_t r = sv + step;
-        if (r >= v.n) r -= v.n;                                      // csa_wt.hpp:343-347
-        if (kTrail) rec[slot0 + slot] = r; else out[slot] = (uint32_t)r;
-        key[e] = (uint16_t)v.sigma;
-        ++n_fin;
-    } else if (kTrail && !kFirst && !probed && member_probe(member, i, owner)) {
-        const uint64_t delta = step;
-        const uint64_t ro = rec[owner];
-        uint64_t r;
-        if (ro == ~0ull) r = (delta << 32) | owner;                  // still walking: follow it
-        else if ((ro >> 32) == 0) r = ro + delta;                    // its position is known
-        else r = ro + (delta << 32);                                 // it follows someone itself: follow that one
-        rec[slot0 + slot] = r;
-        key[e] = (uint16_t)v.sigma;
-        ++n_fin;
-    } else {
-        if (kTrail && kFirst) rec[slot0 + slot] = ~0ull;
-        uint32_t c;
-        const uint64_t j = int_lf(v, sZ, i, c, n_lv);
-        ++n_lf;
-        if (kTrail && kAhead && member_probe(member, j, owner)) {
-            rec[slot0 + slot] = ((uint64_t)(step + 1) << 32) | owner;
-            key[e] = (uint16_t)v.sigma;
-            ++n_fin;
-        } else {
-            val[e] = (v64 & ~0xFFFFFFFFull) | j;
-            key[e] = (uint16_t)c;
-        }
-    }
-}
-
-template <class BV, class Sampling, bool kTrail>
-__global__ void __launch_bounds__(256) int_sweep_step_kernel(IntView v, uint64_t* __restrict__ val, uint16_t* __restrict__ key, uint64_t count, uint32_t step,
-                                                             uint32_t* __restrict__ out, unsigned long long* __restrict__ stats, unsigned long long* __restrict__ n_done,
-                                                             const Block* __restrict__ member, uint64_t* __restrict__ rec, uint64_t slot0, bool probed)
-{
-    __shared__ IntLds<BV> sZ;
-    stage_int(sZ, v);
-    const Sampling sampling(v);
-    uint32_t n_lv = 0, n_lf = 0, n_fin = 0;
-    for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < count; e += (uint64_t)gridDim.x * blockDim.x)
-        int_sweep_element<BV, Sampling, kTrail, false, false>(v, sZ, sampling, e, val[e], val, key, step, out, member, rec, slot0, probed, n_lv, n_lf, n_fin);
-    int_counters_add(n_lf, n_lv, n_fin, stats, n_done);
-}
-
-template <class BV, class Sampling, bool kTrail, bool kAhead>
-__global__ void __launch_bounds__(256) int_sweep_first_kernel(IntView v, const uint64_t* __restrict__ l, const uint64_t* __restrict__ out_off, uint64_t n_pat, uint64_t t0,
-                                                              uint64_t total, uint64_t* __restrict__ val, uint16_t* __restrict__ key, uint32_t* __restrict__ out,
-                                                              unsigned long long* __restrict__ stats, unsigned long long* __restrict__ n_done,
-                                                              const Block* __restrict__ member, uint64_t* __restrict__ rec,
-                                                              const uint32_t* __restrict__ chunk_list)
-{
-    constexpr uint32_t kPer = kSweepChunk / 256;
-    __shared__ IntLds<BV> sZ;
-    stage_int(sZ, v);
-    const Sampling sampling(v);
-    uint32_t n_lv = 0, n_lf = 0, n_fin = 0;
-    for (uint64_t base = t0 + (uint64_t)blockIdx.x * kSweepChunk; base < total; base += (uint64_t)gridDim.x * kSweepChunk) {
-        uint64_t p = chunk_list[(base - t0) / kSweepChunk];         // the list of the chunk's first element (sweep_chunk_lists_kernel)
-#pragma unroll 1
-        for (uint32_t i = 0; i < kPer; ++i) {
-            const uint64_t t = base + i * 256 + threadIdx.x;
-            if (t < total) {
-                while (out_off[p + 1] <= t) ++p;
-                const uint64_t v64 = ((t - t0) << 32) | (l[p] + (t - out_off[p]));
-                int_sweep_element<BV, Sampling, kTrail, true, kAhead>(v, sZ, sampling, t - t0, v64, val, key, 0u, out, member, rec, t0, false, n_lv, n_lf, n_fin);
-            }
-        }
-    }
-    int_counters_add(n_lf, n_lv, n_fin, stats, n_done);
-}
-
-// the stragglers: int_locate_kernel's refilling lanes on the elements val[] = slot << 32 | SA index that have walked `step` steps
-template <class BV, class Sampling>
-__global__ void __launch_bounds__(256) int_sweep_tail_kernel(IntView v, uint32_t* __restrict__ out, uint64_t total, uint32_t per_wave, unsigned long long* __restrict__ stats,
-                                                             const uint64_t* __restrict__ val, uint32_t step, uint64_t* __restrict__ rec, uint64_t slot0,
-                                                             const Block* __restrict__ member)
-{
-    __shared__ IntLds<BV> sZ;
-    stage_int(sZ, v);
-    const Sampling sampling(v);
-    const uint32_t lane = threadIdx.x & 63;
-    const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    uint64_t next = wave * per_wave;
-    const uint64_t slice_end = next + per_wave < total ? next + per_wave : total;
-    uint64_t t = 0, i = 0;
-    uint32_t off = 0, n_lf = 0, n_lv = 0;
-    bool active = false, need = true;
-    for (;;) {
-        const unsigned long long m = __ballot(need);
-        if (m) {
-            const uint32_t before = __popcll(m & ((1ull << lane) - 1ull));
-            if (need) {
-                const uint64_t cand = next + before;
-                if (cand < slice_end) { const uint64_t e = val[cand]; t = e >> 32; i = e & 0xFFFFFFFFull; off = step; active = true; }
-                else active = false;
-                need = false;
-            }
-            next += __popcll(m);
-        }
-        if (!__any(active)) break;
-        if (active) {
-            uint32_t owner = 0;
-            uint64_t sv = 0;
-            if (sampling.probe(i, sv)) {
-                uint64_t r = sv + off;
-                if (r >= v.n) r -= v.n;
-                if (rec) rec[slot0 + t] = r; else out[t] = (uint32_t)r;
-                need = true;
-                active = false;
-            } else if (rec && member && off != 0 && member_probe(member, i, owner)) {
-                const uint64_t delta = off;
-                const uint64_t ro = rec[owner];
-                uint64_t r;
-                if (ro == ~0ull) r = (delta << 32) | owner;
-                else if ((ro >> 32) == 0) r = ro + delta;
-                else r = ro + (delta << 32);
-                rec[slot0 + t] = r;
-                need = true;
-                active = false;
-            } else {
-                uint32_t c;
-                i = int_lf(v, sZ, i, c, n_lv);
-                ++off;
-                ++n_lf;
-            }
-        }
-    }
-    int_counters_add(n_lf, n_lv, 0, stats, nullptr);
-}
+// The locate kernels are the byte index's (sweep_kernels.hpp), walking the matrix through IntWalk (lf_walk.hpp): an LF step reads one
+// super-block per matrix level and the symbol's D entry; the symbol read (its compact number, < sigma <= 65534) is the sweep's partition
+// key.  The sampling policies are device_rank.hpp's on the IntView, with 4-byte samples.
+using IntSaSampling = SaOrderSampling<uint32_t>;
+using IntTextSampling = TextOrderSampling<uint32_t>;
 
 // wt_int::rank(i, c) on raw symbols (for the primitives test): out = #c in BWT[0, i)
 template <class BV>
@@ -517,16 +271,10 @@ __global__ void __launch_bounds__(256) int_bwt_extract_kernel(IntView v, uint32_
 {
     __shared__ IntLds<BV> sZ;
     stage_int(sZ, v);
+    const IntWalk<BV> walk{v, sZ};
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < v.n; i += (uint64_t)gridDim.x * blockDim.x) {
-        uint64_t p = i;
-        uint32_t c = 0;
-        for (uint32_t l = 0; l < v.n_levels; ++l) {
-            uint32_t b;
-            uint64_t r1;
-            BV::rank_bit(v, sZ.sh, (uint32_t)(l * v.stride), p, r1, b);
-            p = b ? sZ.Z[l] + r1 : p - r1;
-            c = (c << 1) | b;
-        }
+        uint32_t c;
+        (void)walk.lf(i, c);                                           // (the symbol is what is wanted; a degenerate index has only the sentinel, 0)
         bwt[i] = c;
     }
 }
@@ -563,13 +311,13 @@ inline void layout_int(IntHeader& h)
 template <class BV, class Visit>
 __device__ __forceinline__ void int_walk_from_samples(const IntView& v, const IntLds<BV>& sZ, const Visit& visit)
 {
-    uint32_t n_lv = 0;
+    const IntWalk<BV> walk{v, sZ};
     for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < v.n_samples; j += (uint64_t)gridDim.x * blockDim.x) {
         uint64_t i = j * v.dens, x = v.samples[j];
         for (uint64_t k = 0; k < v.n && i < v.n; ++k) {
             visit(i, x);
             uint32_t c;
-            i = v.n_levels ? int_lf(v, sZ, i, c, n_lv) : 0;
+            i = walk.lf(i, c);
             x = x ? x - 1 : v.n - 1;
             if (i % v.dens == 0) break;
         }
@@ -593,18 +341,6 @@ __global__ void __launch_bounds__(256) int_isa_samples_kernel(IntView v, uint32_
 }
 
 // ---- text access (extract.hpp): sdsl::extract and csa.isa[i] on the wavelet matrix ---------------------------------------------------
-template <class BV>
-struct IntWalk {
-    const IntView& v;
-    const IntLds<BV>& sZ;
-    __device__ __forceinline__ uint64_t lf(uint64_t i, uint32_t& c) const
-    {
-        uint32_t n_lv = 0;
-        if (!v.n_levels) { c = 0; return 0; }                // degenerate: only the sentinel exists (n = 1)
-        return int_lf(v, sZ, i, c, n_lv);
-    }
-    __device__ __forceinline__ uint32_t sym(uint32_t c) const { return v.comp2char[c]; }      // (sigma up to 2^32: not staged)
-};
 template <class BV>
 __global__ void __launch_bounds__(256) int_extract_kernel(IntView v, ExtractJob job, const uint32_t* __restrict__ isa, uint32_t* __restrict__ out)
 {
@@ -867,6 +603,7 @@ static vlg_status launch_int_locate_sweep_bv(const IntView& v, const uint64_t* d
                                    uint32_t n_member_lists, uint64_t* rec, const std::function<vlg_status()>* while_first_step)
 {
     if (v.sigma >= 0xFFFFu || v.n_levels < 1 || v.n > (1ull << 32)) return fail(VLG_E_INTERNAL, "integer index: not for the sorted sweep");
+    using Walk = IntWalk<BV>;
     auto grid_of = [](uint64_t n, uint32_t cap) { return dim3((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, cap))); };
     SweepKernels K;
     K.n = v.n;
@@ -876,18 +613,20 @@ static vlg_status launch_int_locate_sweep_bv(const IntView& v, const uint64_t* d
         launch_sweep_chunk_lists(d_out_off, n_pat, t0, t1, chunk_list, stream);
         const dim3 g = grid_of((t1 - t0 + 7) / 8, 8192);
         uint32_t* o = static_cast<uint32_t*>(out);
-        if (mem && ahead) hipLaunchKernelGGL(HIP_KERNEL_NAME(int_sweep_first_kernel<BV, Sampling, true, true>), g, dim3(256), 0, stream, v, d_l, d_out_off, n_pat, t0, t1, val, key, o, d_stats, counter, mem, rc, chunk_list);
-        else if (mem) hipLaunchKernelGGL(HIP_KERNEL_NAME(int_sweep_first_kernel<BV, Sampling, true, false>), g, dim3(256), 0, stream, v, d_l, d_out_off, n_pat, t0, t1, val, key, o, d_stats, counter, mem, rc, chunk_list);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(int_sweep_first_kernel<BV, Sampling, false, false>), g, dim3(256), 0, stream, v, d_l, d_out_off, n_pat, t0, t1, val, key, o, d_stats, counter, mem, rc, chunk_list);
+#define VLG_INT_FIRST(TR, AH) hipLaunchKernelGGL(HIP_KERNEL_NAME(sweep_first_kernel<Walk, Sampling, uint32_t, TR, false, AH>), g, dim3(256), 0, stream, v, d_l, d_out_off, n_pat, t0, t1, val, key, o, d_stats, counter, mem, rc, chunk_list, (uint8_t*)nullptr)
+        if (mem && ahead) VLG_INT_FIRST(true, true);
+        else if (mem) VLG_INT_FIRST(true, false);
+        else VLG_INT_FIRST(false, false);
+#undef VLG_INT_FIRST
     };
     K.step = [&](uint64_t* val, uint16_t* key, uint64_t alive, uint32_t step, void* out, unsigned long long* counter, const Block* mem, uint64_t* rc, uint64_t t0, bool probed) {
         const dim3 g = grid_of(alive, 4096);
         uint32_t* o = static_cast<uint32_t*>(out);
-        if (mem) hipLaunchKernelGGL(HIP_KERNEL_NAME(int_sweep_step_kernel<BV, Sampling, true>), g, dim3(256), 0, stream, v, val, key, alive, step, o, d_stats, counter, mem, rc, t0, probed);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(int_sweep_step_kernel<BV, Sampling, false>), g, dim3(256), 0, stream, v, val, key, alive, step, o, d_stats, counter, mem, rc, t0, probed);
+        if (mem) hipLaunchKernelGGL(HIP_KERNEL_NAME(sweep_step_kernel<Walk, Sampling, uint32_t, true, false>), g, dim3(256), 0, stream, v, val, key, alive, step, o, d_stats, counter, mem, rc, t0, probed);
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(sweep_step_kernel<Walk, Sampling, uint32_t, false, false>), g, dim3(256), 0, stream, v, val, key, alive, step, o, d_stats, counter, mem, rc, t0, probed);
     };
     K.tail = [&](void* out, uint64_t alive, uint32_t per_wave, const uint64_t* val, uint32_t step, uint64_t* rc, uint64_t t0, const Block* mem, uint32_t blocks) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(int_sweep_tail_kernel<BV, Sampling>), dim3(blocks), dim3(256), 0, stream, v, static_cast<uint32_t*>(out), alive, per_wave, d_stats, val, step, rc, t0, mem);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(locate_kernel<Walk, Sampling, uint32_t, true, false>), dim3(blocks), dim3(256), 0, stream, v, static_cast<uint32_t*>(out), alive, per_wave, d_stats, val, step, rc, t0, mem);
     };
     return run_locate_sweep<uint32_t, false>(K, d_l, d_out_off, n_pat, total, d_out, val_a, val_b, key_a, key_b, temp, temp_bytes, d_counter, tail_threshold, stream, timer,
                                              member, n_member_lists, rec, while_first_step);
@@ -909,8 +648,8 @@ vlg_status launch_int_locate_sweep(const IntView& v, const uint64_t* d_l, const 
 #define VLG_INT_SWEEP(BV, S) launch_int_locate_sweep_bv<BV, S>(v, d_l, d_out_off, n_pat, total, d_out, val_a, val_b, key_a, key_b, temp, temp_bytes, d_counter, \
                                                               d_stats, tail_threshold, stream, timer, member, n_member_lists, rec, while_first_step)
     const bool rrr = v.bv_kind == kBvRrr63;
-    if (v.sampling == kSamplingTextOrder) return rrr ? VLG_INT_SWEEP(RrrBV, IntTextOrderSampling) : VLG_INT_SWEEP(PlainBV, IntTextOrderSampling);
-    return rrr ? VLG_INT_SWEEP(RrrBV, IntSaOrderSampling) : VLG_INT_SWEEP(PlainBV, IntSaOrderSampling);
+    if (v.sampling == kSamplingTextOrder) return rrr ? VLG_INT_SWEEP(RrrBV, IntTextSampling) : VLG_INT_SWEEP(PlainBV, IntTextSampling);
+    return rrr ? VLG_INT_SWEEP(RrrBV, IntSaSampling) : VLG_INT_SWEEP(PlainBV, IntSaSampling);
 #undef VLG_INT_SWEEP
 }
 
@@ -924,15 +663,12 @@ vlg_status launch_int_dense_copy(const IntView& v, const uint64_t* d_l, const ui
 vlg_status launch_int_locate(const IntView& v, uint32_t* d_io, uint64_t total, unsigned long long* d_stats, hipStream_t st)
 {
     if (!total) return VLG_OK;
-    const uint64_t target_waves = 256ull * 32 * 4;
-    uint64_t per_wave = (total + target_waves - 1) / target_waves;
-    per_wave = std::min<uint64_t>(std::max<uint64_t>(per_wave, 64 * 16), 1u << 20);
-    const uint64_t waves = (total + per_wave - 1) / per_wave;
-    const dim3 grid((uint32_t)((waves + 3) / 4));
-#define VLG_INT_LOCATE(BV, S) hipLaunchKernelGGL(HIP_KERNEL_NAME(int_locate_kernel<BV, S>), grid, dim3(256), 0, st, v, d_io, total, (uint32_t)per_wave, d_stats)
+    const LocateSlices sl = locate_slices(total);
+    const dim3 grid(sl.blocks);
+#define VLG_INT_LOCATE(BV, S) hipLaunchKernelGGL(HIP_KERNEL_NAME(locate_kernel<IntWalk<BV>, S, uint32_t>), grid, dim3(256), 0, st, v, d_io, total, sl.per_wave, d_stats)
     const bool rrr = v.bv_kind == kBvRrr63;
-    if (v.sampling == kSamplingTextOrder) { if (rrr) VLG_INT_LOCATE(RrrBV, IntTextOrderSampling); else VLG_INT_LOCATE(PlainBV, IntTextOrderSampling); }
-    else { if (rrr) VLG_INT_LOCATE(RrrBV, IntSaOrderSampling); else VLG_INT_LOCATE(PlainBV, IntSaOrderSampling); }
+    if (v.sampling == kSamplingTextOrder) { if (rrr) VLG_INT_LOCATE(RrrBV, IntTextSampling); else VLG_INT_LOCATE(PlainBV, IntTextSampling); }
+    else { if (rrr) VLG_INT_LOCATE(RrrBV, IntSaSampling); else VLG_INT_LOCATE(PlainBV, IntSaSampling); }
 #undef VLG_INT_LOCATE
     VLG_HIP_TRY(hipGetLastError());
     return VLG_OK;

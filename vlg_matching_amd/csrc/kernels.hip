@@ -4,8 +4,8 @@
 #include <string.h>
 #include <vector>
 #include "common.hpp"
-#include "device_rank.hpp"
 #include "kernels.hpp"
+#include "sweep_kernels.hpp"
 #include "extract.hpp"
 #include <rocprim/rocprim.hpp>
 
@@ -411,24 +411,6 @@ __global__ void __launch_bounds__(256) backward_search_kernel(IndexView iv, cons
     }
 }
 
-// Statistics counters: a wave-level sum, then ONE atomic per workgroup and counter -- a single word takes ~90 atomics per
-// microsecond, so one per wave (16 k waves a launch) would cost every launch of the sweep a fifth of a millisecond.
-template <int N>
-__device__ __forceinline__ void block_add(unsigned long long (&v)[N], unsigned long long* const (&dst)[N])
-{
-    __shared__ unsigned long long s_acc[N];
-    if (threadIdx.x < N) s_acc[threadIdx.x] = 0;
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-        unsigned long long x = v[k];
-        for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o);
-        if ((threadIdx.x & 63) == 0 && x) atomicAdd(&s_acc[k], x);
-    }
-    __syncthreads();
-    if (threadIdx.x < N && s_acc[threadIdx.x] && dst[threadIdx.x]) atomicAdd(dst[threadIdx.x], s_acc[threadIdx.x]);
-}
-
 // ---- member bit-vector: which SA indices are elements of the batch, and which (sweep_element explains what for) ----------------
 // bit i = one of the lists [l[d], l[d] + off[d + 1] - off[d]), d < n_lists, holds SA index i; the lists are pairwise disjoint and
 // ascend, and list d owns the slots [off[d], off[d + 1]) -- so the number of set bits before i IS the slot of index i.  Same 256-bit
@@ -461,117 +443,6 @@ __global__ void __launch_bounds__(256) member_build_kernel(const uint64_t* __res
     }
 }
 
-// =============================================================================================
-// K3: csa[i] = LF iteration to the next sampled SA index (include/sdsl/csa_wt.hpp:335-348,
-//     LF = C[c] + inverse_select(i): suffix_array_helper.hpp:336-349, wt_pc.hpp:385-402).
-//
-// io[t] holds the SA index on entry and the text position on exit (in place).
-// Work is dealt to lanes, not to waves: a wave owns a contiguous slice of io[] and every lane that
-// finishes an occurrence immediately pulls the next one of the slice (ballot + prefix popcount), so
-// all 64 lanes issue one 32-byte super-block read per iteration whatever the (geometric) number
-// of LF steps and whatever the code lengths.
-// =============================================================================================
-// kTail: the same walk for the stragglers of the sorted sweep (K3s below): the elements are val[] = slot << kShift | SA index, they
-// have walked `step` steps already, positions go to out[slot] -- or to rec[slot0 + slot] when LF steps are shared, and then a walk
-// also ends on the first index that is an element of the batch itself (sweep_element explains the records and `member`).
-// kWide: SA indices need 33 bits and the samples are 64-bit words (n > 2^32, or VLG_FORCE_POS64); the positions written may still be
-// 32-bit (pos_t) when the text has at most 2^32 characters -- only the tail mode can split the two, the in-place mode keeps the SA
-// index in io[] itself.
-template <typename pos_t, class BV, bool kTail = false, bool kWide = (sizeof(pos_t) == 8), bool kTextOrder = false>
-__global__ void __launch_bounds__(256) locate_kernel(IndexView iv, pos_t* __restrict__ io, uint64_t total, uint32_t per_wave,
-                                                     unsigned long long* __restrict__ stats /* [2]: lf steps, levels */,
-                                                     const uint64_t* __restrict__ val = nullptr, uint32_t step = 0,
-                                                     uint64_t* __restrict__ rec = nullptr, uint64_t slot0 = 0,
-                                                     const Block* __restrict__ member = nullptr)
-{
-    static_assert(kTail || kWide == (sizeof(pos_t) == 8), "in place, io[] holds the SA index: its width is the index width");
-    using sample_t = typename std::conditional<kWide, uint64_t, uint32_t>::type;
-    constexpr uint32_t kShift = kWide ? 33 : 32;
-    constexpr uint64_t kPosMask = (1ull << kShift) - 1;
-    __shared__ WalkLds<BV> s;
-    stage_walk(s, iv);
-    const uint32_t lane = threadIdx.x & 63;
-    const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    uint64_t next = wave * per_wave;                       // wave-uniform cursor into the slice
-    const uint64_t slice_end = next + per_wave < total ? next + per_wave : total;
-    using Sampling = typename std::conditional<kTextOrder, TextOrderSampling<sample_t>, SaOrderSampling<sample_t>>::type;
-    const Sampling sampling(iv);
-
-    uint64_t t = 0;          // slot being worked on
-    uint64_t i = 0;          // SA index at the root, node-relative index below it
-    uint32_t v = 0, off = 0;
-    bool active = false, need = true;
-    uint32_t n_lf = 0, n_lv = 0;
-    for (;;) {
-        // ---- refill ---------------------------------------------------------------------------
-        unsigned long long m = __ballot(need);
-        if (m) {
-            uint32_t before = __popcll(m & ((1ull << lane) - 1ull));
-            if (need) {
-                uint64_t cand = next + before;
-                if (cand < slice_end) {
-                    if (kTail) { const uint64_t e = val[cand]; t = e >> kShift; i = e & kPosMask; off = step; }
-                    else { t = cand; i = io[cand]; off = 0; }
-                    v = 0;
-                    active = true;
-                }
-                else active = false;
-                need = false;
-            }
-            next += __popcll(m);
-        }
-        if (!__any(active)) break;
-        if (active) {
-            uint64_t sv = 0;
-            uint32_t owner = 0;
-            if (v == 0 && sampling.probe(i, sv)) {         // csa_sampling_strategy.hpp:102-111 / :185-194
-                uint64_t r = sv + off;
-                if (r >= iv.n) r -= iv.n;                  // csa_wt.hpp:343-347
-                if (kTail && rec) rec[slot0 + t] = r;
-                else io[t] = (pos_t)r;
-                need = true;
-                active = false;
-            } else if (kTail && member && v == 0 && off != 0 && member_probe(member, i, owner)) {
-                // this index is where element `owner` started: the rest of the walk is that element's (sweep_element)
-                const uint64_t delta = off;
-                const uint64_t ro = rec[owner];
-                uint64_t r;
-                if (ro == ~0ull) r = (delta << kShift) | owner;               // still walking: follow it
-                else if ((ro >> kShift) == 0) r = ro + delta;                  // its position is known
-                else r = ro + (delta << kShift);                               // it follows someone itself: follow that one
-                rec[slot0 + t] = r;
-                need = true;
-                active = false;
-            } else if (iv.sigma == 1) {                    // degenerate: only the sentinel exists
-                i = 0; ++off;
-            } else {
-                // one level of inverse_select: the bit and the rank come from the same block
-                const DNode nd = s.nodes[v];
-                uint32_t bit;
-                uint64_t r1;
-                BV::rank_bit(iv, s.sh, nd.base, i, r1, bit);
-                ++n_lv;
-                uint64_t ni = bit ? r1 : i - r1;
-                uint32_t ch = bit ? nd.child[1] : nd.child[0];      // (a select, not an indexed read: the node stays in registers)
-                if (ch & kLeafFlag) {                      // reached the symbol: LF = C[c] + rank
-                    i = s.C[ch & ~kLeafFlag] + ni;
-                    v = 0;
-                    ++off;
-                    ++n_lf;
-                } else {
-                    i = ni;
-                    v = ch;
-                }
-            }
-        }
-    }
-    if (stats) {
-        unsigned long long v[2] = {n_lf, n_lv};
-        unsigned long long* const dst[2] = {&stats[0], &stats[1]};
-        block_add<2>(v, dst);
-    }
-}
-
 // io[off[p] + j] = l[p] + j : the SA indices of every occurrence (input of locate_kernel), plus seg[]
 template <typename pos_t>
 __global__ void expand_kernel(const uint64_t* __restrict__ l, const uint64_t* __restrict__ out_off, uint64_t n_pat, uint64_t total,
@@ -597,18 +468,8 @@ __global__ void expand_kernel(const uint64_t* __restrict__ l, const uint64_t* __
     }
 }
 
-// =============================================================================================
-// K3s: locate as a synchronous SORTED SWEEP (n <= 2^32).
-//
-// All occurrences advance one LF step per round.  The round's elements are kept in ascending SA-index order:
-// LF restricted to one symbol is monotone (LF(i) = C[c] + rank_c(i)), so after a round a STABLE partition of the
-// elements by the symbol they read restores the order -- no comparison sort.  With ascending positions the 64
-// lanes of a wave read the same or neighbouring super-blocks at every level of the tree (coalesced loads instead
-// of 64 unrelated 64-byte requests), which is what lifts the kernel off the random-access wall of HBM
-// (tools/k1_bench.py: ~50 G random ranks/s vs ~280 G sorted ranks/s).
-// An element leaves the sweep when it reaches a sampled SA index (csa_sampling_strategy.hpp:102-111).
-// val = slot << 32 | position;  key = comp of the symbol read, or sigma for "finished".
-// =============================================================================================
+// K3 (locate_kernel) and the rounds of K3s, the sorted sweep (sweep_first_kernel, sweep_step_kernel), are in sweep_kernels.hpp: the
+// integer index runs them too.  What follows here are the sweep's passes that no LF step is taken in.
 // val = slot << kShift | position: 32 + 32 bits for n <= 2^32, 31 + 33 bits beyond (then a sweep covers at most 2^31 occurrences
 // [t0, t1) at a time and slots are relative to t0).
 template <uint32_t kShift>
@@ -635,29 +496,6 @@ __global__ void sweep_init_kernel(const uint64_t* __restrict__ l, const uint64_t
         }
         __syncthreads();
     }
-}
-
-// The lists that hold the elements [base, end) of a workgroup's turn, staged in LDS: looking an element's list up (whose interval it
-// belongs to, where that starts) is a chain of dependent reads in front of everything else the element does, and the next element's
-// chain starts where this one's ended -- out of LDS it costs tens of cycles instead of L2 round trips.  A turn whose elements spread
-// over more than kListStage lists (lists of a few elements each) walks the global arrays as before.  VLG_STAGE_LISTS=0: never staged.
-#ifndef VLG_STAGE_LISTS
-#define VLG_STAGE_LISTS 1
-#endif
-constexpr bool kStageLists = VLG_STAGE_LISTS != 0;
-static_assert(VLG_STAGE_LISTS == 0 || VLG_STAGE_LISTS == 1, "VLG_STAGE_LISTS: 0 or 1");
-constexpr uint32_t kListStage = 256;
-struct ListStage { uint64_t off[kListStage + 1]; uint64_t l[kListStage]; };
-__device__ __forceinline__ bool stage_lists(ListStage& ls, const uint64_t* __restrict__ out_off, const uint64_t* __restrict__ l, uint64_t n_pat,
-                                            uint64_t first, uint64_t end)
-{
-    for (uint32_t j = threadIdx.x; j <= kListStage; j += blockDim.x) {
-        const uint64_t p = first + j;
-        ls.off[j] = out_off[p < n_pat ? p : n_pat];
-        if (j < kListStage) ls.l[j] = l[p < n_pat ? p : n_pat - 1];
-    }
-    __syncthreads();
-    return ls.off[kListStage] >= end;                      // (the same word in every thread: the branch on it is uniform)
 }
 
 // The suffix array itself resident in HBM (SA-order sampling with density 1: csa_wt<wt_huff<>, 1, .>, 4 B x n -- 4.3 GB for a 1 GiB text,
@@ -703,196 +541,6 @@ __global__ void __launch_bounds__(256) sa_dense_copy_kernel(const sample_t* __re
     }
 }
 
-// kTrail: LF steps are shared inside the batch.  An LF walk from SA index i visits the indices of the text positions SA[i] - 1,
-// SA[i] - 2, ...; when it stands on an index that is ITSELF an element of the batch (the start of another occurrence's walk: text
-// position SA[i] - k is an occurrence too) the rest of the walk is that element's walk, so it stops there and records
-// (that element, k): csa[i] = csa[LF^k(i)] + k (csa_wt.hpp:335-348 applied to a value another lane computes).  Which indices are
-// elements is known before the sweep starts -- the batch's lists are SA intervals -- and kept as a rank-enabled bit-vector over
-// the SA indices in the usual 256-bit super-blocks (`member`, member_build_kernel): one 32-byte read says whether index i is an
-// element AND which one (its slot = the number of member indices before it: the lists lie in SA order in the slot space).
-// This replaces the table of round 2 / 3 (8 bytes per text position, written and read at random by every step, told apart by
-// generation stamps) with n / 7 bytes that are only read; a walk also stops wherever it can, not only where another one has passed
-// EARLIER, so every non-member index is visited by at most one walk.
-// rec[slot]: a position (high bits 0), or delta << kShift | slot of the element it follows; ~0 while the element is still walking.
-// slot0 = first slot of the sweep.
-// one element of one round: v64 = its word (slot << kShift | SA index), e = its place in val / key
-// kAhead (round 0): the index an element steps ONTO is looked up at once -- six in ten elements of a dense batch stand next to
-// another occurrence in the text -- so that they leave the sweep before its largest partition instead of after it; `probed` tells
-// round 1 that its elements have been looked up already.
-template <class BV, typename pos_t, bool kTrail, bool kWide, bool kFirst = false, bool kAhead = false, class Sampling>
-__device__ __forceinline__ void sweep_element(const IndexView& iv, const WalkLds<BV>& s, const Sampling& sampling, uint64_t e, uint64_t v64,
-                                              uint64_t* __restrict__ val, uint16_t* __restrict__ key, uint32_t step, pos_t* __restrict__ out,
-                                              const Block* __restrict__ member, uint64_t* __restrict__ rec, uint64_t slot0,
-                                              uint32_t& n_lv, uint32_t& n_lf, uint32_t& n_fin, bool probed = false, uint8_t* __restrict__ front = nullptr)
-{
-    constexpr uint32_t kShift = kWide ? 33 : 32;
-    constexpr uint64_t kPosMask = (1ull << kShift) - 1;
-    uint64_t i = v64 & kPosMask;
-    uint8_t in_front = 0xFF;                             // (kFirst: the symbol in front of an element that stops on its first step)
-    uint64_t sv = 0;
-    uint32_t owner = 0;
-    if (sampling.probe(i, sv)) {
-        uint64_t r = sv + step;
-        if (r >= iv.n) r -= iv.n;                        // csa_wt.hpp:343-347
-        if (kTrail) rec[slot0 + (v64 >> kShift)] = r;
-        else out[v64 >> kShift] = (pos_t)r;
-        key[e] = (uint16_t)iv.sigma;
-        ++n_fin;
-    } else if (kTrail && !kFirst && !probed && member_probe(member, i, owner)) {
-        // (round 0: every element stands on its own index.)  Index i is where element `owner` started: same text trail, `step`
-        // positions further left
-        const uint64_t delta = step;
-        const uint64_t ro = rec[owner];
-        uint64_t r;
-        if (ro == ~0ull) r = (delta << kShift) | owner;                       // still walking: follow it
-        else if ((ro >> kShift) == 0) r = ro + delta;                          // its position is known
-        else r = ro + (delta << kShift);                                       // it follows someone itself: follow that one
-        rec[slot0 + (v64 >> kShift)] = r;
-        key[e] = (uint16_t)iv.sigma;
-        ++n_fin;
-    } else {
-        if (kTrail && kFirst) rec[slot0 + (v64 >> kShift)] = ~0ull;               // still walking (no pass clears the records beforehand)
-        uint32_t v = 0, c;
-        using walk_t = typename std::conditional<kWide, uint64_t, uint32_t>::type;      // node-relative positions: < n
-        walk_t pos = (walk_t)i;
-        for (;;) {                                       // inverse_select: wt_pc.hpp:385-402
-            const DNode nd = s.nodes[v];
-            uint32_t bit;
-            walk_t r1;
-            BV::rank_bit(iv, s.sh, nd.base, pos, r1, bit);
-            ++n_lv;
-            pos = bit ? r1 : pos - r1;
-            uint32_t ch = bit ? nd.child[1] : nd.child[0];      // (a select, not an indexed read: the node stays in registers)
-            if (ch & kLeafFlag) { c = ch & ~kLeafFlag; break; }
-            v = ch;
-        }
-        ++n_lf;
-        const uint64_t j = s.C[c] + pos;                                      // LF: suffix_array_helper.hpp:341-348
-        if (kTrail && kAhead && member_probe(member, j, owner)) {
-            // (the owner is in its own round 0 right now: its record reads "still walking" or is not written yet -- either way this
-            // element follows it)
-            rec[slot0 + (v64 >> kShift)] = ((uint64_t)(step + 1) << kShift) | owner;
-            key[e] = (uint16_t)iv.sigma;
-            ++n_fin;
-            in_front = (uint8_t)c;
-        } else {
-            val[e] = (v64 & ~kPosMask) | j;
-            key[e] = (uint16_t)c;
-        }
-    }
-    if (kTrail && kFirst && front) front[slot0 + (v64 >> kShift)] = in_front;
-}
-
-#ifndef VLG_SWEEP_PAIRS
-#define VLG_SWEEP_PAIRS 1
-#endif
-constexpr bool kSweepPairs = VLG_SWEEP_PAIRS != 0;
-static_assert(VLG_SWEEP_PAIRS == 0 || VLG_SWEEP_PAIRS == 1, "VLG_SWEEP_PAIRS: 0 or 1");
-template <class BV, typename pos_t, bool kTrail, bool kWide, bool kTextOrder>
-__global__ void __launch_bounds__(256) sweep_step_kernel(IndexView iv, uint64_t* __restrict__ val, uint16_t* __restrict__ key, uint64_t count,
-                                                         uint32_t step, pos_t* __restrict__ out,
-                                                         unsigned long long* __restrict__ stats /* lf, levels */,
-                                                         unsigned long long* __restrict__ n_done, const Block* __restrict__ member,
-                                                         uint64_t* __restrict__ rec, uint64_t slot0, bool probed)
-{
-    __shared__ WalkLds<BV> s;
-    stage_walk(s, iv);
-    using sample_t = typename std::conditional<kWide, uint64_t, uint32_t>::type;
-    using Sampling = typename std::conditional<kTextOrder, TextOrderSampling<sample_t>, SaOrderSampling<sample_t>>::type;
-    const Sampling sampling(iv);
-    uint32_t n_lv = 0, n_lf = 0, n_fin = 0;
-    // (pairs of elements as in round 0 -- sweep_first_pair -- were measured here too, on C4: nothing; the later rounds' elements are sparse)
-    for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < count; e += (uint64_t)gridDim.x * blockDim.x)
-        sweep_element<BV, pos_t, kTrail, kWide>(iv, s, sampling, e, val[e], val, key, step, out, member, rec, slot0, n_lv, n_lf, n_fin, probed);
-    unsigned long long v[3] = {n_lf, n_lv, n_fin};
-    unsigned long long* const dst[3] = {&stats[0], &stats[1], n_done};
-    block_add<3>(v, dst);
-}
-
-// Two elements of round 0 side by side (plain bit-vectors): every tree level and the look-ahead probe of both are loaded before either
-// is used, so a lane has two dependent chains in flight instead of one (the kernel runs at full occupancy on 46 registers and waits
-// ~1 us per wave-wide dependent load: more waves cannot come, more loads per wave can).  Same outcome as two sweep_element calls.
-template <typename pos_t, bool kTrail, bool kWide, bool kAhead, class Sampling>
-__device__ __forceinline__ void sweep_first_pair(const IndexView& iv, const WalkLds<PlainBV>& s, const Sampling& sampling, bool onA, uint64_t eA, uint64_t wA,
-                                                 bool onB, uint64_t eB, uint64_t wB, uint64_t* __restrict__ val, uint16_t* __restrict__ key,
-                                                 pos_t* __restrict__ out, const Block* __restrict__ member, uint64_t* __restrict__ rec, uint64_t slot0,
-                                                 uint32_t& n_lv, uint32_t& n_lf, uint32_t& n_fin, uint8_t* __restrict__ front)
-{
-    constexpr uint32_t kShift = kWide ? 33 : 32;
-    constexpr uint64_t kPosMask = (1ull << kShift) - 1;
-    using walk_t = typename std::conditional<kWide, uint64_t, uint32_t>::type;
-    const uint64_t iA = wA & kPosMask, iB = wB & kPosMask;
-    const bool hadA = onA, hadB = onB;
-    uint64_t sv = 0;
-    if (onA && sampling.probe(iA, sv)) {                                     // csa_wt.hpp:343-347 (round 0: no steps yet)
-        if (kTrail) rec[slot0 + (wA >> kShift)] = sv; else out[wA >> kShift] = (pos_t)sv;
-        key[eA] = (uint16_t)iv.sigma; ++n_fin; onA = false;
-    }
-    if (onB && sampling.probe(iB, sv)) {
-        if (kTrail) rec[slot0 + (wB >> kShift)] = sv; else out[wB >> kShift] = (pos_t)sv;
-        key[eB] = (uint16_t)iv.sigma; ++n_fin; onB = false;
-    }
-    if (kTrail) {                                                            // still walking (no pass clears the records beforehand)
-        if (onA) rec[slot0 + (wA >> kShift)] = ~0ull;
-        if (onB) rec[slot0 + (wB >> kShift)] = ~0ull;
-    }
-    // inverse_select of both (wt_pc.hpp:385-402), level by level
-    uint32_t vA = 0, vB = 0, cA = 0, cB = 0;
-    walk_t pA = (walk_t)iA, pB = (walk_t)iB;
-    bool a = onA, b = onB;
-    while (a || b) {
-        const DNode ndA = s.nodes[vA], ndB = s.nodes[vB];
-        uint32_t blkA, offA, blkB, offB;
-        split224((uint64_t)pA, blkA, offA);
-        split224((uint64_t)pB, blkB, offB);
-        BlockRegs rA, rB;
-        if (a) rA = load_block(iv.blocks, ndA.base + blkA);
-        if (b) rB = load_block(iv.blocks, ndB.base + blkB);
-        if (a) {
-            uint32_t bit;
-            const walk_t r1 = (walk_t)block_rank_bit(rA, offA, bit);
-            ++n_lv;
-            pA = bit ? r1 : pA - r1;
-            const uint32_t ch = bit ? ndA.child[1] : ndA.child[0];
-            if (ch & kLeafFlag) { cA = ch & ~kLeafFlag; a = false; } else vA = ch;
-        }
-        if (b) {
-            uint32_t bit;
-            const walk_t r1 = (walk_t)block_rank_bit(rB, offB, bit);
-            ++n_lv;
-            pB = bit ? r1 : pB - r1;
-            const uint32_t ch = bit ? ndB.child[1] : ndB.child[0];
-            if (ch & kLeafFlag) { cB = ch & ~kLeafFlag; b = false; } else vB = ch;
-        }
-    }
-    const uint64_t jA = s.C[cA] + (uint64_t)pA, jB = s.C[cB] + (uint64_t)pB;  // LF: suffix_array_helper.hpp:341-348
-    n_lf += (onA ? 1u : 0u) + (onB ? 1u : 0u);
-    bool stopA = false, stopB = false;
-    uint32_t ownA = 0, ownB = 0;
-    if (kTrail && kAhead) {                                                  // the look-ahead probes of both, their blocks in flight together
-        uint32_t blkA, offA, blkB, offB, bit;
-        split224(jA, blkA, offA);
-        split224(jB, blkB, offB);
-        BlockRegs rA, rB;
-        if (onA) rA = load_block(member, blkA);
-        if (onB) rB = load_block(member, blkB);
-        if (onA) { ownA = block_rank_bit(rA, offA, bit); stopA = bit != 0; }
-        if (onB) { ownB = block_rank_bit(rB, offB, bit); stopB = bit != 0; }
-    }
-    if (onA) {
-        if (stopA) { rec[slot0 + (wA >> kShift)] = (1ull << kShift) | ownA; key[eA] = (uint16_t)iv.sigma; ++n_fin; }
-        else { val[eA] = (wA & ~kPosMask) | jA; key[eA] = (uint16_t)cA; }
-    }
-    if (onB) {
-        if (stopB) { rec[slot0 + (wB >> kShift)] = (1ull << kShift) | ownB; key[eB] = (uint16_t)iv.sigma; ++n_fin; }
-        else { val[eB] = (wB & ~kPosMask) | jB; key[eB] = (uint16_t)cB; }
-    }
-    if (kTrail && front) {                                                   // the symbol in front of an element that stopped on its first step
-        if (hadA) front[slot0 + (wA >> kShift)] = (onA && stopA) ? (uint8_t)cA : (uint8_t)0xFF;
-        if (hadB) front[slot0 + (wB >> kShift)] = (onB && stopB) ? (uint8_t)cB : (uint8_t)0xFF;
-    }
-}
-
 __global__ void __launch_bounds__(256) sweep_chunk_lists_kernel(const uint64_t* __restrict__ out_off, uint64_t n_pat, uint64_t t0, uint64_t t1,
                                                                 uint32_t* __restrict__ chunk_list)
 {
@@ -903,72 +551,6 @@ __global__ void __launch_bounds__(256) sweep_chunk_lists_kernel(const uint64_t* 
     while (hi - lo > 1) { const uint64_t mid = (lo + hi) >> 1; if (out_off[mid] <= base) lo = mid; else hi = mid; }
     chunk_list[c] = (uint32_t)lo;
 }
-
-// Round 0 without the pass that would write the elements' words first and the read that would fetch them again: an element's word
-// follows from its place -- slot t - t0, SA index l[list] + (t - first slot of the list) -- so a workgroup looks its list up once per
-// 2048 consecutive elements (as sweep_init_kernel does) and walks them at once.
-template <class BV, typename pos_t, bool kTrail, bool kWide, bool kTextOrder, bool kAhead>
-__global__ void __launch_bounds__(256) sweep_first_kernel(IndexView iv, const uint64_t* __restrict__ l, const uint64_t* __restrict__ out_off, uint64_t n_pat,
-                                                          uint64_t t0, uint64_t total, uint64_t* __restrict__ val, uint16_t* __restrict__ key,
-                                                          pos_t* __restrict__ out, unsigned long long* __restrict__ stats,
-                                                          unsigned long long* __restrict__ n_done, const Block* __restrict__ member,
-                                                          uint64_t* __restrict__ rec, const uint32_t* __restrict__ chunk_list, uint8_t* __restrict__ front)
-{
-    __shared__ WalkLds<BV> s;
-    __shared__ ListStage s_lists;
-    stage_walk(s, iv);
-    using sample_t = typename std::conditional<kWide, uint64_t, uint32_t>::type;
-    using Sampling = typename std::conditional<kTextOrder, TextOrderSampling<sample_t>, SaOrderSampling<sample_t>>::type;
-    const Sampling sampling(iv);
-    constexpr uint32_t kShift = kWide ? 33 : 32;
-    constexpr uint32_t kPer = kSweepChunk / 256;
-    uint32_t n_lv = 0, n_lf = 0, n_fin = 0;
-    for (uint64_t base = t0 + (uint64_t)blockIdx.x * kSweepChunk; base < total; base += (uint64_t)gridDim.x * kSweepChunk) {
-        __syncthreads();                                                         // (the lists staged for the previous turn have been read)
-        uint64_t p = chunk_list[(base - t0) / kSweepChunk];                      // the list of the chunk's first element (sweep_chunk_lists_kernel)
-        const uint64_t end = base + 256 * kPer < total ? base + 256 * kPer : total;
-        const bool staged = kStageLists && stage_lists(s_lists, out_off, l, n_pat, p, end);
-        uint32_t q = 0;
-        auto word_of = [&](uint64_t t) -> uint64_t {                            // slot << kShift | SA index of element t (t ascends from call to call)
-            uint64_t sai;
-            if (staged) {
-                while (s_lists.off[q + 1] <= t) ++q;
-                sai = s_lists.l[q] + (t - s_lists.off[q]);
-            } else {
-                while (out_off[p + 1] <= t) ++p;
-                sai = l[p] + (t - out_off[p]);
-            }
-            return ((t - t0) << kShift) | sai;
-        };
-        // (measured, round 4: C4 -- 33-bit indices, a deeper tree -- locate 98 -> 93 ms; C3 16.9 -> 17.4 ms: there the kernel has no issue slots
-        //  to spare and loses a wave per SIMD to the registers: pairs for wide indices only)
-        if constexpr (std::is_same<BV, PlainBV>::value && kSweepPairs && kWide) {
-            static_assert(kPer % 2 == 0, "elements are taken in pairs");
-#pragma unroll 1
-            for (uint32_t i = 0; i < kPer; i += 2) {
-                const uint64_t tA = base + i * 256 + threadIdx.x, tB = tA + 256;
-                const bool onA = tA < total, onB = tB < total;
-                const uint64_t wA = onA ? word_of(tA) : 0, wB = onB ? word_of(tB) : 0;
-                sweep_first_pair<pos_t, kTrail, kWide, kAhead>(iv, s, sampling, onA, tA - t0, wA, onB, tB - t0, wB, val, key, out, member, rec, t0, n_lv, n_lf, n_fin, front);
-            }
-        } else {
-#pragma unroll 1
-            for (uint32_t i = 0; i < kPer; ++i) {
-                const uint64_t t = base + i * 256 + threadIdx.x;
-                if (t < total)
-                    sweep_element<BV, pos_t, kTrail, kWide, true, kAhead>(iv, s, sampling, t - t0, word_of(t), val, key, 0u, out, member, rec, t0, n_lv, n_lf, n_fin, false, front);
-            }
-        }
-    }
-    unsigned long long v[3] = {n_lf, n_lv, n_fin};
-    unsigned long long* const dst[3] = {&stats[0], &stats[1], n_done};
-    block_add<3>(v, dst);
-}
-
-// stragglers: the elements still alive after the sweep are finished without sorting them any more, by locate_kernel<.., kTail>:
-// how long an element still walks is geometrically distributed (one SA index in `dens` is sampled), so a lane that kept one
-// element to its end would idle most of the time behind the longest walk of its wave; there a lane that has finished takes the
-// next element of its wave's slice.
 
 // Records of a trail-sharing sweep -> positions: every element follows its chain of records (element it follows, steps apart) to
 // the end, at most kResolveHops hops per round, and replaces its record by what it found -- a position, or a shorter pointer for
@@ -1176,27 +758,6 @@ template <> struct WalkerWord<true> {
     static __device__ __forceinline__ uint16_t key(uint32_t c, uint32_t v) { return (uint16_t)(c | ((v >> 31) << 15)); }
 };
 
-// one LF step from SA index i: the symbol read (compact) and LF(i)
-template <class BV, bool kWide>
-__device__ __forceinline__ uint64_t lf_step(const IndexView& iv, const WalkLds<BV>& s, uint64_t i, uint32_t& c, uint32_t& n_lv)
-{
-    using walk_t = typename std::conditional<kWide, uint64_t, uint32_t>::type;      // node-relative positions: < n
-    uint32_t v = 0;
-    walk_t pos = (walk_t)i;
-    for (;;) {                                               // inverse_select: wt_pc.hpp:385-402
-        const DNode nd = s.nodes[v];
-        uint32_t bit;
-        walk_t r1;
-        BV::rank_bit(iv, s.sh, nd.base, pos, r1, bit);
-        ++n_lv;
-        pos = bit ? r1 : pos - r1;
-        const uint32_t ch = bit ? nd.child[1] : nd.child[0];
-        if (ch & kLeafFlag) { c = ch & ~kLeafFlag; break; }
-        v = ch;
-    }
-    return s.C[c] + (uint64_t)pos;                           // LF: suffix_array_helper.hpp:341-348
-}
-
 // kFirst: round 0 -- element e is sample e (no words read); otherwise the walkers [0, count) of val / key, dead ones skipped (the
 // host may pass a count from a few rounds ago: the dead are at the end, the partition keeps them there).
 template <class BV, bool kWide, bool kFirst>
@@ -1206,6 +767,7 @@ __global__ void __launch_bounds__(256) unsample_step_kernel(IndexView iv, uint64
 {
     __shared__ WalkLds<BV> s;
     stage_walk(s, iv);
+    const ByteWalk<BV, kWide> walk{iv, s};
     using sample_t = typename std::conditional<kWide, uint64_t, uint32_t>::type;
     const sample_t* __restrict__ samples = reinterpret_cast<const sample_t*>(iv.samples);
     const uint32_t dens = iv.dens, dmask = dens - 1;
@@ -1226,7 +788,7 @@ __global__ void __launch_bounds__(256) unsample_step_kernel(IndexView iv, uint64
             WalkerWord<kWide>::unpack(val[e], k, i, v);
         }
         uint32_t c;
-        const uint64_t i2 = lf_step<BV, kWide>(iv, s, i, c, n_lv);
+        const uint64_t i2 = walk.lf(i, c, n_lv);
         ++n_lf;
         const uint32_t v2 = (!kWide && v == 0) ? (uint32_t)(iv.n - 1) : v - 1;      // SA[LF(i)] = SA[i] - 1 (mod n): csa_wt.hpp:343-347
         const bool arrived = pow2 ? ((i2 & dmask) == 0) : (i2 % dens == 0);
@@ -1243,60 +805,41 @@ __global__ void __launch_bounds__(256) unsample_step_kernel(IndexView iv, uint64
 }
 
 // The last walkers (how long a walk is, is geometrically distributed: a few are still on their way after 100 rounds) finish without
-// being sorted any more, lane by lane with refill as in locate_kernel: a wave owns a slice of the walkers, a lane that arrives pulls
-// the next one.
+// being sorted any more, lane by lane with refill as in locate_kernel (WaveSlice): a wave owns a slice of the walkers, a lane that
+// arrives pulls the next one.
 template <class BV, bool kWide>
 __global__ void __launch_bounds__(256) unsample_tail_kernel(IndexView iv, const uint64_t* __restrict__ val, const uint16_t* __restrict__ key, uint64_t total,
                                                             uint32_t per_wave, uint32_t* __restrict__ sa, unsigned long long* __restrict__ stats)
 {
+    using Walk = ByteWalk<BV, kWide>;
     __shared__ WalkLds<BV> s;
     stage_walk(s, iv);
-    const uint32_t lane = threadIdx.x & 63;
-    const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    uint64_t next = wave * per_wave;
-    const uint64_t slice_end = next + per_wave < total ? next + per_wave : total;
+    const Walk walk{iv, s};
+    WaveSlice slice(total, per_wave);
     const uint32_t dens = iv.dens, dmask = dens - 1;
     const bool pow2 = (dens & dmask) == 0;
     uint64_t i = 0;
-    uint32_t v = 0, node = 0;
+    uint32_t v = 0;
+    typename Walk::Cursor node;
     bool active = false, need = true;
     uint32_t n_lf = 0, n_lv = 0;
     for (;;) {
-        const unsigned long long m = __ballot(need);
-        if (m) {
-            const uint32_t before = __popcll(m & ((1ull << lane) - 1ull));
-            if (need) {
-                const uint64_t cand = next + before;
-                active = false;
-                if (cand < slice_end) {
-                    const uint16_t k = key[cand];
-                    if ((k & 0x7FFFu) != kUnsampleDead) { WalkerWord<kWide>::unpack(val[cand], k, i, v); node = 0; active = true; }
-                }
-                need = !active && cand < slice_end;          // a dead walker: take another one next turn
+        slice.refill(need, [&](uint64_t cand) {
+            active = false;
+            if (cand < slice.end) {
+                const uint16_t k = key[cand];
+                if ((k & 0x7FFFu) != kUnsampleDead) { WalkerWord<kWide>::unpack(val[cand], k, i, v); node = typename Walk::Cursor(); active = true; }
             }
-            next += __popcll(m);
-        }
+            need = !active && cand < slice.end;              // a dead walker: take another one next turn
+        });
         if (!__any(active) && !__any(need)) break;
-        if (active) {
-            const DNode nd = s.nodes[node];
-            uint32_t bit;
-            uint64_t r1;
-            BV::rank_bit(iv, s.sh, nd.base, i, r1, bit);
-            ++n_lv;
-            const uint64_t ni = bit ? r1 : i - r1;
-            const uint32_t ch = bit ? nd.child[1] : nd.child[0];
-            if (ch & kLeafFlag) {
-                i = s.C[ch & ~kLeafFlag] + ni;
-                v = (!kWide && v == 0) ? (uint32_t)(iv.n - 1) : v - 1;
-                node = 0;
-                ++n_lf;
-                const bool arrived = pow2 ? ((i & dmask) == 0) : (i % dens == 0);
-                if (arrived) { need = true; active = false; }
-                else sa[i] = v;
-            } else {
-                i = ni;
-                node = ch;
-            }
+        uint32_t c;
+        if (active && walk.level(node, i, c, n_lv)) {
+            v = (!kWide && v == 0) ? (uint32_t)(iv.n - 1) : v - 1;
+            ++n_lf;
+            const bool arrived = pow2 ? ((i & dmask) == 0) : (i % dens == 0);
+            if (arrived) { need = true; active = false; }
+            else sa[i] = v;
         }
     }
     if (stats) {
@@ -1314,44 +857,20 @@ __global__ void __launch_bounds__(256) isa_samples_kernel(IndexView iv, uint32_t
 {
     __shared__ WalkLds<BV> s;
     stage_walk(s, iv);
+    const ByteWalk<BV, true> walk{iv, s};                    // (node-relative positions in 64 bits whatever the width of the samples)
     const pos_t* samples = reinterpret_cast<const pos_t*>(iv.samples);
     for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < iv.n_samples; j += (uint64_t)gridDim.x * blockDim.x) {
         uint64_t i = j * iv.dens, v = samples[j];
         do {
             if (v % inv_dens == 0) out[v / inv_dens] = (out_t)i;
-            uint32_t node = 0, c;
-            uint64_t pos = i;
-            for (;;) {                                       // inverse_select: wt_pc.hpp:385-402
-                const DNode nd = s.nodes[node];
-                uint32_t bit;
-                uint64_t r1;
-                BV::rank_bit(iv, s.sh, nd.base, pos, r1, bit);
-                pos = bit ? r1 : pos - r1;
-                const uint32_t ch = bit ? nd.child[1] : nd.child[0];      // (a select, not an indexed read: the node stays in registers)
-                if (ch & kLeafFlag) { c = ch & ~kLeafFlag; break; }
-                node = ch;
-            }
-            i = s.C[c] + pos;                                // LF
+            uint32_t c, n_lv = 0;
+            i = walk.lf(i, c, n_lv);
             v = v ? v - 1 : iv.n - 1;
         } while (i % iv.dens);
     }
 }
 
 // ---- text access (extract.hpp): sdsl::extract and csa.isa[i] on the Huffman-shaped tree -----------------------------------------------
-template <class BV, bool kWide>
-struct ByteWalk {
-    const IndexView& iv;
-    const WalkLds<BV>& s;
-    const uint8_t* c2c;                                      // comp2char in LDS
-    __device__ __forceinline__ uint64_t lf(uint64_t i, uint32_t& c) const
-    {
-        if (iv.sigma == 1) { c = 0; return 0; }              // degenerate: only the sentinel exists (n = 1)
-        uint32_t n_lv = 0;
-        return lf_step<BV, kWide>(iv, s, i, c, n_lv);
-    }
-    __device__ __forceinline__ uint8_t sym(uint32_t c) const { return c2c[c]; }
-};
-
 template <class BV, bool kWide, typename isa_t>
 __global__ void __launch_bounds__(256) extract_kernel(IndexView iv, ExtractJob job, const isa_t* __restrict__ isa, const uint8_t* __restrict__ comp2char,
                                                       uint8_t* __restrict__ out)
@@ -1369,7 +888,7 @@ __global__ void __launch_bounds__(256) isa_kernel(IndexView iv, uint32_t d, cons
 {
     __shared__ WalkLds<BV> s;
     stage_walk(s, iv);
-    isa_queries(p, out, count, iv.n, d, isa, ByteWalk<BV, kWide>{iv, s, nullptr}, bad);
+    isa_queries(p, out, count, iv.n, d, isa, ByteWalk<BV, kWide>{iv, s}, bad);
 }
 
 // comp2char of a byte index from its char2comp (comp 0 is the sentinel; absent characters map to 0 and are skipped)
@@ -1404,6 +923,11 @@ __global__ void narrow_kernel(const uint64_t* __restrict__ in, pos_t* __restrict
     for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < count; j += (uint64_t)gridDim.x * blockDim.x) out[j] = (pos_t)in[j];
 }
 
+// the byte index's sampling policy: sample words as wide as its SA indices
+template <bool kWide, bool kTextOrder>
+using ByteSampling = typename std::conditional<kTextOrder, TextOrderSampling<typename std::conditional<kWide, uint64_t, uint32_t>::type>,
+                                               SaOrderSampling<typename std::conditional<kWide, uint64_t, uint32_t>::type>>::type;
+
 inline uint32_t grid_for(uint64_t n, uint32_t cap = 16384) { return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, cap)); }
 
 }  // namespace
@@ -1437,29 +961,18 @@ vlg_status launch_expand(const uint64_t* d_l, const uint64_t* d_out_off, uint64_
 template vlg_status launch_expand<uint32_t>(const uint64_t*, const uint64_t*, uint64_t, uint64_t, uint32_t*, uint32_t*, hipStream_t);
 template vlg_status launch_expand<uint64_t>(const uint64_t*, const uint64_t*, uint64_t, uint64_t, uint64_t*, uint32_t*, hipStream_t);
 
-// Slices: enough waves to fill 256 CUs x 32 waves several times over, but slices long enough that the
-// drain tail (the slowest occurrence of a slice) stays a small fraction of the slice.
 template <typename pos_t>
 vlg_status launch_locate(const IndexView& iv, pos_t* d_io, uint64_t total, unsigned long long* d_stats, hipStream_t stream)
 {
     if (!total) return VLG_OK;
-    const uint64_t target_waves = 256ull * 32 * 4;
-    uint64_t per_wave = (total + target_waves - 1) / target_waves;
-    per_wave = std::max<uint64_t>(per_wave, 64 * 16);
-    per_wave = std::min<uint64_t>(per_wave, 1u << 20);
-    uint64_t waves = (total + per_wave - 1) / per_wave;
-    uint64_t wgs = (waves + 3) / 4;
+    const LocateSlices sl = locate_slices(total);
     const bool rrr = iv.bv_kind == kBvRrr63, text_order = iv.sampling == kSamplingTextOrder;
     if (iv.sample_bytes != sizeof(pos_t)) return fail(VLG_E_INTERNAL, "locate: sample width does not match the instantiation");
-    const dim3 grid((uint32_t)wgs);
-#define VLG_LOCATE(BV, TO) hipLaunchKernelGGL(HIP_KERNEL_NAME(locate_kernel<pos_t, BV, false, (sizeof(pos_t) == 8), TO>), grid, dim3(256), 0, stream, iv, d_io, total, (uint32_t)per_wave, d_stats)
-    if constexpr (sizeof(pos_t) == 4) {
-        if (text_order) { if (rrr) VLG_LOCATE(RrrBV, true); else VLG_LOCATE(PlainBV, true); }
-        else { if (rrr) VLG_LOCATE(RrrBV, false); else VLG_LOCATE(PlainBV, false); }
-    } else {
-        if (text_order) { if (rrr) VLG_LOCATE(RrrBV, true); else VLG_LOCATE(PlainBV, true); }
-        else { if (rrr) VLG_LOCATE(RrrBV, false); else VLG_LOCATE(PlainBV, false); }
-    }
+    constexpr bool kWide = sizeof(pos_t) == 8;
+    const dim3 grid(sl.blocks);
+#define VLG_LOCATE(BV, TO) hipLaunchKernelGGL(HIP_KERNEL_NAME(locate_kernel<ByteWalk<BV, kWide>, ByteSampling<kWide, TO>, pos_t, false, kWide>), grid, dim3(256), 0, stream, iv, d_io, total, sl.per_wave, d_stats)
+    if (text_order) { if (rrr) VLG_LOCATE(RrrBV, true); else VLG_LOCATE(PlainBV, true); }
+    else { if (rrr) VLG_LOCATE(RrrBV, false); else VLG_LOCATE(PlainBV, false); }
 #undef VLG_LOCATE
     VLG_HIP_TRY(hipGetLastError());
     return VLG_OK;
@@ -1558,14 +1071,9 @@ vlg_status run_locate_sweep(const SweepKernels& K, const uint64_t* d_l, const ui
             if (step > 1u << 20) return fail(VLG_E_INTERNAL, "locate sweep did not converge");
         }
         if (alive) {
-            // slices as launch_locate cuts them: enough waves to fill the chip several times over, long enough that a slice's slowest
-            // element is a small part of it
-            const uint64_t target_waves = 256ull * 32 * 4;
-            uint64_t per_wave = (alive + target_waves - 1) / target_waves;
-            per_wave = std::min<uint64_t>(std::max<uint64_t>(per_wave, 64 * 16), 1u << 20);
-            const uint64_t waves = (alive + per_wave - 1) / per_wave;
+            const LocateSlices sl = locate_slices(alive);
             if (timer) timer->begin(0);
-            K.tail(out, alive, (uint32_t)per_wave, val_a, step, member ? rec : nullptr, t0, member, (uint32_t)((waves + 3) / 4));
+            K.tail(out, alive, sl.per_wave, val_a, step, member ? rec : nullptr, t0, member, sl.blocks);
             if (timer) timer->end(0);
             VLG_HIP_TRY(hipGetLastError());
         }
@@ -1634,8 +1142,8 @@ vlg_status launch_locate_sweep(const IndexView& iv, const uint64_t* d_l, const u
         pos_t* out = static_cast<pos_t*>(out_);
         launch_sweep_chunk_lists(d_out_off, n_pat, t0, t1, chunk_list, stream);
         const dim3 grid_first(grid_for((t1 - t0 + 7) / 8, 8192));
-#define VLG_FIRST(BV, TR, TO) do { if (ahead) hipLaunchKernelGGL(HIP_KERNEL_NAME(sweep_first_kernel<BV, pos_t, TR, kWide, TO, TR>), grid_first, dim3(256), 0, stream, iv, d_l, d_out_off, n_pat, t0, t1, val, key, out, d_stats, counter, mem, rc, chunk_list, fr); \
-                                    else hipLaunchKernelGGL(HIP_KERNEL_NAME(sweep_first_kernel<BV, pos_t, TR, kWide, TO, false>), grid_first, dim3(256), 0, stream, iv, d_l, d_out_off, n_pat, t0, t1, val, key, out, d_stats, counter, mem, rc, chunk_list, fr); } while (0)
+#define VLG_FIRST(BV, TR, TO) do { if (ahead) hipLaunchKernelGGL(HIP_KERNEL_NAME(sweep_first_kernel<ByteWalk<BV, kWide>, ByteSampling<kWide, TO>, pos_t, TR, kWide, TR>), grid_first, dim3(256), 0, stream, iv, d_l, d_out_off, n_pat, t0, t1, val, key, out, d_stats, counter, mem, rc, chunk_list, fr); \
+                                    else hipLaunchKernelGGL(HIP_KERNEL_NAME(sweep_first_kernel<ByteWalk<BV, kWide>, ByteSampling<kWide, TO>, pos_t, TR, kWide, false>), grid_first, dim3(256), 0, stream, iv, d_l, d_out_off, n_pat, t0, t1, val, key, out, d_stats, counter, mem, rc, chunk_list, fr); } while (0)
 #define VLG_FIRST_BV(TR, TO) do { if (rrr) VLG_FIRST(RrrBV, TR, TO); else VLG_FIRST(PlainBV, TR, TO); } while (0)
         if (text_order) { if (mem) VLG_FIRST_BV(true, true); else VLG_FIRST_BV(false, true); }
         else { if (mem) VLG_FIRST_BV(true, false); else VLG_FIRST_BV(false, false); }
@@ -1645,7 +1153,7 @@ vlg_status launch_locate_sweep(const IndexView& iv, const uint64_t* d_l, const u
     K.step = [&](uint64_t* val, uint16_t* key, uint64_t alive, uint32_t step, void* out_, unsigned long long* counter, const Block* mem, uint64_t* rc, uint64_t t0, bool probed) {
         pos_t* out = static_cast<pos_t*>(out_);
         const dim3 grid(grid_for(alive, 4096));
-#define VLG_STEP(BV, TR, TO) hipLaunchKernelGGL(HIP_KERNEL_NAME(sweep_step_kernel<BV, pos_t, TR, kWide, TO>), grid, dim3(256), 0, stream, iv, val, key, alive, step, out, d_stats, counter, mem, rc, t0, probed)
+#define VLG_STEP(BV, TR, TO) hipLaunchKernelGGL(HIP_KERNEL_NAME(sweep_step_kernel<ByteWalk<BV, kWide>, ByteSampling<kWide, TO>, pos_t, TR, kWide>), grid, dim3(256), 0, stream, iv, val, key, alive, step, out, d_stats, counter, mem, rc, t0, probed)
 #define VLG_STEP_BV(TR, TO) do { if (rrr) VLG_STEP(RrrBV, TR, TO); else VLG_STEP(PlainBV, TR, TO); } while (0)
         if (text_order) { if (mem) VLG_STEP_BV(true, true); else VLG_STEP_BV(false, true); }
         else { if (mem) VLG_STEP_BV(true, false); else VLG_STEP_BV(false, false); }
@@ -1655,7 +1163,7 @@ vlg_status launch_locate_sweep(const IndexView& iv, const uint64_t* d_l, const u
     K.tail = [&](void* out_, uint64_t alive, uint32_t per_wave, const uint64_t* val, uint32_t step, uint64_t* rc, uint64_t t0, const Block* mem, uint32_t blocks) {
         pos_t* out = static_cast<pos_t*>(out_);
         const dim3 grid(blocks);
-#define VLG_TAIL(BV, TO) hipLaunchKernelGGL(HIP_KERNEL_NAME(locate_kernel<pos_t, BV, true, kWide, TO>), grid, dim3(256), 0, stream, iv, out, alive, per_wave, d_stats, val, step, rc, t0, mem)
+#define VLG_TAIL(BV, TO) hipLaunchKernelGGL(HIP_KERNEL_NAME(locate_kernel<ByteWalk<BV, kWide>, ByteSampling<kWide, TO>, pos_t, true, kWide>), grid, dim3(256), 0, stream, iv, out, alive, per_wave, d_stats, val, step, rc, t0, mem)
         if (text_order) { if (rrr) VLG_TAIL(RrrBV, true); else VLG_TAIL(PlainBV, true); }
         else { if (rrr) VLG_TAIL(RrrBV, false); else VLG_TAIL(PlainBV, false); }
 #undef VLG_TAIL
@@ -1725,14 +1233,11 @@ vlg_status launch_unsample(const IndexView& iv, const uint64_t* d_l, const uint6
     if (alive || round == 1) {
         // (after an unsorted round 0 the dead are anywhere: the tail looks at all of them)
         const uint64_t span = round == 1 ? iv.n_samples : alive;
-        const uint64_t target_waves = 256ull * 32 * 4;
-        uint64_t per_wave = (span + target_waves - 1) / target_waves;
-        per_wave = std::min<uint64_t>(std::max<uint64_t>(per_wave, 64 * 4), 1u << 20);
-        const uint64_t waves = (span + per_wave - 1) / per_wave;
-        const dim3 grid((uint32_t)((waves + 3) / 4));
+        const LocateSlices sl = locate_slices(span, 64 * 4);
+        const dim3 grid(sl.blocks);
         if (timer) timer->begin(0);
-        if (rrr) hipLaunchKernelGGL(HIP_KERNEL_NAME(unsample_tail_kernel<RrrBV, kWide>), grid, dim3(256), 0, stream, iv, val_a, key_a, span, (uint32_t)per_wave, sa_full, d_stats);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(unsample_tail_kernel<PlainBV, kWide>), grid, dim3(256), 0, stream, iv, val_a, key_a, span, (uint32_t)per_wave, sa_full, d_stats);
+        if (rrr) hipLaunchKernelGGL(HIP_KERNEL_NAME(unsample_tail_kernel<RrrBV, kWide>), grid, dim3(256), 0, stream, iv, val_a, key_a, span, sl.per_wave, sa_full, d_stats);
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(unsample_tail_kernel<PlainBV, kWide>), grid, dim3(256), 0, stream, iv, val_a, key_a, span, sl.per_wave, sa_full, d_stats);
         if (timer) timer->end(0);
         VLG_HIP_TRY(hipGetLastError());
     }

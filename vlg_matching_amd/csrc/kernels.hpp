@@ -1,5 +1,6 @@
 // Internal launch interface between kernels.hip and search.hip.
 #pragma once
+#include <algorithm>
 #include <functional>
 #include "common.hpp"
 
@@ -23,6 +24,18 @@ struct LaunchTimer {
     virtual void begin(int which, uint64_t algorithmic_bytes = 0) = 0;     // which: 0 = LF step kernel, 1 = stable partition by symbol, 2 = trail record resolution
     virtual void end(int which) = 0;
 };
+
+// The slices the refilling-lane kernels (locate_kernel, unsample_tail_kernel) cut `count` elements into, one per wave: enough waves to
+// fill 256 CUs x 32 waves several times over, but slices long enough (min_per_wave) that the drain tail -- the slowest element of a
+// slice -- stays a small fraction of the slice.  blocks: workgroups of four waves.
+struct LocateSlices { uint32_t per_wave, blocks; };
+inline LocateSlices locate_slices(uint64_t count, uint64_t min_per_wave = 64 * 16)
+{
+    const uint64_t target_waves = 256ull * 32 * 4;
+    const uint64_t per_wave = std::min<uint64_t>(std::max<uint64_t>((count + target_waves - 1) / target_waves, min_per_wave), 1u << 20);
+    const uint64_t waves = (count + per_wave - 1) / per_wave;
+    return LocateSlices{(uint32_t)per_wave, (uint32_t)((waves + 3) / 4)};
+}
 
 size_t sweep_temp_bytes(uint64_t total, uint32_t sigma, hipStream_t stream);
 // occurrences one sweep can cover: slots share a 64-bit word with the SA index (32 + 32 bits, or 31 + 33 when SA indices are wide)
