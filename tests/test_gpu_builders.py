@@ -167,3 +167,53 @@ def test_int_builder_adversarial(torch_cuda, V, oracle, name):
     w.sa_device(d_i.data_ptr(), d_o.data_ptr(), o.n)
     torch.cuda.synchronize()
     assert (d_o.cpu().numpy().view(np.uint64) == sa).all()
+
+
+def test_failure_paths_free_their_scratch(torch_cuda, V):
+    """A builder that fails after it has allocated device scratch gives all of it back: 64 refused calls of each of
+      * build_int on 2^19 symbols whose last one is 0 (VLG_E_ZERO_BYTE, after the text and the suffix-array flags, 12 MiB, are on the device),
+      * vlg_wtsa_from_parts, through the Python loader, on the dna_3000 golden with one count word altered (VLG_E_INVALID),
+      * resample of a text-order index (VLG_E_INVALID),
+    with the device's free memory read before and after (a build_int that freed nothing would be down 768 MiB), and a
+    build_int and a WtsaIndex built right after still pass the suffix-array certificate."""
+    import os
+    from vlg_matching_amd import capi
+    from vlg_matching_amd.index import read_sdsl_wtsa_file
+    torch = torch_cuda
+
+    def refused(call, status):
+        with pytest.raises(V.VlgError) as e:
+            call()
+        assert e.value.status == status
+
+    with_zero = np.full(1 << 19, 7, dtype=np.uint32)
+    with_zero[-1] = 0
+    good = read_sdsl_wtsa_file(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "wtsa_sdsl", "dna_3000.sdsl"))
+    damaged = dict(good, data=good["data"].copy())
+    damaged["data"][9 * 3] ^= np.uint64(1)
+    text = INT_TEXTS["zero_bytes_random"]
+    text_order = V.VlgIndex.build_int(text).resample(text_order=True, dens=16)
+    torch.cuda.synchronize()
+    free_before = torch.cuda.mem_get_info()[0]
+    for _ in range(64):
+        refused(lambda: V.VlgIndex.build_int(with_zero), capi.E_ZERO_BYTE)
+    torch.cuda.synchronize()
+    free_after = torch.cuda.mem_get_info()[0]
+    print("free device memory: %d before, %d after 64 refused build_int calls" % (free_before, free_after))
+    assert free_before - free_after < 128 << 20
+    for _ in range(64):
+        refused(lambda: V.WtsaIndex.from_parts(damaged), capi.E_INVALID)
+        refused(lambda: text_order.resample(text_order=False, dens=32), capi.E_INVALID)
+    # right after: both builders still work
+    n = len(text) + 1
+    d_text = torch.from_numpy(text.astype(np.int64)).cuda()
+    d_i = torch.arange(n, dtype=torch.int64, device="cuda")
+    d_sa = torch.zeros_like(d_i)
+    idx = V.VlgIndex.build_int(text)
+    V.capi.check(V.lib().vlg_sa_batch(idx._h, d_i.data_ptr(), d_sa.data_ptr(), n, None))
+    torch.cuda.synchronize()
+    certify_suffix_array(d_text, d_sa)
+    d_sa.zero_()
+    V.WtsaIndex(text).sa_device(d_i.data_ptr(), d_sa.data_ptr(), n)
+    torch.cuda.synchronize()
+    certify_suffix_array(d_text, d_sa)

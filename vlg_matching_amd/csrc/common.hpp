@@ -21,6 +21,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <algorithm>
+#include <memory>
 #include <new>
 #include <string>
 #include <vector>
@@ -137,6 +139,42 @@ void release_cached_device_memory();      // result buffers parked for reuse (se
                                std::string(#expr) + ": " + hipGetErrorString(_e));               \
     } while (0)
 
+// Device scratch that frees itself: whatever a builder or an export allocates and does not hand to an index.  release() frees now
+// (a builder lets its big arrays go as soon as no later stage reads them), take() hands the allocation to the object that owns it
+// from then on.  An empty request still allocates (256 bytes), so that a buffer of an empty text is a pointer like any other.
+struct DevBuf {
+    void* p = nullptr;
+    size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; } return *this; }
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
+    hipError_t alloc(size_t bytes)
+    {
+        release();
+        const hipError_t e = hipMalloc(&p, bytes ? bytes : 256);
+        if (e == hipSuccess) cap = bytes; else p = nullptr;
+        return e;
+    }
+    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+    void* take() { void* q = p; p = nullptr; cap = 0; return q; }
+    template <class T> T* as() const { return reinterpret_cast<T*>(p); }
+};
+// rocPRIM's two calls -- call(nullptr, bytes) asks for the scratch size, call(scratch, bytes) runs -- around a scratch buffer that
+// grows when a call wants more than it holds
+template <class Call>
+hipError_t with_scratch(DevBuf& scratch, Call&& call)
+{
+    size_t bytes = 0;
+    hipError_t e = call(nullptr, bytes);
+    if (e == hipSuccess && (!scratch.p || bytes > scratch.cap)) e = scratch.alloc(bytes);
+    return e == hipSuccess ? call(scratch.p, bytes) : e;
+}
+// blocks of 256 threads for n items of a grid-stride kernel, at most `cap` and at least one
+inline dim3 launch_grid(uint64_t n, uint32_t cap = 16384) { return dim3((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, cap))); }
+
 // Host memory the batch path copies from / into.  Pageable vectors there are pinned by the runtime on the fly, and
 // freeing them afterwards (munmap) makes the driver evict and restore the process's GPU queues: tens of ms in which the
 // next kernel does not start.  These vectors live in pinned blocks owned by the workspace instead: handed out bump-style
@@ -252,6 +290,12 @@ struct vlg_index {
 };
 
 namespace vlg {
+// an object under construction: its destroy function takes it, with what it owns by then, unless release() hands it to the caller
+template <class T, void (*Destroy)(T*)> struct DestroyWith { void operator()(T* p) const { Destroy(p); } };
+template <class T, void (*Destroy)(T*)> using Building = std::unique_ptr<T, DestroyWith<T, Destroy>>;
+// (an index frees d_blob only where owns_blob is set: a fresh one holds no blob, and whoever points d_blob at memory of the caller's
+// clears owns_blob in the same place -- the attach functions -- so a failure after that never frees the caller's blob)
+using IndexPtr = Building<vlg_index, vlg_index_destroy>;
 // the paper's index on disk (wtsa_sdsl.hpp): m_text packed to `width` bits (in: 0 = the index's own width; out: the width used), and
 // bit_vector_il<512>::m_data of the tree, both converted on the device and copied to the host
 vlg_status wtsa_text_words(const vlg_wtsa* idx, uint32_t& width, std::vector<uint64_t>& words);

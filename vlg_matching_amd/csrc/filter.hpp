@@ -1027,7 +1027,7 @@ vlg_status filter_group(uint64_t n_positions /* every list element is smaller */
             // fences of the survivors' lists: whole blocks of [Pc, Pc + total) (Pc starts on a block)
             if (L.F && fg.cpre.back() >= 64) {
                 const uint64_t g0 = (uint64_t)(Pc - P) / 64;
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(fence_build_kernel<pos_t>), dim3(grid_for(fg.cpre.back() / 64, 8192)), dim3(256), 0, st, P, g0, g0 + fg.cpre.back() / 64, L.F);
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(fence_build_kernel<pos_t>), launch_grid(fg.cpre.back() / 64, 8192), dim3(256), 0, st, P, g0, g0 + fg.cpre.back() / 64, L.F);
                 VLG_HIP_TRY(hipGetLastError());
             }
         }

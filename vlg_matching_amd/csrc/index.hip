@@ -129,13 +129,6 @@ InnerTable make_inner_table(const HostTree& t)
     return tab;
 }
 
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 256); }
-    template <class T> T* as() { return reinterpret_cast<T*>(p); }
-};
-
 void bind_view(vlg_index* idx)
 {
     uint8_t* b = reinterpret_cast<uint8_t*>(idx->d_blob);
@@ -212,7 +205,9 @@ vlg_status alloc_blob(vlg_index* idx, uint64_t n, uint32_t dens, hipStream_t str
     const char* f64 = getenv("VLG_FORCE_POS64");
     h.sample_bytes = (n <= 0x100000000ull && !(f64 && (f64[0] == '1' || f64[0] == '2'))) ? 4 : 8;
     layout_blob(h);
-    VLG_HIP_TRY(hipMalloc(&idx->d_blob, h.total_bytes));
+    DevBuf blob;
+    VLG_HIP_TRY(blob.alloc(h.total_bytes));
+    idx->d_blob = blob.take();
     idx->owns_blob = true;
     uint8_t* b = reinterpret_cast<uint8_t*>(idx->d_blob);
     VLG_HIP_TRY(hipMemcpyAsync(b, &h, sizeof h, hipMemcpyHostToDevice, stream));
@@ -240,12 +235,10 @@ vlg_status fill_block_counts(vlg_index* idx, const InnerTable* d_tab, hipStream_
     DevBuf scan, temp;
     VLG_HIP_TRY(scan.alloc(nb * 8));
     auto in = rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint64_t>(0), BlockPop{blocks});
-    size_t tb = 0;
-    VLG_HIP_TRY(rocprim::exclusive_scan(nullptr, tb, in, scan.as<uint64_t>(), (uint64_t)0, nb, rocprim::plus<uint64_t>(), stream));
-    VLG_HIP_TRY(temp.alloc(tb));
-    VLG_HIP_TRY(rocprim::exclusive_scan(temp.p, tb, in, scan.as<uint64_t>(), (uint64_t)0, nb, rocprim::plus<uint64_t>(), stream));
-    uint32_t grid = (uint32_t)std::min<uint64_t>((nb + 255) / 256, 8192);
-    hipLaunchKernelGGL(fill_counts_kernel, dim3(grid), dim3(256), 0, stream, blocks, scan.as<uint64_t>(), nb, d_tab);
+    VLG_HIP_TRY(with_scratch(temp, [&](void* t, size_t& tb) {
+        return rocprim::exclusive_scan(t, tb, in, scan.as<uint64_t>(), (uint64_t)0, nb, rocprim::plus<uint64_t>(), stream);
+    }));
+    hipLaunchKernelGGL(fill_counts_kernel, launch_grid(nb, 8192), dim3(256), 0, stream, blocks, scan.as<uint64_t>(), nb, d_tab);
     VLG_HIP_TRY(hipGetLastError());
     VLG_HIP_TRY(hipStreamSynchronize(stream));
     return VLG_OK;
@@ -289,44 +282,36 @@ extern "C" vlg_status vlg_index_from_parts(const vlg_index_parts* p, vlg_index**
     if (p->n > (1ull << 36)) return fail(VLG_E_UNSUPPORTED, "text longer than 2^36");
     if (p->n_samples != (p->n + p->sa_sample_dens - 1) / p->sa_sample_dens)
         return fail(VLG_E_INVALID, "n_samples must be ceil(n/dens)");
-    vlg_index* idx = new vlg_index();
-    vlg_status st = tree_from_nodes(p->nodes, p->n_nodes, p->bv_bits, p->char2comp, p->C, p->sigma, idx->tree);
-    if (st) { delete idx; return st; }
+    IndexPtr idx(new vlg_index());
+    if (vlg_status st = tree_from_nodes(p->nodes, p->n_nodes, p->bv_bits, p->char2comp, p->C, p->sigma, idx->tree)) return st;
     hipStream_t stream = nullptr;
-    st = alloc_blob(idx, p->n, p->sa_sample_dens, stream);
-    if (st) { vlg_index_destroy(idx); return st; }
-    auto run = [&]() -> vlg_status {
-        const BlobHeader& h = idx->hdr;
-        uint8_t* b = reinterpret_cast<uint8_t*>(idx->d_blob);
-        // samples
-        if (h.sample_bytes == 4) {
-            std::vector<uint32_t> s32(h.n_samples);
-            for (uint64_t i = 0; i < h.n_samples; ++i) s32[i] = (uint32_t)p->sa_samples[i];
-            VLG_HIP_TRY(hipMemcpy(b + h.off_samples, s32.data(), h.n_samples * 4, hipMemcpyHostToDevice));
-        } else {
-            VLG_HIP_TRY(hipMemcpy(b + h.off_samples, p->sa_samples, h.n_samples * 8, hipMemcpyHostToDevice));
-        }
-        if (h.n_blocks) {
-            InnerTable tab = make_inner_table(idx->tree);
-            DevBuf d_tab, d_src;
-            VLG_HIP_TRY(d_tab.alloc(sizeof tab));
-            VLG_HIP_TRY(hipMemcpy(d_tab.p, &tab, sizeof tab, hipMemcpyHostToDevice));
-            uint64_t words = (p->bv_bits + 63) / 64;
-            VLG_HIP_TRY(d_src.alloc(words * 8 + 8));
-            VLG_HIP_TRY(hipMemcpy(d_src.p, p->bv_words, words * 8, hipMemcpyHostToDevice));
-            Block* blocks = const_cast<Block*>(idx->view.blocks);
-            uint32_t grid = (uint32_t)std::min<uint64_t>((h.n_blocks * 8 + 255) / 256, 16384);
-            hipLaunchKernelGGL(repack_kernel, dim3(grid), dim3(256), 0, stream, d_src.as<uint64_t>(), words, blocks,
-                               h.n_blocks, d_tab.as<InnerTable>());
-            VLG_HIP_TRY(hipGetLastError());
-            if (vlg_status s2 = fill_block_counts(idx, d_tab.as<InnerTable>(), stream)) return s2;
-        }
-        VLG_HIP_TRY(hipDeviceSynchronize());
-        return VLG_OK;
-    };
-    st = run();
-    if (st) { vlg_index_destroy(idx); return st; }
-    *out = idx;
+    if (vlg_status st = alloc_blob(idx.get(), p->n, p->sa_sample_dens, stream)) return st;
+    const BlobHeader& h = idx->hdr;
+    uint8_t* b = reinterpret_cast<uint8_t*>(idx->d_blob);
+    // samples
+    if (h.sample_bytes == 4) {
+        std::vector<uint32_t> s32(h.n_samples);
+        for (uint64_t i = 0; i < h.n_samples; ++i) s32[i] = (uint32_t)p->sa_samples[i];
+        VLG_HIP_TRY(hipMemcpy(b + h.off_samples, s32.data(), h.n_samples * 4, hipMemcpyHostToDevice));
+    } else {
+        VLG_HIP_TRY(hipMemcpy(b + h.off_samples, p->sa_samples, h.n_samples * 8, hipMemcpyHostToDevice));
+    }
+    if (h.n_blocks) {
+        InnerTable tab = make_inner_table(idx->tree);
+        DevBuf d_tab, d_src;
+        VLG_HIP_TRY(d_tab.alloc(sizeof tab));
+        VLG_HIP_TRY(hipMemcpy(d_tab.p, &tab, sizeof tab, hipMemcpyHostToDevice));
+        uint64_t words = (p->bv_bits + 63) / 64;
+        VLG_HIP_TRY(d_src.alloc(words * 8 + 8));
+        VLG_HIP_TRY(hipMemcpy(d_src.p, p->bv_words, words * 8, hipMemcpyHostToDevice));
+        Block* blocks = const_cast<Block*>(idx->view.blocks);
+        hipLaunchKernelGGL(repack_kernel, launch_grid(h.n_blocks * 8), dim3(256), 0, stream, d_src.as<uint64_t>(), words, blocks,
+                           h.n_blocks, d_tab.as<InnerTable>());
+        VLG_HIP_TRY(hipGetLastError());
+        if (vlg_status s2 = fill_block_counts(idx.get(), d_tab.as<InnerTable>(), stream)) return s2;
+    }
+    VLG_HIP_TRY(hipDeviceSynchronize());
+    *out = idx.release();
     return VLG_OK;
 }
 
@@ -357,8 +342,7 @@ extern "C" vlg_status vlg_index_export_parts(const vlg_index* idx, vlg_index_par
         VLG_HIP_TRY(d_tab.alloc(sizeof tab));
         VLG_HIP_TRY(hipMemcpy(d_tab.p, &tab, sizeof tab, hipMemcpyHostToDevice));
         VLG_HIP_TRY(d_dst.alloc(words * 8));
-        uint32_t grid = (uint32_t)std::min<uint64_t>((words + 255) / 256, 16384);
-        hipLaunchKernelGGL(unpack_kernel, dim3(grid), dim3(256), 0, nullptr, idx->view.blocks, d_dst.as<uint64_t>(), words,
+        hipLaunchKernelGGL(unpack_kernel, launch_grid(words), dim3(256), 0, nullptr, idx->view.blocks, d_dst.as<uint64_t>(), words,
                            h.wt_bits, d_tab.as<InnerTable>());
         VLG_HIP_TRY(hipGetLastError());
         VLG_HIP_TRY(hipMemcpy(bv.data(), d_dst.p, words * 8, hipMemcpyDeviceToHost));
@@ -450,19 +434,19 @@ extern "C" vlg_status vlg_index_replicate(const vlg_index* src, int device, vlg_
     VLG_HIP_TRY(hipGetDevice(&cur));
     hipPointerAttribute_t at;
     VLG_HIP_TRY(hipPointerGetAttributes(&at, src->d_blob));
-    void* d = nullptr;
     vlg_index* idx = nullptr;
-    auto run = [&]() -> vlg_status {
+    auto run = [&]() -> vlg_status {                   // (on the other device; the caller's is restored whatever happens)
         VLG_HIP_TRY(hipSetDevice(device));
-        VLG_HIP_TRY(hipMalloc(&d, src->hdr.total_bytes));
-        VLG_HIP_TRY(hipMemcpyPeer(d, device, src->d_blob, at.device, src->hdr.total_bytes));
+        DevBuf d;
+        VLG_HIP_TRY(d.alloc(src->hdr.total_bytes));
+        VLG_HIP_TRY(hipMemcpyPeer(d.p, device, src->d_blob, at.device, src->hdr.total_bytes));
         VLG_HIP_TRY(hipDeviceSynchronize());
-        if (vlg_status st = vlg_index_attach_blob(d, src->hdr.total_bytes, &idx)) return st;
+        if (vlg_status st = vlg_index_attach_blob(d.p, src->hdr.total_bytes, &idx)) return st;
         idx->owns_blob = true;
+        d.take();
         return VLG_OK;
     };
     vlg_status st = run();
-    if (st && d && !idx) (void)hipFree(d);
     (void)hipSetDevice(cur);
     if (st) return st;
     *out = idx;
@@ -474,33 +458,31 @@ extern "C" vlg_status vlg_index_attach_blob(const void* d_blob, uint64_t bytes, 
     if (!d_blob || !out) return fail(VLG_E_INVALID, "null argument");
     *out = nullptr;
     if (bytes < sizeof(BlobHeader)) return fail(VLG_E_INVALID, "blob too small");
-    vlg_index* idx = new vlg_index();
-    auto run = [&]() -> vlg_status {
-        VLG_HIP_TRY(hipMemcpy(&idx->hdr, d_blob, sizeof(BlobHeader), hipMemcpyDeviceToHost));
-        if (idx->hdr.magic == kIntBlobMagic) return attach_int_blob(d_blob, bytes, idx);          // integer-alphabet index (int_index.hpp)
-        const BlobHeader& h = idx->hdr;
-        if (h.magic != kBlobMagic || h.total_bytes > bytes || h.n_nodes > kMaxNodes || h.sigma > 256)
-            return fail(VLG_E_INVALID, "not a VLG index blob");
-        idx->d_blob = const_cast<void*>(d_blob);
-        idx->owns_blob = false;
-        bind_view(idx);
-        // rebuild the host-side tree copy from the tables stored in the blob
-        const uint8_t* b = reinterpret_cast<const uint8_t*>(d_blob);
-        std::vector<uint64_t> Cc(h.sigma + 1, 0);
-        std::vector<vlg_wt_node> nodes(h.n_nodes ? h.n_nodes : 1);
-        uint8_t c2c[256];
-        VLG_HIP_TRY(hipMemcpy(Cc.data(), b + h.off_C, (h.sigma + 1) * 8, hipMemcpyDeviceToHost));
-        VLG_HIP_TRY(hipMemcpy(c2c, b + h.off_c2c, 256, hipMemcpyDeviceToHost));
-        if (h.n_nodes) VLG_HIP_TRY(hipMemcpy(nodes.data(), b + h.off_refnodes, h.n_nodes * sizeof(vlg_wt_node), hipMemcpyDeviceToHost));
-        HostTree t2;
-        vlg_status st = tree_from_nodes(nodes.data(), h.n_nodes, h.wt_bits, c2c, Cc.data(), h.sigma, t2);
-        if (st) return st;
-        idx->tree = t2;
+    IndexPtr idx(new vlg_index());                   // (owns no blob until the caller says so: a failure frees the host object alone)
+    VLG_HIP_TRY(hipMemcpy(&idx->hdr, d_blob, sizeof(BlobHeader), hipMemcpyDeviceToHost));
+    if (idx->hdr.magic == kIntBlobMagic) {            // integer-alphabet index (int_index.hpp)
+        if (vlg_status st = attach_int_blob(d_blob, bytes, idx.get())) return st;
+        *out = idx.release();
         return VLG_OK;
-    };
-    vlg_status st = run();
-    if (st) { delete idx; return st; }
-    *out = idx;
+    }
+    const BlobHeader& h = idx->hdr;
+    if (h.magic != kBlobMagic || h.total_bytes > bytes || h.n_nodes > kMaxNodes || h.sigma > 256)
+        return fail(VLG_E_INVALID, "not a VLG index blob");
+    idx->d_blob = const_cast<void*>(d_blob);
+    idx->owns_blob = false;
+    bind_view(idx.get());
+    // rebuild the host-side tree copy from the tables stored in the blob
+    const uint8_t* b = reinterpret_cast<const uint8_t*>(d_blob);
+    std::vector<uint64_t> Cc(h.sigma + 1, 0);
+    std::vector<vlg_wt_node> nodes(h.n_nodes ? h.n_nodes : 1);
+    uint8_t c2c[256];
+    VLG_HIP_TRY(hipMemcpy(Cc.data(), b + h.off_C, (h.sigma + 1) * 8, hipMemcpyDeviceToHost));
+    VLG_HIP_TRY(hipMemcpy(c2c, b + h.off_c2c, 256, hipMemcpyDeviceToHost));
+    if (h.n_nodes) VLG_HIP_TRY(hipMemcpy(nodes.data(), b + h.off_refnodes, h.n_nodes * sizeof(vlg_wt_node), hipMemcpyDeviceToHost));
+    HostTree t2;
+    if (vlg_status st = tree_from_nodes(nodes.data(), h.n_nodes, h.wt_bits, c2c, Cc.data(), h.sigma, t2)) return st;
+    idx->tree = t2;
+    *out = idx.release();
     return VLG_OK;
 }
 
@@ -613,20 +595,19 @@ vlg_status rrr_encode(const Block* blocks, const RrrTable& tab, uint64_t n_sb, h
     VLG_HIP_TRY(d_code.alloc(64 * 64 * 8));
     VLG_HIP_TRY(hipMemcpy(d_tab.p, &tab, sizeof tab, hipMemcpyHostToDevice));
     VLG_HIP_TRY(hipMemcpy(d_code.p, code.data(), 64 * 64 * 8, hipMemcpyHostToDevice));
-    const uint32_t grid = (uint32_t)std::min<uint64_t>((n_sb + 255) / 256, 4096);
+    const dim3 grid = launch_grid(n_sb, 4096);
     if (n_sb) {
         VLG_HIP_TRY(d_ones.alloc((n_sb + 1) * 8));
         VLG_HIP_TRY(d_words.alloc((n_sb + 1) * 8));
-        hipLaunchKernelGGL(rrr_encode_kernel, dim3(grid), dim3(256), 0, stream, blocks, d_tab.as<RrrTable>(), n_sb, d_code.as<RrrTables>(),
+        hipLaunchKernelGGL(rrr_encode_kernel, grid, dim3(256), 0, stream, blocks, d_tab.as<RrrTable>(), n_sb, d_code.as<RrrTables>(),
                            d_ones.as<uint64_t>(), d_words.as<uint64_t>(), nullptr, nullptr, nullptr, nullptr);
         VLG_HIP_TRY(hipGetLastError());
         uint64_t last_words = 0;
         VLG_HIP_TRY(hipMemcpyAsync(&last_words, d_words.as<uint64_t>() + (n_sb - 1), 8, hipMemcpyDeviceToHost, stream));
-        size_t tb = 0;
-        VLG_HIP_TRY(rocprim::exclusive_scan(nullptr, tb, d_ones.as<uint64_t>(), d_ones.as<uint64_t>(), (uint64_t)0, n_sb, rocprim::plus<uint64_t>(), stream));
-        VLG_HIP_TRY(d_tmp.alloc(tb));
-        VLG_HIP_TRY(rocprim::exclusive_scan(d_tmp.p, tb, d_ones.as<uint64_t>(), d_ones.as<uint64_t>(), (uint64_t)0, n_sb, rocprim::plus<uint64_t>(), stream));
-        VLG_HIP_TRY(rocprim::exclusive_scan(d_tmp.p, tb, d_words.as<uint64_t>(), d_words.as<uint64_t>(), (uint64_t)0, n_sb, rocprim::plus<uint64_t>(), stream));
+        for (uint64_t* a : {d_ones.as<uint64_t>(), d_words.as<uint64_t>()})
+            VLG_HIP_TRY(with_scratch(d_tmp, [&](void* t, size_t& tb) {
+                return rocprim::exclusive_scan(t, tb, a, a, (uint64_t)0, n_sb, rocprim::plus<uint64_t>(), stream);
+            }));
         uint64_t last_off = 0;
         VLG_HIP_TRY(hipMemcpyAsync(&last_off, d_words.as<uint64_t>() + (n_sb - 1), 8, hipMemcpyDeviceToHost, stream));
         VLG_HIP_TRY(hipStreamSynchronize(stream));
@@ -639,11 +620,22 @@ vlg_status rrr_encode(const Block* blocks, const RrrTable& tab, uint64_t n_sb, h
     VLG_HIP_TRY(hipMemsetAsync(w.stream, 0, (total_words + 2) * 8, stream));
     VLG_HIP_TRY(hipMemsetAsync(w.hdr, 0, std::max<uint64_t>(n_sb, 1) * 32, stream));
     if (n_sb) {
-        hipLaunchKernelGGL(rrr_encode_kernel, dim3(grid), dim3(256), 0, stream, blocks, d_tab.as<RrrTable>(), n_sb, d_code.as<RrrTables>(),
+        hipLaunchKernelGGL(rrr_encode_kernel, grid, dim3(256), 0, stream, blocks, d_tab.as<RrrTable>(), n_sb, d_code.as<RrrTables>(),
                            nullptr, nullptr, d_ones.as<uint64_t>(), d_words.as<uint64_t>(), w.hdr, w.stream);
         VLG_HIP_TRY(hipGetLastError());
     }
     VLG_HIP_TRY(hipStreamSynchronize(stream));
+    return VLG_OK;
+}
+
+// a finished integer blob becomes an index that owns it
+vlg_status adopt_int_blob(DevBuf& d_blob, uint64_t bytes, vlg_index** out)
+{
+    IndexPtr idx(new vlg_index());
+    if (vlg_status st = attach_int_blob(d_blob.p, bytes, idx.get())) return st;
+    idx->owns_blob = true;
+    d_blob.take();
+    *out = idx.release();
     return VLG_OK;
 }
 
@@ -669,13 +661,13 @@ vlg_status compress_int(const vlg_index* src, vlg_index** out)
         tab.rbase[l] = (uint32_t)(l * h.n_sb);
         tab.size[l] = sh.n;
     }
-    void* d_blob = nullptr;
+    DevBuf d_blob;
     const uint8_t* sb = reinterpret_cast<const uint8_t*>(src->d_blob);
     vlg_status st = rrr_encode(src->iview.blocks, tab, n_sb, nullptr, [&](uint64_t total_words, RrrTarget& w) -> vlg_status {
         h.rrr_words = total_words;
         layout_int_blob(h);
-        VLG_HIP_TRY(hipMalloc(&d_blob, h.total_bytes));
-        uint8_t* b = reinterpret_cast<uint8_t*>(d_blob);
+        VLG_HIP_TRY(d_blob.alloc(h.total_bytes));
+        uint8_t* b = d_blob.as<uint8_t>();
         VLG_HIP_TRY(hipMemset(b, 0, h.off_levels));
         VLG_HIP_TRY(hipMemcpy(b, &h, sizeof h, hipMemcpyHostToDevice));
         VLG_HIP_TRY(hipMemcpy(b + h.off_Z, sb + sh.off_Z, kMaxIntLevels * 8, hipMemcpyDeviceToDevice));
@@ -688,13 +680,8 @@ vlg_status compress_int(const vlg_index* src, vlg_index** out)
         w.tables = b + h.off_binom;
         return VLG_OK;
     });
-    if (st) { if (d_blob) (void)hipFree(d_blob); return st; }
-    vlg_index* idx = new vlg_index();
-    st = attach_int_blob(d_blob, h.total_bytes, idx);
-    if (st) { (void)hipFree(d_blob); delete idx; return st; }
-    idx->owns_blob = true;
-    *out = idx;
-    return VLG_OK;
+    if (st) return st;
+    return adopt_int_blob(d_blob, h.total_bytes, out);
 }
 
 }  // namespace
@@ -709,7 +696,7 @@ extern "C" vlg_status vlg_index_compress(const vlg_index* src, int kind, vlg_ind
     if (src->is_int) return compress_int(src, out);
     if (src->hdr.bv_kind != kBvPlain) return fail(VLG_E_INVALID, "source index must use plain bit-vectors");
     if (src->hdr.sampling != kSamplingSaOrder) return fail(VLG_E_INVALID, "compress the SA-order index first, then resample it (vlg_index_resample)");
-    vlg_index* idx = new vlg_index();
+    IndexPtr idx(new vlg_index());
     idx->tree = src->tree;
     HostTree& t = idx->tree;
     RrrTable tab;
@@ -724,10 +711,10 @@ extern "C" vlg_status vlg_index_compress(const vlg_index* src, int kind, vlg_ind
             t.dnodes[v].base = (uint32_t)n_sb;
             n_sb += t.node_size[v] / kRrrSuperBits + 1;
         }
-    if (n_sb > 0xFFFFFFF0ull) { delete idx; return fail(VLG_E_UNSUPPORTED, "too many rrr super-blocks"); }
+    if (n_sb > 0xFFFFFFF0ull) return fail(VLG_E_UNSUPPORTED, "too many rrr super-blocks");
     hipStream_t stream = nullptr;
     vlg_status st = rrr_encode(src->view.blocks, tab, n_sb, stream, [&](uint64_t total_words, RrrTarget& w) -> vlg_status {
-        if (vlg_status s2 = alloc_blob(idx, src->hdr.n, src->hdr.dens, stream, std::max<uint64_t>(n_sb, 1), total_words)) return s2;
+        if (vlg_status s2 = alloc_blob(idx.get(), src->hdr.n, src->hdr.dens, stream, std::max<uint64_t>(n_sb, 1), total_words)) return s2;
         const BlobHeader& h = idx->hdr;
         uint8_t* b = reinterpret_cast<uint8_t*>(idx->d_blob);
         const uint8_t* sb = reinterpret_cast<const uint8_t*>(src->d_blob);
@@ -737,8 +724,8 @@ extern "C" vlg_status vlg_index_compress(const vlg_index* src, int kind, vlg_ind
         w.tables = b + h.off_binom;
         return VLG_OK;
     });
-    if (st) { vlg_index_destroy(idx); return st; }
-    *out = idx;
+    if (st) return st;
+    *out = idx.release();
     return VLG_OK;
 }
 
@@ -847,14 +834,39 @@ __global__ void marked_words_kernel(const Block* __restrict__ blocks, uint64_t n
 }  // namespace
 
 namespace {
+// The samples of a sampling strategy from the whole suffix array d_sa (n entries), for both kinds of index: SA order keeps every dens-th
+// entry; text order marks the SA indices whose value is a multiple of dens (the marks, their scan, their counts) and keeps value / dens of
+// those in ascending index.  sa_t: the width of the suffix array and of the samples.
+template <typename sa_t>
+vlg_status write_samples(const sa_t* d_sa, uint64_t n, uint32_t dens, int sampling, sa_t* samples, Block* marked, hipStream_t stream)
+{
+    const uint64_t n_samples = (n + dens - 1) / dens;
+    DevBuf d_pops, d_tmp;
+    if (sampling == VLG_SAMPLING_SA_ORDER) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(sa_order_samples_kernel<sa_t>), launch_grid(n_samples, 8192), dim3(256), 0, stream, d_sa, n_samples, dens, samples);
+    } else {
+        const uint64_t nb = n / kBlockBits + 1;
+        VLG_HIP_TRY(d_pops.alloc((nb + 1) * 4));
+        uint32_t* pops = d_pops.as<uint32_t>();
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(marked_pack_kernel<sa_t>), launch_grid(nb, 8192), dim3(256), 0, stream, d_sa, n, dens, marked, nb, pops);
+        VLG_HIP_TRY(with_scratch(d_tmp, [&](void* t, size_t& tb) { return rocprim::exclusive_scan(t, tb, pops, pops, 0u, nb, rocprim::plus<uint32_t>(), stream); }));
+        hipLaunchKernelGGL(marked_counts_kernel, launch_grid(nb, 8192), dim3(256), 0, stream, marked, pops, nb);
+        VLG_HIP_TRY(hipMemsetAsync(samples, 0, n_samples * sizeof(sa_t), stream));
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(text_order_samples_kernel<sa_t>), launch_grid(n), dim3(256), 0, stream, d_sa, n, dens, marked, samples);
+    }
+    VLG_HIP_TRY(hipGetLastError());
+    VLG_HIP_TRY(hipStreamSynchronize(stream));
+    return VLG_OK;
+}
+
 // sa_t = the width the source keeps its samples in (and the new index keeps its own in): uint32_t for n <= 2^32, uint64_t for wide SA indices
 template <typename sa_t>
 vlg_status resample_run(const vlg_index* src, int sampling, uint32_t dens, vlg_index* idx, hipStream_t stream)
 {
     const uint64_t n = src->hdr.n;
-    DevBuf d_sa, d_pops, d_tmp;
+    DevBuf d_sa, d_blob;
     VLG_HIP_TRY(d_sa.alloc(n * sizeof(sa_t)));
-    const dim3 grid((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((src->view.n_samples + 255) / 256, 8192)));
+    const dim3 grid = launch_grid(src->view.n_samples, 8192);
     if (src->view.bv_kind == kBvRrr63) hipLaunchKernelGGL(HIP_KERNEL_NAME(sa_expand_kernel<RrrBV, sa_t>), grid, dim3(256), 0, stream, src->view, d_sa.as<sa_t>());
     else hipLaunchKernelGGL(HIP_KERNEL_NAME(sa_expand_kernel<PlainBV, sa_t>), grid, dim3(256), 0, stream, src->view, d_sa.as<sa_t>());
     VLG_HIP_TRY(hipGetLastError());
@@ -864,7 +876,8 @@ vlg_status resample_run(const vlg_index* src, int sampling, uint32_t dens, vlg_i
     h.sampling = (uint32_t)sampling;
     h.n_samples = (n + dens - 1) / dens;
     layout_blob(h);
-    VLG_HIP_TRY(hipMalloc(&idx->d_blob, h.total_bytes));
+    VLG_HIP_TRY(d_blob.alloc(h.total_bytes));
+    idx->d_blob = d_blob.take();
     idx->owns_blob = true;
     uint8_t* b = reinterpret_cast<uint8_t*>(idx->d_blob);
     const uint8_t* sb = reinterpret_cast<const uint8_t*>(src->d_blob);
@@ -877,34 +890,16 @@ vlg_status resample_run(const vlg_index* src, int sampling, uint32_t dens, vlg_i
         if (old[i].bytes != sec[i].bytes) return fail(VLG_E_INTERNAL, "blob sections changed size");
         VLG_HIP_TRY(hipMemcpyAsync(b + h.*(sec[i].off), sb + src->hdr.*(old[i].off), sec[i].bytes, hipMemcpyDeviceToDevice, stream));
     }
-    sa_t* samples = reinterpret_cast<sa_t*>(b + h.off_samples);
-    if (sampling == VLG_SAMPLING_SA_ORDER) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(sa_order_samples_kernel<sa_t>), dim3((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((h.n_samples + 255) / 256, 8192))), dim3(256), 0, stream,
-                           d_sa.as<sa_t>(), h.n_samples, dens, samples);
-    } else {
-        const uint64_t nb = n / kBlockBits + 1;
-        if (h.n_samples > 0xFFFFFFF0ull) return fail(VLG_E_UNSUPPORTED, "text-order sampling: more than 2^32 marked indices (choose a larger density)");
-        Block* mk = reinterpret_cast<Block*>(b + h.off_marked);
-        VLG_HIP_TRY(d_pops.alloc((nb + 1) * 4));
-        const dim3 gb((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((nb + 255) / 256, 8192)));
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(marked_pack_kernel<sa_t>), gb, dim3(256), 0, stream, d_sa.as<sa_t>(), n, dens, mk, nb, d_pops.as<uint32_t>());
-        size_t tb = 0;
-        VLG_HIP_TRY(rocprim::exclusive_scan(nullptr, tb, d_pops.as<uint32_t>(), d_pops.as<uint32_t>(), 0u, nb, rocprim::plus<uint32_t>(), stream));
-        VLG_HIP_TRY(d_tmp.alloc(tb + 16));
-        VLG_HIP_TRY(rocprim::exclusive_scan(d_tmp.p, tb, d_pops.as<uint32_t>(), d_pops.as<uint32_t>(), 0u, nb, rocprim::plus<uint32_t>(), stream));
-        hipLaunchKernelGGL(marked_counts_kernel, gb, dim3(256), 0, stream, mk, d_pops.as<uint32_t>(), nb);
-        VLG_HIP_TRY(hipMemsetAsync(samples, 0, h.n_samples * sizeof(sa_t), stream));
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(text_order_samples_kernel<sa_t>), dim3((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, 16384))), dim3(256), 0, stream,
-                           d_sa.as<sa_t>(), n, dens, mk, samples);
-    }
-    VLG_HIP_TRY(hipGetLastError());
-    VLG_HIP_TRY(hipStreamSynchronize(stream));
+    if (sampling == VLG_SAMPLING_TEXT_ORDER && h.n_samples > 0xFFFFFFF0ull)
+        return fail(VLG_E_UNSUPPORTED, "text-order sampling: more than 2^32 marked indices (choose a larger density)");
+    if (vlg_status st = write_samples(d_sa.as<sa_t>(), n, dens, sampling, reinterpret_cast<sa_t*>(b + h.off_samples), reinterpret_cast<Block*>(b + h.off_marked), stream))
+        return st;
     bind_view(idx);
     return VLG_OK;
 }
 
 // The integer index (int_index.hpp): the suffix array from the SA-order samples by LF walks on the wavelet matrix (int_sa_expand_kernel),
-// then the samples -- and the marks -- of the new strategy by the kernels above.  Everything in front of the samples (levels or rrr
+// then the samples -- and the marks -- of the new strategy as above.  Everything in front of the samples (levels or rrr
 // streams, Z, D, C, comp2char) has the same size and place in both images and is copied as it is.
 vlg_status resample_int(const vlg_index* src, int sampling, uint32_t dens, vlg_index** out)
 {
@@ -918,48 +913,18 @@ vlg_status resample_int(const vlg_index* src, int sampling, uint32_t dens, vlg_i
     h.n_samples = (n + dens - 1) / dens;
     layout_int_blob(h);
     if (h.off_samples != sh.off_samples) return fail(VLG_E_INTERNAL, "integer index: sections in front of the samples moved");
-    DevBuf d_sa, d_pops, d_tmp;
+    DevBuf d_sa, d_blob;
     VLG_HIP_TRY(d_sa.alloc(n * 4));
     if (vlg_status s = launch_int_sa_expand(src->iview, d_sa.as<uint32_t>(), stream)) return s;
-    void* d_blob = nullptr;
-    auto run = [&]() -> vlg_status {
-        VLG_HIP_TRY(hipMalloc(&d_blob, h.total_bytes));
-        uint8_t* b = reinterpret_cast<uint8_t*>(d_blob);
-        const uint8_t* sb = reinterpret_cast<const uint8_t*>(src->d_blob);
-        VLG_HIP_TRY(hipMemsetAsync(b, 0, h.off_levels, stream));
-        VLG_HIP_TRY(hipMemcpyAsync(b, &h, sizeof h, hipMemcpyHostToDevice, stream));
-        VLG_HIP_TRY(hipMemcpyAsync(b + h.off_levels, sb + sh.off_levels, sh.off_samples - sh.off_levels, hipMemcpyDeviceToDevice, stream));
-        uint32_t* samples = reinterpret_cast<uint32_t*>(b + h.off_samples);
-        if (sampling == VLG_SAMPLING_SA_ORDER) {
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(sa_order_samples_kernel<uint32_t>), dim3((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((h.n_samples + 255) / 256, 8192))),
-                               dim3(256), 0, stream, d_sa.as<uint32_t>(), h.n_samples, dens, samples);
-        } else {
-            const uint64_t nb = n / kBlockBits + 1;
-            Block* mk = reinterpret_cast<Block*>(b + h.off_marked);
-            VLG_HIP_TRY(d_pops.alloc((nb + 1) * 4));
-            const dim3 gb((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((nb + 255) / 256, 8192)));
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(marked_pack_kernel<uint32_t>), gb, dim3(256), 0, stream, d_sa.as<uint32_t>(), n, dens, mk, nb, d_pops.as<uint32_t>());
-            size_t tb = 0;
-            VLG_HIP_TRY(rocprim::exclusive_scan(nullptr, tb, d_pops.as<uint32_t>(), d_pops.as<uint32_t>(), 0u, nb, rocprim::plus<uint32_t>(), stream));
-            VLG_HIP_TRY(d_tmp.alloc(tb + 16));
-            VLG_HIP_TRY(rocprim::exclusive_scan(d_tmp.p, tb, d_pops.as<uint32_t>(), d_pops.as<uint32_t>(), 0u, nb, rocprim::plus<uint32_t>(), stream));
-            hipLaunchKernelGGL(marked_counts_kernel, gb, dim3(256), 0, stream, mk, d_pops.as<uint32_t>(), nb);
-            VLG_HIP_TRY(hipMemsetAsync(samples, 0, h.n_samples * 4, stream));
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(text_order_samples_kernel<uint32_t>), dim3((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, 16384))), dim3(256), 0,
-                               stream, d_sa.as<uint32_t>(), n, dens, mk, samples);
-        }
-        VLG_HIP_TRY(hipGetLastError());
-        VLG_HIP_TRY(hipStreamSynchronize(stream));
-        return VLG_OK;
-    };
-    vlg_status st = run();
-    if (st) { if (d_blob) (void)hipFree(d_blob); return st; }
-    vlg_index* idx = new vlg_index();
-    st = attach_int_blob(d_blob, h.total_bytes, idx);
-    if (st) { (void)hipFree(d_blob); delete idx; return st; }
-    idx->owns_blob = true;
-    *out = idx;
-    return VLG_OK;
+    VLG_HIP_TRY(d_blob.alloc(h.total_bytes));
+    uint8_t* b = d_blob.as<uint8_t>();
+    const uint8_t* sb = reinterpret_cast<const uint8_t*>(src->d_blob);
+    VLG_HIP_TRY(hipMemsetAsync(b, 0, h.off_levels, stream));
+    VLG_HIP_TRY(hipMemcpyAsync(b, &h, sizeof h, hipMemcpyHostToDevice, stream));
+    VLG_HIP_TRY(hipMemcpyAsync(b + h.off_levels, sb + sh.off_levels, sh.off_samples - sh.off_levels, hipMemcpyDeviceToDevice, stream));
+    if (vlg_status s = write_samples(d_sa.as<uint32_t>(), n, dens, sampling, reinterpret_cast<uint32_t*>(b + h.off_samples), reinterpret_cast<Block*>(b + h.off_marked), stream))
+        return s;
+    return adopt_int_blob(d_blob, h.total_bytes, out);
 }
 }  // namespace
 
@@ -973,13 +938,13 @@ extern "C" vlg_status vlg_index_resample(const vlg_index* src, int sampling, uin
     if (src->hdr.sampling != kSamplingSaOrder) return fail(VLG_E_INVALID, "the source index must be sampled in SA order");
     if (src->is_int) return resample_int(src, sampling, dens, out);
     if (src->hdr.sample_bytes != 4 && src->hdr.sample_bytes != 8) return fail(VLG_E_INTERNAL, "unknown sample width");
-    vlg_index* idx = new vlg_index();
+    IndexPtr idx(new vlg_index());
     idx->tree = src->tree;
     hipStream_t stream = nullptr;
     // (the new index keeps the source's sample width: 8 bytes when SA indices are wide -- n > 2^32, or VLG_FORCE_POS64)
-    const vlg_status st = src->hdr.sample_bytes == 8 ? resample_run<uint64_t>(src, sampling, dens, idx, stream) : resample_run<uint32_t>(src, sampling, dens, idx, stream);
-    if (st) { vlg_index_destroy(idx); return st; }
-    *out = idx;
+    const vlg_status st = src->hdr.sample_bytes == 8 ? resample_run<uint64_t>(src, sampling, dens, idx.get(), stream) : resample_run<uint32_t>(src, sampling, dens, idx.get(), stream);
+    if (st) return st;
+    *out = idx.release();
     return VLG_OK;
 }
 
@@ -990,7 +955,7 @@ extern "C" vlg_status vlg_index_export_marked(const vlg_index* idx, uint64_t* h_
     const uint64_t n = idx->hdr.n, nw = (n + 63) / 64;
     DevBuf d;
     VLG_HIP_TRY(d.alloc(nw * 8));
-    hipLaunchKernelGGL(marked_words_kernel, dim3((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((nw + 255) / 256, 8192))), dim3(256), 0, nullptr,
+    hipLaunchKernelGGL(marked_words_kernel, launch_grid(nw, 8192), dim3(256), 0, nullptr,
                        idx->is_int ? idx->iview.marked : idx->view.marked, n,
                        d.as<uint64_t>(), nw);
     VLG_HIP_TRY(hipGetLastError());
@@ -1140,21 +1105,11 @@ __global__ void wt_emit_kernel(const uint8_t* __restrict__ syms, Block* __restri
 }
 
 template <class K, class V>
-vlg_status sort_pairs(DevBuf& temp, size_t& temp_cap, K* kin, K* kout, V* vin, V* vout, uint64_t n, unsigned b0, unsigned b1,
-                      hipStream_t stream)
+vlg_status sort_pairs(DevBuf& temp, K* kin, K* kout, V* vin, V* vout, uint64_t n, unsigned b0, unsigned b1, hipStream_t stream)
 {
-    size_t tb = 0;
-    VLG_HIP_TRY(rocprim::radix_sort_pairs(nullptr, tb, kin, kout, vin, vout, n, b0, b1, stream));
-    if (tb > temp_cap) {
-        if (temp.p) { (void)hipFree(temp.p); temp.p = nullptr; }
-        VLG_HIP_TRY(temp.alloc(tb));
-        temp_cap = tb;
-    }
-    VLG_HIP_TRY(rocprim::radix_sort_pairs(temp.p, tb, kin, kout, vin, vout, n, b0, b1, stream));
+    VLG_HIP_TRY(with_scratch(temp, [&](void* t, size_t& tb) { return rocprim::radix_sort_pairs(t, tb, kin, kout, vin, vout, n, b0, b1, stream); }));
     return VLG_OK;
 }
-
-inline uint32_t grid_for(uint64_t n) { return (uint32_t)std::min<uint64_t>((n + 255) / 256, 16384); }
 
 __global__ void sa_export_kernel(const uint32_t* __restrict__ sa, uint64_t n_text, uint32_t* __restrict__ out)
 {
@@ -1171,162 +1126,155 @@ vlg_status build_on_device(const uint8_t* d_text, uint64_t n_text, uint32_t dens
     // their ids and ranks fit 32 bits for texts up to 2^32 bytes (BASELINE config 4).
     const uint64_t ns = n_text;
     if (n_text > 0x100000000ull) return fail(VLG_E_UNSUPPORTED, "device builder handles texts of up to 2^32 bytes");
-    vlg_index* idx = new vlg_index();
-    auto run = [&]() -> vlg_status {
-        DevBuf keys_a, keys_b, sa_a, sa_b, rank_of, head, temp, counter, bwt;
-        size_t temp_cap = 0;
-        VLG_HIP_TRY(keys_a.alloc(ns * 8));
-        VLG_HIP_TRY(keys_b.alloc(ns * 8));
-        VLG_HIP_TRY(sa_a.alloc(ns * 4));
-        VLG_HIP_TRY(sa_b.alloc(ns * 4));
-        VLG_HIP_TRY(rank_of.alloc(ns * 4));
-        VLG_HIP_TRY(head.alloc(ns * 4));
-        VLG_HIP_TRY(counter.alloc(8 + 256 * 8));
-        unsigned long long* d_groups = counter.as<unsigned long long>();
-        unsigned long long* d_hist = d_groups + 1;
-        const uint32_t g = grid_for(n);
-        {   // a zero byte in the text is a std::logic_error in the reference (construct.hpp:36-45)
+    IndexPtr idx(new vlg_index());
+    DevBuf keys_a, keys_b, sa_a, sa_b, rank_of, head, temp, counter, bwt;
+    VLG_HIP_TRY(keys_a.alloc(ns * 8));
+    VLG_HIP_TRY(keys_b.alloc(ns * 8));
+    VLG_HIP_TRY(sa_a.alloc(ns * 4));
+    VLG_HIP_TRY(sa_b.alloc(ns * 4));
+    VLG_HIP_TRY(rank_of.alloc(ns * 4));
+    VLG_HIP_TRY(head.alloc(ns * 4));
+    VLG_HIP_TRY(counter.alloc(8 + 256 * 8));
+    unsigned long long* d_groups = counter.as<unsigned long long>();
+    unsigned long long* d_hist = d_groups + 1;
+    const dim3 g = launch_grid(n);
+    {   // a zero byte in the text is a std::logic_error in the reference (construct.hpp:36-45)
+        VLG_HIP_TRY(hipMemsetAsync(d_groups, 0, 8, stream));
+        hipLaunchKernelGGL(count_zero_kernel, launch_grid(n, 4096), dim3(256), 0, stream, d_text, n_text, d_groups);
+        unsigned long long zeros = 0;
+        VLG_HIP_TRY(hipMemcpyAsync(&zeros, d_groups, 8, hipMemcpyDeviceToHost, stream));
+        VLG_HIP_TRY(hipStreamSynchronize(stream));
+        if (zeros) return fail(VLG_E_ZERO_BYTE, "text contains a zero byte (sdsl::construct throws std::logic_error)");
+    }
+    // --- suffix array by prefix doubling (8 characters first, then h = 8, 16, ...) ------------
+    uint32_t* sa_cur = sa_b.as<uint32_t>();
+    if (ns) {
+        hipLaunchKernelGGL(sa_init_keys, g, dim3(256), 0, stream, d_text, ns, keys_a.as<uint64_t>(), sa_a.as<uint32_t>());
+        VLG_HIP_TRY(hipGetLastError());
+        if (vlg_status st = sort_pairs(temp, keys_a.as<uint64_t>(), keys_b.as<uint64_t>(), sa_a.as<uint32_t>(),
+                                       sa_b.as<uint32_t>(), ns, 0, 64, stream)) return st;
+        uint64_t* keys_sorted = keys_b.as<uint64_t>();
+        uint64_t* keys_other = keys_a.as<uint64_t>();
+        uint32_t* sa_other = sa_a.as<uint32_t>();
+        for (uint64_t h = 8;; h <<= 1) {
             VLG_HIP_TRY(hipMemsetAsync(d_groups, 0, 8, stream));
-            hipLaunchKernelGGL(count_zero_kernel, dim3(std::min<uint32_t>(g, 4096)), dim3(256), 0, stream, d_text, n_text, d_groups);
-            unsigned long long zeros = 0;
-            VLG_HIP_TRY(hipMemcpyAsync(&zeros, d_groups, 8, hipMemcpyDeviceToHost, stream));
-            VLG_HIP_TRY(hipStreamSynchronize(stream));
-            if (zeros) return fail(VLG_E_ZERO_BYTE, "text contains a zero byte (sdsl::construct throws std::logic_error)");
-        }
-        // --- suffix array by prefix doubling (8 characters first, then h = 8, 16, ...) ------------
-        uint32_t* sa_cur = sa_b.as<uint32_t>();
-        if (ns) {
-            hipLaunchKernelGGL(sa_init_keys, dim3(g), dim3(256), 0, stream, d_text, ns, keys_a.as<uint64_t>(), sa_a.as<uint32_t>());
+            hipLaunchKernelGGL(sa_group_heads, g, dim3(256), 0, stream, keys_sorted, ns, head.as<uint32_t>(), d_groups);
             VLG_HIP_TRY(hipGetLastError());
-            if (vlg_status st = sort_pairs(temp, temp_cap, keys_a.as<uint64_t>(), keys_b.as<uint64_t>(), sa_a.as<uint32_t>(),
-                                           sa_b.as<uint32_t>(), ns, 0, 64, stream)) return st;
-            uint64_t* keys_sorted = keys_b.as<uint64_t>();
-            uint64_t* keys_other = keys_a.as<uint64_t>();
-            uint32_t* sa_other = sa_a.as<uint32_t>();
-            for (uint64_t h = 8;; h <<= 1) {
-                VLG_HIP_TRY(hipMemsetAsync(d_groups, 0, 8, stream));
-                hipLaunchKernelGGL(sa_group_heads, dim3(g), dim3(256), 0, stream, keys_sorted, ns, head.as<uint32_t>(), d_groups);
-                VLG_HIP_TRY(hipGetLastError());
-                unsigned long long groups = 0;
-                VLG_HIP_TRY(hipMemcpyAsync(&groups, d_groups, 8, hipMemcpyDeviceToHost, stream));
-                VLG_HIP_TRY(hipStreamSynchronize(stream));
-                if (groups == ns) break;
-                if (h > 2 * n) return fail(VLG_E_INTERNAL, "suffix sort did not converge");
-                size_t tb = 0;
-                VLG_HIP_TRY(rocprim::inclusive_scan(nullptr, tb, head.as<uint32_t>(), head.as<uint32_t>(), ns, rocprim::plus<uint32_t>(), stream));
-                if (tb > temp_cap) { if (temp.p) { (void)hipFree(temp.p); temp.p = nullptr; } VLG_HIP_TRY(temp.alloc(tb)); temp_cap = tb; }
-                VLG_HIP_TRY(rocprim::inclusive_scan(temp.p, tb, head.as<uint32_t>(), head.as<uint32_t>(), ns, rocprim::plus<uint32_t>(), stream));
-                hipLaunchKernelGGL(sa_scatter_rank, dim3(g), dim3(256), 0, stream, sa_cur, head.as<uint32_t>(), ns, rank_of.as<uint32_t>());
-                hipLaunchKernelGGL(sa_next_keys, dim3(g), dim3(256), 0, stream, sa_cur, rank_of.as<uint32_t>(), ns, h, keys_other);
-                VLG_HIP_TRY(hipGetLastError());
-                if (vlg_status st = sort_pairs(temp, temp_cap, keys_other, keys_sorted, sa_cur, sa_other, ns, 0, 64, stream)) return st;
-                std::swap(sa_cur, sa_other);                   // keys_sorted now holds the sorted keys again
-            }
-        }
-        if (d_sa_out) {
-            hipLaunchKernelGGL(sa_export_kernel, dim3(g), dim3(256), 0, stream, sa_cur, n_text, d_sa_out);
-            VLG_HIP_TRY(hipGetLastError());
+            unsigned long long groups = 0;
+            VLG_HIP_TRY(hipMemcpyAsync(&groups, d_groups, 8, hipMemcpyDeviceToHost, stream));
             VLG_HIP_TRY(hipStreamSynchronize(stream));
+            if (groups == ns) break;
+            if (h > 2 * n) return fail(VLG_E_INTERNAL, "suffix sort did not converge");
+            VLG_HIP_TRY(with_scratch(temp, [&](void* t, size_t& tb) {
+                return rocprim::inclusive_scan(t, tb, head.as<uint32_t>(), head.as<uint32_t>(), ns, rocprim::plus<uint32_t>(), stream);
+            }));
+            hipLaunchKernelGGL(sa_scatter_rank, g, dim3(256), 0, stream, sa_cur, head.as<uint32_t>(), ns, rank_of.as<uint32_t>());
+            hipLaunchKernelGGL(sa_next_keys, g, dim3(256), 0, stream, sa_cur, rank_of.as<uint32_t>(), ns, h, keys_other);
+            VLG_HIP_TRY(hipGetLastError());
+            if (vlg_status st = sort_pairs(temp, keys_other, keys_sorted, sa_cur, sa_other, ns, 0, 64, stream)) return st;
+            std::swap(sa_cur, sa_other);                   // keys_sorted now holds the sorted keys again
         }
-        if (sa_only) return VLG_OK;
-        // free the big sort buffers we no longer need
-        (void)hipFree(keys_a.p); keys_a.p = nullptr;
-        (void)hipFree(keys_b.p); keys_b.p = nullptr;
-        (void)hipFree(rank_of.p); rank_of.p = nullptr;
-        (void)hipFree(head.p); head.p = nullptr;
-        // --- BWT + alphabet ------------------------------------------------------------------------
-        VLG_HIP_TRY(bwt.alloc(n));
-        VLG_HIP_TRY(hipMemsetAsync(d_hist, 0, 256 * 8, stream));
-        hipLaunchKernelGGL(bwt_kernel, dim3(std::min<uint32_t>(g, 4096)), dim3(256), 0, stream, d_text, sa_cur, n, bwt.as<uint8_t>(), d_hist);
-        VLG_HIP_TRY(hipGetLastError());
-        uint64_t counts[256];
-        VLG_HIP_TRY(hipMemcpyAsync(counts, d_hist, sizeof counts, hipMemcpyDeviceToHost, stream));
-        VLG_HIP_TRY(hipStreamSynchronize(stream));
-        if (counts[0] != 1) return fail(VLG_E_ZERO_BYTE, "text contains a zero byte (sdsl::construct throws std::logic_error)");
-        if (vlg_status st = tree_from_counts(counts, idx->tree)) return st;
-        if (vlg_status st = alloc_blob(idx, n, dens, stream)) return st;
-        const BlobHeader& hd = idx->hdr;
-        uint8_t* blob = reinterpret_cast<uint8_t*>(idx->d_blob);
-        // --- SA samples ----------------------------------------------------------------------------
-        hipLaunchKernelGGL(sample_kernel, dim3(grid_for(hd.n_samples)), dim3(256), 0, stream, sa_cur, n_text, hd.n_samples, dens,
-                           blob + hd.off_samples, hd.sample_bytes);
+    }
+    if (d_sa_out) {
+        hipLaunchKernelGGL(sa_export_kernel, g, dim3(256), 0, stream, sa_cur, n_text, d_sa_out);
         VLG_HIP_TRY(hipGetLastError());
         VLG_HIP_TRY(hipStreamSynchronize(stream));
-        (void)hipFree(sa_a.p); sa_a.p = nullptr;
-        (void)hipFree(sa_b.p); sa_b.p = nullptr;
-        // --- wavelet tree, one depth at a time -------------------------------------------------------
-        const HostTree& t = idx->tree;
-        if (hd.n_blocks) {
-            InnerTable tab = make_inner_table(t);
-            DevBuf d_tab, d_lt, d_arr, syms_b, keys16_a, keys16_b;
-            VLG_HIP_TRY(d_tab.alloc(sizeof tab));
-            VLG_HIP_TRY(hipMemcpy(d_tab.p, &tab, sizeof tab, hipMemcpyHostToDevice));
-            VLG_HIP_TRY(d_lt.alloc(sizeof(LevelTables)));
-            VLG_HIP_TRY(d_arr.alloc(256 * 8));
-            VLG_HIP_TRY(syms_b.alloc(n));
-            VLG_HIP_TRY(keys16_a.alloc(n * 2));
-            VLG_HIP_TRY(keys16_b.alloc(n * 2));
-            uint8_t* cur = bwt.as<uint8_t>();
-            uint8_t* other = syms_b.as<uint8_t>();
-            uint64_t alive = n;                              // symbols whose code is longer than d
-            Block* blocks = const_cast<Block*>(idx->view.blocks);
-            for (uint32_t d = 0; d < t.max_code_len; ++d) {
-                // inner nodes of this depth are consecutive in BFS order
-                uint32_t first_inner = 0, n_inner = 0;
-                for (uint32_t k = 0; k < tab.count; ++k)
-                    if (tab.depth[k] == d) { if (!n_inner) first_inner = k; ++n_inner; }
-                if (!n_inner) break;
-                LevelTables lt;
-                memset(&lt, 0, sizeof lt);
-                uint64_t alive_next = 0;
-                for (uint32_t c = 0; c < 256; ++c) {
-                    lt.key_next[c] = 511;
-                    if (t.c_to_leaf[c] == 0xFFFF) continue;
-                    uint32_t len = (uint32_t)(t.paths[c] >> 56);
-                    if (len <= d) continue;
-                    lt.bit[c] = (uint8_t)((t.paths[c] >> d) & 1);
-                    if (len > d + 1) {
-                        uint32_t v = 0;
-                        for (uint32_t l = 0; l <= d; ++l) v = t.nodes[v].child[(t.paths[c] >> l) & 1];
-                        lt.key_next[c] = (uint16_t)v;
-                        uint32_t cc = t.char2comp[c];
-                        alive_next += t.C[cc + 1] - t.C[cc];
-                    }
+    }
+    if (sa_only) return VLG_OK;
+    // free the big sort buffers we no longer need
+    keys_a.release();
+    keys_b.release();
+    rank_of.release();
+    head.release();
+    // --- BWT + alphabet ------------------------------------------------------------------------
+    VLG_HIP_TRY(bwt.alloc(n));
+    VLG_HIP_TRY(hipMemsetAsync(d_hist, 0, 256 * 8, stream));
+    hipLaunchKernelGGL(bwt_kernel, launch_grid(n, 4096), dim3(256), 0, stream, d_text, sa_cur, n, bwt.as<uint8_t>(), d_hist);
+    VLG_HIP_TRY(hipGetLastError());
+    uint64_t counts[256];
+    VLG_HIP_TRY(hipMemcpyAsync(counts, d_hist, sizeof counts, hipMemcpyDeviceToHost, stream));
+    VLG_HIP_TRY(hipStreamSynchronize(stream));
+    if (counts[0] != 1) return fail(VLG_E_ZERO_BYTE, "text contains a zero byte (sdsl::construct throws std::logic_error)");
+    if (vlg_status st = tree_from_counts(counts, idx->tree)) return st;
+    if (vlg_status st = alloc_blob(idx.get(), n, dens, stream)) return st;
+    const BlobHeader& hd = idx->hdr;
+    uint8_t* blob = reinterpret_cast<uint8_t*>(idx->d_blob);
+    // --- SA samples ----------------------------------------------------------------------------
+    hipLaunchKernelGGL(sample_kernel, launch_grid(hd.n_samples), dim3(256), 0, stream, sa_cur, n_text, hd.n_samples, dens,
+                       blob + hd.off_samples, hd.sample_bytes);
+    VLG_HIP_TRY(hipGetLastError());
+    VLG_HIP_TRY(hipStreamSynchronize(stream));
+    sa_a.release();
+    sa_b.release();
+    // --- wavelet tree, one depth at a time -------------------------------------------------------
+    const HostTree& t = idx->tree;
+    if (hd.n_blocks) {
+        InnerTable tab = make_inner_table(t);
+        DevBuf d_tab, d_lt, d_arr, syms_b, keys16_a, keys16_b;
+        VLG_HIP_TRY(d_tab.alloc(sizeof tab));
+        VLG_HIP_TRY(hipMemcpy(d_tab.p, &tab, sizeof tab, hipMemcpyHostToDevice));
+        VLG_HIP_TRY(d_lt.alloc(sizeof(LevelTables)));
+        VLG_HIP_TRY(d_arr.alloc(256 * 8));
+        VLG_HIP_TRY(syms_b.alloc(n));
+        VLG_HIP_TRY(keys16_a.alloc(n * 2));
+        VLG_HIP_TRY(keys16_b.alloc(n * 2));
+        uint8_t* cur = bwt.as<uint8_t>();
+        uint8_t* other = syms_b.as<uint8_t>();
+        uint64_t alive = n;                              // symbols whose code is longer than d
+        Block* blocks = const_cast<Block*>(idx->view.blocks);
+        for (uint32_t d = 0; d < t.max_code_len; ++d) {
+            // inner nodes of this depth are consecutive in BFS order
+            uint32_t first_inner = 0, n_inner = 0;
+            for (uint32_t k = 0; k < tab.count; ++k)
+                if (tab.depth[k] == d) { if (!n_inner) first_inner = k; ++n_inner; }
+            if (!n_inner) break;
+            LevelTables lt;
+            memset(&lt, 0, sizeof lt);
+            uint64_t alive_next = 0;
+            for (uint32_t c = 0; c < 256; ++c) {
+                lt.key_next[c] = 511;
+                if (t.c_to_leaf[c] == 0xFFFF) continue;
+                uint32_t len = (uint32_t)(t.paths[c] >> 56);
+                if (len <= d) continue;
+                lt.bit[c] = (uint8_t)((t.paths[c] >> d) & 1);
+                if (len > d + 1) {
+                    uint32_t v = 0;
+                    for (uint32_t l = 0; l <= d; ++l) v = t.nodes[v].child[(t.paths[c] >> l) & 1];
+                    lt.key_next[c] = (uint16_t)v;
+                    uint32_t cc = t.char2comp[c];
+                    alive_next += t.C[cc + 1] - t.C[cc];
                 }
-                std::vector<uint64_t> arr_start(n_inner);
-                uint64_t acc = 0, first_block = tab.base[first_inner], last_block = 0;
-                for (uint32_t k = 0; k < n_inner; ++k) {
-                    arr_start[k] = acc;
-                    acc += tab.size[first_inner + k];
-                    last_block = (uint64_t)tab.base[first_inner + k] + tab.size[first_inner + k] / kBlockBits + 1;
-                }
-                if (acc != alive) return fail(VLG_E_INTERNAL, "wavelet tree level size mismatch");
-                VLG_HIP_TRY(hipMemcpyAsync(d_lt.p, &lt, sizeof lt, hipMemcpyHostToDevice, stream));
-                VLG_HIP_TRY(hipMemcpyAsync(d_arr.p, arr_start.data(), n_inner * 8, hipMemcpyHostToDevice, stream));
-                uint64_t nb = last_block - first_block;
-                hipLaunchKernelGGL(wt_emit_kernel, dim3(grid_for(nb * 8)), dim3(256), 0, stream, cur, blocks, d_tab.as<InnerTable>(),
-                                   d_lt.as<LevelTables>(), first_inner, n_inner, first_block, nb, d_arr.as<uint64_t>());
-                VLG_HIP_TRY(hipGetLastError());
-                if (alive_next) {
-                    hipLaunchKernelGGL(wt_keys_kernel, dim3(grid_for(alive)), dim3(256), 0, stream, cur, alive, d_lt.as<LevelTables>(),
-                                       keys16_a.as<uint16_t>());
-                    VLG_HIP_TRY(hipGetLastError());
-                    if (vlg_status st = sort_pairs(temp, temp_cap, keys16_a.as<uint16_t>(), keys16_b.as<uint16_t>(), cur, other,
-                                                   alive, 0, 9, stream)) return st;
-                    std::swap(cur, other);
-                }
-                VLG_HIP_TRY(hipStreamSynchronize(stream));   // lt / arr_start are reused next iteration
-                alive = alive_next;
-                if (!alive) break;
             }
-            if (vlg_status st = fill_block_counts(idx, d_tab.as<InnerTable>(), stream)) return st;
+            std::vector<uint64_t> arr_start(n_inner);
+            uint64_t acc = 0, first_block = tab.base[first_inner], last_block = 0;
+            for (uint32_t k = 0; k < n_inner; ++k) {
+                arr_start[k] = acc;
+                acc += tab.size[first_inner + k];
+                last_block = (uint64_t)tab.base[first_inner + k] + tab.size[first_inner + k] / kBlockBits + 1;
+            }
+            if (acc != alive) return fail(VLG_E_INTERNAL, "wavelet tree level size mismatch");
+            VLG_HIP_TRY(hipMemcpyAsync(d_lt.p, &lt, sizeof lt, hipMemcpyHostToDevice, stream));
+            VLG_HIP_TRY(hipMemcpyAsync(d_arr.p, arr_start.data(), n_inner * 8, hipMemcpyHostToDevice, stream));
+            uint64_t nb = last_block - first_block;
+            hipLaunchKernelGGL(wt_emit_kernel, launch_grid(nb * 8), dim3(256), 0, stream, cur, blocks, d_tab.as<InnerTable>(),
+                               d_lt.as<LevelTables>(), first_inner, n_inner, first_block, nb, d_arr.as<uint64_t>());
+            VLG_HIP_TRY(hipGetLastError());
+            if (alive_next) {
+                hipLaunchKernelGGL(wt_keys_kernel, launch_grid(alive), dim3(256), 0, stream, cur, alive, d_lt.as<LevelTables>(),
+                                   keys16_a.as<uint16_t>());
+                VLG_HIP_TRY(hipGetLastError());
+                if (vlg_status st = sort_pairs(temp, keys16_a.as<uint16_t>(), keys16_b.as<uint16_t>(), cur, other,
+                                               alive, 0, 9, stream)) return st;
+                std::swap(cur, other);
+            }
+            VLG_HIP_TRY(hipStreamSynchronize(stream));   // lt / arr_start are reused next iteration
+            alive = alive_next;
+            if (!alive) break;
         }
-        VLG_HIP_TRY(hipStreamSynchronize(stream));
-        return VLG_OK;
-    };
-    vlg_status st = run();
-    if (st || sa_only) { vlg_index_destroy(idx); return st; }
-    *out = idx;
+        if (vlg_status st = fill_block_counts(idx.get(), d_tab.as<InnerTable>(), stream)) return st;
+    }
+    VLG_HIP_TRY(hipStreamSynchronize(stream));
+    *out = idx.release();
     return VLG_OK;
 }
 

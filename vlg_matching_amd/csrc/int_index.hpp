@@ -391,7 +391,9 @@ vlg_status int_alloc_blob(vlg_index* idx, uint64_t n, uint64_t sigma, uint32_t d
     h.levels = sigma > 1 ? bit_width64(sigma - 1) : 0;
     if (h.levels > kMaxIntLevels || (uint64_t)h.levels * h.nb >= 0xFFFFFFF0ull) return fail(VLG_E_UNSUPPORTED, "integer index too large for 32-bit block numbers");
     layout_int(h);
-    VLG_HIP_TRY(hipMalloc(&idx->d_blob, h.total_bytes));
+    DevBuf blob;
+    VLG_HIP_TRY(blob.alloc(h.total_bytes));
+    idx->d_blob = blob.take();
     idx->owns_blob = true;
     VLG_HIP_TRY(hipMemset(idx->d_blob, 0, h.total_bytes));
     VLG_HIP_TRY(hipMemcpy(idx->d_blob, &h, sizeof h, hipMemcpyHostToDevice));
@@ -400,56 +402,38 @@ vlg_status int_alloc_blob(vlg_index* idx, uint64_t n, uint64_t sigma, uint32_t d
 }
 
 // The tail every integer index shares (vlg_index_build_int, vlg_index_from_int_parts): the BWT in compact symbols in d_cur (n words) ->
-// the wavelet matrix level by level, Z and D, in the blob of int_alloc_blob whose C and comp2char are filled.  d_other, d_ka, d_kb: n-word
-// scratch; d_tmp: rocPRIM scratch of tmp_bytes (allocated here when smaller than the stable partition needs).
-vlg_status int_matrix_from_bwt(vlg_index* idx, uint32_t* d_cur, uint32_t* d_other, uint32_t* d_ka, uint32_t* d_kb, void* d_tmp, size_t tmp_bytes)
+// the wavelet matrix level by level (wtsa.hpp: wtsa_emit_level), Z and D, in the blob of int_alloc_blob whose C and comp2char are filled.
+// d_other, d_ka, d_kb: n-word scratch; tmp: rocPRIM scratch, grown here when the scan or the stable partition needs more than it holds.
+vlg_status int_matrix_from_bwt(vlg_index* idx, uint32_t* d_cur, uint32_t* d_other, uint32_t* d_ka, uint32_t* d_kb, DevBuf& tmp)
 {
     const IntHeader& h = idx->ihdr;
     const uint64_t n = h.n;
-    auto grid = [](uint64_t m) { return dim3((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((m + 255) / 256, 16384))); };
     uint8_t* b = reinterpret_cast<uint8_t*>(idx->d_blob);
     Block* lv = reinterpret_cast<Block*>(b + h.off_levels);
     uint64_t* d_Z = reinterpret_cast<uint64_t*>(b + h.off_Z);
     std::vector<uint64_t> Z(kMaxIntLevels, 0);
     uint32_t* cur = d_cur;
     uint32_t* other = d_other;
-    uint32_t* d_pops = nullptr;
-    void *d_tmp2 = nullptr, *d_own = nullptr;
-    size_t pops_tb = 0, pair_tb = 0;
-    auto run = [&]() -> vlg_status {
-        VLG_HIP_TRY(rocprim::radix_sort_pairs(nullptr, pair_tb, d_ka, d_kb, cur, other, n, 0, 1, nullptr));
-        if (tmp_bytes < pair_tb) { VLG_HIP_TRY(hipMalloc(&d_own, pair_tb + 16)); d_tmp = d_own; }
-        VLG_HIP_TRY(hipMalloc((void**)&d_pops, (h.nb + 1) * 4));
-        VLG_HIP_TRY(rocprim::exclusive_scan(nullptr, pops_tb, d_pops, d_pops, 0u, h.nb + 1, rocprim::plus<uint32_t>(), nullptr));
-        VLG_HIP_TRY(hipMalloc(&d_tmp2, pops_tb + 16));
-        for (uint32_t l = 0; l < h.levels; ++l) {
-            const uint32_t bit = h.levels - 1 - l;
-            Block* lb = lv + (uint64_t)l * h.nb;
-            VLG_HIP_TRY(hipMemsetAsync(d_pops, 0, (h.nb + 1) * 4, nullptr));
-            hipLaunchKernelGGL(wtsa_emit_kernel, grid(h.nb * 7), dim3(256), 0, nullptr, cur, n, bit, lb, h.nb, d_pops);
-            size_t tb = pops_tb;
-            VLG_HIP_TRY(rocprim::exclusive_scan(d_tmp2, tb, d_pops, d_pops, 0u, h.nb + 1, rocprim::plus<uint32_t>(), nullptr));
-            hipLaunchKernelGGL(wtsa_counts_kernel, grid(h.nb), dim3(256), 0, nullptr, lb, d_pops, h.nb);
-            uint32_t ones = 0;
-            VLG_HIP_TRY(hipMemcpy(&ones, d_pops + h.nb, 4, hipMemcpyDeviceToHost));
-            Z[l] = n - ones;
-            if (l + 1 < h.levels) {                                    // next arrangement: stable by this bit, zeros first
-                hipLaunchKernelGGL(int_bit_keys_kernel, grid(n), dim3(256), 0, nullptr, cur, n, bit, d_ka);
-                tb = pair_tb;
-                VLG_HIP_TRY(rocprim::radix_sort_pairs(d_tmp, tb, d_ka, d_kb, cur, other, n, 0, 1, nullptr));
-                std::swap(cur, other);
-            }
-            VLG_HIP_TRY(hipGetLastError());
+    DevBuf d_pops;
+    VLG_HIP_TRY(d_pops.alloc((h.nb + 1) * 4));
+    for (uint32_t l = 0; l < h.levels; ++l) {
+        const uint32_t bit = h.levels - 1 - l;
+        if (vlg_status s = wtsa_emit_level(cur, n, bit, lv + (uint64_t)l * h.nb, h.nb, d_pops.as<uint32_t>(), tmp)) return s;
+        uint32_t ones = 0;
+        VLG_HIP_TRY(hipMemcpy(&ones, d_pops.as<uint32_t>() + h.nb, 4, hipMemcpyDeviceToHost));
+        Z[l] = n - ones;
+        if (l + 1 < h.levels) {                                    // next arrangement: stable by this bit, zeros first
+            hipLaunchKernelGGL(int_bit_keys_kernel, launch_grid(n), dim3(256), 0, nullptr, cur, n, bit, d_ka);
+            VLG_HIP_TRY(with_scratch(tmp, [&](void* t, size_t& tb) { return rocprim::radix_sort_pairs(t, tb, d_ka, d_kb, cur, other, n, 0, 1, nullptr); }));
+            std::swap(cur, other);
         }
-        VLG_HIP_TRY(hipMemcpy(d_Z, Z.data(), kMaxIntLevels * 8, hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(int_D_kernel, grid(h.sigma), dim3(256), 0, nullptr, idx->iview, reinterpret_cast<uint64_t*>(b + h.off_D));
         VLG_HIP_TRY(hipGetLastError());
-        VLG_HIP_TRY(hipDeviceSynchronize());
-        return VLG_OK;
-    };
-    const vlg_status st = run();
-    for (void* p : {(void*)d_pops, d_tmp2, d_own}) if (p) (void)hipFree(p);
-    return st;
+    }
+    VLG_HIP_TRY(hipMemcpy(d_Z, Z.data(), kMaxIntLevels * 8, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(int_D_kernel, launch_grid(h.sigma), dim3(256), 0, nullptr, idx->iview, reinterpret_cast<uint64_t*>(b + h.off_D));
+    VLG_HIP_TRY(hipGetLastError());
+    VLG_HIP_TRY(hipDeviceSynchronize());
+    return VLG_OK;
 }
 
 }  // namespace
@@ -461,94 +445,59 @@ extern "C" vlg_status vlg_index_build_int(const uint32_t* h_text, uint64_t n_sym
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(VLG_E_NO_DEVICE, "no HIP device available (the VLG library has no CPU fallback)");
     if (!dens) dens = 32;
-    const uint64_t byte_len = n_symbols * 5;
-    if (byte_len >= 0xFFFFFFF0ull) return fail(VLG_E_UNSUPPORTED, "integer text too long for the 32-bit suffix array of this index");
+    if (n_symbols * 5 >= 0xFFFFFFF0ull) return fail(VLG_E_UNSUPPORTED, "integer text too long for the 32-bit suffix array of this index");
     release_cached_device_memory();
     const uint64_t n = n_symbols + 1;
-    vlg_index* idx = new vlg_index();
-    uint32_t *d_text = nullptr, *d_sa5 = nullptr, *d_flag = nullptr, *d_pos = nullptr, *d_sa = nullptr, *d_a = nullptr, *d_b = nullptr, *d_ka = nullptr,
-             *d_kb = nullptr, *d_c2c = nullptr;
-    uint8_t* d_bytes = nullptr;
-    uint64_t* d_C = nullptr;
-    void* d_tmp = nullptr;
-    auto grid = [](uint64_t m) { return dim3((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((m + 255) / 256, 16384))); };
-    auto run = [&]() -> vlg_status {
-        VLG_HIP_TRY(hipMalloc((void**)&d_text, std::max<uint64_t>(n_symbols * 4, 16)));
-        if (n_symbols) VLG_HIP_TRY(hipMemcpy(d_text, h_text, n_symbols * 4, hipMemcpyHostToDevice));
-        VLG_HIP_TRY(hipMalloc((void**)&d_flag, (byte_len + 2) * 4));
-        VLG_HIP_TRY(hipMemset(d_flag, 0, 4));
-        if (n_symbols) hipLaunchKernelGGL(int_zero_check_kernel, grid(n_symbols), dim3(256), 0, nullptr, d_text, n_symbols, d_flag);
-        uint32_t has_zero = 0;
-        VLG_HIP_TRY(hipMemcpy(&has_zero, d_flag, 4, hipMemcpyDeviceToHost));
-        if (has_zero) return fail(VLG_E_ZERO_BYTE, "the integer text contains the symbol 0 (reserved for the sentinel: construct.hpp:36-45)");
-        // ---- suffix array: the integer text as five base-255 digits + 1 per symbol, then the aligned suffixes (as vlg_wtsa_build) ------------
-        VLG_HIP_TRY(hipMalloc((void**)&d_sa5, (byte_len + 1) * 4));
-        VLG_HIP_TRY(hipMalloc((void**)&d_sa, n * 4));
-        if (n_symbols) {
-            VLG_HIP_TRY(hipMalloc((void**)&d_bytes, byte_len));
-            hipLaunchKernelGGL(wtsa_expand_kernel, grid(n_symbols), dim3(256), 0, nullptr, d_text, n_symbols, d_bytes);
-            VLG_HIP_TRY(hipGetLastError());
-            if (vlg_status s = vlg_suffix_array_device(d_bytes, byte_len, d_sa5, nullptr)) return s;
-            (void)hipFree(d_bytes); d_bytes = nullptr;
-            const uint64_t nb5 = byte_len + 1;
-            VLG_HIP_TRY(hipMalloc((void**)&d_pos, nb5 * 4));
-            hipLaunchKernelGGL(wtsa_aligned_flags_kernel, grid(nb5), dim3(256), 0, nullptr, d_sa5, nb5, d_flag);
-            size_t tb = 0;
-            VLG_HIP_TRY(rocprim::exclusive_scan(nullptr, tb, d_flag, d_pos, 0u, nb5, rocprim::plus<uint32_t>(), nullptr));
-            VLG_HIP_TRY(hipMalloc(&d_tmp, tb + 16));
-            VLG_HIP_TRY(rocprim::exclusive_scan(d_tmp, tb, d_flag, d_pos, 0u, nb5, rocprim::plus<uint32_t>(), nullptr));
-            hipLaunchKernelGGL(wtsa_aligned_compact_kernel, grid(nb5), dim3(256), 0, nullptr, d_sa5, d_pos, nb5, d_sa);
-            VLG_HIP_TRY(hipGetLastError());
-            VLG_HIP_TRY(hipDeviceSynchronize());
-            (void)hipFree(d_tmp); d_tmp = nullptr;
-            (void)hipFree(d_pos); d_pos = nullptr;
-        } else {
-            VLG_HIP_TRY(hipMemset(d_sa, 0, 4));
-        }
-        (void)hipFree(d_sa5); d_sa5 = nullptr;
-        (void)hipFree(d_flag); d_flag = nullptr;
-        // ---- int_alphabet: sorted distinct symbols and their cumulative counts (csa_alphabet_strategy.hpp:496-536) ----------------------
-        VLG_HIP_TRY(hipMalloc((void**)&d_a, n * 4));
-        VLG_HIP_TRY(hipMalloc((void**)&d_b, n * 4));
-        VLG_HIP_TRY(hipMalloc((void**)&d_ka, n * 4));
-        VLG_HIP_TRY(hipMalloc((void**)&d_kb, n * 4));
-        size_t sort_tb = 0, scan_tb = 0, pair_tb = 0;
-        VLG_HIP_TRY(rocprim::radix_sort_keys(nullptr, sort_tb, d_a, d_b, n, 0, 32, nullptr));
-        VLG_HIP_TRY(rocprim::inclusive_scan(nullptr, scan_tb, d_ka, d_kb, n, rocprim::plus<uint32_t>(), nullptr));
-        VLG_HIP_TRY(rocprim::radix_sort_pairs(nullptr, pair_tb, d_ka, d_kb, d_a, d_b, n, 0, 1, nullptr));
-        VLG_HIP_TRY(hipMalloc(&d_tmp, std::max(std::max(sort_tb, scan_tb), pair_tb) + 16));
-        uint64_t sigma = 1;
-        if (n_symbols) {
-            size_t tb = sort_tb;
-            VLG_HIP_TRY(rocprim::radix_sort_keys(d_tmp, tb, d_text, d_b, n_symbols, 0, 32, nullptr));       // d_b = sorted text
-            hipLaunchKernelGGL(int_heads_kernel, grid(n_symbols), dim3(256), 0, nullptr, d_b, n_symbols, d_ka);
-            tb = scan_tb;
-            VLG_HIP_TRY(rocprim::inclusive_scan(d_tmp, tb, d_ka, d_kb, n_symbols, rocprim::plus<uint32_t>(), nullptr));   // d_kb = symbol number (1-based)
-            uint32_t distinct = 0;
-            VLG_HIP_TRY(hipMemcpy(&distinct, d_kb + (n_symbols - 1), 4, hipMemcpyDeviceToHost));
-            sigma = (uint64_t)distinct + 1;
-        }
-        if (vlg_status s = int_alloc_blob(idx, n, sigma, dens)) return s;
-        const IntHeader& h = idx->ihdr;
-        uint8_t* b = reinterpret_cast<uint8_t*>(idx->d_blob);
-        d_c2c = reinterpret_cast<uint32_t*>(b + h.off_c2c);
-        d_C = reinterpret_cast<uint64_t*>(b + h.off_C);
-        if (n_symbols) hipLaunchKernelGGL(int_alphabet_kernel, grid(n_symbols), dim3(256), 0, nullptr, d_b, d_kb, n_symbols, d_c2c, d_C);   // comp 0 = the sentinel, C[0] = 0
-        VLG_HIP_TRY(hipMemcpy(d_C + sigma, &n, 8, hipMemcpyHostToDevice));
-        // ---- BWT in compact symbols, then the wavelet matrix level by level ----------------------------------------------------------------
-        hipLaunchKernelGGL(int_bwt_kernel, grid(n), dim3(256), 0, nullptr, d_text, d_sa, n, d_c2c, sigma, d_a);
-        VLG_HIP_TRY(hipGetLastError());
-        if (vlg_status s = int_matrix_from_bwt(idx, d_a, d_b, d_ka, d_kb, d_tmp, std::max(std::max(sort_tb, scan_tb), pair_tb))) return s;
-        hipLaunchKernelGGL(int_samples_kernel, grid(h.n_samples), dim3(256), 0, nullptr, d_sa, h.n_samples, dens, reinterpret_cast<uint32_t*>(b + h.off_samples));
-        VLG_HIP_TRY(hipGetLastError());
-        VLG_HIP_TRY(hipDeviceSynchronize());
-        return VLG_OK;
-    };
-    const vlg_status st = run();
-    for (void* p : {(void*)d_text, (void*)d_sa5, (void*)d_flag, (void*)d_pos, (void*)d_sa, (void*)d_a, (void*)d_b, (void*)d_ka, (void*)d_kb, (void*)d_bytes, d_tmp})
-        if (p) (void)hipFree(p);
-    if (st) { vlg_index_destroy(idx); return st; }
-    *out = idx;
+    IndexPtr idx(new vlg_index());
+    DevBuf text, flag, sa, arr_a, arr_b, ka, kb, tmp;
+    VLG_HIP_TRY(text.alloc(n_symbols * 4));
+    uint32_t* d_text = text.as<uint32_t>();
+    if (n_symbols) VLG_HIP_TRY(hipMemcpy(d_text, h_text, n_symbols * 4, hipMemcpyHostToDevice));
+    VLG_HIP_TRY(flag.alloc((n_symbols * 5 + 2) * 4));               // the zero check's word now, the flags of symbol_suffix_array after it
+    VLG_HIP_TRY(hipMemset(flag.p, 0, 4));
+    if (n_symbols) hipLaunchKernelGGL(int_zero_check_kernel, launch_grid(n_symbols), dim3(256), 0, nullptr, d_text, n_symbols, flag.as<uint32_t>());
+    uint32_t has_zero = 0;
+    VLG_HIP_TRY(hipMemcpy(&has_zero, flag.p, 4, hipMemcpyDeviceToHost));
+    if (has_zero) return fail(VLG_E_ZERO_BYTE, "the integer text contains the symbol 0 (reserved for the sentinel: construct.hpp:36-45)");
+    // ---- suffix array of the symbols (wtsa.hpp, as vlg_wtsa_build) -----------------------------------------------------------------------
+    if (vlg_status s = symbol_suffix_array(d_text, n_symbols, flag, sa)) return s;
+    flag.release();
+    uint32_t* d_sa = sa.as<uint32_t>();
+    // ---- int_alphabet: sorted distinct symbols and their cumulative counts (csa_alphabet_strategy.hpp:496-536) ----------------------
+    VLG_HIP_TRY(arr_a.alloc(n * 4));
+    VLG_HIP_TRY(arr_b.alloc(n * 4));
+    VLG_HIP_TRY(ka.alloc(n * 4));
+    VLG_HIP_TRY(kb.alloc(n * 4));
+    uint32_t *d_a = arr_a.as<uint32_t>(), *d_b = arr_b.as<uint32_t>(), *d_ka = ka.as<uint32_t>(), *d_kb = kb.as<uint32_t>();
+    size_t sort_tb = 0, scan_tb = 0, pair_tb = 0;                   // the largest request of the stages below and of the matrix builder: no stage regrows tmp
+    VLG_HIP_TRY(rocprim::radix_sort_keys(nullptr, sort_tb, d_a, d_b, n, 0, 32, nullptr));
+    VLG_HIP_TRY(rocprim::inclusive_scan(nullptr, scan_tb, d_ka, d_kb, n, rocprim::plus<uint32_t>(), nullptr));
+    VLG_HIP_TRY(rocprim::radix_sort_pairs(nullptr, pair_tb, d_ka, d_kb, d_a, d_b, n, 0, 1, nullptr));
+    VLG_HIP_TRY(tmp.alloc(std::max(std::max(sort_tb, scan_tb), pair_tb)));
+    uint64_t sigma = 1;
+    if (n_symbols) {
+        VLG_HIP_TRY(with_scratch(tmp, [&](void* t, size_t& tb) { return rocprim::radix_sort_keys(t, tb, d_text, d_b, n_symbols, 0, 32, nullptr); }));       // d_b = sorted text
+        hipLaunchKernelGGL(int_heads_kernel, launch_grid(n_symbols), dim3(256), 0, nullptr, d_b, n_symbols, d_ka);
+        VLG_HIP_TRY(with_scratch(tmp, [&](void* t, size_t& tb) { return rocprim::inclusive_scan(t, tb, d_ka, d_kb, n_symbols, rocprim::plus<uint32_t>(), nullptr); }));   // d_kb = symbol number (1-based)
+        uint32_t distinct = 0;
+        VLG_HIP_TRY(hipMemcpy(&distinct, d_kb + (n_symbols - 1), 4, hipMemcpyDeviceToHost));
+        sigma = (uint64_t)distinct + 1;
+    }
+    if (vlg_status s = int_alloc_blob(idx.get(), n, sigma, dens)) return s;
+    const IntHeader& h = idx->ihdr;
+    uint8_t* b = reinterpret_cast<uint8_t*>(idx->d_blob);
+    uint32_t* d_c2c = reinterpret_cast<uint32_t*>(b + h.off_c2c);
+    uint64_t* d_C = reinterpret_cast<uint64_t*>(b + h.off_C);
+    if (n_symbols) hipLaunchKernelGGL(int_alphabet_kernel, launch_grid(n_symbols), dim3(256), 0, nullptr, d_b, d_kb, n_symbols, d_c2c, d_C);   // comp 0 = the sentinel, C[0] = 0
+    VLG_HIP_TRY(hipMemcpy(d_C + sigma, &n, 8, hipMemcpyHostToDevice));
+    // ---- BWT in compact symbols, then the wavelet matrix level by level ----------------------------------------------------------------
+    hipLaunchKernelGGL(int_bwt_kernel, launch_grid(n), dim3(256), 0, nullptr, d_text, d_sa, n, d_c2c, sigma, d_a);
+    VLG_HIP_TRY(hipGetLastError());
+    if (vlg_status s = int_matrix_from_bwt(idx.get(), d_a, d_b, d_ka, d_kb, tmp)) return s;
+    hipLaunchKernelGGL(int_samples_kernel, launch_grid(h.n_samples), dim3(256), 0, nullptr, d_sa, h.n_samples, dens, reinterpret_cast<uint32_t*>(b + h.off_samples));
+    VLG_HIP_TRY(hipGetLastError());
+    VLG_HIP_TRY(hipDeviceSynchronize());
+    *out = idx.release();
     return VLG_OK;
 }
 
@@ -574,9 +523,9 @@ extern "C" vlg_status vlg_int_rank_batch(const vlg_index* idx, const uint64_t* d
     if (!idx->is_int) return fail(VLG_E_INVALID, "not an integer-alphabet index");
     if (!count) return VLG_OK;
     if (idx->iview.bv_kind == kBvRrr63)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(int_rank_kernel<RrrBV>), dim3(grid_for(count, 8192)), dim3(256), 0, (hipStream_t)stream, idx->iview, d_i, d_sym, d_out, count);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(int_rank_kernel<RrrBV>), launch_grid(count, 8192), dim3(256), 0, (hipStream_t)stream, idx->iview, d_i, d_sym, d_out, count);
     else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(int_rank_kernel<PlainBV>), dim3(grid_for(count, 8192)), dim3(256), 0, (hipStream_t)stream, idx->iview, d_i, d_sym, d_out, count);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(int_rank_kernel<PlainBV>), launch_grid(count, 8192), dim3(256), 0, (hipStream_t)stream, idx->iview, d_i, d_sym, d_out, count);
     VLG_HIP_TRY(hipGetLastError());
     return VLG_OK;
 }
@@ -588,9 +537,9 @@ vlg_status launch_int_backward_search(const IntView& v, const uint8_t* d_blob, c
 {
     if (!n_pat) return VLG_OK;
     if (v.bv_kind == kBvRrr63)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(int_backward_search_kernel<RrrBV>), dim3(grid_for(n_pat, 4096)), dim3(256), 0, st, v, d_blob, d_off, n_pat, d_l, d_r, d_stat_levels);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(int_backward_search_kernel<RrrBV>), launch_grid(n_pat, 4096), dim3(256), 0, st, v, d_blob, d_off, n_pat, d_l, d_r, d_stat_levels);
     else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(int_backward_search_kernel<PlainBV>), dim3(grid_for(n_pat, 4096)), dim3(256), 0, st, v, d_blob, d_off, n_pat, d_l, d_r, d_stat_levels);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(int_backward_search_kernel<PlainBV>), launch_grid(n_pat, 4096), dim3(256), 0, st, v, d_blob, d_off, n_pat, d_l, d_r, d_stat_levels);
     VLG_HIP_TRY(hipGetLastError());
     return VLG_OK;
 }
@@ -604,14 +553,13 @@ static vlg_status launch_int_locate_sweep_bv(const IntView& v, const uint64_t* d
 {
     if (v.sigma >= 0xFFFFu || v.n_levels < 1 || v.n > (1ull << 32)) return fail(VLG_E_INTERNAL, "integer index: not for the sorted sweep");
     using Walk = IntWalk<BV>;
-    auto grid_of = [](uint64_t n, uint32_t cap) { return dim3((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, cap))); };
     SweepKernels K;
     K.n = v.n;
     K.sigma = (uint32_t)v.sigma;
     K.first = [&](uint64_t t0, uint64_t t1, uint64_t* val, uint16_t* key, void* out, unsigned long long* counter, const Block* mem, uint64_t* rc, bool ahead,
                   uint32_t* chunk_list) {
         launch_sweep_chunk_lists(d_out_off, n_pat, t0, t1, chunk_list, stream);
-        const dim3 g = grid_of((t1 - t0 + 7) / 8, 8192);
+        const dim3 g = launch_grid((t1 - t0 + 7) / 8, 8192);
         uint32_t* o = static_cast<uint32_t*>(out);
 #define VLG_INT_FIRST(TR, AH) hipLaunchKernelGGL(HIP_KERNEL_NAME(sweep_first_kernel<Walk, Sampling, uint32_t, TR, false, AH>), g, dim3(256), 0, stream, v, d_l, d_out_off, n_pat, t0, t1, val, key, o, d_stats, counter, mem, rc, chunk_list, (uint8_t*)nullptr)
         if (mem && ahead) VLG_INT_FIRST(true, true);
@@ -620,7 +568,7 @@ static vlg_status launch_int_locate_sweep_bv(const IntView& v, const uint64_t* d
 #undef VLG_INT_FIRST
     };
     K.step = [&](uint64_t* val, uint16_t* key, uint64_t alive, uint32_t step, void* out, unsigned long long* counter, const Block* mem, uint64_t* rc, uint64_t t0, bool probed) {
-        const dim3 g = grid_of(alive, 4096);
+        const dim3 g = launch_grid(alive, 4096);
         uint32_t* o = static_cast<uint32_t*>(out);
         if (mem) hipLaunchKernelGGL(HIP_KERNEL_NAME(sweep_step_kernel<Walk, Sampling, uint32_t, true, false>), g, dim3(256), 0, stream, v, val, key, alive, step, o, d_stats, counter, mem, rc, t0, probed);
         else hipLaunchKernelGGL(HIP_KERNEL_NAME(sweep_step_kernel<Walk, Sampling, uint32_t, false, false>), g, dim3(256), 0, stream, v, val, key, alive, step, o, d_stats, counter, mem, rc, t0, probed);
@@ -678,7 +626,7 @@ vlg_status launch_int_locate(const IntView& v, uint32_t* d_io, uint64_t total, u
 vlg_status launch_int_sa_expand(const IntView& v, uint32_t* d_sa, hipStream_t st)
 {
     if (v.sampling != kSamplingSaOrder) return fail(VLG_E_INTERNAL, "integer index: expanding the suffix array needs SA-order samples");
-    const dim3 grid(grid_for(v.n_samples, 8192));
+    const dim3 grid = launch_grid(v.n_samples, 8192);
     if (v.bv_kind == kBvRrr63) hipLaunchKernelGGL(HIP_KERNEL_NAME(int_sa_expand_kernel<RrrBV>), grid, dim3(256), 0, st, v, d_sa);
     else hipLaunchKernelGGL(HIP_KERNEL_NAME(int_sa_expand_kernel<PlainBV>), grid, dim3(256), 0, st, v, d_sa);
     VLG_HIP_TRY(hipGetLastError());
@@ -689,7 +637,7 @@ vlg_status launch_int_sa_expand(const IntView& v, uint32_t* d_sa, hipStream_t st
 vlg_status launch_int_isa_samples(const IntView& v, uint32_t inv_dens, uint32_t* d_out, hipStream_t st)
 {
     if (v.sampling != kSamplingSaOrder || !inv_dens) return fail(VLG_E_INTERNAL, "integer index: ISA samples need SA-order samples");
-    const dim3 grid(grid_for(v.n_samples, 8192));
+    const dim3 grid = launch_grid(v.n_samples, 8192);
     if (v.bv_kind == kBvRrr63) hipLaunchKernelGGL(HIP_KERNEL_NAME(int_isa_samples_kernel<RrrBV>), grid, dim3(256), 0, st, v, inv_dens, d_out);
     else hipLaunchKernelGGL(HIP_KERNEL_NAME(int_isa_samples_kernel<PlainBV>), grid, dim3(256), 0, st, v, inv_dens, d_out);
     VLG_HIP_TRY(hipGetLastError());
@@ -698,7 +646,7 @@ vlg_status launch_int_isa_samples(const IntView& v, uint32_t inv_dens, uint32_t*
 
 vlg_status launch_int_extract(const IntView& v, const ExtractJob& job, const uint32_t* d_isa, uint32_t* d_out, hipStream_t st)
 {
-    const dim3 grid(grid_for(job.n_segs, 8192));
+    const dim3 grid = launch_grid(job.n_segs, 8192);
     if (v.bv_kind == kBvRrr63) hipLaunchKernelGGL(HIP_KERNEL_NAME(int_extract_kernel<RrrBV>), grid, dim3(256), 0, st, v, job, d_isa, d_out);
     else hipLaunchKernelGGL(HIP_KERNEL_NAME(int_extract_kernel<PlainBV>), grid, dim3(256), 0, st, v, job, d_isa, d_out);
     VLG_HIP_TRY(hipGetLastError());
@@ -708,7 +656,7 @@ vlg_status launch_int_extract(const IntView& v, const ExtractJob& job, const uin
 vlg_status launch_int_isa(const IntView& v, uint32_t d, const uint32_t* d_isa, const uint64_t* d_i, uint64_t* d_out, uint64_t count,
                           unsigned long long* d_bad, hipStream_t st)
 {
-    const dim3 grid(grid_for(count, 8192));
+    const dim3 grid = launch_grid(count, 8192);
     if (v.bv_kind == kBvRrr63) hipLaunchKernelGGL(HIP_KERNEL_NAME(int_isa_kernel<RrrBV>), grid, dim3(256), 0, st, v, d, d_isa, d_i, d_out, count, d_bad);
     else hipLaunchKernelGGL(HIP_KERNEL_NAME(int_isa_kernel<PlainBV>), grid, dim3(256), 0, st, v, d, d_isa, d_i, d_out, count, d_bad);
     VLG_HIP_TRY(hipGetLastError());
@@ -724,38 +672,35 @@ inline uint32_t int_max_level(uint64_t largest) { return (uint32_t)bit_width64(s
 
 // device scratch of the level steps: the tree, (payload, first comp) twice, the per-node tables and the popcount scan of one level
 struct TreeScratch {
-    uint64_t* tree = nullptr;
-    uint32_t *pay[2] = {nullptr, nullptr}, *first[2] = {nullptr, nullptr}, *split = nullptr, *end = nullptr, *pops = nullptr, *bad = nullptr;
-    void* tmp = nullptr;
-    size_t tmp_bytes = 0;
+    DevBuf tree, pay[2], first[2], split, end, pops, bad, tmp;
     uint64_t words = 0, max_nw = 0;
     vlg_status alloc(uint64_t n, uint64_t sigma, uint32_t L)
     {
         words = (n * L + 63) / 64;
         max_nw = n / 64 + 2;                                            // words one level of n bits touches
-        VLG_HIP_TRY(hipMalloc((void**)&tree, (words + 1) * 8));
+        VLG_HIP_TRY(tree.alloc((words + 1) * 8));
         for (int k = 0; k < 2; ++k) {
-            VLG_HIP_TRY(hipMalloc((void**)&pay[k], n * 4));
-            VLG_HIP_TRY(hipMalloc((void**)&first[k], n * 4));
+            VLG_HIP_TRY(pay[k].alloc(n * 4));
+            VLG_HIP_TRY(first[k].alloc(n * 4));
         }
-        VLG_HIP_TRY(hipMalloc((void**)&split, (sigma + 1) * 4));
-        VLG_HIP_TRY(hipMalloc((void**)&end, (sigma + 1) * 4));
-        VLG_HIP_TRY(hipMalloc((void**)&pops, (max_nw + 1) * 4));
-        VLG_HIP_TRY(hipMalloc((void**)&bad, 4));
-        VLG_HIP_TRY(hipMemset(bad, 0, 4));
-        VLG_HIP_TRY(rocprim::exclusive_scan(nullptr, tmp_bytes, pops, pops, 0u, max_nw, rocprim::plus<uint32_t>(), nullptr));
-        VLG_HIP_TRY(hipMalloc(&tmp, tmp_bytes + 16));
+        VLG_HIP_TRY(split.alloc((sigma + 1) * 4));
+        VLG_HIP_TRY(end.alloc((sigma + 1) * 4));
+        VLG_HIP_TRY(pops.alloc((max_nw + 1) * 4));
+        VLG_HIP_TRY(bad.alloc(4));
+        VLG_HIP_TRY(hipMemset(bad.p, 0, 4));
+        size_t tb = 0;                                                  // the scan's scratch for the widest level, so that no level regrows it
+        VLG_HIP_TRY(rocprim::exclusive_scan(nullptr, tb, pops.as<uint32_t>(), pops.as<uint32_t>(), 0u, max_nw, rocprim::plus<uint32_t>(), nullptr));
+        VLG_HIP_TRY(tmp.alloc(tb));
         return VLG_OK;
     }
-    void release()
+    // exclusive scan of the popcounts of one level's nw words, in place
+    vlg_status scan_pops(uint64_t nw)
     {
-        for (void* p : {(void*)tree, (void*)pay[0], (void*)pay[1], (void*)first[0], (void*)first[1], (void*)split, (void*)end, (void*)pops, (void*)bad, tmp})
-            if (p) (void)hipFree(p);
-        *this = TreeScratch();
+        uint32_t* p = pops.as<uint32_t>();
+        VLG_HIP_TRY(with_scratch(tmp, [&](void* t, size_t& tb) { return rocprim::exclusive_scan(t, tb, p, p, 0u, nw, rocprim::plus<uint32_t>(), nullptr); }));
+        return VLG_OK;
     }
 };
-
-inline dim3 int_grid(uint64_t m) { return dim3((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((m + 255) / 256, 16384))); }
 
 // level l of the tree: first word g0 and the number of words nw it touches
 inline void tree_level_words(uint64_t n, uint32_t l, uint64_t& base, uint64_t& g0, uint64_t& nw)
@@ -768,57 +713,58 @@ inline void tree_level_words(uint64_t n, uint32_t l, uint64_t& base, uint64_t& g
 // encode: compact BWT in s.pay[0] -> the level-wise tree over comp2char (d_c2c) in s.tree, L levels
 vlg_status int_tree_encode(TreeScratch& s, uint64_t n, uint64_t sigma, uint32_t L, const uint32_t* d_c2c, const uint64_t* d_C)
 {
-    VLG_HIP_TRY(hipMemset(s.tree, 0, (s.words + 1) * 8));
-    VLG_HIP_TRY(hipMemset(s.first[0], 0, n * 4));
+    uint64_t* tree = s.tree.as<uint64_t>();
+    uint32_t *pops = s.pops.as<uint32_t>(), *split = s.split.as<uint32_t>(), *end = s.end.as<uint32_t>(), *bad_flag = s.bad.as<uint32_t>();
+    VLG_HIP_TRY(hipMemset(tree, 0, (s.words + 1) * 8));
+    VLG_HIP_TRY(hipMemset(s.first[0].p, 0, n * 4));
     int cur = 0;
     for (uint32_t l = 0; l < L; ++l) {
         uint64_t base, g0, nw;
         tree_level_words(n, l, base, g0, nw);
-        const uint32_t waves_per_block = 4;
-        const dim3 eg((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((nw + waves_per_block - 1) / waves_per_block, 16384)));
-        hipLaunchKernelGGL(int_tree_emit_kernel, eg, dim3(256), 0, nullptr, s.pay[cur], d_c2c, base, n, L - 1 - l, g0, nw, s.tree, s.pops);
+        // one wave per word: nw * 64 threads, that is four words to a block of 256
+        hipLaunchKernelGGL(int_tree_emit_kernel, launch_grid(nw * 64), dim3(256), 0, nullptr, s.pay[cur].as<uint32_t>(), d_c2c, base, n, L - 1 - l, g0, nw, tree, pops);
         if (l + 1 == L) break;                                         // the last level's bits are all the file needs
-        size_t tb = s.tmp_bytes;
-        VLG_HIP_TRY(rocprim::exclusive_scan(s.tmp, tb, s.pops, s.pops, 0u, nw, rocprim::plus<uint32_t>(), nullptr));
-        hipLaunchKernelGGL(int_tree_split_kernel, int_grid(sigma + 1), dim3(256), 0, nullptr, d_c2c, sigma, L - l, s.split, s.end);
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(int_tree_step_kernel<false>), int_grid(n), dim3(256), 0, nullptr, s.tree, s.pops, base, g0, n, d_C, s.split, s.end,
-                           s.pay[cur], s.first[cur], s.pay[cur ^ 1], s.first[cur ^ 1], s.bad);
+        if (vlg_status st = s.scan_pops(nw)) return st;
+        hipLaunchKernelGGL(int_tree_split_kernel, launch_grid(sigma + 1), dim3(256), 0, nullptr, d_c2c, sigma, L - l, split, end);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(int_tree_step_kernel<false>), launch_grid(n), dim3(256), 0, nullptr, tree, pops, base, g0, n, d_C, split, end,
+                           s.pay[cur].as<uint32_t>(), s.first[cur].as<uint32_t>(), s.pay[cur ^ 1].as<uint32_t>(), s.first[cur ^ 1].as<uint32_t>(), bad_flag);
         VLG_HIP_TRY(hipGetLastError());
         cur ^= 1;
     }
     VLG_HIP_TRY(hipGetLastError());
     uint32_t bad = 0;
-    VLG_HIP_TRY(hipMemcpy(&bad, s.bad, 4, hipMemcpyDeviceToHost));
+    VLG_HIP_TRY(hipMemcpy(&bad, bad_flag, 4, hipMemcpyDeviceToHost));
     if (bad) return fail(VLG_E_INTERNAL, "integer index: the level-wise tree does not agree with the alphabet");
     return VLG_OK;
 }
 
-// decode: the level-wise tree in s.tree -> compact BWT in *bwt (one of s's payload arrays); C and comp2char on the device
-vlg_status int_tree_decode(TreeScratch& s, uint64_t n, uint64_t sigma, uint32_t L, const uint32_t* d_c2c, const uint64_t* d_C, uint32_t** bwt)
+// decode: the level-wise tree in s.tree -> compact BWT in s.pay[*bwt]; C and comp2char on the device
+vlg_status int_tree_decode(TreeScratch& s, uint64_t n, uint64_t sigma, uint32_t L, const uint32_t* d_c2c, const uint64_t* d_C, int* bwt)
 {
-    hipLaunchKernelGGL(int_iota_kernel, int_grid(n), dim3(256), 0, nullptr, s.pay[0], n);
-    VLG_HIP_TRY(hipMemset(s.first[0], 0, n * 4));
+    const uint64_t* tree = s.tree.as<uint64_t>();
+    uint32_t *pops = s.pops.as<uint32_t>(), *split = s.split.as<uint32_t>(), *end = s.end.as<uint32_t>(), *bad_flag = s.bad.as<uint32_t>();
+    hipLaunchKernelGGL(int_iota_kernel, launch_grid(n), dim3(256), 0, nullptr, s.pay[0].as<uint32_t>(), n);
+    VLG_HIP_TRY(hipMemset(s.first[0].p, 0, n * 4));
     int cur = 0;
     for (uint32_t l = 0; l < L; ++l) {
         uint64_t base, g0, nw;
         tree_level_words(n, l, base, g0, nw);
-        hipLaunchKernelGGL(int_tree_pops_kernel, int_grid(nw), dim3(256), 0, nullptr, s.tree, g0, nw, s.pops);
-        size_t tb = s.tmp_bytes;
-        VLG_HIP_TRY(rocprim::exclusive_scan(s.tmp, tb, s.pops, s.pops, 0u, nw, rocprim::plus<uint32_t>(), nullptr));
-        hipLaunchKernelGGL(int_tree_split_kernel, int_grid(sigma + 1), dim3(256), 0, nullptr, d_c2c, sigma, L - l, s.split, s.end);
+        hipLaunchKernelGGL(int_tree_pops_kernel, launch_grid(nw), dim3(256), 0, nullptr, tree, g0, nw, pops);
+        if (vlg_status st = s.scan_pops(nw)) return st;
+        hipLaunchKernelGGL(int_tree_split_kernel, launch_grid(sigma + 1), dim3(256), 0, nullptr, d_c2c, sigma, L - l, split, end);
         if (l + 1 < L)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(int_tree_step_kernel<false>), int_grid(n), dim3(256), 0, nullptr, s.tree, s.pops, base, g0, n, d_C, s.split, s.end,
-                               s.pay[cur], s.first[cur], s.pay[cur ^ 1], s.first[cur ^ 1], s.bad);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(int_tree_step_kernel<false>), launch_grid(n), dim3(256), 0, nullptr, tree, pops, base, g0, n, d_C, split, end,
+                               s.pay[cur].as<uint32_t>(), s.first[cur].as<uint32_t>(), s.pay[cur ^ 1].as<uint32_t>(), s.first[cur ^ 1].as<uint32_t>(), bad_flag);
         else
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(int_tree_step_kernel<true>), int_grid(n), dim3(256), 0, nullptr, s.tree, s.pops, base, g0, n, d_C, s.split, s.end,
-                               s.pay[cur], s.first[cur], s.pay[cur ^ 1], nullptr, s.bad);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(int_tree_step_kernel<true>), launch_grid(n), dim3(256), 0, nullptr, tree, pops, base, g0, n, d_C, split, end,
+                               s.pay[cur].as<uint32_t>(), s.first[cur].as<uint32_t>(), s.pay[cur ^ 1].as<uint32_t>(), (uint32_t*)nullptr, bad_flag);
         VLG_HIP_TRY(hipGetLastError());
         uint32_t bad = 0;                                              // a step that flagged left holes: the next one must not read them
-        VLG_HIP_TRY(hipMemcpy(&bad, s.bad, 4, hipMemcpyDeviceToHost));
+        VLG_HIP_TRY(hipMemcpy(&bad, bad_flag, 4, hipMemcpyDeviceToHost));
         if (bad) return fail(VLG_E_INVALID, "wt_int tree does not agree with the alphabet's C (level " + std::to_string(l) + ")");
         cur ^= 1;
     }
-    *bwt = s.pay[cur];
+    *bwt = cur;
     return VLG_OK;
 }
 
@@ -837,18 +783,13 @@ extern "C" vlg_status vlg_index_export_int_tree(const vlg_index* idx, uint32_t* 
     if (!h_words) return VLG_OK;
     release_cached_device_memory();
     TreeScratch s;
-    auto run = [&]() -> vlg_status {
-        if (vlg_status st = s.alloc(n, sigma, L)) return st;
-        if (v.bv_kind == kBvRrr63) hipLaunchKernelGGL(HIP_KERNEL_NAME(int_bwt_extract_kernel<RrrBV>), int_grid(n), dim3(256), 0, nullptr, v, s.pay[0]);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(int_bwt_extract_kernel<PlainBV>), int_grid(n), dim3(256), 0, nullptr, v, s.pay[0]);
-        VLG_HIP_TRY(hipGetLastError());
-        if (vlg_status st = int_tree_encode(s, n, sigma, L, v.comp2char, v.C)) return st;
-        VLG_HIP_TRY(hipMemcpy(h_words, s.tree, s.words * 8, hipMemcpyDeviceToHost));
-        return VLG_OK;
-    };
-    const vlg_status st = run();
-    s.release();
-    return st;
+    if (vlg_status st = s.alloc(n, sigma, L)) return st;
+    if (v.bv_kind == kBvRrr63) hipLaunchKernelGGL(HIP_KERNEL_NAME(int_bwt_extract_kernel<RrrBV>), launch_grid(n), dim3(256), 0, nullptr, v, s.pay[0].as<uint32_t>());
+    else hipLaunchKernelGGL(HIP_KERNEL_NAME(int_bwt_extract_kernel<PlainBV>), launch_grid(n), dim3(256), 0, nullptr, v, s.pay[0].as<uint32_t>());
+    VLG_HIP_TRY(hipGetLastError());
+    if (vlg_status st = int_tree_encode(s, n, sigma, L, v.comp2char, v.C)) return st;
+    VLG_HIP_TRY(hipMemcpy(h_words, s.tree.p, s.words * 8, hipMemcpyDeviceToHost));
+    return VLG_OK;
 }
 
 extern "C" vlg_status vlg_index_from_int_parts(const vlg_int_index_parts* p, vlg_index** out)
@@ -877,31 +818,25 @@ extern "C" vlg_status vlg_index_from_int_parts(const vlg_int_index_parts* p, vlg
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(VLG_E_NO_DEVICE, "no HIP device available (the VLG library has no CPU fallback)");
     release_cached_device_memory();
-    vlg_index* idx = new vlg_index();
+    IndexPtr idx(new vlg_index());
     TreeScratch s;
-    auto run = [&]() -> vlg_status {
-        if (vlg_status st = int_alloc_blob(idx, n, sigma, p->sa_sample_dens)) return st;
-        const IntHeader& h = idx->ihdr;
-        uint8_t* b = reinterpret_cast<uint8_t*>(idx->d_blob);
-        uint32_t* d_c2c = reinterpret_cast<uint32_t*>(b + h.off_c2c);
-        uint64_t* d_C = reinterpret_cast<uint64_t*>(b + h.off_C);
-        VLG_HIP_TRY(hipMemcpy(d_C, p->C, (sigma + 1) * 8, hipMemcpyHostToDevice));
-        VLG_HIP_TRY(hipMemcpy(d_c2c, c2c.data(), sigma * 4, hipMemcpyHostToDevice));
-        VLG_HIP_TRY(hipMemcpy(b + h.off_samples, smp.data(), p->n_samples * 4, hipMemcpyHostToDevice));
-        if (vlg_status st = s.alloc(n, sigma, L)) return st;
-        VLG_HIP_TRY(hipMemset(s.tree + s.words, 0, 8));
-        VLG_HIP_TRY(hipMemcpy(s.tree, p->tree_words, s.words * 8, hipMemcpyHostToDevice));
-        uint32_t* bwt = nullptr;
-        if (vlg_status st = int_tree_decode(s, n, sigma, L, d_c2c, d_C, &bwt)) return st;
-        // the tree, the tables and the scan go; the four n-word arrays are the matrix builder's scratch
-        for (void* q : {(void*)s.tree, (void*)s.split, (void*)s.end, (void*)s.pops, (void*)s.bad, s.tmp}) (void)hipFree(q);
-        s.tree = nullptr; s.split = s.end = s.pops = s.bad = nullptr; s.tmp = nullptr;
-        uint32_t* other = bwt == s.pay[0] ? s.pay[1] : s.pay[0];
-        return int_matrix_from_bwt(idx, bwt, other, s.first[0], s.first[1], nullptr, 0);
-    };
-    const vlg_status st = run();
-    s.release();
-    if (st) { vlg_index_destroy(idx); return st; }
-    *out = idx;
+    if (vlg_status st = int_alloc_blob(idx.get(), n, sigma, p->sa_sample_dens)) return st;
+    const IntHeader& h = idx->ihdr;
+    uint8_t* b = reinterpret_cast<uint8_t*>(idx->d_blob);
+    uint32_t* d_c2c = reinterpret_cast<uint32_t*>(b + h.off_c2c);
+    uint64_t* d_C = reinterpret_cast<uint64_t*>(b + h.off_C);
+    VLG_HIP_TRY(hipMemcpy(d_C, p->C, (sigma + 1) * 8, hipMemcpyHostToDevice));
+    VLG_HIP_TRY(hipMemcpy(d_c2c, c2c.data(), sigma * 4, hipMemcpyHostToDevice));
+    VLG_HIP_TRY(hipMemcpy(b + h.off_samples, smp.data(), p->n_samples * 4, hipMemcpyHostToDevice));
+    if (vlg_status st = s.alloc(n, sigma, L)) return st;
+    VLG_HIP_TRY(hipMemset(s.tree.as<uint64_t>() + s.words, 0, 8));
+    VLG_HIP_TRY(hipMemcpy(s.tree.p, p->tree_words, s.words * 8, hipMemcpyHostToDevice));
+    int bwt = 0;
+    if (vlg_status st = int_tree_decode(s, n, sigma, L, d_c2c, d_C, &bwt)) return st;
+    // the tree, the tables and the scan go; the four n-word arrays are the matrix builder's scratch
+    for (DevBuf* q : {&s.tree, &s.split, &s.end, &s.pops, &s.bad, &s.tmp}) q->release();
+    if (vlg_status st = int_matrix_from_bwt(idx.get(), s.pay[bwt].as<uint32_t>(), s.pay[bwt ^ 1].as<uint32_t>(), s.first[0].as<uint32_t>(), s.first[1].as<uint32_t>(), s.tmp))
+        return st;
+    *out = idx.release();
     return VLG_OK;
 }

@@ -93,29 +93,21 @@ extern "C" vlg_status vlg_bitvector_create(const uint64_t* h_words, uint64_t nbi
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(VLG_E_NO_DEVICE, "no HIP device available");
     if (nbits >= (1ull << 32)) return fail(VLG_E_UNSUPPORTED, "stand-alone bit-vectors are limited to 2^32-1 bits (32-bit block counts)");
-    vlg_bitvector* bv = new vlg_bitvector();
+    Building<vlg_bitvector, vlg_bitvector_destroy> bv(new vlg_bitvector());
     bv->nbits = nbits;
     bv->n_blocks = nbits / kBlockBits + 1;
     uint64_t words = (nbits + 63) / 64;
-    uint64_t* d_src = nullptr;
-    uint32_t* d_pops = nullptr;
-    auto run = [&]() -> vlg_status {
-        VLG_HIP_TRY(hipMalloc((void**)&bv->d_blocks, bv->n_blocks * sizeof(Block)));
-        VLG_HIP_TRY(hipMalloc((void**)&d_src, words * 8 + 8));
-        VLG_HIP_TRY(hipMalloc((void**)&d_pops, bv->n_blocks * 4));
-        if (words) VLG_HIP_TRY(hipMemcpy(d_src, h_words, words * 8, hipMemcpyHostToDevice));
-        uint32_t grid = (uint32_t)std::min<uint64_t>((bv->n_blocks + 255) / 256, 8192);
-        hipLaunchKernelGGL(bv_pack_kernel, dim3(grid), dim3(256), 0, nullptr, d_src, words, nbits, bv->d_blocks, bv->n_blocks, d_pops);
-        hipLaunchKernelGGL(bv_count_kernel, dim3(1), dim3(1024), 0, nullptr, bv->d_blocks, d_pops, bv->n_blocks);
-        VLG_HIP_TRY(hipGetLastError());
-        VLG_HIP_TRY(hipDeviceSynchronize());
-        return VLG_OK;
-    };
-    vlg_status st = run();
-    if (d_src) (void)hipFree(d_src);
-    if (d_pops) (void)hipFree(d_pops);
-    if (st) { vlg_bitvector_destroy(bv); return st; }
-    *out = bv;
+    DevBuf d_src, d_pops;
+    VLG_HIP_TRY(hipMalloc((void**)&bv->d_blocks, bv->n_blocks * sizeof(Block)));
+    VLG_HIP_TRY(d_src.alloc(words * 8 + 8));
+    VLG_HIP_TRY(d_pops.alloc(bv->n_blocks * 4));
+    if (words) VLG_HIP_TRY(hipMemcpy(d_src.p, h_words, words * 8, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(bv_pack_kernel, launch_grid(bv->n_blocks, 8192), dim3(256), 0, nullptr, d_src.as<uint64_t>(), words, nbits, bv->d_blocks, bv->n_blocks,
+                       d_pops.as<uint32_t>());
+    hipLaunchKernelGGL(bv_count_kernel, dim3(1), dim3(1024), 0, nullptr, bv->d_blocks, d_pops.as<uint32_t>(), bv->n_blocks);
+    VLG_HIP_TRY(hipGetLastError());
+    VLG_HIP_TRY(hipDeviceSynchronize());
+    *out = bv.release();
     return VLG_OK;
 }
 
@@ -123,8 +115,7 @@ extern "C" vlg_status vlg_bitvector_rank_batch(const vlg_bitvector* bv, const ui
 {
     if (!bv || (count && (!d_idx || !d_out))) return fail(VLG_E_INVALID, "null argument");
     if (!count) return VLG_OK;
-    uint32_t grid = (uint32_t)std::min<uint64_t>((count + 255) / 256, 256 * 32);
-    hipLaunchKernelGGL(bitrank_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, bv->d_blocks, d_idx, d_out, count);
+    hipLaunchKernelGGL(bitrank_kernel, launch_grid(count, 8192), dim3(256), 0, (hipStream_t)stream, bv->d_blocks, d_idx, d_out, count);
     VLG_HIP_TRY(hipGetLastError());
     return VLG_OK;
 }
@@ -312,8 +303,7 @@ extern "C" vlg_status vlg_rrr_bitvector_rank_batch(const vlg_rrr_bitvector* bv, 
 {
     if (!bv || (count && (!d_idx || !d_out))) return fail(VLG_E_INVALID, "null argument");
     if (!count) return VLG_OK;
-    uint32_t grid = (uint32_t)std::min<uint64_t>((count + 255) / 256, 256 * 8);
-    hipLaunchKernelGGL(rrr_rank_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, bv->d_hdr, bv->d_stream, bv->d_binom, d_idx, d_out,
+    hipLaunchKernelGGL(rrr_rank_kernel, launch_grid(count, 2048), dim3(256), 0, (hipStream_t)stream, bv->d_hdr, bv->d_stream, bv->d_binom, d_idx, d_out,
                        count);
     VLG_HIP_TRY(hipGetLastError());
     return VLG_OK;
@@ -928,8 +918,6 @@ template <bool kWide, bool kTextOrder>
 using ByteSampling = typename std::conditional<kTextOrder, TextOrderSampling<typename std::conditional<kWide, uint64_t, uint32_t>::type>,
                                                SaOrderSampling<typename std::conditional<kWide, uint64_t, uint32_t>::type>>::type;
 
-inline uint32_t grid_for(uint64_t n, uint32_t cap = 16384) { return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, cap)); }
-
 }  // namespace
 
 namespace vlg {
@@ -939,10 +927,10 @@ vlg_status launch_backward_search(const IndexView& iv, const uint8_t* d_blob, co
 {
     if (!n_pat) return VLG_OK;
     if (iv.bv_kind == kBvRrr63)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(backward_search_kernel<RrrBV>), dim3(grid_for(n_pat, 4096)), dim3(256), 0, stream, iv, d_blob, d_off,
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(backward_search_kernel<RrrBV>), launch_grid(n_pat, 4096), dim3(256), 0, stream, iv, d_blob, d_off,
                            n_pat, d_l, d_r, d_stat_levels);
     else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(backward_search_kernel<PlainBV>), dim3(grid_for(n_pat, 4096)), dim3(256), 0, stream, iv, d_blob, d_off,
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(backward_search_kernel<PlainBV>), launch_grid(n_pat, 4096), dim3(256), 0, stream, iv, d_blob, d_off,
                            n_pat, d_l, d_r, d_stat_levels);
     VLG_HIP_TRY(hipGetLastError());
     return VLG_OK;
@@ -953,7 +941,7 @@ vlg_status launch_expand(const uint64_t* d_l, const uint64_t* d_out_off, uint64_
                          hipStream_t stream)
 {
     if (!total) return VLG_OK;
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(expand_kernel<pos_t>), dim3(grid_for(total, 32768)), dim3(256), 0, stream, d_l, d_out_off, n_pat,
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(expand_kernel<pos_t>), launch_grid(total, 32768), dim3(256), 0, stream, d_l, d_out_off, n_pat,
                        total, d_io, d_seg);
     VLG_HIP_TRY(hipGetLastError());
     return VLG_OK;
@@ -1021,7 +1009,7 @@ vlg_status run_locate_sweep(const SweepKernels& K, const uint64_t* d_l, const ui
     if (member) {
         if (total > 0xFFFFFF00ull) return fail(VLG_E_INTERNAL, "member bit-vector: slots need 32 bits");
         if (timer) timer->begin(0);
-        hipLaunchKernelGGL(member_build_kernel, dim3(grid_for(member_blocks(K.n), 16384)), dim3(256), 0, stream, d_l, d_out_off, n_member_lists,
+        hipLaunchKernelGGL(member_build_kernel, launch_grid(member_blocks(K.n), 16384), dim3(256), 0, stream, d_l, d_out_off, n_member_lists,
                            member_blocks(K.n), member);
         if (timer) timer->end(0);
         VLG_HIP_TRY(hipGetLastError());
@@ -1039,7 +1027,7 @@ vlg_status run_locate_sweep(const SweepKernels& K, const uint64_t* d_l, const ui
         static const bool ahead = [] { const char* e = getenv("VLG_SWEEP_LOOKAHEAD"); return !(e && e[0] == '0'); }();
         if (!fused_first) {
             if (member) VLG_HIP_TRY(hipMemsetAsync(rec + t0, 0xFF, (t1 - t0) * 8, stream));     // "still walking" (the first-round kernel writes it itself)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(sweep_init_kernel<kShift>), dim3(grid_for((t1 - t0 + 7) / 8, 32768)), dim3(256), 0, stream, d_l, d_out_off, n_pat,
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(sweep_init_kernel<kShift>), launch_grid((t1 - t0 + 7) / 8, 32768), dim3(256), 0, stream, d_l, d_out_off, n_pat,
                                t0, t1, val_a);
         }
         VLG_HIP_TRY(hipGetLastError());
@@ -1125,7 +1113,7 @@ vlg_status launch_locate_sweep(const IndexView& iv, const uint64_t* d_l, const u
     if (iv.dens == 1 && !text_order && total) {                  // every SA index is sampled: no walk, no trails, no records
         using sample_t = typename std::conditional<kWide, uint64_t, uint32_t>::type;
         if (timer) timer->begin(0);
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(sa_dense_copy_kernel<pos_t, sample_t>), dim3(grid_for((total + 7) / 8, 32768)), dim3(256), 0, stream,
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(sa_dense_copy_kernel<pos_t, sample_t>), launch_grid((total + 7) / 8, 32768), dim3(256), 0, stream,
                            reinterpret_cast<const sample_t*>(iv.samples), d_l, d_out_off, n_pat, total, d_out);
         if (timer) timer->end(0);
         VLG_HIP_TRY(hipGetLastError());
@@ -1141,7 +1129,7 @@ vlg_status launch_locate_sweep(const IndexView& iv, const uint64_t* d_l, const u
                   uint32_t* chunk_list) {
         pos_t* out = static_cast<pos_t*>(out_);
         launch_sweep_chunk_lists(d_out_off, n_pat, t0, t1, chunk_list, stream);
-        const dim3 grid_first(grid_for((t1 - t0 + 7) / 8, 8192));
+        const dim3 grid_first = launch_grid((t1 - t0 + 7) / 8, 8192);
 #define VLG_FIRST(BV, TR, TO) do { if (ahead) hipLaunchKernelGGL(HIP_KERNEL_NAME(sweep_first_kernel<ByteWalk<BV, kWide>, ByteSampling<kWide, TO>, pos_t, TR, kWide, TR>), grid_first, dim3(256), 0, stream, iv, d_l, d_out_off, n_pat, t0, t1, val, key, out, d_stats, counter, mem, rc, chunk_list, fr); \
                                     else hipLaunchKernelGGL(HIP_KERNEL_NAME(sweep_first_kernel<ByteWalk<BV, kWide>, ByteSampling<kWide, TO>, pos_t, TR, kWide, false>), grid_first, dim3(256), 0, stream, iv, d_l, d_out_off, n_pat, t0, t1, val, key, out, d_stats, counter, mem, rc, chunk_list, fr); } while (0)
 #define VLG_FIRST_BV(TR, TO) do { if (rrr) VLG_FIRST(RrrBV, TR, TO); else VLG_FIRST(PlainBV, TR, TO); } while (0)
@@ -1152,7 +1140,7 @@ vlg_status launch_locate_sweep(const IndexView& iv, const uint64_t* d_l, const u
     };
     K.step = [&](uint64_t* val, uint16_t* key, uint64_t alive, uint32_t step, void* out_, unsigned long long* counter, const Block* mem, uint64_t* rc, uint64_t t0, bool probed) {
         pos_t* out = static_cast<pos_t*>(out_);
-        const dim3 grid(grid_for(alive, 4096));
+        const dim3 grid = launch_grid(alive, 4096);
 #define VLG_STEP(BV, TR, TO) hipLaunchKernelGGL(HIP_KERNEL_NAME(sweep_step_kernel<ByteWalk<BV, kWide>, ByteSampling<kWide, TO>, pos_t, TR, kWide>), grid, dim3(256), 0, stream, iv, val, key, alive, step, out, d_stats, counter, mem, rc, t0, probed)
 #define VLG_STEP_BV(TR, TO) do { if (rrr) VLG_STEP(RrrBV, TR, TO); else VLG_STEP(PlainBV, TR, TO); } while (0)
         if (text_order) { if (mem) VLG_STEP_BV(true, true); else VLG_STEP_BV(false, true); }
@@ -1194,7 +1182,7 @@ vlg_status launch_unsample(const IndexView& iv, const uint64_t* d_l, const uint6
     while (alive > tail_threshold) {
         for (uint32_t r = 0; r < kUnsampleSync; ++r, ++round) {
             if (timer) timer->begin(0);
-            const dim3 grid(grid_for(alive, 8192));
+            const dim3 grid = launch_grid(alive, 8192);
 #define VLG_UNS(BV) do { if (round == 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(unsample_step_kernel<BV, kWide, true>), grid, dim3(256), 0, stream, iv, val_a, key_a, alive, sa_full, d_stats, d_counter); \
                          else hipLaunchKernelGGL(HIP_KERNEL_NAME(unsample_step_kernel<BV, kWide, false>), grid, dim3(256), 0, stream, iv, val_a, key_a, alive, sa_full, d_stats, d_counter); } while (0)
             if (rrr) VLG_UNS(RrrBV); else VLG_UNS(PlainBV);
@@ -1222,7 +1210,7 @@ vlg_status launch_unsample(const IndexView& iv, const uint64_t* d_l, const uint6
     if (round == 0 && iv.n_samples) {
         // too few walkers for a single sorted round: round 0 still makes their words (and writes the samples themselves)
         if (timer) timer->begin(0);
-        const dim3 grid(grid_for(alive, 8192));
+        const dim3 grid = launch_grid(alive, 8192);
         if (rrr) hipLaunchKernelGGL(HIP_KERNEL_NAME(unsample_step_kernel<RrrBV, kWide, true>), grid, dim3(256), 0, stream, iv, val_a, key_a, alive, sa_full, d_stats, d_counter);
         else hipLaunchKernelGGL(HIP_KERNEL_NAME(unsample_step_kernel<PlainBV, kWide, true>), grid, dim3(256), 0, stream, iv, val_a, key_a, alive, sa_full, d_stats, d_counter);
         if (timer) timer->end(0);
@@ -1243,7 +1231,7 @@ vlg_status launch_unsample(const IndexView& iv, const uint64_t* d_l, const uint6
     }
     if (total) {
         if (timer) timer->begin(0);
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(sa_dense_copy_kernel<uint32_t, uint32_t>), dim3(grid_for((total + 7) / 8, 32768)), dim3(256), 0, stream,
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(sa_dense_copy_kernel<uint32_t, uint32_t>), launch_grid((total + 7) / 8, 32768), dim3(256), 0, stream,
                            sa_full, d_l, d_out_off, n_pat, total, d_out);
         if (timer) timer->end(0);
         VLG_HIP_TRY(hipGetLastError());
@@ -1262,7 +1250,7 @@ vlg_status launch_sa_dense_copy(const uint32_t* sa, const uint64_t* d_l, const u
                                 hipStream_t stream)
 {
     if (!total) return VLG_OK;
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(sa_dense_copy_kernel<uint32_t, uint32_t>), dim3(grid_for((total + 7) / 8, 32768)), dim3(256), 0, stream,
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(sa_dense_copy_kernel<uint32_t, uint32_t>), launch_grid((total + 7) / 8, 32768), dim3(256), 0, stream,
                        sa, d_l, d_out_off, n_pat, total, d_out);
     VLG_HIP_TRY(hipGetLastError());
     return VLG_OK;
@@ -1282,7 +1270,7 @@ template <typename T>
 vlg_status launch_narrow(const uint64_t* d_in, T* d_out, uint64_t count, hipStream_t stream)
 {
     if (!count) return VLG_OK;
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(narrow_kernel<T>), dim3(grid_for(count)), dim3(256), 0, stream, d_in, d_out, count);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(narrow_kernel<T>), launch_grid(count), dim3(256), 0, stream, d_in, d_out, count);
     VLG_HIP_TRY(hipGetLastError());
     return VLG_OK;
 }
@@ -1291,7 +1279,7 @@ template <typename T>
 vlg_status launch_widen(const T* d_in, uint64_t* d_out, uint64_t count, hipStream_t stream)
 {
     if (!count) return VLG_OK;
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(widen_kernel<T>), dim3(grid_for(count)), dim3(256), 0, stream, d_in, d_out, count);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(widen_kernel<T>), launch_grid(count), dim3(256), 0, stream, d_in, d_out, count);
     VLG_HIP_TRY(hipGetLastError());
     return VLG_OK;
 }
@@ -1312,10 +1300,10 @@ extern "C" vlg_status vlg_wt_rank_batch(const vlg_index* idx, const uint64_t* d_
     if (idx->is_int) return fail(VLG_E_INVALID, "integer-alphabet index: use vlg_int_rank_batch");
     if (!count) return VLG_OK;
     if (idx->view.bv_kind == kBvRrr63)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(wt_rank_kernel<RrrBV>), dim3(grid_for(count, 8192)), dim3(256), 0, (hipStream_t)stream, idx->view, d_i, d_c,
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(wt_rank_kernel<RrrBV>), launch_grid(count, 8192), dim3(256), 0, (hipStream_t)stream, idx->view, d_i, d_c,
                            d_out, count);
     else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(wt_rank_kernel<PlainBV>), dim3(grid_for(count, 8192)), dim3(256), 0, (hipStream_t)stream, idx->view, d_i,
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(wt_rank_kernel<PlainBV>), launch_grid(count, 8192), dim3(256), 0, (hipStream_t)stream, idx->view, d_i,
                            d_c, d_out, count);
     VLG_HIP_TRY(hipGetLastError());
     return VLG_OK;
@@ -1339,13 +1327,13 @@ extern "C" vlg_status vlg_sa_batch(const vlg_index* idx, const uint64_t* d_i, ui
         if (d_out != d_i) VLG_HIP_TRY(hipMemcpyAsync(d_out, d_i, count * 8, hipMemcpyDeviceToDevice, st));
         return launch_locate<uint64_t>(idx->view, d_out, count, nullptr, st);
     }
-    uint32_t* tmp = nullptr;
-    VLG_HIP_TRY(hipMalloc((void**)&tmp, count * 4));
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(narrow_kernel<uint32_t>), dim3(grid_for(count)), dim3(256), 0, st, d_i, tmp, count);
+    DevBuf tmp_buf;
+    VLG_HIP_TRY(tmp_buf.alloc(count * 4));
+    uint32_t* tmp = tmp_buf.as<uint32_t>();
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(narrow_kernel<uint32_t>), launch_grid(count), dim3(256), 0, st, d_i, tmp, count);
     vlg_status s2 = idx->is_int ? launch_int_locate(idx->iview, tmp, count, nullptr, st) : launch_locate<uint32_t>(idx->view, tmp, count, nullptr, st);
-    if (!s2) hipLaunchKernelGGL(HIP_KERNEL_NAME(widen_kernel<uint32_t>), dim3(grid_for(count)), dim3(256), 0, st, tmp, d_out, count);
-    hipError_t e = hipStreamSynchronize(st);
-    (void)hipFree(tmp);
+    if (!s2) hipLaunchKernelGGL(HIP_KERNEL_NAME(widen_kernel<uint32_t>), launch_grid(count), dim3(256), 0, st, tmp, d_out, count);
+    hipError_t e = hipStreamSynchronize(st);                      // (before tmp goes)
     if (s2) return s2;
     VLG_HIP_TRY(e);
     return VLG_OK;
@@ -1362,13 +1350,13 @@ extern "C" vlg_status vlg_locate_batch(const vlg_index* idx, const uint64_t* d_l
         if (vlg_status s = launch_expand<uint64_t>(d_l, d_out_off, n_patterns, total, d_out, nullptr, st)) return s;
         return launch_locate<uint64_t>(idx->view, d_out, total, nullptr, st);
     }
-    uint32_t* tmp = nullptr;
-    VLG_HIP_TRY(hipMalloc((void**)&tmp, total * 4));
+    DevBuf tmp_buf;
+    VLG_HIP_TRY(tmp_buf.alloc(total * 4));
+    uint32_t* tmp = tmp_buf.as<uint32_t>();
     vlg_status s2 = launch_expand<uint32_t>(d_l, d_out_off, n_patterns, total, tmp, nullptr, st);
     if (!s2) s2 = idx->is_int ? launch_int_locate(idx->iview, tmp, total, nullptr, st) : launch_locate<uint32_t>(idx->view, tmp, total, nullptr, st);
-    if (!s2) hipLaunchKernelGGL(HIP_KERNEL_NAME(widen_kernel<uint32_t>), dim3(grid_for(total)), dim3(256), 0, st, tmp, d_out, total);
-    hipError_t e = hipStreamSynchronize(st);
-    (void)hipFree(tmp);
+    if (!s2) hipLaunchKernelGGL(HIP_KERNEL_NAME(widen_kernel<uint32_t>), launch_grid(total), dim3(256), 0, st, tmp, d_out, total);
+    hipError_t e = hipStreamSynchronize(st);                      // (before tmp goes)
     if (s2) return s2;
     VLG_HIP_TRY(e);
     return VLG_OK;
@@ -1385,7 +1373,7 @@ vlg_status isa_samples_device(const vlg_index* idx, uint32_t inv_dens, void* d_o
     VLG_HIP_TRY(hipMemsetAsync(d_out, 0, count * w, st));
     if (idx->is_int)                                               // the walk on the wavelet matrix (int_index.hpp), plain or rrr levels
         return launch_int_isa_samples(idx->iview, inv_dens, (uint32_t*)d_out, st);
-    const dim3 grid(grid_for(idx->view.n_samples, 8192));
+    const dim3 grid = launch_grid(idx->view.n_samples, 8192);
     const bool rrr = idx->view.bv_kind == kBvRrr63, wide = idx->hdr.sample_bytes == 8;
 #define VLG_ISA_SAMPLES(BV_, POS_, OUT_) \
     hipLaunchKernelGGL(HIP_KERNEL_NAME(isa_samples_kernel<BV_, POS_, OUT_>), grid, dim3(256), 0, st, idx->view, inv_dens, (OUT_*)d_out)
@@ -1413,14 +1401,14 @@ extern "C" vlg_status vlg_index_isa_samples(const vlg_index* idx, uint32_t inv_d
     if (count != (n - 1) / inv_dens + 1) return fail(VLG_E_INVALID, "ISA sample count must be (n-1)/inv_dens + 1");
     if (idx->hdr.sampling != kSamplingSaOrder) return fail(VLG_E_UNSUPPORTED, "ISA samples are computed from an SA-order index");
     const uint32_t w = isa_sample_bytes(n);
-    uint64_t* d_out = nullptr;
-    VLG_HIP_TRY(hipMalloc((void**)&d_out, count * (8 + w)));          // the samples as the device keeps them, then widened
+    DevBuf out_buf;
+    VLG_HIP_TRY(out_buf.alloc(count * (8 + w)));                      // the samples as the device keeps them, then widened
+    uint64_t* d_out = out_buf.as<uint64_t>();
     void* d_smp = d_out + count;
     vlg_status s = isa_samples_device(idx, inv_dens, d_smp, nullptr);
     if (!s) s = w == 8 ? (hipMemcpyAsync(d_out, d_smp, count * 8, hipMemcpyDeviceToDevice, nullptr) == hipSuccess ? VLG_OK : VLG_E_NO_DEVICE)
                        : launch_widen<uint32_t>((const uint32_t*)d_smp, d_out, count, nullptr);
     hipError_t e = s ? hipSuccess : hipMemcpy(h_out, d_out, count * 8, hipMemcpyDeviceToHost);
-    (void)hipFree(d_out);
     if (s) return s == VLG_E_NO_DEVICE ? fail(s, "ISA samples: device copy failed") : s;
     VLG_HIP_TRY(e);
     return VLG_OK;
@@ -1487,13 +1475,15 @@ extern "C" vlg_status vlg_extract_batch(const vlg_text_access* t, const uint64_t
     uint64_t* seg = nullptr;
     VLG_HIP_TRY(rocprim::exclusive_scan(nullptr, tb, seg, seg, (uint64_t)0, n_ranges + 1, rocprim::plus<uint64_t>(), st));
     const size_t seg_bytes = align_up((n_ranges + 1) * 8 + 8, 256);
-    VLG_HIP_TRY(hipMalloc((void**)&seg, seg_bytes + tb));
+    DevBuf seg_buf;
+    VLG_HIP_TRY(seg_buf.alloc(seg_bytes + tb));
+    seg = seg_buf.as<uint64_t>();
     unsigned long long* d_bad = reinterpret_cast<unsigned long long*>(seg + n_ranges + 1);
     void* temp = reinterpret_cast<uint8_t*>(seg) + seg_bytes;
     uint64_t h[2] = {0, 0};                                        // bad ranges, segments
     hipError_t e = hipMemsetAsync(d_bad, 0, 8, st);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(extract_check_kernel, dim3(grid_for(n_ranges + 1, 4096)), dim3(256), 0, st, d_begin, d_end, d_out_off, n_ranges, idx->hdr.n,
+        hipLaunchKernelGGL(extract_check_kernel, launch_grid(n_ranges + 1, 4096), dim3(256), 0, st, d_begin, d_end, d_out_off, n_ranges, idx->hdr.n,
                            total, t->d, seg, d_bad);
         e = hipGetLastError();
     }
@@ -1506,7 +1496,7 @@ extern "C" vlg_status vlg_extract_batch(const vlg_text_access* t, const uint64_t
     else if (h[0]) s = fail(VLG_E_INVALID, std::to_string(h[0]) + " extract range(s) with begin > end, end >= n, or output beyond total");
     if (!s) {
         const ExtractJob job{d_begin, d_end, d_out_off, seg, n_ranges, h[1], idx->hdr.n, t->d};
-        const dim3 grid(grid_for(h[1], 8192));
+        const dim3 grid = launch_grid(h[1], 8192);
         if (idx->is_int) s = launch_int_extract(idx->iview, job, (const uint32_t*)t->d_isa, (uint32_t*)d_out, st);
         else {
             const bool rrr = idx->view.bv_kind == kBvRrr63, wide = idx->hdr.sample_bytes == 8, w8 = t->isa_bytes == 8;
@@ -1523,10 +1513,9 @@ extern "C" vlg_status vlg_extract_batch(const vlg_text_access* t, const uint64_t
             e = hipGetLastError();
             if (e != hipSuccess) s = fail(VLG_E_NO_DEVICE, std::string("extract: ") + hipGetErrorString(e));
         }
-        e = hipStreamSynchronize(st);                              // the scratch is freed below
+        e = hipStreamSynchronize(st);                              // the scratch is freed on return
         if (!s && e != hipSuccess) s = fail(VLG_E_NO_DEVICE, std::string("extract: ") + hipGetErrorString(e));
     }
-    (void)hipFree(seg);
     return s;
 }
 
@@ -1536,15 +1525,16 @@ extern "C" vlg_status vlg_isa_batch(const vlg_text_access* t, const uint64_t* d_
     if (!count) return VLG_OK;
     const vlg_index* idx = t->idx;
     hipStream_t st = (hipStream_t)stream;
-    unsigned long long* d_bad = nullptr;
-    VLG_HIP_TRY(hipMalloc((void**)&d_bad, 8));
+    DevBuf bad_buf;
+    VLG_HIP_TRY(bad_buf.alloc(8));
+    unsigned long long* d_bad = bad_buf.as<unsigned long long>();
     unsigned long long h_bad = 0;
     vlg_status s = VLG_OK;
     hipError_t e = hipMemsetAsync(d_bad, 0, 8, st);
     if (e == hipSuccess) {
         if (idx->is_int) s = launch_int_isa(idx->iview, t->d, (const uint32_t*)t->d_isa, d_i, d_out, count, d_bad, st);
         else {
-            const dim3 grid(grid_for(count, 8192));
+            const dim3 grid = launch_grid(count, 8192);
             const bool rrr = idx->view.bv_kind == kBvRrr63, wide = idx->hdr.sample_bytes == 8, w8 = t->isa_bytes == 8;
 #define VLG_ISA(BV_, W_, ISA_) \
     hipLaunchKernelGGL(HIP_KERNEL_NAME(isa_kernel<BV_, W_, ISA_>), grid, dim3(256), 0, st, idx->view, t->d, (const ISA_*)t->d_isa, d_i, d_out, count, d_bad)
@@ -1562,7 +1552,6 @@ extern "C" vlg_status vlg_isa_batch(const vlg_text_access* t, const uint64_t* d_
     if (e == hipSuccess && !s) e = hipMemcpyAsync(&h_bad, d_bad, 8, hipMemcpyDeviceToHost, st);
     const hipError_t e2 = hipStreamSynchronize(st);
     if (e == hipSuccess) e = e2;
-    (void)hipFree(d_bad);
     if (s) return s;
     if (e != hipSuccess) return fail(VLG_E_NO_DEVICE, std::string("isa: ") + hipGetErrorString(e));
     if (h_bad) return fail(VLG_E_INVALID, std::to_string(h_bad) + " ISA position(s) >= n");

@@ -581,8 +581,6 @@ namespace {
 
 inline uint32_t runs_grid(uint64_t slots, uint32_t run = kRun) { return (uint32_t)((((slots + run - 1) / run) + 3) / 4); }   // 4 waves per workgroup
 
-inline uint32_t grid_for(uint64_t n, uint32_t cap = 16384) { return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, cap)); }
-
 // Host loops over the queries (or sub-patterns) of a big batch, cut into slices for a few threads: fn(begin, end, thread).
 // Batches below 2 x min_per_thread items run on the caller's thread.
 constexpr uint32_t kHostThreads = 8;
@@ -1049,11 +1047,11 @@ struct PhysicalPass {
             uint64_t* ka = reinterpret_cast<uint64_t*>(scratch);
             uint64_t* kb = ka + acc;
             Timed t(ws, KS_SORT, 2ull * acc * sizeof(pos_t));
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(sort_compose_kernel<pos_t>), dim3(grid_for((acc + 7) / 8, 32768)), dim3(256), 0, st, Pa, d_off64, (uint64_t)nd, acc, bits, ka);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(sort_compose_kernel<pos_t>), launch_grid((acc + 7) / 8, 32768), dim3(256), 0, st, Pa, d_off64, (uint64_t)nd, acc, bits, ka);
             rocprim::double_buffer<uint64_t> keys(ka, kb);
             size_t tb = cp.sort_tmp;
             VLG_HIP_TRY(rocprim::radix_sort_keys(d_tmp, tb, keys, acc, 0, bits + list_bits, st));
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(sort_narrow_kernel<pos_t>), dim3(grid_for(acc, 32768)), dim3(256), 0, st, keys.current(), acc, bits, Pa);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(sort_narrow_kernel<pos_t>), launch_grid(acc, 32768), dim3(256), 0, st, keys.current(), acc, bits, Pa);
             VLG_HIP_TRY(hipGetLastError());
         } else {
             Timed t(ws, KS_SORT, 2ull * acc * sizeof(pos_t));
@@ -1136,13 +1134,13 @@ struct PhysicalPass {
         if (nr_) VLG_HIP_TRY(hipMemcpyAsync(d_r_src, r_src.data(), nr_ * 8, hipMemcpyHostToDevice, st));
         VLG_HIP_TRY(hipMemcpyAsync(d_r_dst, r_dst.data(), (nr_ + 1) * 8, hipMemcpyHostToDevice, st));
         Timed t(ws, KS_EXCHANGE, r_at * sizeof(pos_t));
-        if (s_at) hipLaunchKernelGGL(HIP_KERNEL_NAME(segments_copy_kernel<pos_t, true>), dim3(grid_for((s_at + 7) / 8, 16384)), dim3(256), 0, st, Pg, d_send, d_s_src, d_s_dst, ns, s_at);
+        if (s_at) hipLaunchKernelGGL(HIP_KERNEL_NAME(segments_copy_kernel<pos_t, true>), launch_grid((s_at + 7) / 8, 16384), dim3(256), 0, st, Pg, d_send, d_s_src, d_s_dst, ns, s_at);
         VLG_HIP_TRY(hipGetLastError());
         int rc = 0;
         if (ws->x_a2a) rc = ws->x_a2a(ws->x_ctx, d_send, scount.data(), d_recv, rcount.data(), (uint32_t)sizeof(pos_t), n, me, st);
         else rc = (int)vlg_comm_alltoallv(ws->x_comm, d_send, scount.data(), d_recv, rcount.data(), (uint32_t)sizeof(pos_t), st);
         if (rc) return ws->x_a2a ? fail(VLG_E_INTERNAL, "the exchange callback failed with code " + std::to_string(rc)) : (vlg_status)rc;
-        if (r_at) hipLaunchKernelGGL(HIP_KERNEL_NAME(segments_copy_kernel<pos_t, false>), dim3(grid_for((r_at + 7) / 8, 16384)), dim3(256), 0, st, Pg, d_recv, d_r_src, d_r_dst, nr_, r_at);
+        if (r_at) hipLaunchKernelGGL(HIP_KERNEL_NAME(segments_copy_kernel<pos_t, false>), launch_grid((r_at + 7) / 8, 16384), dim3(256), 0, st, Pg, d_recv, d_r_src, d_r_dst, nr_, r_at);
         VLG_HIP_TRY(hipGetLastError());
         return VLG_OK;
     }
@@ -1158,7 +1156,7 @@ struct PhysicalPass {
         unsigned long long flags[2] = {0, 0};
         VLG_HIP_TRY(hipMemsetAsync(d_flags, 0, 16, st));
         const uint64_t n = all ? gacc : acc;
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(lists_check_kernel<pos_t>), dim3(grid_for((n + 7) / 8, 8192)), dim3(256), 0, st, pairwise ? Pa : L.P, all ? d_goff64 : d_off64,
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(lists_check_kernel<pos_t>), launch_grid((n + 7) / 8, 8192), dim3(256), 0, st, pairwise ? Pa : L.P, all ? d_goff64 : d_off64,
                            (uint64_t)(all ? gnd : nd), n, d_flags);
         VLG_HIP_TRY(hipGetLastError());
         VLG_HIP_TRY(hipMemcpyAsync(flags, d_flags, 16, hipMemcpyDeviceToHost, st));
@@ -1191,7 +1189,7 @@ struct PhysicalPass {
                 fences_written = kRungsHoldFences && rl.levels >= 6 / kRungShift;      // the fences are one of its levels: written on the way
                 {
                     Timed t(ws, KS_FILTER_LADDER, gacc * sizeof(pos_t));
-                    hipLaunchKernelGGL(HIP_KERNEL_NAME(rung_build_kernel<pos_t>), dim3(grid_for(gacc >> kRungShift, 16384)), dim3(256), 0, st, L.P, gacc, R, d_off,
+                    hipLaunchKernelGGL(HIP_KERNEL_NAME(rung_build_kernel<pos_t>), launch_grid(gacc >> kRungShift, 16384), dim3(256), 0, st, L.P, gacc, R, d_off,
                                        rl.levels, fences_written ? L.F : (pos_t*)nullptr);
                 }
                 VLG_HIP_TRY(hipGetLastError());
@@ -1200,7 +1198,7 @@ struct PhysicalPass {
             }
         }
         if (L.F && !fences_written && gacc >= 64) {
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(fence_build_kernel<pos_t>), dim3(grid_for(gacc / 64, 8192)), dim3(256), 0, st, L.P, (uint64_t)0, gacc / 64, L.F);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(fence_build_kernel<pos_t>), launch_grid(gacc / 64, 8192), dim3(256), 0, st, L.P, (uint64_t)0, gacc / 64, L.F);
             VLG_HIP_TRY(hipGetLastError());
         }
         return VLG_OK;
@@ -1307,7 +1305,7 @@ vlg_status run_join_chunk(const vlg_queries* q, vlg_workspace* ws, vlg_result* r
         // fences of the survivors' lists: whole blocks of [Pc, Pc + pc_total) (Pc starts on a block)
         if (L.F && pc_total >= 64) {
             const uint64_t g0 = (uint64_t)(Pc - P) / 64;
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(fence_build_kernel<pos_t>), dim3(grid_for(pc_total / 64, 8192)), dim3(256), 0, st, P, g0, g0 + pc_total / 64, L.F);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(fence_build_kernel<pos_t>), launch_grid(pc_total / 64, 8192), dim3(256), 0, st, P, g0, g0 + pc_total / 64, L.F);
         }
         VLG_HIP_TRY(hipGetLastError());
     }
@@ -1451,7 +1449,7 @@ vlg_status run_join_chunk(const vlg_queries* q, vlg_workspace* ws, vlg_result* r
         uint64_t w0 = b0 >> 6, w1 = (b1 + 63) >> 6;                          // word range written at the level below
         for (uint32_t l = 1; l < kBitLevels; ++l) {
             w0 >>= 6; w1 = (w1 + 63) >> 6;
-            hipLaunchKernelGGL(bits_summary_kernel, dim3(grid_for(w1 - w0, 4096)), dim3(256), 0, st, fb.lvl[l - 1], fb.words[l - 1], w0, w1, lvl_ptr[l]);
+            hipLaunchKernelGGL(bits_summary_kernel, launch_grid(w1 - w0, 4096), dim3(256), 0, st, fb.lvl[l - 1], fb.words[l - 1], w0, w1, lvl_ptr[l]);
         }
         VLG_HIP_TRY(hipGetLastError());
         return VLG_OK;
@@ -1970,16 +1968,16 @@ vlg_status plan_on_device(const vlg_queries* q, vlg_workspace* ws, const uint64_
     uint32_t* d_flags = (uint32_t*)(mem + bytes - 256);          // [0] overflow, [2..3] sum of the list lengths
     auto run = [&]() -> vlg_status {
         VLG_HIP_TRY(hipMemsetAsync(d_flags, 0, 16, st));
-        hipLaunchKernelGGL(interval_keys_kernel, dim3(grid_for(nq, 2048)), dim3(256), 0, st, d_l, d_r, q->d_qsub, nq, kbits, keys_a, sub_a, d_flags);
+        hipLaunchKernelGGL(interval_keys_kernel, launch_grid(nq, 2048), dim3(256), 0, st, d_l, d_r, q->d_qsub, nq, kbits, keys_a, sub_a, d_flags);
         rocprim::double_buffer<uint64_t> dk(keys_a, keys_b);
         rocprim::double_buffer<uint32_t> dv(sub_a, sub_b);
         size_t tb = sort_tb;
         VLG_HIP_TRY(rocprim::radix_sort_pairs(d_tmp, tb, dk, dv, nsub, 0, 64, st));
-        hipLaunchKernelGGL(interval_heads_kernel, dim3(grid_for(nsub, 2048)), dim3(256), 0, st, dk.current(), nsub, d_head);
+        hipLaunchKernelGGL(interval_heads_kernel, launch_grid(nsub, 2048), dim3(256), 0, st, dk.current(), nsub, d_head);
         tb = scan_tb;
         VLG_HIP_TRY(rocprim::inclusive_scan(d_tmp, tb, d_head, d_gid, nsub, rocprim::plus<uint32_t>(), st));
         uint64_t* d_occ = dk.alternate();                        // the sort's other key buffer is free now
-        hipLaunchKernelGGL(interval_scatter_kernel, dim3(grid_for(nsub, 2048)), dim3(256), 0, st, dk.current(), dv.current(), d_gid, nsub, kbits, d_did,
+        hipLaunchKernelGGL(interval_scatter_kernel, launch_grid(nsub, 2048), dim3(256), 0, st, dk.current(), dv.current(), d_gid, nsub, kbits, d_did,
                            d_occ, d_dl, d_docc, reinterpret_cast<unsigned long long*>(d_flags + 2));
         VLG_HIP_TRY(hipGetLastError());
         svec<uint32_t> h_flags(5, 0);                            // overflow, -, sum lo, sum hi, distinct intervals
@@ -2319,7 +2317,7 @@ extern "C" vlg_status vlg_join_batch(const uint64_t* d_lists, const uint64_t* h_
             VLG_HIP_TRY(hipMalloc((void**)&d_off_in, (n_lists + 1) * 8));
             hipError_t e = hipMemcpyAsync(d_off_in, off_stage.data(), (n_lists + 1) * 8, hipMemcpyHostToDevice, st);
             if (e == hipSuccess) {
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(lists_check_kernel<uint64_t>), dim3(grid_for((total + 7) / 8, 8192)), dim3(256), 0, st, d_lists, d_off_in, n_lists, total, d_stats + 4);
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(lists_check_kernel<uint64_t>), launch_grid((total + 7) / 8, 8192), dim3(256), 0, st, d_lists, d_off_in, n_lists, total, d_stats + 4);
                 e = hipGetLastError();
             }
             if (e == hipSuccess) e = hipMemcpyAsync(flags, d_stats + 4, sizeof flags, hipMemcpyDeviceToHost, st);
@@ -2340,7 +2338,7 @@ extern "C" vlg_status vlg_join_batch(const uint64_t* d_lists, const uint64_t* h_
         if (total) {
             VLG_HIP_TRY(hipMemcpyAsync(L.P, d_lists, total * 8, hipMemcpyDeviceToDevice, st));
             if (total >= 64)
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(fence_build_kernel<uint64_t>), dim3(grid_for(total / 64, 8192)), dim3(256), 0, st, L.P, (uint64_t)0, total / 64, F);
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(fence_build_kernel<uint64_t>), launch_grid(total / 64, 8192), dim3(256), 0, st, L.P, (uint64_t)0, total / 64, F);
             VLG_HIP_TRY(hipGetLastError());
             L.F = F;
         }

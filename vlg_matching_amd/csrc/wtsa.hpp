@@ -96,6 +96,55 @@ __global__ void wtsa_counts_kernel(Block* __restrict__ blocks, const uint32_t* _
     for (uint64_t b = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; b < nb; b += (uint64_t)gridDim.x * blockDim.x) blocks[b].cnt = before[b];
 }
 
+// An integer text -> the suffix array of its symbols (vlg_wtsa_build, vlg_index_build_int): the text as bytes (above) through the byte
+// sorter, then the suffixes that start on a symbol, in order.  d_sa gets the n_symbols + 1 entries, the sentinel's first.  d_flag:
+// scratch of 5 n_symbols + 1 words, allocated here (after the sort) unless the caller brings a buffer that large.
+vlg_status symbol_suffix_array(const uint32_t* d_text, uint64_t n_symbols, DevBuf& d_flag, DevBuf& d_sa)
+{
+    if (!n_symbols) {                                               // the sentinel's suffix alone
+        VLG_HIP_TRY(d_sa.alloc(4));
+        VLG_HIP_TRY(hipMemset(d_sa.p, 0, 4));
+        return VLG_OK;
+    }
+    const uint64_t byte_len = n_symbols * 5, nb5 = byte_len + 1;
+    DevBuf d_sa5, d_bytes, d_pos, d_tmp;
+    VLG_HIP_TRY(d_sa5.alloc(nb5 * 4));
+    VLG_HIP_TRY(d_bytes.alloc(byte_len));
+    hipLaunchKernelGGL(wtsa_expand_kernel, launch_grid(n_symbols), dim3(256), 0, nullptr, d_text, n_symbols, d_bytes.as<uint8_t>());
+    VLG_HIP_TRY(hipGetLastError());
+    if (vlg_status st = vlg_suffix_array_device(d_bytes.as<uint8_t>(), byte_len, d_sa5.as<uint32_t>(), nullptr)) return st;
+    d_bytes.release();
+    if (d_flag.cap < nb5 * 4) VLG_HIP_TRY(d_flag.alloc(nb5 * 4));
+    VLG_HIP_TRY(d_pos.alloc(nb5 * 4));
+    VLG_HIP_TRY(d_sa.alloc((n_symbols + 1) * 4));
+    hipLaunchKernelGGL(wtsa_aligned_flags_kernel, launch_grid(nb5), dim3(256), 0, nullptr, d_sa5.as<uint32_t>(), nb5, d_flag.as<uint32_t>());
+    VLG_HIP_TRY(with_scratch(d_tmp, [&](void* t, size_t& tb) {
+        return rocprim::exclusive_scan(t, tb, d_flag.as<uint32_t>(), d_pos.as<uint32_t>(), 0u, nb5, rocprim::plus<uint32_t>(), nullptr);
+    }));
+    hipLaunchKernelGGL(wtsa_aligned_compact_kernel, launch_grid(nb5), dim3(256), 0, nullptr, d_sa5.as<uint32_t>(), d_pos.as<uint32_t>(), nb5, d_sa.as<uint32_t>());
+    VLG_HIP_TRY(hipGetLastError());
+    VLG_HIP_TRY(hipDeviceSynchronize());
+    return VLG_OK;
+}
+
+// The count words of one level whose blocks hold their data words and whose ones stand in pops[0, nb) (pops[nb] = 0): pops becomes its
+// exclusive scan -- pops[nb] the ones of the whole level -- and every block gets the ones before it.  scratch: rocPRIM's, grown on demand.
+vlg_status wtsa_level_counts(Block* lb, uint64_t nb, uint32_t* pops, DevBuf& scratch)
+{
+    VLG_HIP_TRY(with_scratch(scratch, [&](void* t, size_t& tb) { return rocprim::exclusive_scan(t, tb, pops, pops, 0u, nb + 1, rocprim::plus<uint32_t>(), nullptr); }));
+    hipLaunchKernelGGL(wtsa_counts_kernel, launch_grid(nb), dim3(256), 0, nullptr, lb, pops, nb);
+    VLG_HIP_TRY(hipGetLastError());
+    return VLG_OK;
+}
+// One level of a wavelet tree (vlg_wtsa_build) or matrix (int_matrix_from_bwt) from its arrangement: bit `bit` of the n values in cur
+// -> the level's blocks, data and count words; pops: nb + 1 words, left as wtsa_level_counts leaves them.
+vlg_status wtsa_emit_level(const uint32_t* cur, uint64_t n, uint32_t bit, Block* lb, uint64_t nb, uint32_t* pops, DevBuf& scratch)
+{
+    VLG_HIP_TRY(hipMemsetAsync(pops, 0, (nb + 1) * 4, nullptr));
+    hipLaunchKernelGGL(wtsa_emit_kernel, launch_grid(nb * 7), dim3(256), 0, nullptr, cur, n, bit, lb, nb, pops);
+    return wtsa_level_counts(lb, nb, pops, scratch);
+}
+
 // ---- the two walks ---------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t level_rank(const WtsaView& w, uint32_t base, uint64_t i) { return (uint32_t)node_rank1(w.blocks, base, i); }
 
@@ -330,6 +379,8 @@ extern "C" void vlg_wtsa_destroy(vlg_wtsa* x)
     delete x;
 }
 
+using WtsaPtr = Building<vlg_wtsa, vlg_wtsa_destroy>;
+
 extern "C" vlg_status vlg_wtsa_build(const void* h_text, uint64_t n_symbols, uint32_t symbol_bytes, vlg_wtsa** out)
 {
     if (!out || (n_symbols && !h_text)) return fail(VLG_E_INVALID, "null argument");
@@ -340,87 +391,52 @@ extern "C" vlg_status vlg_wtsa_build(const void* h_text, uint64_t n_symbols, uin
     const uint64_t byte_len = n_symbols * (symbol_bytes == 1 ? 1 : 5);
     if (byte_len >= 0xFFFFFFF0ull) return fail(VLG_E_UNSUPPORTED, "text too long for the 32-bit suffix array of this index");
     release_cached_device_memory();
-    vlg_wtsa* x = new vlg_wtsa();
+    WtsaPtr x(new vlg_wtsa());
     x->n_text = n_symbols; x->n_vals = n_symbols + 1; x->sym_bytes = symbol_bytes;
     x->levels = std::max(1u, bit_width64(n_symbols));               // values 0..n_symbols
     x->nb = x->n_vals / kBlockBits + 1;
-    uint8_t* d_bytes = nullptr;
-    uint32_t *d_sa = nullptr, *d_a = nullptr, *d_b = nullptr, *d_ka = nullptr, *d_kb = nullptr, *d_pops = nullptr;
-    uint32_t *d_flag = nullptr, *d_pos = nullptr, *d_out = nullptr;        // integer texts: the aligned suffixes (freed below on every path)
-    void *d_tmp = nullptr, *d_scan2 = nullptr;
-    auto grid = [](uint64_t n) { return dim3((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, 16384))); };
-    auto run = [&]() -> vlg_status {
-        VLG_HIP_TRY(hipMalloc(&x->d_text, std::max<uint64_t>(n_symbols * symbol_bytes, 16)));
-        if (n_symbols) VLG_HIP_TRY(hipMemcpy(x->d_text, h_text, n_symbols * symbol_bytes, hipMemcpyHostToDevice));
-        // ---- suffix array of text + sentinel (the sorter of the FM-index builder) -----------------------------------------------------
-        VLG_HIP_TRY(hipMalloc((void**)&d_sa, (byte_len + 1) * 4));
-        if (symbol_bytes == 1) {
-            if (vlg_status st = vlg_suffix_array_device((const uint8_t*)x->d_text, n_symbols, d_sa, nullptr)) return st;
-        } else {
-            VLG_HIP_TRY(hipMalloc((void**)&d_bytes, std::max<uint64_t>(byte_len, 16)));
-            hipLaunchKernelGGL(wtsa_expand_kernel, grid(n_symbols), dim3(256), 0, nullptr, (const uint32_t*)x->d_text, n_symbols, d_bytes);
-            VLG_HIP_TRY(hipGetLastError());
-            if (vlg_status st = vlg_suffix_array_device(d_bytes, byte_len, d_sa, nullptr)) return st;
-            (void)hipFree(d_bytes); d_bytes = nullptr;
-            // the suffixes that start on a symbol, in order
-            const uint64_t nb5 = byte_len + 1;
-            VLG_HIP_TRY(hipMalloc((void**)&d_flag, nb5 * 4));
-            VLG_HIP_TRY(hipMalloc((void**)&d_pos, nb5 * 4));
-            VLG_HIP_TRY(hipMalloc((void**)&d_out, x->n_vals * 4));
-            hipLaunchKernelGGL(wtsa_aligned_flags_kernel, grid(nb5), dim3(256), 0, nullptr, d_sa, nb5, d_flag);
-            size_t tb = 0;
-            VLG_HIP_TRY(rocprim::exclusive_scan(nullptr, tb, d_flag, d_pos, 0u, nb5, rocprim::plus<uint32_t>(), nullptr));
-            VLG_HIP_TRY(hipMalloc(&d_scan2, tb + 16));
-            VLG_HIP_TRY(rocprim::exclusive_scan(d_scan2, tb, d_flag, d_pos, 0u, nb5, rocprim::plus<uint32_t>(), nullptr));
-            hipLaunchKernelGGL(wtsa_aligned_compact_kernel, grid(nb5), dim3(256), 0, nullptr, d_sa, d_pos, nb5, d_out);
-            VLG_HIP_TRY(hipGetLastError());
-            VLG_HIP_TRY(hipDeviceSynchronize());
-            (void)hipFree(d_scan2); d_scan2 = nullptr;
-            (void)hipFree(d_flag); d_flag = nullptr;
-            (void)hipFree(d_pos); d_pos = nullptr;
-            (void)hipFree(d_sa);
-            d_sa = d_out; d_out = nullptr;
+    DevBuf d_text, d_sa, d_blocks, d_a, d_b, d_ka, d_kb, d_pops, d_tmp;
+    VLG_HIP_TRY(d_text.alloc(n_symbols * symbol_bytes));
+    if (n_symbols) VLG_HIP_TRY(hipMemcpy(d_text.p, h_text, n_symbols * symbol_bytes, hipMemcpyHostToDevice));
+    x->d_text = d_text.take();
+    // ---- suffix array of text + sentinel (the sorter of the FM-index builder) -----------------------------------------------------
+    if (symbol_bytes == 1) {
+        VLG_HIP_TRY(d_sa.alloc((n_symbols + 1) * 4));
+        if (vlg_status st = vlg_suffix_array_device((const uint8_t*)x->d_text, n_symbols, d_sa.as<uint32_t>(), nullptr)) return st;
+    } else {
+        DevBuf d_flag;                                              // (the stage allocates it)
+        if (vlg_status st = symbol_suffix_array((const uint32_t*)x->d_text, n_symbols, d_flag, d_sa)) return st;
+    }
+    // ---- the tree, one level at a time: emit the bits of the current arrangement, then sort stably by one more bit of prefix ---------
+    const uint64_t n = x->n_vals;
+    VLG_HIP_TRY(d_blocks.alloc((uint64_t)x->levels * x->nb * sizeof(Block)));
+    x->d_blocks = static_cast<Block*>(d_blocks.take());
+    VLG_HIP_TRY(d_a.alloc(n * 4));
+    VLG_HIP_TRY(d_b.alloc(n * 4));
+    VLG_HIP_TRY(d_ka.alloc(n * 4));
+    VLG_HIP_TRY(d_kb.alloc(n * 4));
+    VLG_HIP_TRY(d_pops.alloc((x->nb + 1) * 4));
+    size_t sort_tb = 0, scan_tb = 0;                                // the larger request of the level loop: no level regrows d_tmp
+    VLG_HIP_TRY(rocprim::radix_sort_pairs(nullptr, sort_tb, d_ka.as<uint32_t>(), d_kb.as<uint32_t>(), d_a.as<uint32_t>(), d_b.as<uint32_t>(), n, 0, 32, nullptr));
+    VLG_HIP_TRY(rocprim::exclusive_scan(nullptr, scan_tb, d_pops.as<uint32_t>(), d_pops.as<uint32_t>(), 0u, x->nb + 1, rocprim::plus<uint32_t>(), nullptr));
+    VLG_HIP_TRY(d_tmp.alloc(std::max(sort_tb, scan_tb)));
+    VLG_HIP_TRY(hipMemcpy(d_a.p, d_sa.p, n * 4, hipMemcpyDeviceToDevice));
+    uint32_t* cur = d_a.as<uint32_t>();
+    uint32_t* other = d_b.as<uint32_t>();
+    for (uint32_t lvl = 0; lvl < x->levels; ++lvl) {
+        const uint32_t bit = x->levels - 1 - lvl;
+        if (vlg_status st = wtsa_emit_level(cur, n, bit, x->d_blocks + (uint64_t)lvl * x->nb, x->nb, d_pops.as<uint32_t>(), d_tmp)) return st;
+        if (lvl + 1 < x->levels) {                              // arrangement of the next level: stable by the top lvl + 1 bits
+            hipLaunchKernelGGL(wtsa_prefix_keys_kernel, launch_grid(n), dim3(256), 0, nullptr, cur, n, bit, d_ka.as<uint32_t>());
+            VLG_HIP_TRY(with_scratch(d_tmp, [&](void* t, size_t& tb) {
+                return rocprim::radix_sort_pairs(t, tb, d_ka.as<uint32_t>(), d_kb.as<uint32_t>(), cur, other, n, 0, lvl + 1, nullptr);
+            }));
+            std::swap(cur, other);
         }
-        // ---- the tree, one level at a time: emit the bits of the current arrangement, then sort stably by one more bit of prefix ---------
-        const uint64_t n = x->n_vals;
-        VLG_HIP_TRY(hipMalloc((void**)&x->d_blocks, (uint64_t)x->levels * x->nb * sizeof(Block)));
-        VLG_HIP_TRY(hipMalloc((void**)&d_a, n * 4));
-        VLG_HIP_TRY(hipMalloc((void**)&d_b, n * 4));
-        VLG_HIP_TRY(hipMalloc((void**)&d_ka, n * 4));
-        VLG_HIP_TRY(hipMalloc((void**)&d_kb, n * 4));
-        VLG_HIP_TRY(hipMalloc((void**)&d_pops, (x->nb + 1) * 4));
-        size_t sort_tb = 0, scan_tb = 0;
-        VLG_HIP_TRY(rocprim::radix_sort_pairs(nullptr, sort_tb, d_ka, d_kb, d_a, d_b, n, 0, 32, nullptr));
-        VLG_HIP_TRY(rocprim::exclusive_scan(nullptr, scan_tb, d_pops, d_pops, 0u, x->nb, rocprim::plus<uint32_t>(), nullptr));
-        VLG_HIP_TRY(hipMalloc(&d_tmp, std::max(sort_tb, scan_tb) + 16));
-        VLG_HIP_TRY(hipMemcpy(d_a, d_sa, n * 4, hipMemcpyDeviceToDevice));
-        uint32_t* cur = d_a;
-        uint32_t* other = d_b;
-        for (uint32_t lvl = 0; lvl < x->levels; ++lvl) {
-            Block* lb = x->d_blocks + (uint64_t)lvl * x->nb;
-            VLG_HIP_TRY(hipMemsetAsync(d_pops, 0, (x->nb + 1) * 4, nullptr));
-            hipLaunchKernelGGL(wtsa_emit_kernel, grid(x->nb * 7), dim3(256), 0, nullptr, cur, n, x->levels - 1 - lvl, lb, x->nb, d_pops);
-            size_t tb = scan_tb;
-            VLG_HIP_TRY(rocprim::exclusive_scan(d_tmp, tb, d_pops, d_pops, 0u, x->nb, rocprim::plus<uint32_t>(), nullptr));
-            hipLaunchKernelGGL(wtsa_counts_kernel, grid(x->nb), dim3(256), 0, nullptr, lb, d_pops, x->nb);
-            VLG_HIP_TRY(hipGetLastError());
-            if (lvl + 1 < x->levels) {                              // arrangement of the next level: stable by the top lvl + 1 bits
-                hipLaunchKernelGGL(wtsa_prefix_keys_kernel, grid(n), dim3(256), 0, nullptr, cur, n, x->levels - 1 - lvl, d_ka);
-                tb = sort_tb;
-                VLG_HIP_TRY(rocprim::radix_sort_pairs(d_tmp, tb, d_ka, d_kb, cur, other, n, 0, lvl + 1, nullptr));
-                std::swap(cur, other);
-            }
-        }
-        if (vlg_status st = wtsa_level_prefix(x)) return st;
-        VLG_HIP_TRY(hipDeviceSynchronize());
-        return VLG_OK;
-    };
-    vlg_status st = run();
-    for (void* p : {(void*)d_bytes, (void*)d_sa, (void*)d_a, (void*)d_b, (void*)d_ka, (void*)d_kb, (void*)d_pops, d_tmp, (void*)d_flag, (void*)d_pos,
-                    (void*)d_out, d_scan2})
-        if (p) (void)hipFree(p);
-    if (st) { vlg_wtsa_destroy(x); return st; }
-    *out = x;
+    }
+    if (vlg_status st = wtsa_level_prefix(x.get())) return st;
+    VLG_HIP_TRY(hipDeviceSynchronize());
+    *out = x.release();
     return VLG_OK;
 }
 
@@ -436,7 +452,7 @@ extern "C" vlg_status vlg_wtsa_sa_batch(const vlg_wtsa* x, const uint64_t* d_i, 
 {
     if (!x || (count && (!d_i || !d_out))) return fail(VLG_E_INVALID, "null argument");
     if (!count) return VLG_OK;
-    hipLaunchKernelGGL(wtsa_sa_kernel, dim3(grid_for(count, 8192)), dim3(256), 0, (hipStream_t)stream, wtsa_view(x), d_i, d_out, count);
+    hipLaunchKernelGGL(wtsa_sa_kernel, launch_grid(count, 8192), dim3(256), 0, (hipStream_t)stream, wtsa_view(x), d_i, d_out, count);
     VLG_HIP_TRY(hipGetLastError());
     return VLG_OK;
 }
@@ -481,13 +497,11 @@ extern "C" vlg_status vlg_wtsa_export_level(const vlg_wtsa* x, uint32_t level, u
     if (!x || !h_words) return fail(VLG_E_INVALID, "null argument");
     if (level >= x->levels) return fail(VLG_E_INVALID, "no such level");
     const uint64_t nw = (x->n_vals + 63) / 64;
-    uint64_t* d = nullptr;
-    VLG_HIP_TRY(hipMalloc((void**)&d, nw * 8));
-    hipLaunchKernelGGL(wtsa_level_words_kernel, dim3(grid_for(nw, 8192)), dim3(256), 0, nullptr, wtsa_view(x), level, d, nw);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpy(h_words, d, nw * 8, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    VLG_HIP_TRY(e);
+    DevBuf d;
+    VLG_HIP_TRY(d.alloc(nw * 8));
+    hipLaunchKernelGGL(wtsa_level_words_kernel, launch_grid(nw, 8192), dim3(256), 0, nullptr, wtsa_view(x), level, d.as<uint64_t>(), nw);
+    VLG_HIP_TRY(hipGetLastError());
+    VLG_HIP_TRY(hipMemcpy(h_words, d.p, nw * 8, hipMemcpyDeviceToHost));
     return VLG_OK;
 }
 
@@ -496,7 +510,7 @@ extern "C" vlg_status vlg_wtsa_range_walk_batch(const vlg_wtsa* x, const uint64_
 {
     if (!x || (count && (!d_l || !d_len || !d_x || !d_out))) return fail(VLG_E_INVALID, "null argument");
     if (!count) return VLG_OK;
-    hipLaunchKernelGGL(wtsa_range_walk_kernel, dim3(grid_for(count, 8192)), dim3(256), 0, (hipStream_t)stream, wtsa_view(x), d_l, d_len, d_x,
+    hipLaunchKernelGGL(wtsa_range_walk_kernel, launch_grid(count, 8192), dim3(256), 0, (hipStream_t)stream, wtsa_view(x), d_l, d_len, d_x,
                        quantile, d_out, count);
     VLG_HIP_TRY(hipGetLastError());
     return VLG_OK;
@@ -507,7 +521,7 @@ vlg_status wtsa_ranges_device(const vlg_wtsa* x, const vlg_queries* q, uint64_t*
 {
     if (q->sym_bytes != x->sym_bytes) return fail(VLG_E_INVALID, "the query batch and the index have different alphabets");
     if (!q->nsub) return VLG_OK;
-    hipLaunchKernelGGL(wtsa_ranges_kernel, dim3(grid_for(q->nsub, 4096)), dim3(256), 0, st, wtsa_view(x), q->d_blob, q->d_suboff, q->nsub, d_sp, d_len);
+    hipLaunchKernelGGL(wtsa_ranges_kernel, launch_grid(q->nsub, 4096), dim3(256), 0, st, wtsa_view(x), q->d_blob, q->d_suboff, q->nsub, d_sp, d_len);
     VLG_HIP_TRY(hipGetLastError());
     return VLG_OK;
 }
@@ -517,16 +531,12 @@ extern "C" vlg_status vlg_wtsa_ranges(const vlg_wtsa* x, const vlg_queries* q, u
 {
     if (!x || !q || (q->nsub && (!h_sp || !h_ep))) return fail(VLG_E_INVALID, "null argument");
     if (!q->nsub) return VLG_OK;
-    uint64_t* d = nullptr;
-    VLG_HIP_TRY(hipMalloc((void**)&d, 2 * q->nsub * 8));
+    DevBuf d;
+    VLG_HIP_TRY(d.alloc(2 * q->nsub * 8));
     std::vector<uint64_t> h(2 * q->nsub);
-    vlg_status s = wtsa_ranges_device(x, q, d, d + q->nsub, (hipStream_t)stream);
-    hipError_t e = hipSuccess;
-    if (!s) e = hipMemcpyAsync(h.data(), d, 2 * q->nsub * 8, hipMemcpyDeviceToHost, (hipStream_t)stream);
-    if (!s && e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
-    (void)hipFree(d);
-    if (s) return s;
-    VLG_HIP_TRY(e);
+    if (vlg_status s = wtsa_ranges_device(x, q, d.as<uint64_t>(), d.as<uint64_t>() + q->nsub, (hipStream_t)stream)) return s;
+    VLG_HIP_TRY(hipMemcpyAsync(h.data(), d.p, 2 * q->nsub * 8, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    VLG_HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     for (uint64_t i = 0; i < q->nsub; ++i) { h_sp[i] = h[i]; h_ep[i] = h[i] + h[q->nsub + i] - 1; }    // sp = ep + 1 when there is no occurrence
     return VLG_OK;
 }
@@ -544,15 +554,15 @@ extern "C" vlg_status vlg_wtsa_search_batch(const vlg_wtsa* x, const vlg_queries
     res->counts.assign(nq, 0);
     res->k.resize(nq);
     for (uint64_t i = 0; i < nq; ++i) res->k[i] = (uint32_t)(q->qsub[i + 1] - q->qsub[i]);
-    uint8_t* d_mem = nullptr;
+    DevBuf d_mem;
     ResultPiece piece;
     piece.q0 = 0; piece.q1 = nq;
     auto run = [&]() -> vlg_status {
         if (!nq) { res->pieces.push_back(piece); return VLG_OK; }
         // device scratch: ranges, gap bounds, query table, counts, checksum
         const uint64_t bytes = (4 * (nsub + 1) + nq + 2) * 8 + (nq + 1) * sizeof(WQuery) + 1024;
-        VLG_HIP_TRY(hipMalloc((void**)&d_mem, bytes));
-        uint64_t* d_sp = (uint64_t*)d_mem;
+        VLG_HIP_TRY(d_mem.alloc(bytes));
+        uint64_t* d_sp = d_mem.as<uint64_t>();
         uint64_t* d_len = d_sp + nsub + 1;
         uint64_t* d_lo = d_len + nsub + 1;
         uint64_t* d_hi = d_lo + nsub + 1;
@@ -581,9 +591,9 @@ extern "C" vlg_status vlg_wtsa_search_batch(const vlg_wtsa* x, const vlg_queries
         // A capped search whose matches fit a scratch buffer at cap per query runs ONCE (the uncapped one counts first, then emits)
         const uint64_t per_query = max_matches * (1 + (ws->tuples ? (uint64_t)kmax : 0)) * 8;
         if (wave && max_matches && max_matches <= (1u << 20) && nq * per_query <= (2ull << 30)) {
-            uint64_t* t_first = nullptr;
-            VLG_HIP_TRY(hipMalloc((void**)&t_first, nq * per_query + 2 * (nq + 1) * 8));
-            struct Free { void* p; ~Free() { (void)hipFree(p); } } free_tmp{t_first};
+            DevBuf d_capped;
+            VLG_HIP_TRY(d_capped.alloc(nq * per_query + 2 * (nq + 1) * 8));
+            uint64_t* t_first = d_capped.as<uint64_t>();
             uint64_t* t_tuples = ws->tuples ? t_first + nq * max_matches : nullptr;
             uint64_t* d_to_first = t_first + nq * per_query / 8;
             uint64_t* d_to_tuple = d_to_first + nq + 1;
@@ -614,7 +624,7 @@ extern "C" vlg_status vlg_wtsa_search_batch(const vlg_wtsa* x, const vlg_queries
                 VLG_HIP_TRY(hipMemcpyAsync(d_to_first, to_first.data(), nq * 8, hipMemcpyHostToDevice, st));
                 VLG_HIP_TRY(hipMemcpyAsync(d_to_tuple, to_tuple.data(), nq * 8, hipMemcpyHostToDevice, st));
                 Timed t(ws, KS_GATHER, 8ull * (M + TV));
-                hipLaunchKernelGGL(wtsa_compact_kernel, dim3(grid_for(nq * max_matches, 8192)), dim3(256), 0, st, d_q, d_to_first, d_to_tuple, d_counts,
+                hipLaunchKernelGGL(wtsa_compact_kernel, launch_grid(nq * max_matches, 8192), dim3(256), 0, st, d_q, d_to_first, d_to_tuple, d_counts,
                                    (uint32_t)nq, max_matches, t_first, TV ? t_tuples : nullptr, static_cast<uint64_t*>(piece.d_first),
                                    static_cast<uint64_t*>(piece.d_tuples));
                 VLG_HIP_TRY(hipGetLastError());
@@ -676,7 +686,6 @@ extern "C" vlg_status vlg_wtsa_search_batch(const vlg_wtsa* x, const vlg_queries
         try { stt = run(); }
         catch (const std::bad_alloc&) { stt = fail(VLG_E_OOM, "out of host memory (pinned staging)"); }
     }
-    if (d_mem) (void)hipFree(d_mem);
     if (stt) { if (piece.d_first && res->pieces.empty()) result_cache().give(piece.d_first, piece.first_bytes);
                if (piece.d_tuples && res->pieces.empty()) result_cache().give(piece.d_tuples, piece.tuple_bytes);
                vlg_result_destroy(res); return stt; }

@@ -184,7 +184,9 @@ __global__ void wtsa_max_kernel(const uint32_t* __restrict__ syms, uint64_t coun
 // x->d_level_prefix, once the device tree is complete (vlg_wtsa_build, vlg_wtsa_from_parts)
 vlg_status wtsa_level_prefix(vlg_wtsa* x)
 {
-    VLG_HIP_TRY(hipMalloc((void**)&x->d_level_prefix, ((uint64_t)x->levels + 1) * 8));
+    DevBuf d_prefix;
+    VLG_HIP_TRY(d_prefix.alloc(((uint64_t)x->levels + 1) * 8));
+    x->d_level_prefix = static_cast<uint64_t*>(d_prefix.take());
     hipLaunchKernelGGL(wtsa_level_prefix_kernel, dim3(1), dim3(64), 0, nullptr, wtsa_view(x), x->d_level_prefix);
     VLG_HIP_TRY(hipGetLastError());
     return VLG_OK;
@@ -193,7 +195,7 @@ vlg_status wtsa_level_prefix(vlg_wtsa* x)
 vlg_status wtsa_il_device_impl(const vlg_wtsa* x, uint64_t* d_words, hipStream_t st)
 {
     const IlShape s = il_shape(x->n_vals, x->levels);
-    hipLaunchKernelGGL(wtsa_il_fill_kernel, dim3(grid_for(s.data_words, 1u << 20)), dim3(256), 0, st, wtsa_view(x), (const uint64_t*)x->d_level_prefix,
+    hipLaunchKernelGGL(wtsa_il_fill_kernel, launch_grid(s.data_words, 1u << 20), dim3(256), 0, st, wtsa_view(x), (const uint64_t*)x->d_level_prefix,
                        s.data_words, s.superblocks, d_words);
     VLG_HIP_TRY(hipGetLastError());
     return VLG_OK;                                                  // asynchronous on `st`
@@ -211,19 +213,13 @@ extern "C" vlg_status vlg_wtsa_il_device(const vlg_wtsa* x, uint64_t* d_words, u
 vlg_status vlg::wtsa_il_words(const vlg_wtsa* x, std::vector<uint64_t>& words)
 {
     const IlShape s = il_shape(x->n_vals, x->levels);
-    uint64_t* d = nullptr;
-    VLG_HIP_TRY(hipMalloc((void**)&d, s.block_num * 8));
-    vlg_status r = wtsa_il_device_impl(x, d, nullptr);
-    if (!r) {
-        try { words.resize(s.block_num); }
-        catch (const std::bad_alloc&) { r = fail(VLG_E_OOM, "out of host memory for the tree image"); }
-    }
-    if (!r) {                                                       // (on the null stream, after the fill)
-        const hipError_t e = hipMemcpy(words.data(), d, s.block_num * 8, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) r = fail(e == hipErrorOutOfMemory ? VLG_E_OOM : VLG_E_NO_DEVICE, hipGetErrorString(e));
-    }
-    (void)hipFree(d);
-    return r;
+    DevBuf d;
+    VLG_HIP_TRY(d.alloc(s.block_num * 8));
+    if (vlg_status r = wtsa_il_device_impl(x, d.as<uint64_t>(), nullptr)) return r;
+    try { words.resize(s.block_num); }
+    catch (const std::bad_alloc&) { return fail(VLG_E_OOM, "out of host memory for the tree image"); }
+    VLG_HIP_TRY(hipMemcpy(words.data(), d.p, s.block_num * 8, hipMemcpyDeviceToHost));   // (on the null stream, after the fill)
+    return VLG_OK;
 }
 
 vlg_status vlg::wtsa_text_words(const vlg_wtsa* x, uint32_t& width, std::vector<uint64_t>& words)
@@ -238,17 +234,15 @@ vlg_status vlg::wtsa_text_words(const vlg_wtsa* x, uint32_t& width, std::vector<
         return VLG_OK;
     }
     if (width > 64) return fail(VLG_E_INVALID, "text_width must be 0..64");
-    unsigned* d_max = nullptr;
-    VLG_HIP_TRY(hipMalloc((void**)&d_max, 4));
+    DevBuf d_max, d;
+    VLG_HIP_TRY(d_max.alloc(4));
     unsigned mx = 0;
-    hipError_t e = hipMemset(d_max, 0, 4);
-    if (e == hipSuccess && count) {
-        hipLaunchKernelGGL(wtsa_max_kernel, dim3(grid_for(count, 4096)), dim3(256), 0, nullptr, (const uint32_t*)x->d_text, count, d_max);
-        e = hipGetLastError();
+    VLG_HIP_TRY(hipMemset(d_max.p, 0, 4));
+    if (count) {
+        hipLaunchKernelGGL(wtsa_max_kernel, launch_grid(count, 4096), dim3(256), 0, nullptr, (const uint32_t*)x->d_text, count, d_max.as<unsigned>());
+        VLG_HIP_TRY(hipGetLastError());
     }
-    if (e == hipSuccess) e = hipMemcpy(&mx, d_max, 4, hipMemcpyDeviceToHost);
-    (void)hipFree(d_max);
-    VLG_HIP_TRY(e);
+    VLG_HIP_TRY(hipMemcpy(&mx, d_max.p, 4, hipMemcpyDeviceToHost));
     const uint32_t need = std::max(1u, bit_width64(mx));
     if (!width) width = x->file_width ? x->file_width : need;
     if (width < need)
@@ -257,13 +251,10 @@ vlg_status vlg::wtsa_text_words(const vlg_wtsa* x, uint32_t& width, std::vector<
     try { words.assign(n_words, 0); }
     catch (const std::bad_alloc&) { return fail(VLG_E_OOM, "out of host memory for the text"); }
     if (!n_words) return VLG_OK;
-    uint64_t* d = nullptr;
-    VLG_HIP_TRY(hipMalloc((void**)&d, n_words * 8));
-    hipLaunchKernelGGL(wtsa_pack_kernel, dim3(grid_for(n_words, 8192)), dim3(256), 0, nullptr, (const uint32_t*)x->d_text, count, width, d, n_words);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpy(words.data(), d, n_words * 8, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    VLG_HIP_TRY(e);
+    VLG_HIP_TRY(d.alloc(n_words * 8));
+    hipLaunchKernelGGL(wtsa_pack_kernel, launch_grid(n_words, 8192), dim3(256), 0, nullptr, (const uint32_t*)x->d_text, count, width, d.as<uint64_t>(), n_words);
+    VLG_HIP_TRY(hipGetLastError());
+    VLG_HIP_TRY(hipMemcpy(words.data(), d.p, n_words * 8, hipMemcpyDeviceToHost));
     return VLG_OK;
 }
 
@@ -293,63 +284,56 @@ extern "C" vlg_status vlg_wtsa_from_parts(const vlg_wtsa_parts* p, vlg_wtsa** ou
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(VLG_E_NO_DEVICE, "no HIP device available (the VLG library has no CPU fallback)");
     release_cached_device_memory();
-    vlg_wtsa* x = new vlg_wtsa();
+    WtsaPtr x(new vlg_wtsa());
     x->n_text = n - 1; x->n_vals = n; x->sym_bytes = p->symbol_bytes; x->levels = L;
     x->nb = n / kBlockBits + 1;
     x->file_width = p->symbol_bytes == 4 ? w : 0;
-    uint64_t *d_img = nullptr, *d_words = nullptr, *d_ones = nullptr;
-    uint32_t* d_pops = nullptr;
-    unsigned* d_flag = nullptr;
-    void* d_tmp = nullptr;
-    auto run = [&]() -> vlg_status {
+    DevBuf d_flag_buf, d_text, d_words, d_img, d_blocks, d_pops_buf, d_tmp, d_ones;
+    auto run = [&]() -> vlg_status {                                 // (host vectors in here: std::bad_alloc becomes a status below)
         const uint64_t count = n - 1, nb = x->nb;
-        VLG_HIP_TRY(hipMalloc((void**)&d_flag, 16));
+        VLG_HIP_TRY(d_flag_buf.alloc(16));
+        unsigned* d_flag = d_flag_buf.as<unsigned>();
         VLG_HIP_TRY(hipMemset(d_flag, 0, 16));
         // ---- text ----------------------------------------------------------------------------------------------------------------------
-        VLG_HIP_TRY(hipMalloc(&x->d_text, std::max<uint64_t>(count * x->sym_bytes, 16)));
+        VLG_HIP_TRY(d_text.alloc(count * x->sym_bytes));
+        x->d_text = d_text.take();
         if (x->sym_bytes == 1) {
             if (count) {
                 VLG_HIP_TRY(hipMemcpy(x->d_text, p->text_words, count, hipMemcpyHostToDevice));
-                hipLaunchKernelGGL(wtsa_zero_byte_kernel, dim3(grid_for(count, 8192)), dim3(256), 0, nullptr, (const uint8_t*)x->d_text, count, d_flag);
+                hipLaunchKernelGGL(wtsa_zero_byte_kernel, launch_grid(count, 8192), dim3(256), 0, nullptr, (const uint8_t*)x->d_text, count, d_flag);
                 VLG_HIP_TRY(hipGetLastError());
             }
         } else if (count) {
             const uint64_t nw = (count * w + 63) / 64;
-            VLG_HIP_TRY(hipMalloc((void**)&d_words, nw * 8));
-            VLG_HIP_TRY(hipMemcpy(d_words, p->text_words, nw * 8, hipMemcpyHostToDevice));
-            hipLaunchKernelGGL(wtsa_unpack_kernel, dim3(grid_for(count, 8192)), dim3(256), 0, nullptr, d_words, count, w, (uint32_t*)x->d_text, d_flag + 1);
+            VLG_HIP_TRY(d_words.alloc(nw * 8));
+            VLG_HIP_TRY(hipMemcpy(d_words.p, p->text_words, nw * 8, hipMemcpyHostToDevice));
+            hipLaunchKernelGGL(wtsa_unpack_kernel, launch_grid(count, 8192), dim3(256), 0, nullptr, d_words.as<uint64_t>(), count, w, (uint32_t*)x->d_text, d_flag + 1);
             VLG_HIP_TRY(hipGetLastError());
         }
         // ---- the tree ------------------------------------------------------------------------------------------------------------------
-        VLG_HIP_TRY(hipMalloc((void**)&d_img, s.block_num * 8));
-        VLG_HIP_TRY(hipMemcpy(d_img, p->data, s.block_num * 8, hipMemcpyHostToDevice));
-        VLG_HIP_TRY(hipMalloc((void**)&x->d_blocks, (uint64_t)L * nb * sizeof(Block)));
-        VLG_HIP_TRY(hipMalloc((void**)&d_pops, (uint64_t)L * (nb + 1) * 4));
+        VLG_HIP_TRY(d_img.alloc(s.block_num * 8));
+        VLG_HIP_TRY(hipMemcpy(d_img.p, p->data, s.block_num * 8, hipMemcpyHostToDevice));
+        VLG_HIP_TRY(d_blocks.alloc((uint64_t)L * nb * sizeof(Block)));
+        x->d_blocks = static_cast<Block*>(d_blocks.take());
+        VLG_HIP_TRY(d_pops_buf.alloc((uint64_t)L * (nb + 1) * 4));
+        uint32_t* d_pops = d_pops_buf.as<uint32_t>();
         VLG_HIP_TRY(hipMemset(d_pops, 0, (uint64_t)L * (nb + 1) * 4));
-        hipLaunchKernelGGL(wtsa_il_gather_kernel, dim3(grid_for((uint64_t)L * nb, 16384)), dim3(256), 0, nullptr, (const uint64_t*)d_img, n, L, nb,
+        hipLaunchKernelGGL(wtsa_il_gather_kernel, launch_grid((uint64_t)L * nb), dim3(256), 0, nullptr, d_img.as<uint64_t>(), n, L, nb,
                            x->d_blocks, d_pops);
         VLG_HIP_TRY(hipGetLastError());
-        size_t tb = 0;
-        VLG_HIP_TRY(rocprim::exclusive_scan(nullptr, tb, d_pops, d_pops, 0u, nb + 1, rocprim::plus<uint32_t>(), nullptr));
-        VLG_HIP_TRY(hipMalloc(&d_tmp, tb + 16));
-        for (uint32_t lvl = 0; lvl < L; ++lvl) {
-            uint32_t* lp = d_pops + (uint64_t)lvl * (nb + 1);
-            size_t t2 = tb;
-            VLG_HIP_TRY(rocprim::exclusive_scan(d_tmp, t2, lp, lp, 0u, nb + 1, rocprim::plus<uint32_t>(), nullptr));
-            hipLaunchKernelGGL(wtsa_counts_kernel, dim3(grid_for(nb)), dim3(256), 0, nullptr, x->d_blocks + (uint64_t)lvl * nb, lp, nb);
-            VLG_HIP_TRY(hipGetLastError());
-        }
-        VLG_HIP_TRY(hipMalloc((void**)&d_ones, (uint64_t)L * 8));
-        hipLaunchKernelGGL(wtsa_level_ones_kernel, dim3(1), dim3(64), 0, nullptr, d_pops, L, nb, d_ones);
+        for (uint32_t lvl = 0; lvl < L; ++lvl)
+            if (vlg_status r = wtsa_level_counts(x->d_blocks + (uint64_t)lvl * nb, nb, d_pops + (uint64_t)lvl * (nb + 1), d_tmp)) return r;
+        VLG_HIP_TRY(d_ones.alloc((uint64_t)L * 8));
+        hipLaunchKernelGGL(wtsa_level_ones_kernel, dim3(1), dim3(64), 0, nullptr, d_pops, L, nb, d_ones.as<uint64_t>());
         VLG_HIP_TRY(hipGetLastError());
         // the count words against the tree just built
-        if (vlg_status r = wtsa_level_prefix(x)) return r;
-        hipLaunchKernelGGL(wtsa_il_check_kernel, dim3(grid_for(s.superblocks, 16384)), dim3(256), 0, nullptr, wtsa_view(x), (const uint64_t*)x->d_level_prefix,
-                           (const uint64_t*)d_img, s.data_words, s.superblocks, d_flag + 2);
+        if (vlg_status r = wtsa_level_prefix(x.get())) return r;
+        hipLaunchKernelGGL(wtsa_il_check_kernel, launch_grid(s.superblocks), dim3(256), 0, nullptr, wtsa_view(x.get()), (const uint64_t*)x->d_level_prefix,
+                           d_img.as<uint64_t>(), s.data_words, s.superblocks, d_flag + 2);
         VLG_HIP_TRY(hipGetLastError());
         std::vector<uint64_t> ones(L);
         unsigned flags[4] = {0, 0, 0, 0};
-        VLG_HIP_TRY(hipMemcpy(ones.data(), d_ones, (uint64_t)L * 8, hipMemcpyDeviceToHost));
+        VLG_HIP_TRY(hipMemcpy(ones.data(), d_ones.p, (uint64_t)L * 8, hipMemcpyDeviceToHost));
         VLG_HIP_TRY(hipMemcpy(flags, d_flag, 16, hipMemcpyDeviceToHost));
         // ---- the checks --------------------------------------------------------------------------------------------------------------
         if (flags[0]) return fail(VLG_E_ZERO_BYTE, "the byte text holds a 0 byte (construct.hpp:36-45)");
@@ -369,9 +353,7 @@ extern "C" vlg_status vlg_wtsa_from_parts(const vlg_wtsa_parts* p, vlg_wtsa** ou
     vlg_status st;
     try { st = run(); }
     catch (const std::bad_alloc&) { st = fail(VLG_E_OOM, "out of host memory"); }
-    for (void* q : {(void*)d_img, (void*)d_words, (void*)d_ones, (void*)d_pops, (void*)d_flag, d_tmp})
-        if (q) (void)hipFree(q);
-    if (st) { vlg_wtsa_destroy(x); return st; }
-    *out = x;
+    if (st) return st;
+    *out = x.release();
     return VLG_OK;
 }
