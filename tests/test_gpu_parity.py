@@ -1018,6 +1018,60 @@ def test_join_batch_vs_oracle_join(torch_cuda, V, oracle, filt):
     assert (res2.counts == res.counts).all() and res2.summary["checksum"] == chk and res2.summary["n_tuple_values"] == 0
 
 
+def _mixed_k_join_cases():
+    """Joins of 1, 2, 3 and 5 lists (two of them dead) whose first lists land in the classes 0, 1, 2 and 4 of one chunk, with lengths on
+    both sides of the class alignment (64 slots) and of the chain tile (1024 slots)."""
+    rng = np.random.default_rng(20261018)
+    lens = [[65], [63, 10], [64, 1, 7], [1, 130, 2, 1025, 3], [50, 0], [0], [1023, 1024, 1]]
+    span, cases = 6000, []
+    for ln in lens:
+        lists = [np.sort(rng.choice(span, size=n, replace=False)).astype(np.uint64) for n in ln]
+        lo = [int(rng.integers(0, 20)) for _ in ln[1:]]
+        hi = [l + int(rng.integers(1500, 3000)) for l in lo]
+        cases.append((lists, lo, hi, int(rng.integers(1, 9))))
+    # one match made by hand, from the single element of the five-list join's first list: every next list holds the element at the
+    # near end of the window of the one before
+    lists, lo, hi, _ = cases[3]
+    p = 100
+    for i, a in enumerate(lists):
+        p += lo[i - 1] if i else 0
+        others = rng.choice(span, size=len(a) + 1, replace=False)           # one spare: p may be among them
+        lists[i] = np.sort(np.append(others[others != p][:len(a) - 1], p)).astype(np.uint64)
+    return lens, cases
+
+
+def test_join_chunk_slot_layout_mixed_k(torch_cuda, V, oracle):
+    from vlg_matching_amd.index import Workspace
+    lens, cases = _mixed_k_join_cases()
+    assert [[len(a) for a in c[0]] for c in cases] == lens
+    # the slots of the one chunk: classes (lists after this one in its join) from the highest down, each starting on a multiple of 64;
+    # a dead join has no slots, and neither has a last list unless it is the only one
+    live = [c for c in cases if all(len(a) for a in c[0])]
+    kmax, slots = max(len(c[0]) for c in live), 0
+    for d in range(kmax - 1, -1, -1):
+        slots = (slots + 63) // 64 * 64
+        for ls, _, _, _ in live:
+            i = len(ls) - 1 - d
+            if i >= 0 and (d > 0 or len(ls) == 1):
+                slots += len(ls[i])
+    assert slots == 3649
+    want = [oracle.join(*c) for c in cases]
+    assert sum(1 for m, _ in want if m) >= 4 and want[4][0] == 0 and want[5][0] == 0
+    assert want[3][0] >= 1 and int(want[3][1][0, 0]) == 100                  # the match made by hand
+    ws = Workspace()
+    ws.set_option("filter", 0)
+    for tuples in (1, 0):
+        ws.set_option("tuples", tuples)
+        res = _run_join_batch(torch_cuda, V, cases, ws)
+        assert res.summary["n_chunks"] == 1 and res.summary["join_slots"] == slots
+        for j, (m, t) in enumerate(want):
+            assert int(res.counts[j]) == m, j
+            assert res.positions(j).tolist() == t[:, 0].tolist(), j
+            if tuples:
+                assert res.tuples(j).tolist() == t.tolist(), j
+        assert res.summary["n_tuple_values"] == (sum(m * len(c[0]) for (m, _), c in zip(want, cases)) if tuples else 0)
+
+
 def test_join_batch_rejects_bad_input_and_chunks(torch_cuda, V, oracle):
     from vlg_matching_amd.index import Workspace, join_batch
     from vlg_matching_amd.capi import VlgError

@@ -21,6 +21,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <numeric>
 #include <thread>
 #include <string.h>
 #include <string>
@@ -630,8 +631,20 @@ struct Lists {                      // the sorted occurrence lists the joins rea
 };
 
 template <typename pos_t> constexpr uint64_t kPhysScratchPerElem() { return 20; }   // sweep scratch; the sorted lists reuse it
-constexpr uint64_t kJoinBytesPerSlot = 4 + 8 + 1;      // link, endp(<=8), feasibility bits + summaries (any slot)
-constexpr uint64_t kJoinBytesPerSlot0 = 4 + 4 + 8 + 1; // jump, mlist, (exit,hops), chain records (slots of list 0)
+// What JoinChunk carves, as the planners count it.  Per slot:
+constexpr uint64_t kJoinBytesPerSlot = 4 + 8 + 1;      // any slot: link, endp (<= 8), lvl_ptr[] (feasibility bits + summaries)
+constexpr uint64_t kJoinBytesPerSlot0 = 4 + 4 + 8 + 1; // slots of list 0: jump, mlist, xh (exit, hops), d_recq + d_rec (chain records)
+// ... and per item of the tables the host builds for a chunk (upper bounds with room to spare):
+constexpr uint64_t kJoinMetaPerSub = sizeof(SegMeta) + 48;      // d_sm; d_segb and compact_survivors' d_tseg, d_tcidx, d_trun0 (20 B)
+constexpr uint64_t kJoinMetaPerQuery = sizeof(QueryMeta) + 96;  // d_qm; d_counts, d_qstart, d_recb, d_recc (20 B)
+constexpr uint64_t kJoinMetaPerRecord = 48;                     // d_recq, d_rec (12 B per chain record)
+// Per-chunk metadata on top of `join_bytes` of join scratch.  Chain records: a first list of n slots overlaps at most n / kTile + 2
+// tiles, and kTile of its slots are more than 8192 B of scratch.  The constant pays for d_fb, the slots of the class alignment and of
+// the first tile before the level-0 range, and the rounding of every take.  (compact_survivors' d_cnt and d_off: JoinPlan::filter_need.)
+inline uint64_t join_meta_bytes(uint64_t subs, uint64_t queries, uint64_t join_bytes)
+{
+    return (subs + 4) * kJoinMetaPerSub + (queries + 4) * kJoinMetaPerQuery + (join_bytes / 8192 + queries + 8) * kJoinMetaPerRecord + (1ull << 20);
+}
 
 // ---- sort of all lists at once: one radix sort of (list, position) keys instead of one sort per list -------------
 template <typename pos_t>
@@ -1236,51 +1249,76 @@ vlg_status build_physical(const vlg_index* idx, vlg_workspace* ws, vlg_result* r
 namespace {
 
 // ---- join of the queries [q0,q1) against the physical lists -------------------------------------------
+// The stages run one after the other (run_join_chunk, below).  The host tables the async copies read are members: they outlive the
+// synchronize that ends gather().
 template <typename pos_t>
-vlg_status run_join_chunk(const vlg_queries* q, vlg_workspace* ws, vlg_result* res, uint64_t q0, uint64_t q1, const Plan& pl, const Lists<pos_t>& L,
-                          Arena A /* by value: scratch past the lists */, unsigned long long* d_stats, const FilterGroup* fg)
-{
+struct JoinChunk {
+    const vlg_queries* q; vlg_workspace* ws; vlg_result* res; const uint64_t q0, q1; const Plan& pl; const Lists<pos_t>& L;
+    Arena A;                            // by value: scratch past the lists
+    unsigned long long* d_stats; const FilterGroup* fg;
     hipStream_t st = ws->stream;
+    PhaseTrace jt{st};
     const pos_t* P = L.P;
     pos_t* Pc = L.Pc;                   // survivors of filtered lists go here
-    const std::vector<uint32_t>& poff = L.off;
-    PhaseTrace jt(st);
-    // list lengths as the join sees them: the survivors of the window filter where it ran
-    auto eo = [&](uint64_t s) -> uint64_t { return fg ? fg->eff[s - fg->sub0] : pl.occ[s]; };
-    auto filtered = [&](uint64_t s) -> bool { return fg && fg->cidx[s - fg->sub0] != kNone; };
+    const pos_t* F = L.F;
     const uint64_t s0 = q->qsub[q0], s1 = q->qsub[q1];
     const uint32_t nseg = (uint32_t)(s1 - s0), nq = (uint32_t)(q1 - q0);
-    ResultPiece piece;
-    piece.q0 = q0; piece.q1 = q1;
-    // ---- host-side metadata of the chunk: segments in class-major order (dist descending) -------------
-    // The filtered sub-patterns of the chunk are collected on the same walk (in Pc order): their compaction is launched first so
-    // that it runs while the rest of the metadata is built.
-    svec<QueryMeta> qm(nq);
-    uint32_t kmax = 0;
-    svec<uint32_t> t_seg, t_cidx;
-    svec<uint64_t> t_run0;
-    if (fg) { t_seg.reserve(nseg); t_cidx.reserve(nseg); t_run0.reserve(nseg + 1); }
-    t_run0.push_back(0);
+    ResultPiece piece{q0, q1};
+    bool empty = false;                 // no live query, or no slot of a first list: the chunk has no match and launches no join
+    // host tables
+    svec<QueryMeta> qm;
+    uint32_t kmax = 0, nlive = 0, n_rec = 0;
+    svec<uint32_t> t_seg, t_cidx; svec<uint64_t> t_run0;            // compaction tasks: the chunk's filtered lists, in Pc order
     uint64_t pc_total = 0;
-    for (uint64_t qi = q0; qi < q1; ++qi) {
-        const uint64_t a = q->qsub[qi];
-        uint32_t k = (uint32_t)(q->qsub[qi + 1] - a);
-        QueryMeta& Q = qm[qi - q0];
-        Q.k = k; Q.end_len = q->end_len[qi]; Q.out_first = Q.out_tuple = 0; Q.seg0 = kNone;
-        if (!(k > 0 && eo(a) > 0)) continue;
-        kmax = std::max(kmax, k);
-        if (fg && !fg->speculated)
-            for (uint32_t i = 0; i < k; ++i) {
-                const uint32_t c = fg->cidx[a + i - fg->sub0];
-                if (c == kNone) continue;
-                t_cidx.push_back(c);
-                t_seg.push_back(fg->cseg[c]);
-                t_run0.push_back(t_run0.back() + (fg->crun0[c + 1] - fg->crun0[c]));
-                pc_total += fg->eff[a + i - fg->sub0];
-            }
+    std::vector<uint32_t> cls_count, cls_first;                     // segments per dist class; classes are stored from the highest dist down to 0
+    std::vector<uint64_t> cls_slot_begin, cls_slot_end;
+    svec<SegMeta> sm; svec<uint32_t> seg_begin;
+    uint64_t T = 0, lvl0_begin = 0, lvl0_end = 0, t0 = 0;
+    svec<uint32_t> rec_begin, rec_query;
+    svec<unsigned long long> counts, first_of;
+    // device arrays
+    uint32_t* link = nullptr; pos_t* endp = nullptr;
+    FeasBits fb; uint64_t* lvl_ptr[kBitLevels]; FeasBits* d_fb = nullptr; FeasRef fref{nullptr, nullptr};
+    uint32_t* jump = nullptr; uint32_t* mlist = nullptr; uint2* xh = nullptr;
+    SegMeta* d_sm = nullptr; QueryMeta* d_qm = nullptr; uint32_t* d_segb = nullptr; unsigned long long* d_counts = nullptr;
+    uint32_t* d_qstart = nullptr; uint32_t* d_recb = nullptr; uint32_t* d_recc = nullptr; uint32_t* d_recq = nullptr; uint2* d_rec = nullptr;
+
+    // list lengths as the join sees them: the survivors of the window filter where it ran
+    uint64_t eo(uint64_t s) const { return fg ? fg->eff[s - fg->sub0] : pl.occ[s]; }
+    bool filtered(uint64_t s) const { return fg && fg->cidx[s - fg->sub0] != kNone; }
+    // a query is joined when it has lists and the first one is not empty (a query with an empty list has all lengths 0)
+    bool live(uint64_t qi) const { return q->qsub[qi + 1] > q->qsub[qi] && eo(q->qsub[qi]) > 0; }
+
+    // per query: its QueryMeta; the filtered sub-patterns of the chunk, when the chunk compacts them itself, in Pc order
+    void survivor_tasks()
+    {
+        qm.resize(nq);
+        if (fg) { t_seg.reserve(nseg); t_cidx.reserve(nseg); t_run0.reserve(nseg + 1); }
+        t_run0.push_back(0);
+        for (uint64_t qi = q0; qi < q1; ++qi) {
+            const uint64_t a = q->qsub[qi];
+            const uint32_t k = (uint32_t)(q->qsub[qi + 1] - a);
+            QueryMeta& Q = qm[qi - q0];
+            Q.k = k; Q.end_len = q->end_len[qi]; Q.out_first = Q.out_tuple = 0; Q.seg0 = kNone;
+            if (!live(qi)) continue;
+            kmax = std::max(kmax, k);
+            if (fg && !fg->speculated)
+                for (uint32_t i = 0; i < k; ++i) {
+                    const uint32_t c = fg->cidx[a + i - fg->sub0];
+                    if (c == kNone) continue;
+                    t_cidx.push_back(c);
+                    t_seg.push_back(fg->cseg[c]);
+                    t_run0.push_back(t_run0.back() + (fg->crun0[c + 1] - fg->crun0[c]));
+                    pc_total += fg->eff[a + i - fg->sub0];
+                }
+        }
     }
-    // ---- private lists: compact the survivors of the chunk's filtered lists behind P ------------------------
-    if (!t_seg.empty()) {
+
+    // private lists: the survivors of the chunk's filtered lists compacted behind P, and their fences.  Enqueued BEFORE layout()
+    // builds the rest of the host metadata, so that the compaction runs meanwhile (DESIGN §9 counts on that overlap).
+    vlg_status compact_survivors()
+    {
+        if (t_seg.empty()) return VLG_OK;
         const uint64_t runs = t_run0.back();
         uint32_t* d_tseg = A.take<uint32_t>(t_seg.size());
         uint32_t* d_tcidx = A.take<uint32_t>(t_cidx.size());
@@ -1303,147 +1341,144 @@ vlg_status run_join_chunk(const vlg_queries* q, vlg_workspace* ws, vlg_result* r
                                dim3(256), 0, st, P, fg->d_segs, d_tseg, d_trun0, (uint32_t)t_seg.size(), fg->d_abits, d_cnt, d_off, Pc, ~0ull, ws->compact_dense_min);
         }
         // fences of the survivors' lists: whole blocks of [Pc, Pc + pc_total) (Pc starts on a block)
-        if (L.F && pc_total >= 64) {
+        if (F && pc_total >= 64) {
             const uint64_t g0 = (uint64_t)(Pc - P) / 64;
             hipLaunchKernelGGL(HIP_KERNEL_NAME(fence_build_kernel<pos_t>), launch_grid(pc_total / 64, 8192), dim3(256), 0, st, P, g0, g0 + pc_total / 64, L.F);
         }
         VLG_HIP_TRY(hipGetLastError());
+        return VLG_OK;
     }
-    const pos_t* F = L.F;
-    jt.mark("  chunk: compaction launched");
-    std::vector<uint32_t> cls_count(kmax + 1, 0), cls_first(kmax + 2, 0);   // segments per dist class
-    for (uint64_t qi = q0; qi < q1; ++qi) {
-        uint32_t k = qm[qi - q0].k;
-        if (!(k > 0 && eo(q->qsub[qi]) > 0)) continue;
-        for (uint32_t i = 0; i < k; ++i) cls_count[k - 1 - i]++;
-    }
-    // classes are stored from the highest dist down to 0
-    uint32_t nlive = 0;
-    for (int d = (int)kmax - 1; d >= 0; --d) { cls_first[d] = nlive; nlive += cls_count[d]; }
-    svec<SegMeta> sm(nlive + 1);
-    svec<uint32_t> seg_begin(nlive + 2, 0);
-    std::vector<uint32_t> fill(kmax + 1, 0);
-    std::vector<uint32_t> seg_of_sub(nseg, kNone);
-    for (uint64_t qi = q0; qi < q1; ++qi) {
-        uint32_t k = qm[qi - q0].k;
-        if (!(k > 0 && eo(q->qsub[qi]) > 0)) continue;
-        for (uint32_t i = 0; i < k; ++i) {
-            uint32_t d = k - 1 - i;
-            seg_of_sub[q->qsub[qi] + i - s0] = cls_first[d] + fill[d]++;
-        }
-        qm[qi - q0].seg0 = seg_of_sub[q->qsub[qi] - s0];
-    }
-    uint64_t pc_used = 0;
-    for (uint64_t qi = q0; qi < q1; ++qi) {
-        uint32_t k = qm[qi - q0].k;
-        if (qm[qi - q0].seg0 == kNone) continue;
-        for (uint32_t i = 0; i < k; ++i) {
-            uint64_t s = q->qsub[qi] + i;
-            SegMeta& m = sm[seg_of_sub[s - s0]];
-            m.level = i; m.dist = k - 1 - i;
-            m.lo = q->lo[s]; m.hi = q->hi[s];
-            if (filtered(s) && fg->speculated) {                 // compacted with its whole group: segment c starts at cpre[c]
-                m.pbegin = (uint32_t)((Pc - P) + fg->cpre[fg->cidx[s - fg->sub0]]);
-            } else if (filtered(s)) {                            // private list of the query: the survivors, compacted behind P
-                m.pbegin = (uint32_t)((Pc - P) + pc_used);                 // the order of the compaction tasks
-                pc_used += eo(s);
-            } else {
-                m.pbegin = poff[s];
-            }
-            m.pend = m.pbegin + (uint32_t)eo(s);
-            m.next = (i + 1 < k) ? seg_of_sub[s + 1 - s0] : kNone;
-            m.query = (uint32_t)(qi - q0);
-        }
-    }
-    // slots: class-major, segments of a class in query order
-    uint64_t acc = 0;
-    std::vector<uint64_t> cls_slot_begin(kmax + 1, 0), cls_slot_end(kmax + 1, 0);
-    for (int d = (int)kmax - 1; d >= 0; --d) {
-        acc = align_up(acc, 64);                                             // a wave step of a class owns whole words of the feasibility bitmap
-        cls_slot_begin[d] = acc;
-        for (uint32_t j = 0; j < cls_count[d]; ++j) {
-            SegMeta& m = sm[cls_first[d] + j];
-            seg_begin[cls_first[d] + j] = (uint32_t)acc;
-            m.begin = (uint32_t)acc;
-            if (m.dist > 0 || m.level == 0) acc += (m.pend - m.pbegin);      // the last list of a k>=2 query needs no join state
-            m.end = (uint32_t)acc;
-        }
-        cls_slot_end[d] = acc;
-    }
-    const uint64_t T = acc;
-    seg_begin[nlive] = (uint32_t)acc;
-    seg_begin[nlive + 1] = 0xFFFFFFFFu;
-    sm[nlive] = SegMeta{(uint32_t)acc, (uint32_t)acc, 0, 0, 0, 0, kNone, 0, 0, 0};
-    if (T == 0 || nlive == 0) { res->pieces.push_back(piece); return VLG_OK; }
-    // level-0 slots span the classes k-1 of every live query: [lvl0_begin, lvl0_end) bounds them
-    uint64_t lvl0_begin = T, lvl0_end = 0;
-    for (uint32_t i = 0; i < nq; ++i)
-        if (qm[i].seg0 != kNone) {
-            const SegMeta& m0 = sm[qm[i].seg0];
-            if (m0.end > m0.begin) { lvl0_begin = std::min<uint64_t>(lvl0_begin, m0.begin); lvl0_end = std::max<uint64_t>(lvl0_end, m0.end); }
-        }
-    if (lvl0_end <= lvl0_begin) { res->pieces.push_back(piece); return VLG_OK; }
-    jt.mark("  chunk: host metadata");
-    jt.mark("  chunk: compaction");
-    // ---- carve the arena ---------------------------------------------------------------------------
-    uint32_t* link = ws->tuples ? A.take<uint32_t>(T) : nullptr;      // only the tuples walk the links
-    pos_t* endp = A.take<pos_t>(T);
-    // feasibility bitset + summaries
-    FeasBits fb;
-    uint64_t* lvl_ptr[kBitLevels];
+
+    // host-side metadata of the chunk (no HIP call): segments in class-major order (dist descending), their lists and slots, the
+    // range of the level-0 slots and the chain records; -> empty
+    void layout()
     {
+        cls_count.assign(kmax + 1, 0); cls_first.assign(kmax + 2, 0);
+        for (uint64_t qi = q0; qi < q1; ++qi) {
+            const uint32_t k = qm[qi - q0].k;
+            if (!live(qi)) continue;
+            for (uint32_t i = 0; i < k; ++i) cls_count[k - 1 - i]++;
+        }
+        for (int d = (int)kmax - 1; d >= 0; --d) { cls_first[d] = nlive; nlive += cls_count[d]; }
+        sm.resize(nlive + 1);
+        seg_begin.assign(nlive + 2, 0);
+        std::vector<uint32_t> fill(kmax + 1, 0);
+        std::vector<uint32_t> seg_of_sub(nseg, kNone);
+        uint64_t pc_used = 0;
+        for (uint64_t qi = q0; qi < q1; ++qi) {
+            const uint32_t k = qm[qi - q0].k;
+            if (!live(qi)) continue;
+            const uint64_t a = q->qsub[qi];
+            for (uint32_t i = 0; i < k; ++i) seg_of_sub[a + i - s0] = cls_first[k - 1 - i] + fill[k - 1 - i]++;
+            qm[qi - q0].seg0 = seg_of_sub[a - s0];
+            for (uint32_t i = 0; i < k; ++i) {
+                const uint64_t s = a + i;
+                SegMeta& m = sm[seg_of_sub[s - s0]];
+                m.level = i; m.dist = k - 1 - i;
+                m.lo = q->lo[s]; m.hi = q->hi[s];
+                if (filtered(s) && fg->speculated) {                 // compacted with its whole group: segment c starts at cpre[c]
+                    m.pbegin = (uint32_t)((Pc - P) + fg->cpre[fg->cidx[s - fg->sub0]]);
+                } else if (filtered(s)) {                            // private list of the query: the survivors, compacted behind P
+                    m.pbegin = (uint32_t)((Pc - P) + pc_used);                 // the order of the compaction tasks
+                    pc_used += eo(s);
+                } else {
+                    m.pbegin = L.off[s];
+                }
+                m.pend = m.pbegin + (uint32_t)eo(s);
+                m.next = (i + 1 < k) ? seg_of_sub[s + 1 - s0] : kNone;
+                m.query = (uint32_t)(qi - q0);
+            }
+        }
+        // slots: class-major, segments of a class in query order
+        uint64_t acc = 0;
+        cls_slot_begin.assign(kmax + 1, 0); cls_slot_end.assign(kmax + 1, 0);
+        for (int d = (int)kmax - 1; d >= 0; --d) {
+            acc = align_up(acc, 64);                                             // a wave step of a class owns whole words of the feasibility bitmap
+            cls_slot_begin[d] = acc;
+            for (uint32_t j = 0; j < cls_count[d]; ++j) {
+                SegMeta& m = sm[cls_first[d] + j];
+                seg_begin[cls_first[d] + j] = (uint32_t)acc;
+                m.begin = (uint32_t)acc;
+                if (m.dist > 0 || m.level == 0) acc += (m.pend - m.pbegin);      // the last list of a k>=2 query needs no join state
+                m.end = (uint32_t)acc;
+            }
+            cls_slot_end[d] = acc;
+        }
+        T = acc;
+        seg_begin[nlive] = (uint32_t)acc;
+        seg_begin[nlive + 1] = 0xFFFFFFFFu;
+        sm[nlive] = SegMeta{(uint32_t)acc, (uint32_t)acc, 0, 0, 0, 0, kNone, 0, 0, 0};
+        if (T == 0 || nlive == 0) { empty = true; return; }
+        // level-0 slots span the classes k-1 of every live query: [lvl0_begin, lvl0_end) bounds them
+        // chain records: one per tile a level-0 list overlaps (upper bound of the tiles its chain can visit)
+        lvl0_begin = T; lvl0_end = 0;
+        rec_begin.assign(nq + 1, 0);
+        for (uint32_t i = 0; i < nq; ++i) {
+            uint32_t cnt = 0;
+            const SegMeta& m0 = sm[qm[i].seg0 != kNone ? qm[i].seg0 : nlive];      // (sm[nlive] is empty)
+            if (m0.end > m0.begin) {
+                lvl0_begin = std::min<uint64_t>(lvl0_begin, m0.begin); lvl0_end = std::max<uint64_t>(lvl0_end, m0.end);
+                cnt = (m0.end - 1) / kTile - m0.begin / kTile + 1;
+            }
+            rec_begin[i + 1] = rec_begin[i] + cnt;
+            rec_query.insert(rec_query.end(), cnt, i);
+        }
+        n_rec = rec_begin[nq];
+        empty = lvl0_end <= lvl0_begin;
+        t0 = lvl0_begin / kTile * kTile;
+    }
+
+    vlg_status carve()
+    {
+        link = ws->tuples ? A.take<uint32_t>(T) : nullptr;                // only the tuples walk the links
+        endp = A.take<pos_t>(T);
+        // feasibility bitset + summaries
         uint64_t words = (T + 63) / 64 + 1;
         for (uint32_t l = 0; l < kBitLevels; ++l) {
-            lvl_ptr[l] = A.take<uint64_t>(words);
-            fb.lvl[l] = lvl_ptr[l];
+            fb.lvl[l] = lvl_ptr[l] = A.take<uint64_t>(words);
             fb.words[l] = words;
-            if (lvl_ptr[l]) VLG_HIP_TRY(hipMemsetAsync(lvl_ptr[l], 0, words * 8, st));
             words = (words + 63) / 64 + 1;
         }
+        d_fb = A.take<FeasBits>(1);
+        fref = FeasRef{lvl_ptr[0], d_fb};
+        // arrays that exist for the slots of list 0 only (indexed by absolute slot through an offset pointer)
+        const uint64_t n0 = lvl0_end - t0;
+        uint32_t* jump_a = A.take<uint32_t>(n0);
+        uint32_t* mlist_a = A.take<uint32_t>(n0);
+        uint2* xh_a = A.take<uint2>(n0);
+        jump = jump_a ? jump_a - t0 : nullptr;
+        mlist = mlist_a ? mlist_a - t0 : nullptr;
+        xh = xh_a ? xh_a - t0 : nullptr;
+        d_sm = A.take<SegMeta>(nlive + 1);
+        d_qm = A.take<QueryMeta>(nq);
+        d_segb = A.take<uint32_t>(nlive + 2);
+        d_counts = A.take<unsigned long long>(nq);
+        d_qstart = A.take<uint32_t>(nq);
+        d_recb = A.take<uint32_t>(nq + 1);
+        d_recc = A.take<uint32_t>(nq);
+        d_recq = A.take<uint32_t>(n_rec + 1);
+        d_rec = A.take<uint2>(n_rec + 1);
+        if (A.failed) return fail(VLG_E_INTERNAL, "arena carve failed (join)");
+        return VLG_OK;
     }
-    FeasBits* d_fb = A.take<FeasBits>(1);
-    if (d_fb) VLG_HIP_TRY(hipMemcpyAsync(d_fb, &fb, sizeof fb, hipMemcpyHostToDevice, st));
-    const FeasRef fref{lvl_ptr[0], d_fb};
-    // arrays that exist for the slots of list 0 only (indexed by absolute slot through an offset pointer)
-    const uint64_t t0 = lvl0_begin / kTile * kTile;
-    const uint64_t n0 = lvl0_end - t0;
-    uint32_t* jump_a = A.take<uint32_t>(n0);
-    uint32_t* mlist_a = A.take<uint32_t>(n0);
-    uint2* xh_a = A.take<uint2>(n0);
-    uint32_t* jump = jump_a ? jump_a - t0 : nullptr;
-    uint32_t* mlist = mlist_a ? mlist_a - t0 : nullptr;
-    uint2* xh = xh_a ? xh_a - t0 : nullptr;
-    SegMeta* d_sm = A.take<SegMeta>(nlive + 1);
-    QueryMeta* d_qm = A.take<QueryMeta>(nq);
-    uint32_t* d_segb = A.take<uint32_t>(nlive + 2);
-    unsigned long long* d_counts = A.take<unsigned long long>(nq);
-    // chain records: one per tile a level-0 list overlaps (upper bound of the tiles its chain can visit)
-    svec<uint32_t> rec_begin(nq + 1, 0), rec_query;
-    for (uint32_t i = 0; i < nq; ++i) {
-        uint32_t cnt = 0;
-        if (qm[i].seg0 != kNone) {
-            const SegMeta& m0 = sm[qm[i].seg0];
-            if (m0.end > m0.begin) cnt = (m0.end - 1) / kTile - m0.begin / kTile + 1;
-        }
-        rec_begin[i + 1] = rec_begin[i] + cnt;
-        rec_query.insert(rec_query.end(), cnt, i);
+
+    vlg_status upload()
+    {
+        for (uint32_t l = 0; l < kBitLevels; ++l) VLG_HIP_TRY(hipMemsetAsync(lvl_ptr[l], 0, fb.words[l] * 8, st));
+        VLG_HIP_TRY(hipMemcpyAsync(d_fb, &fb, sizeof fb, hipMemcpyHostToDevice, st));
+        VLG_HIP_TRY(hipMemcpyAsync(d_recb, rec_begin.data(), (nq + 1) * 4, hipMemcpyHostToDevice, st));
+        if (n_rec) VLG_HIP_TRY(hipMemcpyAsync(d_recq, rec_query.data(), n_rec * 4, hipMemcpyHostToDevice, st));
+        VLG_HIP_TRY(hipMemsetAsync(d_qstart, 0xFF, nq * 4, st));
+        VLG_HIP_TRY(hipMemcpyAsync(d_sm, sm.data(), (nlive + 1) * sizeof(SegMeta), hipMemcpyHostToDevice, st));
+        VLG_HIP_TRY(hipMemcpyAsync(d_segb, seg_begin.data(), (nlive + 2) * 4, hipMemcpyHostToDevice, st));
+        VLG_HIP_TRY(hipMemcpyAsync(d_qm, qm.data(), nq * sizeof(QueryMeta), hipMemcpyHostToDevice, st));
+        return VLG_OK;
     }
-    const uint32_t n_rec = rec_begin[nq];
-    uint32_t* d_qstart = A.take<uint32_t>(nq);
-    uint32_t* d_recb = A.take<uint32_t>(nq + 1);
-    uint32_t* d_recc = A.take<uint32_t>(nq);
-    uint32_t* d_recq = A.take<uint32_t>(n_rec + 1);
-    uint2* d_rec = A.take<uint2>(n_rec + 1);
-    if (A.failed) return fail(VLG_E_INTERNAL, "arena carve failed (join)");
-    VLG_HIP_TRY(hipMemcpyAsync(d_recb, rec_begin.data(), (nq + 1) * 4, hipMemcpyHostToDevice, st));
-    if (n_rec) VLG_HIP_TRY(hipMemcpyAsync(d_recq, rec_query.data(), n_rec * 4, hipMemcpyHostToDevice, st));
-    VLG_HIP_TRY(hipMemsetAsync(d_qstart, 0xFF, nq * 4, st));
-    VLG_HIP_TRY(hipMemcpyAsync(d_sm, sm.data(), (nlive + 1) * sizeof(SegMeta), hipMemcpyHostToDevice, st));
-    VLG_HIP_TRY(hipMemcpyAsync(d_segb, seg_begin.data(), (nlive + 2) * 4, hipMemcpyHostToDevice, st));
-    VLG_HIP_TRY(hipMemcpyAsync(d_qm, qm.data(), nq * sizeof(QueryMeta), hipMemcpyHostToDevice, st));
+
     // after a class's pass wrote its words of level 0, refresh the summary words above them
-    auto summarize_class = [&](uint32_t d) -> vlg_status {
-        uint64_t b0 = cls_slot_begin[d], b1 = cls_slot_end[d];
+    vlg_status summarize_class(uint32_t d)
+    {
+        const uint64_t b0 = cls_slot_begin[d], b1 = cls_slot_end[d];
         if (b1 <= b0) return VLG_OK;
         Timed t(ws, KS_JOIN_SCAN, (b1 - b0) / 8);
         uint64_t w0 = b0 >> 6, w1 = (b1 + 63) >> 6;                          // word range written at the level below
@@ -1453,96 +1488,131 @@ vlg_status run_join_chunk(const vlg_queries* q, vlg_workspace* ws, vlg_result* r
         }
         VLG_HIP_TRY(hipGetLastError());
         return VLG_OK;
-    };
-    if (cls_slot_end[0] > cls_slot_begin[0]) {
-        Timed t(ws, KS_JOIN_INIT, 0);
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(join_init_kernel<pos_t>), dim3(runs_grid(cls_slot_end[0] - cls_slot_begin[0])), dim3(256), 0, st, P,
-                           d_segb, nlive, d_sm, cls_slot_begin[0], cls_slot_end[0], lvl_ptr[0], endp);
     }
-    if (vlg_status s = summarize_class(0)) return s;
-    for (uint32_t dist = 1; dist < kmax; ++dist) {
-        uint64_t b0 = cls_slot_begin[dist], b1 = cls_slot_end[dist];
-        if (b1 > b0) {
-            Timed t(ws, KS_JOIN_LINK, 8ull * (b1 - b0));
-            if (dist == 1)
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(join_link_kernel<pos_t, true>), dim3(runs_grid(b1 - b0, kLinkRun)), dim3(256), 0, st, P, F, d_segb, nlive, d_sm,
-                                   (uint32_t)b0, (uint32_t)b1, fref, lvl_ptr[0], endp, link);
-            else
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(join_link_kernel<pos_t, false>), dim3(runs_grid(b1 - b0, kLinkRun)), dim3(256), 0, st, P, F, d_segb, nlive, d_sm,
-                                   (uint32_t)b0, (uint32_t)b1, fref, lvl_ptr[0], endp, link);
-        }
-        if (vlg_status s = summarize_class(dist)) return s;
-    }
+
+    // the last lists' slots, then one link pass per class, last gap first; the summaries behind each
+    vlg_status link_classes()
     {
-        Timed t(ws, KS_JOIN_CHAIN, 8ull * (lvl0_end - lvl0_begin));
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(join_jump_kernel<pos_t>), dim3(runs_grid(lvl0_end - lvl0_begin)), dim3(256), 0, st, P, F, d_segb, nlive, d_sm,
-                           d_qm, lvl0_begin, lvl0_end, fref, endp, jump, d_qstart);
-        if (t0 < lvl0_begin) VLG_HIP_TRY(hipMemsetAsync(jump + t0, 0xFF, (lvl0_begin - t0) * 4, st));   // slots of the first tile before the range
-        hipLaunchKernelGGL(chain_tiles_kernel, dim3((uint32_t)((lvl0_end - t0 + kTile - 1) / kTile)), dim3(256), 0, st, jump, t0, lvl0_end, xh);
-        hipLaunchKernelGGL(chain_walk_kernel, dim3((nq + 63) / 64), dim3(64), 0, st, d_sm, d_qm, nq, d_qstart, xh, d_recb, d_rec, d_recc,
-                           d_counts);
-        if (n_rec)
-            hipLaunchKernelGGL(chain_emit_kernel, dim3((n_rec + 3) / 4), dim3(256), 0, st, d_recb, d_recc, d_rec, n_rec, d_recq, jump, xh, lvl0_end, mlist);
+        if (cls_slot_end[0] > cls_slot_begin[0]) {
+            Timed t(ws, KS_JOIN_INIT, 0);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(join_init_kernel<pos_t>), dim3(runs_grid(cls_slot_end[0] - cls_slot_begin[0])), dim3(256), 0, st, P,
+                               d_segb, nlive, d_sm, cls_slot_begin[0], cls_slot_end[0], lvl_ptr[0], endp);
+        }
+        if (vlg_status s = summarize_class(0)) return s;
+        for (uint32_t dist = 1; dist < kmax; ++dist) {
+            const uint64_t b0 = cls_slot_begin[dist], b1 = cls_slot_end[dist];
+            if (b1 > b0) {
+                Timed t(ws, KS_JOIN_LINK, 8ull * (b1 - b0));
+                const auto kernel = dist == 1 ? join_link_kernel<pos_t, true> : join_link_kernel<pos_t, false>;
+                hipLaunchKernelGGL(kernel, dim3(runs_grid(b1 - b0, kLinkRun)), dim3(256), 0, st, P, F, d_segb, nlive, d_sm, (uint32_t)b0, (uint32_t)b1, fref,
+                                   lvl_ptr[0], endp, link);
+            }
+            if (vlg_status s = summarize_class(dist)) return s;
+        }
+        return VLG_OK;
     }
-    VLG_HIP_TRY(hipGetLastError());
-    // ---- sizes of the result, then gather -------------------------------------------------------------
-    svec<unsigned long long> counts(nq);
-    VLG_HIP_TRY(hipMemcpyAsync(counts.data(), d_counts, nq * 8, hipMemcpyDeviceToHost, st));
-    VLG_HIP_TRY(hipStreamSynchronize(st));
-    jt.mark("  chunk: link + chain");
-    uint64_t M = 0, TV = 0;
-    for (uint32_t i = 0; i < nq; ++i) {
-        qm[i].out_first = M; qm[i].out_tuple = TV;
-        M += counts[i]; TV += ws->tuples ? counts[i] * qm[i].k : 0;
-        res->counts[q0 + i] = counts[i];
-    }
-    piece.matches = M; piece.tuple_vals = TV;
-    if (M) {
-        piece.width = sizeof(pos_t);
-        VLG_HIP_TRY(result_alloc(&piece.d_first, M * sizeof(pos_t), &piece.first_bytes));
-        if (TV) VLG_HIP_TRY(result_alloc(&piece.d_tuples, TV * sizeof(pos_t), &piece.tuple_bytes));
-        res->pieces.push_back(piece);
-        jt.mark("  chunk: result malloc");
-        VLG_HIP_TRY(hipMemcpyAsync(d_qm, qm.data(), nq * sizeof(QueryMeta), hipMemcpyHostToDevice, st));
-        svec<unsigned long long> first_of(nq);                      // where every query's matches start, dense (the counts have been read: their place is free)
-        for (uint32_t i = 0; i < nq; ++i) first_of[i] = qm[i].out_first;
-        VLG_HIP_TRY(hipMemcpyAsync(d_counts, first_of.data(), nq * 8, hipMemcpyHostToDevice, st));
-        Timed t(ws, KS_GATHER, sizeof(pos_t) * (M + TV));
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(join_gather_kernel<pos_t>), dim3(runs_grid(M)), dim3(256), 0, st, P, d_sm, d_qm, d_counts, nq, M, link, mlist,
-                           static_cast<pos_t*>(piece.d_first), static_cast<pos_t*>(piece.d_tuples), d_stats + kStatsChecksum);
+
+    // jump over the level-0 slots, in-tile hops, one lane per query from tile to tile, the matches of every visited tile
+    vlg_status chain()
+    {
+        {
+            Timed t(ws, KS_JOIN_CHAIN, 8ull * (lvl0_end - lvl0_begin));
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(join_jump_kernel<pos_t>), dim3(runs_grid(lvl0_end - lvl0_begin)), dim3(256), 0, st, P, F, d_segb, nlive, d_sm,
+                               d_qm, lvl0_begin, lvl0_end, fref, endp, jump, d_qstart);
+            if (t0 < lvl0_begin) VLG_HIP_TRY(hipMemsetAsync(jump + t0, 0xFF, (lvl0_begin - t0) * 4, st));   // slots of the first tile before the range
+            hipLaunchKernelGGL(chain_tiles_kernel, dim3((uint32_t)((lvl0_end - t0 + kTile - 1) / kTile)), dim3(256), 0, st, jump, t0, lvl0_end, xh);
+            hipLaunchKernelGGL(chain_walk_kernel, dim3((nq + 63) / 64), dim3(64), 0, st, d_sm, d_qm, nq, d_qstart, xh, d_recb, d_rec, d_recc,
+                               d_counts);
+            if (n_rec)
+                hipLaunchKernelGGL(chain_emit_kernel, dim3((n_rec + 3) / 4), dim3(256), 0, st, d_recb, d_recc, d_rec, n_rec, d_recq, jump, xh, lvl0_end, mlist);
+        }
         VLG_HIP_TRY(hipGetLastError());
-    } else {
-        res->pieces.push_back(piece);
+        return VLG_OK;
     }
-    VLG_HIP_TRY(hipStreamSynchronize(st));     // qm / counts host buffers are read by the async copies above
-    jt.mark("  chunk: gather");
-    res->sum.n_matches += M;
-    res->sum.n_tuple_values += TV;
-    res->sum.n_chunks++;
-    res->sum.join_slots += T;
-    return VLG_OK;
+
+    // sizes of the result, then gather
+    vlg_status gather()
+    {
+        counts.resize(nq);
+        VLG_HIP_TRY(hipMemcpyAsync(counts.data(), d_counts, nq * 8, hipMemcpyDeviceToHost, st));
+        VLG_HIP_TRY(hipStreamSynchronize(st));
+        jt.mark("  chunk: link + chain");
+        uint64_t M = 0, TV = 0;
+        for (uint32_t i = 0; i < nq; ++i) {
+            qm[i].out_first = M; qm[i].out_tuple = TV;
+            M += counts[i]; TV += ws->tuples ? counts[i] * qm[i].k : 0;
+            res->counts[q0 + i] = counts[i];
+        }
+        piece.matches = M; piece.tuple_vals = TV;
+        if (M) {
+            piece.width = sizeof(pos_t);
+            VLG_HIP_TRY(result_alloc(&piece.d_first, M * sizeof(pos_t), &piece.first_bytes));
+            if (TV) VLG_HIP_TRY(result_alloc(&piece.d_tuples, TV * sizeof(pos_t), &piece.tuple_bytes));
+            res->pieces.push_back(piece);
+            jt.mark("  chunk: result malloc");
+            VLG_HIP_TRY(hipMemcpyAsync(d_qm, qm.data(), nq * sizeof(QueryMeta), hipMemcpyHostToDevice, st));
+            first_of.resize(nq);                                        // where every query's matches start, dense (the counts have been read: their place is free)
+            for (uint32_t i = 0; i < nq; ++i) first_of[i] = qm[i].out_first;
+            VLG_HIP_TRY(hipMemcpyAsync(d_counts, first_of.data(), nq * 8, hipMemcpyHostToDevice, st));
+            Timed t(ws, KS_GATHER, sizeof(pos_t) * (M + TV));
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(join_gather_kernel<pos_t>), dim3(runs_grid(M)), dim3(256), 0, st, P, d_sm, d_qm, d_counts, nq, M, link, mlist,
+                               static_cast<pos_t*>(piece.d_first), static_cast<pos_t*>(piece.d_tuples), d_stats + kStatsChecksum);
+            VLG_HIP_TRY(hipGetLastError());
+        } else {
+            res->pieces.push_back(piece);
+        }
+        VLG_HIP_TRY(hipStreamSynchronize(st));     // qm, counts and first_of are read by the async copies above
+        jt.mark("  chunk: gather");
+        res->sum.n_matches += M;
+        res->sum.n_tuple_values += TV;
+        res->sum.n_chunks++;
+        res->sum.join_slots += T;
+        return VLG_OK;
+    }
+};
+
+template <typename pos_t>
+vlg_status run_join_chunk(const vlg_queries* q, vlg_workspace* ws, vlg_result* res, uint64_t q0, uint64_t q1, const Plan& pl, const Lists<pos_t>& L,
+                          const Arena& A, unsigned long long* d_stats, const FilterGroup* fg)
+{
+    JoinChunk<pos_t> jc{q, ws, res, q0, q1, pl, L, A, d_stats, fg};
+    jc.survivor_tasks();
+    if (vlg_status s = jc.compact_survivors()) return s;
+    jc.jt.mark("  chunk: compaction launched");
+    jc.layout();
+    if (jc.empty) { res->pieces.push_back(jc.piece); return VLG_OK; }
+    jc.jt.mark("  chunk: host metadata");
+    if (vlg_status s = jc.carve()) return s;
+    if (vlg_status s = jc.upload()) return s;
+    if (vlg_status s = jc.link_classes()) return s;
+    if (vlg_status s = jc.chain()) return s;
+    return jc.gather();
 }
 
 // ---- planning and running the joins of the queries [Q0,Q1) over lists that are already in P --------------------------------
-// cost of a query in bytes of join scratch / in join slots, for list lengths given by occ_of(sub-pattern)
-template <class F>
-uint64_t join_bytes_of(const vlg_queries* q, uint64_t qi, F&& occ_of)
+// What joining query qi costs, for list lengths occ_of(sub-pattern): bytes of join scratch, join slots (slot indices are 32-bit inside
+// a chunk), and the survivors it puts into Pc in a chunk that compacts the lists compacted(sub-pattern) says it does.
+struct JoinCost { uint64_t bytes, slots, survivors; };
+template <class F, class C>
+JoinCost join_cost(const vlg_queries* q, uint64_t qi, F&& occ_of, C&& compacted)
 {
-    const bool uniform_k = q->kmin == q->kmax;
-    uint32_t k = (uint32_t)(q->qsub[qi + 1] - q->qsub[qi]);
-    uint64_t t = 0;
-    for (uint32_t i = 0; i < k; ++i) if (i + 1 < k || k == 1) t += occ_of(q->qsub[qi] + i);
+    const uint64_t a = q->qsub[qi];
+    const uint32_t k = (uint32_t)(q->qsub[qi + 1] - a);
+    uint64_t t = 0, first = 0, pc = 0;
+    for (uint32_t i = 0; i < k; ++i) {
+        const uint64_t e = occ_of(a + i);
+        if (i == 0) first = e;
+        if (i + 1 < k || k == 1) t += e;                              // the last list of a k>=2 query has no slots
+        if (compacted(a + i)) pc += e;
+    }
     // list-0 arrays cover the slot range of all lists 0, which is exactly those slots when every query has the same k
-    uint64_t t0s = k ? (uniform_k ? occ_of(q->qsub[qi]) : t) : 0;
-    return t * kJoinBytesPerSlot + t0s * kJoinBytesPerSlot0;
+    const uint64_t t0s = k ? (q->kmin == q->kmax ? first : t) : 0;
+    return {t * kJoinBytesPerSlot + t0s * kJoinBytesPerSlot0, t + 64ull * k /* class alignment slack */, pc};
 }
-template <class F>
-uint64_t join_slots_of(const vlg_queries* q, uint64_t qi, F&& occ_of)        // slot indices are 32-bit inside a chunk
+// ... on its full lists
+inline JoinCost join_cost(const vlg_queries* q, const Plan& pl, uint64_t qi)
 {
-    uint32_t k = (uint32_t)(q->qsub[qi + 1] - q->qsub[qi]);
-    uint64_t t = 64ull * k;                                           // class alignment slack
-    for (uint32_t i = 0; i < k; ++i) if (i + 1 < k || k == 1) t += occ_of(q->qsub[qi] + i);
-    return t;
+    return join_cost(q, qi, [&](uint64_t s) -> uint64_t { return pl.occ[s]; }, [](uint64_t) { return false; });
 }
 
 struct JoinPlan {
@@ -1558,7 +1628,6 @@ struct JoinPlan {
 vlg_status plan_joins(const vlg_queries* q, const Plan& pl, const vlg_workspace* ws, uint64_t Q0, uint64_t Q1, uint64_t join_budget,
                       uint64_t n_positions, JoinPlan& jp)
 {
-    auto full = [&](uint64_t s) -> uint64_t { return pl.occ[s]; };
     uint64_t logical_total = 0;
     jp.logical_max_query = 0;
     {
@@ -1566,7 +1635,7 @@ vlg_status plan_joins(const vlg_queries* q, const Plan& pl, const vlg_workspace*
         parallel_slices(Q0, Q1, 1u << 16, [&](uint64_t a, uint64_t b, uint32_t th) {
             uint64_t sum = 0, mx = 0;
             for (uint64_t qi = a; qi < b; ++qi) {
-                const uint64_t t = join_bytes_of(q, qi, full);
+                const uint64_t t = join_cost(q, pl, qi).bytes;
                 sum += t;
                 mx = std::max(mx, t);
             }
@@ -1615,8 +1684,7 @@ vlg_status plan_joins(const vlg_queries* q, const Plan& pl, const vlg_workspace*
         return fail(VLG_E_WORKSPACE, "a query needs " + std::to_string(jp.logical_max_query) + " bytes of join scratch; workspace cap allows " +
                                          std::to_string(cap_bytes));
     jp.want_bytes = std::min<uint64_t>(logical_total, cap_bytes);
-    jp.meta = (q->qsub[Q1] - q->qsub[Q0] + 4) * (sizeof(SegMeta) + 48) + (Q1 - Q0 + 4) * (sizeof(QueryMeta) + 96) +
-              (jp.want_bytes / 8192 + (Q1 - Q0) + 8) * 48 + (1ull << 20);
+    jp.meta = join_meta_bytes(q->qsub[Q1] - q->qsub[Q0], Q1 - Q0, jp.want_bytes);
     return VLG_OK;
 }
 
@@ -1648,31 +1716,17 @@ vlg_status run_joins(uint64_t n_positions, const vlg_queries* q, vlg_workspace* 
             if (fg.any) fgp = &fg;
             tr.mark("filter group");
         }
-        // one walk over the lists of a query: its join scratch (join_bytes_of), its slots (join_slots_of), the survivors it puts into Pc
-        const bool uniform_k = q->kmin == q->kmax;
-        auto cost_of = [&](uint64_t qi, uint64_t& bytes, uint64_t& slots, uint64_t& pc) {
-            const uint64_t a = q->qsub[qi];
-            const uint32_t k = (uint32_t)(q->qsub[qi + 1] - a);
-            uint64_t t = 0, first = 0;
-            pc = 0;
-            for (uint32_t i = 0; i < k; ++i) {
-                const uint64_t e = fgp ? fgp->eff[a + i - fgp->sub0] : pl.occ[a + i];
-                if (i == 0) first = e;
-                if (i + 1 < k || k == 1) t += e;
-                if (fgp && !fgp->speculated && fgp->cidx[a + i - fgp->sub0] != kNone) pc += e;      // (speculated: the survivors are in Pc already)
-            }
-            bytes = t * kJoinBytesPerSlot + (k ? (uniform_k ? first : t) : 0) * kJoinBytesPerSlot0;
-            slots = t + 64ull * k;
-        };
+        // list lengths as the chunks will see them; a chunk compacts its filtered lists itself unless the group has done so (speculated)
+        auto eff = [&](uint64_t s) -> uint64_t { return fgp ? fgp->eff[s - fgp->sub0] : pl.occ[s]; };
+        auto compacted = [&](uint64_t s) -> bool { return fgp && !fgp->speculated && fgp->cidx[s - fgp->sub0] != kNone; };
         uint64_t q0 = g0;
         while (q0 < g1) {
             uint64_t T = 0, S = 0, C = 0, q1 = q0;
             while (q1 < g1) {
-                uint64_t t, sl, pc;
-                cost_of(q1, t, sl, pc);
-                if (sl > max_chunk_slots) return fail(VLG_E_WORKSPACE, "a query has more than 2^32 join slots");
-                if (((T + t > jp.want_bytes || S + sl > max_chunk_slots || C + pc > pc_cap) && q1 > q0) || (q1 - q0) >= (1u << 22)) break;
-                T += t; S += sl; C += pc;
+                const JoinCost c = join_cost(q, q1, eff, compacted);
+                if (c.slots > max_chunk_slots) return fail(VLG_E_WORKSPACE, "a query has more than 2^32 join slots");
+                if (((T + c.bytes > jp.want_bytes || S + c.slots > max_chunk_slots || C + c.survivors > pc_cap) && q1 > q0) || (q1 - q0) >= (1u << 22)) break;
+                T += c.bytes; S += c.slots; C += c.survivors;
                 ++q1;
             }
             vlg_status s = run_join_chunk<pos_t>(q, ws, res, q0, q1, pl, L, GA, d_stats, fgp);
@@ -1770,7 +1824,7 @@ vlg_status plan_super_chunk(const vlg_index* idx, const vlg_queries* q, const Pl
         parallel_slices(Q0, Q1, 1u << 16, [&](uint64_t a, uint64_t b, uint32_t t) {
             uint64_t mx = 0, pv_sum = 0;
             for (uint64_t qi = a; qi < b; ++qi) {
-                mx = std::max(mx, join_bytes_of(q, qi, [&](uint64_t s) -> uint64_t { return pl.occ[s]; }));
+                mx = std::max(mx, join_cost(q, pl, qi).bytes);
                 uint32_t pv = 0;
                 if (count_pivots && filter_mode(q, pl, ws, qi, &pv) == 2) pv_sum += pl.occ[q->qsub[qi] + pv];
             }
@@ -1804,9 +1858,7 @@ vlg_status plan_super_chunk(const vlg_index* idx, const vlg_queries* q, const Pl
     cp.join_budget = budget > cp.phys_bytes ? budget - cp.phys_bytes : 0;
     // When the arena already holds whatever a plan can ask for (the caller reserved the whole cap), locate + sort are launched
     // first and the joins are planned while the GPU works; otherwise the plan decides how much to allocate.
-    const uint64_t meta_upper = (q->qsub[Q1] - q->qsub[Q0] + 4) * (sizeof(SegMeta) + 48) + (Q1 - Q0 + 4) * (sizeof(QueryMeta) + 96) +
-                                (budget / 8192 + (Q1 - Q0) + 8) * 48 + (1ull << 20);
-    cp.launch_first = ws->arena_bytes >= budget + meta_upper + 2 * fixed;
+    cp.launch_first = ws->arena_bytes >= budget + join_meta_bytes(q->qsub[Q1] - q->qsub[Q0], Q1 - Q0, budget) + 2 * fixed;
     return VLG_OK;
 }
 
@@ -1816,7 +1868,7 @@ std::vector<uint64_t> cut_queries(const vlg_queries* q, const Plan& pl, uint64_t
 {
     std::vector<uint64_t> cum(Q1 - Q0 + 1, 0);
     for (uint64_t qi = Q0; qi < Q1; ++qi)
-        cum[qi - Q0 + 1] = cum[qi - Q0] + 1 + (pl.occ[q->qsub[qi]] ? join_slots_of(q, qi, [&](uint64_t sidx) -> uint64_t { return pl.occ[sidx]; }) : 0);
+        cum[qi - Q0 + 1] = cum[qi - Q0] + 1 + (pl.occ[q->qsub[qi]] ? join_cost(q, pl, qi).slots : 0);
     auto cut_at = [&](int r) -> uint64_t {
         if (r <= 0) return Q0;
         if (r >= n_ranks) return Q1;
@@ -2053,6 +2105,20 @@ vlg_status plan_on_host(const vlg_queries* q, vlg_workspace* ws, const uint64_t*
     return VLG_OK;
 }
 
+// the result of a batch of n queries before anything ran: no match; k[i] = the sub-patterns of query i
+vlg_result* new_result(uint64_t n, const std::vector<uint64_t>& qsub)
+{
+    vlg_result* res = new vlg_result();
+    memset(&res->sum, 0, sizeof res->sum);
+    res->sum.n_queries = n;
+    res->counts.assign(n, 0);
+    res->k.resize(n);
+    for (uint64_t i = 0; i < n; ++i) res->k[i] = (uint32_t)(qsub[i + 1] - qsub[i]);
+    return res;
+}
+// the partial checksums of the gather kernel added up, modulo 2^64 like gm_search.cpp:110-114
+uint64_t fold_checksum(const unsigned long long* stats) { return std::accumulate(stats + kStatsChecksum, stats + kStatsWords, (uint64_t)0); }
+
 }  // namespace
 
 extern "C" vlg_status vlg_search_batch(const vlg_index* idx, const vlg_queries* q, vlg_workspace* ws, vlg_result** out)
@@ -2062,12 +2128,7 @@ extern "C" vlg_status vlg_search_batch(const vlg_index* idx, const vlg_queries* 
     if (!idx->is_int && q->sym_bytes != 1) return fail(VLG_E_INVALID, "integer-alphabet query batch: it takes an integer-alphabet index (vlg_index_build_int) or vlg_wtsa_*");
     if (idx->is_int && q->sym_bytes != 4 && q->nsub) return fail(VLG_E_INVALID, "an integer-alphabet index takes query batches parsed by vlg_queries_parse_int");
     hipStream_t st = ws->stream;
-    vlg_result* res = new vlg_result();
-    memset(&res->sum, 0, sizeof res->sum);
-    res->sum.n_queries = q->nq;
-    res->counts.assign(q->nq, 0);
-    res->k.resize(q->nq);
-    for (uint64_t i = 0; i < q->nq; ++i) res->k[i] = (uint32_t)(q->qsub[i + 1] - q->qsub[i]);
+    vlg_result* res = new_result(q->nq, q->qsub);
     uint64_t* d_l = nullptr;
     uint64_t* d_r = nullptr;
     unsigned long long* d_stats = nullptr;
@@ -2121,8 +2182,7 @@ extern "C" vlg_status vlg_search_batch(const vlg_index* idx, const vlg_queries* 
         VLG_HIP_TRY(hipStreamSynchronize(st));
         res->sum.lf_steps = hs[0];
         res->sum.wt_levels_locate = hs[1];
-        res->sum.checksum = 0;
-        for (uint32_t i = 0; i < kChecksumSlots; ++i) res->sum.checksum += hs[kStatsChecksum + i];      // modulo 2^64, like gm_search.cpp:110-114
+        res->sum.checksum = fold_checksum(hs);
         res->sum.wt_levels_bsearch = hs[3];
         // algorithmic bytes: 32 B per super-block read (+ one sample per occurrence)
         ws->stats[KS_LOCATE].algorithmic_bytes += 32ull * hs[1] + (uint64_t)idx->hdr.sample_bytes * ws->sample_reads;
@@ -2263,12 +2323,7 @@ extern "C" vlg_status vlg_join_batch(const uint64_t* d_lists, const uint64_t* h_
     qq.end_len.assign(h_end_len, h_end_len + n_joins);
     qq.kmax = 0; qq.kmin = 0xFFFFFFFFu;
     hipStream_t st = ws->stream;
-    vlg_result* res = new vlg_result();
-    memset(&res->sum, 0, sizeof res->sum);
-    res->sum.n_queries = n_joins;
-    res->counts.assign(n_joins, 0);
-    res->k.resize(n_joins);
-    for (uint64_t j = 0; j < n_joins; ++j) res->k[j] = (uint32_t)(qq.qsub[j + 1] - qq.qsub[j]);
+    vlg_result* res = new_result(n_joins, qq.qsub);
     unsigned long long* d_stats = nullptr;
     auto run = [&]() -> vlg_status {
         // (the plan's arrays are staged memory: they live inside the scope this runs in)
@@ -2349,8 +2404,7 @@ extern "C" vlg_status vlg_join_batch(const uint64_t* d_lists, const uint64_t* h_
         unsigned long long hs[kStatsWords];
         VLG_HIP_TRY(hipMemcpyAsync(hs, d_stats, sizeof hs, hipMemcpyDeviceToHost, st));
         VLG_HIP_TRY(hipStreamSynchronize(st));
-        res->sum.checksum = 0;
-        for (uint32_t i = 0; i < kChecksumSlots; ++i) res->sum.checksum += hs[kStatsChecksum + i];
+        res->sum.checksum = fold_checksum(hs);
         return VLG_OK;
     };
     vlg_status stt;

@@ -548,12 +548,7 @@ extern "C" vlg_status vlg_wtsa_search_batch(const vlg_wtsa* x, const vlg_queries
     hipStream_t st = ws->stream;
     const uint64_t nq = q->nq, nsub = q->nsub;
     if (nq > 0xFFFFFFF0ull) return fail(VLG_E_UNSUPPORTED, "too many queries in one batch");
-    vlg_result* res = new vlg_result();
-    memset(&res->sum, 0, sizeof res->sum);
-    res->sum.n_queries = nq;
-    res->counts.assign(nq, 0);
-    res->k.resize(nq);
-    for (uint64_t i = 0; i < nq; ++i) res->k[i] = (uint32_t)(q->qsub[i + 1] - q->qsub[i]);
+    vlg_result* res = new_result(nq, q->qsub);
     DevBuf d_mem;
     ResultPiece piece;
     piece.q0 = 0; piece.q1 = nq;
