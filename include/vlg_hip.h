@@ -367,6 +367,43 @@ vlg_status vlg_extract_batch(const vlg_text_access* t, const uint64_t* d_begin, 
  * isa_sample.sample_qeq, csa_sampling_strategy.hpp:650-663): d_out[j] = ISA[d_i[j]], fewer than d LF steps from the next sample.  A position >= n gives VLG_E_INVALID (d_out is then undefined).  Synchronises `stream`. */
 vlg_status vlg_isa_batch(const vlg_text_access* t, const uint64_t* d_i, uint64_t* d_out, uint64_t count, void* stream);
 
+/* Select.  A vlg_select_support holds, in HBM, what select needs beside a bit-vector or an index: select hints, `sample` ones (and
+ * zeros) apart -- the super-block that holds every sample-th one (zero) of every wavelet-tree node (byte index), of every
+ * wavelet-matrix level (integer index) or of the bit-vector; sample = 0 means 512, otherwise a power of two in [64, 65536]
+ * (VLG_E_INVALID for anything else).  At 512 the hints take 1/16 of the bytes of the plain bit-vectors they serve.  It replaces
+ * select_support_mcl<1> and <0> (include/sdsl/select_support_mcl.hpp:347-400), select_support_rrr<1> and <0>
+ * (include/sdsl/rrr_vector.hpp:638-700) and the select structures inside wt_pc / wt_int.  The handle does not change its source,
+ * which must outlive it; an index of any kind is taken (byte or integer alphabet, plain or rrr-63, SA-order or text-order sampling,
+ * built, loaded or attached).  Creation first reads the source's totals with blocking copies (the last block or header of a
+ * bit-vector; the node table, C or Z of an index: a few KiB), then uploads its tables and runs one pass over the super-block counts
+ * on `stream`, which it synchronises. */
+typedef struct vlg_select_support vlg_select_support;
+vlg_status vlg_bitvector_select_create(const vlg_bitvector* bv, uint32_t sample, void* stream, vlg_select_support** out);
+vlg_status vlg_rrr_bitvector_select_create(const vlg_rrr_bitvector* bv, uint32_t sample, void* stream, vlg_select_support** out);
+vlg_status vlg_index_select_create(const vlg_index* idx, uint32_t sample, void* stream, vlg_select_support** out);
+uint64_t vlg_select_support_hbm_bytes(const vlg_select_support* s);
+void vlg_select_support_destroy(vlg_select_support* s);
+/* select_support_mcl<bit>::select(k) (select_support_mcl.hpp:347-400; select_support_rrr<bit>::select, rrr_vector.hpp:638-700):
+ * d_out[j] = position of the d_k[j]-th `bit` (k = 1 .. number of them) of the bit-vector the support was made from; k = 0 or a k
+ * larger than that number gives nbits.  A support made from an index gives VLG_E_INVALID.  Asynchronous on `stream`. */
+vlg_status vlg_bit_select_batch(const vlg_select_support* s, int bit, const uint64_t* d_k, uint64_t* d_out, uint64_t count, void* stream);
+/* wt_pc::select(k, c) (include/sdsl/wt_pc.hpp:415-442) on the BWT of a byte index: d_out[j] = SA index of the d_k[j]-th occurrence of the
+ * text byte d_c[j] in the BWT (c = 0: the sentinel).  k = 0, a k larger than the number of occurrences, or a byte that does not occur
+ * gives n (wt_pc.hpp:418-420).  A support made from a bit-vector or from an integer index gives VLG_E_INVALID. */
+vlg_status vlg_wt_select_batch(const vlg_select_support* s, const uint64_t* d_k, const uint8_t* d_c, uint64_t* d_out, uint64_t count, void* stream);
+/* wt_int::select(k, c) (include/sdsl/wt_int.hpp:442-480) on the BWT of an integer index; symbols as vlg_int_rank_batch takes them (the
+ * original symbols, 0 = the sentinel).  The same refusals: n for k = 0, k too large, an absent symbol or one above the largest. */
+vlg_status vlg_int_select_batch(const vlg_select_support* s, const uint64_t* d_k, const uint32_t* d_sym, uint64_t* d_out, uint64_t count, void* stream);
+/* csa.psi[i] (psi_of_csa_wt::operator[], include/sdsl/suffix_array_helper.hpp:322-332) = wt.select(i - C[comp(F[i])] + 1, F[i]), byte and
+ * integer indexes: d_out[j] = ISA[(SA[d_i[j]] + 1) mod n].  An i >= n gives ~0. */
+vlg_status vlg_psi_batch(const vlg_select_support* s, const uint64_t* d_i, uint64_t* d_out, uint64_t count, void* stream);
+/* csa.lf[i] (lf_of_csa_wt::operator[], suffix_array_helper.hpp:336-349) and csa.bwt[i] (bwt_of_csa_wt::operator[], :425-429): the LF step
+ * of the locate kernels, byte and integer indexes, no support needed.  lf: d_out[j] = ISA[(SA[d_i[j]] - 1) mod n], ~0 for i >= n.
+ * bwt: d_out holds uint8_t (byte index, comp2char applied) or uint32_t original symbols (integer index), as vlg_extract_batch
+ * writes them; the sentinel and an i >= n give 0. */
+vlg_status vlg_lf_batch(const vlg_index* idx, const uint64_t* d_i, uint64_t* d_out, uint64_t count, void* stream);
+vlg_status vlg_bwt_batch(const vlg_index* idx, const uint64_t* d_i, void* d_out, uint64_t count, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Query batches.  Parsing mirrors the reference's two dialects:
  *   VLG_DIALECT_LIBRARY   gapped_pattern_query(const std::string&)   include/sdsl/vlg_index.hpp:54-105

@@ -142,6 +142,17 @@ SYMBOLS = [
     ("vlg_text_access_destroy", None, [_P]),
     ("vlg_extract_batch", _I, [_P, _P, _P, _P, _U64, _U64, _P, _P]),
     ("vlg_isa_batch", _I, [_P, _P, _P, _U64, _P]),
+    ("vlg_bitvector_select_create", _I, [_P, C.c_uint32, _P, C.POINTER(_P)]),
+    ("vlg_rrr_bitvector_select_create", _I, [_P, C.c_uint32, _P, C.POINTER(_P)]),
+    ("vlg_index_select_create", _I, [_P, C.c_uint32, _P, C.POINTER(_P)]),
+    ("vlg_select_support_hbm_bytes", _U64, [_P]),
+    ("vlg_select_support_destroy", None, [_P]),
+    ("vlg_bit_select_batch", _I, [_P, _I, _P, _P, _U64, _P]),
+    ("vlg_wt_select_batch", _I, [_P, _P, _P, _P, _U64, _P]),
+    ("vlg_int_select_batch", _I, [_P, _P, _P, _P, _U64, _P]),
+    ("vlg_psi_batch", _I, [_P, _P, _P, _U64, _P]),
+    ("vlg_lf_batch", _I, [_P, _P, _P, _U64, _P]),
+    ("vlg_bwt_batch", _I, [_P, _P, _P, _U64, _P]),
     ("vlg_parse_query", _I, [C.c_char_p, _U64, _I, C.POINTER(ParsedQuery)]),
     ("vlg_queries_parse", _I, [C.c_char_p, _P, _U64, _I, _P, C.POINTER(_P)]),
     ("vlg_queries_create", _I, [_P, _P, _P, _P, _P, _P, _U64, C.POINTER(_P)]),

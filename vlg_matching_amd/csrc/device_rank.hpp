@@ -4,6 +4,7 @@
 #pragma once
 #include "common.hpp"
 #include "rrr_code.hpp"
+#include "select_code.hpp"
 
 namespace vlg {
 
@@ -79,6 +80,34 @@ __device__ __forceinline__ bool member_probe(const Block* __restrict__ member, u
     return bit != 0;
 }
 
+// ---- the super-block search of a select (select.hpp) ----------------------------------------------------------------------------
+// hints: of one node and one bit value -- entry j is the node's super-block that holds its (j << shift) + 1-th such bit, and one entry
+// more closes the list with the node's last super-block.  The k-th bit (1 <= k <= how many the node has) therefore lies in a
+// super-block of [hints[(k - 1) >> shift], the entry after it]: the largest one there with fewer than k such bits in front of it.
+// A long range (a sparse node: neighbouring hints may lie 10^5 super-blocks apart) is halved, one dependent 4-byte read per step, until
+// eight candidates are left; those are read with eight independent loads and counted.  ones_before(b): the node's ones in front of
+// its super-block b; bits_per_sb: 224 (plain) or 2016 (rrr-63).
+template <class OnesBefore>
+__device__ __forceinline__ uint32_t select_superblock(const uint32_t* __restrict__ hints, uint32_t shift, uint32_t bits_per_sb, uint32_t bit, uint64_t k,
+                                                      const OnesBefore& ones_before)
+{
+    const uint64_t j = (k - 1) >> shift;
+    uint32_t lo = hints[j], hi = hints[j + 1];
+    if (hi < lo) hi = lo;                                      // (never in a support built from its source; keeps every read inside [lo, hi])
+    auto before = [&](uint32_t b) -> uint64_t { const uint64_t c = ones_before(b); return bit ? c : (uint64_t)b * bits_per_sb - c; };
+    while (hi - lo > 8) {
+        const uint32_t mid = lo + (hi - lo + 1) / 2;
+        if (before(mid) < k) lo = mid; else hi = mid - 1;
+    }
+    uint32_t add = 0;
+#pragma unroll
+    for (uint32_t t = 1; t <= 8; ++t) {
+        const uint32_t b = lo + t < hi ? lo + t : hi;          // (clamped: a read past the range never leaves the node)
+        add += (lo + t <= hi && before(b) < k) ? 1u : 0u;
+    }
+    return lo + add;
+}
+
 // ---- bit-vector policies: how one node-relative (rank1, bit) pair is obtained -----------------------------------
 // (View: IndexView, or the integer index's IntView -- whatever carries `blocks` / `rrr_hdr`, `rrr_stream`, `rrr_tables`)
 // Plain: one 256-bit super-block read (K1).
@@ -103,7 +132,32 @@ struct PlainBV {
     {
         return node_rank1(iv.blocks, base, i);
     }
+    // position in node `base` of its k-th `bit`, 1 <= k <= how many it has (select_support_mcl<bit>::select,
+    // include/sdsl/select_support_mcl.hpp:347-400): the hinted super-block search, then select224 on the block's words
+    template <class View> static __device__ __forceinline__ uint64_t select(const View& iv, const Shared&, uint32_t base, const uint32_t* __restrict__ hints,
+                                                                           uint32_t shift, uint32_t bit, uint64_t k)
+    {
+        const Block* node = iv.blocks + base;
+        const uint32_t b = select_superblock(hints, shift, kBlockBits, bit, k, [&](uint32_t x) { return node[x].cnt; });
+        const BlockRegs r = load_block(node, b);
+        const uint32_t kk = (uint32_t)(k - (bit ? (uint64_t)r.c.w : (uint64_t)b * kBlockBits - r.c.w));
+        const uint32_t m = bit ? 0u : ~0u;
+        return (uint64_t)b * kBlockBits + select224(r.a.x ^ m, r.a.y ^ m, r.a.z ^ m, r.a.w ^ m, r.c.x ^ m, r.c.y ^ m, r.c.z ^ m, kk);
+    }
 };
+
+// `len` bits (0 .. 64) of an rrr offset stream from bit position ptr on: the offset of one block, for both rrr layouts (the index's and K6's)
+__device__ __forceinline__ uint64_t rrr_stream_bits(const uint64_t* __restrict__ stream, uint64_t ptr, uint32_t len)
+{
+    uint64_t o = 0;
+    if (len) {
+        const uint64_t w = ptr >> 6, sh = ptr & 63;
+        o = stream[w] >> sh;
+        if (sh + len > 64) o |= stream[w + 1] << (64 - sh);
+        o &= (len == 64) ? ~0ull : ((1ull << len) - 1);
+    }
+    return o;
+}
 
 // rrr-63: 32-byte header {ones before, offset word position, 32 x 6-bit classes} per 32 blocks of 63 bits, offsets in a bit stream
 // (each super-block's offsets start on a word) -- the sizes of rrr_vector<63> (include/sdsl/rrr_vector.hpp:145-237; rank:
@@ -147,13 +201,7 @@ struct RrrBV {
         if (kBit || off) {
             const uint32_t k = (uint32_t)c0 & 63u;
             const uint32_t len = s.t.space[k];
-            uint64_t o = 0;
-            if (len) {
-                const uint64_t w = ptr >> 6, sh = ptr & 63;
-                o = iv.rrr_stream[w] >> sh;
-                if (sh + len > 64) o |= iv.rrr_stream[w + 1] << (64 - sh);
-                o &= (len == 64) ? ~0ull : ((1ull << len) - 1);
-            }
+            const uint64_t o = rrr_stream_bits(iv.rrr_stream, ptr, len);
             rank += rrr_dec63(s.t, k, o, off, bit);
         }
         r1 = rank;
@@ -173,6 +221,33 @@ struct RrrBV {
         uint64_t r1; uint32_t bit;
         decode<false>(iv, s, base, i, r1, bit);
         return r1;
+    }
+    // position in node `base` of its k-th `bit` (select_support_rrr<bit, 63>::select, include/sdsl/rrr_vector.hpp:638-700): the hinted
+    // search over the headers' "ones before" words, the 32 classes of the super-block walked up to the block that holds the bit
+    // (a block past the node's end holds zeros only and is never reached: k counts bits of the node), rrr_select63 inside it
+    template <class View> static __device__ __forceinline__ uint64_t select(const View& iv, const Shared& s, uint32_t base, const uint32_t* __restrict__ hints,
+                                                                           uint32_t shift, uint32_t bit, uint64_t k)
+    {
+        const uint4* node = iv.rrr_hdr + 2 * (uint64_t)base;
+        const uint32_t sb = select_superblock(hints, shift, kRrrSuperBits, bit, k, [&](uint32_t x) { return node[2 * (uint64_t)x].x; });
+        const uint4 h0 = node[2 * (uint64_t)sb], h1 = node[2 * (uint64_t)sb + 1];
+        uint32_t kk = (uint32_t)(k - (bit ? (uint64_t)h0.x : (uint64_t)sb * kRrrSuperBits - h0.x));
+        uint64_t ptr = (uint64_t)h0.y << 6;
+        uint64_t c0 = (uint64_t)h0.z | ((uint64_t)h0.w << 32), c1 = (uint64_t)h1.x | ((uint64_t)h1.y << 32),
+                 c2 = (uint64_t)h1.z | ((uint64_t)h1.w << 32);
+        uint32_t blk = 0;
+        for (; blk < kRrrBlocksPerSuper - 1; ++blk) {
+            const uint32_t cls = (uint32_t)c0 & 63u, have = bit ? cls : kRrrBlockBits - cls;
+            if (kk <= have) break;
+            kk -= have;
+            ptr += s.t.space[cls];
+            c0 = (c0 >> 6) | (c1 << 58);
+            c1 = (c1 >> 6) | (c2 << 58);
+            c2 >>= 6;
+        }
+        const uint32_t cls = (uint32_t)c0 & 63u, len = s.t.space[cls];
+        const uint64_t o = rrr_stream_bits(iv.rrr_stream, ptr, len);
+        return (uint64_t)sb * kRrrSuperBits + blk * kRrrBlockBits + rrr_select63(s.t, cls, o, bit, kk);
     }
 };
 

@@ -22,6 +22,7 @@
 // (the suffix sorter sees five bytes per symbol).
 #pragma once
 #include "extract.hpp"
+#include "select.hpp"
 #include "sweep_kernels.hpp"
 
 namespace {
@@ -357,6 +358,47 @@ __global__ void __launch_bounds__(256) int_isa_kernel(IntView v, uint32_t d, con
     isa_queries(p, out, count, v.n, d, isa, IntWalk<BV>{v, sZ}, bad);
 }
 
+// ---- select (select.hpp): wt_int::select, csa.psi, csa.lf and csa.bwt on the wavelet matrix -----------------------------------------------
+// sym non-null: wt_int::select(arg[j], sym[j]) on raw symbols (absent symbol, k = 0 or k past its count: n); sym null: csa.psi[arg[j]]
+template <class BV>
+__global__ void __launch_bounds__(256) int_select_kernel(IntView v, SelView sv, const uint64_t* __restrict__ arg, const uint32_t* __restrict__ sym,
+                                                         uint64_t* __restrict__ out, uint64_t count)
+{
+    __shared__ IntLds<BV> sZ;
+    stage_int(sZ, v);
+    for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < count; j += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t a = arg[j];
+        uint32_t cc;
+        uint64_t k;
+        if (sym) {
+            const uint32_t c = sym[j];
+            cc = int_char2comp(v, c);
+            k = a;
+            if ((cc == 0 && c > 0) || k == 0 || k > v.C[cc + 1] - v.C[cc]) { out[j] = v.n; continue; }
+        } else {
+            if (a >= v.n) { out[j] = ~0ull; continue; }
+            cc = first_column(v.C, v.sigma, a);
+            k = a - v.C[cc] + 1;
+        }
+        out[j] = v.n_levels ? int_select<BV>(v, sZ, sv, cc, k) : k - 1;      // (only the sentinel: no level)
+    }
+}
+template <class BV>
+__global__ void __launch_bounds__(256) int_lf_bwt_kernel(IntView v, const uint64_t* __restrict__ in, uint64_t* __restrict__ out_lf, uint32_t* __restrict__ out_bwt,
+                                                         uint64_t count)
+{
+    __shared__ IntLds<BV> sZ;
+    stage_int(sZ, v);
+    const IntWalk<BV> walk{v, sZ};
+    for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < count; j += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t i = in[j];
+        uint32_t c = 0;
+        const uint64_t r = i < v.n ? walk.lf(i, c) : ~0ull;
+        if (out_lf) out_lf[j] = r;
+        if (out_bwt) out_bwt[j] = i < v.n ? walk.sym(c) : 0u;
+    }
+}
+
 }  // namespace
 
 namespace vlg {
@@ -644,6 +686,22 @@ vlg_status launch_int_isa_samples(const IntView& v, uint32_t inv_dens, uint32_t*
     return VLG_OK;
 }
 
+vlg_status launch_int_select(const IntView& v, const SelView& sv, const uint64_t* d_arg, const uint32_t* d_sym, uint64_t* d_out, uint64_t count, hipStream_t st)
+{
+    if (!count) return VLG_OK;
+    if (v.bv_kind == kBvRrr63) hipLaunchKernelGGL(HIP_KERNEL_NAME(int_select_kernel<RrrBV>), launch_grid(count, 8192), dim3(256), 0, st, v, sv, d_arg, d_sym, d_out, count);
+    else hipLaunchKernelGGL(HIP_KERNEL_NAME(int_select_kernel<PlainBV>), launch_grid(count, 8192), dim3(256), 0, st, v, sv, d_arg, d_sym, d_out, count);
+    VLG_HIP_TRY(hipGetLastError());
+    return VLG_OK;
+}
+vlg_status launch_int_lf_bwt(const IntView& v, const uint64_t* d_i, uint64_t* d_lf, uint32_t* d_bwt, uint64_t count, hipStream_t st)
+{
+    if (!count) return VLG_OK;
+    if (v.bv_kind == kBvRrr63) hipLaunchKernelGGL(HIP_KERNEL_NAME(int_lf_bwt_kernel<RrrBV>), launch_grid(count, 8192), dim3(256), 0, st, v, d_i, d_lf, d_bwt, count);
+    else hipLaunchKernelGGL(HIP_KERNEL_NAME(int_lf_bwt_kernel<PlainBV>), launch_grid(count, 8192), dim3(256), 0, st, v, d_i, d_lf, d_bwt, count);
+    VLG_HIP_TRY(hipGetLastError());
+    return VLG_OK;
+}
 vlg_status launch_int_extract(const IntView& v, const ExtractJob& job, const uint32_t* d_isa, uint32_t* d_out, hipStream_t st)
 {
     const dim3 grid = launch_grid(job.n_segs, 8192);

@@ -7,6 +7,7 @@
 #include "kernels.hpp"
 #include "sweep_kernels.hpp"
 #include "extract.hpp"
+#include "select.hpp"
 #include <rocprim/rocprim.hpp>
 
 using namespace vlg;
@@ -154,6 +155,18 @@ struct RrrLds {
     uint8_t space[64];
 };
 
+// the binomial table into LDS and, from its row 63, the offset widths (every K6 kernel starts with this; ends with a barrier)
+__device__ __forceinline__ void stage_rrr_lds(RrrLds& s, const uint64_t* __restrict__ binom)
+{
+    for (uint32_t i = threadIdx.x; i < 64 * 64; i += blockDim.x) (&s.binom[0][0])[i] = binom[i];
+    __syncthreads();
+    if (threadIdx.x < 64) {                      // space_for_bt: bits of C(63,k), 0 for the two uniform classes
+        uint64_t c = s.binom[63][threadIdx.x];
+        s.space[threadIdx.x] = (c == 1) ? 0 : (uint8_t)(64 - __clzll((long long)c));
+    }
+    __syncthreads();
+}
+
 __device__ __forceinline__ uint32_t rrr_class(uint64_t c0, uint64_t c1, uint64_t c2, uint32_t j)
 {
     uint32_t bit = 6u * j;                       // classes are packed little-endian into 192 bits
@@ -170,13 +183,7 @@ __global__ void __launch_bounds__(256) rrr_rank_kernel(const uint4* __restrict__
                                                        uint64_t* __restrict__ out, uint64_t count)
 {
     __shared__ RrrLds s;
-    for (uint32_t i = threadIdx.x; i < 64 * 64; i += blockDim.x) (&s.binom[0][0])[i] = binom[i];
-    __syncthreads();
-    if (threadIdx.x < 64) {                      // space_for_bt: bits of C(63,k), 0 for the two uniform classes
-        uint64_t c = s.binom[63][threadIdx.x];
-        s.space[threadIdx.x] = (c == 1) ? 0 : (uint8_t)(64 - __clzll((long long)c));
-    }
-    __syncthreads();
+    stage_rrr_lds(s, binom);
     for (uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; q < count; q += (uint64_t)gridDim.x * blockDim.x) {
         const uint64_t i = idx[q];
         const uint64_t sb = i / (kRrrBlock * kRrrSuper);
@@ -195,13 +202,7 @@ __global__ void __launch_bounds__(256) rrr_rank_kernel(const uint4* __restrict__
         if (off) {
             uint32_t k = rrr_class(c0, c1, c2, blk);
             const uint32_t len = s.space[k];
-            uint64_t nr = 0;
-            if (len) {
-                const uint64_t w = ptr >> 6, o = ptr & 63;
-                nr = stream[w] >> o;
-                if (o + len > 64) nr |= stream[w + 1] << (64 - o);
-                nr &= (len == 64) ? ~0ull : ((1ull << len) - 1);
-            }
+            uint64_t nr = rrr_stream_bits(stream, ptr, len);
             // decode_popcount (rrr_helper.hpp:411-460): walk the block from bit 0, C(nn-1,k) decides each bit
             uint32_t ones = 0;
             if (k == kRrrBlock) ones = off;
@@ -1556,4 +1557,411 @@ extern "C" vlg_status vlg_isa_batch(const vlg_text_access* t, const uint64_t* d_
     if (e != hipSuccess) return fail(VLG_E_NO_DEVICE, std::string("isa: ") + hipGetErrorString(e));
     if (h_bad) return fail(VLG_E_INVALID, std::to_string(h_bad) + " ISA position(s) >= n");
     return VLG_OK;
+}
+
+// ---- select (select.hpp): select_support_mcl / select_support_rrr on a bit-vector, wt_pc::select / wt_int::select, csa.psi, csa.lf, csa.bwt --
+struct vlg_select_support {
+    int kind = 0;                                                  // kSelPlainBv, kSelRrrBv, kSelIndex
+    const vlg_bitvector* bv = nullptr;
+    const vlg_rrr_bitvector* rrr = nullptr;
+    const vlg_index* idx = nullptr;
+    SelView view{};
+    void* d_mem = nullptr;                                         // nodes, leaf_up, the hint pass's lists, hints: one allocation
+    uint64_t bytes = 0;
+};
+
+namespace {
+
+constexpr int kSelPlainBv = 0, kSelRrrBv = 1, kSelIndex = 2;
+
+template <class Counts>
+__global__ void __launch_bounds__(256) select_hints_kernel(Counts src, const SelNode* __restrict__ nodes, const uint32_t* __restrict__ list,
+                                                           const uint64_t* __restrict__ first, uint32_t n_list, uint32_t shift, uint32_t* __restrict__ hints)
+{
+    select_build_hints(src, nodes, list, first, n_list, shift, hints);
+}
+
+// K1's view of a stand-alone bit-vector, as the plain policy reads an index
+struct BitsView {
+    const Block* blocks;
+};
+
+template <int kBit>
+__global__ void __launch_bounds__(256) bit_select_kernel(BitsView bv, SelView sv, const uint64_t* __restrict__ k, uint64_t* __restrict__ out, uint64_t count)
+{
+    const PlainBV::Shared sh{};
+    for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < count; j += (uint64_t)gridDim.x * blockDim.x)
+        out[j] = bit_select<PlainBV>(bv, sh, sv, (uint32_t)kBit, k[j]);
+}
+
+// select_support_rrr on K6's layout: the header search of the rrr policy, the classes of the super-block, then the block decoded bit
+// by bit as K6 numbers it (rrr_select63_seq), the binomial table in LDS as in rrr_rank_kernel
+template <int kBit>
+__global__ void __launch_bounds__(256) rrr_bit_select_kernel(const uint4* __restrict__ hdr, const uint64_t* __restrict__ stream, const uint64_t* __restrict__ binom,
+                                                             SelView sv, const uint64_t* __restrict__ k_in, uint64_t* __restrict__ out, uint64_t count)
+{
+    __shared__ RrrLds s;
+    stage_rrr_lds(s, binom);
+    constexpr uint32_t bit = (uint32_t)kBit;
+    const SelNode nd = sv.nodes[0];
+    const uint64_t have = bit ? nd.ones : nd.size - nd.ones;
+    const uint32_t* hints = sv.hints + (bit ? nd.h1 : nd.h0);
+    for (uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; q < count; q += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t k = k_in[q];
+        if (k == 0 || k > have) { out[q] = nd.size; continue; }
+        const uint32_t sb = select_superblock(hints, sv.shift, kRrrBlock * kRrrSuper, bit, k, [&](uint32_t x) { return hdr[2 * (uint64_t)x].x; });
+        const uint4 h0 = hdr[2 * (uint64_t)sb], h1 = hdr[2 * (uint64_t)sb + 1];
+        uint32_t kk = (uint32_t)(k - (bit ? (uint64_t)h0.x : (uint64_t)sb * (kRrrBlock * kRrrSuper) - h0.x));
+        uint64_t ptr = h0.y;
+        const uint64_t c0 = (uint64_t)h0.z | ((uint64_t)h0.w << 32), c1 = (uint64_t)h1.x | ((uint64_t)h1.y << 32),
+                       c2 = (uint64_t)h1.z | ((uint64_t)h1.w << 32);
+        uint32_t blk = 0, cls = rrr_class(c0, c1, c2, 0);
+        for (; blk < kRrrSuper - 1; ++blk) {
+            const uint32_t n_here = bit ? cls : kRrrBlock - cls;
+            if (kk <= n_here) break;
+            kk -= n_here;
+            ptr += s.space[cls];
+            cls = rrr_class(c0, c1, c2, blk + 1);
+        }
+        const uint32_t len = s.space[cls];
+        const uint64_t nr = rrr_stream_bits(stream, ptr, len);
+        out[q] = (uint64_t)sb * (kRrrBlock * kRrrSuper) + blk * kRrrBlock + rrr_select63_seq(&s.binom[0][0], cls, nr, bit, kk);
+    }
+}
+
+// wt_pc::select(k, c) for text bytes c (kPsi = false), or csa.psi[i] = select(i - C[F[i]] + 1, F[i]) (kPsi = true: `arg` holds i)
+template <class BV, bool kPsi>
+__global__ void __launch_bounds__(256) wt_select_kernel(IndexView iv, SelView sv, const uint64_t* __restrict__ arg, const uint8_t* __restrict__ sym,
+                                                        uint64_t* __restrict__ out, uint64_t count)
+{
+    __shared__ uint64_t sC[257];
+    __shared__ typename BV::Shared sh;
+    for (uint32_t i = threadIdx.x; i <= iv.sigma; i += blockDim.x) sC[i] = iv.C[i];
+    BV::stage(sh, iv);
+    __syncthreads();
+    for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < count; j += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t a = arg[j];
+        if (kPsi) {
+            if (a >= iv.n) { out[j] = ~0ull; continue; }
+            const uint32_t c = first_column(sC, iv.sigma, a);
+            out[j] = byte_select<BV>(iv, sh, sv, c, a - sC[c] + 1);
+        } else {
+            const uint8_t ch = sym[j];
+            const uint32_t c = iv.char2comp[ch];
+            const bool present = ch == 0 || c != 0;                // wt_pc.hpp:418-420
+            out[j] = (present && a >= 1 && a <= sC[c + 1] - sC[c]) ? byte_select<BV>(iv, sh, sv, c, a) : iv.n;
+        }
+    }
+}
+
+// csa.lf[i] and csa.bwt[i]: one LF step of lf_walk.hpp per lane; either output may be null
+template <class BV, bool kWide>
+__global__ void __launch_bounds__(256) lf_bwt_kernel(IndexView iv, const uint64_t* __restrict__ in, uint64_t* __restrict__ out_lf, uint8_t* __restrict__ out_bwt,
+                                                     uint64_t count)
+{
+    __shared__ WalkLds<BV> s;
+    __shared__ uint8_t c2c[256];
+    c2c[threadIdx.x] = 0;
+    __syncthreads();
+    { const uint32_t ch = threadIdx.x, c = iv.char2comp[ch]; if (ch == 0 || c != 0) c2c[c] = (uint8_t)ch; }      // comp2char (256 threads)
+    stage_walk(s, iv);
+    const ByteWalk<BV, kWide> walk{iv, s, c2c};
+    for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < count; j += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t i = in[j];
+        uint32_t c = 0;
+        const uint64_t r = i < iv.n ? walk.lf(i, c) : ~0ull;
+        if (out_lf) out_lf[j] = r;
+        if (out_bwt) out_bwt[j] = i < iv.n ? walk.sym(c) : (uint8_t)0;
+    }
+}
+
+bool select_sample_shift(uint32_t sample, uint32_t& shift)
+{
+    const uint32_t s = sample ? sample : kSelectSampleDefault;
+    if (s < kSelectSampleMin || s > kSelectSampleMax || (s & (s - 1))) return false;
+    shift = 31u - (uint32_t)__builtin_clz(s);
+    return true;
+}
+
+// Lay the handle out, upload its tables and run the hint pass.  nodes: every SelNode with size, ones, base, nb, up set (nb = 0: no
+// bit-vector, a leaf); hint offsets are assigned here.  run(nodes, list, first, n_list, hints) launches the pass for the source's layout.
+template <class Run>
+vlg_status select_support_finish(vlg_select_support* s, std::vector<SelNode>& nodes, const std::vector<uint32_t>& leaf_up, uint32_t shift, hipStream_t st,
+                                 const Run& run)
+{
+    std::vector<uint32_t> list;
+    std::vector<uint64_t> first(1, 0);
+    uint64_t n_hints = 0;
+    for (uint32_t v = 0; v < nodes.size(); ++v) {
+        if (!nodes[v].nb) continue;
+        nodes[v].h1 = n_hints; n_hints += select_hint_count(nodes[v].ones, shift);
+        nodes[v].h0 = n_hints; n_hints += select_hint_count(nodes[v].size - nodes[v].ones, shift);
+        list.push_back(v);
+        first.push_back(first.back() + nodes[v].nb);
+    }
+    const uint64_t off_nodes = 0, off_leaf = align_up(off_nodes + std::max<size_t>(nodes.size(), 1) * sizeof(SelNode), 256),
+                   off_list = align_up(off_leaf + std::max<size_t>(leaf_up.size(), 1) * 4, 256), off_first = align_up(off_list + std::max<size_t>(list.size(), 1) * 4, 256),
+                   off_hints = align_up(off_first + first.size() * 8, 256);
+    s->bytes = align_up(off_hints + std::max<uint64_t>(n_hints, 1) * 4, 256);
+    if (hipMalloc(&s->d_mem, s->bytes) != hipSuccess) { s->d_mem = nullptr; return fail(VLG_E_OOM, "select support: " + std::to_string(s->bytes) + " bytes"); }
+    uint8_t* b = reinterpret_cast<uint8_t*>(s->d_mem);
+    s->view.nodes = reinterpret_cast<const SelNode*>(b + off_nodes);
+    s->view.leaf_up = reinterpret_cast<const uint32_t*>(b + off_leaf);
+    s->view.hints = reinterpret_cast<const uint32_t*>(b + off_hints);
+    s->view.shift = shift;
+    s->view.n_nodes = (uint32_t)nodes.size();
+    if (!nodes.empty()) VLG_HIP_TRY(hipMemcpyAsync(b + off_nodes, nodes.data(), nodes.size() * sizeof(SelNode), hipMemcpyHostToDevice, st));
+    if (!leaf_up.empty()) VLG_HIP_TRY(hipMemcpyAsync(b + off_leaf, leaf_up.data(), leaf_up.size() * 4, hipMemcpyHostToDevice, st));
+    if (!list.empty()) VLG_HIP_TRY(hipMemcpyAsync(b + off_list, list.data(), list.size() * 4, hipMemcpyHostToDevice, st));
+    VLG_HIP_TRY(hipMemcpyAsync(b + off_first, first.data(), first.size() * 8, hipMemcpyHostToDevice, st));
+    VLG_HIP_TRY(hipMemsetAsync(b + off_hints, 0, std::max<uint64_t>(n_hints, 1) * 4, st));
+    if (!list.empty()) {
+        run(s->view.nodes, reinterpret_cast<const uint32_t*>(b + off_list), reinterpret_cast<const uint64_t*>(b + off_first), (uint32_t)list.size(),
+            reinterpret_cast<uint32_t*>(b + off_hints), launch_grid(first.back(), 8192));
+        VLG_HIP_TRY(hipGetLastError());
+    }
+    VLG_HIP_TRY(hipStreamSynchronize(st));                         // (the host tables are read until here)
+    return VLG_OK;
+}
+
+vlg_status select_create_checks(const void* src, uint32_t sample, vlg_select_support** out, uint32_t& shift)
+{
+    if (!src || !out) return fail(VLG_E_INVALID, "null argument");
+    *out = nullptr;
+    if (!select_sample_shift(sample, shift))
+        return fail(VLG_E_INVALID, "select support: sample must be 0 (the default, 512) or a power of two in [64, 65536]");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(VLG_E_NO_DEVICE, "no HIP device available");
+    return VLG_OK;
+}
+
+using SelectPtr = Building<vlg_select_support, vlg_select_support_destroy>;
+
+}  // namespace
+
+extern "C" vlg_status vlg_bitvector_select_create(const vlg_bitvector* bv, uint32_t sample, void* stream, vlg_select_support** out)
+{
+    uint32_t shift = 0;
+    if (vlg_status st = select_create_checks(bv, sample, out, shift)) return st;
+    SelectPtr s(new vlg_select_support());
+    s->kind = kSelPlainBv;
+    s->bv = bv;
+    // ones of the whole vector: the count before the last block + its popcount (bv_pack_kernel leaves the bits past nbits zero).  A
+    // blocking read of 32 bytes: the source was synchronised when it was created; everything after it runs on `stream`.
+    uint64_t ones = 0;
+    {
+        Block last;
+        VLG_HIP_TRY(hipMemcpy(&last, bv->d_blocks + (bv->n_blocks - 1), sizeof(Block), hipMemcpyDeviceToHost));
+        ones = last.cnt;
+        for (uint32_t w = 0; w < 7; ++w) ones += (uint32_t)__builtin_popcount(last.w[w]);
+    }
+    std::vector<SelNode> nodes(1, SelNode{bv->nbits, ones, 0, 0, 0, (uint32_t)bv->n_blocks, kSelNoParent, 0});
+    const PlainCounts src{bv->d_blocks};
+    hipStream_t st = (hipStream_t)stream;
+    if (vlg_status r = select_support_finish(s.get(), nodes, {}, shift, st, [&](const SelNode* nd, const uint32_t* list, const uint64_t* first, uint32_t n_list,
+                                                                                 uint32_t* hints, dim3 grid) {
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(select_hints_kernel<PlainCounts>), grid, dim3(256), 0, st, src, nd, list, first, n_list, shift, hints);
+        })) return r;
+    *out = s.release();
+    return VLG_OK;
+}
+
+extern "C" vlg_status vlg_rrr_bitvector_select_create(const vlg_rrr_bitvector* bv, uint32_t sample, void* stream, vlg_select_support** out)
+{
+    uint32_t shift = 0;
+    if (vlg_status st = select_create_checks(bv, sample, out, shift)) return st;
+    SelectPtr s(new vlg_select_support());
+    s->kind = kSelRrrBv;
+    s->rrr = bv;
+    // ones before the last super-block + its 32 classes (blocks past nbits are class 0); a blocking read of 32 bytes, as above
+    uint64_t ones = 0;
+    {
+        uint32_t H[8];
+        VLG_HIP_TRY(hipMemcpy(H, bv->d_hdr + 2 * (bv->n_sb - 1), 32, hipMemcpyDeviceToHost));
+        ones = H[0];
+        const uint64_t c[3] = {(uint64_t)H[2] | ((uint64_t)H[3] << 32), (uint64_t)H[4] | ((uint64_t)H[5] << 32), (uint64_t)H[6] | ((uint64_t)H[7] << 32)};
+        for (uint32_t j = 0; j < 32; ++j) {
+            const uint32_t bit = 6 * j, w = bit >> 6, o = bit & 63;
+            uint64_t v = c[w] >> o;
+            if (o > 58) v |= c[w + 1] << (64 - o);
+            ones += v & 63;
+        }
+    }
+    std::vector<SelNode> nodes(1, SelNode{bv->nbits, ones, 0, 0, 0, (uint32_t)bv->n_sb, kSelNoParent, 0});
+    const RrrCounts src{bv->d_hdr};
+    hipStream_t st = (hipStream_t)stream;
+    if (vlg_status r = select_support_finish(s.get(), nodes, {}, shift, st, [&](const SelNode* nd, const uint32_t* list, const uint64_t* first, uint32_t n_list,
+                                                                                 uint32_t* hints, dim3 grid) {
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(select_hints_kernel<RrrCounts>), grid, dim3(256), 0, st, src, nd, list, first, n_list, shift, hints);
+        })) return r;
+    *out = s.release();
+    return VLG_OK;
+}
+
+extern "C" vlg_status vlg_index_select_create(const vlg_index* idx, uint32_t sample, void* stream, vlg_select_support** out)
+{
+    uint32_t shift = 0;
+    if (vlg_status st = select_create_checks(idx, sample, out, shift)) return st;
+    SelectPtr s(new vlg_select_support());
+    s->kind = kSelIndex;
+    s->idx = idx;
+    std::vector<SelNode> nodes;
+    std::vector<uint32_t> leaf_up;
+    const uint64_t n = idx->hdr.n;
+    bool rrr;
+    if (idx->is_int) {                                             // one node per level of the matrix: n bits, n - Z[l] ones
+        const IntView& v = idx->iview;
+        rrr = v.bv_kind == kBvRrr63;
+        uint64_t Z[kMaxIntLevels] = {0};
+        if (v.n_levels) VLG_HIP_TRY(hipMemcpy(Z, v.Z, v.n_levels * 8, hipMemcpyDeviceToHost));
+        for (uint32_t l = 0; l < v.n_levels; ++l) {
+            if (Z[l] > n) return fail(VLG_E_INVALID, "select support: a level has more zeros than symbols");
+            nodes.push_back(SelNode{n, n - Z[l], 0, 0, (uint32_t)(l * v.stride), (uint32_t)(n / (rrr ? kRrrSuperBits : kBlockBits) + 1), kSelNoParent, 0});
+        }
+    } else {                                                       // the tree as the kernels walk it; sizes from the symbol counts
+        const IndexView& v = idx->view;
+        rrr = v.bv_kind == kBvRrr63;
+        const uint32_t nn = v.n_nodes, sigma = v.sigma;
+        std::vector<DNode> dn(std::max<uint32_t>(nn, 1));
+        std::vector<uint64_t> Cc(sigma + 1, 0);
+        if (nn) VLG_HIP_TRY(hipMemcpy(dn.data(), v.nodes, nn * sizeof(DNode), hipMemcpyDeviceToHost));
+        VLG_HIP_TRY(hipMemcpy(Cc.data(), v.C, (sigma + 1) * 8, hipMemcpyDeviceToHost));
+        leaf_up.assign(std::max<uint32_t>(sigma, 1), kSelNoParent);
+        if (sigma > 1) {
+            nodes.assign(nn, SelNode{0, 0, 0, 0, 0, 0, kSelNoParent, 0});
+            std::vector<uint8_t> inner(nn, 0);
+            inner[0] = 1;
+            for (uint32_t p = 0; p < nn; ++p) {                    // top-down: who is inner, and the way up
+                if (!inner[p]) continue;
+                for (uint32_t b = 0; b < 2; ++b) {
+                    const uint32_t ch = dn[p].child[b];
+                    if (ch & kLeafFlag) { if ((ch & ~kLeafFlag) >= sigma) return fail(VLG_E_INVALID, "select support: leaf symbol out of range"); leaf_up[ch & ~kLeafFlag] = 2 * p + b; }
+                    else if (ch <= p || ch >= nn) return fail(VLG_E_INVALID, "select support: node table is not in BFS order");
+                    else { inner[ch] = 1; nodes[ch].up = 2 * p + b; }
+                }
+            }
+            for (uint32_t p = nn; p-- > 0;) {                      // bottom-up: sizes
+                if (!inner[p]) continue;
+                uint64_t cnt[2];
+                for (uint32_t b = 0; b < 2; ++b) {
+                    const uint32_t ch = dn[p].child[b];
+                    cnt[b] = (ch & kLeafFlag) ? Cc[(ch & ~kLeafFlag) + 1] - Cc[ch & ~kLeafFlag] : nodes[ch].size;
+                }
+                nodes[p].size = cnt[0] + cnt[1];
+                nodes[p].ones = cnt[1];
+                nodes[p].base = dn[p].base;
+                nodes[p].nb = (uint32_t)(nodes[p].size / (rrr ? kRrrSuperBits : kBlockBits) + 1);
+            }
+            if (nodes[0].size != n) return fail(VLG_E_INVALID, "select support: the tree does not hold n symbols");
+        }
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const PlainCounts plain{idx->is_int ? idx->iview.blocks : idx->view.blocks};
+    const RrrCounts packed{idx->is_int ? idx->iview.rrr_hdr : idx->view.rrr_hdr};
+    if (vlg_status r = select_support_finish(s.get(), nodes, leaf_up, shift, st, [&](const SelNode* nd, const uint32_t* list, const uint64_t* first, uint32_t n_list,
+                                                                                      uint32_t* hints, dim3 grid) {
+            if (rrr) hipLaunchKernelGGL(HIP_KERNEL_NAME(select_hints_kernel<RrrCounts>), grid, dim3(256), 0, st, packed, nd, list, first, n_list, shift, hints);
+            else hipLaunchKernelGGL(HIP_KERNEL_NAME(select_hints_kernel<PlainCounts>), grid, dim3(256), 0, st, plain, nd, list, first, n_list, shift, hints);
+        })) return r;
+    *out = s.release();
+    return VLG_OK;
+}
+
+extern "C" uint64_t vlg_select_support_hbm_bytes(const vlg_select_support* s) { return s ? s->bytes : 0; }
+
+extern "C" void vlg_select_support_destroy(vlg_select_support* s)
+{
+    if (!s) return;
+    if (s->d_mem) (void)hipFree(s->d_mem);
+    delete s;
+}
+
+extern "C" vlg_status vlg_bit_select_batch(const vlg_select_support* s, int bit, const uint64_t* d_k, uint64_t* d_out, uint64_t count, void* stream)
+{
+    if (!s || (count && (!d_k || !d_out))) return fail(VLG_E_INVALID, "null argument");
+    if (bit != 0 && bit != 1) return fail(VLG_E_INVALID, "bit select: bit must be 0 or 1");
+    if (s->kind == kSelIndex) return fail(VLG_E_INVALID, "bit select: the support was made from an index (use vlg_wt_select_batch / vlg_int_select_batch)");
+    if (!count) return VLG_OK;
+    hipStream_t st = (hipStream_t)stream;
+    if (s->kind == kSelPlainBv) {
+        const BitsView bv{s->bv->d_blocks};
+        if (bit) hipLaunchKernelGGL(HIP_KERNEL_NAME(bit_select_kernel<1>), launch_grid(count, 8192), dim3(256), 0, st, bv, s->view, d_k, d_out, count);
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(bit_select_kernel<0>), launch_grid(count, 8192), dim3(256), 0, st, bv, s->view, d_k, d_out, count);
+    } else {
+        const vlg_rrr_bitvector* r = s->rrr;
+        if (bit) hipLaunchKernelGGL(HIP_KERNEL_NAME(rrr_bit_select_kernel<1>), launch_grid(count, 2048), dim3(256), 0, st, r->d_hdr, r->d_stream, r->d_binom, s->view, d_k, d_out, count);
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(rrr_bit_select_kernel<0>), launch_grid(count, 2048), dim3(256), 0, st, r->d_hdr, r->d_stream, r->d_binom, s->view, d_k, d_out, count);
+    }
+    VLG_HIP_TRY(hipGetLastError());
+    return VLG_OK;
+}
+
+extern "C" vlg_status vlg_wt_select_batch(const vlg_select_support* s, const uint64_t* d_k, const uint8_t* d_c, uint64_t* d_out, uint64_t count, void* stream)
+{
+    if (!s || (count && (!d_k || !d_c || !d_out))) return fail(VLG_E_INVALID, "null argument");
+    if (s->kind != kSelIndex) return fail(VLG_E_INVALID, "wt select: the support was made from a bit-vector (use vlg_bit_select_batch)");
+    if (s->idx->is_int) return fail(VLG_E_INVALID, "integer-alphabet index: use vlg_int_select_batch");
+    if (!count) return VLG_OK;
+    const dim3 grid = launch_grid(count, 8192);
+    if (s->idx->view.bv_kind == kBvRrr63)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(wt_select_kernel<RrrBV, false>), grid, dim3(256), 0, (hipStream_t)stream, s->idx->view, s->view, d_k, d_c, d_out, count);
+    else
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(wt_select_kernel<PlainBV, false>), grid, dim3(256), 0, (hipStream_t)stream, s->idx->view, s->view, d_k, d_c, d_out, count);
+    VLG_HIP_TRY(hipGetLastError());
+    return VLG_OK;
+}
+
+extern "C" vlg_status vlg_int_select_batch(const vlg_select_support* s, const uint64_t* d_k, const uint32_t* d_sym, uint64_t* d_out, uint64_t count, void* stream)
+{
+    if (!s || (count && (!d_k || !d_sym || !d_out))) return fail(VLG_E_INVALID, "null argument");
+    if (s->kind != kSelIndex) return fail(VLG_E_INVALID, "int select: the support was made from a bit-vector (use vlg_bit_select_batch)");
+    if (!s->idx->is_int) return fail(VLG_E_INVALID, "byte-alphabet index: use vlg_wt_select_batch");
+    if (!count) return VLG_OK;
+    return launch_int_select(s->idx->iview, s->view, d_k, d_sym, d_out, count, (hipStream_t)stream);
+}
+
+extern "C" vlg_status vlg_psi_batch(const vlg_select_support* s, const uint64_t* d_i, uint64_t* d_out, uint64_t count, void* stream)
+{
+    if (!s || (count && (!d_i || !d_out))) return fail(VLG_E_INVALID, "null argument");
+    if (s->kind != kSelIndex) return fail(VLG_E_INVALID, "psi: the support was made from a bit-vector");
+    if (!count) return VLG_OK;
+    if (s->idx->is_int) return launch_int_select(s->idx->iview, s->view, d_i, nullptr, d_out, count, (hipStream_t)stream);
+    const dim3 grid = launch_grid(count, 8192);
+    if (s->idx->view.bv_kind == kBvRrr63)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(wt_select_kernel<RrrBV, true>), grid, dim3(256), 0, (hipStream_t)stream, s->idx->view, s->view, d_i, nullptr, d_out, count);
+    else
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(wt_select_kernel<PlainBV, true>), grid, dim3(256), 0, (hipStream_t)stream, s->idx->view, s->view, d_i, nullptr, d_out, count);
+    VLG_HIP_TRY(hipGetLastError());
+    return VLG_OK;
+}
+
+namespace {
+vlg_status lf_bwt_batch(const vlg_index* idx, const uint64_t* d_i, uint64_t* d_lf, void* d_bwt, uint64_t count, hipStream_t st)
+{
+    if (idx->is_int) return launch_int_lf_bwt(idx->iview, d_i, d_lf, (uint32_t*)d_bwt, count, st);
+    const dim3 grid = launch_grid(count, 8192);
+    const bool rrr = idx->view.bv_kind == kBvRrr63, wide = idx->hdr.sample_bytes == 8;
+#define VLG_LF_BWT(BV_, W_) hipLaunchKernelGGL(HIP_KERNEL_NAME(lf_bwt_kernel<BV_, W_>), grid, dim3(256), 0, st, idx->view, d_i, d_lf, (uint8_t*)d_bwt, count)
+    if (rrr && wide) VLG_LF_BWT(RrrBV, true);
+    else if (rrr) VLG_LF_BWT(RrrBV, false);
+    else if (wide) VLG_LF_BWT(PlainBV, true);
+    else VLG_LF_BWT(PlainBV, false);
+#undef VLG_LF_BWT
+    VLG_HIP_TRY(hipGetLastError());
+    return VLG_OK;
+}
+}  // namespace
+
+extern "C" vlg_status vlg_lf_batch(const vlg_index* idx, const uint64_t* d_i, uint64_t* d_out, uint64_t count, void* stream)
+{
+    if (!idx || (count && (!d_i || !d_out))) return fail(VLG_E_INVALID, "null argument");
+    if (!count) return VLG_OK;
+    return lf_bwt_batch(idx, d_i, d_out, nullptr, count, (hipStream_t)stream);
+}
+
+extern "C" vlg_status vlg_bwt_batch(const vlg_index* idx, const uint64_t* d_i, void* d_out, uint64_t count, void* stream)
+{
+    if (!idx || (count && (!d_i || !d_out))) return fail(VLG_E_INVALID, "null argument");
+    if (!count) return VLG_OK;
+    return lf_bwt_batch(idx, d_i, nullptr, d_out, count, (hipStream_t)stream);
 }

@@ -109,6 +109,11 @@ struct ExtractJob;
 vlg_status launch_int_extract(const IntView& v, const ExtractJob& job, const uint32_t* d_isa, uint32_t* d_out, hipStream_t st);
 vlg_status launch_int_isa(const IntView& v, uint32_t d, const uint32_t* d_isa, const uint64_t* d_i, uint64_t* d_out, uint64_t count,
                           unsigned long long* d_bad, hipStream_t st);
+// select on an integer index (select.hpp): wt_int::select(d_arg[j], d_sym[j]), or with d_sym null csa.psi[d_arg[j]]; csa.lf / csa.bwt of
+// d_i (either output may be null; bwt in original symbols)
+struct SelView;
+vlg_status launch_int_select(const IntView& v, const SelView& sv, const uint64_t* d_arg, const uint32_t* d_sym, uint64_t* d_out, uint64_t count, hipStream_t st);
+vlg_status launch_int_lf_bwt(const IntView& v, const uint64_t* d_i, uint64_t* d_lf, uint32_t* d_bwt, uint64_t count, hipStream_t st);
 // can this index's occurrences be located by the sorted sweep at all (the byte index always; the integer index with a 16-bit key)
 inline bool int_sweep_possible(const IntView& v) { return v.sigma < 0xFFFFu && v.n_levels >= 1 && v.n <= (1ull << 32); }
 

@@ -486,6 +486,39 @@ class VlgIndex:
         HBM.  SA-order indexes only (a text-order one raises VLG_E_UNSUPPORTED)."""
         return TextAccess(self, inv_dens, stream)
 
+    def select_support(self, sample=0, stream=None):
+        """A SelectSupport over the BWT of this index: wt.select(k, c) and csa.psi[i] from select hints `sample` ones / zeros apart per
+        wavelet-tree node or matrix level (0 = the default, 512; otherwise a power of two in [64, 65536]).  Any kind of index."""
+        return SelectSupport(self, sample, stream)
+
+    def lf_device(self, d_i_ptr, d_out_ptr, count, stream=None):
+        """vlg_lf_batch on device pointers"""
+        check(lib().vlg_lf_batch(self._h, d_i_ptr, d_out_ptr, int(count), stream))
+
+    def bwt_device(self, d_i_ptr, d_out_ptr, count, stream=None):
+        """vlg_bwt_batch on device pointers (uint8 out for a byte index, uint32 for an integer one)"""
+        check(lib().vlg_bwt_batch(self._h, d_i_ptr, d_out_ptr, int(count), stream))
+
+    def lf(self, i):
+        """csa.lf[i] for a scalar (-> int) or an array (-> np.uint64 array); an i >= n gives 2^64 - 1"""
+        return _u64_batch(i, "i", lambda d_i, d_o, count: self.lf_device(d_i, d_o, count))
+
+    def bwt(self, i):
+        """csa.bwt[i] for a scalar (-> int) or an array (-> np.uint8 / np.uint32 array of original symbols); the sentinel and an
+        i >= n give 0"""
+        import torch
+        scalar = np.ndim(i) == 0
+        p = _u64_index_array(i, "i")
+        is_int = self.info()["bv_kind"] in (2, 3)
+        if not len(p):
+            return np.zeros(0, np.uint32 if is_int else np.uint8)
+        d_i = torch.from_numpy(p.view(np.int64)).cuda()
+        d_o = torch.empty(len(p), dtype=torch.int32 if is_int else torch.uint8, device="cuda")
+        self.bwt_device(d_i.data_ptr(), d_o.data_ptr(), len(p))
+        out = d_o.cpu().numpy()
+        out = out.view(np.uint32) if is_int else out
+        return int(out[0]) if scalar else out
+
     @classmethod
     def attach_blob(cls, d_ptr, nbytes, keep=None):
         h = C.c_void_p()
@@ -725,6 +758,93 @@ class TextAccess:
         return int(out[0]) if scalar else out
 
 
+def _u64_batch(a, name, run, *more):
+    """run(d_in_ptr, d_out_ptr, count, *device pointers of `more`) on a host scalar / array of uint64 -> int / np.uint64 array"""
+    import torch
+    scalar = np.ndim(a) == 0
+    p = _u64_index_array(a, name)
+    if not len(p):
+        return np.zeros(0, np.uint64)
+    d_i = torch.from_numpy(p.view(np.int64)).cuda()
+    d_o = torch.empty_like(d_i)
+    d_more = [torch.from_numpy(x).cuda() for x in more]
+    run(d_i.data_ptr(), d_o.data_ptr(), len(p), *[x.data_ptr() for x in d_more])
+    out = d_o.cpu().numpy().view(np.uint64)
+    return int(out[0]) if scalar else out
+
+
+class SelectSupport:
+    """Select hints in HBM beside a bit-vector or an index (vlg_select_support).  From a BitVector / RrrBitVector: bit_select =
+    select_support_mcl<bit>::select / select_support_rrr<bit>::select.  From a VlgIndex: select = wt.select(k, c) on the BWT (c: a text
+    byte, or an original symbol of an integer index), psi = csa.psi[i].  k counts from 1; k = 0, a k past the last occurrence or an
+    absent symbol give the size of the sequence (nbits, or n)."""
+
+    def __init__(self, source, sample=0, stream=None):
+        sample = int(sample)
+        if sample < 0 or sample >= 1 << 32:
+            raise ValueError("sample must be in [0, 2^32)")
+        self.source = source                      # the handle refers to its source: keep it alive
+        self.is_index = isinstance(source, VlgIndex)
+        self.is_int = self.is_index and source.info()["bv_kind"] in (2, 3)
+        self._h = None
+        h = C.c_void_p()
+        if self.is_index:
+            check(lib().vlg_index_select_create(source._h, sample, stream, C.byref(h)))
+        elif isinstance(source, RrrBitVector):
+            check(lib().vlg_rrr_bitvector_select_create(source._h, sample, stream, C.byref(h)))
+        elif isinstance(source, BitVector):
+            check(lib().vlg_bitvector_select_create(source._h, sample, stream, C.byref(h)))
+        else:
+            raise TypeError("a VlgIndex, BitVector or RrrBitVector expected")
+        self._h = h
+
+    def __del__(self):
+        try:
+            if self._h:
+                lib().vlg_select_support_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def hbm_bytes(self):
+        return int(lib().vlg_select_support_hbm_bytes(self._h))
+
+    def bit_select_device(self, d_k_ptr, d_out_ptr, count, bit=1, stream=None):
+        """vlg_bit_select_batch on device pointers"""
+        check(lib().vlg_bit_select_batch(self._h, int(bit), d_k_ptr, d_out_ptr, int(count), stream))
+
+    def select_device(self, d_k_ptr, d_c_ptr, d_out_ptr, count, stream=None):
+        """vlg_wt_select_batch (byte index: uint8 symbols) / vlg_int_select_batch (integer index: uint32 symbols) on device pointers"""
+        f = lib().vlg_int_select_batch if self.is_int else lib().vlg_wt_select_batch
+        check(f(self._h, d_k_ptr, d_c_ptr, d_out_ptr, int(count), stream))
+
+    def psi_device(self, d_i_ptr, d_out_ptr, count, stream=None):
+        """vlg_psi_batch on device pointers"""
+        check(lib().vlg_psi_batch(self._h, d_i_ptr, d_out_ptr, int(count), stream))
+
+    def bit_select(self, k, bit=1):
+        """position of the k-th `bit` for a scalar (-> int) or an array (-> np.uint64 array) of k"""
+        if bit not in (0, 1):
+            raise ValueError("bit must be 0 or 1")
+        return _u64_batch(k, "k", lambda d_k, d_o, count: self.bit_select_device(d_k, d_o, count, bit))
+
+    def select(self, k, c):
+        """wt.select(k, c): SA index of the k-th c in the BWT; scalars (-> int) or arrays of equal length (-> np.uint64 array)"""
+        ka = _u64_index_array(k, "k")
+        ca = _u64_index_array(c, "c")
+        if len(ka) != len(ca):
+            raise ValueError("k and c differ in length")
+        if len(ca) and int(ca.max()) > (0xFFFFFFFF if self.is_int else 0xFF):
+            raise ValueError("c: symbol out of range")
+        sym = np.ascontiguousarray(ca.astype(np.uint32).view(np.int32) if self.is_int else ca.astype(np.uint8))
+        out = _u64_batch(ka, "k", lambda d_k, d_o, count, d_c: self.select_device(d_k, d_c, d_o, count), sym)
+        return int(out[0]) if np.ndim(k) == 0 and np.ndim(c) == 0 else out
+
+    def psi(self, i):
+        """csa.psi[i] for a scalar (-> int) or an array (-> np.uint64 array); an i >= n gives 2^64 - 1"""
+        return _u64_batch(i, "i", lambda d_i, d_o, count: self.psi_device(d_i, d_o, count))
+
+
 class WtsaIndex:
     """sdsl::vlg_index<alphabet_tag, wt_int<>> in HBM: the text + a wavelet tree over its suffix array, searched lazily
     (include/sdsl/vlg_index.hpp:109-373).  `text`: bytes / uint8 array (byte alphabet) or a uint32 array (integer alphabet)."""
@@ -889,6 +1009,10 @@ class BitVector:
     def rank_device(self, d_idx_ptr, d_out_ptr, count, stream=None):
         check(lib().vlg_bitvector_rank_batch(self._h, d_idx_ptr, d_out_ptr, count, stream))
 
+    def select_support(self, sample=0, stream=None):
+        """select_support_mcl<1> and <0> over this bit-vector (SelectSupport.bit_select)"""
+        return SelectSupport(self, sample, stream)
+
     def hbm_bytes(self):
         return int(lib().vlg_bitvector_hbm_bytes(self._h))
 
@@ -913,6 +1037,10 @@ class RrrBitVector:
 
     def rank_device(self, d_idx_ptr, d_out_ptr, count, stream=None):
         check(lib().vlg_rrr_bitvector_rank_batch(self._h, d_idx_ptr, d_out_ptr, count, stream))
+
+    def select_support(self, sample=0, stream=None):
+        """select_support_rrr<1> and <0> over this bit-vector (SelectSupport.bit_select)"""
+        return SelectSupport(self, sample, stream)
 
     def hbm_bytes(self):
         return int(lib().vlg_rrr_bitvector_hbm_bytes(self._h))
