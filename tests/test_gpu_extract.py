@@ -109,13 +109,23 @@ BYTE_TEXTS = {
 }
 
 
-@pytest.mark.parametrize("name", sorted(BYTE_TEXTS))
-def test_byte_extract_and_isa(torch_cuda, V, name):
+# (name, force): the ids of the force=None cases stay "<name>"
+BYTE_CASES = [pytest.param(name, force, id=name + ("-pos64=" + force if force else "")) for name in sorted(BYTE_TEXTS) for force in (None, "2")]
+
+
+@pytest.mark.parametrize("name,force", BYTE_CASES)
+def test_byte_extract_and_isa(torch_cuda, V, monkeypatch, name, force):
+    """force: VLG_FORCE_POS64 -- "2" builds the index with 64-bit samples and wide SA indices, so the same checks run on the kWide arms of
+    extract_kernel, isa_kernel and isa_samples_kernel (the 8-byte ISA samples of n >= 2^32 stay out of reach of a small text)"""
+    if force:
+        monkeypatch.setenv("VLG_FORCE_POS64", force)
     text = BYTE_TEXTS[name]
     full = with_sentinel(text).astype(np.uint8)
     n = len(full)
     isa_ref = byte_naive_isa(text)
     idx = V.VlgIndex.build(text.tobytes(), dens=32)
+    if force:
+        assert idx.info()["pos_bytes"] == 8
     for ix, label in ((idx, "plain"), (idx.compress(), "rrr"), (idx.resample(text_order=False, dens=1), "sa-dens-1"),
                       (idx.resample(text_order=False, dens=7), "sa-dens-7")):
         check_text_access(torch_cuda, V, ix, full, isa_ref, [1, 3, 64, n + 5])

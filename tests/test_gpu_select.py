@@ -182,8 +182,16 @@ BYTE_TEXTS = {
 }
 
 
-@pytest.mark.parametrize("name", sorted(BYTE_TEXTS))
-def test_byte_select_psi_lf_bwt(torch_cuda, V, name):
+# (name, force): the ids of the force=None cases stay "<name>"
+BYTE_CASES = [pytest.param(name, force, id=name + ("-pos64=" + force if force else "")) for name in sorted(BYTE_TEXTS) for force in (None, "2")]
+
+
+@pytest.mark.parametrize("name,force", BYTE_CASES)
+def test_byte_select_psi_lf_bwt(torch_cuda, V, monkeypatch, name, force):
+    """force: VLG_FORCE_POS64 -- "2" builds the index with 64-bit samples and wide SA indices: lf_bwt_kernel's kWide arms, and select and
+    psi on a wide index"""
+    if force:
+        monkeypatch.setenv("VLG_FORCE_POS64", force)
     text = BYTE_TEXTS[name]
     full = with_sentinel(text).astype(np.uint8)
     sa = naive_sa(full)
@@ -191,6 +199,8 @@ def test_byte_select_psi_lf_bwt(torch_cuda, V, name):
     assert np.array_equal(truth.bwt, bwt_from_sa(full, sa))
     absent = np.setdiff1d(np.arange(256), np.unique(full))
     idx = V.VlgIndex.build(text.tobytes(), dens=32)
+    if force:
+        assert idx.info()["pos_bytes"] == 8
     for ix in (idx, idx.compress(), idx.resample(text_order=True, dens=8), idx.compress().resample(text_order=True, dens=8)):
         check_index(V, ix, truth, absent)
 

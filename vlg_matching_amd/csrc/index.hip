@@ -7,6 +7,7 @@
 #include "common.hpp"
 #include <functional>
 #include "device_rank.hpp"
+#include "shape_dispatch.hpp"
 #include "kernels.hpp"
 #include "rrr_code.hpp"
 #include <rocprim/rocprim.hpp>
@@ -866,10 +867,9 @@ vlg_status resample_run(const vlg_index* src, int sampling, uint32_t dens, vlg_i
     const uint64_t n = src->hdr.n;
     DevBuf d_sa, d_blob;
     VLG_HIP_TRY(d_sa.alloc(n * sizeof(sa_t)));
-    const dim3 grid = launch_grid(src->view.n_samples, 8192);
-    if (src->view.bv_kind == kBvRrr63) hipLaunchKernelGGL(HIP_KERNEL_NAME(sa_expand_kernel<RrrBV, sa_t>), grid, dim3(256), 0, stream, src->view, d_sa.as<sa_t>());
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(sa_expand_kernel<PlainBV, sa_t>), grid, dim3(256), 0, stream, src->view, d_sa.as<sa_t>());
-    VLG_HIP_TRY(hipGetLastError());
+    if (vlg_status st = on_bv(src->view.bv_kind, [&](auto bv) {
+            return launch(sa_expand_kernel<tag_t<decltype(bv)>, sa_t>, launch_grid(src->view.n_samples, 8192), stream, src->view, d_sa.as<sa_t>());
+        })) return st;
     BlobHeader& h = idx->hdr;
     h = src->hdr;
     h.dens = dens;

@@ -1,5 +1,6 @@
 // FM-index of an INTEGER text on the device: csa_wt<wt_int<>, dens, ., sa_order_sa_sampling, ., int_alphabet<>>.
-// Internal to search.hip's translation unit; included exactly once, behind wtsa.hpp (whose builder kernels it shares).
+// Internal to search.hip's translation unit; included exactly once, behind wtsa.hpp (whose builder kernels it shares).  The launchers
+// at the end pick plain or rrr levels and the sampling through shape_dispatch.hpp, the sweep through bind_sweep (sweep_kernels.hpp).
 //   int_alphabet (char2comp / comp2char / C)   include/sdsl/csa_alphabet_strategy.hpp:394-470, 496-536
 //   wt_int::rank / inverse_select on the BWT   include/sdsl/wt_int.hpp:370-395, 405-430
 //   LF, csa[i], backward_search, locate        suffix_array_helper.hpp:336-349, csa_wt.hpp:335-348, suffix_array_algorithm.hpp:250-326, 604-619
@@ -116,6 +117,7 @@ __global__ void __launch_bounds__(256) int_backward_search_kernel(IntView v, con
 // key.  The sampling policies are device_rank.hpp's on the IntView, with 4-byte samples.
 using IntSaSampling = SaOrderSampling<uint32_t>;
 using IntTextSampling = TextOrderSampling<uint32_t>;
+template <bool kTextOrder> using IntSampling = typename std::conditional<kTextOrder, IntTextSampling, IntSaSampling>::type;
 
 // wt_int::rank(i, c) on raw symbols (for the primitives test): out = #c in BWT[0, i)
 template <class BV>
@@ -564,12 +566,9 @@ extern "C" vlg_status vlg_int_rank_batch(const vlg_index* idx, const uint64_t* d
     if (!idx || (count && (!d_i || !d_sym || !d_out))) return fail(VLG_E_INVALID, "null argument");
     if (!idx->is_int) return fail(VLG_E_INVALID, "not an integer-alphabet index");
     if (!count) return VLG_OK;
-    if (idx->iview.bv_kind == kBvRrr63)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(int_rank_kernel<RrrBV>), launch_grid(count, 8192), dim3(256), 0, (hipStream_t)stream, idx->iview, d_i, d_sym, d_out, count);
-    else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(int_rank_kernel<PlainBV>), launch_grid(count, 8192), dim3(256), 0, (hipStream_t)stream, idx->iview, d_i, d_sym, d_out, count);
-    VLG_HIP_TRY(hipGetLastError());
-    return VLG_OK;
+    return on_bv(idx->iview.bv_kind, [&](auto bv) {
+        return launch(int_rank_kernel<tag_t<decltype(bv)>>, launch_grid(count, 8192), (hipStream_t)stream, idx->iview, d_i, d_sym, d_out, count);
+    });
 }
 
 namespace vlg {
@@ -578,69 +577,26 @@ vlg_status launch_int_backward_search(const IntView& v, const uint8_t* d_blob, c
                                       unsigned long long* d_stat_levels, hipStream_t st)
 {
     if (!n_pat) return VLG_OK;
-    if (v.bv_kind == kBvRrr63)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(int_backward_search_kernel<RrrBV>), launch_grid(n_pat, 4096), dim3(256), 0, st, v, d_blob, d_off, n_pat, d_l, d_r, d_stat_levels);
-    else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(int_backward_search_kernel<PlainBV>), launch_grid(n_pat, 4096), dim3(256), 0, st, v, d_blob, d_off, n_pat, d_l, d_r, d_stat_levels);
-    VLG_HIP_TRY(hipGetLastError());
-    return VLG_OK;
+    return on_bv(v.bv_kind, [&](auto bv) {
+        return launch(int_backward_search_kernel<tag_t<decltype(bv)>>, launch_grid(n_pat, 4096), st, v, d_blob, d_off, n_pat, d_l, d_r, d_stat_levels);
+    });
 }
 
 // the integer index in the sorted sweep (sigma <= 65534: the partition key is 16 bits wide)
-template <class BV, class Sampling>
-static vlg_status launch_int_locate_sweep_bv(const IntView& v, const uint64_t* d_l, const uint64_t* d_out_off, uint64_t n_pat, uint64_t total, uint32_t* d_out,
-                                   uint64_t* val_a, uint64_t* val_b, uint16_t* key_a, uint16_t* key_b, void* temp, size_t temp_bytes, unsigned long long* d_counter,
-                                   unsigned long long* d_stats, uint64_t tail_threshold, hipStream_t stream, LaunchTimer* timer, Block* member,
-                                   uint32_t n_member_lists, uint64_t* rec, const std::function<vlg_status()>* while_first_step)
-{
-    if (v.sigma >= 0xFFFFu || v.n_levels < 1 || v.n > (1ull << 32)) return fail(VLG_E_INTERNAL, "integer index: not for the sorted sweep");
-    using Walk = IntWalk<BV>;
-    SweepKernels K;
-    K.n = v.n;
-    K.sigma = (uint32_t)v.sigma;
-    K.first = [&](uint64_t t0, uint64_t t1, uint64_t* val, uint16_t* key, void* out, unsigned long long* counter, const Block* mem, uint64_t* rc, bool ahead,
-                  uint32_t* chunk_list) {
-        launch_sweep_chunk_lists(d_out_off, n_pat, t0, t1, chunk_list, stream);
-        const dim3 g = launch_grid((t1 - t0 + 7) / 8, 8192);
-        uint32_t* o = static_cast<uint32_t*>(out);
-#define VLG_INT_FIRST(TR, AH) hipLaunchKernelGGL(HIP_KERNEL_NAME(sweep_first_kernel<Walk, Sampling, uint32_t, TR, false, AH>), g, dim3(256), 0, stream, v, d_l, d_out_off, n_pat, t0, t1, val, key, o, d_stats, counter, mem, rc, chunk_list, (uint8_t*)nullptr)
-        if (mem && ahead) VLG_INT_FIRST(true, true);
-        else if (mem) VLG_INT_FIRST(true, false);
-        else VLG_INT_FIRST(false, false);
-#undef VLG_INT_FIRST
-    };
-    K.step = [&](uint64_t* val, uint16_t* key, uint64_t alive, uint32_t step, void* out, unsigned long long* counter, const Block* mem, uint64_t* rc, uint64_t t0, bool probed) {
-        const dim3 g = launch_grid(alive, 4096);
-        uint32_t* o = static_cast<uint32_t*>(out);
-        if (mem) hipLaunchKernelGGL(HIP_KERNEL_NAME(sweep_step_kernel<Walk, Sampling, uint32_t, true, false>), g, dim3(256), 0, stream, v, val, key, alive, step, o, d_stats, counter, mem, rc, t0, probed);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(sweep_step_kernel<Walk, Sampling, uint32_t, false, false>), g, dim3(256), 0, stream, v, val, key, alive, step, o, d_stats, counter, mem, rc, t0, probed);
-    };
-    K.tail = [&](void* out, uint64_t alive, uint32_t per_wave, const uint64_t* val, uint32_t step, uint64_t* rc, uint64_t t0, const Block* mem, uint32_t blocks) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(locate_kernel<Walk, Sampling, uint32_t, true, false>), dim3(blocks), dim3(256), 0, stream, v, static_cast<uint32_t*>(out), alive, per_wave, d_stats, val, step, rc, t0, mem);
-    };
-    return run_locate_sweep<uint32_t, false>(K, d_l, d_out_off, n_pat, total, d_out, val_a, val_b, key_a, key_b, temp, temp_bytes, d_counter, tail_threshold, stream, timer,
-                                             member, n_member_lists, rec, while_first_step);
-}
-
 vlg_status launch_int_locate_sweep(const IntView& v, const uint64_t* d_l, const uint64_t* d_out_off, uint64_t n_pat, uint64_t total, uint32_t* d_out,
                                    uint64_t* val_a, uint64_t* val_b, uint16_t* key_a, uint16_t* key_b, void* temp, size_t temp_bytes, unsigned long long* d_counter,
                                    unsigned long long* d_stats, uint64_t tail_threshold, hipStream_t stream, LaunchTimer* timer, Block* member,
                                    uint32_t n_member_lists, uint64_t* rec, const std::function<vlg_status()>* while_first_step)
 {
-    if (v.dens == 1 && v.sampling == kSamplingSaOrder && total) {     // the resident suffix array: no walk, no trails, no records
-        if (timer) timer->begin(0);
-        const vlg_status s = launch_int_dense_copy(v, d_l, d_out_off, n_pat, total, d_out, stream);
-        if (timer) timer->end(0);
-        if (s) return s;
-        if (while_first_step) if (vlg_status hs = (*while_first_step)()) return hs;
-        return VLG_OK;
-    }
-#define VLG_INT_SWEEP(BV, S) launch_int_locate_sweep_bv<BV, S>(v, d_l, d_out_off, n_pat, total, d_out, val_a, val_b, key_a, key_b, temp, temp_bytes, d_counter, \
-                                                              d_stats, tail_threshold, stream, timer, member, n_member_lists, rec, while_first_step)
-    const bool rrr = v.bv_kind == kBvRrr63;
-    if (v.sampling == kSamplingTextOrder) return rrr ? VLG_INT_SWEEP(RrrBV, IntTextSampling) : VLG_INT_SWEEP(PlainBV, IntTextSampling);
-    return rrr ? VLG_INT_SWEEP(RrrBV, IntSaSampling) : VLG_INT_SWEEP(PlainBV, IntSaSampling);
-#undef VLG_INT_SWEEP
+    const bool text_order = shape(v).text_order;
+    if (v.dens == 1 && !text_order && total)                          // the resident suffix array
+        return sweep_dense_copy(timer, while_first_step, [&] { return launch_int_dense_copy(v, d_l, d_out_off, n_pat, total, d_out, stream); });
+    if (!int_sweep_possible(v)) return fail(VLG_E_INTERNAL, "integer index: not for the sorted sweep");
+    return on_bv(v.bv_kind, [&](auto bv) { return on_flag(text_order, [&](auto to) {
+        const SweepKernels K = bind_sweep<IntWalk<tag_t<decltype(bv)>>, IntSampling<decltype(to)::value>, uint32_t, false>(v, d_l, d_out_off, n_pat, d_stats, stream, nullptr);
+        return run_locate_sweep<uint32_t, false>(K, d_l, d_out_off, n_pat, total, d_out, val_a, val_b, key_a, key_b, temp, temp_bytes, d_counter, tail_threshold, stream, timer,
+                                                 member, n_member_lists, rec, while_first_step);
+    }); });
 }
 
 // SA-order density 1: the samples are the suffix array, and locate copies SA intervals (kernels.hip: sa_dense_copy_kernel)
@@ -654,71 +610,46 @@ vlg_status launch_int_locate(const IntView& v, uint32_t* d_io, uint64_t total, u
 {
     if (!total) return VLG_OK;
     const LocateSlices sl = locate_slices(total);
-    const dim3 grid(sl.blocks);
-#define VLG_INT_LOCATE(BV, S) hipLaunchKernelGGL(HIP_KERNEL_NAME(locate_kernel<IntWalk<BV>, S, uint32_t>), grid, dim3(256), 0, st, v, d_io, total, sl.per_wave, d_stats)
-    const bool rrr = v.bv_kind == kBvRrr63;
-    if (v.sampling == kSamplingTextOrder) { if (rrr) VLG_INT_LOCATE(RrrBV, IntTextSampling); else VLG_INT_LOCATE(PlainBV, IntTextSampling); }
-    else { if (rrr) VLG_INT_LOCATE(RrrBV, IntSaSampling); else VLG_INT_LOCATE(PlainBV, IntSaSampling); }
-#undef VLG_INT_LOCATE
-    VLG_HIP_TRY(hipGetLastError());
-    return VLG_OK;
+    return on_bv(v.bv_kind, [&](auto bv) { return on_flag(shape(v).text_order, [&](auto to) {
+        // (in place: no words, no records -- the tail mode's parameters are empty)
+        return launch(locate_kernel<IntWalk<tag_t<decltype(bv)>>, IntSampling<decltype(to)::value>, uint32_t>, dim3(sl.blocks), st, v, d_io, total, sl.per_wave, d_stats,
+                      nullptr, 0u, nullptr, 0ull, nullptr);
+    }); });
 }
 
 // every SA value of an SA-order integer index into d_sa (n words): the input of vlg_index_resample
 vlg_status launch_int_sa_expand(const IntView& v, uint32_t* d_sa, hipStream_t st)
 {
     if (v.sampling != kSamplingSaOrder) return fail(VLG_E_INTERNAL, "integer index: expanding the suffix array needs SA-order samples");
-    const dim3 grid = launch_grid(v.n_samples, 8192);
-    if (v.bv_kind == kBvRrr63) hipLaunchKernelGGL(HIP_KERNEL_NAME(int_sa_expand_kernel<RrrBV>), grid, dim3(256), 0, st, v, d_sa);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(int_sa_expand_kernel<PlainBV>), grid, dim3(256), 0, st, v, d_sa);
-    VLG_HIP_TRY(hipGetLastError());
-    return VLG_OK;
+    return on_bv(v.bv_kind, [&](auto bv) { return launch(int_sa_expand_kernel<tag_t<decltype(bv)>>, launch_grid(v.n_samples, 8192), st, v, d_sa); });
 }
 
 // isa_sample of an SA-order integer index into d_out ((n - 1) / inv_dens + 1 words): vlg_index_isa_samples
 vlg_status launch_int_isa_samples(const IntView& v, uint32_t inv_dens, uint32_t* d_out, hipStream_t st)
 {
     if (v.sampling != kSamplingSaOrder || !inv_dens) return fail(VLG_E_INTERNAL, "integer index: ISA samples need SA-order samples");
-    const dim3 grid = launch_grid(v.n_samples, 8192);
-    if (v.bv_kind == kBvRrr63) hipLaunchKernelGGL(HIP_KERNEL_NAME(int_isa_samples_kernel<RrrBV>), grid, dim3(256), 0, st, v, inv_dens, d_out);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(int_isa_samples_kernel<PlainBV>), grid, dim3(256), 0, st, v, inv_dens, d_out);
-    VLG_HIP_TRY(hipGetLastError());
-    return VLG_OK;
+    return on_bv(v.bv_kind, [&](auto bv) { return launch(int_isa_samples_kernel<tag_t<decltype(bv)>>, launch_grid(v.n_samples, 8192), st, v, inv_dens, d_out); });
 }
 
 vlg_status launch_int_select(const IntView& v, const SelView& sv, const uint64_t* d_arg, const uint32_t* d_sym, uint64_t* d_out, uint64_t count, hipStream_t st)
 {
     if (!count) return VLG_OK;
-    if (v.bv_kind == kBvRrr63) hipLaunchKernelGGL(HIP_KERNEL_NAME(int_select_kernel<RrrBV>), launch_grid(count, 8192), dim3(256), 0, st, v, sv, d_arg, d_sym, d_out, count);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(int_select_kernel<PlainBV>), launch_grid(count, 8192), dim3(256), 0, st, v, sv, d_arg, d_sym, d_out, count);
-    VLG_HIP_TRY(hipGetLastError());
-    return VLG_OK;
+    return on_bv(v.bv_kind, [&](auto bv) { return launch(int_select_kernel<tag_t<decltype(bv)>>, launch_grid(count, 8192), st, v, sv, d_arg, d_sym, d_out, count); });
 }
 vlg_status launch_int_lf_bwt(const IntView& v, const uint64_t* d_i, uint64_t* d_lf, uint32_t* d_bwt, uint64_t count, hipStream_t st)
 {
     if (!count) return VLG_OK;
-    if (v.bv_kind == kBvRrr63) hipLaunchKernelGGL(HIP_KERNEL_NAME(int_lf_bwt_kernel<RrrBV>), launch_grid(count, 8192), dim3(256), 0, st, v, d_i, d_lf, d_bwt, count);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(int_lf_bwt_kernel<PlainBV>), launch_grid(count, 8192), dim3(256), 0, st, v, d_i, d_lf, d_bwt, count);
-    VLG_HIP_TRY(hipGetLastError());
-    return VLG_OK;
+    return on_bv(v.bv_kind, [&](auto bv) { return launch(int_lf_bwt_kernel<tag_t<decltype(bv)>>, launch_grid(count, 8192), st, v, d_i, d_lf, d_bwt, count); });
 }
 vlg_status launch_int_extract(const IntView& v, const ExtractJob& job, const uint32_t* d_isa, uint32_t* d_out, hipStream_t st)
 {
-    const dim3 grid = launch_grid(job.n_segs, 8192);
-    if (v.bv_kind == kBvRrr63) hipLaunchKernelGGL(HIP_KERNEL_NAME(int_extract_kernel<RrrBV>), grid, dim3(256), 0, st, v, job, d_isa, d_out);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(int_extract_kernel<PlainBV>), grid, dim3(256), 0, st, v, job, d_isa, d_out);
-    VLG_HIP_TRY(hipGetLastError());
-    return VLG_OK;
+    return on_bv(v.bv_kind, [&](auto bv) { return launch(int_extract_kernel<tag_t<decltype(bv)>>, launch_grid(job.n_segs, 8192), st, v, job, d_isa, d_out); });
 }
 
 vlg_status launch_int_isa(const IntView& v, uint32_t d, const uint32_t* d_isa, const uint64_t* d_i, uint64_t* d_out, uint64_t count,
                           unsigned long long* d_bad, hipStream_t st)
 {
-    const dim3 grid = launch_grid(count, 8192);
-    if (v.bv_kind == kBvRrr63) hipLaunchKernelGGL(HIP_KERNEL_NAME(int_isa_kernel<RrrBV>), grid, dim3(256), 0, st, v, d, d_isa, d_i, d_out, count, d_bad);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(int_isa_kernel<PlainBV>), grid, dim3(256), 0, st, v, d, d_isa, d_i, d_out, count, d_bad);
-    VLG_HIP_TRY(hipGetLastError());
-    return VLG_OK;
+    return on_bv(v.bv_kind, [&](auto bv) { return launch(int_isa_kernel<tag_t<decltype(bv)>>, launch_grid(count, 8192), st, v, d, d_isa, d_i, d_out, count, d_bad); });
 }
 
 }  // namespace vlg
@@ -842,9 +773,8 @@ extern "C" vlg_status vlg_index_export_int_tree(const vlg_index* idx, uint32_t* 
     release_cached_device_memory();
     TreeScratch s;
     if (vlg_status st = s.alloc(n, sigma, L)) return st;
-    if (v.bv_kind == kBvRrr63) hipLaunchKernelGGL(HIP_KERNEL_NAME(int_bwt_extract_kernel<RrrBV>), launch_grid(n), dim3(256), 0, nullptr, v, s.pay[0].as<uint32_t>());
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(int_bwt_extract_kernel<PlainBV>), launch_grid(n), dim3(256), 0, nullptr, v, s.pay[0].as<uint32_t>());
-    VLG_HIP_TRY(hipGetLastError());
+    if (vlg_status st = on_bv(v.bv_kind, [&](auto bv) { return launch(int_bwt_extract_kernel<tag_t<decltype(bv)>>, launch_grid(n), nullptr, v, s.pay[0].as<uint32_t>()); }))
+        return st;
     if (vlg_status st = int_tree_encode(s, n, sigma, L, v.comp2char, v.C)) return st;
     VLG_HIP_TRY(hipMemcpy(h_words, s.tree.p, s.words * 8, hipMemcpyDeviceToHost));
     return VLG_OK;

@@ -927,14 +927,9 @@ vlg_status launch_backward_search(const IndexView& iv, const uint8_t* d_blob, co
                                   uint64_t* d_r, unsigned long long* d_stat_levels, hipStream_t stream)
 {
     if (!n_pat) return VLG_OK;
-    if (iv.bv_kind == kBvRrr63)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(backward_search_kernel<RrrBV>), launch_grid(n_pat, 4096), dim3(256), 0, stream, iv, d_blob, d_off,
-                           n_pat, d_l, d_r, d_stat_levels);
-    else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(backward_search_kernel<PlainBV>), launch_grid(n_pat, 4096), dim3(256), 0, stream, iv, d_blob, d_off,
-                           n_pat, d_l, d_r, d_stat_levels);
-    VLG_HIP_TRY(hipGetLastError());
-    return VLG_OK;
+    return on_bv(iv.bv_kind, [&](auto bv) {
+        return launch(backward_search_kernel<tag_t<decltype(bv)>>, launch_grid(n_pat, 4096), stream, iv, d_blob, d_off, n_pat, d_l, d_r, d_stat_levels);
+    });
 }
 
 template <typename pos_t>
@@ -955,16 +950,13 @@ vlg_status launch_locate(const IndexView& iv, pos_t* d_io, uint64_t total, unsig
 {
     if (!total) return VLG_OK;
     const LocateSlices sl = locate_slices(total);
-    const bool rrr = iv.bv_kind == kBvRrr63, text_order = iv.sampling == kSamplingTextOrder;
     if (iv.sample_bytes != sizeof(pos_t)) return fail(VLG_E_INTERNAL, "locate: sample width does not match the instantiation");
     constexpr bool kWide = sizeof(pos_t) == 8;
-    const dim3 grid(sl.blocks);
-#define VLG_LOCATE(BV, TO) hipLaunchKernelGGL(HIP_KERNEL_NAME(locate_kernel<ByteWalk<BV, kWide>, ByteSampling<kWide, TO>, pos_t, false, kWide>), grid, dim3(256), 0, stream, iv, d_io, total, sl.per_wave, d_stats)
-    if (text_order) { if (rrr) VLG_LOCATE(RrrBV, true); else VLG_LOCATE(PlainBV, true); }
-    else { if (rrr) VLG_LOCATE(RrrBV, false); else VLG_LOCATE(PlainBV, false); }
-#undef VLG_LOCATE
-    VLG_HIP_TRY(hipGetLastError());
-    return VLG_OK;
+    return on_bv(iv.bv_kind, [&](auto bv) { return on_flag(shape(iv).text_order, [&](auto to) {
+        // (in place: no words, no records -- the tail mode's parameters are empty)
+        return launch(locate_kernel<ByteWalk<tag_t<decltype(bv)>, kWide>, ByteSampling<kWide, decltype(to)::value>, pos_t, false, kWide>, dim3(sl.blocks), stream, iv, d_io,
+                      total, sl.per_wave, d_stats, nullptr, 0u, nullptr, 0ull, nullptr);
+    }); });
 }
 template vlg_status launch_locate<uint32_t>(const IndexView&, uint32_t*, uint64_t, unsigned long long*, hipStream_t);
 template vlg_status launch_locate<uint64_t>(const IndexView&, uint64_t*, uint64_t, unsigned long long*, hipStream_t);
@@ -1038,10 +1030,10 @@ vlg_status run_locate_sweep(const SweepKernels& K, const uint64_t* d_l, const ui
         while (alive > tail_threshold && step < 0xFFFFFFu) {
             VLG_HIP_TRY(hipMemsetAsync(d_counter, 0, 8, stream));
             if (timer) timer->begin(0);
-            if (fused_first && step == 0) K.first(t0, t1, val_a, key_a, out, d_counter, member, rec, ahead, reinterpret_cast<uint32_t*>(val_b));      // round 0 makes the elements' words itself
-            else K.step(val_a, key_a, alive, step, out, d_counter, member, rec, t0, ahead && fused_first && step == 1);
+            const vlg_status ks = fused_first && step == 0 ? K.first(t0, t1, val_a, key_a, out, d_counter, member, rec, ahead, reinterpret_cast<uint32_t*>(val_b))      // round 0 makes the elements' words itself
+                                                           : K.step(val_a, key_a, alive, step, out, d_counter, member, rec, t0, ahead && fused_first && step == 1);
             if (timer) timer->end(0);
-            VLG_HIP_TRY(hipGetLastError());
+            if (ks) return ks;
             size_t tb = temp_bytes;
             if (timer) timer->begin(1, 20ull * alive);           // key + element read once and written once
             rocprim::double_buffer<uint16_t> dk(key_a, key_b);
@@ -1062,9 +1054,9 @@ vlg_status run_locate_sweep(const SweepKernels& K, const uint64_t* d_l, const ui
         if (alive) {
             const LocateSlices sl = locate_slices(alive);
             if (timer) timer->begin(0);
-            K.tail(out, alive, sl.per_wave, val_a, step, member ? rec : nullptr, t0, member, sl.blocks);
+            const vlg_status ks = K.tail(out, alive, sl.per_wave, val_a, step, member ? rec : nullptr, t0, member, sl.blocks);
             if (timer) timer->end(0);
-            VLG_HIP_TRY(hipGetLastError());
+            if (ks) return ks;
         }
     }
     if (hook_due) { hook_due = false; if (vlg_status hs = (*while_first_step)()) return hs; }
@@ -1110,55 +1102,20 @@ vlg_status launch_locate_sweep(const IndexView& iv, const uint64_t* d_l, const u
                                const std::function<vlg_status()>* while_first_step, uint8_t* front)
 {
     if (iv.sample_bytes != (kWide ? 8u : 4u)) return fail(VLG_E_INTERNAL, "sorted sweep: sample width does not match the instantiation");
-    const bool rrr = iv.bv_kind == kBvRrr63, text_order = iv.sampling == kSamplingTextOrder;
-    if (iv.dens == 1 && !text_order && total) {                  // every SA index is sampled: no walk, no trails, no records
+    const bool text_order = shape(iv).text_order;
+    if (iv.dens == 1 && !text_order && total) {
         using sample_t = typename std::conditional<kWide, uint64_t, uint32_t>::type;
-        if (timer) timer->begin(0);
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(sa_dense_copy_kernel<pos_t, sample_t>), launch_grid((total + 7) / 8, 32768), dim3(256), 0, stream,
-                           reinterpret_cast<const sample_t*>(iv.samples), d_l, d_out_off, n_pat, total, d_out);
-        if (timer) timer->end(0);
-        VLG_HIP_TRY(hipGetLastError());
-        if (while_first_step) if (vlg_status hs = (*while_first_step)()) return hs;
-        return VLG_OK;
+        return sweep_dense_copy(timer, while_first_step, [&] {
+            return launch(sa_dense_copy_kernel<pos_t, sample_t>, launch_grid((total + 7) / 8, 32768), stream, reinterpret_cast<const sample_t*>(iv.samples), d_l, d_out_off,
+                          n_pat, total, d_out);
+        });
     }
-    SweepKernels K;
-    K.n = iv.n;
-    K.sigma = iv.sigma;
-    K.front = rec ? front : nullptr;
-    uint8_t* const fr = K.front;
-    K.first = [&](uint64_t t0, uint64_t t1, uint64_t* val, uint16_t* key, void* out_, unsigned long long* counter, const Block* mem, uint64_t* rc, bool ahead,
-                  uint32_t* chunk_list) {
-        pos_t* out = static_cast<pos_t*>(out_);
-        launch_sweep_chunk_lists(d_out_off, n_pat, t0, t1, chunk_list, stream);
-        const dim3 grid_first = launch_grid((t1 - t0 + 7) / 8, 8192);
-#define VLG_FIRST(BV, TR, TO) do { if (ahead) hipLaunchKernelGGL(HIP_KERNEL_NAME(sweep_first_kernel<ByteWalk<BV, kWide>, ByteSampling<kWide, TO>, pos_t, TR, kWide, TR>), grid_first, dim3(256), 0, stream, iv, d_l, d_out_off, n_pat, t0, t1, val, key, out, d_stats, counter, mem, rc, chunk_list, fr); \
-                                    else hipLaunchKernelGGL(HIP_KERNEL_NAME(sweep_first_kernel<ByteWalk<BV, kWide>, ByteSampling<kWide, TO>, pos_t, TR, kWide, false>), grid_first, dim3(256), 0, stream, iv, d_l, d_out_off, n_pat, t0, t1, val, key, out, d_stats, counter, mem, rc, chunk_list, fr); } while (0)
-#define VLG_FIRST_BV(TR, TO) do { if (rrr) VLG_FIRST(RrrBV, TR, TO); else VLG_FIRST(PlainBV, TR, TO); } while (0)
-        if (text_order) { if (mem) VLG_FIRST_BV(true, true); else VLG_FIRST_BV(false, true); }
-        else { if (mem) VLG_FIRST_BV(true, false); else VLG_FIRST_BV(false, false); }
-#undef VLG_FIRST_BV
-#undef VLG_FIRST
-    };
-    K.step = [&](uint64_t* val, uint16_t* key, uint64_t alive, uint32_t step, void* out_, unsigned long long* counter, const Block* mem, uint64_t* rc, uint64_t t0, bool probed) {
-        pos_t* out = static_cast<pos_t*>(out_);
-        const dim3 grid = launch_grid(alive, 4096);
-#define VLG_STEP(BV, TR, TO) hipLaunchKernelGGL(HIP_KERNEL_NAME(sweep_step_kernel<ByteWalk<BV, kWide>, ByteSampling<kWide, TO>, pos_t, TR, kWide>), grid, dim3(256), 0, stream, iv, val, key, alive, step, out, d_stats, counter, mem, rc, t0, probed)
-#define VLG_STEP_BV(TR, TO) do { if (rrr) VLG_STEP(RrrBV, TR, TO); else VLG_STEP(PlainBV, TR, TO); } while (0)
-        if (text_order) { if (mem) VLG_STEP_BV(true, true); else VLG_STEP_BV(false, true); }
-        else { if (mem) VLG_STEP_BV(true, false); else VLG_STEP_BV(false, false); }
-#undef VLG_STEP_BV
-#undef VLG_STEP
-    };
-    K.tail = [&](void* out_, uint64_t alive, uint32_t per_wave, const uint64_t* val, uint32_t step, uint64_t* rc, uint64_t t0, const Block* mem, uint32_t blocks) {
-        pos_t* out = static_cast<pos_t*>(out_);
-        const dim3 grid(blocks);
-#define VLG_TAIL(BV, TO) hipLaunchKernelGGL(HIP_KERNEL_NAME(locate_kernel<ByteWalk<BV, kWide>, ByteSampling<kWide, TO>, pos_t, true, kWide>), grid, dim3(256), 0, stream, iv, out, alive, per_wave, d_stats, val, step, rc, t0, mem)
-        if (text_order) { if (rrr) VLG_TAIL(RrrBV, true); else VLG_TAIL(PlainBV, true); }
-        else { if (rrr) VLG_TAIL(RrrBV, false); else VLG_TAIL(PlainBV, false); }
-#undef VLG_TAIL
-    };
-    return run_locate_sweep<pos_t, kWide>(K, d_l, d_out_off, n_pat, total, d_out, val_a, val_b, key_a, key_b, temp, temp_bytes, d_counter, tail_threshold, stream, timer,
-                                          member, n_member_lists, rec, while_first_step);
+    return on_bv(iv.bv_kind, [&](auto bv) { return on_flag(text_order, [&](auto to) {
+        const SweepKernels K = bind_sweep<ByteWalk<tag_t<decltype(bv)>, kWide>, ByteSampling<kWide, decltype(to)::value>, pos_t, kWide>(iv, d_l, d_out_off, n_pat, d_stats, stream,
+                                                                                                                                  rec ? front : nullptr);
+        return run_locate_sweep<pos_t, kWide>(K, d_l, d_out_off, n_pat, total, d_out, val_a, val_b, key_a, key_b, temp, temp_bytes, d_counter, tail_threshold, stream, timer,
+                                              member, n_member_lists, rec, while_first_step);
+    }); });
 }
 // K3u (above): the whole suffix array into sa_full (n words of 32 bits), then the SA intervals of the lists into d_out.
 // val / key buffers for n_samples walkers; temp as for the sweep.  Rounds are enqueued kUnsampleSync at a time: the count of walkers
@@ -1175,21 +1132,23 @@ vlg_status launch_unsample(const IndexView& iv, const uint64_t* d_l, const uint6
     if (iv.sample_bytes != (kWide ? 8u : 4u)) return fail(VLG_E_INTERNAL, "unsampling: sample width does not match the instantiation");
     if (iv.n > (1ull << 32) + 1 || (!kWide && iv.n > (1ull << 32))) return fail(VLG_E_UNSUPPORTED, "unsampling: text too long for 32-bit positions");
     if (iv.sigma >= 0x7FFFu) return fail(VLG_E_INTERNAL, "unsampling: alphabet too large for the key");
-    const bool rrr = iv.bv_kind == kBvRrr63;
     const unsigned bits = bit_width64(iv.sigma);            // keys 0 .. sigma - 1, dead = all ones in these bits too (sorts last)
     uint64_t alive = iv.n_samples, done_total = 0;
+    // one round of the walkers val_a / key_a [0, alive) as they stand when it is called; the first one makes their words
+    const auto step_round = [&](bool first) {
+        if (timer) timer->begin(0);
+        const vlg_status ks = on_bv(iv.bv_kind, [&](auto bv) { return on_flag(first, [&](auto f) {
+            return launch(unsample_step_kernel<tag_t<decltype(bv)>, kWide, decltype(f)::value>, launch_grid(alive, 8192), stream, iv, val_a, key_a, alive, sa_full, d_stats,
+                          d_counter);
+        }); });
+        if (timer) timer->end(0);
+        return ks;
+    };
     VLG_HIP_TRY(hipMemsetAsync(d_counter, 0, 8, stream));
     uint32_t round = 0;
     while (alive > tail_threshold) {
         for (uint32_t r = 0; r < kUnsampleSync; ++r, ++round) {
-            if (timer) timer->begin(0);
-            const dim3 grid = launch_grid(alive, 8192);
-#define VLG_UNS(BV) do { if (round == 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(unsample_step_kernel<BV, kWide, true>), grid, dim3(256), 0, stream, iv, val_a, key_a, alive, sa_full, d_stats, d_counter); \
-                         else hipLaunchKernelGGL(HIP_KERNEL_NAME(unsample_step_kernel<BV, kWide, false>), grid, dim3(256), 0, stream, iv, val_a, key_a, alive, sa_full, d_stats, d_counter); } while (0)
-            if (rrr) VLG_UNS(RrrBV); else VLG_UNS(PlainBV);
-#undef VLG_UNS
-            if (timer) timer->end(0);
-            VLG_HIP_TRY(hipGetLastError());
+            if (vlg_status ks = step_round(round == 0)) return ks;
             size_t tb = temp_bytes;
             if (timer) timer->begin(1, 20ull * alive);
             rocprim::double_buffer<uint16_t> dk(key_a, key_b);
@@ -1210,12 +1169,7 @@ vlg_status launch_unsample(const IndexView& iv, const uint64_t* d_l, const uint6
     }
     if (round == 0 && iv.n_samples) {
         // too few walkers for a single sorted round: round 0 still makes their words (and writes the samples themselves)
-        if (timer) timer->begin(0);
-        const dim3 grid = launch_grid(alive, 8192);
-        if (rrr) hipLaunchKernelGGL(HIP_KERNEL_NAME(unsample_step_kernel<RrrBV, kWide, true>), grid, dim3(256), 0, stream, iv, val_a, key_a, alive, sa_full, d_stats, d_counter);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(unsample_step_kernel<PlainBV, kWide, true>), grid, dim3(256), 0, stream, iv, val_a, key_a, alive, sa_full, d_stats, d_counter);
-        if (timer) timer->end(0);
-        VLG_HIP_TRY(hipGetLastError());
+        if (vlg_status ks = step_round(true)) return ks;
         ++round;
     }
     if (hook_due) { hook_due = false; if (vlg_status hs = (*while_first_step)()) return hs; }
@@ -1223,19 +1177,18 @@ vlg_status launch_unsample(const IndexView& iv, const uint64_t* d_l, const uint6
         // (after an unsorted round 0 the dead are anywhere: the tail looks at all of them)
         const uint64_t span = round == 1 ? iv.n_samples : alive;
         const LocateSlices sl = locate_slices(span, 64 * 4);
-        const dim3 grid(sl.blocks);
         if (timer) timer->begin(0);
-        if (rrr) hipLaunchKernelGGL(HIP_KERNEL_NAME(unsample_tail_kernel<RrrBV, kWide>), grid, dim3(256), 0, stream, iv, val_a, key_a, span, sl.per_wave, sa_full, d_stats);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(unsample_tail_kernel<PlainBV, kWide>), grid, dim3(256), 0, stream, iv, val_a, key_a, span, sl.per_wave, sa_full, d_stats);
+        const vlg_status ks = on_bv(iv.bv_kind, [&](auto bv) {
+            return launch(unsample_tail_kernel<tag_t<decltype(bv)>, kWide>, dim3(sl.blocks), stream, iv, val_a, key_a, span, sl.per_wave, sa_full, d_stats);
+        });
         if (timer) timer->end(0);
-        VLG_HIP_TRY(hipGetLastError());
+        if (ks) return ks;
     }
     if (total) {
         if (timer) timer->begin(0);
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(sa_dense_copy_kernel<uint32_t, uint32_t>), launch_grid((total + 7) / 8, 32768), dim3(256), 0, stream,
-                           sa_full, d_l, d_out_off, n_pat, total, d_out);
+        const vlg_status ks = launch_sa_dense_copy(sa_full, d_l, d_out_off, n_pat, total, d_out, stream);
         if (timer) timer->end(0);
-        VLG_HIP_TRY(hipGetLastError());
+        if (ks) return ks;
     }
     return VLG_OK;
 }
@@ -1251,10 +1204,7 @@ vlg_status launch_sa_dense_copy(const uint32_t* sa, const uint64_t* d_l, const u
                                 hipStream_t stream)
 {
     if (!total) return VLG_OK;
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(sa_dense_copy_kernel<uint32_t, uint32_t>), launch_grid((total + 7) / 8, 32768), dim3(256), 0, stream,
-                       sa, d_l, d_out_off, n_pat, total, d_out);
-    VLG_HIP_TRY(hipGetLastError());
-    return VLG_OK;
+    return launch(sa_dense_copy_kernel<uint32_t, uint32_t>, launch_grid((total + 7) / 8, 32768), stream, sa, d_l, d_out_off, n_pat, total, d_out);
 }
 
 #define VLG_SWEEP_INST(P, W)                                                                                                          \
@@ -1271,18 +1221,14 @@ template <typename T>
 vlg_status launch_narrow(const uint64_t* d_in, T* d_out, uint64_t count, hipStream_t stream)
 {
     if (!count) return VLG_OK;
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(narrow_kernel<T>), launch_grid(count), dim3(256), 0, stream, d_in, d_out, count);
-    VLG_HIP_TRY(hipGetLastError());
-    return VLG_OK;
+    return launch(narrow_kernel<T>, launch_grid(count), stream, d_in, d_out, count);
 }
 template vlg_status launch_narrow<uint32_t>(const uint64_t*, uint32_t*, uint64_t, hipStream_t);
 template <typename T>
 vlg_status launch_widen(const T* d_in, uint64_t* d_out, uint64_t count, hipStream_t stream)
 {
     if (!count) return VLG_OK;
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(widen_kernel<T>), launch_grid(count), dim3(256), 0, stream, d_in, d_out, count);
-    VLG_HIP_TRY(hipGetLastError());
-    return VLG_OK;
+    return launch(widen_kernel<T>, launch_grid(count), stream, d_in, d_out, count);
 }
 template vlg_status launch_widen<uint32_t>(const uint32_t*, uint64_t*, uint64_t, hipStream_t);
 
@@ -1300,14 +1246,9 @@ extern "C" vlg_status vlg_wt_rank_batch(const vlg_index* idx, const uint64_t* d_
     if (!idx || (count && (!d_i || !d_c || !d_out))) return fail(VLG_E_INVALID, "null argument");
     if (idx->is_int) return fail(VLG_E_INVALID, "integer-alphabet index: use vlg_int_rank_batch");
     if (!count) return VLG_OK;
-    if (idx->view.bv_kind == kBvRrr63)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(wt_rank_kernel<RrrBV>), launch_grid(count, 8192), dim3(256), 0, (hipStream_t)stream, idx->view, d_i, d_c,
-                           d_out, count);
-    else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(wt_rank_kernel<PlainBV>), launch_grid(count, 8192), dim3(256), 0, (hipStream_t)stream, idx->view, d_i,
-                           d_c, d_out, count);
-    VLG_HIP_TRY(hipGetLastError());
-    return VLG_OK;
+    return on_bv(idx->view.bv_kind, [&](auto bv) {
+        return launch(wt_rank_kernel<tag_t<decltype(bv)>>, launch_grid(count, 8192), (hipStream_t)stream, idx->view, d_i, d_c, d_out, count);
+    });
 }
 
 extern "C" vlg_status vlg_backward_search_batch(const vlg_index* idx, const uint8_t* d_blob, const uint64_t* d_off, uint64_t n_patterns,
@@ -1319,6 +1260,25 @@ extern "C" vlg_status vlg_backward_search_batch(const vlg_index* idx, const uint
     return launch_backward_search(idx->view, d_blob, d_off, n_patterns, d_l, d_r, nullptr, (hipStream_t)stream);
 }
 
+namespace {
+// The 32-bit path of vlg_sa_batch and vlg_locate_batch: fill(tmp) puts `count` SA indices into a scratch buffer, they are located in
+// place and widened into d_out, and the stream is synchronised before the buffer goes.
+template <class Fill>
+vlg_status locate_narrow(const vlg_index* idx, uint64_t count, uint64_t* d_out, hipStream_t st, const Fill& fill)
+{
+    DevBuf tmp_buf;
+    VLG_HIP_TRY(tmp_buf.alloc(count * 4));
+    uint32_t* tmp = tmp_buf.as<uint32_t>();
+    vlg_status s = fill(tmp);
+    if (!s) s = idx->is_int ? launch_int_locate(idx->iview, tmp, count, nullptr, st) : launch_locate<uint32_t>(idx->view, tmp, count, nullptr, st);
+    if (!s) s = launch_widen<uint32_t>(tmp, d_out, count, st);
+    const hipError_t e = hipStreamSynchronize(st);                // (before tmp goes)
+    if (s) return s;
+    VLG_HIP_TRY(e);
+    return VLG_OK;
+}
+}  // namespace
+
 extern "C" vlg_status vlg_sa_batch(const vlg_index* idx, const uint64_t* d_i, uint64_t* d_out, uint64_t count, void* stream)
 {
     if (!idx || (count && (!d_i || !d_out))) return fail(VLG_E_INVALID, "null argument");
@@ -1328,16 +1288,7 @@ extern "C" vlg_status vlg_sa_batch(const vlg_index* idx, const uint64_t* d_i, ui
         if (d_out != d_i) VLG_HIP_TRY(hipMemcpyAsync(d_out, d_i, count * 8, hipMemcpyDeviceToDevice, st));
         return launch_locate<uint64_t>(idx->view, d_out, count, nullptr, st);
     }
-    DevBuf tmp_buf;
-    VLG_HIP_TRY(tmp_buf.alloc(count * 4));
-    uint32_t* tmp = tmp_buf.as<uint32_t>();
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(narrow_kernel<uint32_t>), launch_grid(count), dim3(256), 0, st, d_i, tmp, count);
-    vlg_status s2 = idx->is_int ? launch_int_locate(idx->iview, tmp, count, nullptr, st) : launch_locate<uint32_t>(idx->view, tmp, count, nullptr, st);
-    if (!s2) hipLaunchKernelGGL(HIP_KERNEL_NAME(widen_kernel<uint32_t>), launch_grid(count), dim3(256), 0, st, tmp, d_out, count);
-    hipError_t e = hipStreamSynchronize(st);                      // (before tmp goes)
-    if (s2) return s2;
-    VLG_HIP_TRY(e);
-    return VLG_OK;
+    return locate_narrow(idx, count, d_out, st, [&](uint32_t* tmp) { return launch_narrow<uint32_t>(d_i, tmp, count, st); });
 }
 
 extern "C" vlg_status vlg_locate_batch(const vlg_index* idx, const uint64_t* d_l, const uint64_t* d_r, const uint64_t* d_out_off,
@@ -1351,16 +1302,7 @@ extern "C" vlg_status vlg_locate_batch(const vlg_index* idx, const uint64_t* d_l
         if (vlg_status s = launch_expand<uint64_t>(d_l, d_out_off, n_patterns, total, d_out, nullptr, st)) return s;
         return launch_locate<uint64_t>(idx->view, d_out, total, nullptr, st);
     }
-    DevBuf tmp_buf;
-    VLG_HIP_TRY(tmp_buf.alloc(total * 4));
-    uint32_t* tmp = tmp_buf.as<uint32_t>();
-    vlg_status s2 = launch_expand<uint32_t>(d_l, d_out_off, n_patterns, total, tmp, nullptr, st);
-    if (!s2) s2 = idx->is_int ? launch_int_locate(idx->iview, tmp, total, nullptr, st) : launch_locate<uint32_t>(idx->view, tmp, total, nullptr, st);
-    if (!s2) hipLaunchKernelGGL(HIP_KERNEL_NAME(widen_kernel<uint32_t>), launch_grid(total), dim3(256), 0, st, tmp, d_out, total);
-    hipError_t e = hipStreamSynchronize(st);                      // (before tmp goes)
-    if (s2) return s2;
-    VLG_HIP_TRY(e);
-    return VLG_OK;
+    return locate_narrow(idx, total, d_out, st, [&](uint32_t* tmp) { return launch_expand<uint32_t>(d_l, d_out_off, n_patterns, total, tmp, nullptr, st); });
 }
 
 namespace {
@@ -1374,24 +1316,11 @@ vlg_status isa_samples_device(const vlg_index* idx, uint32_t inv_dens, void* d_o
     VLG_HIP_TRY(hipMemsetAsync(d_out, 0, count * w, st));
     if (idx->is_int)                                               // the walk on the wavelet matrix (int_index.hpp), plain or rrr levels
         return launch_int_isa_samples(idx->iview, inv_dens, (uint32_t*)d_out, st);
-    const dim3 grid = launch_grid(idx->view.n_samples, 8192);
-    const bool rrr = idx->view.bv_kind == kBvRrr63, wide = idx->hdr.sample_bytes == 8;
-#define VLG_ISA_SAMPLES(BV_, POS_, OUT_) \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(isa_samples_kernel<BV_, POS_, OUT_>), grid, dim3(256), 0, st, idx->view, inv_dens, (OUT_*)d_out)
-    if (w == 8) {
-        if (rrr && wide) VLG_ISA_SAMPLES(RrrBV, uint64_t, uint64_t);
-        else if (rrr) VLG_ISA_SAMPLES(RrrBV, uint32_t, uint64_t);
-        else if (wide) VLG_ISA_SAMPLES(PlainBV, uint64_t, uint64_t);
-        else VLG_ISA_SAMPLES(PlainBV, uint32_t, uint64_t);
-    } else {
-        if (rrr && wide) VLG_ISA_SAMPLES(RrrBV, uint64_t, uint32_t);
-        else if (rrr) VLG_ISA_SAMPLES(RrrBV, uint32_t, uint32_t);
-        else if (wide) VLG_ISA_SAMPLES(PlainBV, uint64_t, uint32_t);
-        else VLG_ISA_SAMPLES(PlainBV, uint32_t, uint32_t);
-    }
-#undef VLG_ISA_SAMPLES
-    VLG_HIP_TRY(hipGetLastError());
-    return VLG_OK;
+    const IndexView& iv = idx->view;
+    return on_bv(iv.bv_kind, [&](auto bv) { return on_isa_samples_shape(shape(iv).wide, w, [&](auto pos, auto out) {
+        using out_t = tag_t<decltype(out)>;
+        return launch(isa_samples_kernel<tag_t<decltype(bv)>, tag_t<decltype(pos)>, out_t>, launch_grid(iv.n_samples, 8192), st, iv, inv_dens, (out_t*)d_out);
+    }); });
 }
 }  // namespace
 
@@ -1497,23 +1426,12 @@ extern "C" vlg_status vlg_extract_batch(const vlg_text_access* t, const uint64_t
     else if (h[0]) s = fail(VLG_E_INVALID, std::to_string(h[0]) + " extract range(s) with begin > end, end >= n, or output beyond total");
     if (!s) {
         const ExtractJob job{d_begin, d_end, d_out_off, seg, n_ranges, h[1], idx->hdr.n, t->d};
-        const dim3 grid = launch_grid(h[1], 8192);
+        const IndexView& iv = idx->view;
         if (idx->is_int) s = launch_int_extract(idx->iview, job, (const uint32_t*)t->d_isa, (uint32_t*)d_out, st);
-        else {
-            const bool rrr = idx->view.bv_kind == kBvRrr63, wide = idx->hdr.sample_bytes == 8, w8 = t->isa_bytes == 8;
-#define VLG_EXTRACT(BV_, W_, ISA_) \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(extract_kernel<BV_, W_, ISA_>), grid, dim3(256), 0, st, idx->view, job, (const ISA_*)t->d_isa, t->d_c2c, (uint8_t*)d_out)
-            if (w8) {                                              // n >= 2^32: SA indices are wide too
-                if (rrr) VLG_EXTRACT(RrrBV, true, uint64_t);
-                else VLG_EXTRACT(PlainBV, true, uint64_t);
-            } else if (rrr && wide) VLG_EXTRACT(RrrBV, true, uint32_t);
-            else if (rrr) VLG_EXTRACT(RrrBV, false, uint32_t);
-            else if (wide) VLG_EXTRACT(PlainBV, true, uint32_t);
-            else VLG_EXTRACT(PlainBV, false, uint32_t);
-#undef VLG_EXTRACT
-            e = hipGetLastError();
-            if (e != hipSuccess) s = fail(VLG_E_NO_DEVICE, std::string("extract: ") + hipGetErrorString(e));
-        }
+        else s = on_bv(iv.bv_kind, [&](auto bv) { return on_text_access_shape(shape(iv).wide, t->isa_bytes, [&](auto wide, auto isa) {
+            using isa_t = tag_t<decltype(isa)>;
+            return launch(extract_kernel<tag_t<decltype(bv)>, decltype(wide)::value, isa_t>, launch_grid(h[1], 8192), st, iv, job, (const isa_t*)t->d_isa, t->d_c2c, (uint8_t*)d_out);
+        }); });
         e = hipStreamSynchronize(st);                              // the scratch is freed on return
         if (!s && e != hipSuccess) s = fail(VLG_E_NO_DEVICE, std::string("extract: ") + hipGetErrorString(e));
     }
@@ -1534,21 +1452,10 @@ extern "C" vlg_status vlg_isa_batch(const vlg_text_access* t, const uint64_t* d_
     hipError_t e = hipMemsetAsync(d_bad, 0, 8, st);
     if (e == hipSuccess) {
         if (idx->is_int) s = launch_int_isa(idx->iview, t->d, (const uint32_t*)t->d_isa, d_i, d_out, count, d_bad, st);
-        else {
-            const dim3 grid = launch_grid(count, 8192);
-            const bool rrr = idx->view.bv_kind == kBvRrr63, wide = idx->hdr.sample_bytes == 8, w8 = t->isa_bytes == 8;
-#define VLG_ISA(BV_, W_, ISA_) \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(isa_kernel<BV_, W_, ISA_>), grid, dim3(256), 0, st, idx->view, t->d, (const ISA_*)t->d_isa, d_i, d_out, count, d_bad)
-            if (w8) {
-                if (rrr) VLG_ISA(RrrBV, true, uint64_t);
-                else VLG_ISA(PlainBV, true, uint64_t);
-            } else if (rrr && wide) VLG_ISA(RrrBV, true, uint32_t);
-            else if (rrr) VLG_ISA(RrrBV, false, uint32_t);
-            else if (wide) VLG_ISA(PlainBV, true, uint32_t);
-            else VLG_ISA(PlainBV, false, uint32_t);
-#undef VLG_ISA
-            e = hipGetLastError();
-        }
+        else s = on_bv(idx->view.bv_kind, [&](auto bv) { return on_text_access_shape(shape(idx->view).wide, t->isa_bytes, [&](auto wide, auto isa) {
+            using isa_t = tag_t<decltype(isa)>;
+            return launch(isa_kernel<tag_t<decltype(bv)>, decltype(wide)::value, isa_t>, launch_grid(count, 8192), st, idx->view, t->d, (const isa_t*)t->d_isa, d_i, d_out, count, d_bad);
+        }); });
     }
     if (e == hipSuccess && !s) e = hipMemcpyAsync(&h_bad, d_bad, 8, hipMemcpyDeviceToHost, st);
     const hipError_t e2 = hipStreamSynchronize(st);
@@ -1675,6 +1582,15 @@ __global__ void __launch_bounds__(256) lf_bwt_kernel(IndexView iv, const uint64_
     }
 }
 
+// the hint pass of select_support_finish over one source of counts
+template <class Counts>
+auto select_hints_pass(const Counts& src, uint32_t shift, hipStream_t st)
+{
+    return [=](const SelNode* nd, const uint32_t* list, const uint64_t* first, uint32_t n_list, uint32_t* hints, dim3 grid) {
+        return launch(select_hints_kernel<Counts>, grid, st, src, nd, list, first, n_list, shift, hints);
+    };
+}
+
 bool select_sample_shift(uint32_t sample, uint32_t& shift)
 {
     const uint32_t s = sample ? sample : kSelectSampleDefault;
@@ -1684,7 +1600,8 @@ bool select_sample_shift(uint32_t sample, uint32_t& shift)
 }
 
 // Lay the handle out, upload its tables and run the hint pass.  nodes: every SelNode with size, ones, base, nb, up set (nb = 0: no
-// bit-vector, a leaf); hint offsets are assigned here.  run(nodes, list, first, n_list, hints) launches the pass for the source's layout.
+// bit-vector, a leaf); hint offsets are assigned here.  run(nodes, list, first, n_list, hints, grid) launches the pass for the source's
+// layout (select_hints_pass).
 template <class Run>
 vlg_status select_support_finish(vlg_select_support* s, std::vector<SelNode>& nodes, const std::vector<uint32_t>& leaf_up, uint32_t shift, hipStream_t st,
                                  const Run& run)
@@ -1716,9 +1633,8 @@ vlg_status select_support_finish(vlg_select_support* s, std::vector<SelNode>& no
     VLG_HIP_TRY(hipMemcpyAsync(b + off_first, first.data(), first.size() * 8, hipMemcpyHostToDevice, st));
     VLG_HIP_TRY(hipMemsetAsync(b + off_hints, 0, std::max<uint64_t>(n_hints, 1) * 4, st));
     if (!list.empty()) {
-        run(s->view.nodes, reinterpret_cast<const uint32_t*>(b + off_list), reinterpret_cast<const uint64_t*>(b + off_first), (uint32_t)list.size(),
-            reinterpret_cast<uint32_t*>(b + off_hints), launch_grid(first.back(), 8192));
-        VLG_HIP_TRY(hipGetLastError());
+        if (vlg_status r = run(s->view.nodes, reinterpret_cast<const uint32_t*>(b + off_list), reinterpret_cast<const uint64_t*>(b + off_first), (uint32_t)list.size(),
+                               reinterpret_cast<uint32_t*>(b + off_hints), launch_grid(first.back(), 8192))) return r;
     }
     VLG_HIP_TRY(hipStreamSynchronize(st));                         // (the host tables are read until here)
     return VLG_OK;
@@ -1756,12 +1672,8 @@ extern "C" vlg_status vlg_bitvector_select_create(const vlg_bitvector* bv, uint3
         for (uint32_t w = 0; w < 7; ++w) ones += (uint32_t)__builtin_popcount(last.w[w]);
     }
     std::vector<SelNode> nodes(1, SelNode{bv->nbits, ones, 0, 0, 0, (uint32_t)bv->n_blocks, kSelNoParent, 0});
-    const PlainCounts src{bv->d_blocks};
     hipStream_t st = (hipStream_t)stream;
-    if (vlg_status r = select_support_finish(s.get(), nodes, {}, shift, st, [&](const SelNode* nd, const uint32_t* list, const uint64_t* first, uint32_t n_list,
-                                                                                 uint32_t* hints, dim3 grid) {
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(select_hints_kernel<PlainCounts>), grid, dim3(256), 0, st, src, nd, list, first, n_list, shift, hints);
-        })) return r;
+    if (vlg_status r = select_support_finish(s.get(), nodes, {}, shift, st, select_hints_pass(PlainCounts{bv->d_blocks}, shift, st))) return r;
     *out = s.release();
     return VLG_OK;
 }
@@ -1788,12 +1700,8 @@ extern "C" vlg_status vlg_rrr_bitvector_select_create(const vlg_rrr_bitvector* b
         }
     }
     std::vector<SelNode> nodes(1, SelNode{bv->nbits, ones, 0, 0, 0, (uint32_t)bv->n_sb, kSelNoParent, 0});
-    const RrrCounts src{bv->d_hdr};
     hipStream_t st = (hipStream_t)stream;
-    if (vlg_status r = select_support_finish(s.get(), nodes, {}, shift, st, [&](const SelNode* nd, const uint32_t* list, const uint64_t* first, uint32_t n_list,
-                                                                                 uint32_t* hints, dim3 grid) {
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(select_hints_kernel<RrrCounts>), grid, dim3(256), 0, st, src, nd, list, first, n_list, shift, hints);
-        })) return r;
+    if (vlg_status r = select_support_finish(s.get(), nodes, {}, shift, st, select_hints_pass(RrrCounts{bv->d_hdr}, shift, st))) return r;
     *out = s.release();
     return VLG_OK;
 }
@@ -1811,7 +1719,7 @@ extern "C" vlg_status vlg_index_select_create(const vlg_index* idx, uint32_t sam
     bool rrr;
     if (idx->is_int) {                                             // one node per level of the matrix: n bits, n - Z[l] ones
         const IntView& v = idx->iview;
-        rrr = v.bv_kind == kBvRrr63;
+        rrr = shape(v).rrr;
         uint64_t Z[kMaxIntLevels] = {0};
         if (v.n_levels) VLG_HIP_TRY(hipMemcpy(Z, v.Z, v.n_levels * 8, hipMemcpyDeviceToHost));
         for (uint32_t l = 0; l < v.n_levels; ++l) {
@@ -1820,7 +1728,7 @@ extern "C" vlg_status vlg_index_select_create(const vlg_index* idx, uint32_t sam
         }
     } else {                                                       // the tree as the kernels walk it; sizes from the symbol counts
         const IndexView& v = idx->view;
-        rrr = v.bv_kind == kBvRrr63;
+        rrr = shape(v).rrr;
         const uint32_t nn = v.n_nodes, sigma = v.sigma;
         std::vector<DNode> dn(std::max<uint32_t>(nn, 1));
         std::vector<uint64_t> Cc(sigma + 1, 0);
@@ -1856,13 +1764,9 @@ extern "C" vlg_status vlg_index_select_create(const vlg_index* idx, uint32_t sam
         }
     }
     hipStream_t st = (hipStream_t)stream;
-    const PlainCounts plain{idx->is_int ? idx->iview.blocks : idx->view.blocks};
-    const RrrCounts packed{idx->is_int ? idx->iview.rrr_hdr : idx->view.rrr_hdr};
-    if (vlg_status r = select_support_finish(s.get(), nodes, leaf_up, shift, st, [&](const SelNode* nd, const uint32_t* list, const uint64_t* first, uint32_t n_list,
-                                                                                      uint32_t* hints, dim3 grid) {
-            if (rrr) hipLaunchKernelGGL(HIP_KERNEL_NAME(select_hints_kernel<RrrCounts>), grid, dim3(256), 0, st, packed, nd, list, first, n_list, shift, hints);
-            else hipLaunchKernelGGL(HIP_KERNEL_NAME(select_hints_kernel<PlainCounts>), grid, dim3(256), 0, st, plain, nd, list, first, n_list, shift, hints);
-        })) return r;
+    const auto finish = [&](const auto& src) { return select_support_finish(s.get(), nodes, leaf_up, shift, st, select_hints_pass(src, shift, st)); };
+    if (vlg_status r = rrr ? finish(RrrCounts{idx->is_int ? idx->iview.rrr_hdr : idx->view.rrr_hdr}) : finish(PlainCounts{idx->is_int ? idx->iview.blocks : idx->view.blocks}))
+        return r;
     *out = s.release();
     return VLG_OK;
 }
@@ -1883,17 +1787,12 @@ extern "C" vlg_status vlg_bit_select_batch(const vlg_select_support* s, int bit,
     if (s->kind == kSelIndex) return fail(VLG_E_INVALID, "bit select: the support was made from an index (use vlg_wt_select_batch / vlg_int_select_batch)");
     if (!count) return VLG_OK;
     hipStream_t st = (hipStream_t)stream;
-    if (s->kind == kSelPlainBv) {
-        const BitsView bv{s->bv->d_blocks};
-        if (bit) hipLaunchKernelGGL(HIP_KERNEL_NAME(bit_select_kernel<1>), launch_grid(count, 8192), dim3(256), 0, st, bv, s->view, d_k, d_out, count);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(bit_select_kernel<0>), launch_grid(count, 8192), dim3(256), 0, st, bv, s->view, d_k, d_out, count);
-    } else {
+    return on_flag(bit != 0, [&](auto one) {
+        constexpr int kBit = decltype(one)::value ? 1 : 0;
+        if (s->kind == kSelPlainBv) return launch(bit_select_kernel<kBit>, launch_grid(count, 8192), st, BitsView{s->bv->d_blocks}, s->view, d_k, d_out, count);
         const vlg_rrr_bitvector* r = s->rrr;
-        if (bit) hipLaunchKernelGGL(HIP_KERNEL_NAME(rrr_bit_select_kernel<1>), launch_grid(count, 2048), dim3(256), 0, st, r->d_hdr, r->d_stream, r->d_binom, s->view, d_k, d_out, count);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(rrr_bit_select_kernel<0>), launch_grid(count, 2048), dim3(256), 0, st, r->d_hdr, r->d_stream, r->d_binom, s->view, d_k, d_out, count);
-    }
-    VLG_HIP_TRY(hipGetLastError());
-    return VLG_OK;
+        return launch(rrr_bit_select_kernel<kBit>, launch_grid(count, 2048), st, r->d_hdr, r->d_stream, r->d_binom, s->view, d_k, d_out, count);
+    });
 }
 
 extern "C" vlg_status vlg_wt_select_batch(const vlg_select_support* s, const uint64_t* d_k, const uint8_t* d_c, uint64_t* d_out, uint64_t count, void* stream)
@@ -1902,13 +1801,9 @@ extern "C" vlg_status vlg_wt_select_batch(const vlg_select_support* s, const uin
     if (s->kind != kSelIndex) return fail(VLG_E_INVALID, "wt select: the support was made from a bit-vector (use vlg_bit_select_batch)");
     if (s->idx->is_int) return fail(VLG_E_INVALID, "integer-alphabet index: use vlg_int_select_batch");
     if (!count) return VLG_OK;
-    const dim3 grid = launch_grid(count, 8192);
-    if (s->idx->view.bv_kind == kBvRrr63)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(wt_select_kernel<RrrBV, false>), grid, dim3(256), 0, (hipStream_t)stream, s->idx->view, s->view, d_k, d_c, d_out, count);
-    else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(wt_select_kernel<PlainBV, false>), grid, dim3(256), 0, (hipStream_t)stream, s->idx->view, s->view, d_k, d_c, d_out, count);
-    VLG_HIP_TRY(hipGetLastError());
-    return VLG_OK;
+    return on_bv(s->idx->view.bv_kind, [&](auto bv) {
+        return launch(wt_select_kernel<tag_t<decltype(bv)>, false>, launch_grid(count, 8192), (hipStream_t)stream, s->idx->view, s->view, d_k, d_c, d_out, count);
+    });
 }
 
 extern "C" vlg_status vlg_int_select_batch(const vlg_select_support* s, const uint64_t* d_k, const uint32_t* d_sym, uint64_t* d_out, uint64_t count, void* stream)
@@ -1926,29 +1821,19 @@ extern "C" vlg_status vlg_psi_batch(const vlg_select_support* s, const uint64_t*
     if (s->kind != kSelIndex) return fail(VLG_E_INVALID, "psi: the support was made from a bit-vector");
     if (!count) return VLG_OK;
     if (s->idx->is_int) return launch_int_select(s->idx->iview, s->view, d_i, nullptr, d_out, count, (hipStream_t)stream);
-    const dim3 grid = launch_grid(count, 8192);
-    if (s->idx->view.bv_kind == kBvRrr63)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(wt_select_kernel<RrrBV, true>), grid, dim3(256), 0, (hipStream_t)stream, s->idx->view, s->view, d_i, nullptr, d_out, count);
-    else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(wt_select_kernel<PlainBV, true>), grid, dim3(256), 0, (hipStream_t)stream, s->idx->view, s->view, d_i, nullptr, d_out, count);
-    VLG_HIP_TRY(hipGetLastError());
-    return VLG_OK;
+    return on_bv(s->idx->view.bv_kind, [&](auto bv) {
+        return launch(wt_select_kernel<tag_t<decltype(bv)>, true>, launch_grid(count, 8192), (hipStream_t)stream, s->idx->view, s->view, d_i, nullptr, d_out, count);
+    });
 }
 
 namespace {
 vlg_status lf_bwt_batch(const vlg_index* idx, const uint64_t* d_i, uint64_t* d_lf, void* d_bwt, uint64_t count, hipStream_t st)
 {
     if (idx->is_int) return launch_int_lf_bwt(idx->iview, d_i, d_lf, (uint32_t*)d_bwt, count, st);
-    const dim3 grid = launch_grid(count, 8192);
-    const bool rrr = idx->view.bv_kind == kBvRrr63, wide = idx->hdr.sample_bytes == 8;
-#define VLG_LF_BWT(BV_, W_) hipLaunchKernelGGL(HIP_KERNEL_NAME(lf_bwt_kernel<BV_, W_>), grid, dim3(256), 0, st, idx->view, d_i, d_lf, (uint8_t*)d_bwt, count)
-    if (rrr && wide) VLG_LF_BWT(RrrBV, true);
-    else if (rrr) VLG_LF_BWT(RrrBV, false);
-    else if (wide) VLG_LF_BWT(PlainBV, true);
-    else VLG_LF_BWT(PlainBV, false);
-#undef VLG_LF_BWT
-    VLG_HIP_TRY(hipGetLastError());
-    return VLG_OK;
+    const IndexView& iv = idx->view;
+    return on_bv(iv.bv_kind, [&](auto bv) { return on_flag(shape(iv).wide, [&](auto wide) {
+        return launch(lf_bwt_kernel<tag_t<decltype(bv)>, decltype(wide)::value>, launch_grid(count, 8192), st, iv, d_i, d_lf, (uint8_t*)d_bwt, count);
+    }); });
 }
 }  // namespace
 

@@ -1,4 +1,5 @@
-// Internal launch interface between kernels.hip and search.hip.
+// Internal launch interface between kernels.hip and search.hip.  A launcher takes a view and decides nothing about its shape by hand:
+// which instantiation runs -- bit-vector kind, index width, sampling -- is chosen through shape_dispatch.hpp, inside the launcher.
 #pragma once
 #include <algorithm>
 #include <functional>
@@ -49,8 +50,8 @@ vlg_status launch_locate_sweep(const IndexView& iv, const uint64_t* d_l, const u
                                hipStream_t stream, LaunchTimer* timer, Block* member, uint32_t n_member_lists, uint64_t* rec,
                                const std::function<vlg_status()>* while_first_step = nullptr,
                                uint8_t* front = nullptr /* with rec: one byte per element, the symbol in front of it (see SweepKernels) */);
-// The three launches of a sorted sweep over some index; run_locate_sweep owns the rounds, the partitions, the member bit-vector, the
-// records and their resolution.  `out` is the sweep's slice of the position array (pos_t*), `rec` null when no LF step is shared.
+// The three launches of a sorted sweep over some index (filled by bind_sweep, sweep_kernels.hpp; each returns the launch's status);
+// run_locate_sweep owns the rounds, the partitions, the member bit-vector, the records and their resolution.  `out` is the sweep's slice of the position array (pos_t*), `rec` null when no LF step is shared.
 constexpr uint32_t kSweepChunk = 2048;          // elements a workgroup of the first round takes per turn
 // the list that holds the first element of every chunk of a sweep [t0, t1): looked up for all chunks at once, in parallel, instead of by
 // one lane of every workgroup in front of its work (a binary search is seventeen dependent loads)
@@ -62,13 +63,13 @@ struct SweepKernels {
     uint64_t n = 0;
     uint32_t sigma = 0;                  // partition keys are the symbols 0 .. sigma - 1 (16 bits at most); sigma = finished
     // round 0 of the elements [t0, t1): their words follow from their places (lists l / out_off are the launcher's business)
-    std::function<void(uint64_t t0, uint64_t t1, uint64_t* val, uint16_t* key, void* out, unsigned long long* n_done, const Block* member, uint64_t* rec, bool ahead,
+    std::function<vlg_status(uint64_t t0, uint64_t t1, uint64_t* val, uint16_t* key, void* out, unsigned long long* n_done, const Block* member, uint64_t* rec, bool ahead,
                        uint32_t* chunk_list /* scratch, one word per kSweepChunk elements: sweep_chunk_lists_kernel */)> first;
     // one round of the elements val / key [0, alive)
-    std::function<void(uint64_t* val, uint16_t* key, uint64_t alive, uint32_t step, void* out, unsigned long long* n_done, const Block* member, uint64_t* rec, uint64_t t0,
+    std::function<vlg_status(uint64_t* val, uint16_t* key, uint64_t alive, uint32_t step, void* out, unsigned long long* n_done, const Block* member, uint64_t* rec, uint64_t t0,
                        bool probed)> step;
     // the stragglers, unsorted: a wave owns per_wave elements of val
-    std::function<void(void* out, uint64_t alive, uint32_t per_wave, const uint64_t* val, uint32_t step, uint64_t* rec_or_null, uint64_t t0, const Block* member,
+    std::function<vlg_status(void* out, uint64_t alive, uint32_t per_wave, const uint64_t* val, uint32_t step, uint64_t* rec_or_null, uint64_t t0, const Block* member,
                        uint32_t blocks)> tail;
 };
 template <typename pos_t, bool kWide>

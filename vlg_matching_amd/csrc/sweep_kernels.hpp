@@ -1,10 +1,12 @@
 // The locate family, written once over the LF-walk policy (lf_walk.hpp): the sorted sweep's rounds (sweep_first_kernel,
 // sweep_step_kernel) and the refilling-lane walk that locates in place and finishes the sweep's stragglers (locate_kernel).
-// kernels.hip instantiates them with ByteWalk for the byte index, int_index.hpp with IntWalk for the integer index (kWide = false,
-// pos_t = uint32_t, front = nullptr); run_locate_sweep (kernels.hip) drives both.
+// bind_sweep (at the end) fills the sweep's three launches for one <Walk, Sampling, pos_t, kWide>; which one an index gets is decided
+// through shape_dispatch.hpp by its launcher -- launch_locate_sweep (kernels.hip: ByteWalk) or launch_int_locate_sweep (int_index.hpp:
+// IntWalk, kWide = false, pos_t = uint32_t, front = nullptr) -- and run_locate_sweep (kernels.hip) drives both.
 #pragma once
 #include "lf_walk.hpp"
 #include "kernels.hpp"
+#include "shape_dispatch.hpp"
 
 namespace vlg {
 
@@ -412,6 +414,47 @@ __global__ void __launch_bounds__(256) sweep_first_kernel(typename Walk::View iv
     unsigned long long v[3] = {n_lf, n_lv, n_fin};
     unsigned long long* const dst[3] = {&stats[0], &stats[1], n_done};
     block_add<3>(v, dst);
+}
+
+// The sweep's launches over one walk and one sampling.  run_locate_sweep calls them after this frame has gone, so they hold the view
+// and everything else by value.  front: null unless the resolve regroups by it (SweepKernels).
+template <class Walk, class Sampling, typename pos_t, bool kWide>
+SweepKernels bind_sweep(const typename Walk::View& iv, const uint64_t* d_l, const uint64_t* d_out_off, uint64_t n_pat, unsigned long long* d_stats,
+                        hipStream_t stream, uint8_t* front)
+{
+    SweepKernels K;
+    K.n = iv.n;
+    K.sigma = (uint32_t)iv.sigma;
+    K.front = front;
+    K.first = [=](uint64_t t0, uint64_t t1, uint64_t* val, uint16_t* key, void* out, unsigned long long* counter, const Block* mem, uint64_t* rc, bool ahead,
+                  uint32_t* chunk_list) {
+        launch_sweep_chunk_lists(d_out_off, n_pat, t0, t1, chunk_list, stream);
+        return on_trails_ahead(mem != nullptr, ahead, [&](auto tr, auto ah) {
+            return launch(sweep_first_kernel<Walk, Sampling, pos_t, decltype(tr)::value, kWide, decltype(ah)::value>, launch_grid((t1 - t0 + 7) / 8, 8192), stream, iv,
+                          d_l, d_out_off, n_pat, t0, t1, val, key, static_cast<pos_t*>(out), d_stats, counter, mem, rc, chunk_list, front);
+        });
+    };
+    K.step = [=](uint64_t* val, uint16_t* key, uint64_t alive, uint32_t step, void* out, unsigned long long* counter, const Block* mem, uint64_t* rc, uint64_t t0, bool probed) {
+        return on_flag(mem != nullptr, [&](auto tr) {
+            return launch(sweep_step_kernel<Walk, Sampling, pos_t, decltype(tr)::value, kWide>, launch_grid(alive, 4096), stream, iv, val, key, alive, step,
+                          static_cast<pos_t*>(out), d_stats, counter, mem, rc, t0, probed);
+        });
+    };
+    K.tail = [=](void* out, uint64_t alive, uint32_t per_wave, const uint64_t* val, uint32_t step, uint64_t* rc, uint64_t t0, const Block* mem, uint32_t blocks) {
+        return launch(locate_kernel<Walk, Sampling, pos_t, true, kWide>, dim3(blocks), stream, iv, static_cast<pos_t*>(out), alive, per_wave, d_stats, val, step, rc, t0, mem);
+    };
+    return K;
+}
+
+// Every SA index is sampled (SA-order samples of density 1): no walk, no trails, no records -- the sweep is `copy`, one launch
+template <class Copy>
+vlg_status sweep_dense_copy(LaunchTimer* timer, const std::function<vlg_status()>* while_first_step, const Copy& copy)
+{
+    if (timer) timer->begin(0);
+    const vlg_status s = copy();
+    if (timer) timer->end(0);
+    if (s) return s;
+    return while_first_step ? (*while_first_step)() : VLG_OK;
 }
 
 }  // namespace vlg
