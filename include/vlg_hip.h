@@ -633,6 +633,43 @@ vlg_status vlg_queries_parse_int_mapped(const vlg_symbol_map* map, const char* h
 /* sdsl::locate / count on the batch, at most max_matches_per_query matches each (0 = all). */
 vlg_status vlg_wtsa_search_batch(const vlg_wtsa* idx, const vlg_queries* q, uint64_t max_matches_per_query, vlg_workspace* ws,
                                  vlg_result** out);
+/* The same search inside a text window per query: query j is answered on [h_begin[j], h_end[j]) and its matches are exactly those of
+ * the same query on the stand-alone text T[begin, end), with begin added to every position -- what a caller with a document
+ * collection, or one that pages through matches, asks for.  An occurrence of a sub-pattern of m symbols counts only if it lies wholly
+ * inside: begin <= v and v + m <= end.  h_begin / h_end are host arrays of vlg_queries_count(q) entries; a NULL h_begin means all
+ * zeros, a NULL h_end "to the end of the text", an end beyond the text is clamped to it (and a begin beyond it is an empty window).
+ * begin[j] > end[j] gives VLG_E_INVALID, decided on the host before any launch; a window shorter than a sub-pattern, or begin == end,
+ * is an empty query and no error.  Gaps, end_len, max_matches_per_query and the workspace's "tuples" option keep their meaning; the
+ * checksum is the sum over what is returned; byte and integer alphabets, parsed and caller-built batches are taken.
+ * The occurrence list of a sub-pattern exists only as the sorted values of its suffix-array range, so the window is a rank interval of
+ * it: two count_less walks per sub-pattern (wt_int::range_search_2d's descent to the value bounds, include/sdsl/wt_int.hpp:612-700),
+ * nothing located, nothing sorted -- the cost follows the matches inside the window.  vlg_wtsa_search_batch is this call with two NULLs.
+ * (vlg_search_batch on the FM-index takes no windows: its sorted lists are shared between the queries of a batch) */
+vlg_status vlg_wtsa_search_window_batch(const vlg_wtsa* idx, const vlg_queries* q, const uint64_t* h_begin, const uint64_t* h_end,
+                                        uint64_t max_matches_per_query, vlg_workspace* ws, vlg_result** out);
+/* Where a search stopped, so that it can be continued as the reference's iterator continues (pull_forward, include/sdsl/vlg_index.hpp:254-266):
+ * h_next[j] (vlg_queries_count entries) = the position at which the next search of query j has to begin -- the last position of its last
+ * returned match + end_len, and never beyond the window's end, so that it can be passed back as it is -- when the query stopped at
+ * max_matches_per_query; UINT64_MAX when it ran out of matches inside its window.  Searching again with begin[j] = next[j] and the same
+ * end[j], without the queries that gave UINT64_MAX, yields the following matches: all pages together are the uncapped search of the
+ * window, whatever the page size.  A query that returned exactly max_matches_per_query matches and has none left reports a position;
+ * the following call returns no match and UINT64_MAX.  A result that does not come from a vlg_wtsa_* search gives VLG_E_INVALID. */
+vlg_status vlg_result_next_positions(const vlg_result* r, uint64_t* h_next);
+/* wt_int::range_search_2d(lb, rb, vlb, vrb) (include/sdsl/wt_int.hpp:612-700) on the tree over the suffix array, as a batched pair: the
+ * occurrences of a suffix-array range whose text position lies in [vlb, vrb].
+ * count:  d_count[j] = number of SA[d_l[j], d_l[j] + d_len[j]) with d_vlb[j] <= value <= d_vrb[j]
+ *         (range_search_2d(lb, rb, vlb, vrb, false).first, wt_int.hpp:621-635)
+ * report: those values, ASCENDING, range j written from d_out[d_out_off[j]] on; d_out_off = the exclusive prefix sum of the counts
+ *         (count + 1 entries, as vlg_locate_batch takes it), total = d_out_off[count].
+ * The reference returns (suffix-array index, value) pairs in the order of its descent; this returns the values alone, sorted: a text
+ * position is what a caller of this index wants, and the index of a value would need a select structure the device tree does not keep.
+ * A range outside the suffix array gives the count ~0 and writes nothing (like vlg_wtsa_range_walk_batch); vlb > vrb gives 0; a vrb
+ * beyond every value is clamped.  Both calls are asynchronous on `stream`. */
+vlg_status vlg_wtsa_range_count_batch(const vlg_wtsa* idx, const uint64_t* d_l, const uint64_t* d_len, const uint64_t* d_vlb,
+                                      const uint64_t* d_vrb, uint64_t* d_count, uint64_t count, void* stream);
+vlg_status vlg_wtsa_range_report_batch(const vlg_wtsa* idx, const uint64_t* d_l, const uint64_t* d_len, const uint64_t* d_vlb,
+                                       const uint64_t* d_vrb, const uint64_t* d_out_off, uint64_t count, uint64_t total,
+                                       uint64_t* d_out, void* stream);
 
 /* Per-kernel accounting of the last calls on this workspace (HIP events on the workspace stream).
  * Enabled with vlg_workspace_profile(ws, 1); reset by vlg_workspace_profile(ws, 1) again. */

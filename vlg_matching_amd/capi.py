@@ -193,6 +193,10 @@ SYMBOLS = [
     ("vlg_symbol_map_apply", _I, [_P, _P, _U64, _P]),
     ("vlg_symbol_map_destroy", None, [_P]),
     ("vlg_wtsa_search_batch", _I, [_P, _P, _U64, _P, C.POINTER(_P)]),
+    ("vlg_wtsa_search_window_batch", _I, [_P, _P, _P, _P, _U64, _P, C.POINTER(_P)]),
+    ("vlg_result_next_positions", _I, [_P, _P]),
+    ("vlg_wtsa_range_count_batch", _I, [_P, _P, _P, _P, _P, _P, _U64, _P]),
+    ("vlg_wtsa_range_report_batch", _I, [_P, _P, _P, _P, _P, _P, _U64, _U64, _P, _P]),
     ("vlg_workspace_profile", _I, [_P, _I]),
     ("vlg_workspace_set_option", _I, [_P, C.c_char_p, C.c_int64]),
     ("vlg_workspace_kernel_stats", _I, [_P, C.POINTER(KernelStat), C.c_uint32, C.POINTER(C.c_uint32)]),

@@ -340,6 +340,8 @@ struct vlg_result {
     std::vector<uint32_t> k;               // host: sub-patterns per query
     std::vector<ResultPiece> pieces;
     std::vector<uint64_t> owned;           // collective search: [begin, end) pairs of the queries this rank joined (empty: all of them)
+    std::vector<uint64_t> next;            // vlg_wtsa_* searches: per query, where the next search continues this one (~0: it ran out)
+    bool has_next = false;
 };
 
 // Result buffers are large and batches come one after the other: freed buffers are parked (up to kResultCacheBytes) and

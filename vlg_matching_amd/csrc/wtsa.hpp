@@ -18,6 +18,7 @@
 // independent walks in flight.
 #pragma once
 #include "device_rank.hpp"
+#include "extract.hpp"
 
 struct vlg_wtsa {
     uint64_t n_text = 0, n_vals = 0;       // symbols; suffix-array entries (n_text + 1)
@@ -213,6 +214,30 @@ __global__ void __launch_bounds__(256) wtsa_ranges_kernel(WtsaView w, const uint
     }
 }
 
+// The text window [wbegin, wend) of every query (begin <= end <= n_text, made so on the host) as ranks of its sub-patterns' lists: an
+// occurrence v of a sub-pattern of m symbols lies wholly inside when begin <= v and v + m <= end, and the list is the sorted
+// SA[sp, sp + len), so those are its elements of rank [count_less(begin), count_less(end - m + 1)).  One lane per sub-pattern of the
+// batch, its query found in qsub; a side of the window that cuts nothing (begin 0, end = the text's) takes no walk.
+__global__ void __launch_bounds__(256) wtsa_window_kernel(WtsaView w, const uint64_t* __restrict__ off, const uint64_t* __restrict__ qsub, uint64_t nq,
+                                                          uint64_t n_pat, const uint64_t* __restrict__ sp, const uint64_t* __restrict__ len,
+                                                          const uint64_t* __restrict__ wbegin, const uint64_t* __restrict__ wend,
+                                                          uint64_t* __restrict__ rlo, uint64_t* __restrict__ rhi)
+{
+    for (uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n_pat; p += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t m = (off[p + 1] - off[p]) / w.sym_bytes, l = sp[p], n = len[p];
+        const uint64_t qj = extract_range_of(qsub, nq, p);
+        const uint64_t b = wbegin[qj], e = wend[qj];
+        uint64_t from = 0, to = n;
+        if (e - b < m) to = 0;                                      // the window is shorter than the sub-pattern
+        else if (n) {
+            if (b) from = wtsa_walk<false>(w, l, n, b);
+            if (e < w.n_text) to = wtsa_walk<false>(w, l, n, e - m + 1);
+        }
+        rlo[p] = from;
+        rhi[p] = to;
+    }
+}
+
 // ---- the lazy search ----------------------------------------------------------------------------------------------------------------
 // Semantics: SURVEY.md Appendix C (what vlg_iterator yields, include/sdsl/vlg_index.hpp:227-291) -- the left-most, lazy,
 // non-overlapping tuples.  One lane owns a query and keeps the reference's k monotone pointers, as RANKS into the sorted
@@ -231,11 +256,21 @@ struct WQuery { uint32_t k, sub0; uint64_t end_len, out_first, out_tuple; };
 // position (the argument of the window filter); what it removes is the query's sequential walk over every
 // fruitless alignment -- 3 k leaps per element of the shortest list, each two 30-level walks -- which is what a heavy query
 // without early matches used to cost (seconds on C3).  kWave false: one lane per query, 64 queries per wavefront.
+//
+// A text window [begin, end) of a query (vlg_wtsa_search_window_batch) cuts every list to the rank interval [rlo, rhi) of its sorted
+// values (wtsa_window_kernel below); the walks still run on the true (sp, len).  Every key a pointer is moved to lies at or behind
+// `begin` -- it is derived from an element under another pointer -- so count_less never answers below rlo: the window is the rank the
+// first pointer starts at, `r >= rhi` for "the list has run out", the pivot chosen and scanned inside [rlo, rhi), and its partner
+// counts clamped to the neighbour's interval.  Without a window rlo = 0 and rhi = len: the machine of before.
+// next[q]: where a search that stopped at max_matches is continued (vlg_result_next_positions), ~0 when the query ran out.
 template <bool kEmit, bool kWave>
 __global__ void __launch_bounds__(64) wtsa_search_kernel(WtsaView w, const uint64_t* __restrict__ sp, const uint64_t* __restrict__ len,
+                                                         const uint64_t* __restrict__ rlo, const uint64_t* __restrict__ rhi,
+                                                         const uint64_t* __restrict__ wend,
                                                          const uint64_t* __restrict__ lo, const uint64_t* __restrict__ hi,
                                                          const WQuery* __restrict__ qs, uint32_t nq, uint32_t kmax, uint64_t max_matches,
-                                                         unsigned long long* __restrict__ counts, uint64_t* __restrict__ out_first,
+                                                         unsigned long long* __restrict__ counts, uint64_t* __restrict__ next,
+                                                         uint64_t* __restrict__ out_first,
                                                          uint64_t* __restrict__ out_tuples, unsigned long long* __restrict__ checksum)
 {
     extern __shared__ uint32_t s_dyn[];                            // [2][kmax][64]: rank and value under every pointer, per lane
@@ -248,32 +283,32 @@ __global__ void __launch_bounds__(64) wtsa_search_kernel(WtsaView w, const uint6
     if (qi < nq) Q = qs[qi];
     const uint32_t k = Q.k;
     bool fin = qi >= nq || k == 0;
-    for (uint32_t i = 0; i < k && !fin; ++i) fin = len[Q.sub0 + i] == 0;     // vlg_index.hpp:315-316: an empty range ends it at once
-    uint32_t piv = 0;                                              // kWave: the shortest list of the query
+    for (uint32_t i = 0; i < k && !fin; ++i) fin = rhi[Q.sub0 + i] <= rlo[Q.sub0 + i];   // vlg_index.hpp:315-316: an empty range ends it at once
+    uint32_t piv = 0;                                              // kWave: the shortest list of the query (inside its window)
     if (kWave && !fin && k >= 2) {
         uint64_t best = ~0ull;
-        for (uint32_t i = 0; i < k; ++i) if (len[Q.sub0 + i] < best) { best = len[Q.sub0 + i]; piv = i; }
+        for (uint32_t i = 0; i < k; ++i) { const uint64_t n_in = rhi[Q.sub0 + i] - rlo[Q.sub0 + i]; if (n_in < best) { best = n_in; piv = i; } }
     }
-    uint64_t emitted = 0;
+    uint64_t emitted = 0, nxt = ~0ull;
     unsigned long long sum = 0;
     // pending walk: level `lv`; op 0 = count_less(key) -> rank, then always the quantile of that rank
     uint32_t lv = 0;
     bool need_count = false;                                       // false: the rank at lv is set, read its value
     uint64_t key = 0;
     uint32_t have = 0;                                             // levels (< 32 tracked; beyond: always recomputed) whose pointer holds a value
-    if (!fin) s_rank[lane] = 0;
+    if (!fin) s_rank[lane] = (uint32_t)rlo[Q.sub0];
     while (__any(!fin)) {
         if (!fin) {
             const uint32_t s = Q.sub0 + lv;
-            const uint64_t li = sp[s], ni = len[s];
+            const uint64_t li = sp[s], ni = len[s], re = rhi[s];
             uint64_t r = s_rank[lv * 64 + lane];
             if (need_count) r = wtsa_walk<false>(w, li, ni, key);         // (every key lies beyond the element under the pointer: it only moves forward)
             if (kWave && k >= 2 && lv == piv) {
                 // (wave-uniform from here to the ballot: every lane holds the same r)  64 elements of the shortest list at a time
-                while (r < ni) {
+                while (r < re) {
                     const uint64_t cand = r + lane;
                     bool ok = false;
-                    if (cand < ni) {
+                    if (cand < re) {
                         const uint64_t v = wtsa_walk<true>(w, li, ni, cand);
                         ok = true;
                         if (piv > 0) {                                      // an element u of the list before with lo <= v - u <= hi
@@ -282,14 +317,19 @@ __global__ void __launch_bounds__(64) wtsa_search_kernel(WtsaView w, const uint6
                             else {
                                 const uint64_t a = v > h_ ? v - h_ : 0, b = v - l_;
                                 const uint64_t lp = sp[s - 1], np = len[s - 1];
-                                ok = wtsa_walk<false>(w, lp, np, b + 1) > wtsa_walk<false>(w, lp, np, a);
+                                const uint64_t from = wtsa_walk<false>(w, lp, np, a), to = wtsa_walk<false>(w, lp, np, b + 1);
+                                ok = (to < rhi[s - 1] ? to : rhi[s - 1]) > (from > rlo[s - 1] ? from : rlo[s - 1]);
                             }
                         }
                         if (ok && piv + 1 < k) {                            // an element x of the list behind with lo' <= x - v <= hi'
                             const uint64_t l_ = lo[s + 1], h_ = hi[s + 1];
                             const uint64_t a = v + l_ < v ? ~0ull : v + l_, b = v + h_ < v ? ~0ull : v + h_;
                             const uint64_t ln = sp[s + 1], nn = len[s + 1];
-                            ok = a != ~0ull && (b == ~0ull ? nn : wtsa_walk<false>(w, ln, nn, b + 1)) > wtsa_walk<false>(w, ln, nn, a);
+                            if (a == ~0ull) ok = false;
+                            else {
+                                const uint64_t from = wtsa_walk<false>(w, ln, nn, a), to = b == ~0ull ? nn : wtsa_walk<false>(w, ln, nn, b + 1);
+                                ok = (to < rhi[s + 1] ? to : rhi[s + 1]) > (from > rlo[s + 1] ? from : rlo[s + 1]);
+                            }
                         }
                     }
                     const unsigned long long m = __ballot(ok);
@@ -297,7 +337,7 @@ __global__ void __launch_bounds__(64) wtsa_search_kernel(WtsaView w, const uint6
                     r += 64;
                 }
             }
-            if (r >= ni) fin = true;                                        // the list has run out: nothing more for this query
+            if (r >= re) fin = true;                                        // the list has run out (inside the window): nothing more for this query
             else {
                 const uint64_t v = wtsa_walk<true>(w, li, ni, r);
                 s_rank[lv * 64 + lane] = (uint32_t)r;
@@ -328,7 +368,12 @@ __global__ void __launch_bounds__(64) wtsa_search_kernel(WtsaView w, const uint6
                             }
                         }
                         ++emitted;
-                        if (max_matches && emitted >= max_matches) { fin = true; break; }
+                        if (max_matches && emitted >= max_matches) {       // stopped, not run out: the next search begins behind this match
+                            const uint64_t we = wend[qi];                   // (never beyond the window's end: begin <= end holds for the next call)
+                            nxt = cur + Q.end_len < we ? cur + Q.end_len : we;
+                            fin = true;
+                            break;
+                        }
                         key = cur + Q.end_len;                              // vlg_index.hpp:254-266 (pull_forward)
                         lv = 0; need_count = true;
                         break;
@@ -345,6 +390,7 @@ __global__ void __launch_bounds__(64) wtsa_search_kernel(WtsaView w, const uint6
         }
     }
     if (qi < nq && writer && counts) counts[qi] = emitted;
+    if (qi < nq && writer && next) next[qi] = nxt;
     if (kEmit && checksum) {
         for (int o = 32; o > 0; o >>= 1) sum += __shfl_down(sum, o);
         if (lane == 0 && sum) atomicAdd(checksum, sum);
@@ -490,6 +536,47 @@ __global__ void __launch_bounds__(256) wtsa_range_walk_kernel(WtsaView w, const 
         out[t] = !ok ? ~0ull : (quantile ? wtsa_walk<true>(w, a, n, x[t]) : (n ? wtsa_walk<false>(w, a, n, x[t]) : 0));
     }
 }
+// wt_int::range_search_2d (wt_int.hpp:612-700) on SA[l, l + len) x [vlb, vrb]: the values inside are the ranks
+// [count_less(vlb), count_less(vrb + 1)) of the sorted range.  ok: the range lies inside the suffix array.
+__device__ __forceinline__ void wtsa_value_ranks(const WtsaView& w, uint64_t a, uint64_t n, uint64_t vlb, uint64_t vrb, bool& ok, uint64_t& from, uint64_t& to)
+{
+    ok = a <= w.n_vals && n <= w.n_vals - a;
+    from = to = 0;
+    if (!ok || !n || vlb > vrb) return;
+    from = wtsa_walk<false>(w, a, n, vlb);
+    to = vrb == ~0ull ? n : wtsa_walk<false>(w, a, n, vrb + 1);     // (a vrb beyond every value: the walk answers n)
+}
+__global__ void __launch_bounds__(256) wtsa_range_count_kernel(WtsaView w, const uint64_t* __restrict__ l, const uint64_t* __restrict__ len,
+                                                               const uint64_t* __restrict__ vlb, const uint64_t* __restrict__ vrb,
+                                                               uint64_t* __restrict__ out, uint64_t count)
+{
+    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < count; t += (uint64_t)gridDim.x * blockDim.x) {
+        bool ok;
+        uint64_t from, to;
+        wtsa_value_ranks(w, l[t], len[t], vlb[t], vrb[t], ok, from, to);
+        out[t] = ok ? to - from : ~0ull;
+    }
+}
+// One lane per reported value: element t of the output belongs to the last range j with out_off[j] <= t (extract_range_of) and is
+// the (count_less(vlb) + t - out_off[j])-th smallest of SA[l, l + len) -- one quantile walk, independent of every other output, and the
+// outputs of a range come out ascending.  Consecutive lanes hold consecutive ranks of one range: their walks share the first levels
+// (the same super-blocks, one read for the wave) and part only where their ranks do.  An element whose range lies outside the
+// suffix array, or whose rank lies beyond the values inside [vlb, vrb] (offsets that are not the prefix sum of the counts), is not written.
+__global__ void __launch_bounds__(256) wtsa_range_report_kernel(WtsaView w, const uint64_t* __restrict__ l, const uint64_t* __restrict__ len,
+                                                                const uint64_t* __restrict__ vlb, const uint64_t* __restrict__ vrb,
+                                                                const uint64_t* __restrict__ out_off, uint64_t count, uint64_t total,
+                                                                uint64_t* __restrict__ out)
+{
+    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t j = extract_range_of(out_off, count, t);
+        if (t < out_off[j]) continue;                               // (offsets that do not start at 0)
+        bool ok;
+        uint64_t from, to;
+        wtsa_value_ranks(w, l[j], len[j], vlb[j], vrb[j], ok, from, to);
+        const uint64_t r = from + (t - out_off[j]);
+        if (ok && r < to) out[t] = wtsa_walk<true>(w, l[j], len[j], r);
+    }
+}
 }  // namespace
 
 extern "C" vlg_status vlg_wtsa_export_level(const vlg_wtsa* x, uint32_t level, uint64_t* h_words)
@@ -512,6 +599,29 @@ extern "C" vlg_status vlg_wtsa_range_walk_batch(const vlg_wtsa* x, const uint64_
     if (!count) return VLG_OK;
     hipLaunchKernelGGL(wtsa_range_walk_kernel, launch_grid(count, 8192), dim3(256), 0, (hipStream_t)stream, wtsa_view(x), d_l, d_len, d_x,
                        quantile, d_out, count);
+    VLG_HIP_TRY(hipGetLastError());
+    return VLG_OK;
+}
+
+extern "C" vlg_status vlg_wtsa_range_count_batch(const vlg_wtsa* x, const uint64_t* d_l, const uint64_t* d_len, const uint64_t* d_vlb,
+                                                 const uint64_t* d_vrb, uint64_t* d_count, uint64_t count, void* stream)
+{
+    if (!x || (count && (!d_l || !d_len || !d_vlb || !d_vrb || !d_count))) return fail(VLG_E_INVALID, "null argument");
+    if (!count) return VLG_OK;
+    hipLaunchKernelGGL(wtsa_range_count_kernel, launch_grid(count, 8192), dim3(256), 0, (hipStream_t)stream, wtsa_view(x), d_l, d_len, d_vlb, d_vrb,
+                       d_count, count);
+    VLG_HIP_TRY(hipGetLastError());
+    return VLG_OK;
+}
+
+extern "C" vlg_status vlg_wtsa_range_report_batch(const vlg_wtsa* x, const uint64_t* d_l, const uint64_t* d_len, const uint64_t* d_vlb,
+                                                  const uint64_t* d_vrb, const uint64_t* d_out_off, uint64_t count, uint64_t total, uint64_t* d_out,
+                                                  void* stream)
+{
+    if (!x || (count && (!d_l || !d_len || !d_vlb || !d_vrb || !d_out_off)) || (total && !d_out)) return fail(VLG_E_INVALID, "null argument");
+    if (!count || !total) return VLG_OK;
+    hipLaunchKernelGGL(wtsa_range_report_kernel, launch_grid(total, 8192), dim3(256), 0, (hipStream_t)stream, wtsa_view(x), d_l, d_len, d_vlb, d_vrb,
+                       d_out_off, count, total, d_out);
     VLG_HIP_TRY(hipGetLastError());
     return VLG_OK;
 }
@@ -541,29 +651,47 @@ extern "C" vlg_status vlg_wtsa_ranges(const vlg_wtsa* x, const vlg_queries* q, u
     return VLG_OK;
 }
 
-extern "C" vlg_status vlg_wtsa_search_batch(const vlg_wtsa* x, const vlg_queries* q, uint64_t max_matches, vlg_workspace* ws, vlg_result** out)
+extern "C" vlg_status vlg_wtsa_search_window_batch(const vlg_wtsa* x, const vlg_queries* q, const uint64_t* h_begin, const uint64_t* h_end,
+                                                   uint64_t max_matches, vlg_workspace* ws, vlg_result** out)
 {
     if (!x || !q || !ws || !out) return fail(VLG_E_INVALID, "null argument");
     *out = nullptr;
     hipStream_t st = ws->stream;
     const uint64_t nq = q->nq, nsub = q->nsub;
     if (nq > 0xFFFFFFF0ull) return fail(VLG_E_UNSUPPORTED, "too many queries in one batch");
+    if (h_begin && h_end)
+        for (uint64_t i = 0; i < nq; ++i) if (h_begin[i] > h_end[i]) return fail(VLG_E_INVALID, "a window begins behind its end");
     vlg_result* res = new_result(nq, q->qsub);
+    res->has_next = true;
+    res->next.assign(nq, ~0ull);
     DevBuf d_mem;
     ResultPiece piece;
     piece.q0 = 0; piece.q1 = nq;
     auto run = [&]() -> vlg_status {
         if (!nq) { res->pieces.push_back(piece); return VLG_OK; }
-        // device scratch: ranges, gap bounds, query table, counts, checksum
-        const uint64_t bytes = (4 * (nsub + 1) + nq + 2) * 8 + (nq + 1) * sizeof(WQuery) + 1024;
+        // device scratch: ranges, their cut to the windows, gap bounds, windows, next positions, query table, counts, checksum
+        const uint64_t bytes = (6 * (nsub + 1) + 4 * nq + 2) * 8 + (nq + 1) * sizeof(WQuery) + 1024;
         VLG_HIP_TRY(d_mem.alloc(bytes));
         uint64_t* d_sp = d_mem.as<uint64_t>();
         uint64_t* d_len = d_sp + nsub + 1;
-        uint64_t* d_lo = d_len + nsub + 1;
+        uint64_t* d_rlo = d_len + nsub + 1;
+        uint64_t* d_rhi = d_rlo + nsub + 1;
+        uint64_t* d_lo = d_rhi + nsub + 1;
         uint64_t* d_hi = d_lo + nsub + 1;
-        unsigned long long* d_counts = (unsigned long long*)(d_hi + nsub + 1);
+        uint64_t* d_wb = d_hi + nsub + 1;
+        uint64_t* d_we = d_wb + nq;
+        uint64_t* d_next = d_we + nq;
+        unsigned long long* d_counts = (unsigned long long*)(d_next + nq);
         unsigned long long* d_chk = d_counts + nq;
         WQuery* d_q = (WQuery*)(d_chk + 2);
+        // the windows: end clamped to the text, begin to the end (a window behind the text is an empty one)
+        svec<uint64_t> hwb(nq), hwe(nq), hnext(nq);
+        for (uint64_t i = 0; i < nq; ++i) {
+            hwe[i] = h_end ? std::min<uint64_t>(h_end[i], x->n_text) : x->n_text;
+            hwb[i] = h_begin ? std::min<uint64_t>(h_begin[i], hwe[i]) : 0;
+        }
+        VLG_HIP_TRY(hipMemcpyAsync(d_wb, hwb.data(), nq * 8, hipMemcpyHostToDevice, st));
+        VLG_HIP_TRY(hipMemcpyAsync(d_we, hwe.data(), nq * 8, hipMemcpyHostToDevice, st));
         svec<WQuery> hq(nq);
         for (uint64_t i = 0; i < nq; ++i) hq[i] = WQuery{res->k[i], (uint32_t)q->qsub[i], q->end_len[i], 0, 0};
         svec<uint64_t> hlo(q->lo.begin(), q->lo.end()), hhi(q->hi.begin(), q->hi.end());
@@ -576,6 +704,11 @@ extern "C" vlg_status vlg_wtsa_search_batch(const vlg_wtsa* x, const vlg_queries
         {
             Timed t(ws, KS_BSEARCH, 0);
             if (vlg_status s = wtsa_ranges_device(x, q, d_sp, d_len, st)) return s;
+            if (nsub) {
+                hipLaunchKernelGGL(wtsa_window_kernel, launch_grid(nsub, 4096), dim3(256), 0, st, wtsa_view(x), q->d_suboff, q->d_qsub, nq, nsub, d_sp,
+                                   d_len, d_wb, d_we, d_rlo, d_rhi);
+                VLG_HIP_TRY(hipGetLastError());
+            }
         }
         const uint32_t kmax = std::max<uint32_t>(q->kmax, 1);
         const size_t lds = (size_t)2 * kmax * 64 * 4;
@@ -596,15 +729,17 @@ extern "C" vlg_status vlg_wtsa_search_batch(const vlg_wtsa* x, const vlg_queries
             VLG_HIP_TRY(hipMemcpyAsync(d_q, hq.data(), nq * sizeof(WQuery), hipMemcpyHostToDevice, st));
             {
                 Timed t(ws, KS_JOIN_CHAIN, 0);
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(wtsa_search_kernel<true, true>), dim3(wgs), dim3(64), lds, st, w, d_sp, d_len, d_lo, d_hi, d_q,
-                                   (uint32_t)nq, kmax, max_matches, d_counts, t_first, t_tuples, d_chk);
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(wtsa_search_kernel<true, true>), dim3(wgs), dim3(64), lds, st, w, d_sp, d_len, d_rlo, d_rhi, d_we, d_lo,
+                                   d_hi, d_q, (uint32_t)nq, kmax, max_matches, d_counts, d_next, t_first, t_tuples, d_chk);
             }
             VLG_HIP_TRY(hipGetLastError());
             svec<unsigned long long> counts(nq);
             unsigned long long chk = 0;
             VLG_HIP_TRY(hipMemcpyAsync(counts.data(), d_counts, nq * 8, hipMemcpyDeviceToHost, st));
+            VLG_HIP_TRY(hipMemcpyAsync(hnext.data(), d_next, nq * 8, hipMemcpyDeviceToHost, st));
             VLG_HIP_TRY(hipMemcpyAsync(&chk, d_chk, 8, hipMemcpyDeviceToHost, st));
             VLG_HIP_TRY(hipStreamSynchronize(st));
+            std::copy(hnext.begin(), hnext.end(), res->next.begin());
             svec<uint64_t> to_first(nq + 1), to_tuple(nq + 1);
             uint64_t M = 0, TV = 0;
             for (uint64_t i = 0; i < nq; ++i) {
@@ -635,16 +770,18 @@ extern "C" vlg_status vlg_wtsa_search_batch(const vlg_wtsa* x, const vlg_queries
         {
             Timed t(ws, KS_JOIN_CHAIN, 0);
             if (wave)
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(wtsa_search_kernel<false, true>), dim3(wgs), dim3(64), lds, st, w, d_sp, d_len, d_lo, d_hi, d_q,
-                                   (uint32_t)nq, kmax, max_matches, d_counts, nullptr, nullptr, nullptr);
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(wtsa_search_kernel<false, true>), dim3(wgs), dim3(64), lds, st, w, d_sp, d_len, d_rlo, d_rhi, d_we, d_lo,
+                                   d_hi, d_q, (uint32_t)nq, kmax, max_matches, d_counts, d_next, nullptr, nullptr, nullptr);
             else
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(wtsa_search_kernel<false, false>), dim3(wgs), dim3(64), lds, st, w, d_sp, d_len, d_lo, d_hi, d_q,
-                                   (uint32_t)nq, kmax, max_matches, d_counts, nullptr, nullptr, nullptr);
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(wtsa_search_kernel<false, false>), dim3(wgs), dim3(64), lds, st, w, d_sp, d_len, d_rlo, d_rhi, d_we, d_lo,
+                                   d_hi, d_q, (uint32_t)nq, kmax, max_matches, d_counts, d_next, nullptr, nullptr, nullptr);
         }
         VLG_HIP_TRY(hipGetLastError());
         svec<unsigned long long> counts(nq);
         VLG_HIP_TRY(hipMemcpyAsync(counts.data(), d_counts, nq * 8, hipMemcpyDeviceToHost, st));
+        VLG_HIP_TRY(hipMemcpyAsync(hnext.data(), d_next, nq * 8, hipMemcpyDeviceToHost, st));
         VLG_HIP_TRY(hipStreamSynchronize(st));
+        std::copy(hnext.begin(), hnext.end(), res->next.begin());
         uint64_t M = 0, TV = 0;
         for (uint64_t i = 0; i < nq; ++i) {
             hq[i].out_first = M; hq[i].out_tuple = TV;
@@ -658,11 +795,13 @@ extern "C" vlg_status vlg_wtsa_search_batch(const vlg_wtsa* x, const vlg_queries
             VLG_HIP_TRY(hipMemcpyAsync(d_q, hq.data(), nq * sizeof(WQuery), hipMemcpyHostToDevice, st));
             Timed t(ws, KS_GATHER, 8ull * (M + TV));
             if (wave)
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(wtsa_search_kernel<true, true>), dim3(wgs), dim3(64), lds, st, w, d_sp, d_len, d_lo, d_hi, d_q,
-                                   (uint32_t)nq, kmax, max_matches, d_counts, static_cast<uint64_t*>(piece.d_first), static_cast<uint64_t*>(piece.d_tuples), d_chk);
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(wtsa_search_kernel<true, true>), dim3(wgs), dim3(64), lds, st, w, d_sp, d_len, d_rlo, d_rhi, d_we, d_lo,
+                                   d_hi, d_q, (uint32_t)nq, kmax, max_matches, d_counts, nullptr, static_cast<uint64_t*>(piece.d_first),
+                                   static_cast<uint64_t*>(piece.d_tuples), d_chk);
             else
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(wtsa_search_kernel<true, false>), dim3(wgs), dim3(64), lds, st, w, d_sp, d_len, d_lo, d_hi, d_q,
-                                   (uint32_t)nq, kmax, max_matches, d_counts, static_cast<uint64_t*>(piece.d_first), static_cast<uint64_t*>(piece.d_tuples), d_chk);
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(wtsa_search_kernel<true, false>), dim3(wgs), dim3(64), lds, st, w, d_sp, d_len, d_rlo, d_rhi, d_we, d_lo,
+                                   d_hi, d_q, (uint32_t)nq, kmax, max_matches, d_counts, nullptr, static_cast<uint64_t*>(piece.d_first),
+                                   static_cast<uint64_t*>(piece.d_tuples), d_chk);
             VLG_HIP_TRY(hipGetLastError());
         }
         unsigned long long chk = 0;
@@ -685,5 +824,18 @@ extern "C" vlg_status vlg_wtsa_search_batch(const vlg_wtsa* x, const vlg_queries
                if (piece.d_tuples && res->pieces.empty()) result_cache().give(piece.d_tuples, piece.tuple_bytes);
                vlg_result_destroy(res); return stt; }
     *out = res;
+    return VLG_OK;
+}
+
+extern "C" vlg_status vlg_wtsa_search_batch(const vlg_wtsa* x, const vlg_queries* q, uint64_t max_matches, vlg_workspace* ws, vlg_result** out)
+{
+    return vlg_wtsa_search_window_batch(x, q, nullptr, nullptr, max_matches, ws, out);
+}
+
+extern "C" vlg_status vlg_result_next_positions(const vlg_result* r, uint64_t* h_next)
+{
+    if (!r || (!h_next && !r->next.empty())) return fail(VLG_E_INVALID, "null argument");
+    if (!r->has_next) return fail(VLG_E_INVALID, "next positions exist for the results of vlg_wtsa_* searches only");
+    std::copy(r->next.begin(), r->next.end(), h_next);
     return VLG_OK;
 }

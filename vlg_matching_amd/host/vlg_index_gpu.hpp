@@ -5,8 +5,10 @@
 //   count(idx, query)                    :403-411
 //   store_to_file / load_from_file       the file of vlg_index<alphabet_tag, wt_int<bit_vector_il<>, rank_support_il<>>>
 //                                        (serialize / load :181-198; vlg_wtsa_save_sdsl / vlg_wtsa_load_sdsl)
-// The iterator is lazy like the reference's: it asks the device for the first matches only and, when the caller walks past them,
-// for four times as many (vlg_wtsa_search_batch's max_matches_per_query) -- a caller that stops early never pays for the rest.
+// The iterator is lazy like the reference's: it asks the device for the first 16 matches only and, when the caller walks past them,
+// for three times what it holds FROM WHERE THAT SEARCH STOPPED (vlg_wtsa_search_window_batch's begin, vlg_result_next_positions) -- it
+// continues like pull_forward (:254-266), keeps the tuples it has, and a caller that stops early never pays for the rest.
+// locate(idx, query, begin, end) answers on the text window [begin, end): the matches of the query on text[begin, end), shifted.
 #pragma once
 #include <memory>
 #include <string>
@@ -63,8 +65,12 @@ class vlg_index_gpu
         return i.n - 1;
     }
 
-    // the first `cap` matches (0 = all) of one query: tuples, k values per match
-    void fetch(const std::string& query, uint64_t cap, std::vector<uint64_t>& tuples, uint32_t& k, uint64_t& matches) const
+    static const uint64_t npos = ~0ull;    // no position to continue at: the query ran out of matches
+
+    // the first `cap` matches (0 = all) of one query inside the text window [begin, end): tuples, k values per match; next: where
+    // a search that stopped at `cap` is continued (npos: it ran out)
+    void fetch(const std::string& query, uint64_t cap, std::vector<uint64_t>& tuples, uint32_t& k, uint64_t& matches, uint64_t begin = 0,
+               uint64_t end = npos, uint64_t* next = nullptr) const
     {
         if (!m_h) throw std::runtime_error("vlg_index_gpu: not constructed");
         uint64_t off[2] = {0, query.size()};
@@ -74,13 +80,14 @@ class vlg_index_gpu
         vlg_status st = vlg_queries_k(q, &k);
         vlg_result* r = nullptr;
         if (!st) st = vlg_workspace_set_option(m_h->ws, "tuples", 1);
-        if (!st) st = vlg_wtsa_search_batch(m_h->idx, q, cap, m_h->ws, &r);
+        if (!st) st = vlg_wtsa_search_window_batch(m_h->idx, q, &begin, &end, cap, m_h->ws, &r);
         vlg_queries_destroy(q);
         check(st);
         vlg_result_summary s;
         st = vlg_result_summary_get(r, &s);
         tuples.assign(st ? 1 : s.n_tuple_values + 1, 0);
         if (!st) st = vlg_result_fetch(r, nullptr, nullptr, nullptr, tuples.data());
+        if (!st && next) st = vlg_result_next_positions(r, next);
         vlg_result_destroy(r);
         check(st);
         matches = s.n_matches;
@@ -96,20 +103,25 @@ class vlg_iterator_gpu
     std::string m_query;
     std::vector<uint64_t> m_tuples;
     uint32_t m_k = 0;
-    uint64_t m_have = 0, m_cap = 0, m_at = 0;
+    uint64_t m_have = 0, m_at = 0;
+    uint64_t m_next = 0, m_stop = type_index::npos;           // where the next request begins; the end of the text window
     bool m_all = true, m_end = true;
 
-    void refill(uint64_t cap)
+    void refill(uint64_t cap)                                  // the next `cap` matches, behind the ones already held
     {
-        m_cap = cap;
-        m_idx->fetch(m_query, cap, m_tuples, m_k, m_have);
-        m_all = m_have < cap;                                  // fewer than asked for: that was everything
+        std::vector<uint64_t> more;
+        uint64_t got = 0;
+        m_idx->fetch(m_query, cap, more, m_k, got, m_next, m_stop, &m_next);
+        m_tuples.insert(m_tuples.end(), more.begin(), more.end());
+        m_have += got;
+        m_all = m_next == type_index::npos;                    // the search ran out instead of stopping at the cap
     }
 
   public:
     typedef uint64_t position_type;
     vlg_iterator_gpu() = default;
-    vlg_iterator_gpu(const type_index& idx, const std::string& query) : m_idx(&idx), m_query(query), m_end(false)
+    vlg_iterator_gpu(const type_index& idx, const std::string& query, uint64_t begin = 0, uint64_t end = type_index::npos)
+        : m_idx(&idx), m_query(query), m_next(begin), m_stop(end), m_end(false)
     {
         refill(16);
         m_end = m_have == 0;
@@ -124,7 +136,7 @@ class vlg_iterator_gpu
         ++m_at;
         if (m_at >= m_have) {
             if (m_all) m_end = true;
-            else { refill(m_cap * 4); m_end = m_at >= m_have; }   // the matches come in the same order: the first m_at are the ones already seen
+            else { refill(m_have * 3); m_end = m_at >= m_have; }  // the following matches, four times as many held afterwards: the search goes on where the last one stopped
         }
         return *this;
     }
@@ -179,6 +191,12 @@ template <typename type_index>
 container<vlg_iterator_gpu<type_index>> locate(const type_index& idx, const typename type_index::query_type& query)
 {
     return container<vlg_iterator_gpu<type_index>>(vlg_iterator_gpu<type_index>(idx, query), vlg_iterator_gpu<type_index>());
+}
+// the matches inside the text window [begin, end) (end beyond the text: to its end; begin > end: std::runtime_error)
+template <typename type_index>
+container<vlg_iterator_gpu<type_index>> locate(const type_index& idx, const typename type_index::query_type& query, uint64_t begin, uint64_t end)
+{
+    return container<vlg_iterator_gpu<type_index>>(vlg_iterator_gpu<type_index>(idx, query, begin, end), vlg_iterator_gpu<type_index>());
 }
 template <typename type_index>
 typename type_index::size_type count(const type_index& idx, const typename type_index::query_type& query)

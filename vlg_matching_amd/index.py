@@ -23,6 +23,9 @@ def _u8(a):
     return np.ascontiguousarray(a, dtype=np.uint8)
 
 
+NO_NEXT = (1 << 64) - 1           # SearchResult.next_positions(): the query ran out of matches
+
+
 class SearchResult:
     """Per-query match counts, first positions (gapped_search_result::positions) and full tuples."""
 
@@ -76,6 +79,15 @@ class SearchResult:
         tuples = np.zeros(max(self.summary["n_tuple_values"], 1), dtype=np.uint32)
         self.fetch32_into(first.ctypes.data, tuples.ctypes.data if self.summary["n_tuple_values"] else None)
         return first[: self.summary["n_matches"]], tuples[: self.summary["n_tuple_values"]]
+
+    def next_positions(self):
+        """vlg_result_next_positions: per query, where the next search has to begin to continue this one (a WtsaIndex.search that
+        stopped at max_matches), NO_NEXT (2^64 - 1) when the query ran out of matches inside its window.  VlgError for the result
+        of any other search."""
+        nq = self.summary["n_queries"]
+        nxt = np.zeros(max(nq, 1), dtype=np.uint64)
+        check(lib().vlg_result_next_positions(self._h, nxt.ctypes.data))
+        return nxt[:nq]
 
     @property
     def counts(self):
@@ -948,16 +960,100 @@ class WtsaIndex:
         check(lib().vlg_wtsa_ranges(self._h, q._h, sp.ctypes.data, ep.ctypes.data, None))
         return sp[:nsub], ep[:nsub]
 
-    def search(self, queries, max_matches=0, workspace=None):
-        """sdsl::locate(idx, query) for a batch, lazily: at most max_matches matches per query (0 = all)."""
+    def _window(self, v, nq, name):
+        """begin / end of search(): None, a scalar for every query, or one value per query -> uint64 array or None"""
+        if v is None:
+            return None
+        if np.ndim(v) == 0:
+            a = np.full(nq, int(v), dtype=np.uint64)
+        elif isinstance(v, np.ndarray):
+            a = _u64_index_array(v, name)
+        else:
+            a = np.array([int(x) for x in v], dtype=np.uint64)
+        if len(a) != nq:
+            raise ValueError("%s: one value per query expected (%d), got %d" % (name, nq, len(a)))
+        return a
+
+    def search(self, queries, max_matches=0, workspace=None, begin=None, end=None):
+        """sdsl::locate(idx, query) for a batch, lazily: at most max_matches matches per query (0 = all).  begin / end: the text window
+        [begin, end) every query is answered on (a scalar for the whole batch or one value per query; None: from 0 / to the end of
+        the text) -- its matches are those of the query on text[begin:end], shifted by begin."""
         q = self.queries(queries)
         if workspace is None:
             if self._ws is None:
                 self._ws = Workspace()
             workspace = self._ws
+        b, e = self._window(begin, q.n, "begin"), self._window(end, q.n, "end")
         h = C.c_void_p()
-        check(lib().vlg_wtsa_search_batch(self._h, q._h, int(max_matches), workspace._h, C.byref(h)))
+        check(lib().vlg_wtsa_search_window_batch(self._h, q._h, b.ctypes.data if b is not None and len(b) else None,
+                                                 e.ctypes.data if e is not None and len(e) else None, int(max_matches), workspace._h, C.byref(h)))
         return SearchResult(h, q.ks)
+
+    def pages(self, query, page=16, begin=0, end=None):
+        """The matches of one query inside [begin, end), `page` at a time: a generator of tuple arrays [matches, k].  Every page is one
+        capped search that begins where the one before stopped (SearchResult.next_positions) -- like the reference's iterator it
+        continues (pull_forward, vlg_index.hpp:254-266) and never walks a prefix twice."""
+        if int(page) < 1:
+            raise ValueError("page must be at least 1")
+        q = self.queries([query])
+        at = int(begin)
+        while at != NO_NEXT:
+            r = self.search(q, max_matches=int(page), begin=at, end=end)
+            t = r.tuples(0)
+            if len(t):
+                yield t
+            at = int(r.next_positions()[0])
+
+    def range_count_device(self, d_l_ptr, d_len_ptr, d_vlb_ptr, d_vrb_ptr, d_count_ptr, count, stream=None):
+        """wt_int::range_search_2d's count: how many of SA[l, l + len) lie in [vlb, vrb], device pointers"""
+        check(lib().vlg_wtsa_range_count_batch(self._h, d_l_ptr, d_len_ptr, d_vlb_ptr, d_vrb_ptr, d_count_ptr, count, stream))
+
+    def range_report_device(self, d_l_ptr, d_len_ptr, d_vlb_ptr, d_vrb_ptr, d_out_off_ptr, count, total, d_out_ptr, stream=None):
+        """those values, ascending, range j from d_out[d_out_off[j]] on (d_out_off: exclusive prefix sum of the counts, count + 1 entries)"""
+        check(lib().vlg_wtsa_range_report_batch(self._h, d_l_ptr, d_len_ptr, d_vlb_ptr, d_vrb_ptr, d_out_off_ptr, count, total, d_out_ptr, stream))
+
+    def range_report(self, l, length, vlb, vrb):
+        """Host convenience over the pair: suffix-array ranges [l, l + length) and value windows [vlb, vrb] (arrays of equal length) ->
+        (counts, offsets, values): range j's values, ascending, are values[offsets[j]:offsets[j + 1]].  A range outside the suffix
+        array raises ValueError."""
+        import torch
+        a = [_u64_index_array(x, n) for x, n in ((l, "l"), (length, "length"), (vlb, "vlb"), (vrb, "vrb"))]
+        m = len(a[0])
+        if any(len(x) != m for x in a):
+            raise ValueError("l, length, vlb and vrb must be equally long")
+        if not m:
+            return np.zeros(0, np.uint64), np.zeros(1, np.uint64), np.zeros(0, np.uint64)
+        d = [torch.from_numpy(x.view(np.int64)).cuda() for x in a]
+        d_cnt = torch.empty_like(d[0])
+        self.range_count_device(d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), d[3].data_ptr(), d_cnt.data_ptr(), m)
+        counts = d_cnt.cpu().numpy().view(np.uint64)
+        if (counts == np.uint64((1 << 64) - 1)).any():
+            raise ValueError("a range lies outside the suffix array")
+        off = np.zeros(m + 1, dtype=np.uint64)
+        off[1:] = np.cumsum(counts)
+        total = int(off[m])
+        d_off = torch.from_numpy(off.view(np.int64)).cuda()
+        d_out = torch.zeros(max(total, 1), dtype=torch.int64, device="cuda")
+        self.range_report_device(d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), d[3].data_ptr(), d_off.data_ptr(), m, total, d_out.data_ptr())
+        return counts, off, d_out.cpu().numpy().view(np.uint64)[:total]
+
+    def locate_window(self, pattern, begin=0, end=None):
+        """The occurrences of one pattern (bytes; integer index: an array of symbols) that lie wholly inside the text window
+        [begin, end), ascending: forward search, then the values of its suffix-array range inside [begin, end - |pattern|]."""
+        n_text = self.info()["n"] - 1
+        if self.symbol_bytes == 1:
+            pat = bytes(pattern)
+            q = Queries.from_arrays([[pat]], [[]], [[]], [1]) if len(pat) else None
+        else:
+            pat = np.asarray(pattern)
+            q = self.queries([" ".join(str(int(x)) for x in pat)]) if len(pat) else None
+        b, e = int(begin), n_text if end is None else min(int(end), n_text)
+        if b < 0 or (end is not None and int(end) < b):
+            raise ValueError("locate_window: 0 <= begin <= end expected")
+        if q is None or e - b < len(pat):
+            return np.zeros(0, np.uint64)
+        sp, ep = self.ranges(q)
+        return self.range_report([int(sp[0])], [int(ep[0]) + 1 - int(sp[0])], [b], [e - len(pat)])[2]
 
 
 def join_batch(d_lists_ptr, list_off, join_list, lo, hi, end_len, workspace, ks=None):
