@@ -509,6 +509,12 @@ typedef struct {
     uint64_t join_slots;          /* list elements the join passes evaluated: the non-final lists of every live
                                      query, after the window filter                               */
     uint64_t locate_mode;         /* how the last super-chunk's occurrences were located: VLG_LOCATE_*  */
+    uint64_t filter_stream_segments; /* lists the window filter compacted, by how their survivors were kept: activity bits   */
+    uint64_t filter_bit_segments;    /* of streamed queries, activity bits of pivot-filtered queries, index ranges of       */
+    uint64_t filter_range_segments;  /* pivot-filtered queries ("pivot_range_ratio")                                          */
+    uint64_t filter_survivors;       /* elements the joins read of those lists (the same however the joins were cut into chunks) */
+    uint64_t filter_overflows;       /* groups of filtered queries whose survivors did not fit the room behind the lists at once:
+                                        their join chunks compacted their own lists                                            */
 } vlg_result_summary;
 /* csa[i] = iterated LF to a sampled index (csa_wt.hpp:335-348), organised per batch as
  *   WALKS     one walk per occurrence (few occurrences; integer alphabets; workspace option "sweep" = 0)
@@ -697,6 +703,10 @@ vlg_status vlg_workspace_profile(vlg_workspace* ws, int enable);
  * ("filter_stream_min", default 2^16, for the queries filtered by streaming sweeps);
  * "filter_pivot" (default 1): filter outwards from the shortest list of a query when it is >= 6x shorter than all of
  * them together ("filter_pivot_ratio", default 6), otherwise (or with 0) by streaming sweeps over block bitmaps;
+ * "pivot_range_ratio" (default 16): a query filtered from its shortest list keeps, for the lists it marks, the index ranges of the
+ * windows (8 bytes per element of the shortest list and marked list) instead of a bit per list element when the marked lists
+ * together are at least this many times longer than that; 0 = always bits.  Below 64 the ranges are the larger state (by up to
+ * 68 / ratio), which counts against "filter_group_bytes": ratios below 8 are meant for tests;
  * "filter_group_bytes" (default 0 = a third of the join scratch) caps the filter state of the queries filtered together.
  * "reserve" = bytes of scratch to allocate right away (at most the workspace's cap) instead of on first use.
  * "tuples" (default 1): materialise every sub-pattern position of every match (what sdsl::locate returns); 0 = first

@@ -47,7 +47,9 @@ class IndexInfo(C.Structure):
 class ResultSummary(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("n_queries", "n_matches", "checksum", "n_tuple_values", "located_occurrences",
                                            "lf_steps", "wt_levels_locate", "wt_levels_bsearch", "n_chunks",
-                                           "logical_occurrences", "join_slots", "locate_mode")]
+                                           "logical_occurrences", "join_slots", "locate_mode", "filter_stream_segments",
+                                           "filter_bit_segments", "filter_range_segments", "filter_survivors",
+                                           "filter_overflows")]
 
 
 class ParsedQuery(C.Structure):

@@ -20,10 +20,11 @@ struct RSeg {                 // one per sub-pattern of a filtered query
     uint32_t pbegin, pend;    // physical list
     uint64_t lo, hi;          // gap bounds to the previous sub-pattern (level > 0)
     uint64_t nlo, nhi;        // gap bounds to the next sub-pattern (dist > 0)
-    uint64_t abit;            // first activity bit of the segment (64-aligned); the last sub-pattern has none (~0)
+    uint64_t abit;            // first activity bit of the segment (64-aligned); the last sub-pattern has none (~0).
+                              // Range-kind segment (rng): its first group in the range arrays instead
     uint32_t fq;              // filtered-query ordinal: selects the query's pair of block bitmaps
     uint32_t level, dist;
-    uint32_t pad;
+    uint32_t rng;             // 1: the pivot filter keeps index ranges for this segment, no activity bits
 };
 
 struct RPass {
@@ -493,6 +494,14 @@ __device__ __forceinline__ void pivot_ranges_rungs(const pos_t* __restrict__ P, 
 // window form an index range, which is marked in that list's activity bits; the hull of the range's positions is the
 // "element" followed to the next level (a superset of what the exact windows would mark, which is all the filter needs).
 struct PTask { uint32_t seg0, k, p, pad; };          // first segment of the query, sub-patterns, pivot level
+// Range-kind segments: what the pivot kernel writes per (pivot element, level) and per group of 64 pivot elements.  The arrays are
+// laid out [task][marked level, ascending][pivot element], every level padded to whole groups: the order of the compaction.
+struct PivotRanges {
+    uint2* ranges;           // [64 x groups] {i0, i1} of the element's window in the level's list; {0, 0}: none
+    uint64_t* key;           // [groups] segment << 32 | largest i1 of the group: a running maximum over it restarts at every segment
+    uint2* first;            // [groups] range of the group's first on-element
+    uint32_t* inner;         // [groups] elements the later on-elements of the group add to it
+};
 constexpr uint32_t kPivotRun = 64 * kPivotGroups;     // pivot elements per wave and turn
 #ifndef VLG_PIVOT_TURNS
 #define VLG_PIVOT_TURNS 1
@@ -501,12 +510,14 @@ static_assert(VLG_PIVOT_TURNS >= 1, "VLG_PIVOT_TURNS: at least one run per wave"
 constexpr uint32_t kPivotTurns = VLG_PIVOT_TURNS;     // runs a wave takes one after the other (round 4, C3: 1 -> 21.9 ms, 4 -> 24.1 ms: the task
                                                       // look-up in front of a run is not what the kernel waits for; more, shorter waves win)
 
-template <typename pos_t, bool kRungs>
+// kRanges: the launch for the queries that keep ranges (all marked levels of a query are of one kind; a launch per kind, so that
+// neither carries the other's registers).
+template <typename pos_t, bool kRungs, bool kRanges>
 __global__ void __launch_bounds__(256) filter_pivot_kernel(const pos_t* __restrict__ P, const pos_t* __restrict__ F /* fences of P, or null */,
                                                            const pos_t* __restrict__ R, const uint64_t* __restrict__ roff /* kRungs: the ladder over P */,
                                                            const RSeg* __restrict__ segs,
                                                            const PTask* __restrict__ tasks, const uint64_t* __restrict__ task_run0,
-                                                           uint32_t ntasks, uint64_t* __restrict__ abits)
+                                                           uint32_t ntasks, uint64_t* __restrict__ abits, PivotRanges pr)
 {
     constexpr uint32_t G = kPivotGroups;
     const uint32_t lane = threadIdx.x & 63;
@@ -536,22 +547,44 @@ __global__ void __launch_bounds__(256) filter_pivot_kernel(const pos_t* __restri
         const uint64_t i = off0 + 64 * g + lane;
         on0[g] = i < off1;
         x[g] = on0[g] ? (uint64_t)P[pv.pbegin + i] : 0;
-        if (pv.abit != ~0ull && off0 + 64 * g < off1) {                       // every element of the pivot list stays
-            const unsigned long long m = __ballot(on0[g]);
-            if (lane == 0) abits[(pv.abit + off0 + 64 * g) >> 6] = m;
-        }
     }
-    // the marks of one level ascend over the groups: one MarkRun per level collects them
-    auto follow = [&](const RSeg& sg, const uint64_t (&a)[G], const uint64_t (&b)[G], bool (&on)[G], uint64_t (&lo_pos)[G], uint64_t (&hi_pos)[G],
-                      bool more_levels) {
+    // the marks of one level ascend over the groups: one MarkRun per level collects them, or (range-kind segment) the ranges are
+    // stored as they are, with one summary per group of 64 pivot elements for the survivor counts
+    auto follow = [&](uint32_t seg, const RSeg& sg, const uint64_t (&a)[G], const uint64_t (&b)[G], bool (&on)[G], uint64_t (&lo_pos)[G],
+                      uint64_t (&hi_pos)[G], bool more_levels) {
         uint32_t i0[G], i1[G];
         if (kRungs) pivot_ranges_rungs(P, R, roff, sg.pbegin, sg.pend, a, b, on, i0, i1);
         else pivot_ranges(P, F, sg.pbegin, sg.pend, a, b, on, i0, i1);
-        MarkRun mr;
-        mr.bm = abits + (sg.abit >> 6);
+        if constexpr (kRanges) {
 #pragma unroll
-        for (uint32_t g = 0; g < G; ++g) mr.add(i0[g], i1[g] - 1, on[g]);
-        mr.flush();
+            for (uint32_t g = 0; g < G; ++g) {
+                if (off0 + 64 * g >= off1) continue;                             // (wave-uniform) no such group in the pivot list
+                const uint64_t rr = sg.abit + (off0 >> 6) + g;
+                // What the count, the carry scan and the expansion rest on: an on-element has i0 < i1 (the descents clear `on` for an
+                // empty window), an off one stores {0, 0}, and i0 and i1 ascend over the on-elements of a (query, level).
+                const uint32_t a0 = on[g] ? i0[g] : 0, a1 = on[g] ? i1[g] : 0;
+                pr.ranges[rr * 64 + lane] = make_uint2(a0, a1);                  // (the array is padded to whole groups)
+                const unsigned long long m = __ballot(on[g]);
+                const unsigned long long below = m & ((1ull << lane) - 1ull);
+                const uint32_t e_prev = __shfl(a1, below ? 63 - __clzll((long long)below) : 0);
+                const uint32_t from = a0 > e_prev ? a0 : e_prev;
+                uint32_t inner = on[g] && below && a1 > from ? a1 - from : 0;    // what every on-element but the first adds
+                for (int o = 32; o > 0; o >>= 1) inner += __shfl_xor(inner, o);
+                const int first = m ? __ffsll((long long)m) - 1 : 0;
+                const uint32_t f0 = __shfl(a0, first), f1 = __shfl(a1, first), top = wave_max_u32(a1);
+                if (lane == 0) {
+                    pr.key[rr] = ((uint64_t)seg << 32) | top;
+                    pr.first[rr] = make_uint2(f0, f1);
+                    pr.inner[rr] = inner;
+                }
+            }
+        } else {
+            MarkRun mr;
+            mr.bm = abits + (sg.abit >> 6);
+#pragma unroll
+            for (uint32_t g = 0; g < G; ++g) mr.add(i0[g], i1[g] - 1, on[g]);
+            mr.flush();
+        }
         if (more_levels) {
 #pragma unroll
             for (uint32_t g = 0; g < G; ++g) if (on[g]) { lo_pos[g] = P[sg.pbegin + i0[g]]; hi_pos[g] = P[sg.pbegin + i1[g] - 1]; }
@@ -574,7 +607,7 @@ __global__ void __launch_bounds__(256) filter_pivot_kernel(const pos_t* __restri
                     else { a[g] = lo_pos[g] > up.hi ? lo_pos[g] - up.hi : 0; b[g] = hi_pos[g] - up.lo; }
                 }
             }
-            follow(sg, a, b, on, lo_pos, hi_pos, l > 0);
+            follow(tk.seg0 + (uint32_t)l, sg, a, b, on, lo_pos, hi_pos, l > 0);
         }
     }
     // towards the last sub-pattern (which keeps no join state itself)
@@ -592,18 +625,34 @@ __global__ void __launch_bounds__(256) filter_pivot_kernel(const pos_t* __restri
                 b[g] = sat_add(hi_pos[g], sg.hi);
                 if (b[g] == ~0ull) b[g] = ~0ull - 1;                             // (b + 1 is searched)
             }
-            follow(sg, a, b, on, lo_pos, hi_pos, l + 2 < tk.k);
+            follow(tk.seg0 + l, sg, a, b, on, lo_pos, hi_pos, l + 2 < tk.k);
         }
     }
     }
 }
+
+// Runs of one kind, numbered among themselves (bit-kind: run b owns the activity words [32 b, 32 b + 32); range-kind: group rr of the
+// range arrays) -> the run's place among all runs of the group, which is where its count goes.  cseg == nullptr: every run is of
+// this kind and the two numberings agree.
+struct KindRuns {
+    const uint32_t* cseg;    // [n] compacted segment of the kind's t-th segment
+    const uint64_t* run0;    // [n + 1] its first run, in the kind's numbering
+    const uint64_t* crun0;   // first run of every compacted segment
+    uint32_t n;
+    __device__ __forceinline__ uint64_t run(uint64_t b) const
+    {
+        if (!cseg) return b;
+        const uint32_t t = task_find(run0, n, b);
+        return crun0[cseg[t]] + (b - run0[t]);
+    }
+};
 
 // survivors per run (for the compaction offsets): the activity bits of a filtered list start on a run boundary, so run r of
 // the group owns the words [32 r, 32 r + 32).  Sixteen lanes per run (16 bytes each), sixteen runs per wave with their four
 // loads per lane in flight together.
 constexpr uint32_t kCountRunsPerWave = 16;
 __global__ void __launch_bounds__(256) filter_count_runs_kernel(const uint64_t* __restrict__ abits, uint64_t total_runs,
-                                                                uint32_t* __restrict__ runcnt)
+                                                                uint32_t* __restrict__ runcnt, const KindRuns kr)
 {
     static_assert(kRun == 2048, "one run = 32 activity words");
     const uint32_t lane = threadIdx.x & 63, sub = lane & 15, grp = lane >> 4;
@@ -620,8 +669,23 @@ __global__ void __launch_bounds__(256) filter_count_runs_kernel(const uint64_t* 
         const uint64_t r = r0 + it * 4 + grp;
         uint32_t c = (uint32_t)(__popcll(w[it].x) + __popcll(w[it].y));
         for (int o = 8; o > 0; o >>= 1) c += __shfl_xor(c, o);                // the four groups of the wave reduce on their own
-        if (r < total_runs && sub == 0) runcnt[r] = c;
+        if (r < total_runs && sub == 0) runcnt[kr.run(r)] = c;
     }
+}
+
+// The same for the range-kind segments, a lane per group of 64 pivot elements: the group's survivors are what its first on-element
+// adds behind the carry (the largest i1 of the segment's earlier groups, scanned into `top`) and what the later ones add to that.
+__global__ void filter_count_ranges_kernel(const uint64_t* __restrict__ top, const uint2* __restrict__ first, const uint32_t* __restrict__ inner,
+                                           uint64_t total_groups, uint32_t* __restrict__ runcnt, const KindRuns kr)
+{
+    const uint64_t rr = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (rr >= total_groups) return;
+    const uint64_t* __restrict__ run0 = kr.run0;
+    const uint32_t t = task_find(run0, kr.n, rr);
+    const uint32_t carry = rr > run0[t] ? (uint32_t)top[rr - 1] : 0;
+    const uint2 f = first[rr];
+    const uint32_t from = f.x > carry ? f.x : carry;
+    runcnt[kr.crun0[kr.cseg[t]] + (rr - run0[t])] = inner[rr] + (f.y > from ? f.y - from : 0);
 }
 
 // survivors per list (for the host's plan): a wave per list
@@ -660,12 +724,17 @@ static_assert(kCompactRuns >= 1 && kCompactRuns <= 64, "VLG_COMPACT_RUNS: 1 .. 6
 static_assert(VLG_SPARSE_TURN >= 1 && VLG_SPARSE_TURN <= 32, "VLG_SPARSE_TURN: 1 .. 32 (a half word holds 32 survivors at most)");
 constexpr uint32_t kSparseTurn = VLG_SPARSE_TURN;      // survivors of a lane's half word moved per turn of the sparse path: their loads are in flight
                                                        // together (round 4, C3, the class: 2 -> 15.7 ms, 4 -> 13.6, 8 -> 13.3)
-template <typename pos_t>
+// kRanges: the launch for the range-kind segments of the same tasks (a run = the ranges of 64 pivot elements); either launch skips
+// the segments of the other kind.  Both write the fence of every block of 64 outputs they complete: Fc[o / 64] = Pc[o], o % 64 == 63
+// (Pc starts on a block, and the survivors of a batch are contiguous from Pc).
+template <typename pos_t, bool kRanges>
 __global__ void __launch_bounds__(256) filter_compact_kernel(const pos_t* __restrict__ P, const RSeg* __restrict__ segs,
                                                              const uint32_t* __restrict__ task_seg, const uint64_t* __restrict__ task_run0,
                                                              uint32_t ntasks, const uint64_t* __restrict__ abits,
+                                                             const uint2* __restrict__ ranges, const uint64_t* __restrict__ top,
                                                              const uint32_t* __restrict__ run_cnt, const uint32_t* __restrict__ run_off,
-                                                             pos_t* __restrict__ Pc, uint64_t pc_cap /* elements Pc can take */,
+                                                             pos_t* __restrict__ Pc, pos_t* __restrict__ Fc /* fences of Pc, or null */,
+                                                             uint64_t pc_cap /* elements Pc can take */,
                                                              uint32_t dense_min /* runs with fewer survivors move them half a word per lane */)
 {
     const uint32_t lane = threadIdx.x & 63;
@@ -677,6 +746,8 @@ __global__ void __launch_bounds__(256) filter_compact_kernel(const pos_t* __rest
     uint64_t t_begin = 0, t_end = 0;                                             // runs before t_end belong to task t (or to none yet)
     RSeg sg;
     uint64_t ahead_run = ~0ull, ahead_words = 0;                                 // the activity words of the next run, asked for a run early
+    uint2 ahead_range = make_uint2(0, 0);                                        // (kRanges: its ranges and its carry)
+    uint32_t ahead_carry = 0;
     while (todo) {
         const uint64_t run = r0 + (uint32_t)(__ffsll((long long)todo) - 1);
         todo &= todo - 1;
@@ -685,6 +756,50 @@ __global__ void __launch_bounds__(256) filter_compact_kernel(const pos_t* __rest
             t_begin = task_run0[t];
             t_end = task_run0[t + 1];
             sg = segs[task_seg[t]];
+        }
+        if ((sg.rng != 0) != kRanges) continue;
+        if constexpr (kRanges) {
+            // the pieces of the group's 64 elements, [max(i0, largest i1 before), i1), one behind the other: every lane takes an
+            // output index and finds its piece among the 64 prefix sums, so a long piece is moved by the whole wave
+            const uint64_t rr = sg.abit + (run - t_begin);
+            const uint2 r = ahead_run == run ? ahead_range : ranges[rr * 64 + lane];
+            const uint32_t carry = ahead_run == run ? ahead_carry : (run > t_begin ? (uint32_t)top[rr - 1] : 0);
+            ahead_run = ~0ull;
+            if (todo) {                                                          // the next group with survivors, if it is of the same list:
+                const uint64_t nr = r0 + (uint32_t)(__ffsll((long long)todo) - 1);   // its ranges are in flight while this group's survivors move
+                if (nr < t_end) {
+                    ahead_range = ranges[(sg.abit + (nr - t_begin)) * 64 + lane];
+                    ahead_carry = (uint32_t)top[sg.abit + (nr - t_begin) - 1];   // (nr > run >= t_begin)
+                    ahead_run = nr;
+                }
+            }
+            const bool on = r.y > r.x;                                           // = the pivot kernel's on[g]: see where it stores the ranges
+            const unsigned long long m = __ballot(on);
+            const unsigned long long below = m & ((1ull << lane) - 1ull);
+            const uint32_t e_prev = __shfl(r.y, below ? 63 - __clzll((long long)below) : 0);
+            const uint32_t before = below ? e_prev : carry;
+            const uint32_t from = r.x > before ? r.x : before;
+            const uint32_t n = on && r.y > from ? r.y - from : 0;
+            uint32_t incl = n;
+            for (int o = 1; o < 64; o <<= 1) { const uint32_t v = __shfl_up(incl, o); if ((int)lane >= o) incl += v; }
+            const uint32_t total = uniform(__shfl(incl, 63));
+            const uint32_t out0 = run_off[run];
+            if ((uint64_t)out0 + total > pc_cap) continue;
+            const uint32_t shift = from - (incl - n);                            // output o of the group comes from index shift + o
+            const pos_t* __restrict__ src = P + sg.pbegin;
+            for (uint32_t ob = 0; ob < total; ob += 64) {                        // (every lane takes every turn: the shuffles read all lanes)
+                const uint32_t o = ob + lane;
+                uint32_t j = 0;                                                  // first piece that ends behind o
+#pragma unroll
+                for (uint32_t s = 32; s; s >>= 1) if (__shfl(incl, (int)(j + s - 1)) <= o) j += s;
+                const uint32_t at = __shfl(shift, (int)(j & 63)) + o;
+                if (o < total) {
+                    const pos_t v = src[at];
+                    Pc[out0 + o] = v;
+                    if (Fc && ((out0 + o) & 63) == 63) Fc[(out0 + o) >> 6] = v;
+                }
+            }
+            continue;
         }
         const uint64_t len = sg.pend - sg.pbegin;
         const uint64_t off0 = (run - t_begin) * kRun;
@@ -731,7 +846,11 @@ __global__ void __launch_bounds__(256) filter_compact_kernel(const pos_t* __rest
                     }
                 }
 #pragma unroll
-                for (uint32_t u = 0; u < kSparseTurn; ++u) if (u < got) Pc[out + u] = v[u];
+                for (uint32_t u = 0; u < kSparseTurn; ++u)
+                    if (u < got) {
+                        Pc[out + u] = v[u];
+                        if (Fc && ((out + u) & 63) == 63) Fc[(out + u) >> 6] = v[u];
+                    }
                 out += got;
             }
             continue;
@@ -760,7 +879,11 @@ __global__ void __launch_bounds__(256) filter_compact_kernel(const pos_t* __rest
                 }
             }
 #pragma unroll
-            for (uint32_t u = 0; u < U; ++u) if (sel[u]) Pc[at[u]] = v[u];
+            for (uint32_t u = 0; u < U; ++u)
+                if (sel[u]) {
+                    Pc[at[u]] = v[u];
+                    if (Fc && (at[u] & 63) == 63) Fc[at[u] >> 6] = v[u];
+                }
         }
     }
 }
@@ -773,7 +896,11 @@ struct FilterGroup {                 // outcome of the window filter for the que
     std::vector<uint32_t> cidx;      // per sub-pattern: place in the compaction order, kNone = list used as it is
     std::vector<uint64_t> crun0;     // [ncseg+1] first run of every compacted segment
     std::vector<uint32_t> cseg;      // [ncseg] segment (index into d_segs) of every compacted segment
+    std::vector<uint8_t> ckind;      // [ncseg] 1: range-kind segment (a run = 64 pivot elements), 0: activity bits (a run = kRun slots)
     uint32_t ncseg = 0;
+    uint64_t n_stream = 0, n_bits = 0, n_ranges = 0;   // compacted segments of streamed queries, of pivot queries with bits / with ranges
+    uint2* d_ranges = nullptr;       // range-kind segments: PivotRanges::ranges, and the running maximum of PivotRanges::key
+    uint64_t* d_top = nullptr;
     RSeg* d_segs = nullptr;
     uint32_t* d_cseg = nullptr;
     uint64_t* d_crun0 = nullptr;
@@ -785,8 +912,25 @@ struct FilterGroup {                 // outcome of the window filter for the que
     // would idle through that round trip and the chunk planning otherwise): cpre[c] = where compacted segment c starts inside Pc.
     // Valid when all survivors of the group fit pc_cap; otherwise the chunks compact their own lists as before.
     bool speculated = false;
+    bool overflowed = false;         // that compaction was launched and the survivors did not fit: it wrote a part, the chunks write their own
     std::vector<uint64_t> cpre;      // [ncseg + 1]
+    uint64_t survivors = 0;          // elements the joins read of the compacted lists (whatever the chunks are; a dead query adds none)
 };
+
+// survivors of the tasks' segments -> Pc (and the fences of its whole blocks -> Fc): a launch per kind of segment among the tasks
+template <typename pos_t>
+void launch_compact(hipStream_t st, bool bits, bool ranges, uint64_t runs, const pos_t* P, const FilterGroup& fg, const uint32_t* d_task_seg,
+                    const uint64_t* d_task_run0, uint32_t ntasks, const uint32_t* d_cnt, const uint32_t* d_off, pos_t* Pc, pos_t* Fc, uint64_t pc_cap,
+                    uint32_t dense_min)
+{
+    const dim3 grid((uint32_t)(((runs + kCompactRuns - 1) / kCompactRuns + 3) / 4));
+    if (bits)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(filter_compact_kernel<pos_t, false>), grid, dim3(256), 0, st, P, fg.d_segs, d_task_seg, d_task_run0, ntasks, fg.d_abits,
+                           fg.d_ranges, fg.d_top, d_cnt, d_off, Pc, Fc, pc_cap, dense_min);
+    if (ranges)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(filter_compact_kernel<pos_t, true>), grid, dim3(256), 0, st, P, fg.d_segs, d_task_seg, d_task_run0, ntasks, fg.d_abits,
+                           fg.d_ranges, fg.d_top, d_cnt, d_off, Pc, Fc, pc_cap, dense_min);
+}
 
 inline uint32_t filter_block_shift(uint64_t n) { const unsigned b = bit_width64(n); return b > 31 ? b - 23 : 8; }   // <= 2^23 blocks
 
@@ -810,15 +954,41 @@ inline int filter_mode(const vlg_queries* q, const Plan& pl, const vlg_workspace
     return slots >= ws->filter_stream_min ? 1 : 0;         // the block bitmaps of a streamed query are a fixed cost (2 x n / 2^g bits)
 }
 
-// Bytes of filter state a query needs (0 = the query is not filtered).
-inline uint64_t filter_bytes(const vlg_queries* q, const Plan& pl, const vlg_workspace* ws, uint64_t qi, uint64_t nbw)
+// What a pivot-filtered query keeps for the lists it marks: activity bits (a bit per slot) or the index ranges themselves (8 bytes
+// per pivot element and marked level), the latter when the marked slots are at least pivot_range_ratio times the (pivot element,
+// level) pairs -- 64 is where the two cost the same bytes; 0 = always bits.
+// Below that the ranges are the larger state, by design: with the summaries a pair is charged kRangeGroupBytes / 64 = 8.5 bytes, the
+// slots it stands for pivot_range_ratio / 8 at the least, so a query's filter state grows by up to 68 / pivot_range_ratio (4.25 times
+// at the default of 16, 68 times at 1).  plan_joins charges exactly that: under a workspace cap so tight that the ranges of one query
+// pass the group's share (a third of the join budget), that query is joined unfiltered where its bits might have fitted.  Ratios
+// below 8 are for tests.
+inline bool filter_by_ranges(const vlg_queries* q, const Plan& pl, const vlg_workspace* ws, uint64_t qi, uint32_t pivot)
 {
-    const int mode = filter_mode(q, pl, ws, qi);
+    if (!ws->pivot_range_ratio) return false;
+    const uint64_t s0 = q->qsub[qi], k = q->qsub[qi + 1] - s0;
+    uint64_t slots = 0, levels = 0;
+    for (uint64_t i = 0; i + 1 < k; ++i) if (i != pivot) { slots += pl.occ[s0 + i]; ++levels; }
+    return levels && slots / ws->pivot_range_ratio >= pl.occ[s0 + pivot] * levels;
+}
+constexpr uint64_t kRangeGroupBytes = 64 * sizeof(uint2) + 8 /* top */ + 8 + 8 + 4 /* key, first, inner */ + 4 /* count */ + 1 /* scan */;
+
+// Bytes of filter state a query needs (0 = the query is not filtered); runs: what its lists add to the runs of a compaction.
+inline uint64_t filter_bytes(const vlg_queries* q, const Plan& pl, const vlg_workspace* ws, uint64_t qi, uint64_t nbw, uint64_t* runs = nullptr)
+{
+    uint32_t pivot = 0;
+    const int mode = filter_mode(q, pl, ws, qi, &pivot);
     if (!mode) return 0;
     const uint64_t s0 = q->qsub[qi], k = q->qsub[qi + 1] - s0;
-    uint64_t bytes = mode == 1 ? 2 * nbw * 8 : 0;
-    for (uint64_t i = 0; i + 1 < k; ++i) bytes += ((pl.occ[s0 + i] + kRun - 1) / kRun) * (kRun / 8 + 4);
-    return bytes + k * (sizeof(RSeg) + 32) + 64;
+    uint64_t bytes = mode == 1 ? 2 * nbw * 8 : 0, nruns = 0;
+    if (mode == 2 && filter_by_ranges(q, pl, ws, qi, pivot)) {
+        const uint64_t groups = (pl.occ[s0 + pivot] + 63) / 64 * (k - 1 - (pivot + 1 < k ? 1 : 0));
+        bytes += groups * kRangeGroupBytes;
+        nruns = groups;
+    } else {
+        for (uint64_t i = 0; i + 1 < k; ++i) { const uint64_t r = (pl.occ[s0 + i] + kRun - 1) / kRun; bytes += r * (kRun / 8 + 4); nruns += r; }
+    }
+    if (runs) *runs = nruns + k;
+    return bytes + k * (sizeof(RSeg) + 64) + 64;
 }
 
 template <typename pos_t>
@@ -843,8 +1013,10 @@ vlg_status filter_group(uint64_t n_positions /* every list element is smaller */
     std::vector<uint32_t> seg_sub;                    // sub-pattern (group relative) of every segment
     uint32_t nfq = 0, kmaxf = 0;
     uint64_t abit = 0;
-    svec<PTask> ptasks;                        // queries filtered from a pivot list
-    svec<uint64_t> prun0(1, 0);
+    svec<PTask> ptasks[2];                     // queries filtered from a pivot list: keeping bits / keeping ranges
+    svec<uint64_t> prun0[2] = {svec<uint64_t>(1, 0), svec<uint64_t>(1, 0)};
+    svec<uint32_t> kseg[2];                    // compacted segments by kind (0 bits, 1 ranges) and their runs in the kind's numbering
+    svec<uint64_t> krun0[2] = {svec<uint64_t>(1, 0), svec<uint64_t>(1, 0)};
     for (uint64_t qi = fg.g0; qi < fg.g1; ++qi) {
         if (!fg.want[qi - fg.g0]) continue;
         const uint64_t s0 = q->qsub[qi];
@@ -854,9 +1026,10 @@ vlg_status filter_group(uint64_t n_positions /* every list element is smaller */
         // a pivot list keeps every element and the last list is never filtered: with two lists and the first one as the pivot
         // there is nothing to mark
         if (by_pivot && k <= 2 && pivot == 0) continue;
+        const bool by_ranges = by_pivot && filter_by_ranges(q, pl, ws, qi, pivot);
         if (by_pivot) {
-            ptasks.push_back(PTask{(uint32_t)segs.size(), k, pivot, 0});
-            prun0.push_back(prun0.back() + (pl.occ[s0 + pivot] + kPivotRun - 1) / kPivotRun);
+            ptasks[by_ranges].push_back(PTask{(uint32_t)segs.size(), k, pivot, 0});
+            prun0[by_ranges].push_back(prun0[by_ranges].back() + (pl.occ[s0 + pivot] + kPivotRun - 1) / kPivotRun);
         } else {
             kmaxf = std::max(kmaxf, k);
         }
@@ -871,11 +1044,17 @@ vlg_status filter_group(uint64_t n_positions /* every list element is smaller */
             r.abit = ~0ull;
             // the pivot list keeps every element: the join reads it where it lies (no activity bits, no private copy)
             if (i + 1 < k && !(by_pivot && i == pivot)) {
-                r.abit = abit;                                   // on a run boundary
-                abit += (pl.occ[s0 + i] + kRun - 1) / kRun * kRun;
+                const uint64_t runs = by_ranges ? (pl.occ[s0 + pivot] + 63) / 64 : (pl.occ[s0 + i] + kRun - 1) / kRun;
+                r.rng = by_ranges;
+                r.abit = by_ranges ? krun0[1].back() : abit;     // bits: on a run boundary, run b of the kind owns the words [32 b, 32 b + 32)
+                if (!by_ranges) abit += runs * kRun;
+                kseg[by_ranges].push_back((uint32_t)cseg.size());
+                krun0[by_ranges].push_back(krun0[by_ranges].back() + runs);
+                ++(by_ranges ? fg.n_ranges : by_pivot ? fg.n_bits : fg.n_stream);
                 fg.cidx[s0 + i - fg.sub0] = (uint32_t)cseg.size();
+                fg.ckind.push_back(by_ranges);
                 cseg.push_back((uint32_t)segs.size());
-                crun0.push_back(crun0.back() + (pl.occ[s0 + i] + kRun - 1) / kRun);
+                crun0.push_back(crun0.back() + runs);
             }
             seg_sub.push_back((uint32_t)(s0 + i - fg.sub0));
             segs.push_back(r);
@@ -884,7 +1063,7 @@ vlg_status filter_group(uint64_t n_positions /* every list element is smaller */
     }
     if (getenv("VLG_TRACE")) {                         // pivot work by density: neighbour list length / pivot list length
         uint64_t h[24] = {0}, total = 0;
-        for (const PTask& t : ptasks) {
+        for (int kind = 0; kind < 2; ++kind) for (const PTask& t : ptasks[kind]) {
             const uint64_t pl_ = segs[t.seg0 + t.p].pend - segs[t.seg0 + t.p].pbegin;
             for (uint32_t i = 0; i + 1 < t.k; ++i) {
                 if (i == t.p) continue;
@@ -907,35 +1086,60 @@ vlg_status filter_group(uint64_t n_positions /* every list element is smaller */
     fg.d_segs = A.take<RSeg>(segs.size());
     fg.d_cseg = A.take<uint32_t>(cseg.size());
     fg.d_crun0 = A.take<uint64_t>(crun0.size());
+    const uint64_t bit_runs = krun0[0].back(), groups = krun0[1].back();
+    const bool mixed = bit_runs && groups;                            // (one kind only: its numbering is the group's)
     fg.d_abits = A.take<uint64_t>(abit / 64 + 1);
     fg.d_runcnt = A.take<uint32_t>(total_runs + 1);
+    PivotRanges pr{nullptr, nullptr, nullptr, nullptr};
+    if (groups) { fg.d_ranges = pr.ranges = A.take<uint2>(groups * 64); fg.d_top = A.take<uint64_t>(groups); }
     const uint64_t keep = A.used;
+    KindRuns kr[2] = {{nullptr, nullptr, fg.d_crun0, 0}, {nullptr, nullptr, fg.d_crun0, 0}};
+    void* d_top_tmp = nullptr;
+    size_t top_tmp = 0;
+    if (groups) {
+        pr.key = A.take<uint64_t>(groups); pr.first = A.take<uint2>(groups); pr.inner = A.take<uint32_t>(groups);
+        VLG_HIP_TRY(rocprim::inclusive_scan(nullptr, top_tmp, pr.key, fg.d_top, groups, rocprim::maximum<uint64_t>(), st));
+        d_top_tmp = A.take<uint8_t>(top_tmp + 256);
+    }
+    for (int kind = mixed ? 0 : 1; kind < 2; ++kind) {
+        uint32_t* d_kseg = A.take<uint32_t>(kseg[kind].size() + 1);
+        uint64_t* d_krun0 = A.take<uint64_t>(krun0[kind].size());
+        if (A.failed) break;
+        VLG_HIP_TRY(hipMemcpyAsync(d_kseg, kseg[kind].data(), kseg[kind].size() * 4, hipMemcpyHostToDevice, st));
+        VLG_HIP_TRY(hipMemcpyAsync(d_krun0, krun0[kind].data(), krun0[kind].size() * 8, hipMemcpyHostToDevice, st));
+        kr[kind] = KindRuns{d_kseg, d_krun0, fg.d_crun0, (uint32_t)kseg[kind].size()};
+    }
     unsigned long long* d_segcnt = A.take<unsigned long long>(cseg.size());
     uint64_t* d_bm = A.take<uint64_t>((uint64_t)nfq * 2 * nbw + 1);
     uint32_t* d_task_seg = A.take<uint32_t>(segs.size());
     uint64_t* d_task_run0 = A.take<uint64_t>(segs.size() + 1);
-    PTask* d_ptasks = A.take<PTask>(ptasks.size() + 1);
-    uint64_t* d_prun0 = A.take<uint64_t>(prun0.size());
+    PTask* d_ptasks[2] = {A.take<PTask>(ptasks[0].size() + 1), A.take<PTask>(ptasks[1].size() + 1)};
+    uint64_t* d_prun0[2] = {A.take<uint64_t>(prun0[0].size()), A.take<uint64_t>(prun0[1].size())};
     if (A.failed) return fail(VLG_E_INTERNAL, "arena carve failed (filter)");
-    VLG_HIP_TRY(hipMemsetAsync(fg.d_abits, 0, (abit / 64 + 1) * 8, st));    // (11 GB on C3; not clearing them at all would save 1 ms of the step)
+    VLG_HIP_TRY(hipMemsetAsync(fg.d_abits, 0, (abit / 64 + 1) * 8, st));    // (the lists that keep bits: about 2 GB on C3, 11 GB when all of them did)
     VLG_HIP_TRY(hipMemcpyAsync(fg.d_segs, segs.data(), segs.size() * sizeof(RSeg), hipMemcpyHostToDevice, st));
     VLG_HIP_TRY(hipMemcpyAsync(fg.d_cseg, cseg.data(), cseg.size() * 4, hipMemcpyHostToDevice, st));
     VLG_HIP_TRY(hipMemcpyAsync(fg.d_crun0, crun0.data(), crun0.size() * 8, hipMemcpyHostToDevice, st));
     if (nfq) VLG_HIP_TRY(hipMemsetAsync(d_bm, 0, (uint64_t)nfq * 2 * nbw * 8, st));
-    if (!ptasks.empty()) {
-        VLG_HIP_TRY(hipMemcpyAsync(d_ptasks, ptasks.data(), ptasks.size() * sizeof(PTask), hipMemcpyHostToDevice, st));
-        VLG_HIP_TRY(hipMemcpyAsync(d_prun0, prun0.data(), prun0.size() * 8, hipMemcpyHostToDevice, st));
+    if (!ptasks[0].empty() || !ptasks[1].empty()) {
         uint64_t probes = 0;                                      // (pivot element, level) pairs: two lower bounds of 8 bytes each
-        for (const PTask& pt : ptasks) probes += (uint64_t)(segs[pt.seg0 + pt.p].pend - segs[pt.seg0 + pt.p].pbegin) * (pt.k >= 2 ? pt.k - 2 + (pt.p + 1 == pt.k ? 1 : 0) : 0);
+        for (int kind = 0; kind < 2; ++kind) {
+            if (ptasks[kind].empty()) continue;
+            VLG_HIP_TRY(hipMemcpyAsync(d_ptasks[kind], ptasks[kind].data(), ptasks[kind].size() * sizeof(PTask), hipMemcpyHostToDevice, st));
+            VLG_HIP_TRY(hipMemcpyAsync(d_prun0[kind], prun0[kind].data(), prun0[kind].size() * 8, hipMemcpyHostToDevice, st));
+            for (const PTask& pt : ptasks[kind])
+                probes += (uint64_t)(segs[pt.seg0 + pt.p].pend - segs[pt.seg0 + pt.p].pbegin) * (pt.k >= 2 ? pt.k - 2 + (pt.p + 1 == pt.k ? 1 : 0) : 0);
+        }
         Timed t(ws, KS_FILTER_PIVOT, 16 * probes);
-        if (L.R && ws->pivot_rungs)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(filter_pivot_kernel<pos_t, true>), dim3((uint32_t)((prun0.back() + 4 * kPivotTurns - 1) / (4 * kPivotTurns))), dim3(256), 0, st, P,
-                               L.F, L.R, L.roff, fg.d_segs, d_ptasks, d_prun0,
-                               (uint32_t)ptasks.size(), fg.d_abits);
-        else
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(filter_pivot_kernel<pos_t, false>), dim3((uint32_t)((prun0.back() + 4 * kPivotTurns - 1) / (4 * kPivotTurns))), dim3(256), 0, st, P,
-                               L.F, (const pos_t*)nullptr, (const uint64_t*)nullptr, fg.d_segs, d_ptasks, d_prun0,
-                               (uint32_t)ptasks.size(), fg.d_abits);
+        const bool rungs = L.R && ws->pivot_rungs;
+        auto launch = [&](auto kernel, int kind) {
+            if (ptasks[kind].empty()) return;
+            hipLaunchKernelGGL(kernel, dim3((uint32_t)((prun0[kind].back() + 4 * kPivotTurns - 1) / (4 * kPivotTurns))), dim3(256), 0, st, P, L.F,
+                               rungs ? (const pos_t*)L.R : (const pos_t*)nullptr, rungs ? (const uint64_t*)L.roff : (const uint64_t*)nullptr, fg.d_segs,
+                               (const PTask*)d_ptasks[kind], (const uint64_t*)d_prun0[kind], (uint32_t)ptasks[kind].size(), fg.d_abits, pr);
+        };
+        if (rungs) { launch(filter_pivot_kernel<pos_t, true, false>, 0); launch(filter_pivot_kernel<pos_t, true, true>, 1); }
+        else { launch(filter_pivot_kernel<pos_t, false, false>, 0); launch(filter_pivot_kernel<pos_t, false, true>, 1); }
         VLG_HIP_TRY(hipGetLastError());
     }
     auto clear_buf = [&](uint32_t buf) -> vlg_status {
@@ -983,8 +1187,15 @@ vlg_status filter_group(uint64_t n_positions /* every list element is smaller */
     }
     // ---- survivors ------------------------------------------------------------------------------------
     {
-        Timed t(ws, KS_FILTER_COMPACT, abit / 8);
-        hipLaunchKernelGGL(filter_count_runs_kernel, dim3((uint32_t)((total_runs + 4 * kCountRunsPerWave - 1) / (4 * kCountRunsPerWave))), dim3(256), 0, st, fg.d_abits, total_runs, fg.d_runcnt);
+        Timed t(ws, KS_FILTER_COMPACT, abit / 8 + groups * 64 * sizeof(uint2));
+        if (bit_runs)
+            hipLaunchKernelGGL(filter_count_runs_kernel, dim3((uint32_t)((bit_runs + 4 * kCountRunsPerWave - 1) / (4 * kCountRunsPerWave))), dim3(256), 0, st, fg.d_abits,
+                               bit_runs, fg.d_runcnt, kr[0]);
+        if (groups) {
+            VLG_HIP_TRY(rocprim::inclusive_scan(d_top_tmp, top_tmp, pr.key, fg.d_top, groups, rocprim::maximum<uint64_t>(), st));
+            hipLaunchKernelGGL(filter_count_ranges_kernel, dim3((uint32_t)((groups + 255) / 256)), dim3(256), 0, st, fg.d_top, pr.first, pr.inner, groups, fg.d_runcnt,
+                               kr[1]);
+        }
         hipLaunchKernelGGL(filter_count_lists_kernel, dim3((uint32_t)((cseg.size() + 3) / 4)), dim3(256), 0, st, fg.d_crun0, fg.ncseg, fg.d_runcnt,
                            d_segcnt);
     }
@@ -1004,8 +1215,8 @@ vlg_status filter_group(uint64_t n_positions /* every list element is smaller */
         if (!A.failed) {
             Timed t(ws, KS_FILTER_COMPACT, 0);
             VLG_HIP_TRY(rocprim::exclusive_scan(d_scan, scan_tmp, fg.d_runcnt, d_off, 0u, total_runs, rocprim::plus<uint32_t>(), st));
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(filter_compact_kernel<pos_t>), dim3((uint32_t)(((total_runs + kCompactRuns - 1) / kCompactRuns + 3) / 4)),
-                               dim3(256), 0, st, P, fg.d_segs, fg.d_cseg, fg.d_crun0, fg.ncseg, fg.d_abits, fg.d_runcnt, d_off, Pc, fg.pc_cap, ws->compact_dense_min);
+            launch_compact<pos_t>(st, bit_runs != 0, groups != 0, total_runs, P, fg, fg.d_cseg, fg.d_crun0, fg.ncseg, fg.d_runcnt, d_off, Pc,
+                                  L.F ? L.F + (uint64_t)(Pc - P) / 64 : nullptr, fg.pc_cap, ws->compact_dense_min);
             VLG_HIP_TRY(hipGetLastError());
             spec_launched = true;
         } else A.failed = false;                                     // no room for the scan: the chunks compact their own lists
@@ -1022,14 +1233,9 @@ vlg_status filter_group(uint64_t n_positions /* every list element is smaller */
         fg.cpre.assign(cseg.size() + 1, 0);
         for (uint32_t c = 0; c < cseg.size(); ++c) fg.cpre[c + 1] = fg.cpre[c] + segcnt[c];
         fg.speculated = fg.cpre.back() <= fg.pc_cap;
+        fg.overflowed = !fg.speculated;
         if (fg.speculated) {
-            ws->stats[KS_FILTER_COMPACT].algorithmic_bytes += 2 * fg.cpre.back() * sizeof(pos_t);
-            // fences of the survivors' lists: whole blocks of [Pc, Pc + total) (Pc starts on a block)
-            if (L.F && fg.cpre.back() >= 64) {
-                const uint64_t g0 = (uint64_t)(Pc - P) / 64;
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(fence_build_kernel<pos_t>), launch_grid(fg.cpre.back() / 64, 8192), dim3(256), 0, st, P, g0, g0 + fg.cpre.back() / 64, L.F);
-                VLG_HIP_TRY(hipGetLastError());
-            }
+            ws->stats[KS_FILTER_COMPACT].algorithmic_bytes += 2 * fg.cpre.back() * sizeof(pos_t);   // (the writers left the fences of Pc's whole blocks)
         }
     }
     // a query that lost a whole list has no match; one whose survivors do not fit a chunk is joined on its full lists
@@ -1043,6 +1249,7 @@ vlg_status filter_group(uint64_t n_positions /* every list element is smaller */
         for (uint64_t i = 0; i + 1 < k; ++i) { dead |= fg.eff[s0 + i] == 0; if (fg.cidx[s0 + i] != kNone) sum += fg.eff[s0 + i]; }
         if (dead) for (uint64_t i = 0; i < k; ++i) fg.eff[s0 + i] = 0;
         else if (sum > fg.pc_cap && !fg.speculated) for (uint64_t i = 0; i < k; ++i) { fg.eff[s0 + i] = pl.occ[fg.sub0 + s0 + i]; fg.cidx[s0 + i] = kNone; }
+        for (uint64_t i = 0; i < k; ++i) if (fg.cidx[s0 + i] != kNone) fg.survivors += fg.eff[s0 + i];
     }
     A.used = keep;                                   // bitmaps, counters and task lists are dead
     return VLG_OK;

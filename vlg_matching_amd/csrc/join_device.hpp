@@ -65,7 +65,7 @@ __device__ __forceinline__ uint32_t gallop_lower_bound(const pos_t* __restrict__
 
 // ---- fences ------------------------------------------------------------------------------------------------------------------
 // F[g] = P[64 g + 63] for every whole block of 64 elements of the arrays the joins search (fence_build_kernel: the sorted
-// physical lists, and the survivors' private lists once they are compacted).  A search that cannot start from a previous answer
+// physical lists; filter_compact_kernel: the survivors' private lists, as it writes them).  A search that cannot start from a previous answer
 // first ranks its key among the fences of the list -- dense entries, ONE 256-byte load for 64 blocks, where probing the list
 // itself touches 64 lines -- and then looks at one block of the list.  The fences with index in [a >> 6, b >> 6) are elements of
 // the list P[a,b) whatever its borders, so no list needs fences of its own.  F == nullptr: the lists are probed directly.

@@ -65,6 +65,8 @@ struct vlg_workspace {
     uint64_t filter_pivot_ratio = 3;    // ... i.e. when all lists together are at least this many times longer (C3, ms per batch, with the
                                         // ladder: 8 -> 173.2, 6 -> 171.1, 4 -> 169.0, 3 -> 168.9, 2 -> 168.8; with bracket + bisection it was
                                         // 24 -> 262, 12 -> 251, 6 -> 246.6, 4 -> 246.4, <= 3 -> 248): the descents win wherever a list is the shortest
+    uint64_t pivot_range_ratio = 16;    // a pivot-filtered query keeps index ranges instead of activity bits when the slots it marks are at least
+                                        // this many times its (pivot element, level) pairs (filter.hpp: filter_by_ranges); 0 = never
     uint32_t compact_dense_min = 256;        // compaction: runs with fewer survivors move them half a word per lane, fuller ones word by word
                                              // (C3, ms for the class: 0 18.2, 64 18.3, 256 16.6, 512 16.8, 1024 19.2, always half words 31.5)
     uint32_t pivot_rungs = 1;   // the pivot filter searches through the ladder (join_device.hpp): 0 never (fences + bisection), 1 when it pays, 2 always
@@ -259,6 +261,7 @@ extern "C" vlg_status vlg_workspace_set_option(vlg_workspace* ws, const char* na
     if (!strcmp(name, "filter_min")) { ws->filter_min = (uint64_t)value; return VLG_OK; }
     if (!strcmp(name, "filter_pivot")) { ws->filter_pivot = value != 0; return VLG_OK; }
     if (!strcmp(name, "filter_pivot_ratio")) { ws->filter_pivot_ratio = (uint64_t)value; return VLG_OK; }
+    if (!strcmp(name, "pivot_range_ratio")) { ws->pivot_range_ratio = (uint64_t)std::max<int64_t>(0, value); return VLG_OK; }
     if (!strcmp(name, "compact_dense_min")) { ws->compact_dense_min = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 20)); return VLG_OK; }
     if (!strcmp(name, "pivot_rungs")) { ws->pivot_rungs = value <= 0 ? 0u : (value == 1 ? 1u : 2u); return VLG_OK; }
     if (!strcmp(name, "filter_stream_min")) { ws->filter_stream_min = (uint64_t)value; return VLG_OK; }
@@ -1271,6 +1274,7 @@ struct JoinChunk {
     svec<QueryMeta> qm;
     uint32_t kmax = 0, nlive = 0, n_rec = 0;
     svec<uint32_t> t_seg, t_cidx; svec<uint64_t> t_run0;            // compaction tasks: the chunk's filtered lists, in Pc order
+    bool t_kind[2] = {false, false};                                // ... hold segments with activity bits / with index ranges
     uint64_t pc_total = 0;
     std::vector<uint32_t> cls_count, cls_first;                     // segments per dist class; classes are stored from the highest dist down to 0
     std::vector<uint64_t> cls_slot_begin, cls_slot_end;
@@ -1310,6 +1314,7 @@ struct JoinChunk {
                     if (c == kNone) continue;
                     t_cidx.push_back(c);
                     t_seg.push_back(fg->cseg[c]);
+                    t_kind[fg->ckind[c]] = true;
                     t_run0.push_back(t_run0.back() + (fg->crun0[c + 1] - fg->crun0[c]));
                     pc_total += fg->eff[a + i - fg->sub0];
                 }
@@ -1339,13 +1344,9 @@ struct JoinChunk {
             hipLaunchKernelGGL(filter_gather_counts_kernel, dim3((uint32_t)((runs + 255) / 256)), dim3(256), 0, st, d_tcidx, d_trun0,
                                (uint32_t)t_seg.size(), fg->d_crun0, fg->d_runcnt, d_cnt);
             VLG_HIP_TRY(rocprim::exclusive_scan(d_scan, scan_tmp, d_cnt, d_off, 0u, runs, rocprim::plus<uint32_t>(), st));
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(filter_compact_kernel<pos_t>), dim3((uint32_t)(((runs + kCompactRuns - 1) / kCompactRuns + 3) / 4)),
-                               dim3(256), 0, st, P, fg->d_segs, d_tseg, d_trun0, (uint32_t)t_seg.size(), fg->d_abits, d_cnt, d_off, Pc, ~0ull, ws->compact_dense_min);
-        }
-        // fences of the survivors' lists: whole blocks of [Pc, Pc + pc_total) (Pc starts on a block)
-        if (F && pc_total >= 64) {
-            const uint64_t g0 = (uint64_t)(Pc - P) / 64;
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(fence_build_kernel<pos_t>), launch_grid(pc_total / 64, 8192), dim3(256), 0, st, P, g0, g0 + pc_total / 64, L.F);
+            // (the writers leave the fences of the survivors' lists: the whole blocks of [Pc, Pc + pc_total), Pc starts on a block)
+            launch_compact<pos_t>(st, t_kind[0], t_kind[1], runs, P, *fg, d_tseg, d_trun0, (uint32_t)t_seg.size(), d_cnt, d_off, Pc,
+                                  L.F ? L.F + (uint64_t)(Pc - P) / 64 : nullptr, ~0ull, ws->compact_dense_min);
         }
         VLG_HIP_TRY(hipGetLastError());
         return VLG_OK;
@@ -1657,11 +1658,12 @@ vlg_status plan_joins(const vlg_queries* q, const Plan& pl, const vlg_workspace*
         parallel_slices(Q0, Q1, 1u << 16, [&](uint64_t a, uint64_t b_, uint32_t th) {
             uint64_t bytes = 0, runs = 0, slots = 0;
             for (uint64_t qi = a; qi < b_; ++qi) {
-                uint64_t b = filter_bytes(q, pl, ws, qi, nbw);
+                uint64_t qruns = 0;
+                uint64_t b = filter_bytes(q, pl, ws, qi, nbw, &qruns);
                 if (b > jp.group_cap) b = 0;
                 jp.fbytes[qi - Q0] = b;
                 bytes += b;
-                if (b) for (uint64_t s = q->qsub[qi]; s + 1 < q->qsub[qi + 1]; ++s) { runs += pl.occ[s] / kRun + 1; slots += pl.occ[s]; }
+                if (b) { runs += qruns; for (uint64_t s = q->qsub[qi]; s + 1 < q->qsub[qi + 1]; ++s) slots += pl.occ[s]; }
             }
             part_bytes[th] = bytes; part_runs[th] = runs; part_slots[th] = slots;
         });
@@ -1675,7 +1677,7 @@ vlg_status plan_joins(const vlg_queries* q, const Plan& pl, const vlg_workspace*
             filter_total = 0; filter_runs = 0;
         }
     }
-    jp.filter_need = std::min(filter_total, jp.group_cap) + filter_runs * 8;
+    jp.filter_need = std::min(filter_total, jp.group_cap) + filter_runs * 8 + (filter_total ? 16384 : 0) /* scan of the range groups' maxima */;
     if (jp.filter_need >= join_budget || jp.logical_max_query > join_budget - jp.filter_need) {
         // the filter state would not leave room for the largest join: these queries are joined on their full lists
         std::fill(jp.fbytes.begin(), jp.fbytes.end(), 0);
@@ -1716,6 +1718,8 @@ vlg_status run_joins(uint64_t n_positions, const vlg_queries* q, vlg_workspace* 
         if (fb) {
             if (vlg_status s = filter_group<pos_t>(n_positions, q, ws, pl, L, GA, fg)) return s;
             if (fg.any) fgp = &fg;
+            res->sum.filter_stream_segments += fg.n_stream; res->sum.filter_bit_segments += fg.n_bits; res->sum.filter_range_segments += fg.n_ranges;
+            res->sum.filter_survivors += fg.survivors; res->sum.filter_overflows += fg.overflowed;
             tr.mark("filter group");
         }
         // list lengths as the chunks will see them; a chunk compacts its filtered lists itself unless the group has done so (speculated)
