@@ -101,7 +101,7 @@ typedef struct {
  * `index_*(collection&)` (benchmark/gapped-matching/include/index_sasearch.hpp:23-31) and
  * `construct(idx, file, num_bytes)` (include/sdsl/vlg_index.hpp:375-392). */
 vlg_status vlg_index_build(const uint8_t* h_text, uint64_t n_text, uint32_t sa_sample_dens, vlg_index** out);
-/* Same, text already in HBM. */
+/* Same, text already in HBM.  Synchronises `stream`: the index is complete on return. */
 vlg_status vlg_index_build_device(const uint8_t* d_text, uint64_t n_text, uint32_t sa_sample_dens,
                                   void* stream, vlg_index** out);
 /* Adopt an index built by the reference (host arrays in its layout) -- replaces
@@ -183,12 +183,13 @@ vlg_status vlg_symbol_map_apply(const vlg_symbol_map* map, const uint64_t* h_in,
 void vlg_symbol_map_destroy(vlg_symbol_map* map);
 /* int_alphabet of such an index: *sigma symbols (comp 0 = the sentinel), h_C[sigma + 1], h_comp2char[sigma]; null buffers: sigma only */
 vlg_status vlg_index_export_int_alphabet(const vlg_index* idx, uint64_t* sigma, uint64_t* h_C, uint64_t* h_comp2char);
-/* wt_int::rank(i, c) (include/sdsl/wt_int.hpp:370-395) on its BWT: out[j] = #d_sym[j] in BWT[0, d_i[j]) */
+/* wt_int::rank(i, c) (include/sdsl/wt_int.hpp:370-395) on its BWT: out[j] = #d_sym[j] in BWT[0, d_i[j]).  Asynchronous on `stream`. */
 vlg_status vlg_int_rank_batch(const vlg_index* idx, const uint64_t* d_i, const uint32_t* d_sym, uint64_t* d_out, uint64_t count, void* stream);
 void vlg_index_destroy(vlg_index* idx);
 
 /* Suffix array of text + sentinel on the device (what sdsl::construct_sa computes, include/sdsl/construct_sa.hpp:145-170): d_sa
- * receives n_text + 1 entries, d_sa[0] = n_text.  The same prefix-doubling sorter the index builder uses; n_text < 2^32 - 1. */
+ * receives n_text + 1 entries, d_sa[0] = n_text.  The same prefix-doubling sorter the index builder uses; n_text < 2^32 - 1.
+ * Synchronises `stream`. */
 vlg_status vlg_suffix_array_device(const uint8_t* d_text, uint64_t n_text, uint32_t* d_sa, void* stream);
 /* ISA samples as csa_wt keeps them (include/sdsl/csa_sampling_strategy.hpp:626-642): h_out[j] = the SA index i with SA[i] = j * inv_dens,
  * count = (n-1)/inv_dens + 1.  Computed from the index alone by walking LF from every SA sample: the byte index on its wavelet tree, the
@@ -268,6 +269,7 @@ vlg_status vlg_index_export_int_tree(const vlg_index* idx, uint32_t* max_level, 
  * (ncclBroadcast, or torch.distributed.broadcast on a uint8 tensor), every other rank attaches.
  * The attached index borrows the blob: keep it alive until vlg_index_destroy. */
 vlg_status vlg_index_blob_bytes(const vlg_index* idx, uint64_t* bytes);
+/* Synchronises `stream`: the image is complete on return. */
 vlg_status vlg_index_blob_export(const vlg_index* idx, void* d_blob, uint64_t bytes, void* stream);
 vlg_status vlg_index_attach_blob(const void* d_blob, uint64_t bytes, vlg_index** out);
 /* The same for ONE process that drives several GPUs of a node (the C++ host's `gm_search_gpu -g N`): a copy of the index in the
@@ -307,6 +309,7 @@ vlg_status vlg_comm_allgatherv(void* nccl_comm, const void* d_send, const uint64
  * out[j] = number of 1 bits in bv[0, idx[j]),  0 <= idx[j] <= nbits.
  * ---------------------------------------------------------------------------------------- */
 vlg_status vlg_bitvector_create(const uint64_t* h_words, uint64_t nbits, vlg_bitvector** out);
+/* Asynchronous on `stream`. */
 vlg_status vlg_bitvector_rank_batch(const vlg_bitvector* bv, const uint64_t* d_idx, uint64_t* d_out,
                                     uint64_t count, void* stream);
 uint64_t vlg_bitvector_hbm_bytes(const vlg_bitvector* bv);
@@ -320,6 +323,7 @@ void vlg_bitvector_destroy(vlg_bitvector* bv);
  * ---------------------------------------------------------------------------------------- */
 typedef struct vlg_rrr_bitvector vlg_rrr_bitvector;
 vlg_status vlg_rrr_bitvector_create(const uint64_t* h_words, uint64_t nbits, vlg_rrr_bitvector** out);
+/* Asynchronous on `stream`. */
 vlg_status vlg_rrr_bitvector_rank_batch(const vlg_rrr_bitvector* bv, const uint64_t* d_idx, uint64_t* d_out,
                                         uint64_t count, void* stream);
 uint64_t vlg_rrr_bitvector_hbm_bytes(const vlg_rrr_bitvector* bv);
@@ -328,19 +332,22 @@ void vlg_rrr_bitvector_destroy(vlg_rrr_bitvector* bv);
 /* ------------------------------------------------------------------------------------------
  * K2 / K3 primitives on the index (device-resident arguments).
  * ---------------------------------------------------------------------------------------- */
-/* wt_pc::rank(i, c) (include/sdsl/wt_pc.hpp:350-373): out[j] = #c[j] in BWT[0, i[j]). */
+/* wt_pc::rank(i, c) (include/sdsl/wt_pc.hpp:350-373): out[j] = #c[j] in BWT[0, i[j]).  Asynchronous on `stream`. */
 vlg_status vlg_wt_rank_batch(const vlg_index* idx, const uint64_t* d_i, const uint8_t* d_c, uint64_t* d_out,
                              uint64_t count, void* stream);
 /* backward_search(csa, 0, n-1, pat.begin(), pat.end(), l, r)
  * (include/sdsl/suffix_array_algorithm.hpp:305-326): pattern p = d_blob[d_off[p], d_off[p+1]).
- * d_l/d_r receive the interval exactly as the reference leaves it; occurrences = r+1-l. */
+ * d_l/d_r receive the interval exactly as the reference leaves it; occurrences = r+1-l.  Asynchronous on `stream`. */
 vlg_status vlg_backward_search_batch(const vlg_index* idx, const uint8_t* d_blob, const uint64_t* d_off,
                                      uint64_t n_patterns, uint64_t* d_l, uint64_t* d_r, void* stream);
-/* csa[i] (include/sdsl/csa_wt.hpp:335-348) for arbitrary SA indices: out[j] = SA[d_i[j]]. */
+/* csa[i] (include/sdsl/csa_wt.hpp:335-348) for arbitrary SA indices: out[j] = SA[d_i[j]].  Synchronises `stream` when the index keeps
+ * 4-byte samples (vlg_index_info.pos_bytes = 4: the SA indices walk in a narrow temporary that is freed on return); with 8-byte
+ * samples the walk runs in d_out and the call returns while it does. */
 vlg_status vlg_sa_batch(const vlg_index* idx, const uint64_t* d_i, uint64_t* d_out, uint64_t count, void* stream);
 /* locate (include/sdsl/suffix_array_algorithm.hpp:604-619): for pattern p the occurrences
  * csa[l[p]..r[p]] are written, in SA order (unsorted, like the reference), to
- * d_out[d_out_off[p] ...]; d_out_off = exclusive prefix sum of (r+1-l), n_patterns+1 entries. */
+ * d_out[d_out_off[p] ...]; d_out_off = exclusive prefix sum of (r+1-l), n_patterns+1 entries.  Synchronises `stream` under the
+ * same condition as vlg_sa_batch. */
 vlg_status vlg_locate_batch(const vlg_index* idx, const uint64_t* d_l, const uint64_t* d_r,
                             const uint64_t* d_out_off, uint64_t n_patterns, uint64_t total,
                             uint64_t* d_out, void* stream);
@@ -376,7 +383,7 @@ vlg_status vlg_isa_batch(const vlg_text_access* t, const uint64_t* d_i, uint64_t
  * which must outlive it; an index of any kind is taken (byte or integer alphabet, plain or rrr-63, SA-order or text-order sampling,
  * built, loaded or attached).  Creation first reads the source's totals with blocking copies (the last block or header of a
  * bit-vector; the node table, C or Z of an index: a few KiB), then uploads its tables and runs one pass over the super-block counts
- * on `stream`, which it synchronises. */
+ * on `stream`.  Synchronises `stream`: the support is complete on return. */
 typedef struct vlg_select_support vlg_select_support;
 vlg_status vlg_bitvector_select_create(const vlg_bitvector* bv, uint32_t sample, void* stream, vlg_select_support** out);
 vlg_status vlg_rrr_bitvector_select_create(const vlg_rrr_bitvector* bv, uint32_t sample, void* stream, vlg_select_support** out);
@@ -389,18 +396,19 @@ void vlg_select_support_destroy(vlg_select_support* s);
 vlg_status vlg_bit_select_batch(const vlg_select_support* s, int bit, const uint64_t* d_k, uint64_t* d_out, uint64_t count, void* stream);
 /* wt_pc::select(k, c) (include/sdsl/wt_pc.hpp:415-442) on the BWT of a byte index: d_out[j] = SA index of the d_k[j]-th occurrence of the
  * text byte d_c[j] in the BWT (c = 0: the sentinel).  k = 0, a k larger than the number of occurrences, or a byte that does not occur
- * gives n (wt_pc.hpp:418-420).  A support made from a bit-vector or from an integer index gives VLG_E_INVALID. */
+ * gives n (wt_pc.hpp:418-420).  A support made from a bit-vector or from an integer index gives VLG_E_INVALID.  Asynchronous on `stream`. */
 vlg_status vlg_wt_select_batch(const vlg_select_support* s, const uint64_t* d_k, const uint8_t* d_c, uint64_t* d_out, uint64_t count, void* stream);
 /* wt_int::select(k, c) (include/sdsl/wt_int.hpp:442-480) on the BWT of an integer index; symbols as vlg_int_rank_batch takes them (the
- * original symbols, 0 = the sentinel).  The same refusals: n for k = 0, k too large, an absent symbol or one above the largest. */
+ * original symbols, 0 = the sentinel).  The same refusals: n for k = 0, k too large, an absent symbol or one above the largest.
+ * Asynchronous on `stream`. */
 vlg_status vlg_int_select_batch(const vlg_select_support* s, const uint64_t* d_k, const uint32_t* d_sym, uint64_t* d_out, uint64_t count, void* stream);
 /* csa.psi[i] (psi_of_csa_wt::operator[], include/sdsl/suffix_array_helper.hpp:322-332) = wt.select(i - C[comp(F[i])] + 1, F[i]), byte and
- * integer indexes: d_out[j] = ISA[(SA[d_i[j]] + 1) mod n].  An i >= n gives ~0. */
+ * integer indexes: d_out[j] = ISA[(SA[d_i[j]] + 1) mod n].  An i >= n gives ~0.  Asynchronous on `stream`. */
 vlg_status vlg_psi_batch(const vlg_select_support* s, const uint64_t* d_i, uint64_t* d_out, uint64_t count, void* stream);
 /* csa.lf[i] (lf_of_csa_wt::operator[], suffix_array_helper.hpp:336-349) and csa.bwt[i] (bwt_of_csa_wt::operator[], :425-429): the LF step
  * of the locate kernels, byte and integer indexes, no support needed.  lf: d_out[j] = ISA[(SA[d_i[j]] - 1) mod n], ~0 for i >= n.
  * bwt: d_out holds uint8_t (byte index, comp2char applied) or uint32_t original symbols (integer index), as vlg_extract_batch
- * writes them; the sentinel and an i >= n give 0. */
+ * writes them; the sentinel and an i >= n give 0.  Both calls are asynchronous on `stream`. */
 vlg_status vlg_lf_batch(const vlg_index* idx, const uint64_t* d_i, uint64_t* d_out, uint64_t count, void* stream);
 vlg_status vlg_bwt_batch(const vlg_index* idx, const uint64_t* d_i, void* d_out, uint64_t count, void* stream);
 
@@ -444,11 +452,12 @@ vlg_status vlg_queries_create(const uint8_t* h_blob, const uint64_t* h_suboff, c
                               uint64_t n_queries, vlg_queries** out);
 /* sdsl::count(csa, sub-pattern) (include/sdsl/suffix_array_algorithm.hpp:516-529) for every sub-pattern of the batch: one
  * backward-search pass, h_occ[s] = r + 1 - l (vlg_queries_subpatterns(q) entries, in batch order).  What SURVEY.md 8(e) shards
- * a batch by: the sum over a query's sub-patterns estimates its locate + join work. */
+ * a batch by: the sum over a query's sub-patterns estimates its locate + join work.  Synchronises `stream`. */
 vlg_status vlg_queries_occurrences(const vlg_index* idx, const vlg_queries* q, uint64_t* h_occ, void* stream);
 /* The same pass, returning the SA interval [l, r] of every sub-pattern as backward_search leaves it (r + 1 - l occurrences;
  * suffix_array_algorithm.hpp:305-326).  Equal intervals are the same occurrence list: a host that shards a batch can keep the
- * queries that share their longest list on one GPU, so that the list is located once (vlg_matching_amd.dist.shard_by_affinity). */
+ * queries that share their longest list on one GPU, so that the list is located once (vlg_matching_amd.dist.shard_by_affinity).
+ * Synchronises `stream`. */
 vlg_status vlg_queries_intervals(const vlg_index* idx, const vlg_queries* q, uint64_t* h_l, uint64_t* h_r, void* stream);
 uint64_t vlg_queries_count(const vlg_queries* q);
 uint64_t vlg_queries_subpatterns(const vlg_queries* q);
@@ -467,7 +476,9 @@ void vlg_workspace_destroy(vlg_workspace* ws);
  *   per sub-pattern backward_search -> locate -> sort ascending -> gap-bounded merge join
  * = `idx.search(pat)` for every pattern (benchmark/gapped-matching/src/gm_search.cpp:91-121,
  *   index_sasearch.hpp:58-118) and `sdsl::locate(idx, query)` (include/sdsl/vlg_index.hpp:395-401).
- * Matches are the left-most, lazy, non-overlapping tuples of SURVEY.md Appendix C, bit-exact. */
+ * Matches are the left-most, lazy, non-overlapping tuples of SURVEY.md Appendix C, bit-exact.
+ * Every search (this one, vlg_join_batch, vlg_wtsa_search_batch, vlg_wtsa_search_window_batch) runs on the stream its workspace was
+ * created with and synchronises it before it returns: the result can be fetched at once. */
 vlg_status vlg_search_batch(const vlg_index* idx, const vlg_queries* q, vlg_workspace* ws, vlg_result** out);
 
 /* K4 stand-alone (std::sort of one occurrence list, benchmark/gapped-matching/include/index_sasearch.hpp:80): every list
@@ -564,12 +575,12 @@ typedef struct {
 vlg_status vlg_wtsa_build(const void* h_text, uint64_t n_symbols, uint32_t symbol_bytes, vlg_wtsa** out);
 vlg_status vlg_wtsa_get_info(const vlg_wtsa* idx, vlg_wtsa_info* info);
 void vlg_wtsa_destroy(vlg_wtsa* idx);
-/* wt[i] (wt_int::operator[], include/sdsl/wt_int.hpp:339-361) = SA[i] for arbitrary indices. */
+/* wt[i] (wt_int::operator[], include/sdsl/wt_int.hpp:339-361) = SA[i] for arbitrary indices.  Asynchronous on `stream`. */
 vlg_status vlg_wtsa_sa_batch(const vlg_wtsa* idx, const uint64_t* d_i, uint64_t* d_out, uint64_t count, void* stream);
 /* The two walks every search of this index is made of, on arbitrary suffix-array ranges [l, l + len): what the reference gets from
  * wt_int::expand(v) / expand(v, range) as vlg_iterator's wt_range_walker descends (include/sdsl/wt_int.hpp:824-939,
  * wt_helper.hpp:726-785).  quantile == 0: out[j] = number of SA[l, l + len) smaller than x[j]; quantile != 0: out[j] = the x[j]-th
- * smallest of them (0-based, x[j] < len[j]).  A range outside the suffix array (or x[j] >= len[j]) gives ~0. */
+ * smallest of them (0-based, x[j] < len[j]).  A range outside the suffix array (or x[j] >= len[j]) gives ~0.  Asynchronous on `stream`. */
 vlg_status vlg_wtsa_range_walk_batch(const vlg_wtsa* idx, const uint64_t* d_l, const uint64_t* d_len, const uint64_t* d_x, int quantile,
                                      uint64_t* d_out, uint64_t count, void* stream);
 /* Level `level` of the tree as plain words (bit i = h_words[i >> 6] >> (i & 63), ceil(n / 64) words): bits [level * n, (level + 1) * n)
@@ -625,10 +636,11 @@ void vlg_sdsl_wtsa_file_close(vlg_sdsl_wtsa_file* f);
 vlg_status vlg_wtsa_from_parts(const vlg_wtsa_parts* h_parts, vlg_wtsa** out);
 vlg_status vlg_wtsa_load_sdsl(const char* path, uint32_t symbol_bytes, vlg_wtsa** out);
 vlg_status vlg_wtsa_save_sdsl(const vlg_wtsa* idx, const char* path, uint32_t text_width);
+/* Asynchronous on `stream` (see above): synchronise before reading d_words. */
 vlg_status vlg_wtsa_il_device(const vlg_wtsa* idx, uint64_t* d_words, uint64_t n_words, void* stream);
 /* forward_search(text.begin(), text.end(), wt, 0, wt.size()-1, pat.begin(), pat.end(), sp, ep)
  * (include/sdsl/suffix_array_algorithm.hpp:48-112) for every sub-pattern of the batch: h_sp/h_ep receive the suffix-array
- * range [sp, ep] (sp = ep + 1: no occurrence). */
+ * range [sp, ep] (sp = ep + 1: no occurrence).  Synchronises `stream`. */
 vlg_status vlg_wtsa_ranges(const vlg_wtsa* idx, const vlg_queries* q, uint64_t* h_sp, uint64_t* h_ep, void* stream);
 /* Integer-alphabet query batch: like vlg_queries_parse with VLG_DIALECT_LIBRARY, sub-patterns parsed as the reference parses them
  * for int_alphabet_tag (whitespace-separated decimals; gaps count symbols).  Only vlg_wtsa_* entry points accept such a batch. */
