@@ -896,13 +896,12 @@ struct FilterGroup {                 // outcome of the window filter for the que
     std::vector<uint32_t> cidx;      // per sub-pattern: place in the compaction order, kNone = list used as it is
     std::vector<uint64_t> crun0;     // [ncseg+1] first run of every compacted segment
     std::vector<uint32_t> cseg;      // [ncseg] segment (index into d_segs) of every compacted segment
-    std::vector<uint8_t> ckind;      // [ncseg] 1: range-kind segment (a run = 64 pivot elements), 0: activity bits (a run = kRun slots)
+    std::vector<SegKind> ckind;      // [ncseg] kRanges: a run = 64 pivot elements, kBits: a run = kRun slots
     uint32_t ncseg = 0;
     uint64_t n_stream = 0, n_bits = 0, n_ranges = 0;   // compacted segments of streamed queries, of pivot queries with bits / with ranges
     uint2* d_ranges = nullptr;       // range-kind segments: PivotRanges::ranges, and the running maximum of PivotRanges::key
     uint64_t* d_top = nullptr;
     RSeg* d_segs = nullptr;
-    uint32_t* d_cseg = nullptr;
     uint64_t* d_crun0 = nullptr;
     uint64_t* d_abits = nullptr;
     uint32_t* d_runcnt = nullptr;
@@ -917,236 +916,248 @@ struct FilterGroup {                 // outcome of the window filter for the que
     uint64_t survivors = 0;          // elements the joins read of the compacted lists (whatever the chunks are; a dead query adds none)
 };
 
-// survivors of the tasks' segments -> Pc (and the fences of its whole blocks -> Fc): a launch per kind of segment among the tasks
+// Survivors of the tasks' segments -> L.Pc, and the fences of its whole blocks: the exclusive scan of the runs' counts says where
+// every run writes.  Shared by the group (FilterPass::speculate) and the chunks (JoinChunk::compact_survivors), in two steps because
+// the callers differ between them: carve() takes the offsets and the scan's scratch -- no room is A.failed, which means something
+// else to each caller -- and launch() goes under the caller's Timed, behind whatever fills d_cnt.
 template <typename pos_t>
-void launch_compact(hipStream_t st, bool bits, bool ranges, uint64_t runs, const pos_t* P, const FilterGroup& fg, const uint32_t* d_task_seg,
-                    const uint64_t* d_task_run0, uint32_t ntasks, const uint32_t* d_cnt, const uint32_t* d_off, pos_t* Pc, pos_t* Fc, uint64_t pc_cap,
-                    uint32_t dense_min)
-{
-    const dim3 grid((uint32_t)(((runs + kCompactRuns - 1) / kCompactRuns + 3) / 4));
-    if (bits)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(filter_compact_kernel<pos_t, false>), grid, dim3(256), 0, st, P, fg.d_segs, d_task_seg, d_task_run0, ntasks, fg.d_abits,
-                           fg.d_ranges, fg.d_top, d_cnt, d_off, Pc, Fc, pc_cap, dense_min);
-    if (ranges)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(filter_compact_kernel<pos_t, true>), grid, dim3(256), 0, st, P, fg.d_segs, d_task_seg, d_task_run0, ntasks, fg.d_abits,
-                           fg.d_ranges, fg.d_top, d_cnt, d_off, Pc, Fc, pc_cap, dense_min);
-}
+struct Compaction {
+    uint64_t runs; uint32_t* d_cnt;         // (not const: the scan stays the instantiation it was)
+    uint32_t* d_off = nullptr; void* d_scan = nullptr; size_t scan_tmp = 0;
+    vlg_status carve(Arena& A, hipStream_t st)
+    {
+        d_off = A.take<uint32_t>(runs + 1);
+        VLG_HIP_TRY(rocprim::exclusive_scan(nullptr, scan_tmp, d_cnt, d_off, 0u, runs, rocprim::plus<uint32_t>(), st));
+        d_scan = A.take<uint8_t>(scan_tmp + 256);
+        return VLG_OK;
+    }
+    // kinds[SegKind]: the tasks hold such segments (a launch per kind)
+    vlg_status launch(vlg_workspace* ws, const Lists<pos_t>& L, const FilterGroup& fg, const bool kinds[2], const uint32_t* d_task_seg,
+                      const uint64_t* d_task_run0, uint32_t ntasks, uint64_t pc_cap)
+    {
+        hipStream_t st = ws->stream;
+        VLG_HIP_TRY(rocprim::exclusive_scan(d_scan, scan_tmp, d_cnt, d_off, 0u, runs, rocprim::plus<uint32_t>(), st));
+        // (the writers leave the fences of the survivors' lists: the whole blocks of Pc, which starts on a block)
+        pos_t* Fc = L.F ? L.F + (uint64_t)(L.Pc - L.P) / 64 : nullptr;
+        const dim3 grid((uint32_t)(((runs + kCompactRuns - 1) / kCompactRuns + 3) / 4));
+        auto writers = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, (const pos_t*)L.P, fg.d_segs, d_task_seg, d_task_run0, ntasks, fg.d_abits, fg.d_ranges, fg.d_top,
+                               d_cnt, (const uint32_t*)d_off, L.Pc, Fc, pc_cap, ws->compact_dense_min);
+        };
+        if (kinds[kBits]) writers(filter_compact_kernel<pos_t, false>);
+        if (kinds[kRanges]) writers(filter_compact_kernel<pos_t, true>);
+        VLG_HIP_TRY(hipGetLastError());
+        return VLG_OK;
+    }
+};
 
 inline uint32_t filter_block_shift(uint64_t n) { const unsigned b = bit_width64(n); return b > 31 ? b - 23 : 8; }   // <= 2^23 blocks
 
-// How a query is filtered: 0 = not at all, 1 = streaming sweeps over block bitmaps, 2 = from its shortest list outwards.
-// pivot receives the level of the shortest list.
-inline int filter_mode(const vlg_queries* q, const Plan& pl, const vlg_workspace* ws, uint64_t qi, uint32_t* pivot = nullptr)
+// the options filter_shape reads, and the shape of query qi (filter_shape.hpp)
+inline FilterOptions filter_options(const vlg_workspace* ws)
 {
-    const uint64_t s0 = q->qsub[qi], k = q->qsub[qi + 1] - s0;
-    if (!ws->filter || k < 2 || !pl.occ[s0]) return 0;
-    uint64_t slots = 0, all = 0, best = ~0ull;
-    uint32_t p = 0;
-    for (uint64_t i = 0; i < k; ++i) {
-        if (i + 1 < k) slots += pl.occ[s0 + i];
-        all += pl.occ[s0 + i];
-        if (pl.occ[s0 + i] < best) { best = pl.occ[s0 + i]; p = (uint32_t)i; }
-    }
-    if (slots < ws->filter_min || !slots) return 0;
-    if (pivot) *pivot = p;
-    // two binary searches per pivot element and level against a pass (or two) over every element of every list
-    if (ws->filter_pivot && best * ws->filter_pivot_ratio <= all) return 2;
-    return slots >= ws->filter_stream_min ? 1 : 0;         // the block bitmaps of a streamed query are a fixed cost (2 x n / 2^g bits)
+    return FilterOptions{ws->filter, ws->filter_pivot, ws->filter_min, ws->filter_stream_min, ws->filter_pivot_ratio, ws->pivot_range_ratio};
 }
-
-// What a pivot-filtered query keeps for the lists it marks: activity bits (a bit per slot) or the index ranges themselves (8 bytes
-// per pivot element and marked level), the latter when the marked slots are at least pivot_range_ratio times the (pivot element,
-// level) pairs -- 64 is where the two cost the same bytes; 0 = always bits.
-// Below that the ranges are the larger state, by design: with the summaries a pair is charged kRangeGroupBytes / 64 = 8.5 bytes, the
-// slots it stands for pivot_range_ratio / 8 at the least, so a query's filter state grows by up to 68 / pivot_range_ratio (4.25 times
-// at the default of 16, 68 times at 1).  plan_joins charges exactly that: under a workspace cap so tight that the ranges of one query
-// pass the group's share (a third of the join budget), that query is joined unfiltered where its bits might have fitted.  Ratios
-// below 8 are for tests.
-inline bool filter_by_ranges(const vlg_queries* q, const Plan& pl, const vlg_workspace* ws, uint64_t qi, uint32_t pivot)
+inline FilterShape query_shape(const vlg_queries* q, const Plan& pl, const FilterOptions& fo, uint64_t qi)
 {
-    if (!ws->pivot_range_ratio) return false;
-    const uint64_t s0 = q->qsub[qi], k = q->qsub[qi + 1] - s0;
-    uint64_t slots = 0, levels = 0;
-    for (uint64_t i = 0; i + 1 < k; ++i) if (i != pivot) { slots += pl.occ[s0 + i]; ++levels; }
-    return levels && slots / ws->pivot_range_ratio >= pl.occ[s0 + pivot] * levels;
+    return filter_shape(pl.occ.data() + q->qsub[qi], (uint32_t)(q->qsub[qi + 1] - q->qsub[qi]), fo);
 }
-constexpr uint64_t kRangeGroupBytes = 64 * sizeof(uint2) + 8 /* top */ + 8 + 8 + 4 /* key, first, inner */ + 4 /* count */ + 1 /* scan */;
+static_assert(sizeof(RSeg) == kSegBytes && sizeof(uint2) == 8 && sizeof(PTask) == 16, "filter_shape.hpp: filter_bytes charges these sizes");
 
-// Bytes of filter state a query needs (0 = the query is not filtered); runs: what its lists add to the runs of a compaction.
-inline uint64_t filter_bytes(const vlg_queries* q, const Plan& pl, const vlg_workspace* ws, uint64_t qi, uint64_t nbw, uint64_t* runs = nullptr)
-{
-    uint32_t pivot = 0;
-    const int mode = filter_mode(q, pl, ws, qi, &pivot);
-    if (!mode) return 0;
-    const uint64_t s0 = q->qsub[qi], k = q->qsub[qi + 1] - s0;
-    uint64_t bytes = mode == 1 ? 2 * nbw * 8 : 0, nruns = 0;
-    if (mode == 2 && filter_by_ranges(q, pl, ws, qi, pivot)) {
-        const uint64_t groups = (pl.occ[s0 + pivot] + 63) / 64 * (k - 1 - (pivot + 1 < k ? 1 : 0));
-        bytes += groups * kRangeGroupBytes;
-        nruns = groups;
-    } else {
-        for (uint64_t i = 0; i + 1 < k; ++i) { const uint64_t r = (pl.occ[s0 + i] + kRun - 1) / kRun; bytes += r * (kRun / 8 + 4); nruns += r; }
-    }
-    if (runs) *runs = nruns + k;
-    return bytes + k * (sizeof(RSeg) + 64) + 64;
-}
+// (asked per group, not once per process: tools/fuzz_strategies.py switches it from batch to batch)
+inline bool speculative_compact_enabled() { const char* e = getenv("VLG_NO_SPECULATIVE_COMPACT"); return !(e && e[0] == '1'); }
 
+// ---- the window filter of the queries [fg.g0, fg.g1) ----------------------------------------------------
+// The stages run one after the other (filter_group, below).  The host tables the async copies read are members: they outlive the
+// wait for the counts in settle().
 template <typename pos_t>
-vlg_status filter_group(uint64_t n_positions /* every list element is smaller */, const vlg_queries* q, vlg_workspace* ws, const Plan& pl,
-                        const Lists<pos_t>& L, Arena& A /* advanced past the state the join chunks still need */, FilterGroup& fg)
-{
+struct FilterPass {
+    const uint64_t n_positions;          // every list element is smaller
+    const vlg_queries* q; vlg_workspace* ws; const Plan& pl; const Lists<pos_t>& L;
+    Arena& A;                            // advanced past the state the join chunks still need
+    FilterGroup& fg;
     hipStream_t st = ws->stream;
-    const pos_t* P = L.P;
-    pos_t* Pc = L.Pc;                                 // survivors go here
-    PhaseTrace ft(st);
+    PhaseTrace ft{st};
     const uint32_t g = filter_block_shift(n_positions);
     const uint64_t nblocks = (n_positions >> g) + 1, nbw = (nblocks + 63) / 64;
-    const uint64_t nsub = q->qsub[fg.g1] - q->qsub[fg.g0];
-    fg.sub0 = q->qsub[fg.g0];
-    fg.eff.resize(nsub);
-    fg.cidx.assign(nsub, kNone);
-    for (uint64_t s = 0; s < nsub; ++s) fg.eff[s] = pl.occ[fg.sub0 + s];
-    // ---- segments of the filtered queries ------------------------------------------------------------
+    // host tables
     svec<RSeg> segs;
-    svec<uint32_t> cseg;                       // segments that keep activity bits, in (query, level) order
-    svec<uint64_t> crun0(1, 0);
-    std::vector<uint32_t> seg_sub;                    // sub-pattern (group relative) of every segment
-    uint32_t nfq = 0, kmaxf = 0;
+    svec<uint32_t> cseg;                                // compacted segments, in (query, level) order
+    svec<uint64_t> crun0 = svec<uint64_t>(1, 0);
+    std::vector<uint32_t> seg_sub;                      // sub-pattern (group relative) of every segment
+    uint32_t nfq = 0, kmaxf = 0;                        // streamed queries, and the most lists one of them has
     uint64_t abit = 0;
-    svec<PTask> ptasks[2];                     // queries filtered from a pivot list: keeping bits / keeping ranges
-    svec<uint64_t> prun0[2] = {svec<uint64_t>(1, 0), svec<uint64_t>(1, 0)};
-    svec<uint32_t> kseg[2];                    // compacted segments by kind (0 bits, 1 ranges) and their runs in the kind's numbering
-    svec<uint64_t> krun0[2] = {svec<uint64_t>(1, 0), svec<uint64_t>(1, 0)};
-    for (uint64_t qi = fg.g0; qi < fg.g1; ++qi) {
-        if (!fg.want[qi - fg.g0]) continue;
-        const uint64_t s0 = q->qsub[qi];
-        const uint32_t k = (uint32_t)(q->qsub[qi + 1] - s0);
-        uint32_t pivot = 0;
-        const bool by_pivot = filter_mode(q, pl, ws, qi, &pivot) == 2;
-        // a pivot list keeps every element and the last list is never filtered: with two lists and the first one as the pivot
-        // there is nothing to mark
-        if (by_pivot && k <= 2 && pivot == 0) continue;
-        const bool by_ranges = by_pivot && filter_by_ranges(q, pl, ws, qi, pivot);
-        if (by_pivot) {
-            ptasks[by_ranges].push_back(PTask{(uint32_t)segs.size(), k, pivot, 0});
-            prun0[by_ranges].push_back(prun0[by_ranges].back() + (pl.occ[s0 + pivot] + kPivotRun - 1) / kPivotRun);
-        } else {
-            kmaxf = std::max(kmaxf, k);
-        }
-        for (uint32_t i = 0; i < k; ++i) {
-            RSeg r;
-            memset(&r, 0, sizeof r);
-            r.pbegin = L.off[s0 + i];
-            r.pend = r.pbegin + (uint32_t)pl.occ[s0 + i];
-            r.lo = q->lo[s0 + i]; r.hi = q->hi[s0 + i];
-            if (i + 1 < k) { r.nlo = q->lo[s0 + i + 1]; r.nhi = q->hi[s0 + i + 1]; }
-            r.fq = by_pivot ? kNone : nfq; r.level = i; r.dist = k - 1 - i;
-            r.abit = ~0ull;
-            // the pivot list keeps every element: the join reads it where it lies (no activity bits, no private copy)
-            if (i + 1 < k && !(by_pivot && i == pivot)) {
-                const uint64_t runs = by_ranges ? (pl.occ[s0 + pivot] + 63) / 64 : (pl.occ[s0 + i] + kRun - 1) / kRun;
-                r.rng = by_ranges;
-                r.abit = by_ranges ? krun0[1].back() : abit;     // bits: on a run boundary, run b of the kind owns the words [32 b, 32 b + 32)
-                if (!by_ranges) abit += runs * kRun;
-                kseg[by_ranges].push_back((uint32_t)cseg.size());
-                krun0[by_ranges].push_back(krun0[by_ranges].back() + runs);
-                ++(by_ranges ? fg.n_ranges : by_pivot ? fg.n_bits : fg.n_stream);
-                fg.cidx[s0 + i - fg.sub0] = (uint32_t)cseg.size();
-                fg.ckind.push_back(by_ranges);
-                cseg.push_back((uint32_t)segs.size());
-                crun0.push_back(crun0.back() + runs);
+    struct Kind {                                       // the group's segments of one SegKind
+        svec<PTask> ptasks;                             // queries filtered from a pivot list that keep this kind
+        svec<uint64_t> prun0 = svec<uint64_t>(1, 0);    // ... their runs of kPivotRun pivot elements
+        svec<uint32_t> kseg;                            // compacted segments of the kind, and their runs in the kind's numbering
+        svec<uint64_t> krun0 = svec<uint64_t>(1, 0);
+        uint64_t runs() const { return krun0.back(); }
+        PTask* d_ptasks = nullptr; uint64_t* d_prun0 = nullptr; uint32_t* d_kseg = nullptr; uint64_t* d_krun0 = nullptr;
+        KindRuns kr;
+    } kind[2];
+    uint64_t probes = 0, probe_hist[24] = {0};          // (pivot element, level) pairs, and (VLG_TRACE) by log2(neighbour / pivot list length)
+    svec<unsigned long long> segcnt;
+    // device arrays (what the chunks need is in fg)
+    uint64_t keep = 0;                                  // A.used behind them: all that follows is dead after the pass
+    uint32_t* d_cseg = nullptr;
+    PivotRanges pr{nullptr, nullptr, nullptr, nullptr};
+    void* d_top_tmp = nullptr; size_t top_tmp = 0;
+    unsigned long long* d_segcnt = nullptr; uint64_t* d_bm = nullptr; uint32_t* d_task_seg = nullptr; uint64_t* d_task_run0 = nullptr;
+    hipEvent_t counts_ready = nullptr;
+    bool spec_launched = false;
+
+    // host tables from the queries' shapes (no HIP call); -> fg.any
+    void segments()
+    {
+        const FilterOptions fo = filter_options(ws);
+        const uint64_t nsub = q->qsub[fg.g1] - q->qsub[fg.g0];
+        fg.sub0 = q->qsub[fg.g0];
+        fg.eff.resize(nsub);
+        fg.cidx.assign(nsub, kNone);
+        for (uint64_t s = 0; s < nsub; ++s) fg.eff[s] = pl.occ[fg.sub0 + s];
+        for (uint64_t qi = fg.g0; qi < fg.g1; ++qi) {
+            if (!fg.want[qi - fg.g0]) continue;
+            const FilterShape sh = query_shape(q, pl, fo, qi);
+            if (!sh.marks()) continue;
+            const uint64_t s0 = q->qsub[qi];
+            const uint32_t k = sh.k;
+            const SegKind sk = sh.seg_kind();
+            Kind& K = kind[sk];
+            if (sh.by_pivot()) {
+                K.ptasks.push_back(PTask{(uint32_t)segs.size(), k, sh.pivot, 0});
+                K.prun0.push_back(K.prun0.back() + (sh.occ[sh.pivot] + kPivotRun - 1) / kPivotRun);
+                probes += sh.occ[sh.pivot] * sh.levels();          // two lower bounds of 8 bytes each
+            } else {
+                kmaxf = std::max(kmaxf, k);
             }
-            seg_sub.push_back((uint32_t)(s0 + i - fg.sub0));
-            segs.push_back(r);
+            for (uint32_t i = 0; i < k; ++i) {
+                RSeg r;
+                memset(&r, 0, sizeof r);
+                r.pbegin = L.off[s0 + i];
+                r.pend = r.pbegin + (uint32_t)sh.occ[i];
+                r.lo = q->lo[s0 + i]; r.hi = q->hi[s0 + i];
+                if (i + 1 < k) { r.nlo = q->lo[s0 + i + 1]; r.nhi = q->hi[s0 + i + 1]; }
+                r.fq = sh.by_pivot() ? kNone : nfq; r.level = i; r.dist = k - 1 - i;
+                r.abit = ~0ull;
+                // (a pivot list keeps every element: the join reads it where it lies, no activity bits, no private copy)
+                if (sh.marked(i)) {
+                    const uint64_t runs = sh.runs(i);
+                    r.rng = sk;
+                    r.abit = sk == kRanges ? K.runs() : abit;       // bits: on a run boundary, run b of the kind owns the words [32 b, 32 b + 32)
+                    if (sk == kBits) abit += runs * kRun;
+                    K.kseg.push_back((uint32_t)cseg.size());
+                    K.krun0.push_back(K.runs() + runs);
+                    ++(sk == kRanges ? fg.n_ranges : sh.by_pivot() ? fg.n_bits : fg.n_stream);
+                    fg.cidx[s0 + i - fg.sub0] = (uint32_t)cseg.size();
+                    fg.ckind.push_back(sk);
+                    cseg.push_back((uint32_t)segs.size());
+                    crun0.push_back(crun0.back() + runs);
+                    if (ft.on && sh.by_pivot()) {
+                        const unsigned b = bit_width64(sh.occ[sh.pivot] ? sh.occ[i] / sh.occ[sh.pivot] : 0);
+                        probe_hist[b < 23 ? b : 23] += sh.occ[sh.pivot];
+                    }
+                }
+                seg_sub.push_back((uint32_t)(s0 + i - fg.sub0));
+                segs.push_back(r);
+            }
+            if (!sh.by_pivot()) ++nfq;
         }
-        if (!by_pivot) ++nfq;
+        fg.any = !cseg.empty();
+        if (!fg.any) return;
+        fg.ncseg = (uint32_t)cseg.size();
+        fg.crun0.assign(crun0.begin(), crun0.end());
+        fg.cseg.assign(cseg.begin(), cseg.end());
     }
-    if (getenv("VLG_TRACE")) {                         // pivot work by density: neighbour list length / pivot list length
-        uint64_t h[24] = {0}, total = 0;
-        for (int kind = 0; kind < 2; ++kind) for (const PTask& t : ptasks[kind]) {
-            const uint64_t pl_ = segs[t.seg0 + t.p].pend - segs[t.seg0 + t.p].pbegin;
-            for (uint32_t i = 0; i + 1 < t.k; ++i) {
-                if (i == t.p) continue;
-                const uint64_t nl = segs[t.seg0 + i].pend - segs[t.seg0 + i].pbegin;
-                const unsigned b = bit_width64(pl_ ? nl / pl_ : 0);
-                h[b < 23 ? b : 23] += pl_; total += pl_;
-            }
-        }
-        fprintf(stderr, "[vlg trace] pivot probes by log2(neighbour/pivot) (pivot elements x levels, total %llu):", (unsigned long long)total);
-        for (unsigned b = 0; b < 24; ++b) if (h[b]) fprintf(stderr, " %u:%llu", b, (unsigned long long)h[b]);
+
+    void trace_probes() const                          // pivot work by density: neighbour list length / pivot list length
+    {
+        if (!ft.on) return;
+        fprintf(stderr, "[vlg trace] pivot probes by log2(neighbour/pivot) (pivot elements x levels, total %llu):", (unsigned long long)probes);
+        for (unsigned b = 0; b < 24; ++b) if (probe_hist[b]) fprintf(stderr, " %u:%llu", b, (unsigned long long)probe_hist[b]);
         fprintf(stderr, "\n");
     }
-    fg.any = !cseg.empty();
-    if (!fg.any) return VLG_OK;
-    fg.ncseg = (uint32_t)cseg.size();
-    fg.crun0.assign(crun0.begin(), crun0.end());
-    fg.cseg.assign(cseg.begin(), cseg.end());
-    const uint64_t total_runs = crun0.back();
-    // ---- device state: what the chunks need first, the bitmaps and task lists (dead after the passes) last ----------
-    fg.d_segs = A.take<RSeg>(segs.size());
-    fg.d_cseg = A.take<uint32_t>(cseg.size());
-    fg.d_crun0 = A.take<uint64_t>(crun0.size());
-    const uint64_t bit_runs = krun0[0].back(), groups = krun0[1].back();
-    const bool mixed = bit_runs && groups;                            // (one kind only: its numbering is the group's)
-    fg.d_abits = A.take<uint64_t>(abit / 64 + 1);
-    fg.d_runcnt = A.take<uint32_t>(total_runs + 1);
-    PivotRanges pr{nullptr, nullptr, nullptr, nullptr};
-    if (groups) { fg.d_ranges = pr.ranges = A.take<uint2>(groups * 64); fg.d_top = A.take<uint64_t>(groups); }
-    const uint64_t keep = A.used;
-    KindRuns kr[2] = {{nullptr, nullptr, fg.d_crun0, 0}, {nullptr, nullptr, fg.d_crun0, 0}};
-    void* d_top_tmp = nullptr;
-    size_t top_tmp = 0;
-    if (groups) {
-        pr.key = A.take<uint64_t>(groups); pr.first = A.take<uint2>(groups); pr.inner = A.take<uint32_t>(groups);
-        VLG_HIP_TRY(rocprim::inclusive_scan(nullptr, top_tmp, pr.key, fg.d_top, groups, rocprim::maximum<uint64_t>(), st));
-        d_top_tmp = A.take<uint8_t>(top_tmp + 256);
-    }
-    for (int kind = mixed ? 0 : 1; kind < 2; ++kind) {
-        uint32_t* d_kseg = A.take<uint32_t>(kseg[kind].size() + 1);
-        uint64_t* d_krun0 = A.take<uint64_t>(krun0[kind].size());
-        if (A.failed) break;
-        VLG_HIP_TRY(hipMemcpyAsync(d_kseg, kseg[kind].data(), kseg[kind].size() * 4, hipMemcpyHostToDevice, st));
-        VLG_HIP_TRY(hipMemcpyAsync(d_krun0, krun0[kind].data(), krun0[kind].size() * 8, hipMemcpyHostToDevice, st));
-        kr[kind] = KindRuns{d_kseg, d_krun0, fg.d_crun0, (uint32_t)kseg[kind].size()};
-    }
-    unsigned long long* d_segcnt = A.take<unsigned long long>(cseg.size());
-    uint64_t* d_bm = A.take<uint64_t>((uint64_t)nfq * 2 * nbw + 1);
-    uint32_t* d_task_seg = A.take<uint32_t>(segs.size());
-    uint64_t* d_task_run0 = A.take<uint64_t>(segs.size() + 1);
-    PTask* d_ptasks[2] = {A.take<PTask>(ptasks[0].size() + 1), A.take<PTask>(ptasks[1].size() + 1)};
-    uint64_t* d_prun0[2] = {A.take<uint64_t>(prun0[0].size()), A.take<uint64_t>(prun0[1].size())};
-    if (A.failed) return fail(VLG_E_INTERNAL, "arena carve failed (filter)");
-    VLG_HIP_TRY(hipMemsetAsync(fg.d_abits, 0, (abit / 64 + 1) * 8, st));    // (the lists that keep bits: about 2 GB on C3, 11 GB when all of them did)
-    VLG_HIP_TRY(hipMemcpyAsync(fg.d_segs, segs.data(), segs.size() * sizeof(RSeg), hipMemcpyHostToDevice, st));
-    VLG_HIP_TRY(hipMemcpyAsync(fg.d_cseg, cseg.data(), cseg.size() * 4, hipMemcpyHostToDevice, st));
-    VLG_HIP_TRY(hipMemcpyAsync(fg.d_crun0, crun0.data(), crun0.size() * 8, hipMemcpyHostToDevice, st));
-    if (nfq) VLG_HIP_TRY(hipMemsetAsync(d_bm, 0, (uint64_t)nfq * 2 * nbw * 8, st));
-    if (!ptasks[0].empty() || !ptasks[1].empty()) {
-        uint64_t probes = 0;                                      // (pivot element, level) pairs: two lower bounds of 8 bytes each
-        for (int kind = 0; kind < 2; ++kind) {
-            if (ptasks[kind].empty()) continue;
-            VLG_HIP_TRY(hipMemcpyAsync(d_ptasks[kind], ptasks[kind].data(), ptasks[kind].size() * sizeof(PTask), hipMemcpyHostToDevice, st));
-            VLG_HIP_TRY(hipMemcpyAsync(d_prun0[kind], prun0[kind].data(), prun0[kind].size() * 8, hipMemcpyHostToDevice, st));
-            for (const PTask& pt : ptasks[kind])
-                probes += (uint64_t)(segs[pt.seg0 + pt.p].pend - segs[pt.seg0 + pt.p].pbegin) * (pt.k >= 2 ? pt.k - 2 + (pt.p + 1 == pt.k ? 1 : 0) : 0);
+
+    // device state: what the chunks need first, the bitmaps and task lists (dead after the pass) last
+    vlg_status carve()
+    {
+        const uint64_t groups = kind[kRanges].runs();
+        fg.d_segs = A.take<RSeg>(segs.size());
+        d_cseg = A.take<uint32_t>(cseg.size());
+        fg.d_crun0 = A.take<uint64_t>(crun0.size());
+        fg.d_abits = A.take<uint64_t>(abit / 64 + 1);
+        fg.d_runcnt = A.take<uint32_t>(crun0.back() + 1);
+        if (groups) { fg.d_ranges = pr.ranges = A.take<uint2>(groups * 64); fg.d_top = A.take<uint64_t>(groups); }
+        keep = A.used;
+        if (groups) {
+            pr.key = A.take<uint64_t>(groups); pr.first = A.take<uint2>(groups); pr.inner = A.take<uint32_t>(groups);
+            VLG_HIP_TRY(rocprim::inclusive_scan(nullptr, top_tmp, pr.key, fg.d_top, groups, rocprim::maximum<uint64_t>(), st));
+            d_top_tmp = A.take<uint8_t>(top_tmp + 256);
         }
+        const bool mixed = kind[kBits].runs() && groups;
+        for (Kind& K : kind) {
+            K.kr = KindRuns{nullptr, nullptr, fg.d_crun0, 0};
+            if (&K == &kind[kBits] && !mixed) continue;             // (one kind only: bit runs are then numbered as the group's)
+            K.d_kseg = A.take<uint32_t>(K.kseg.size() + 1);
+            K.d_krun0 = A.take<uint64_t>(K.krun0.size());
+            K.kr = KindRuns{K.d_kseg, K.d_krun0, fg.d_crun0, (uint32_t)K.kseg.size()};
+        }
+        d_segcnt = A.take<unsigned long long>(cseg.size());
+        d_bm = A.take<uint64_t>((uint64_t)nfq * 2 * nbw + 1);
+        d_task_seg = A.take<uint32_t>(segs.size());
+        d_task_run0 = A.take<uint64_t>(segs.size() + 1);
+        for (Kind& K : kind) K.d_ptasks = A.take<PTask>(K.ptasks.size() + 1);
+        for (Kind& K : kind) K.d_prun0 = A.take<uint64_t>(K.prun0.size());
+        if (A.failed) return fail(VLG_E_INTERNAL, "arena carve failed (filter)");
+        return VLG_OK;
+    }
+
+    vlg_status upload()
+    {
+        for (const Kind& K : kind) {
+            if (!K.d_kseg) continue;
+            VLG_HIP_TRY(hipMemcpyAsync(K.d_kseg, K.kseg.data(), K.kseg.size() * 4, hipMemcpyHostToDevice, st));
+            VLG_HIP_TRY(hipMemcpyAsync(K.d_krun0, K.krun0.data(), K.krun0.size() * 8, hipMemcpyHostToDevice, st));
+        }
+        VLG_HIP_TRY(hipMemsetAsync(fg.d_abits, 0, (abit / 64 + 1) * 8, st));    // (the lists that keep bits: about 2 GB on C3, 11 GB when all of them did)
+        VLG_HIP_TRY(hipMemcpyAsync(fg.d_segs, segs.data(), segs.size() * sizeof(RSeg), hipMemcpyHostToDevice, st));
+        VLG_HIP_TRY(hipMemcpyAsync(d_cseg, cseg.data(), cseg.size() * 4, hipMemcpyHostToDevice, st));
+        VLG_HIP_TRY(hipMemcpyAsync(fg.d_crun0, crun0.data(), crun0.size() * 8, hipMemcpyHostToDevice, st));
+        if (nfq) VLG_HIP_TRY(hipMemsetAsync(d_bm, 0, (uint64_t)nfq * 2 * nbw * 8, st));
+        for (const Kind& K : kind) {
+            if (K.ptasks.empty()) continue;
+            VLG_HIP_TRY(hipMemcpyAsync(K.d_ptasks, K.ptasks.data(), K.ptasks.size() * sizeof(PTask), hipMemcpyHostToDevice, st));
+            VLG_HIP_TRY(hipMemcpyAsync(K.d_prun0, K.prun0.data(), K.prun0.size() * 8, hipMemcpyHostToDevice, st));
+        }
+        return VLG_OK;
+    }
+
+    // the queries filtered from a pivot list: a launch per kind of state they keep
+    vlg_status pivot()
+    {
+        if (kind[kBits].ptasks.empty() && kind[kRanges].ptasks.empty()) return VLG_OK;
         Timed t(ws, KS_FILTER_PIVOT, 16 * probes);
         const bool rungs = L.R && ws->pivot_rungs;
-        auto launch = [&](auto kernel, int kind) {
-            if (ptasks[kind].empty()) return;
-            hipLaunchKernelGGL(kernel, dim3((uint32_t)((prun0[kind].back() + 4 * kPivotTurns - 1) / (4 * kPivotTurns))), dim3(256), 0, st, P, L.F,
+        auto launch = [&](auto kernel, const Kind& K) {
+            if (K.ptasks.empty()) return;
+            hipLaunchKernelGGL(kernel, dim3((uint32_t)((K.prun0.back() + 4 * kPivotTurns - 1) / (4 * kPivotTurns))), dim3(256), 0, st, (const pos_t*)L.P, L.F,
                                rungs ? (const pos_t*)L.R : (const pos_t*)nullptr, rungs ? (const uint64_t*)L.roff : (const uint64_t*)nullptr, fg.d_segs,
-                               (const PTask*)d_ptasks[kind], (const uint64_t*)d_prun0[kind], (uint32_t)ptasks[kind].size(), fg.d_abits, pr);
+                               (const PTask*)K.d_ptasks, (const uint64_t*)K.d_prun0, (uint32_t)K.ptasks.size(), fg.d_abits, pr);
         };
-        if (rungs) { launch(filter_pivot_kernel<pos_t, true, false>, 0); launch(filter_pivot_kernel<pos_t, true, true>, 1); }
-        else { launch(filter_pivot_kernel<pos_t, false, false>, 0); launch(filter_pivot_kernel<pos_t, false, true>, 1); }
+        if (rungs) { launch(filter_pivot_kernel<pos_t, true, false>, kind[kBits]); launch(filter_pivot_kernel<pos_t, true, true>, kind[kRanges]); }
+        else { launch(filter_pivot_kernel<pos_t, false, false>, kind[kBits]); launch(filter_pivot_kernel<pos_t, false, true>, kind[kRanges]); }
         VLG_HIP_TRY(hipGetLastError());
+        return VLG_OK;
     }
-    auto clear_buf = [&](uint32_t buf) -> vlg_status {
+
+    vlg_status clear_buf(uint32_t buf)
+    {
         if (nfq) VLG_HIP_TRY(hipMemset2DAsync(d_bm + (uint64_t)buf * nbw, 2 * nbw * 8, 0, nbw * 8, nfq, st));
         return VLG_OK;
-    };
-    auto run_pass = [&](const RPass& ps, auto&& pick) -> vlg_status {
+    }
+    template <typename Pick>
+    vlg_status run_pass(const RPass& ps, Pick&& pick)
+    {
         svec<uint32_t> task_seg;                      // fresh pinned storage per pass: the copies below run later, in stream order
         svec<uint64_t> task_run0(1, 0);
         task_seg.reserve(segs.size());
@@ -1164,95 +1175,126 @@ vlg_status filter_group(uint64_t n_positions /* every list element is smaller */
         VLG_HIP_TRY(hipMemcpyAsync(d_task_run0, task_run0.data(), task_run0.size() * 8, hipMemcpyHostToDevice, st));
         {
             Timed t(ws, KS_FILTER_PASS, elems * sizeof(pos_t));
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(filter_pass_kernel<pos_t>), dim3((uint32_t)((task_run0.back() + 3) / 4)), dim3(256), 0, st, P,
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(filter_pass_kernel<pos_t>), dim3((uint32_t)((task_run0.back() + 3) / 4)), dim3(256), 0, st, (const pos_t*)L.P,
                                fg.d_segs, d_task_seg, d_task_run0, (uint32_t)task_seg.size(), d_bm, nbw, g, nblocks, fg.d_abits, ps);
         }
         VLG_HIP_TRY(hipGetLastError());
         return VLG_OK;
-    };
-    // ---- backward sweep: pass j handles the sub-patterns that have j sub-patterns after them -------------------------
-    for (uint32_t j = 0; j < kmaxf; ++j) {
-        if (j >= 2) if (vlg_status s = clear_buf((j + 1) & 1)) return s;          // it held the marks pass j-1 looked up
-        const RPass ps{j ? (int32_t)(j & 1) : -1, (int32_t)((j + 1) & 1), -1, 0, 1};
-        if (vlg_status s = run_pass(ps, [&](const RSeg& r) { return r.fq != kNone && r.dist == j; })) return s;
     }
-    // ---- forward sweep: pass l handles the sub-patterns at level l (the last one of a query has no join state) --------
-    if (kmaxf >= 3) {
-        if (nfq) VLG_HIP_TRY(hipMemsetAsync(d_bm, 0, (uint64_t)nfq * 2 * nbw * 8, st));
-        for (uint32_t l = 0; l + 1 < kmaxf; ++l) {
-            if (l >= 2 && l + 3 <= kmaxf) if (vlg_status s = clear_buf((l + 1) & 1)) return s;   // it held the marks pass l-1 looked up
-            const RPass ps{l ? (int32_t)(l & 1) : -1, (int32_t)((l + 1) & 1), +1, 1, 1};
-            if (vlg_status s = run_pass(ps, [&](const RSeg& r) { return r.fq != kNone && r.level == l && r.dist >= 1 && (l >= 1 || r.dist >= 2); })) return s;
-        }
-    }
-    // ---- survivors ------------------------------------------------------------------------------------
+
+    // the streamed queries
+    vlg_status sweeps()
     {
-        Timed t(ws, KS_FILTER_COMPACT, abit / 8 + groups * 64 * sizeof(uint2));
-        if (bit_runs)
-            hipLaunchKernelGGL(filter_count_runs_kernel, dim3((uint32_t)((bit_runs + 4 * kCountRunsPerWave - 1) / (4 * kCountRunsPerWave))), dim3(256), 0, st, fg.d_abits,
-                               bit_runs, fg.d_runcnt, kr[0]);
-        if (groups) {
-            VLG_HIP_TRY(rocprim::inclusive_scan(d_top_tmp, top_tmp, pr.key, fg.d_top, groups, rocprim::maximum<uint64_t>(), st));
-            hipLaunchKernelGGL(filter_count_ranges_kernel, dim3((uint32_t)((groups + 255) / 256)), dim3(256), 0, st, fg.d_top, pr.first, pr.inner, groups, fg.d_runcnt,
-                               kr[1]);
+        // backward sweep: pass j handles the sub-patterns that have j sub-patterns after them
+        for (uint32_t j = 0; j < kmaxf; ++j) {
+            if (j >= 2) if (vlg_status s = clear_buf((j + 1) & 1)) return s;          // it held the marks pass j-1 looked up
+            const RPass ps{j ? (int32_t)(j & 1) : -1, (int32_t)((j + 1) & 1), -1, 0, 1};
+            if (vlg_status s = run_pass(ps, [&](const RSeg& r) { return r.fq != kNone && r.dist == j; })) return s;
         }
-        hipLaunchKernelGGL(filter_count_lists_kernel, dim3((uint32_t)((cseg.size() + 3) / 4)), dim3(256), 0, st, fg.d_crun0, fg.ncseg, fg.d_runcnt,
-                           d_segcnt);
+        // forward sweep: pass l handles the sub-patterns at level l (the last one of a query has no join state)
+        if (kmaxf >= 3) {
+            if (nfq) VLG_HIP_TRY(hipMemsetAsync(d_bm, 0, (uint64_t)nfq * 2 * nbw * 8, st));
+            for (uint32_t l = 0; l + 1 < kmaxf; ++l) {
+                if (l >= 2 && l + 3 <= kmaxf) if (vlg_status s = clear_buf((l + 1) & 1)) return s;   // it held the marks pass l-1 looked up
+                const RPass ps{l ? (int32_t)(l & 1) : -1, (int32_t)((l + 1) & 1), +1, 1, 1};
+                if (vlg_status s = run_pass(ps, [&](const RSeg& r) { return r.fq != kNone && r.level == l && r.dist >= 1 && (l >= 1 || r.dist >= 2); })) return s;
+            }
+        }
+        return VLG_OK;
     }
-    VLG_HIP_TRY(hipGetLastError());
-    svec<unsigned long long> segcnt(cseg.size());
-    VLG_HIP_TRY(hipMemcpyAsync(segcnt.data(), d_segcnt, cseg.size() * 8, hipMemcpyDeviceToHost, st));
-    hipEvent_t counts_ready = ws_event(ws);                          // the host waits for the counts, not for what is enqueued behind them
-    if (counts_ready) VLG_HIP_TRY(hipEventRecord(counts_ready, st));
+
+    // survivors per run and per list; the lists' counts go back to the host
+    vlg_status count()
+    {
+        const uint64_t bit_runs = kind[kBits].runs(), groups = kind[kRanges].runs();
+        {
+            Timed t(ws, KS_FILTER_COMPACT, abit / 8 + groups * 64 * sizeof(uint2));
+            if (bit_runs)
+                hipLaunchKernelGGL(filter_count_runs_kernel, dim3((uint32_t)((bit_runs + 4 * kCountRunsPerWave - 1) / (4 * kCountRunsPerWave))), dim3(256), 0, st,
+                                   fg.d_abits, bit_runs, fg.d_runcnt, kind[kBits].kr);
+            if (groups) {
+                VLG_HIP_TRY(rocprim::inclusive_scan(d_top_tmp, top_tmp, pr.key, fg.d_top, groups, rocprim::maximum<uint64_t>(), st));
+                hipLaunchKernelGGL(filter_count_ranges_kernel, dim3((uint32_t)((groups + 255) / 256)), dim3(256), 0, st, fg.d_top, pr.first, pr.inner, groups,
+                                   fg.d_runcnt, kind[kRanges].kr);
+            }
+            hipLaunchKernelGGL(filter_count_lists_kernel, dim3((uint32_t)((cseg.size() + 3) / 4)), dim3(256), 0, st, fg.d_crun0, fg.ncseg, fg.d_runcnt, d_segcnt);
+        }
+        VLG_HIP_TRY(hipGetLastError());
+        segcnt.resize(cseg.size());
+        VLG_HIP_TRY(hipMemcpyAsync(segcnt.data(), d_segcnt, cseg.size() * 8, hipMemcpyDeviceToHost, st));
+        counts_ready = ws_event(ws);                                 // the host waits for the counts, not for what is enqueued behind them
+        if (counts_ready) VLG_HIP_TRY(hipEventRecord(counts_ready, st));
+        return VLG_OK;
+    }
+
     // compaction of the whole group, launched before the counts are known (the run counts and their scan stay on the device)
-    bool spec_launched = false;
-    const bool spec_on = [] { const char* e = getenv("VLG_NO_SPECULATIVE_COMPACT"); return !(e && e[0] == '1'); }();
-    if (spec_on && Pc && fg.pc_cap && total_runs && total_runs < 0x7FFFFFFFull) {
-        uint32_t* d_off = A.take<uint32_t>(total_runs + 1);
-        size_t scan_tmp = 0;
-        VLG_HIP_TRY(rocprim::exclusive_scan(nullptr, scan_tmp, fg.d_runcnt, d_off, 0u, total_runs, rocprim::plus<uint32_t>(), st));
-        void* d_scan = A.take<uint8_t>(scan_tmp + 256);
-        if (!A.failed) {
-            Timed t(ws, KS_FILTER_COMPACT, 0);
-            VLG_HIP_TRY(rocprim::exclusive_scan(d_scan, scan_tmp, fg.d_runcnt, d_off, 0u, total_runs, rocprim::plus<uint32_t>(), st));
-            launch_compact<pos_t>(st, bit_runs != 0, groups != 0, total_runs, P, fg, fg.d_cseg, fg.d_crun0, fg.ncseg, fg.d_runcnt, d_off, Pc,
-                                  L.F ? L.F + (uint64_t)(Pc - P) / 64 : nullptr, fg.pc_cap, ws->compact_dense_min);
-            VLG_HIP_TRY(hipGetLastError());
-            spec_launched = true;
-        } else A.failed = false;                                     // no room for the scan: the chunks compact their own lists
+    vlg_status speculate()
+    {
+        const uint64_t total_runs = crun0.back();
+        if (!speculative_compact_enabled() || !L.Pc || !fg.pc_cap || !total_runs || total_runs >= 0x7FFFFFFFull) return VLG_OK;
+        Compaction<pos_t> c{total_runs, fg.d_runcnt};
+        if (vlg_status s = c.carve(A, st)) return s;
+        if (A.failed) { A.failed = false; return VLG_OK; }           // no room for the scan: the chunks compact their own lists
+        Timed t(ws, KS_FILTER_COMPACT, 0);
+        const bool kinds[2] = {kind[kBits].runs() != 0, kind[kRanges].runs() != 0};
+        if (vlg_status s = c.launch(ws, L, fg, kinds, d_cseg, fg.d_crun0, fg.ncseg, fg.pc_cap)) return s;
+        spec_launched = true;
+        return VLG_OK;
     }
-    ft.mark("  filter: launched");
-    if (counts_ready) {
-        const hipError_t e = hipEventSynchronize(counts_ready);
-        ws->free_events.push_back(counts_ready);
-        VLG_HIP_TRY(e);
-    } else VLG_HIP_TRY(hipStreamSynchronize(st));
-    ft.mark("  filter: counts back");
-    for (uint32_t c = 0; c < cseg.size(); ++c) fg.eff[seg_sub[cseg[c]]] = segcnt[c];
-    if (spec_launched) {
-        fg.cpre.assign(cseg.size() + 1, 0);
-        for (uint32_t c = 0; c < cseg.size(); ++c) fg.cpre[c + 1] = fg.cpre[c] + segcnt[c];
-        fg.speculated = fg.cpre.back() <= fg.pc_cap;
-        fg.overflowed = !fg.speculated;
-        if (fg.speculated) {
-            ws->stats[KS_FILTER_COMPACT].algorithmic_bytes += 2 * fg.cpre.back() * sizeof(pos_t);   // (the writers left the fences of Pc's whole blocks)
+
+    // the counts are back: list lengths as the joins see them, and whether the whole-group compaction holds
+    vlg_status settle()
+    {
+        ft.mark("  filter: launched");
+        if (counts_ready) {
+            const hipError_t e = hipEventSynchronize(counts_ready);
+            ws->free_events.push_back(counts_ready);
+            VLG_HIP_TRY(e);
+        } else VLG_HIP_TRY(hipStreamSynchronize(st));
+        ft.mark("  filter: counts back");
+        for (uint32_t c = 0; c < cseg.size(); ++c) fg.eff[seg_sub[cseg[c]]] = segcnt[c];
+        if (spec_launched) {
+            fg.cpre.assign(cseg.size() + 1, 0);
+            for (uint32_t c = 0; c < cseg.size(); ++c) fg.cpre[c + 1] = fg.cpre[c] + segcnt[c];
+            fg.speculated = fg.cpre.back() <= fg.pc_cap;
+            fg.overflowed = !fg.speculated;
+            if (fg.speculated) {
+                ws->stats[KS_FILTER_COMPACT].algorithmic_bytes += 2 * fg.cpre.back() * sizeof(pos_t);   // (the writers left the fences of Pc's whole blocks)
+            }
         }
+        // a query that lost a whole list has no match; one whose survivors do not fit a chunk is joined on its full lists
+        for (uint64_t qi = fg.g0; qi < fg.g1; ++qi) {
+            const uint64_t s0 = q->qsub[qi] - fg.sub0, k = q->qsub[qi + 1] - q->qsub[qi];
+            bool was_filtered = false;
+            for (uint64_t i = 0; i < k; ++i) was_filtered |= fg.cidx[s0 + i] != kNone;
+            if (!was_filtered) continue;
+            bool dead = false;
+            uint64_t sum = 0;
+            for (uint64_t i = 0; i + 1 < k; ++i) { dead |= fg.eff[s0 + i] == 0; if (fg.cidx[s0 + i] != kNone) sum += fg.eff[s0 + i]; }
+            if (dead) for (uint64_t i = 0; i < k; ++i) fg.eff[s0 + i] = 0;
+            else if (sum > fg.pc_cap && !fg.speculated) for (uint64_t i = 0; i < k; ++i) { fg.eff[s0 + i] = pl.occ[fg.sub0 + s0 + i]; fg.cidx[s0 + i] = kNone; }
+            for (uint64_t i = 0; i < k; ++i) if (fg.cidx[s0 + i] != kNone) fg.survivors += fg.eff[s0 + i];
+        }
+        A.used = keep;                                   // bitmaps, counters and task lists are dead
+        return VLG_OK;
     }
-    // a query that lost a whole list has no match; one whose survivors do not fit a chunk is joined on its full lists
-    for (uint64_t qi = fg.g0; qi < fg.g1; ++qi) {
-        const uint64_t s0 = q->qsub[qi] - fg.sub0, k = q->qsub[qi + 1] - q->qsub[qi];
-        bool was_filtered = false;
-        for (uint64_t i = 0; i < k; ++i) was_filtered |= fg.cidx[s0 + i] != kNone;
-        if (!was_filtered) continue;
-        bool dead = false;
-        uint64_t sum = 0;
-        for (uint64_t i = 0; i + 1 < k; ++i) { dead |= fg.eff[s0 + i] == 0; if (fg.cidx[s0 + i] != kNone) sum += fg.eff[s0 + i]; }
-        if (dead) for (uint64_t i = 0; i < k; ++i) fg.eff[s0 + i] = 0;
-        else if (sum > fg.pc_cap && !fg.speculated) for (uint64_t i = 0; i < k; ++i) { fg.eff[s0 + i] = pl.occ[fg.sub0 + s0 + i]; fg.cidx[s0 + i] = kNone; }
-        for (uint64_t i = 0; i < k; ++i) if (fg.cidx[s0 + i] != kNone) fg.survivors += fg.eff[s0 + i];
-    }
-    A.used = keep;                                   // bitmaps, counters and task lists are dead
-    return VLG_OK;
+};
+
+template <typename pos_t>
+vlg_status filter_group(uint64_t n_positions /* every list element is smaller */, const vlg_queries* q, vlg_workspace* ws, const Plan& pl,
+                        const Lists<pos_t>& L, Arena& A /* advanced past the state the join chunks still need */, FilterGroup& fg)
+{
+    FilterPass<pos_t> fp{n_positions, q, ws, pl, L, A, fg};
+    fp.segments();
+    fp.trace_probes();
+    if (!fg.any) return VLG_OK;
+    if (vlg_status s = fp.carve()) return s;
+    if (vlg_status s = fp.upload()) return s;
+    if (vlg_status s = fp.pivot()) return s;
+    if (vlg_status s = fp.sweeps()) return s;
+    if (vlg_status s = fp.count()) return s;
+    if (vlg_status s = fp.speculate()) return s;
+    return fp.settle();
 }
 
 }  // namespace

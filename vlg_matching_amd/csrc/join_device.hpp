@@ -401,9 +401,8 @@ __device__ __forceinline__ bool gap_window<uint32_t>(uint64_t x, uint64_t lo, ui
     return a <= 0xFFFFFFFFull;                                                   // positions fit 32 bits
 }
 
-// Slots are dealt to waves in contiguous runs so a wave can carry the segment it is in and the last answer
-// of its searches from one 64-slot step to the next.
-constexpr uint32_t kRun = 2048;
+// Slots are dealt to waves in contiguous runs of kRun (filter_shape.hpp, which the host planner shares) so a wave can carry the
+// segment it is in and the last answer of its searches from one 64-slot step to the next.
 #ifndef VLG_LINK_RUN
 #define VLG_LINK_RUN 2048
 #endif

@@ -1,7 +1,8 @@
 // Workspace, results and the fused search (backward search -> locate -> sort -> window filter -> join).
 //   queries.cpp      query batches (both dialects parsed on the host, uploaded)
 //   join_device.hpp  the device side of the join: search helpers, feasibility bitset, link / jump / chain / gather kernels
-//   filter.hpp       the window filter before the join (kernels + driver of one filter group)
+//   filter_shape.hpp how one query is filtered and what that is charged (plain C++, also compiled by a CPU test)
+//   filter.hpp       the window filter before the join (kernels + FilterPass, the driver of one filter group)
 //   kernels.hip      backward search, locate (random access and sorted sweep with shared LF trails)
 //
 // Join (K5).  The reference's merge join (benchmark/gapped-matching/include/index_sasearch.hpp:85-116;
@@ -33,6 +34,7 @@
 using namespace vlg;
 
 #include "search_types.hpp"
+#include "filter_shape.hpp"
 
 // =============================================================================================
 // Workspace
@@ -66,7 +68,7 @@ struct vlg_workspace {
                                         // ladder: 8 -> 173.2, 6 -> 171.1, 4 -> 169.0, 3 -> 168.9, 2 -> 168.8; with bracket + bisection it was
                                         // 24 -> 262, 12 -> 251, 6 -> 246.6, 4 -> 246.4, <= 3 -> 248): the descents win wherever a list is the shortest
     uint64_t pivot_range_ratio = 16;    // a pivot-filtered query keeps index ranges instead of activity bits when the slots it marks are at least
-                                        // this many times its (pivot element, level) pairs (filter.hpp: filter_by_ranges); 0 = never
+                                        // this many times its (pivot element, level) pairs (filter_shape.hpp: filter_keeps_ranges); 0 = never
     uint32_t compact_dense_min = 256;        // compaction: runs with fewer survivors move them half a word per lane, fuller ones word by word
                                              // (C3, ms for the class: 0 18.2, 64 18.3, 256 16.6, 512 16.8, 1024 19.2, always half words 31.5)
     uint32_t pivot_rungs = 1;   // the pivot filter searches through the ladder (join_device.hpp): 0 never (fences + bisection), 1 when it pays, 2 always
@@ -1274,7 +1276,7 @@ struct JoinChunk {
     svec<QueryMeta> qm;
     uint32_t kmax = 0, nlive = 0, n_rec = 0;
     svec<uint32_t> t_seg, t_cidx; svec<uint64_t> t_run0;            // compaction tasks: the chunk's filtered lists, in Pc order
-    bool t_kind[2] = {false, false};                                // ... hold segments with activity bits / with index ranges
+    bool t_kind[2] = {false, false};                                // ... hold segments of this SegKind
     uint64_t pc_total = 0;
     std::vector<uint32_t> cls_count, cls_first;                     // segments per dist class; classes are stored from the highest dist down to 0
     std::vector<uint64_t> cls_slot_begin, cls_slot_end;
@@ -1331,25 +1333,16 @@ struct JoinChunk {
         uint32_t* d_tcidx = A.take<uint32_t>(t_cidx.size());
         uint64_t* d_trun0 = A.take<uint64_t>(t_run0.size());
         uint32_t* d_cnt = A.take<uint32_t>(runs + 1);
-        uint32_t* d_off = A.take<uint32_t>(runs + 1);
-        size_t scan_tmp = 0;
-        VLG_HIP_TRY(rocprim::exclusive_scan(nullptr, scan_tmp, d_cnt, d_off, 0u, runs, rocprim::plus<uint32_t>(), st));
-        void* d_scan = A.take<uint8_t>(scan_tmp + 256);
+        Compaction<pos_t> c{runs, d_cnt};
+        if (vlg_status s = c.carve(A, st)) return s;
         if (A.failed) return fail(VLG_E_INTERNAL, "arena carve failed (compaction)");
         VLG_HIP_TRY(hipMemcpyAsync(d_tseg, t_seg.data(), t_seg.size() * 4, hipMemcpyHostToDevice, st));
         VLG_HIP_TRY(hipMemcpyAsync(d_tcidx, t_cidx.data(), t_cidx.size() * 4, hipMemcpyHostToDevice, st));
         VLG_HIP_TRY(hipMemcpyAsync(d_trun0, t_run0.data(), t_run0.size() * 8, hipMemcpyHostToDevice, st));
-        {
-            Timed t(ws, KS_FILTER_COMPACT, 2 * pc_total * sizeof(pos_t));
-            hipLaunchKernelGGL(filter_gather_counts_kernel, dim3((uint32_t)((runs + 255) / 256)), dim3(256), 0, st, d_tcidx, d_trun0,
-                               (uint32_t)t_seg.size(), fg->d_crun0, fg->d_runcnt, d_cnt);
-            VLG_HIP_TRY(rocprim::exclusive_scan(d_scan, scan_tmp, d_cnt, d_off, 0u, runs, rocprim::plus<uint32_t>(), st));
-            // (the writers leave the fences of the survivors' lists: the whole blocks of [Pc, Pc + pc_total), Pc starts on a block)
-            launch_compact<pos_t>(st, t_kind[0], t_kind[1], runs, P, *fg, d_tseg, d_trun0, (uint32_t)t_seg.size(), d_cnt, d_off, Pc,
-                                  L.F ? L.F + (uint64_t)(Pc - P) / 64 : nullptr, ~0ull, ws->compact_dense_min);
-        }
-        VLG_HIP_TRY(hipGetLastError());
-        return VLG_OK;
+        Timed t(ws, KS_FILTER_COMPACT, 2 * pc_total * sizeof(pos_t));
+        hipLaunchKernelGGL(filter_gather_counts_kernel, dim3((uint32_t)((runs + 255) / 256)), dim3(256), 0, st, d_tcidx, d_trun0,
+                           (uint32_t)t_seg.size(), fg->d_crun0, fg->d_runcnt, d_cnt);
+        return c.launch(ws, L, *fg, t_kind, d_tseg, d_trun0, (uint32_t)t_seg.size(), ~0ull);
     }
 
     // host-side metadata of the chunk (no HIP call): segments in class-major order (dist descending), their lists and slots, the
@@ -1655,11 +1648,12 @@ vlg_status plan_joins(const vlg_queries* q, const Plan& pl, const vlg_workspace*
     uint64_t filter_runs = 0;                                             // runs the compaction of one chunk may have to index
     if (ws->filter && jp.logical_max_query + jp.group_cap <= join_budget) {
         uint64_t part_bytes[kHostThreads] = {0}, part_runs[kHostThreads] = {0}, part_slots[kHostThreads] = {0};
+        const FilterOptions fo = filter_options(ws);
         parallel_slices(Q0, Q1, 1u << 16, [&](uint64_t a, uint64_t b_, uint32_t th) {
             uint64_t bytes = 0, runs = 0, slots = 0;
             for (uint64_t qi = a; qi < b_; ++qi) {
                 uint64_t qruns = 0;
-                uint64_t b = filter_bytes(q, pl, ws, qi, nbw, &qruns);
+                uint64_t b = filter_bytes(query_shape(q, pl, fo, qi), nbw, &qruns);
                 if (b > jp.group_cap) b = 0;
                 jp.fbytes[qi - Q0] = b;
                 bytes += b;
@@ -1677,7 +1671,7 @@ vlg_status plan_joins(const vlg_queries* q, const Plan& pl, const vlg_workspace*
             filter_total = 0; filter_runs = 0;
         }
     }
-    jp.filter_need = std::min(filter_total, jp.group_cap) + filter_runs * 8 + (filter_total ? 16384 : 0) /* scan of the range groups' maxima */;
+    jp.filter_need = filter_group_charge(filter_total, jp.group_cap, filter_runs);
     if (jp.filter_need >= join_budget || jp.logical_max_query > join_budget - jp.filter_need) {
         // the filter state would not leave room for the largest join: these queries are joined on their full lists
         std::fill(jp.fbytes.begin(), jp.fbytes.end(), 0);
@@ -1827,12 +1821,14 @@ vlg_status plan_super_chunk(const vlg_index* idx, const vlg_queries* q, const Pl
     {
         uint64_t part_max[kHostThreads] = {0}, part_piv[kHostThreads] = {0};
         const bool count_pivots = ws->filter && ws->filter_pivot && ws->pivot_rungs;
+        const FilterOptions fo = filter_options(ws);
         parallel_slices(Q0, Q1, 1u << 16, [&](uint64_t a, uint64_t b, uint32_t t) {
             uint64_t mx = 0, pv_sum = 0;
             for (uint64_t qi = a; qi < b; ++qi) {
                 mx = std::max(mx, join_cost(q, pl, qi).bytes);
-                uint32_t pv = 0;
-                if (count_pivots && filter_mode(q, pl, ws, qi, &pv) == 2) pv_sum += pl.occ[q->qsub[qi] + pv];
+                if (!count_pivots) continue;
+                const FilterShape sh = query_shape(q, pl, fo, qi);
+                if (sh.by_pivot()) pv_sum += sh.occ[sh.pivot];
             }
             part_max[t] = mx; part_piv[t] = pv_sum;
         });
