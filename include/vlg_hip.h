@@ -463,6 +463,25 @@ uint64_t vlg_queries_count(const vlg_queries* q);
 uint64_t vlg_queries_subpatterns(const vlg_queries* q);
 /* h_k[q] = number of sub-patterns of query q (0 for a query that failed to parse). */
 vlg_status vlg_queries_k(const vlg_queries* q, uint32_t* h_k);
+/* Text windows of a batch: query j is answered on [h_begin[j], h_end[j]) and its matches are exactly those of the same query on the
+ * stand-alone text T[begin, end), with begin added to every position -- what a caller with a document collection asks for: one batch
+ * entry per (query, document) pair, every distinct occurrence list still located once.  An occurrence of a sub-pattern of m symbols
+ * (m = (suboff[s + 1] - suboff[s]) / symbol bytes) counts only if it lies wholly inside: begin <= v and v + m <= end.  h_begin / h_end
+ * are host arrays of vlg_queries_count(q) entries, copied; a NULL h_begin means all zeros, a NULL h_end "to the end of the text"; both
+ * NULL removes the windows and the batch is what it was.  The batch does not know the text: an end beyond it is clamped at search time,
+ * a begin beyond it is an empty window.  begin[j] > end[j] gives VLG_E_INVALID and the batch keeps its previous windows; a window shorter
+ * than a sub-pattern, or begin == end, makes an empty query and is no error.  Host only: no device, no stream.
+ *   vlg_search_batch honours the windows (byte and integer indexes, plain or rrr, either sampling, any density); gaps, end_len, "tuples"
+ *     and every other workspace option keep their meaning, the checksum is the sum over what is returned.  A collective search
+ *     (vlg_workspace_set_comm / _set_exchange* with more than one rank) of a windowed batch gives VLG_E_UNSUPPORTED before any launch.
+ *   vlg_queries_occurrences, vlg_queries_intervals and vlg_wtsa_ranges ignore them: they answer per sub-pattern.
+ *   vlg_wtsa_search_batch and vlg_wtsa_search_window_batch refuse a batch that carries windows with VLG_E_INVALID: that path takes its
+ *     windows as arrays.
+ * A batch must not be changed (windows included) while a search on it runs.
+ * get: *has_windows = 1 when the batch carries windows; h_begin / h_end (either may be NULL) receive them as they were set (a NULL
+ * h_begin reads as zeros, a NULL h_end as UINT64_MAX; a batch without windows gives 0 and UINT64_MAX). */
+vlg_status vlg_queries_set_windows(vlg_queries* q, const uint64_t* h_begin, const uint64_t* h_end);
+vlg_status vlg_queries_get_windows(const vlg_queries* q, int* has_windows, uint64_t* h_begin, uint64_t* h_end);
 void vlg_queries_destroy(vlg_queries* q);
 
 /* ------------------------------------------------------------------------------------------
@@ -527,6 +546,10 @@ typedef struct {
     uint64_t filter_overflows;       /* groups of filtered queries whose survivors did not fit the room behind the lists at once:
                                         their join chunks compacted their own lists                                            */
 } vlg_result_summary;
+/* A batch with text windows (vlg_queries_set_windows): the lists are located whole, so located_occurrences, lf_steps, wt_levels_* and
+ * locate_mode are those of the same batch without windows; logical_occurrences is the sum of the CUT lengths of the live queries (the
+ * list lengths the joins consumed), and everything else -- matches, checksum, chunks, join slots, the filter's counters -- follows
+ * from the cut lists. */
 /* csa[i] = iterated LF to a sampled index (csa_wt.hpp:335-348), organised per batch as
  *   WALKS     one walk per occurrence (few occurrences; integer alphabets; workspace option "sweep" = 0)
  *   SWEEP     all occurrences advance together in SA order, walks that meet share their LF steps ("trail" = 1)
@@ -662,7 +685,9 @@ vlg_status vlg_wtsa_search_batch(const vlg_wtsa* idx, const vlg_queries* q, uint
  * The occurrence list of a sub-pattern exists only as the sorted values of its suffix-array range, so the window is a rank interval of
  * it: two count_less walks per sub-pattern (wt_int::range_search_2d's descent to the value bounds, include/sdsl/wt_int.hpp:612-700),
  * nothing located, nothing sorted -- the cost follows the matches inside the window.  vlg_wtsa_search_batch is this call with two NULLs.
- * (vlg_search_batch on the FM-index takes no windows: its sorted lists are shared between the queries of a batch) */
+ * A batch that carries windows of its own (vlg_queries_set_windows) is refused here with VLG_E_INVALID.
+ * (vlg_search_batch on the FM-index takes its windows from the batch, vlg_queries_set_windows: every list is located and sorted whole,
+ * once, and a window is a cut of it -- the cost follows the lists, not the matches inside the window.  DESIGN.md 8.) */
 vlg_status vlg_wtsa_search_window_batch(const vlg_wtsa* idx, const vlg_queries* q, const uint64_t* h_begin, const uint64_t* h_end,
                                         uint64_t max_matches_per_query, vlg_workspace* ws, vlg_result** out);
 /* Where a search stopped, so that it can be continued as the reference's iterator continues (pull_forward, include/sdsl/vlg_index.hpp:254-266):

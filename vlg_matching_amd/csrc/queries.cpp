@@ -415,6 +415,32 @@ extern "C" vlg_status vlg_queries_k(const vlg_queries* q, uint32_t* h_k)
     for (uint64_t i = 0; i < q->nq; ++i) h_k[i] = (uint32_t)(q->qsub[i + 1] - q->qsub[i]);
     return VLG_OK;
 }
+extern "C" vlg_status vlg_queries_set_windows(vlg_queries* q, const uint64_t* h_begin, const uint64_t* h_end)
+{
+    if (!q) return fail(VLG_E_INVALID, "null argument");
+    if (!h_begin && !h_end) { q->win_begin.clear(); q->win_end.clear(); return VLG_OK; }
+    // (checked before anything is stored: a refused call keeps the batch's previous windows)
+    if (h_begin && h_end)
+        for (uint64_t j = 0; j < q->nq; ++j)
+            if (h_begin[j] > h_end[j]) return fail(VLG_E_INVALID, "window of query " + std::to_string(j) + ": begin > end");
+    std::vector<uint64_t> b(q->nq, 0), e(q->nq, ~0ull);
+    if (h_begin) b.assign(h_begin, h_begin + q->nq);
+    if (h_end) e.assign(h_end, h_end + q->nq);
+    q->win_begin.swap(b);
+    q->win_end.swap(e);                                                  // (an empty batch carries no window: the vectors stay empty)
+    return VLG_OK;
+}
+extern "C" vlg_status vlg_queries_get_windows(const vlg_queries* q, int* has_windows, uint64_t* h_begin, uint64_t* h_end)
+{
+    if (!q) return fail(VLG_E_INVALID, "null argument");
+    const bool has = q->has_windows();
+    if (has_windows) *has_windows = has ? 1 : 0;
+    for (uint64_t j = 0; j < q->nq; ++j) {
+        if (h_begin) h_begin[j] = has ? q->win_begin[j] : 0;
+        if (h_end) h_end[j] = has ? q->win_end[j] : ~0ull;
+    }
+    return VLG_OK;
+}
 extern "C" void vlg_queries_destroy(vlg_queries* q)
 {
     if (!q) return;

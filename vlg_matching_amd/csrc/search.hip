@@ -35,14 +35,15 @@ using namespace vlg;
 
 #include "search_types.hpp"
 #include "filter_shape.hpp"
+#include "window_cut.hpp"
 
 // =============================================================================================
 // Workspace
 // =============================================================================================
 enum { KS_BSEARCH = 0, KS_EXPAND, KS_LOCATE, KS_LOCATE_PART, KS_LOCATE_RESOLVE, KS_SORT, KS_FILTER_LADDER, KS_FILTER_PIVOT, KS_FILTER_PASS, KS_FILTER_COMPACT,
-       KS_JOIN_INIT, KS_JOIN_LINK, KS_JOIN_SCAN, KS_JOIN_CHAIN, KS_GATHER, KS_EXCHANGE, KS_COUNT };
+       KS_JOIN_INIT, KS_JOIN_LINK, KS_JOIN_SCAN, KS_JOIN_CHAIN, KS_GATHER, KS_EXCHANGE, KS_WINDOW_CUT, KS_COUNT };
 static const char* kKernelNames[KS_COUNT] = {"backward_search", "expand", "locate", "locate_partition", "locate_resolve", "sort", "filter_ladder", "filter_pivot",
-                                             "filter_pass", "filter_compact", "join_init", "join_link", "join_scan", "join_chain", "gather", "exchange"};
+                                             "filter_pass", "filter_compact", "join_init", "join_link", "join_scan", "join_chain", "gather", "exchange", "window_cut"};
 
 struct vlg_workspace {
     hipStream_t stream = nullptr;
@@ -1883,6 +1884,130 @@ std::vector<uint64_t> cut_queries(const vlg_queries* q, const Plan& pl, uint64_t
     return xq;
 }
 
+// ---- text windows (vlg_queries_set_windows): every list of a query cut to the query's window -------------------------------------
+// The lists stay whole and shared; a window is the rank interval [lower_bound(klo), lower_bound(khi)) of a list (window_cut.hpp), and
+// the joins and the filter see a list only as (L.off[s], occ[s]).  Fences are elements of any list that covers their index, whatever
+// its borders (join_device.hpp), so a cut list is searched through the same fences and ladder as the whole one.
+//
+// One lane per (sub-pattern, side): the key is ranked among the list's fences by bisection (dense lines: 64 blocks per 256 bytes),
+// then inside one block of 64.  Without fences (no room in the arena), and on short lists, the list itself is bisected.
+// (One wave per key -- wave_kary_lower_bound -- was measured beside it: 2.6 to 4.7 times the time of this class on C3)
+template <typename pos_t>
+__device__ __forceinline__ uint32_t fenced_lower_bound(const pos_t* __restrict__ P, const pos_t* __restrict__ F, uint32_t a, uint32_t b, uint64_t key)
+{
+    if (!F || b - a < 128) return lower_bound_dev(P, a, b, key);
+    const uint64_t g0 = (uint64_t)lower_bound_dev(F, a >> 6, b >> 6, key) << 6;   // first block of the list whose last element is >= key
+    const uint32_t w0 = g0 < a ? a : (uint32_t)g0;
+    const uint32_t w1 = g0 + 64 < b ? (uint32_t)(g0 + 64) : b;                     // (behind the last whole block: the rest of the list)
+    return lower_bound_dev(P, w0, w1, key);
+}
+// cut[2 s] / cut[2 s + 1] = index in P of the first element >= klo[s] / >= khi[s] of the list P[a[s], a[s] + len[s]); keys are
+// 64-bit (khi can be 2^32 over 32-bit positions).  An empty list, or an empty window (the host passes len = 0), gives a[s] twice.
+template <typename pos_t>
+__global__ void __launch_bounds__(256) window_cut_kernel(const pos_t* __restrict__ P, const pos_t* __restrict__ F, const uint32_t* __restrict__ a,
+                                                         const uint32_t* __restrict__ len, const uint64_t* __restrict__ klo, const uint64_t* __restrict__ khi,
+                                                         uint64_t nsub, uint32_t* __restrict__ cut)
+{
+    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < 2 * nsub; t += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t s = t >> 1;
+        const uint32_t la = a[s];
+        cut[t] = fenced_lower_bound(P, F, la, la + len[s], (t & 1) ? khi[s] : klo[s]);
+    }
+}
+// Per query of [Q0, Q1): the cut lengths of its lists, all 0 when one of them is empty (JoinChunk::live: "a query with an empty list
+// has all lengths 0").  s0 = qsub[Q0]; cut and occ are indexed from there.
+__global__ void window_lengths_kernel(const uint64_t* __restrict__ qsub, uint64_t Q0, uint64_t Q1, uint64_t s0, const uint32_t* __restrict__ cut,
+                                      uint64_t* __restrict__ occ)
+{
+    for (uint64_t qi = Q0 + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; qi < Q1; qi += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t sa = qsub[qi] - s0, sb = qsub[qi + 1] - s0;
+        bool live = sb > sa;
+        for (uint64_t s = sa; s < sb && live; ++s) live = cut[2 * s + 1] > cut[2 * s];
+        for (uint64_t s = sa; s < sb; ++s) occ[s] = live ? (uint64_t)(cut[2 * s + 1] - cut[2 * s]) : 0;
+    }
+}
+
+// The queries [sc.Q0, sc.Q1) behind build_physical: -> cut.occ (the cut lengths; did, dl, docc as in pl) and L.off (where every cut
+// list starts in P); `logical` += the cut lengths of the live queries.  The host waits for the lengths -- the join plan follows them.
+// WA: room behind the lists (by value: the joins take it again afterwards).
+template <typename pos_t>
+vlg_status cut_to_windows(const vlg_index* idx, const vlg_queries* q, vlg_workspace* ws, const Plan& pl, const SuperChunk& sc, Lists<pos_t>& L, Arena WA,
+                          Plan& cut, uint64_t& logical)
+{
+    const uint64_t s0 = q->qsub[sc.Q0], ns = q->qsub[sc.Q1] - s0, n_text = idx->hdr.n - 1;      // (hdr.n counts the sentinel)
+    hipStream_t st = ws->stream;
+    if (cut.occ.size() != q->nsub) { cut.occ.resize(q->nsub); cut.did = pl.did; cut.dl = pl.dl; cut.docc = pl.docc; }
+    if (!ns) return VLG_OK;
+    svec<uint32_t> h_a(ns), h_len(ns), h_cut(2 * ns);
+    svec<uint64_t> h_klo(ns), h_khi(ns);
+    parallel_slices(sc.Q0, sc.Q1, 1u << 16, [&](uint64_t qa, uint64_t qb, uint32_t) {
+        for (uint64_t qi = qa; qi < qb; ++qi)
+            for (uint64_t s = q->qsub[qi]; s < q->qsub[qi + 1]; ++s) {
+                const WindowKeys k = window_keys(q->win_begin[qi], q->win_end[qi], (q->suboff[s + 1] - q->suboff[s]) / q->sym_bytes, n_text);
+                const bool none = k.empty || !pl.occ[s];
+                h_a[s - s0] = none ? 0 : L.doff[pl.did[s]];
+                h_len[s - s0] = none ? 0 : (uint32_t)pl.occ[s];
+                h_klo[s - s0] = k.klo; h_khi[s - s0] = k.khi;
+            }
+    });
+    uint32_t* d_a = WA.take<uint32_t>(ns);
+    uint32_t* d_len = WA.take<uint32_t>(ns);
+    uint64_t* d_klo = WA.take<uint64_t>(ns);
+    uint64_t* d_khi = WA.take<uint64_t>(ns);
+    uint32_t* d_cut = WA.take<uint32_t>(2 * ns);
+    uint64_t* d_occ = WA.take<uint64_t>(ns);
+    if (WA.failed) return fail(VLG_E_WORKSPACE, "no room behind the lists for the window cut of " + std::to_string(ns) + " sub-patterns");
+    VLG_HIP_TRY(hipMemcpyAsync(d_a, h_a.data(), ns * 4, hipMemcpyHostToDevice, st));
+    VLG_HIP_TRY(hipMemcpyAsync(d_len, h_len.data(), ns * 4, hipMemcpyHostToDevice, st));
+    VLG_HIP_TRY(hipMemcpyAsync(d_klo, h_klo.data(), ns * 8, hipMemcpyHostToDevice, st));
+    VLG_HIP_TRY(hipMemcpyAsync(d_khi, h_khi.data(), ns * 8, hipMemcpyHostToDevice, st));
+    {
+        Timed t(ws, KS_WINDOW_CUT, 2 * ns * 256);                             // (a line of fences and a block of the list per key)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(window_cut_kernel<pos_t>), launch_grid(2 * ns, 4096), dim3(256), 0, st, (const pos_t*)L.P, (const pos_t*)L.F, d_a,
+                           d_len, d_klo, d_khi, ns, d_cut);
+        hipLaunchKernelGGL(window_lengths_kernel, launch_grid(sc.Q1 - sc.Q0, 2048), dim3(256), 0, st, q->d_qsub, sc.Q0, sc.Q1, s0, d_cut, d_occ);
+    }
+    VLG_HIP_TRY(hipGetLastError());
+    VLG_HIP_TRY(hipMemcpyAsync(h_cut.data(), d_cut, 2 * ns * 4, hipMemcpyDeviceToHost, st));
+    VLG_HIP_TRY(hipMemcpyAsync(cut.occ.data() + s0, d_occ, ns * 8, hipMemcpyDeviceToHost, st));
+    VLG_HIP_TRY(hipStreamSynchronize(st));
+    for (uint64_t s = 0; s < ns; ++s) { L.off[s0 + s] = cut.occ[s0 + s] ? h_cut[2 * s] : 0; logical += cut.occ[s0 + s]; }
+    return VLG_OK;
+}
+
+// A super-chunk of a batch with text windows (one rank): the lists are located and sorted whole, as without windows; then every
+// query's lists are cut to its window and the joins -- filter shapes, filter groups, join chunks, costs -- are planned over the cut
+// lengths, inside the arena as it is by then.  So a query whose full lists would not fit the join budget but whose window does is
+// answered, and VLG_E_WORKSPACE comes from the plan over the cut lengths alone.
+template <typename pos_t>
+vlg_status run_windowed_chunk(const vlg_index* idx, const vlg_queries* q, vlg_workspace* ws, vlg_result* res, const Plan& pl, const SuperChunk& sc,
+                              const ChunkPlan& cp, bool wide, uint64_t fixed, unsigned long long* d_stats, Lists<pos_t>& L, Plan& cut, PhaseTrace& tr)
+{
+    const uint64_t subs = q->qsub[sc.Q1] - q->qsub[sc.Q0], queries = sc.Q1 - sc.Q0;
+    if (!cp.launch_first) {
+        // The arena is sized before the lists exist, so by a plan over the FULL lengths -- which here only sizes the reservation:
+        // where it would refuse, the whole join budget is reserved, and the plan over the cut lengths decides.
+        JoinPlan full;
+        const std::string keep = vlg_last_error();
+        uint64_t join_bytes = cp.join_budget + join_meta_bytes(subs, queries, cp.join_budget);
+        if (plan_joins(q, pl, ws, sc.Q0, sc.Q1, cp.join_budget, idx->hdr.n, full) == VLG_OK) join_bytes = full.filter_need + full.want_bytes + full.meta;
+        else set_error(keep);
+        if (vlg_status s = ws_reserve(ws, cp.phys_bytes + join_bytes + fixed)) return s;
+    }
+    Arena A{ws->arena, ws->arena_bytes};
+    tr.mark("plan super-chunk");
+    if (vlg_status s = build_physical<pos_t>(idx, ws, res, pl, sc, cp, wide, A, d_stats, L)) return s;
+    tr.mark("locate + sort");
+    if (vlg_status s = cut_to_windows<pos_t>(idx, q, ws, pl, sc, L, A, cut, res->sum.logical_occurrences)) return s;
+    tr.mark("window cut");
+    // what the arena holds behind the lists, less the per-chunk metadata of a plan that takes all of it (48 B per 8192 B of scratch)
+    const uint64_t taken = cp.phys_bytes + fixed + join_meta_bytes(subs, queries, 0);
+    const uint64_t room = ws->arena_bytes > taken ? ws->arena_bytes - taken : 0;
+    JoinPlan jp;
+    if (vlg_status s = plan_joins(q, cut, ws, sc.Q0, sc.Q1, std::min<uint64_t>(cp.join_budget, room - room / 128), idx->hdr.n, jp)) return s;
+    return run_joins<pos_t>(idx->hdr.n, q, ws, res, cut, L, A, sc.Q0, sc.Q1, jp, d_stats, tr);
+}
+
 // A super-chunk = a run of queries whose distinct occurrence lists fit the physical budget; inside it
 // the queries are joined in chunks bounded by the logical budget.
 template <typename pos_t>
@@ -1900,6 +2025,10 @@ vlg_status run_batch(const vlg_index* idx, const vlg_queries* q, vlg_workspace* 
     L.off.assign(q->nsub, 0);
     uint32_t epoch = 0;
     PhaseTrace tr(ws->stream);
+    // the one branch of a batch with text windows: without them nothing below is launched, waited for or copied
+    const bool windows = q->has_windows();
+    Plan cut;
+    if (windows) res->sum.logical_occurrences = 0;      // (the plan counted the full lists: run_windowed_chunk adds the cut ones)
     for (uint64_t Q0 = 0; Q0 < q->nq;) {
         SuperChunk sc;
         if (vlg_status s = next_super_chunk(q, pl, ws->dedup, phys_cap, Q0, stamp, epoch, sc)) return s;
@@ -1910,6 +2039,11 @@ vlg_status run_batch(const vlg_index* idx, const vlg_queries* q, vlg_workspace* 
         if (ws->x_ranks > 1) { res->owned.push_back(qa); res->owned.push_back(qb); }
         Agreement ag(ws);
         JoinPlan jp;
+        if (windows) {
+            if (vlg_status s = run_windowed_chunk<pos_t>(idx, q, ws, res, pl, sc, cp, wide, fixed, d_stats, L, cut, tr)) return s;
+            Q0 = sc.Q1;
+            continue;
+        }
         if (!cp.launch_first) {
             if (vlg_status s = plan_joins(q, pl, ws, qa, qb, cp.join_budget, idx->hdr.n, jp)) { ag.mine = s; return s; }
             if (vlg_status s = ws_reserve(ws, cp.phys_bytes + jp.filter_need + jp.want_bytes + jp.meta + fixed)) { ag.mine = s; return s; }
@@ -2129,6 +2263,8 @@ extern "C" vlg_status vlg_search_batch(const vlg_index* idx, const vlg_queries* 
     *out = nullptr;
     if (!idx->is_int && q->sym_bytes != 1) return fail(VLG_E_INVALID, "integer-alphabet query batch: it takes an integer-alphabet index (vlg_index_build_int) or vlg_wtsa_*");
     if (idx->is_int && q->sym_bytes != 4 && q->nsub) return fail(VLG_E_INVALID, "an integer-alphabet index takes query batches parsed by vlg_queries_parse_int");
+    // (every rank holds the same batch and refuses alike, before anything is launched or exchanged: no rank waits for another)
+    if (q->has_windows() && ws->x_ranks > 1) return fail(VLG_E_UNSUPPORTED, "a collective search takes no text windows (vlg_queries_set_windows)");
     hipStream_t st = ws->stream;
     vlg_result* res = new_result(q->nq, q->qsub);
     uint64_t* d_l = nullptr;

@@ -15,4 +15,8 @@ struct vlg_queries {
     uint8_t* d_blob = nullptr;
     uint64_t* d_suboff = nullptr;
     uint64_t* d_qsub = nullptr;      // [nq+1] on the device (the interval plan groups sub-patterns by query)
+    // text windows (vlg_queries_set_windows): empty = the batch carries none; otherwise [nq] each, host only.  win_end holds the
+    // caller's values (UINT64_MAX = "to the end of the text"): the batch does not know n, the search clamps.
+    std::vector<uint64_t> win_begin, win_end;
+    bool has_windows() const { return !win_end.empty(); }
 };

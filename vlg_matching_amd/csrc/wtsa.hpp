@@ -656,6 +656,7 @@ extern "C" vlg_status vlg_wtsa_search_window_batch(const vlg_wtsa* x, const vlg_
 {
     if (!x || !q || !ws || !out) return fail(VLG_E_INVALID, "null argument");
     *out = nullptr;
+    if (q->has_windows()) return fail(VLG_E_INVALID, "the batch carries text windows (vlg_queries_set_windows): this search takes its windows as arrays");
     hipStream_t st = ws->stream;
     const uint64_t nq = q->nq, nsub = q->nsub;
     if (nq > 0xFFFFFFF0ull) return fail(VLG_E_UNSUPPORTED, "too many queries in one batch");

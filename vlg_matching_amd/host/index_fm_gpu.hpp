@@ -46,11 +46,13 @@ class index_fm_gpu
     }
     // one pass of the hot path over pats[b,e) on the current device; positions of query i go to out[i]
     static void search_range(const vlg_index* idx, vlg_workspace* ws, const std::vector<gapped_pattern>& pats, size_t b, size_t e, int dialect,
-                             std::vector<gapped_search_result>& out, vlg_result_summary* summary)
+                             std::vector<gapped_search_result>& out, vlg_result_summary* summary, const uint64_t* begins = nullptr,
+                             const uint64_t* ends = nullptr)
     {
         check(vlg_workspace_set_option(ws, "tuples", 0));        // gapped_search_result holds first positions only
         parsed_batch pb;
         parse(pats, b, e, dialect, pb);
+        if (begins || ends) check(vlg_queries_set_windows(pb.q, begins ? begins + b : nullptr, ends ? ends + b : nullptr));
         vlg_result* r = nullptr;
         check(vlg_search_batch(idx, pb.q, ws, &r));
         vlg_result_summary s;
@@ -174,6 +176,24 @@ class index_fm_gpu
         ensure_ws();
         std::vector<gapped_search_result> out(pats.size());
         search_range(m_idx, m_ws, pats, 0, pats.size(), dialect, out, summary);
+        return out;
+    }
+
+    // The same with a text window per pattern (vlg_queries_set_windows): pats[i] is answered on [begins[i], ends[i]) -- its matches are
+    // those on the stand-alone text T[begin, end), shifted by begin; an end beyond the text is clamped.  One entry per (pattern,
+    // document) pair answers a pattern set on every document of a collection, and every distinct occurrence list of the batch is
+    // still located once.  A window that begins behind its end throws.
+    std::vector<gapped_search_result> search_batch_windows(const std::vector<gapped_pattern>& pats, const std::vector<uint64_t>& begins,
+                                                           const std::vector<uint64_t>& ends, int dialect = VLG_DIALECT_BENCHMARK,
+                                                           vlg_result_summary* summary = nullptr) const
+    {
+        if (begins.size() != pats.size() || ends.size() != pats.size()) throw std::invalid_argument("search_batch_windows: one window per pattern expected");
+        for (size_t i = 0; i < pats.size(); ++i)
+            if (begins[i] > ends[i]) throw std::invalid_argument("search_batch_windows: the window of pattern " + std::to_string(i) + " begins behind its end");
+        ensure_ws();
+        std::vector<gapped_search_result> out(pats.size());
+        if (summary) memset(summary, 0, sizeof *summary);
+        if (!pats.empty()) search_range(m_idx, m_ws, pats, 0, pats.size(), dialect, out, summary, begins.data(), ends.data());
         return out;
     }
 

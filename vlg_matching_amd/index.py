@@ -366,6 +366,20 @@ class Queries:
         self.status = np.zeros(self.n, dtype=np.int32)
         return self
 
+    def set_windows(self, begin=None, end=None):
+        """Text windows of the batch (vlg_queries_set_windows): VlgIndex.search answers query j on [begin[j], end[j]) -- its matches
+        are those of the query on text[begin:end], shifted by begin.  A scalar for the whole batch or one value per query; None: from
+        0 / to the end of the text; both None removes the windows."""
+        b, e = _window_array(begin, self.n, "begin"), _window_array(end, self.n, "end")
+        check(lib().vlg_queries_set_windows(self._h, b.ctypes.data if b is not None else None, e.ctypes.data if e is not None else None))
+
+    def windows(self):
+        """-> (begin[], end[]) as they were set (an end of 2^64 - 1: to the end of the text), or None for a batch without windows"""
+        has = C.c_int(0)
+        b, e = np.zeros(max(self.n, 1), np.uint64), np.zeros(max(self.n, 1), np.uint64)
+        check(lib().vlg_queries_get_windows(self._h, C.byref(has), b.ctypes.data, e.ctypes.data))
+        return (b[: self.n], e[: self.n]) if has.value else None
+
     @property
     def ks(self):
         """sub-patterns per query (0 for a query that failed to parse)"""
@@ -638,12 +652,21 @@ class VlgIndex:
             self._ws = Workspace(max_hbm_bytes)
         return self._ws
 
-    def search(self, queries, dialect=capi.DIALECT_LIBRARY, workspace=None, strict=True):
-        """Batched `idx.search(pat)`: queries is a list of regexps or a Queries object."""
+    def search(self, queries, dialect=capi.DIALECT_LIBRARY, workspace=None, strict=True, begin=None, end=None):
+        """Batched `idx.search(pat)`: queries is a list of regexps or a Queries object.  begin / end: text windows for this call
+        (Queries.set_windows); the batch carries afterwards what it carried before."""
         q = self._queries(queries, dialect, strict)
         ws = workspace or self.workspace()
         h = C.c_void_p()
-        check(lib().vlg_search_batch(self._h, q._h, ws._h, C.byref(h)))
+        if begin is None and end is None:
+            check(lib().vlg_search_batch(self._h, q._h, ws._h, C.byref(h)))
+            return SearchResult(h, q.ks)
+        before = q.windows()
+        q.set_windows(begin, end)
+        try:
+            check(lib().vlg_search_batch(self._h, q._h, ws._h, C.byref(h)))
+        finally:
+            q.set_windows(*(before or (None, None)))
         return SearchResult(h, q.ks)
 
 
@@ -657,6 +680,21 @@ def _u64_index_array(a, name):
     if arr.dtype.kind == "i" and arr.size and int(arr.min()) < 0:
         raise ValueError("%s: negative value" % name)
     return np.ascontiguousarray(arr.reshape(-1), dtype=np.uint64)
+
+
+def _window_array(v, nq, name):
+    """begin / end of a windowed search: None, a scalar for every query, or one value per query -> uint64 array or None"""
+    if v is None:
+        return None
+    if np.ndim(v) == 0:
+        a = np.full(nq, int(v), dtype=np.uint64)
+    elif isinstance(v, np.ndarray):
+        a = _u64_index_array(v, name)
+    else:
+        a = np.array([int(x) for x in v], dtype=np.uint64)
+    if len(a) != nq:
+        raise ValueError("%s: one value per query expected (%d), got %d" % (name, nq, len(a)))
+    return a
 
 
 class TextAccess:
@@ -960,20 +998,6 @@ class WtsaIndex:
         check(lib().vlg_wtsa_ranges(self._h, q._h, sp.ctypes.data, ep.ctypes.data, None))
         return sp[:nsub], ep[:nsub]
 
-    def _window(self, v, nq, name):
-        """begin / end of search(): None, a scalar for every query, or one value per query -> uint64 array or None"""
-        if v is None:
-            return None
-        if np.ndim(v) == 0:
-            a = np.full(nq, int(v), dtype=np.uint64)
-        elif isinstance(v, np.ndarray):
-            a = _u64_index_array(v, name)
-        else:
-            a = np.array([int(x) for x in v], dtype=np.uint64)
-        if len(a) != nq:
-            raise ValueError("%s: one value per query expected (%d), got %d" % (name, nq, len(a)))
-        return a
-
     def search(self, queries, max_matches=0, workspace=None, begin=None, end=None):
         """sdsl::locate(idx, query) for a batch, lazily: at most max_matches matches per query (0 = all).  begin / end: the text window
         [begin, end) every query is answered on (a scalar for the whole batch or one value per query; None: from 0 / to the end of
@@ -983,7 +1007,7 @@ class WtsaIndex:
             if self._ws is None:
                 self._ws = Workspace()
             workspace = self._ws
-        b, e = self._window(begin, q.n, "begin"), self._window(end, q.n, "end")
+        b, e = _window_array(begin, q.n, "begin"), _window_array(end, q.n, "end")
         h = C.c_void_p()
         check(lib().vlg_wtsa_search_window_batch(self._h, q._h, b.ctypes.data if b is not None and len(b) else None,
                                                  e.ctypes.data if e is not None and len(e) else None, int(max_matches), workspace._h, C.byref(h)))
