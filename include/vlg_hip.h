@@ -411,6 +411,16 @@ vlg_status vlg_psi_batch(const vlg_select_support* s, const uint64_t* d_i, uint6
  * writes them; the sentinel and an i >= n give 0.  Both calls are asynchronous on `stream`. */
 vlg_status vlg_lf_batch(const vlg_index* idx, const uint64_t* d_i, uint64_t* d_out, uint64_t count, void* stream);
 vlg_status vlg_bwt_batch(const vlg_index* idx, const uint64_t* d_i, void* d_out, uint64_t count, void* stream);
+/* The quad image of a byte index with plain bit-vectors: the wavelet tree two levels per 32-byte read, derived on the device when the
+ * index is made and kept beside the blob in an allocation of its own (it is not part of the blob, of the exported parts or of a saved
+ * file: whoever attaches a blob derives its own).  The locate kernels walk LF on it (workspace option "quad_walk").  rrr and integer
+ * indexes, sigma = 1 and a tree in which a digit count would not fit 32 bits have none: bytes = 0, n_nodes = 0.  Its bytes are part of
+ * vlg_index_info.hbm_bytes.  Any of the three outputs may be null. */
+vlg_status vlg_index_quad_image(const vlg_index* idx, uint64_t* bytes, uint32_t* n_nodes, double* build_s);
+/* For tests: the LF step of vlg_lf_batch taken through the quad image.  d_lf[j] = LF(d_i[j]) (~0 for i >= n), d_comp[j] = the compact
+ * symbol read on the way, d_levels[j] = the binary tree levels the step accounts for (the symbol's code length); any output may be
+ * null.  VLG_E_UNSUPPORTED for an index without an image.  Runs on the null stream and returns when the results are there. */
+vlg_status vlg_quad_lf_batch(const vlg_index* idx, const uint64_t* d_i, uint64_t* d_lf, uint8_t* d_comp, uint32_t* d_levels, uint64_t count);
 
 /* ------------------------------------------------------------------------------------------
  * Query batches.  Parsing mirrors the reference's two dialects:
@@ -731,6 +741,9 @@ vlg_status vlg_workspace_profile(vlg_workspace* ws, int enable);
  * "trail" (default 1, needs "dedup"): inside a sorted sweep an occurrence that steps onto an SA index another occurrence
  * has visited stops there and takes that occurrence's position plus the distance (csa[i] = csa[LF(i)] + 1 shared between
  * lanes), so a batch walks every LF trail once; 0 = every occurrence walks to its own sample like csa_wt::operator[].
+ * "quad_walk" (default 1): the locate kernels walk LF on the quad image of an index that has one (vlg_index_quad_image) -- two tree
+ * levels per dependent read; 0 = the binary tree (an A/B inside one library).  Results do not depend on it, "lf_steps" and
+ * "wt_levels_locate" included.
  * "list_sort" (default 1): with 32-bit positions every occurrence list is sorted inside itself (short lists in LDS by value ranges;
  * long ones by two LSD radix passes over the top 16 position bits + one LDS pass over windows of whole groups; 2: four LSD passes
  * over all position bits, what lists with clustered positions take anyway); 0, or 64-bit positions: "global_sort_min" (default 2^20): from this many

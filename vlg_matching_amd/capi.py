@@ -154,6 +154,8 @@ SYMBOLS = [
     ("vlg_int_select_batch", _I, [_P, _P, _P, _P, _U64, _P]),
     ("vlg_psi_batch", _I, [_P, _P, _P, _U64, _P]),
     ("vlg_lf_batch", _I, [_P, _P, _P, _U64, _P]),
+    ("vlg_quad_lf_batch", _I, [_P, _P, _P, _P, _P, _U64]),
+    ("vlg_index_quad_image", _I, [_P, _P, _P, _P]),
     ("vlg_bwt_batch", _I, [_P, _P, _P, _U64, _P]),
     ("vlg_parse_query", _I, [C.c_char_p, _U64, _I, C.POINTER(ParsedQuery)]),
     ("vlg_queries_parse", _I, [C.c_char_p, _P, _U64, _I, _P, C.POINTER(_P)]),

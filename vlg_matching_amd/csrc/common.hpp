@@ -18,6 +18,9 @@
 //          text_order_sa_sampling (csa_sampling_strategy.hpp:127-246), SA[i] / d of the SA indices i with SA[i] % d == 0 in
 //          ascending i, plus [marked]: super-blocks {224 marks, ones before} over the SA indices -- is_sampled(i) and the rank
 //          that addresses the sample come out of ONE 32-byte read.
+//
+// Beside the blob, in an allocation of its own (vlg_index::quad): the quad image of a plain byte index -- [QNode x 256][QuadBlock ...],
+// the tree two levels per 32-byte read for the locate walks (quad_code.hpp has the layout).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -87,6 +90,11 @@ struct IndexView {
     const uint4* rrr_hdr;
     const uint64_t* rrr_stream;
     const struct RrrTables* rrr_tables;   // rrr_code.hpp
+    // the 4-ary image of the tree (quad_code.hpp; null = none: rrr bit-vectors, sigma = 1, a digit count beyond 32 bits).  It is not part
+    // of the blob: every index derives its own from `blocks` when it is made (index.hip: derive_quad_image)
+    const struct QuadBlock* qblocks;
+    const struct QNode* qnodes;
+    uint32_t n_qnodes;
 };
 
 // ---- FM-index of an integer text (int_index.hpp): its own blob, recognised by its magic -------------------------------------
@@ -287,6 +295,8 @@ struct vlg_index {
     bool is_int = false;  // integer-alphabet FM-index (int_index.hpp): ihdr / iview are valid, hdr carries the generic fields only
     vlg::IntHeader ihdr;
     vlg::IntView iview;
+    vlg::DevBuf quad;     // the quad image view.qnodes / view.qblocks point into (an allocation of its own, freed with the index)
+    double quad_build_s = 0;
 };
 
 namespace vlg {
@@ -300,6 +310,7 @@ using IndexPtr = Building<vlg_index, vlg_index_destroy>;
 // bit_vector_il<512>::m_data of the tree, both converted on the device and copied to the host
 vlg_status wtsa_text_words(const vlg_wtsa* idx, uint32_t& width, std::vector<uint64_t>& words);
 vlg_status wtsa_il_words(const vlg_wtsa* idx, std::vector<uint64_t>& words);
+vlg_status derive_quad_image(vlg_index* idx, hipStream_t stream);                 // index.hip: what every maker of a plain byte index ends with
 vlg_status attach_int_blob(const void* d_blob, uint64_t bytes, vlg_index* idx);   // int_index.hpp
 void layout_int_blob(IntHeader& h);                                               // int_index.hpp: offsets and total_bytes from the sizes
 }

@@ -1,6 +1,7 @@
 // Index objects in HBM: creation from reference-layout parts, export, blob replication, and the
 // on-device builder (suffix sort by prefix doubling -> BWT -> wavelet-tree super-blocks -> SA samples).
 #include <algorithm>
+#include <chrono>
 #include <cstdlib>
 #include <cstring>
 #include <string.h>
@@ -152,6 +153,74 @@ void bind_view(vlg_index* idx)
     idx->view.rrr_hdr = reinterpret_cast<const uint4*>(b + h.off_rrr_hdr);
     idx->view.rrr_stream = reinterpret_cast<const uint64_t*>(b + h.off_rrr_stream);
     idx->view.rrr_tables = reinterpret_cast<const RrrTables*>(b + h.off_binom);
+    idx->view.qblocks = nullptr;                     // (derive_quad_image, once the blocks are filled)
+    idx->view.qnodes = nullptr;
+    idx->view.n_qnodes = 0;
+}
+
+// ---- the quad image (quad_code.hpp), derived from the plain image ------------------------------------------------------------
+struct QuadTable {           // per quad node: its first quad block, the binary node it images and that node's two children
+    uint32_t count;
+    uint32_t base[kMaxQuadNodes];
+    uint32_t bin_base[kMaxQuadNodes];
+    uint32_t mid[kMaxQuadNodes][2];          // DNode child word: kLeafFlag | comp, or a node id
+    uint32_t mid_base[kMaxQuadNodes][2];     // first block of an inner child
+    uint64_t size[kMaxQuadNodes];
+};
+
+// (block indices are clamped to the image: a blob whose node table and bits disagree may ask for a position past a node's end)
+__device__ __forceinline__ uint32_t quad_src_bit(const Block* __restrict__ blocks, uint64_t n_blocks, uint32_t base, uint64_t p)
+{
+    uint32_t blk, off;
+    split224(p, blk, off);
+    const uint64_t b = (uint64_t)base + blk < n_blocks ? (uint64_t)base + blk : n_blocks - 1;
+    return (blocks[b].w[off >> 5] >> (off & 31u)) & 1u;
+}
+__device__ __forceinline__ uint64_t quad_src_rank1(const Block* __restrict__ blocks, uint64_t n_blocks, uint32_t base, uint64_t p)
+{
+    uint32_t blk, off;
+    split224(p, blk, off);
+    const uint64_t b = (uint64_t)base + blk < n_blocks ? (uint64_t)base + blk : n_blocks - 1;
+    return block_rank(load_block(blocks, (uint32_t)b), off);
+}
+
+// One thread per quad block.  Its three counts are rank_{b2}(child_{b1}, rank_{b1}(v, P)) at its first position P -- no scan -- and its
+// digits follow by stepping the two child positions along v's bits.
+__global__ void __launch_bounds__(256) quad_derive_kernel(const Block* __restrict__ blocks, uint64_t n_blocks, const QuadTable* __restrict__ tab,
+                                                          QuadBlock* __restrict__ out, uint64_t n_qblocks)
+{
+    __shared__ QuadTable t;
+    for (uint32_t i = threadIdx.x; i < sizeof(QuadTable) / 4; i += blockDim.x)
+        reinterpret_cast<uint32_t*>(&t)[i] = reinterpret_cast<const uint32_t*>(tab)[i];
+    __syncthreads();
+    for (uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; g < n_qblocks; g += (uint64_t)gridDim.x * blockDim.x) {
+        uint32_t lo = 0, hi = t.count;                         // last k with base[k] <= g
+        while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (t.base[mid] <= g) lo = mid; else hi = mid; }
+        const uint32_t k = lo;
+        const uint64_t P = (g - t.base[k]) * kQuadDigits, size = t.size[k];
+        const uint64_t r1 = quad_src_rank1(blocks, n_blocks, t.bin_base[k], P);
+        uint64_t pos0 = P - r1, pos1 = r1;                     // positions inside child[0], child[1]
+        const bool leaf0 = (t.mid[k][0] & kLeafFlag) != 0, leaf1 = (t.mid[k][1] & kLeafFlag) != 0;
+        const uint64_t r0 = leaf0 ? 0 : quad_src_rank1(blocks, n_blocks, t.mid_base[k][0], pos0);
+        const uint64_t r2 = leaf1 ? 0 : quad_src_rank1(blocks, n_blocks, t.mid_base[k][1], pos1);
+        uint32_t w[5] = {0, 0, 0, 0, 0};
+#pragma unroll
+        for (uint32_t j = 0; j < kQuadDigits; ++j) {
+            const uint64_t p = P + j;
+            if (p < size) {
+                const uint32_t b1 = quad_src_bit(blocks, n_blocks, t.bin_base[k], p);
+                const bool leaf = b1 ? leaf1 : leaf0;
+                const uint32_t b2 = leaf ? 0u : quad_src_bit(blocks, n_blocks, t.mid_base[k][b1], b1 ? pos1 : pos0);
+                pos0 += 1u - b1;
+                pos1 += b1;
+                w[j >> 4] |= (b1 << 1 | b2) << ((j & 15u) * 2u);
+            }
+        }
+        uint4* o = reinterpret_cast<uint4*>(out + g);
+        // digits 0, 1, 2 before P: zeros and ones of child[0] before P - r1, zeros of child[1] before r1
+        o[0] = make_uint4((uint32_t)(P - r1 - r0), (uint32_t)r0, (uint32_t)(r1 - r2), w[0]);
+        o[1] = make_uint4(w[1], w[2], w[3], w[4]);
+    }
 }
 
 // Section offsets and the total size from the counts in the header (sections in a fixed order, 256-byte aligned).
@@ -255,6 +324,50 @@ vlg_status check_device()
 
 }  // namespace
 
+// What every function that hands out a byte index with plain bit-vectors ends with: the quad image, derived on the device from the
+// binary image (so it does not matter how the index came to be), in an allocation the index owns.  None for rrr and integer indexes,
+// sigma = 1, and a tree where a digit count would not fit 32 bits: they walk the binary tree.
+vlg_status vlg::derive_quad_image(vlg_index* idx, hipStream_t stream)
+{
+    if (idx->is_int || idx->hdr.bv_kind != kBvPlain || idx->hdr.sigma < 2 || !idx->hdr.n_blocks) return VLG_OK;
+    const HostTree& t = idx->tree;
+    std::vector<uint64_t> leaf_count(t.sigma, 0);
+    for (uint32_t c = 0; c < t.sigma && c + 1 < t.C.size(); ++c) leaf_count[c] = t.C[c + 1] - t.C[c];
+    QuadPlan q;
+    if (!quad_collapse(t.dnodes.data(), t.node_size.data(), t.n_nodes, leaf_count.data(), q) || !q.fits) return VLG_OK;
+    const auto t0 = std::chrono::steady_clock::now();
+    std::unique_ptr<QuadTable> tab(new QuadTable());
+    tab->count = (uint32_t)q.nodes.size();
+    for (uint32_t k = 0; k < tab->count; ++k) {
+        const DNode& v = t.dnodes[q.bin[k]];
+        tab->base[k] = q.nodes[k].base;
+        tab->bin_base[k] = v.base;
+        tab->size[k] = q.size[k];
+        for (int b = 0; b < 2; ++b) {
+            tab->mid[k][b] = v.child[b];
+            tab->mid_base[k][b] = v.child[b] & kLeafFlag ? 0u : t.dnodes[v.child[b]].base;
+        }
+    }
+    const uint64_t node_bytes = (uint64_t)kMaxQuadNodes * sizeof(QNode);
+    DevBuf img, d_tab;
+    VLG_HIP_TRY(img.alloc(node_bytes + q.n_blocks * sizeof(QuadBlock)));
+    VLG_HIP_TRY(d_tab.alloc(sizeof(QuadTable)));
+    uint8_t* b = img.as<uint8_t>();
+    VLG_HIP_TRY(hipMemsetAsync(b, 0, node_bytes, stream));
+    VLG_HIP_TRY(hipMemcpyAsync(b, q.nodes.data(), q.nodes.size() * sizeof(QNode), hipMemcpyHostToDevice, stream));
+    VLG_HIP_TRY(hipMemcpyAsync(d_tab.p, tab.get(), sizeof(QuadTable), hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(quad_derive_kernel, launch_grid(q.n_blocks, 65536), dim3(256), 0, stream, idx->view.blocks, idx->hdr.n_blocks, d_tab.as<QuadTable>(),
+                       reinterpret_cast<QuadBlock*>(b + node_bytes), q.n_blocks);
+    VLG_HIP_TRY(hipGetLastError());
+    VLG_HIP_TRY(hipStreamSynchronize(stream));               // (the host sources above go out of scope)
+    idx->quad = std::move(img);
+    idx->view.qnodes = reinterpret_cast<const QNode*>(b);
+    idx->view.qblocks = reinterpret_cast<const QuadBlock*>(b + node_bytes);
+    idx->view.n_qnodes = (uint32_t)q.nodes.size();
+    idx->quad_build_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return VLG_OK;
+}
+
 extern "C" vlg_status vlg_device_count(int* n)
 {
     if (!n) return fail(VLG_E_INVALID, "null argument");
@@ -312,6 +425,7 @@ extern "C" vlg_status vlg_index_from_parts(const vlg_index_parts* p, vlg_index**
         if (vlg_status s2 = fill_block_counts(idx.get(), d_tab.as<InnerTable>(), stream)) return s2;
     }
     VLG_HIP_TRY(hipDeviceSynchronize());
+    if (vlg_status s2 = derive_quad_image(idx.get(), stream)) return s2;
     *out = idx.release();
     return VLG_OK;
 }
@@ -392,7 +506,7 @@ extern "C" vlg_status vlg_index_get_info(const vlg_index* idx, vlg_index_info* i
     info->wt_bits = h.wt_bits;
     info->n_blocks = h.n_blocks;
     info->n_samples = h.n_samples;
-    info->hbm_bytes = h.total_bytes;
+    info->hbm_bytes = h.total_bytes + (idx->view.qblocks ? idx->quad.cap : 0);       // the blob and the quad image beside it
     info->pos_bytes = h.sample_bytes;
     info->bv_kind = (uint32_t)h.bv_kind;
     info->sampling = h.sampling;
@@ -483,6 +597,7 @@ extern "C" vlg_status vlg_index_attach_blob(const void* d_blob, uint64_t bytes, 
     HostTree t2;
     if (vlg_status st = tree_from_nodes(nodes.data(), h.n_nodes, h.wt_bits, c2c, Cc.data(), h.sigma, t2)) return st;
     idx->tree = t2;
+    if (vlg_status st = derive_quad_image(idx.get(), nullptr)) return st;      // (not part of the blob: the receiving side derives its own)
     *out = idx.release();
     return VLG_OK;
 }
@@ -944,6 +1059,7 @@ extern "C" vlg_status vlg_index_resample(const vlg_index* src, int sampling, uin
     // (the new index keeps the source's sample width: 8 bytes when SA indices are wide -- n > 2^32, or VLG_FORCE_POS64)
     const vlg_status st = src->hdr.sample_bytes == 8 ? resample_run<uint64_t>(src, sampling, dens, idx.get(), stream) : resample_run<uint32_t>(src, sampling, dens, idx.get(), stream);
     if (st) return st;
+    if (vlg_status s2 = derive_quad_image(idx.get(), stream)) return s2;
     *out = idx.release();
     return VLG_OK;
 }
@@ -1298,7 +1414,10 @@ extern "C" vlg_status vlg_index_build_device(const uint8_t* d_text, uint64_t n_t
     *out = nullptr;
     if (vlg_status st = check_device()) return st;
     if (dens == 0) dens = 32;
-    return build_on_device(d_text, n_text, dens, (hipStream_t)stream, out);
+    if (vlg_status st = build_on_device(d_text, n_text, dens, (hipStream_t)stream, out)) return st;
+    // (after the builder's arrays have gone: the image is made at the index's own size)
+    if (vlg_status st = derive_quad_image(*out, (hipStream_t)stream)) { vlg_index_destroy(*out); *out = nullptr; return st; }
+    return VLG_OK;
 }
 
 extern "C" vlg_status vlg_index_build(const uint8_t* h_text, uint64_t n_text, uint32_t dens, vlg_index** out)

@@ -952,9 +952,9 @@ vlg_status launch_locate(const IndexView& iv, pos_t* d_io, uint64_t total, unsig
     const LocateSlices sl = locate_slices(total);
     if (iv.sample_bytes != sizeof(pos_t)) return fail(VLG_E_INTERNAL, "locate: sample width does not match the instantiation");
     constexpr bool kWide = sizeof(pos_t) == 8;
-    return on_bv(iv.bv_kind, [&](auto bv) { return on_flag(shape(iv).text_order, [&](auto to) {
+    return on_byte_walk<kWide>(iv, [&](auto walk) { return on_flag(shape(iv).text_order, [&](auto to) {
         // (in place: no words, no records -- the tail mode's parameters are empty)
-        return launch(locate_kernel<ByteWalk<tag_t<decltype(bv)>, kWide>, ByteSampling<kWide, decltype(to)::value>, pos_t, false, kWide>, dim3(sl.blocks), stream, iv, d_io,
+        return launch(locate_kernel<tag_t<decltype(walk)>, ByteSampling<kWide, decltype(to)::value>, pos_t, false, kWide>, dim3(sl.blocks), stream, iv, d_io,
                       total, sl.per_wave, d_stats, nullptr, 0u, nullptr, 0ull, nullptr);
     }); });
 }
@@ -1110,9 +1110,9 @@ vlg_status launch_locate_sweep(const IndexView& iv, const uint64_t* d_l, const u
                           n_pat, total, d_out);
         });
     }
-    return on_bv(iv.bv_kind, [&](auto bv) { return on_flag(text_order, [&](auto to) {
-        const SweepKernels K = bind_sweep<ByteWalk<tag_t<decltype(bv)>, kWide>, ByteSampling<kWide, decltype(to)::value>, pos_t, kWide>(iv, d_l, d_out_off, n_pat, d_stats, stream,
-                                                                                                                                  rec ? front : nullptr);
+    return on_byte_walk<kWide>(iv, [&](auto walk) { return on_flag(text_order, [&](auto to) {
+        const SweepKernels K = bind_sweep<tag_t<decltype(walk)>, ByteSampling<kWide, decltype(to)::value>, pos_t, kWide>(iv, d_l, d_out_off, n_pat, d_stats, stream,
+                                                                                                                   rec ? front : nullptr);
         return run_locate_sweep<pos_t, kWide>(K, d_l, d_out_off, n_pat, total, d_out, val_a, val_b, key_a, key_b, temp, temp_bytes, d_counter, tail_threshold, stream, timer,
                                               member, n_member_lists, rec, while_first_step);
     }); });
@@ -1849,4 +1849,48 @@ extern "C" vlg_status vlg_bwt_batch(const vlg_index* idx, const uint64_t* d_i, v
     if (!idx || (count && (!d_i || !d_out))) return fail(VLG_E_INVALID, "null argument");
     if (!count) return VLG_OK;
     return lf_bwt_batch(idx, d_i, nullptr, d_out, count, (hipStream_t)stream);
+}
+
+namespace {
+// LF through the quad walk, for tests: what QuadWalk::lf returns, reads and counts for every SA index of a batch
+template <bool kWide>
+__global__ void __launch_bounds__(256) quad_lf_kernel(IndexView iv, const uint64_t* __restrict__ in, uint64_t* __restrict__ out_lf, uint8_t* __restrict__ out_comp,
+                                                      uint32_t* __restrict__ out_levels, uint64_t count)
+{
+    __shared__ QuadLds s;
+    QuadWalk<kWide>::stage(s, iv);
+    const QuadWalk<kWide> walk{iv, s};
+    for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < count; j += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t i = in[j];
+        uint32_t c = 0, n_lv = 0;
+        const uint64_t r = i < iv.n ? walk.lf(i, c, n_lv) : ~0ull;
+        if (out_lf) out_lf[j] = r;
+        if (out_comp) out_comp[j] = (uint8_t)c;
+        if (out_levels) out_levels[j] = n_lv;
+    }
+}
+}  // namespace
+
+extern "C" vlg_status vlg_quad_lf_batch(const vlg_index* idx, const uint64_t* d_i, uint64_t* d_lf, uint8_t* d_comp, uint32_t* d_levels, uint64_t count)
+{
+    if (!idx || (count && !d_i)) return fail(VLG_E_INVALID, "null argument");
+    if (idx->is_int || !idx->view.qblocks) return fail(VLG_E_UNSUPPORTED, "the index has no quad image");
+    if (!count) return VLG_OK;
+    const IndexView& iv = idx->view;
+    const vlg_status s = on_flag(shape(iv).wide, [&](auto wide) {
+        return launch(quad_lf_kernel<decltype(wide)::value>, launch_grid(count, 8192), (hipStream_t) nullptr, iv, d_i, d_lf, d_comp, d_levels, count);
+    });
+    if (s) return s;
+    VLG_HIP_TRY(hipStreamSynchronize(nullptr));
+    return VLG_OK;
+}
+
+extern "C" vlg_status vlg_index_quad_image(const vlg_index* idx, uint64_t* bytes, uint32_t* n_nodes, double* build_s)
+{
+    if (!idx) return fail(VLG_E_INVALID, "null argument");
+    const bool have = !idx->is_int && idx->view.qblocks;
+    if (bytes) *bytes = have ? idx->quad.cap : 0;
+    if (n_nodes) *n_nodes = have ? idx->view.n_qnodes : 0;
+    if (build_s) *build_s = have ? idx->quad_build_s : 0.0;
+    return VLG_OK;
 }

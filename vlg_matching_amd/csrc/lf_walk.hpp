@@ -1,10 +1,11 @@
 // The LF step as a policy: LF(i) = C[c] + rank_c(i) with c = bwt[i] read on the way (suffix_array_helper.hpp:336-349), on the byte
-// index's Huffman-shaped tree (ByteWalk: inverse_select of wt_pc.hpp:385-402) and on the integer index's wavelet matrix (IntWalk:
-// wt_int.hpp:405-430 restated on the matrix, int_index.hpp).  Every kernel that walks LF -- the locate family (sweep_kernels.hpp), the
-// unsampling and ISA-sample walks, text access (extract.hpp) -- takes one of the two; a walk is written here and nowhere else.
+// index's Huffman-shaped tree (ByteWalk: inverse_select of wt_pc.hpp:385-402), on that tree's quad image (QuadWalk: two levels per
+// read, quad_code.hpp; the locate family only) and on the integer index's wavelet matrix (IntWalk: wt_int.hpp:405-430 restated on the
+// matrix, int_index.hpp).  Every kernel that walks LF -- the locate family (sweep_kernels.hpp), the unsampling and ISA-sample walks,
+// text access (extract.hpp) -- takes one of them; a walk is written here and nowhere else.
 //   View, Lds, stage(lds, view)   what the walk reads, its LDS block, and how a workgroup fills it (ends with a barrier)
 //   n(), sigma(), degenerate()    degenerate: only the sentinel exists (n = 1), there is nothing to walk and LF(0) = 0
-//   lf(i, c, n_lv)                one whole step: LF(i), c = the compact symbol read, n_lv += super-blocks read
+//   lf(i, c, n_lv)                one whole step: LF(i), c = the compact symbol read, n_lv += binary tree levels (super-blocks of the binary walk)
 //   lf(i, c)                      the same for text access: no count, and the degenerate index answered
 //   Cursor, level(k, i, c, n_lv)  the step one super-block read at a time, for the kernels whose lanes refill: i is the SA index while
 //                                 k.at_root(); a call that returns true has finished a step -- i = LF(i), c = the symbol, k at the root
@@ -12,6 +13,7 @@
 #pragma once
 #include <type_traits>
 #include "device_rank.hpp"
+#include "quad_code.hpp"
 
 namespace vlg {
 
@@ -76,6 +78,90 @@ struct ByteWalk {
             return true;
         }
         i = ni;
+        k.node = ch;
+        return false;
+    }
+
+    __device__ __forceinline__ uint8_t sym(uint32_t c) const { return c2c[c]; }
+};
+
+// The same step on the quad image of the tree (quad_code.hpp): one 32-byte read takes two binary levels -- the digit at the position and
+// the equal digits in front of it -- so a symbol of code length len costs ceil(len / 2) dependent reads instead of len.  n_lv still counts
+// BINARY levels, as the reference does: a digit adds 2, or 1 where its first bit ends in a leaf (kQuadOne), and a finished step has
+// added the symbol's code length.  The quad node table sits in LDS beside C (the same 10 KiB the binary walk stages).
+struct QuadLds {
+    QNode nodes[kMaxQuadNodes];
+    uint64_t C[257];
+};
+static_assert(kQuadLeaf == kLeafFlag, "a leaf child word reads the same in both node tables");
+template <bool kWide>
+struct QuadWalk {
+    using View = IndexView;
+    using Lds = QuadLds;
+    using walk_t = typename std::conditional<kWide, uint64_t, uint32_t>::type;      // node-relative positions: < n
+    static constexpr bool kPlainTree = false;                // (sweep_first_pair reads binary blocks itself)
+    static constexpr bool kStageLists = true;
+    const IndexView& iv;
+    const QuadLds& s;
+    const uint8_t* c2c = nullptr;
+    static __device__ __forceinline__ void stage(Lds& s, const View& iv)
+    {
+        for (uint32_t i = threadIdx.x; i < iv.n_qnodes; i += blockDim.x) s.nodes[i] = iv.qnodes[i];
+        for (uint32_t i = threadIdx.x; i <= iv.sigma; i += blockDim.x) s.C[i] = iv.C[i];
+        __syncthreads();
+    }
+    __device__ __forceinline__ uint64_t n() const { return iv.n; }
+    __device__ __forceinline__ uint32_t sigma() const { return iv.sigma; }
+    __device__ __forceinline__ bool degenerate() const { return iv.sigma == 1; }     // (such an index has no image; kept for the surface)
+
+    // one quad level from position pos of quad node v: -> the child word, pos = the position inside the child
+    template <typename P>
+    __device__ __forceinline__ uint32_t digit_step(uint32_t v, P& pos, uint32_t& n_lv) const
+    {
+        const P blk = pos / kQuadDigits;
+        const uint32_t off = (uint32_t)(pos - blk * kQuadDigits);
+        const uint4* p = reinterpret_cast<const uint4*>(iv.qblocks + ((uint64_t)s.nodes[v].base + blk));
+        const uint4 a = p[0], b = p[1];
+        uint32_t d;
+        pos = quad_rank_digit<P>(a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, blk * kQuadDigits, off, d);
+        const uint32_t ch = s.nodes[v].child[d];
+        n_lv += 2u - ((ch >> 30) & 1u);
+        return ch;
+    }
+
+    __device__ __forceinline__ uint64_t lf(uint64_t i, uint32_t& c, uint32_t& n_lv) const
+    {
+        uint32_t v = 0;
+        walk_t pos = (walk_t)i;
+        for (;;) {
+            const uint32_t ch = digit_step(v, pos, n_lv);
+            if (ch & kQuadLeaf) { c = ch & ~(kQuadLeaf | kQuadOne); break; }
+            v = ch;
+        }
+        return s.C[c] + (uint64_t)pos;                       // LF: suffix_array_helper.hpp:341-348
+    }
+    __device__ __forceinline__ uint64_t lf(uint64_t i, uint32_t& c) const
+    {
+        if (degenerate()) { c = 0; return 0; }
+        uint32_t n_lv = 0;
+        return lf(i, c, n_lv);
+    }
+
+    struct Cursor {
+        uint32_t node = 0;
+        __device__ __forceinline__ bool at_root() const { return node == 0; }
+    };
+    __device__ __forceinline__ bool level(Cursor& k, uint64_t& i, uint32_t& c, uint32_t& n_lv) const
+    {
+        walk_t pos = (walk_t)i;
+        const uint32_t ch = digit_step(k.node, pos, n_lv);
+        if (ch & kQuadLeaf) {                                // reached the symbol: LF = C[c] + rank
+            c = ch & ~(kQuadLeaf | kQuadOne);
+            i = s.C[c] + (uint64_t)pos;
+            k.node = 0;
+            return true;
+        }
+        i = pos;
         k.node = ch;
         return false;
     }

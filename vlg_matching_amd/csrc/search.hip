@@ -36,6 +36,7 @@ using namespace vlg;
 #include "search_types.hpp"
 #include "filter_shape.hpp"
 #include "window_cut.hpp"
+#include "shape_dispatch.hpp"
 
 // =============================================================================================
 // Workspace
@@ -75,6 +76,9 @@ struct vlg_workspace {
     uint32_t pivot_rungs = 1;   // the pivot filter searches through the ladder (join_device.hpp): 0 never (fences + bisection), 1 when it pays, 2 always
     int list_sort = 1;          // 32-bit positions: every list sorted inside itself (list_sort.hpp; 2: without the window passes); 0: the two rocPRIM paths below
     uint64_t global_sort_min = 1ull << 20;  // at least this many occurrences: all lists are sorted by one radix sort of (list, position) keys
+    bool quad_walk = true;      // locate walks LF on the quad image of an index that has one (lf_walk.hpp: QuadWalk); 0 = the binary walk, for an
+                                // A/B inside one library.  Wide SA indices too: round 0 of their sweep then takes its elements one by one instead of
+                                // in the binary pairs of sweep_first_pair, and still wins (C4, ms per batch: locate 95.4 -> 85.9, batch 353.5 -> 342.6)
     uint64_t sweep_min = 1ull << 22;    // below this many occurrences the persistent random-access kernel is used
     uint64_t sweep_tail = 1ull << 22;   // stragglers of a sweep are finished one lane each (C3, ms per batch: 2^20 214.0, 2^22 213.4, 2^24 213.7, 2^26 213.8)
     // K3u (kernels.hip): a batch that locates at least unsample_pct per cent of all text positions rebuilds the whole suffix array from
@@ -259,6 +263,7 @@ extern "C" vlg_status vlg_workspace_set_option(vlg_workspace* ws, const char* na
     if (!strcmp(name, "global_sort_min")) { ws->global_sort_min = (uint64_t)value; return VLG_OK; }
     if (!strcmp(name, "list_sort")) { ws->list_sort = value > 2 ? 1 : (int)value; return VLG_OK; }
     if (!strcmp(name, "trail")) { ws->trail = value != 0; return VLG_OK; }
+    if (!strcmp(name, "quad_walk")) { ws->quad_walk = value != 0; return VLG_OK; }
     if (!strcmp(name, "tuples")) { ws->tuples = value != 0; return VLG_OK; }
     if (!strcmp(name, "filter")) { ws->filter = value != 0; return VLG_OK; }
     if (!strcmp(name, "filter_min")) { ws->filter_min = (uint64_t)value; return VLG_OK; }
@@ -973,6 +978,8 @@ struct PhysicalPass {
         if (!acc) return VLG_OK;
         const uint64_t n_walkers = idx->is_int ? 0 : idx->view.n_samples;
         vlg_status s = VLG_OK;
+        // the view the locate kernels walk: with the quad image or without it (shape_dispatch.hpp: on_byte_walk)
+        const IndexView lview = ws->quad_walk ? idx->view : without_quad(idx->view);
         if (c.locate == VLG_LOCATE_UNSAMPLE) {
             // K3u: the whole suffix array from the samples, inside the sweep's scratch (n x 4 B + 20 B per sample <= 20 B per occurrence)
             uint32_t* sa_full = reinterpret_cast<uint32_t*>(scratch);
@@ -1005,10 +1012,10 @@ struct PhysicalPass {
                                                 &timer, member, n_member_lists, rec, &hook);
                 else s = fail(VLG_E_INTERNAL, "integer-alphabet index with 64-bit positions");
             } else if (wide)
-                s = launch_locate_sweep<pos_t, true>(idx->view, d_lh, d_off64, nd, acc, Pa, val_a, val_b, key_a, key_b, d_tmp, cp.sort_tmp, d_counter, d_stats,
+                s = launch_locate_sweep<pos_t, true>(lview, d_lh, d_off64, nd, acc, Pa, val_a, val_b, key_a, key_b, d_tmp, cp.sort_tmp, d_counter, d_stats,
                                                      ws->sweep_tail, st, &timer, member, n_member_lists, rec, &hook, front);
             else if constexpr (sizeof(pos_t) == 4)                      // (a 64-bit position type always comes with wide indices)
-                s = launch_locate_sweep<uint32_t, false>(idx->view, d_lh, d_off64, nd, acc, Pa, val_a, val_b, key_a, key_b, d_tmp, cp.sort_tmp, d_counter, d_stats,
+                s = launch_locate_sweep<uint32_t, false>(lview, d_lh, d_off64, nd, acc, Pa, val_a, val_b, key_a, key_b, d_tmp, cp.sort_tmp, d_counter, d_stats,
                                                          ws->sweep_tail, st, &timer, member, n_member_lists, rec, &hook, front);
             else s = fail(VLG_E_INTERNAL, "64-bit positions with 32-bit SA indices");
             if (!s) bt.mark("  physical: sweep");
@@ -1029,8 +1036,8 @@ struct PhysicalPass {
                     s = launch_int_locate(idx->iview, Pa, acc, d_stats, st);
                 }
             } else s = fail(VLG_E_INTERNAL, "integer-alphabet index with 64-bit positions");
-        } else if (wide && sizeof(pos_t) == 4) s = walks(reinterpret_cast<uint64_t*>(scratch));   // 33-bit SA indices: 64-bit words of the scratch
-        else s = walks(Pa);
+        } else if (wide && sizeof(pos_t) == 4) s = walks(reinterpret_cast<uint64_t*>(scratch), lview);   // 33-bit SA indices: 64-bit words of the scratch
+        else s = walks(Pa, lview);
         if (s) return s;
         ws->sample_reads += c.locate == VLG_LOCATE_UNSAMPLE ? n_walkers : acc;
         res->sum.locate_mode = c.locate;
@@ -1039,7 +1046,7 @@ struct PhysicalPass {
 
     // few occurrences: one walk per occurrence in place, in words of word_t -- narrowed into Pa when they are wider than a position
     template <typename word_t>
-    vlg_status walks(word_t* io)
+    vlg_status walks(word_t* io, const IndexView& lview)
     {
         if (vlg_status s = plan_sort()) return s;
         {
@@ -1047,7 +1054,7 @@ struct PhysicalPass {
             if (vlg_status s = launch_expand<word_t>(d_lh, d_off64, nd, acc, io, nullptr, st)) return s;
         }
         Timed t(ws, KS_LOCATE, 0);
-        if (vlg_status s = launch_locate<word_t>(idx->view, io, acc, d_stats, st)) return s;
+        if (vlg_status s = launch_locate<word_t>(lview, io, acc, d_stats, st)) return s;
         if constexpr (sizeof(word_t) != sizeof(pos_t)) return launch_narrow<pos_t>(io, Pa, acc, st);
         return VLG_OK;
     }

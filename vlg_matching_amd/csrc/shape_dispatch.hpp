@@ -6,7 +6,7 @@
 // how a site nests its calls.
 #pragma once
 #include <type_traits>
-#include "device_rank.hpp"
+#include "lf_walk.hpp"
 
 namespace vlg {
 
@@ -16,6 +16,15 @@ template <class Tag> using tag_t = typename Tag::type;
 
 template <class F> auto on_bv(uint32_t bv_kind, F&& f) { return bv_kind == kBvRrr63 ? f(type_tag<RrrBV>{}) : f(type_tag<PlainBV>{}); }
 template <class F> auto on_flag(bool b, F&& f) { return b ? f(flag_tag<true>{}) : f(flag_tag<false>{}); }
+
+// the LF walk of the locate family on a byte index (Walk): the quad image where the view carries one, the binary tree otherwise.  A
+// caller that wants the binary walk on an index with an image passes a view without it (without_quad)
+template <bool kWide, class F> auto on_byte_walk(const IndexView& iv, F&& f)
+{
+    if (iv.qblocks && iv.bv_kind == kBvPlain) return f(type_tag<QuadWalk<kWide>>{});
+    return on_bv(iv.bv_kind, [&](auto bv) { return f(type_tag<ByteWalk<tag_t<decltype(bv)>, kWide>>{}); });
+}
+inline IndexView without_quad(IndexView iv) { iv.qblocks = nullptr; iv.qnodes = nullptr; iv.n_qnodes = 0; return iv; }
 
 // byte text access (kWide, isa_t): ISA samples are 8 bytes wide from n = 2^32 on, and SA indices are wide there too
 template <class F> auto on_text_access_shape(bool wide, uint32_t isa_bytes, F&& f)

@@ -565,6 +565,16 @@ class VlgIndex:
         check(lib().vlg_index_get_info(self._h, C.byref(i)))
         return {k: int(getattr(i, k)) for k, _ in capi.IndexInfo._fields_}
 
+    def quad_image(self):
+        """The quad image beside the blob (vlg_index_quad_image): {"bytes", "n_nodes", "build_s"}; all zero where the index has none"""
+        b, nn, s = C.c_uint64(0), C.c_uint32(0), C.c_double(0)
+        check(lib().vlg_index_quad_image(self._h, C.byref(b), C.byref(nn), C.byref(s)))
+        return {"bytes": int(b.value), "n_nodes": int(nn.value), "build_s": float(s.value)}
+
+    def quad_lf_device(self, d_i_ptr, d_lf_ptr, d_comp_ptr, d_levels_ptr, count):
+        """vlg_quad_lf_batch on device pointers (uint64 LF, uint8 compact symbols, uint32 levels; any output may be None); synchronous"""
+        check(lib().vlg_quad_lf_batch(self._h, d_i_ptr, d_lf_ptr, d_comp_ptr, d_levels_ptr, int(count)))
+
     def compress(self, bv_kind=1):
         """A csa_wt<wt_huff<rrr_vector<63>>>-equivalent of this (plain) index (wt_int<rrr_vector<63>> for an integer index); same answers, compressed bit-vectors."""
         h = C.c_void_p()
