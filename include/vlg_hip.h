@@ -494,6 +494,49 @@ vlg_status vlg_queries_set_windows(vlg_queries* q, const uint64_t* h_begin, cons
 vlg_status vlg_queries_get_windows(const vlg_queries* q, int* has_windows, uint64_t* h_begin, uint64_t* h_end);
 void vlg_queries_destroy(vlg_queries* q);
 
+/* Character classes: a position of a sub-pattern may accept a SET of bytes -- PROSITE motifs (C-x(2,4)-C-x(3)-[LIVMFYWC] is
+ * "C.{2,4}?C.{3,3}?[LIVMFYWC]"), IUPAC codes (R = [AG]), case-insensitive words ([Tt]he).  Expanding such a query into one query per
+ * member string gives other answers: the left-most, lazy, non-overlapping rule applies to the UNION of the alternatives' occurrences.
+ * Syntax: the library dialect (s0.{a,b}?s1..., the same gap rules and errors) where, inside a sub-pattern and read left to right,
+ *   [ ... ]   is ONE position that accepts the bytes listed: single bytes and ranges x-y (x > y: VLG_E_PARSE; a '-' right behind '[',
+ *             '[^' or in front of ']' is itself); a leading ^ complements the set over the bytes 1..255; ".{" inside a class is two members
+ *   \x        is the byte x, inside and outside a class (\[ \] \\ \. \- \^); a lone \ at the end is VLG_E_PARSE
+ *   [], [^] and a class without its ] are VLG_E_PARSE.  The 0 byte is never a member: complements leave it out, a class that names it is
+ *   VLG_E_INVALID (so is a complement that accepts nothing).  At most VLG_MAX_SUBPATTERNS sub-patterns, none empty (VLG_E_INVALID).
+ * A sub-pattern's length m is its number of POSITIONS; lo / hi / end_len follow from m as the library dialect derives them from byte
+ * lengths.  vlg_parse_query / vlg_queries_parse are not touched: '[' and '\' stay literal bytes there.
+ *   vlg_parse_class_query  host only, no device.  `out` as for vlg_parse_query with sub_len in positions and sub_off = the first
+ *     position of the sub-pattern in the mask array; h_masks (room for cap_positions positions, VLG_E_INVALID when too small; NULL only
+ *     counts) receives 32 bytes per position, bit c (byte c / 8, bit c % 8) = byte c is accepted; *n_positions (optional) = positions.
+ *   vlg_queries_parse_classes  the batch form, with the per-query status contract of vlg_queries_parse.
+ *   vlg_queries_create_classes  the already-parsed form, as vlg_queries_create with mask rows for bytes (h_suboff counts positions) and
+ *     the same validity rules; a position that accepts no byte, or several with the 0 byte among them, is VLG_E_INVALID.
+ * A batch in which every position accepts exactly one byte HAS no classes: it is the batch vlg_queries_parse / vlg_queries_create make
+ * of the same strings, and every entry point treats it so.
+ * vlg_search_batch answers a batch with classes on a byte index (plain or rrr, either sampling, any density, n <= 2^32 + 1; a longer
+ * text: VLG_E_UNSUPPORTED): every distinct sub-pattern is searched once -- one with a class by a backward search that branches over the
+ * members the text has and keeps a frontier of pairwise disjoint SA intervals, one per member string that occurs -- its intervals are
+ * located into ONE list, sorted, and the lists are joined as ever; "tuples", the window filter and the workspace cap keep their
+ * meaning.  The frontier of a sub-pattern holds at most "class_intervals" intervals (vlg_workspace_set_option, default 1024, 1 .. 2^20)
+ * at any step; one that would pass it makes the search return VLG_E_WORKSPACE, naming the query, the sub-pattern and the option, with
+ * nothing written beyond the cap and nothing further launched (exactly that many is legal).
+ * Summary of such a search: located_occurrences = sum of the distinct lists' lengths, logical_occurrences = sum of the list lengths of
+ * the live queries, lf_steps / wt_levels_locate from the walks, wt_levels_bsearch over both backward searches, locate_mode =
+ * VLG_LOCATE_WALKS (the lists are always located by random-access walks here); everything else as for any batch.
+ * Out of scope, refused with VLG_E_UNSUPPORTED before any launch when the batch has classes: text windows (vlg_queries_set_windows),
+ * collective searches, integer-alphabet indexes, vlg_queries_occurrences, vlg_queries_intervals, vlg_wtsa_ranges, vlg_wtsa_search_batch
+ * and vlg_wtsa_search_window_batch.  The benchmark dialect has no class form. */
+vlg_status vlg_parse_class_query(const char* h_regexp, uint64_t len, vlg_parsed_query* out, uint8_t* h_masks, uint64_t cap_positions,
+                                 uint64_t* n_positions);
+vlg_status vlg_queries_parse_classes(const char* h_text, const uint64_t* h_off, uint64_t n_queries, int* h_status, vlg_queries** out);
+vlg_status vlg_queries_create_classes(const uint8_t* h_masks, const uint64_t* h_suboff, const uint64_t* h_qsub, const uint64_t* h_lo,
+                                      const uint64_t* h_hi, const uint64_t* h_end_len, uint64_t n_queries, vlg_queries** out);
+/* The SA intervals of every sub-pattern of a batch with classes, from a host copy the result of its vlg_search_batch keeps:
+ * sub-pattern s (batch order) has the intervals [h_l[j], h_r[j]], h_ivoff[s] <= j < h_ivoff[s + 1], ascending by l and pairwise
+ * disjoint (a literal sub-pattern has one, or none).  h_ivoff has vlg_queries_subpatterns(q) + 1 entries; h_l / h_r may be NULL to
+ * fetch the offsets alone.  A result of any other search gives VLG_E_INVALID. */
+vlg_status vlg_result_class_intervals(const vlg_result* r, uint64_t* h_ivoff, uint64_t* h_l, uint64_t* h_r);
+
 /* ------------------------------------------------------------------------------------------
  * Workspace, fused search, results.
  * ---------------------------------------------------------------------------------------- */
@@ -758,6 +801,9 @@ vlg_status vlg_workspace_profile(vlg_workspace* ws, int enable);
  * together are at least this many times longer than that; 0 = always bits.  Below 64 the ranges are the larger state (by up to
  * 68 / ratio), which counts against "filter_group_bytes": ratios below 8 are meant for tests;
  * "filter_group_bytes" (default 0 = a third of the join scratch) caps the filter state of the queries filtered together.
+ * "class_intervals" (default 1024; 1 .. 2^20): SA intervals the frontier of one sub-pattern with character classes may hold at any step
+ * of its backward search (32 bytes of scratch per interval and sub-pattern of a group; the sub-patterns of a batch are searched in groups
+ * of 64 MiB of such scratch).  A frontier that would pass it: VLG_E_WORKSPACE (see vlg_queries_parse_classes).
  * "reserve" = bytes of scratch to allocate right away (at most the workspace's cap) instead of on first use.
  * "tuples" (default 1): materialise every sub-pattern position of every match (what sdsl::locate returns); 0 = first
  * positions only, which is all the benchmark's gapped_search_result holds (index_sasearch.hpp:58-118): n_tuple_values

@@ -160,6 +160,10 @@ SYMBOLS = [
     ("vlg_parse_query", _I, [C.c_char_p, _U64, _I, C.POINTER(ParsedQuery)]),
     ("vlg_queries_parse", _I, [C.c_char_p, _P, _U64, _I, _P, C.POINTER(_P)]),
     ("vlg_queries_create", _I, [_P, _P, _P, _P, _P, _P, _U64, C.POINTER(_P)]),
+    ("vlg_parse_class_query", _I, [C.c_char_p, _U64, C.POINTER(ParsedQuery), _P, _U64, C.POINTER(_U64)]),
+    ("vlg_queries_parse_classes", _I, [C.c_char_p, _P, _U64, _P, C.POINTER(_P)]),
+    ("vlg_queries_create_classes", _I, [_P, _P, _P, _P, _P, _P, _U64, C.POINTER(_P)]),
+    ("vlg_result_class_intervals", _I, [_P, _P, _P, _P]),
     ("vlg_queries_occurrences", _I, [_P, _P, _P, _P]),
     ("vlg_queries_intervals", _I, [_P, _P, _P, _P, _P]),
     ("vlg_queries_count", _U64, [_P]),

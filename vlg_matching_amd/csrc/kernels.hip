@@ -402,6 +402,87 @@ __global__ void __launch_bounds__(256) backward_search_kernel(IndexView iv, cons
     }
 }
 
+// K2c: backward search of sub-patterns whose positions are SETS of bytes (character classes).  One wavefront per sub-pattern.  The
+// frontier -- the SA intervals of the member strings of S_t ... S_{m-1} that occur -- ping-pongs between two halves of `cap` intervals
+// in global scratch: half h of task t is frontier[(h * n_tasks + t) * cap ...].  A step deals the (symbol, parent interval) pairs to
+// the lanes symbol-major, parent-minor -- the new left borders then ascend (C[c] dominates; within one c the rank is monotone in the
+// parent's l), so the frontier stays sorted by l without a sort -- takes the two ranks of backward_search_kernel per pair, and
+// compacts the non-empty results with a ballot and a popcount prefix.  The result ends in half 0; count[t] = its intervals, or
+// kClassSearchOverflow when a step would have kept more than `cap` (nothing is written past the cap; exactly `cap` is legal).
+// task[2 t] = first mask row of the sub-pattern (32 bytes per position, bit c = byte c), task[2 t + 1] = its positions.
+template <class BV>
+__global__ void __launch_bounds__(256) class_search_kernel(IndexView iv, const uint8_t* __restrict__ masks, const uint64_t* __restrict__ task,
+                                                           uint64_t n_tasks, uint32_t cap, ulonglong2* frontier, uint32_t* __restrict__ count,
+                                                           unsigned long long* __restrict__ stat_levels)
+{
+    __shared__ WalkLds<BV> s;
+    __shared__ uint8_t syms[4][256];                       // per wave: the members of the step's class that the text has, ascending
+    stage_walk(s, iv);
+    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    uint32_t levels = 0;
+    for (uint64_t t = (uint64_t)blockIdx.x * 4 + wv; t < n_tasks; t += (uint64_t)gridDim.x * 4) {
+        const uint64_t pos0 = task[2 * t];
+        const uint32_t m = (uint32_t)task[2 * t + 1];
+        ulonglong2* const half[2] = {frontier + t * cap, frontier + (n_tasks + t) * cap};
+        uint32_t cur = 0, cnt = 1;                         // before the first step: the whole range, which is not stored
+        bool whole = true, over = false;
+        for (uint32_t p = m; p-- > 0 && cnt && !over;) {
+            const uint8_t* row = masks + (pos0 + p) * 32;
+            uint32_t nsym = 0;
+#pragma unroll
+            for (uint32_t j = 0; j < 4; ++j) {
+                const uint32_t c = 64 * j + lane;
+                const bool on = c > 0 && ((row[c >> 3] >> (c & 7)) & 1u) && iv.char2comp[c] != 0;
+                const unsigned long long b = __ballot(on);
+                if (on) syms[wv][nsym + (uint32_t)__popcll(b & below)] = (uint8_t)c;
+                nsym += (uint32_t)__popcll(b);
+            }
+            // (the list is read by other lanes of this wave than wrote it)
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            const ulonglong2* src = half[cur];
+            ulonglong2* dst = half[cur ^ 1];
+            const uint32_t total = nsym * cnt;             // (cap <= 2^20: fits)
+            uint32_t out = 0;
+            for (uint32_t base = 0; base < total && !over; base += 64) {
+                const uint32_t i = base + lane;
+                bool keep = false;
+                uint64_t nl = 0, nr = 0;
+                if (i < total) {
+                    const uint32_t si = i / cnt, pi = i - si * cnt;
+                    const uint8_t c = syms[wv][si];
+                    const uint32_t cc = iv.char2comp[c];
+                    const uint64_t c_begin = s.C[cc];
+                    uint64_t l = 0, r = iv.n - 1;
+                    if (!whole) { const ulonglong2 par = src[pi]; l = par.x; r = par.y; }
+                    if (l == 0 && r + 1 == iv.n) { nl = c_begin; nr = s.C[cc + 1] - 1; keep = s.C[cc + 1] > c_begin; }      // as backward_search_kernel
+                    else {
+                        const uint64_t path = iv.paths[c];
+                        const uint64_t a = wt_rank_dev(iv, s, path, l, levels), b = wt_rank_dev(iv, s, path, r + 1, levels);
+                        nl = c_begin + a; nr = c_begin + b - 1; keep = b > a;
+                    }
+                }
+                const unsigned long long kb = __ballot(keep);
+                const uint32_t at = out + (uint32_t)__popcll(kb & below);
+                out += (uint32_t)__popcll(kb);
+                if (out > cap) over = true;                // (wave-uniform) this turn would pass the cap: none of its lanes writes
+                else if (keep) dst[at] = make_ulonglong2(nl, nr);
+            }
+            cnt = out; cur ^= 1; whole = false;
+            __threadfence();                               // the next step's lanes read what other lanes wrote
+        }
+        if (!over && cnt && cur == 1) for (uint32_t i = lane; i < cnt; i += 64) half[0][i] = half[1][i];
+        if (lane == 0) count[t] = over ? kClassSearchOverflow : cnt;
+    }
+    if (stat_levels) {
+        unsigned long long tl = levels;
+        for (int o = 32; o > 0; o >>= 1) tl += __shfl_down(tl, o);
+        if ((threadIdx.x & 63) == 0 && tl) atomicAdd(stat_levels, tl);
+    }
+}
+
 // ---- member bit-vector: which SA indices are elements of the batch, and which (sweep_element explains what for) ----------------
 // bit i = one of the lists [l[d], l[d] + off[d + 1] - off[d]), d < n_lists, holds SA index i; the lists are pairwise disjoint and
 // ascend, and list d owns the slots [off[d], off[d + 1]) -- so the number of set bits before i IS the slot of index i.  Same 256-bit
@@ -929,6 +1010,19 @@ vlg_status launch_backward_search(const IndexView& iv, const uint8_t* d_blob, co
     if (!n_pat) return VLG_OK;
     return on_bv(iv.bv_kind, [&](auto bv) {
         return launch(backward_search_kernel<tag_t<decltype(bv)>>, launch_grid(n_pat, 4096), stream, iv, d_blob, d_off, n_pat, d_l, d_r, d_stat_levels);
+    });
+}
+
+vlg_status launch_class_search(const IndexView& iv, const uint8_t* d_masks, const uint64_t* d_task, uint64_t n_tasks, uint32_t cap, uint64_t* d_frontier,
+                               uint32_t* d_count, unsigned long long* d_stat_levels, hipStream_t stream)
+{
+    if (!n_tasks) return VLG_OK;
+    if (!cap || cap > kClassIntervalsMax) return fail(VLG_E_INTERNAL, "class search: frontier cap out of range");
+    // one wave per task, four to a workgroup; enough workgroups to fill the device, the rest of the tasks in turns
+    const dim3 grid((uint32_t)std::min<uint64_t>((n_tasks + 3) / 4, 16384));
+    return on_bv(iv.bv_kind, [&](auto bv) {
+        return launch(class_search_kernel<tag_t<decltype(bv)>>, grid, stream, iv, d_masks, d_task, n_tasks, cap, reinterpret_cast<ulonglong2*>(d_frontier), d_count,
+                      d_stat_levels);
     });
 }
 

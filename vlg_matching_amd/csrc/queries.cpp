@@ -8,6 +8,7 @@
 #include <vector>
 #include "common.hpp"
 #include "search_types.hpp"
+#include "class_query.hpp"
 
 using namespace vlg;
 
@@ -407,6 +408,124 @@ extern "C" vlg_status vlg_queries_create(const uint8_t* h_blob, const uint64_t* 
     return VLG_OK;
 }
 
+// =============================================================================================
+// Character classes (class_query.hpp): a position of a sub-pattern is a set of bytes
+// =============================================================================================
+namespace {
+// The mask rows beside the blob.  A batch in which every position accepts one byte keeps none: it IS the byte batch of the same strings.
+vlg_status attach_masks(vlg_queries* q, std::vector<uint8_t>& masks)
+{
+    q->sub_literal.assign(q->nsub, 1);
+    bool any = false;
+    for (uint64_t s = 0; s < q->nsub; ++s)
+        for (uint64_t p = q->suboff[s]; p < q->suboff[s + 1]; ++p)
+            if (byteset_count(masks.data() + p * 32) != 1) { q->sub_literal[s] = 0; any = true; }
+    if (!any) { q->sub_literal.clear(); return VLG_OK; }
+    q->masks.swap(masks);
+    VLG_HIP_TRY(hipMalloc((void**)&q->d_masks, q->masks.size() + 32));
+    VLG_HIP_TRY(hipMemcpy(q->d_masks, q->masks.data(), q->masks.size(), hipMemcpyHostToDevice));
+    return VLG_OK;
+}
+}  // namespace
+
+extern "C" vlg_status vlg_parse_class_query(const char* re, uint64_t len, vlg_parsed_query* out, uint8_t* h_masks, uint64_t cap_positions,
+                                            uint64_t* n_positions)
+{
+    if (!out || (len && !re)) return fail(VLG_E_INVALID, "null argument");
+    memset(out, 0, sizeof *out);
+    if (n_positions) *n_positions = 0;
+    ClassParsed p;
+    std::string why;
+    try {
+        const int st = parse_class_query(re, len, VLG_MAX_SUBPATTERNS, p, why);
+        if (st) return fail((vlg_status)st, why);
+    } catch (const std::bad_alloc&) { return fail(VLG_E_OOM, "out of host memory while parsing the query"); }
+    out->k = (uint32_t)p.sub.size();
+    for (uint32_t i = 0; i < out->k; ++i) {
+        out->sub_off[i] = p.sub[i].first; out->sub_len[i] = p.sub[i].second;
+        out->lo[i] = p.lo[i]; out->hi[i] = p.hi[i];
+    }
+    out->end_len = p.end_len;
+    if (n_positions) *n_positions = p.pos.size();
+    if (h_masks) {
+        if (cap_positions < p.pos.size()) return fail(VLG_E_INVALID, "room for " + std::to_string(cap_positions) + " positions, the query has " + std::to_string(p.pos.size()));
+        for (size_t i = 0; i < p.pos.size(); ++i) memcpy(h_masks + i * 32, p.pos[i].w, 32);
+    }
+    return VLG_OK;
+}
+
+extern "C" vlg_status vlg_queries_parse_classes(const char* h_text, const uint64_t* h_off, uint64_t n_queries, int* h_status, vlg_queries** out)
+{
+    if (!out || (n_queries && (!h_text || !h_off))) return fail(VLG_E_INVALID, "null argument");
+    *out = nullptr;
+    vlg_queries* q = new vlg_queries();
+    std::vector<uint8_t> masks;
+    vlg_status first_err = VLG_OK;
+    std::string first_why;
+    try {
+        q->nq = n_queries;
+        q->qsub.assign(1, 0);
+        q->suboff.assign(1, 0);
+        for (uint64_t i = 0; i < n_queries; ++i) {
+            ClassParsed p;
+            std::string why;
+            const vlg_status st = (vlg_status)parse_class_query(h_text + h_off[i], h_off[i + 1] - h_off[i], VLG_MAX_SUBPATTERNS, p, why);
+            if (h_status) h_status[i] = st;
+            if (st) {
+                if (!first_err) { first_err = st; first_why = "query " + std::to_string(i) + ": " + why; }
+            } else {
+                for (size_t s = 0; s < p.sub.size(); ++s) {
+                    q->suboff.push_back(q->suboff.back() + p.sub[s].second);
+                    q->lo.push_back(p.lo[s]);
+                    q->hi.push_back(p.hi[s]);
+                }
+                for (const ByteSet& b : p.pos) {
+                    q->blob.push_back((uint8_t)b.lowest());
+                    masks.insert(masks.end(), b.w, b.w + 32);
+                }
+            }
+            q->qsub.push_back(q->suboff.size() - 1);           // a failed query keeps zero sub-patterns
+            q->end_len.push_back(st ? 0 : p.end_len);
+        }
+        q->nsub = q->suboff.size() - 1;
+    } catch (const std::bad_alloc&) { delete q; return fail(VLG_E_OOM, "out of host memory while parsing the batch"); }
+    if (first_err && !h_status) { delete q; return fail(first_err, first_why); }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { delete q; return fail(VLG_E_NO_DEVICE, "no HIP device available"); }
+    if (vlg_status st = upload_queries(q)) { vlg_queries_destroy(q); return st; }
+    if (vlg_status st = attach_masks(q, masks)) { vlg_queries_destroy(q); return st; }
+    *out = q;
+    return VLG_OK;
+}
+
+extern "C" vlg_status vlg_queries_create_classes(const uint8_t* h_masks, const uint64_t* h_suboff, const uint64_t* h_qsub, const uint64_t* h_lo,
+                                                 const uint64_t* h_hi, const uint64_t* h_end_len, uint64_t n_queries, vlg_queries** out)
+{
+    if (!out || (n_queries && (!h_suboff || !h_qsub))) return fail(VLG_E_INVALID, "null argument");
+    *out = nullptr;
+    const uint64_t nsub = n_queries ? h_qsub[n_queries] : 0;
+    for (uint64_t s = 0; s < nsub; ++s) if (h_suboff[s + 1] <= h_suboff[s]) return fail(VLG_E_INVALID, "empty sub-pattern");
+    const uint64_t npos = nsub ? h_suboff[nsub] : 0;
+    if (npos && !h_masks) return fail(VLG_E_INVALID, "null argument");
+    std::vector<uint8_t> blob, masks;
+    try {
+        blob.resize(npos + 1, 0);
+        for (uint64_t p = 0; p < npos; ++p) {
+            const uint8_t* row = h_masks + p * 32;
+            const uint32_t cnt = byteset_count(row);
+            if (!cnt) return fail(VLG_E_INVALID, "position " + std::to_string(p) + " accepts no byte");
+            if (cnt > 1 && (row[0] & 1)) return fail(VLG_E_INVALID, "position " + std::to_string(p) + ": a class holds the 0 byte");
+            blob[p] = (uint8_t)byteset_lowest(row);
+        }
+        masks.assign(h_masks, h_masks + npos * 32);
+    } catch (const std::bad_alloc&) { return fail(VLG_E_OOM, "out of host memory while assembling the batch"); }
+    vlg_queries* q = nullptr;
+    if (vlg_status st = vlg_queries_create(blob.data(), h_suboff, h_qsub, h_lo, h_hi, h_end_len, n_queries, &q)) return st;
+    if (vlg_status st = attach_masks(q, masks)) { vlg_queries_destroy(q); return st; }
+    *out = q;
+    return VLG_OK;
+}
+
 extern "C" uint64_t vlg_queries_count(const vlg_queries* q) { return q ? q->nq : 0; }
 extern "C" uint64_t vlg_queries_subpatterns(const vlg_queries* q) { return q ? q->nsub : 0; }
 extern "C" vlg_status vlg_queries_k(const vlg_queries* q, uint32_t* h_k)
@@ -419,6 +538,7 @@ extern "C" vlg_status vlg_queries_set_windows(vlg_queries* q, const uint64_t* h_
 {
     if (!q) return fail(VLG_E_INVALID, "null argument");
     if (!h_begin && !h_end) { q->win_begin.clear(); q->win_end.clear(); return VLG_OK; }
+    if (q->has_classes()) return fail(VLG_E_UNSUPPORTED, "a batch with character classes takes no text windows");
     // (checked before anything is stored: a refused call keeps the batch's previous windows)
     if (h_begin && h_end)
         for (uint64_t j = 0; j < q->nq; ++j)
@@ -447,6 +567,7 @@ extern "C" void vlg_queries_destroy(vlg_queries* q)
     if (q->d_blob) (void)hipFree(q->d_blob);
     if (q->d_suboff) (void)hipFree(q->d_suboff);
     if (q->d_qsub) (void)hipFree(q->d_qsub);
+    if (q->d_masks) (void)hipFree(q->d_masks);
     delete q;
 }
 

@@ -24,6 +24,7 @@
 #include <mutex>
 #include <numeric>
 #include <thread>
+#include <unordered_map>
 #include <string.h>
 #include <string>
 #include <vector>
@@ -42,9 +43,9 @@ using namespace vlg;
 // Workspace
 // =============================================================================================
 enum { KS_BSEARCH = 0, KS_EXPAND, KS_LOCATE, KS_LOCATE_PART, KS_LOCATE_RESOLVE, KS_SORT, KS_FILTER_LADDER, KS_FILTER_PIVOT, KS_FILTER_PASS, KS_FILTER_COMPACT,
-       KS_JOIN_INIT, KS_JOIN_LINK, KS_JOIN_SCAN, KS_JOIN_CHAIN, KS_GATHER, KS_EXCHANGE, KS_WINDOW_CUT, KS_COUNT };
+       KS_JOIN_INIT, KS_JOIN_LINK, KS_JOIN_SCAN, KS_JOIN_CHAIN, KS_GATHER, KS_EXCHANGE, KS_WINDOW_CUT, KS_CLASS_SEARCH, KS_COUNT };
 static const char* kKernelNames[KS_COUNT] = {"backward_search", "expand", "locate", "locate_partition", "locate_resolve", "sort", "filter_ladder", "filter_pivot",
-                                             "filter_pass", "filter_compact", "join_init", "join_link", "join_scan", "join_chain", "gather", "exchange", "window_cut"};
+                                             "filter_pass", "filter_compact", "join_init", "join_link", "join_scan", "join_chain", "gather", "exchange", "window_cut", "class_search"};
 
 struct vlg_workspace {
     hipStream_t stream = nullptr;
@@ -89,6 +90,8 @@ struct vlg_workspace {
     uint32_t unsample_pct = 0;
     uint64_t unsample_min = 1ull << 28;     // ... and at least this many occurrences: ~110 rounds of two launches each are a fixed cost
     uint64_t unsample_tail = 1ull << 20;    // walkers left when the sorted rounds end and the lanes finish them one by one
+    uint32_t class_intervals = 1024;        // character classes: SA intervals one sub-pattern may have at any step of its backward search
+                                            // (kernels.hip: class_search_kernel; 32 B of scratch per interval and task of a group)
     uint64_t sample_reads = 0;              // SA samples read by the locate stage of the batch in work (algorithmic bytes)
     // one process per GPU: a collective search shards the DISTINCT LISTS of a batch over the ranks for locate + sort,
     // exchanges the sorted lists (all-gather) and shards the QUERIES for filter + join
@@ -282,6 +285,11 @@ extern "C" vlg_status vlg_workspace_set_option(vlg_workspace* ws, const char* na
     if (!strcmp(name, "exchange_all")) { ws->exchange_all = value != 0; return VLG_OK; }
     if (!strcmp(name, "unsample_pct")) { ws->unsample_pct = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 20)); return VLG_OK; }
     if (!strcmp(name, "unsample_tail")) { ws->unsample_tail = (uint64_t)value; return VLG_OK; }
+    if (!strcmp(name, "class_intervals")) {
+        if (value < 1 || value > (int64_t)kClassIntervalsMax) return fail(VLG_E_INVALID, "class_intervals: 1 .. 2^20");
+        ws->class_intervals = (uint32_t)value;
+        return VLG_OK;
+    }
     if (!strcmp(name, "unsample_min")) { ws->unsample_min = (uint64_t)value; return VLG_OK; }
     return fail(VLG_E_INVALID, std::string("unknown workspace option ") + name);
 }
@@ -351,6 +359,8 @@ struct vlg_result {
     std::vector<uint32_t> k;               // host: sub-patterns per query
     std::vector<ResultPiece> pieces;
     std::vector<uint64_t> owned;           // collective search: [begin, end) pairs of the queries this rank joined (empty: all of them)
+    std::vector<uint64_t> civ_off, civ_l, civ_r;   // a batch with character classes: the SA intervals of sub-pattern s are [civ_off[s], civ_off[s + 1])
+    bool has_class_intervals = false;
     std::vector<uint64_t> next;            // vlg_wtsa_* searches: per query, where the next search continues this one (~0: it ran out)
     bool has_next = false;
 };
@@ -2262,7 +2272,264 @@ vlg_result* new_result(uint64_t n, const std::vector<uint64_t>& qsub)
 // the partial checksums of the gather kernel added up, modulo 2^64 like gm_search.cpp:110-114
 uint64_t fold_checksum(const unsigned long long* stats) { return std::accumulate(stats + kStatsChecksum, stats + kStatsWords, (uint64_t)0); }
 
+
+// =============================================================================================
+// Batches with character classes (queries.cpp: vlg_queries_parse_classes)
+// =============================================================================================
+// A sub-pattern whose positions are sets of bytes has a SET of pairwise disjoint SA intervals, one per member string that occurs
+// (kernels.hip: class_search_kernel).  Everything behind the occurrence lists sees a list as (L.off[s], occ[s]) only, so the batch
+// is assembled as vlg_join_batch assembles one: distinct sub-patterns are found by content on the host, each is searched once
+// (literal ones by backward_search_kernel: one interval), the intervals come to the host, and per super-chunk the intervals of a
+// distinct sub-pattern are expanded back to back into ONE list, located by the random-access walks (the stages of vlg_locate_batch),
+// sorted inside itself and joined by plan_joins / run_joins unchanged.
+vlg_status run_class_batch(const vlg_index* idx, const vlg_queries* q, vlg_workspace* ws, vlg_result* res, PhaseTrace& tr)
+{
+    hipStream_t st = ws->stream;
+    const uint64_t nsub = q->nsub, n = idx->hdr.n;
+    const uint32_t cap = ws->class_intervals;
+    // ---- distinct sub-patterns, by content: literal ones by their bytes, the others by their mask rows ---------------------------
+    std::vector<uint32_t> sub_d(nsub, 0);
+    std::vector<uint64_t> d_sub;                                  // per distinct sub-pattern: the first sub-pattern of the batch that is it
+    {
+        std::unordered_map<std::string, uint32_t> seen;
+        seen.reserve(nsub * 2 + 16);
+        std::string key;
+        for (uint64_t s = 0; s < nsub; ++s) {
+            const uint64_t a = q->suboff[s], b = q->suboff[s + 1];
+            if (q->sub_literal[s]) { key.assign(1, 'L'); key.append(reinterpret_cast<const char*>(q->blob.data() + a), b - a); }
+            else { key.assign(1, 'C'); key.append(reinterpret_cast<const char*>(q->masks.data() + a * 32), (b - a) * 32); }
+            const auto it = seen.emplace(key, (uint32_t)d_sub.size());
+            if (it.second) d_sub.push_back(s);
+            sub_d[s] = it.first->second;
+        }
+    }
+    const uint64_t nd = d_sub.size();
+    if (nd >= 0xFFFFFFF0ull) return fail(VLG_E_UNSUPPORTED, "too many distinct sub-patterns in one batch");
+    std::vector<uint32_t> lit, cls;                               // distinct ids of either kind
+    for (uint32_t d = 0; d < nd; ++d) (q->sub_literal[d_sub[d]] ? lit : cls).push_back(d);
+    const uint64_t nlit = lit.size(), ncls = cls.size();
+    // ---- device memory of the front: counters, the literal patterns and their intervals, tasks, counts, the frontier -----------------
+    svec<uint8_t> lblob;
+    svec<uint64_t> loff(nlit + 1, 0), task(2 * std::max<uint64_t>(ncls, 1), 0);
+    for (uint64_t i = 0; i < nlit; ++i) {
+        const uint64_t s = d_sub[lit[i]];
+        lblob.insert(lblob.end(), q->blob.begin() + q->suboff[s], q->blob.begin() + q->suboff[s + 1]);
+        loff[i + 1] = lblob.size();
+    }
+    for (uint64_t i = 0; i < ncls; ++i) { const uint64_t s = d_sub[cls[i]]; task[2 * i] = q->suboff[s]; task[2 * i + 1] = q->suboff[s + 1] - q->suboff[s]; }
+    const uint64_t kClassScratch = 64ull << 20;                  // the frontiers of one group of tasks
+    const uint64_t group = std::max<uint64_t>(1, std::min<uint64_t>(std::max<uint64_t>(ncls, 1), kClassScratch / (32ull * cap)));
+    const uint64_t st_bytes = align_up(kStatsWords * 8, 256), lb_bytes = align_up(lblob.size() + 16, 256), lo_bytes = align_up((nlit + 1) * 8, 256);
+    const uint64_t tk_bytes = align_up(2 * (ncls + 1) * 8, 256), ct_bytes = align_up(group * 4, 256), fr_bytes = align_up(2 * group * cap * 16, 256);
+    uint8_t* head = nullptr;
+    if (vlg_status hs = ws_head(ws, st_bytes + lb_bytes + 3 * lo_bytes + tk_bytes + ct_bytes + fr_bytes, &head)) return hs;
+    unsigned long long* d_stats = (unsigned long long*)head;
+    uint8_t* d_lblob = head + st_bytes;
+    uint64_t* d_loff = (uint64_t*)(d_lblob + lb_bytes);
+    uint64_t* d_ll = (uint64_t*)((uint8_t*)d_loff + lo_bytes);
+    uint64_t* d_lr = (uint64_t*)((uint8_t*)d_ll + lo_bytes);
+    uint64_t* d_task = (uint64_t*)((uint8_t*)d_lr + lo_bytes);
+    uint32_t* d_count = (uint32_t*)((uint8_t*)d_task + tk_bytes);
+    uint64_t* d_frontier = (uint64_t*)((uint8_t*)d_count + ct_bytes);
+    VLG_HIP_TRY(hipMemsetAsync(d_stats, 0, kStatsWords * 8, st));
+    ws->sample_reads = 0;
+    ws->x_agreed = 0;
+    // ---- the intervals of every distinct sub-pattern ------------------------------------------------------------------------------
+    std::vector<uint64_t> doff(nd + 1, 0);                        // per distinct sub-pattern: its intervals inside dl_ / dr_, in two passes
+    std::vector<std::vector<uint64_t>> piece_l(nd), piece_r(nd);
+    if (nlit) {
+        if (!lblob.empty()) VLG_HIP_TRY(hipMemcpyAsync(d_lblob, lblob.data(), lblob.size(), hipMemcpyHostToDevice, st));
+        VLG_HIP_TRY(hipMemcpyAsync(d_loff, loff.data(), (nlit + 1) * 8, hipMemcpyHostToDevice, st));
+        {
+            Timed t(ws, KS_BSEARCH, 0);
+            if (vlg_status s = launch_backward_search(idx->view, d_lblob, d_loff, nlit, d_ll, d_lr, d_stats + 3, st)) return s;
+        }
+        svec<uint64_t> hl(nlit), hr(nlit);
+        VLG_HIP_TRY(hipMemcpyAsync(hl.data(), d_ll, nlit * 8, hipMemcpyDeviceToHost, st));
+        VLG_HIP_TRY(hipMemcpyAsync(hr.data(), d_lr, nlit * 8, hipMemcpyDeviceToHost, st));
+        VLG_HIP_TRY(hipStreamSynchronize(st));
+        for (uint64_t i = 0; i < nlit; ++i)
+            if (hr[i] + 1 > hl[i]) { piece_l[lit[i]].push_back(hl[i]); piece_r[lit[i]].push_back(hr[i]); }
+    }
+    if (ncls) {
+        VLG_HIP_TRY(hipMemcpyAsync(d_task, task.data(), 2 * ncls * 8, hipMemcpyHostToDevice, st));
+        svec<uint32_t> hc(group);
+        svec<uint64_t> hf;
+        for (uint64_t g0 = 0; g0 < ncls; g0 += group) {
+            const uint64_t g = std::min<uint64_t>(group, ncls - g0);
+            {
+                Timed t(ws, KS_CLASS_SEARCH, 0);
+                if (vlg_status s = launch_class_search(idx->view, q->d_masks, d_task + 2 * g0, g, cap, d_frontier, d_count, d_stats + 3, st)) return s;
+            }
+            VLG_HIP_TRY(hipMemcpyAsync(hc.data(), d_count, g * 4, hipMemcpyDeviceToHost, st));
+            VLG_HIP_TRY(hipStreamSynchronize(st));
+            uint64_t widest = 0;
+            for (uint64_t i = 0; i < g; ++i) {
+                if (hc[i] == kClassSearchOverflow) {
+                    // (nothing else is launched: the batch ends here)
+                    const uint64_t s = d_sub[cls[g0 + i]];
+                    const uint64_t qi = (uint64_t)(std::upper_bound(q->qsub.begin(), q->qsub.end(), s) - q->qsub.begin()) - 1;
+                    return fail(VLG_E_WORKSPACE, "query " + std::to_string(qi) + ", sub-pattern " + std::to_string(s - q->qsub[qi]) + ": more than " +
+                                                     std::to_string(cap) + " SA intervals at one step of its class search (workspace option \"class_intervals\")");
+                }
+                widest = std::max<uint64_t>(widest, hc[i]);
+            }
+            if (!widest) continue;
+            // half 0 of the group's frontiers: `cap` intervals of 16 bytes per task, of which the first `widest` are fetched
+            hf.resize(g * widest * 2);
+            VLG_HIP_TRY(hipMemcpy2DAsync(hf.data(), widest * 16, d_frontier, (size_t)cap * 16, widest * 16, g, hipMemcpyDeviceToHost, st));
+            VLG_HIP_TRY(hipStreamSynchronize(st));
+            for (uint64_t i = 0; i < g; ++i) {
+                const uint32_t d = cls[g0 + i];
+                piece_l[d].reserve(hc[i]); piece_r[d].reserve(hc[i]);
+                for (uint64_t j = 0; j < hc[i]; ++j) { piece_l[d].push_back(hf[(i * widest + j) * 2]); piece_r[d].push_back(hf[(i * widest + j) * 2 + 1]); }
+            }
+        }
+    }
+    tr.mark("class search");
+    std::vector<uint64_t> dl_, dr_;
+    Plan pl;
+    pl.occ.assign(nsub, 0);
+    pl.did.assign(nsub, 0);
+    pl.dl.assign(nd, 0);
+    pl.docc.assign(nd, 0);
+    for (uint64_t d = 0; d < nd; ++d) {
+        doff[d] = dl_.size();
+        dl_.insert(dl_.end(), piece_l[d].begin(), piece_l[d].end());
+        dr_.insert(dr_.end(), piece_r[d].begin(), piece_r[d].end());
+        for (size_t j = 0; j < piece_l[d].size(); ++j) pl.docc[d] += piece_r[d][j] + 1 - piece_l[d][j];
+        pl.dl[d] = piece_l[d].empty() ? 0 : piece_l[d][0];
+    }
+    doff[nd] = dl_.size();
+    piece_l.clear(); piece_r.clear();
+    // what vlg_result_class_intervals returns: per sub-pattern of the batch, the intervals of its distinct sub-pattern
+    res->has_class_intervals = true;
+    res->civ_off.assign(nsub + 1, 0);
+    for (uint64_t s = 0; s < nsub; ++s) res->civ_off[s + 1] = res->civ_off[s] + (doff[sub_d[s] + 1] - doff[sub_d[s]]);
+    res->civ_l.reserve(res->civ_off[nsub]); res->civ_r.reserve(res->civ_off[nsub]);
+    for (uint64_t s = 0; s < nsub; ++s) {
+        res->civ_l.insert(res->civ_l.end(), dl_.begin() + doff[sub_d[s]], dl_.begin() + doff[sub_d[s] + 1]);
+        res->civ_r.insert(res->civ_r.end(), dr_.begin() + doff[sub_d[s]], dr_.begin() + doff[sub_d[s] + 1]);
+    }
+    // a query with an empty occurrence list has no match: none of its lists is materialised (vlg_index.hpp:315-316)
+    for (uint64_t qi = 0; qi < q->nq; ++qi) {
+        bool live = q->qsub[qi + 1] > q->qsub[qi];
+        for (uint64_t s = q->qsub[qi]; s < q->qsub[qi + 1] && live; ++s) live = pl.docc[sub_d[s]] > 0;
+        if (!live) continue;
+        for (uint64_t s = q->qsub[qi]; s < q->qsub[qi + 1]; ++s) { pl.did[s] = sub_d[s]; pl.occ[s] = pl.docc[sub_d[s]]; res->sum.logical_occurrences += pl.occ[s]; }
+    }
+    // ---- super-chunks: whole queries while their distinct lists fit the physical budget (next_super_chunk, as the byte path) ----------
+    const bool wide = idx->hdr.sample_bytes == 8;                 // 33-bit SA indices; the positions still fit 32 bits (n <= 2^32 + 1)
+    const uint64_t fixed = 8ull << 20;
+    if (ws->cap_bytes <= 2 * fixed) return fail(VLG_E_WORKSPACE, "workspace cap too small");
+    const uint64_t budget = ws->cap_bytes - fixed;
+    const uint64_t phys_cap = std::min<uint64_t>(budget / 2 / (sizeof(uint32_t) + kPhysScratchPerElem<uint32_t>() + 1), 0xFFFFFF00ull);
+    const unsigned pos_bits = std::max(1u, bit_width64(n >= 2 ? n - 2 : 0));
+    const IndexView lview = ws->quad_walk ? idx->view : without_quad(idx->view);
+    std::vector<uint32_t> stamp(nd, 0xFFFFFFFFu);
+    uint32_t epoch = 0;
+    Lists<uint32_t> L;
+    L.doff.assign(nd, 0);
+    L.off.assign(nsub, 0);
+    for (uint64_t Q0 = 0; Q0 < q->nq;) {
+        SuperChunk sc;
+        if (vlg_status s = next_super_chunk(q, pl, false, phys_cap, Q0, stamp, epoch, sc)) return s;
+        const uint64_t nl = sc.dlist.size();
+        // the lists of the super-chunk one after the other, and the intervals each of them is made of
+        svec<uint64_t> off64(nl + 1, 0), iv_l, iv_off(1, 0);
+        for (uint64_t i = 0; i < nl; ++i) {
+            const uint32_t d = sc.dlist[i];
+            L.doff[d] = (uint32_t)off64[i];
+            for (uint64_t j = doff[d]; j < doff[d + 1]; ++j) { iv_l.push_back(dl_[j]); iv_off.push_back(iv_off.back() + (dr_[j] + 1 - dl_[j])); }
+            off64[i + 1] = off64[i] + pl.docc[d];
+        }
+        const uint64_t total = off64[nl], niv = iv_l.size();
+        if (total != iv_off.back() || total != sc.phys) return fail(VLG_E_INTERNAL, "class batch: list lengths disagree with their intervals");
+        uint64_t n_long = 0, n_tiles = 0, n_chunks = 0;
+        for (uint64_t i = 0; i < nl; ++i) {
+            const uint64_t len = off64[i + 1] - off64[i];
+            if (len > kSortTile) { const uint64_t t = (len + kSortTile - 1) / kSortTile; ++n_long; n_tiles += t; n_chunks += (t + kSortChunk - 1) / kSortChunk; }
+        }
+        // arena: [lists][room for the survivors of the window filter][walk / sort scratch][tables][fences] | filter state, join scratch
+        const uint64_t pc_first = align_up(total, 64);
+        const uint64_t pc_cap = ws->filter && total ? std::min<uint64_t>(total, 0xFFFFFF00ull - pc_first) : 0;
+        const uint64_t fence_entries = (pc_first + pc_cap) / 64 + 2;
+        const uint64_t list_bytes = align_up((pc_first + pc_cap + 64) * 4, 256) + align_up(total * (wide ? 8 : 4) + 8, 256) + align_up((nl + 1) * 8, 256) +
+                                    align_up((niv + 1) * 8, 256) + align_up((niv + 2) * 8, 256) + align_up(fence_entries * 4, 256) + align_up(nl * 4, 256) +
+                                    kSortClasses * 256 + list_sort_scratch_bytes(n_long, n_tiles, n_chunks) + 16 * 256 + 8192;
+        if (list_bytes >= budget) return fail(VLG_E_WORKSPACE, "the lists of a super-chunk do not fit the workspace cap");
+        JoinPlan jp;
+        if (vlg_status s = plan_joins(q, pl, ws, sc.Q0, sc.Q1, budget - list_bytes, n, jp)) return s;
+        if (vlg_status s = ws_reserve(ws, list_bytes + jp.filter_need + jp.want_bytes + jp.meta + fixed)) return s;
+        Arena A{ws->arena, ws->arena_bytes};
+        L.P = A.take<uint32_t>(pc_first + pc_cap + 64);
+        uint8_t* other = A.take<uint8_t>(total * (wide ? 8 : 4) + 8);
+        uint64_t* d_off = A.take<uint64_t>(nl + 1);
+        uint64_t* d_ivl = A.take<uint64_t>(niv + 1);
+        uint64_t* d_ivoff = A.take<uint64_t>(niv + 2);
+        uint32_t* F = A.take<uint32_t>(fence_entries);
+        if (A.failed) return fail(VLG_E_INTERNAL, "arena carve failed (class lists)");
+        L.Pc = nullptr; L.pc_cap = 0; L.F = nullptr; L.R = nullptr; L.roff = nullptr;
+        if (total) {
+            VLG_HIP_TRY(hipMemcpyAsync(d_off, off64.data(), (nl + 1) * 8, hipMemcpyHostToDevice, st));
+            VLG_HIP_TRY(hipMemcpyAsync(d_ivl, iv_l.data(), niv * 8, hipMemcpyHostToDevice, st));
+            VLG_HIP_TRY(hipMemcpyAsync(d_ivoff, iv_off.data(), (niv + 1) * 8, hipMemcpyHostToDevice, st));
+            ListSortPlan lp;
+            if (vlg_status s = list_sort_prepare(off64, (uint32_t)nl, A, st, lp)) return s;
+            if (wide) {
+                uint64_t* io = reinterpret_cast<uint64_t*>(other);
+                { Timed t(ws, KS_EXPAND, 0); if (vlg_status s = launch_expand<uint64_t>(d_ivl, d_ivoff, niv, total, io, nullptr, st)) return s; }
+                Timed t(ws, KS_LOCATE, 0);
+                if (vlg_status s = launch_locate<uint64_t>(lview, io, total, d_stats, st)) return s;
+                if (vlg_status s = launch_narrow<uint32_t>(io, L.P, total, st)) return s;
+            } else {
+                { Timed t(ws, KS_EXPAND, 0); if (vlg_status s = launch_expand<uint32_t>(d_ivl, d_ivoff, niv, total, L.P, nullptr, st)) return s; }
+                Timed t(ws, KS_LOCATE, 0);
+                if (vlg_status s = launch_locate<uint32_t>(lview, L.P, total, d_stats, st)) return s;
+            }
+            ws->sample_reads += total;
+            res->sum.locate_mode = VLG_LOCATE_WALKS;
+            {
+                Timed t(ws, KS_SORT, 2ull * total * 4);
+                if (vlg_status s = list_sort_enqueue(lp, L.P, reinterpret_cast<uint32_t*>(other), d_off, pos_bits, st, ws->list_sort != 2)) return s;
+            }
+            if (total >= 64) {
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(fence_build_kernel<uint32_t>), launch_grid(total / 64, 8192), dim3(256), 0, st, L.P, (uint64_t)0, total / 64, F);
+                VLG_HIP_TRY(hipGetLastError());
+            }
+            L.F = F;
+            L.Pc = pc_cap ? L.P + pc_first : nullptr;
+            L.pc_cap = pc_cap;
+        }
+        res->sum.located_occurrences += total;
+        tr.mark("class lists: locate + sort");
+        for (uint64_t s = q->qsub[sc.Q0]; s < q->qsub[sc.Q1]; ++s) L.off[s] = pl.occ[s] ? L.doff[pl.did[s]] : 0;
+        if (vlg_status s = run_joins<uint32_t>(n, q, ws, res, pl, L, A, sc.Q0, sc.Q1, jp, d_stats, tr)) return s;
+        Q0 = sc.Q1;
+    }
+    unsigned long long hs[kStatsWords];
+    VLG_HIP_TRY(hipMemcpyAsync(hs, d_stats, sizeof hs, hipMemcpyDeviceToHost, st));
+    VLG_HIP_TRY(hipStreamSynchronize(st));
+    res->sum.lf_steps = hs[0];
+    res->sum.wt_levels_locate = hs[1];
+    res->sum.checksum = fold_checksum(hs);
+    res->sum.wt_levels_bsearch = hs[3];
+    ws->stats[KS_LOCATE].algorithmic_bytes += 32ull * hs[1] + (uint64_t)idx->hdr.sample_bytes * ws->sample_reads;
+    ws->stats[KS_CLASS_SEARCH].algorithmic_bytes += 32ull * hs[3];
+    return VLG_OK;
+}
+
 }  // namespace
+
+extern "C" vlg_status vlg_result_class_intervals(const vlg_result* r, uint64_t* h_ivoff, uint64_t* h_l, uint64_t* h_r)
+{
+    if (!r || !h_ivoff) return fail(VLG_E_INVALID, "null argument");
+    if (!r->has_class_intervals) return fail(VLG_E_INVALID, "the result does not come from a batch with character classes");
+    std::copy(r->civ_off.begin(), r->civ_off.end(), h_ivoff);
+    if (h_l) std::copy(r->civ_l.begin(), r->civ_l.end(), h_l);
+    if (h_r) std::copy(r->civ_r.begin(), r->civ_r.end(), h_r);
+    return VLG_OK;
+}
 
 extern "C" vlg_status vlg_search_batch(const vlg_index* idx, const vlg_queries* q, vlg_workspace* ws, vlg_result** out)
 {
@@ -2272,6 +2539,13 @@ extern "C" vlg_status vlg_search_batch(const vlg_index* idx, const vlg_queries* 
     if (idx->is_int && q->sym_bytes != 4 && q->nsub) return fail(VLG_E_INVALID, "an integer-alphabet index takes query batches parsed by vlg_queries_parse_int");
     // (every rank holds the same batch and refuses alike, before anything is launched or exchanged: no rank waits for another)
     if (q->has_windows() && ws->x_ranks > 1) return fail(VLG_E_UNSUPPORTED, "a collective search takes no text windows (vlg_queries_set_windows)");
+    // the one branch of a batch with character classes: without them nothing of that path is launched, waited for or copied
+    const bool classes = q->has_classes();
+    if (classes) {
+        if (idx->is_int) return fail(VLG_E_UNSUPPORTED, "character classes are searched on a byte index");
+        if (ws->x_ranks > 1) return fail(VLG_E_UNSUPPORTED, "a collective search takes no batch with character classes");
+        if (idx->hdr.n > (1ull << 32) + 1) return fail(VLG_E_UNSUPPORTED, "character classes: the text needs 64-bit positions");
+    }
     hipStream_t st = ws->stream;
     vlg_result* res = new_result(q->nq, q->qsub);
     uint64_t* d_l = nullptr;
@@ -2283,6 +2557,7 @@ extern "C" vlg_status vlg_search_batch(const vlg_index* idx, const vlg_queries* 
         fprintf(stderr, "[vlg trace] %-28s %9.3f ms\n", "(between two batches)",
                 std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - last_end).count());
     auto run = [&]() -> vlg_status {
+        if (classes) return run_class_batch(idx, q, ws, res, tr);
         const uint64_t nsub = q->nsub;
         // SA intervals, counters and the interval plan's arrays live in the workspace's head buffer (no allocation per batch)
         const bool may_plan_on_device = ws->dedup && idx->hdr.n <= (1ull << 33) && nsub > 0 && nsub < 0xFFFFFFF0ull;
@@ -2361,6 +2636,7 @@ extern "C" vlg_status vlg_search_batch(const vlg_index* idx, const vlg_queries* 
 extern "C" vlg_status vlg_queries_intervals(const vlg_index* idx, const vlg_queries* q, uint64_t* h_l, uint64_t* h_r, void* stream)
 {
     if (!idx || !q || (q->nsub && (!h_l || !h_r))) return fail(VLG_E_INVALID, "null argument");
+    if (q->has_classes()) return fail(VLG_E_UNSUPPORTED, "a batch with character classes has several SA intervals per sub-pattern (vlg_search_batch + vlg_result_class_intervals)");
     if (idx->is_int != (q->sym_bytes == 4) && q->nsub) return fail(VLG_E_INVALID, "query batch and index are of different alphabets");
     const uint64_t nsub = q->nsub;
     if (!nsub) return VLG_OK;
@@ -2382,6 +2658,7 @@ extern "C" vlg_status vlg_queries_intervals(const vlg_index* idx, const vlg_quer
 extern "C" vlg_status vlg_queries_occurrences(const vlg_index* idx, const vlg_queries* q, uint64_t* h_occ, void* stream)
 {
     if (!idx || !q || (q->nsub && !h_occ)) return fail(VLG_E_INVALID, "null argument");
+    if (q->has_classes()) return fail(VLG_E_UNSUPPORTED, "a batch with character classes has several SA intervals per sub-pattern (vlg_search_batch + vlg_result_class_intervals)");
     std::vector<uint64_t> r(q->nsub + 1);
     if (vlg_status s = vlg_queries_intervals(idx, q, h_occ, r.data(), stream)) return s;
     for (uint64_t i = 0; i < q->nsub; ++i) h_occ[i] = r[i] + 1 - h_occ[i];        // r + 1 - l (suffix_array_algorithm.hpp:325)

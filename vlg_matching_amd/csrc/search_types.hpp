@@ -19,4 +19,12 @@ struct vlg_queries {
     // caller's values (UINT64_MAX = "to the end of the text"): the batch does not know n, the search clamps.
     std::vector<uint64_t> win_begin, win_end;
     bool has_windows() const { return !win_end.empty(); }
+    // character classes (vlg_queries_parse_classes / _create_classes): empty = the batch has none and is a byte batch like any other.
+    // Otherwise one 256-bit row per position of the batch (bit c = byte c), position p of the batch = byte p of blob, so that suboff
+    // still counts positions; blob then holds placeholders (the byte itself where a position accepts one byte, the least member
+    // otherwise) that only vlg_search_batch's class path may read, and only for the sub-patterns sub_literal[] marks.
+    std::vector<uint8_t> masks;      // [positions * 32]
+    std::vector<uint8_t> sub_literal;    // [nsub]: every position of the sub-pattern accepts exactly one byte
+    uint8_t* d_masks = nullptr;
+    bool has_classes() const { return !masks.empty(); }
 };

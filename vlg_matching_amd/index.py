@@ -89,6 +89,17 @@ class SearchResult:
         check(lib().vlg_result_next_positions(self._h, nxt.ctypes.data))
         return nxt[:nq]
 
+    def class_intervals(self):
+        """vlg_result_class_intervals: the SA intervals of every sub-pattern of a batch with character classes (Queries.from_classes)
+        -> (ivoff[nsub + 1], l[], r[]): sub-pattern s has the intervals [l[j], r[j]], ivoff[s] <= j < ivoff[s + 1], ascending and
+        disjoint.  VlgError for the result of a batch without classes."""
+        nsub = int(np.sum(np.asarray(self._ks, dtype=np.int64)))
+        off = np.zeros(nsub + 1, dtype=np.uint64)
+        check(lib().vlg_result_class_intervals(self._h, off.ctypes.data, None, None))
+        l, r = np.zeros(max(int(off[-1]), 1), np.uint64), np.zeros(max(int(off[-1]), 1), np.uint64)
+        check(lib().vlg_result_class_intervals(self._h, off.ctypes.data, l.ctypes.data, r.ctypes.data))
+        return off, l[: int(off[-1])], r[: int(off[-1])]
+
     @property
     def counts(self):
         return self.fetch()[0]
@@ -294,6 +305,31 @@ def parse_query(regexp, dialect=capi.DIALECT_LIBRARY):
     return subs, [int(p.lo[i]) for i in range(1, p.k)], [int(p.hi[i]) for i in range(1, p.k)], int(p.end_len)
 
 
+def parse_class_query(regexp):
+    """The library dialect with character classes on the host (vlg_parse_class_query): -> (sub-patterns, lo[], hi[], end_len), a
+    sub-pattern being a uint8 array [positions, 32] of 256-bit sets (bit c of a row = byte c is accepted; class_mask_members reads
+    one).  Lengths count positions.  Raises VlgError(E_PARSE / E_INVALID)."""
+    raw = regexp.encode("latin-1") if isinstance(regexp, str) else bytes(regexp)
+    p = capi.ParsedQuery()
+    n = C.c_uint64()
+    masks = np.zeros((max(len(raw), 1), 32), dtype=np.uint8)           # (a position takes at least one byte of the query)
+    check(lib().vlg_parse_class_query(raw, len(raw), C.byref(p), masks.ctypes.data, len(masks), C.byref(n)))
+    subs = [masks[p.sub_off[i]: p.sub_off[i] + p.sub_len[i]].copy() for i in range(p.k)]
+    return subs, [int(p.lo[i]) for i in range(1, p.k)], [int(p.hi[i]) for i in range(1, p.k)], int(p.end_len)
+
+
+def class_mask_members(row):
+    """the bytes a 32-byte mask row accepts, ascending"""
+    return np.flatnonzero(np.unpackbits(np.asarray(row, dtype=np.uint8), bitorder="little")).astype(np.uint8)
+
+
+def class_mask(members):
+    """the 32-byte mask row that accepts exactly `members` (bytes or integers)"""
+    bits = np.zeros(256, dtype=np.uint8)
+    bits[np.frombuffer(bytes(members), dtype=np.uint8) if isinstance(members, (bytes, bytearray)) else np.asarray(list(members), dtype=np.int64)] = 1
+    return np.packbits(bits, bitorder="little")
+
+
 class Queries:
     """A parsed query batch resident in HBM."""
 
@@ -338,6 +374,42 @@ class Queries:
         else:
             check(lib().vlg_queries_parse_int(b"".join(raws), off.ctypes.data, len(raws), st, C.byref(h)))
         self._h, self.n, self.status = h, len(raws), status[: len(raws)]
+        return self
+
+    @classmethod
+    def from_classes(cls, regexps, strict=True):
+        """The library dialect with character classes (vlg_queries_parse_classes): a[bc]d, [^a], \\[ ...; VlgIndex.search takes the
+        batch as any other.  A batch in which no position accepts more than one byte is the batch Queries(regexps) makes."""
+        raws = [r.encode("latin-1") if isinstance(r, str) else bytes(r) for r in regexps]
+        off = np.zeros(len(raws) + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(r) for r in raws])
+        self = cls.__new__(cls)
+        h = C.c_void_p()
+        status = np.zeros(max(len(raws), 1), dtype=np.int32)
+        check(lib().vlg_queries_parse_classes(b"".join(raws), off.ctypes.data, len(raws), None if strict else status.ctypes.data, C.byref(h)))
+        self._h, self.n, self.status = h, len(raws), status[: len(raws)]
+        return self
+
+    @classmethod
+    def from_class_arrays(cls, subpatterns, lo, hi, end_len):
+        """As from_arrays with mask rows for bytes (vlg_queries_create_classes): subpatterns is a list (per query) of lists of uint8
+        arrays [positions, 32] (class_mask builds a row); lo / hi: per query lists of k-1 start-to-start bounds, in positions."""
+        self = cls.__new__(cls)
+        rows, suboff, qsub, flo, fhi = [], [0], [0], [], []
+        for subs, l, h in zip(subpatterns, lo, hi):
+            for i, s in enumerate(subs):
+                s = np.ascontiguousarray(s, dtype=np.uint8).reshape(-1, 32)
+                rows.append(s)
+                suboff.append(suboff[-1] + len(s))
+                flo.append(0 if i == 0 else int(l[i - 1]))
+                fhi.append(0 if i == 0 else int(h[i - 1]))
+            qsub.append(len(suboff) - 1)
+        m = np.ascontiguousarray(np.concatenate(rows + [np.zeros((1, 32), np.uint8)]))
+        a = [np.asarray(x, dtype=np.uint64) for x in (suboff, qsub, flo + [0], fhi + [0], list(end_len) + [0])]
+        hq = C.c_void_p()
+        check(lib().vlg_queries_create_classes(m.ctypes.data, a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, a[3].ctypes.data,
+                                               a[4].ctypes.data, len(subpatterns), C.byref(hq)))
+        self._h, self.n, self.status = hq, len(subpatterns), np.zeros(len(subpatterns), dtype=np.int32)
         return self
 
     def subpattern_range(self):
