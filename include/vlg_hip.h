@@ -805,6 +805,10 @@ vlg_status vlg_workspace_profile(vlg_workspace* ws, int enable);
  * of its backward search (32 bytes of scratch per interval and sub-pattern of a group; the sub-patterns of a batch are searched in groups
  * of 64 MiB of such scratch).  A frontier that would pass it: VLG_E_WORKSPACE (see vlg_queries_parse_classes).
  * "reserve" = bytes of scratch to allocate right away (at most the workspace's cap) instead of on first use.
+ * "fuse_jump" (default 1): the link pass of the join finds, for the elements of a query's first list, where the next match can start
+ * (the jump of the match chain) while it still holds their chain ends; 0 = a separate pass over all first lists does (an A/B inside
+ * one library; the environment variable VLG_FUSE_JUMP=0 does the same for every workspace).  Queries of one sub-pattern take the
+ * separate pass either way.
  * "tuples" (default 1): materialise every sub-pattern position of every match (what sdsl::locate returns); 0 = first
  * positions only, which is all the benchmark's gapped_search_result holds (index_sasearch.hpp:58-118): n_tuple_values
  * is 0 and vlg_result_fetch refuses a tuples buffer.

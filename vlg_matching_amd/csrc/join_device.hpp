@@ -506,25 +506,81 @@ __global__ void __launch_bounds__(256) join_init_kernel(const pos_t* __restrict_
 
 // what a slot does with its lower bound j (value v) in the next list: the first FEASIBLE element at or after it, if still
 // inside the window, becomes its link
+// (`end`: the chain end of a slot that is ok; store_end false: the caller uses it at once and nobody reads endp[e] -- level 0 of the
+// fused pass)
 template <typename pos_t, bool kLast>
 __device__ __forceinline__ bool link_finish(const pos_t* __restrict__ P, const SegMeta& nx, const FeasRef& fb, uint32_t e, bool want, uint32_t j,
-                                            pos_t v, pos_t thi, pos_t* __restrict__ endp, uint32_t* __restrict__ link)
+                                            pos_t v, pos_t thi, pos_t* __restrict__ endp, uint32_t* __restrict__ link, bool store_end, pos_t& end)
 {
     bool ok = false;
     if (want && j < nx.pend) {
         if (kLast) {
             ok = v <= thi;
-            if (ok) { if (link) link[e] = j; endp[e] = v; }
+            if (ok) { if (link) link[e] = j; if (store_end) endp[e] = v; end = v; }
         } else {
             const uint32_t at = nx.begin + (j - nx.pbegin);
             const uint32_t ej = next_feasible(fb, at);     // nearest feasible logical element at or after it
             if (ej < nx.end) {
                 const pos_t pv = ej == at ? v : P[phys_of(nx, ej)];
-                if (pv <= thi) { ok = true; if (link) link[e] = ej; endp[e] = endp[ej]; }
+                if (pv <= thi) { ok = true; if (link) link[e] = ej; end = endp[ej]; if (store_end) endp[e] = end; }
             }
         }
     }
     return ok;
+}
+
+// ---- the level-0 jump inside the link pass -----------------------------------------------------------------------------------------
+// jump[a] of a level-0 slot is the lower bound of end(a) + end_len in the slot's OWN list, behind the slot.  A wave of the link pass
+// that has just linked a step of level-0 slots holds their chain ends and the list elements themselves in registers; the answers
+// lie a few elements on (the window is two gaps and the pattern lengths wide), so the wave stages kStretch elements of the list from
+// the step's first slot on in LDS -- its own keys from registers, the rest is the next steps' keys, which it prefetches anyway -- and
+// every lane bisects there.  What it writes is the RAW target, the lower bound as a logical slot: whether that slot is feasible is
+// still being decided by other waves of the same launch, so the tile pass settles it (chain_tiles_kernel).
+constexpr uint32_t kStretch = 256;          // list elements staged per step (64 or 128 of them are the step's own)
+
+// keys the staged stretch does not reach: the blocked search from its end (a call, to keep it out of the link loop's registers)
+template <typename pos_t>
+__device__ __noinline__ uint32_t jump_far_lower_bound(const pos_t* __restrict__ P, const pos_t* __restrict__ F, uint32_t wb, uint32_t b, pos_t key, bool need)
+{
+    uint32_t j = b;
+    pos_t v = 0;
+    wave_far_lower_bound(P, F, wb < b ? wb : b, b, key, need, j, v);
+    return j < b ? j : b;
+}
+
+// Raw jump targets of kN keys per lane (key i belongs to the slot at tile offset 64 i + lane) in the list of segment m, whose
+// elements [pb, pb + kStretch) are staged in `tile` (+inf behind the list).  kNone: no key, or no element at or after it.
+template <typename pos_t, uint32_t kN>
+__device__ __forceinline__ void stretch_jump_targets(const pos_t* __restrict__ P, const pos_t* __restrict__ F, const SegMeta& m, uint32_t pb,
+                                                     const pos_t* __restrict__ tile, const pos_t (&key)[kN], const bool (&need)[kN], uint32_t (&out)[kN])
+{
+    const uint32_t lane = threadIdx.x & 63;
+    const pos_t tile_last = tile[kStretch - 1];
+    uint32_t pos[kN];
+    bool far[kN], any_far = false;
+#pragma unroll
+    for (uint32_t i = 0; i < kN; ++i) { pos[i] = 0; far[i] = need[i] && key[i] > tile_last; any_far |= far[i]; }
+#pragma unroll
+    for (uint32_t step = kStretch / 2; step; step >>= 1) {
+#pragma unroll
+        for (uint32_t i = 0; i < kN; ++i)
+            if (tile[pos[i] + step - 1] < key[i]) pos[i] += step;
+    }
+    uint32_t j[kN];
+#pragma unroll
+    for (uint32_t i = 0; i < kN; ++i) {
+        const uint32_t own = 64 * i + lane;                            // an answer lies behind its own element (end_len >= 1)
+        j[i] = pb + (pos[i] > own ? pos[i] : own + 1);
+    }
+    if (__any(any_far)) {                                              // tile_last is an element of the list (+inf is above every key)
+#pragma unroll
+        for (uint32_t i = 0; i < kN; ++i) {
+            const uint32_t jf = jump_far_lower_bound<pos_t>(P, F, pb + kStretch, m.pend, key[i], far[i]);
+            if (far[i]) j[i] = jf;
+        }
+    }
+#pragma unroll
+    for (uint32_t i = 0; i < kN; ++i) out[i] = need[i] && j[i] < m.pend ? m.begin + (j[i] - m.pbegin) : kNone;
 }
 
 // (link == nullptr: only the chain ends are wanted -- first positions without tuples)
@@ -533,21 +589,30 @@ __device__ __forceinline__ bool link_finish(const pos_t* __restrict__ P, const S
 // Steps that lie inside one segment (almost all of them: lists are long) keep the segment's metadata in registers,
 // search as a wave behind the previous step's answer and have the next step's positions already in flight.
 // Slot numbers are 32-bit inside a chunk (r1 <= 0xF0000000 + alignment), so all loop arithmetic is.
-template <typename pos_t, bool kLast>
+// kJump: the pass also leaves jump[] for the slots of the class inside [jlo, jhi), the slot range of the chain passes: the raw target
+// (stretch_jump_targets above) for the slots of a first list, whose endp[] it then does not write -- the jump was its only reader --
+// and kNone for every other level.
+template <typename pos_t, bool kLast, bool kJump>
 __global__ void __launch_bounds__(256) join_link_kernel(const pos_t* __restrict__ P, const pos_t* __restrict__ F /* fences of P, or null */,
                                                         const uint32_t* __restrict__ seg_begin, uint32_t nseg,
                                                         const SegMeta* __restrict__ sm, uint32_t r0, uint32_t r1,
                                                         FeasRef fb, uint64_t* __restrict__ fbits_out,
-                                                        pos_t* __restrict__ endp, uint32_t* __restrict__ link)
+                                                        pos_t* __restrict__ endp, uint32_t* __restrict__ link,
+                                                        const QueryMeta* __restrict__ qm, uint32_t jlo, uint32_t jhi, uint32_t* __restrict__ jump)
 {
+    __shared__ pos_t s_stretch[kJump ? 4 : 1][kJump ? kStretch : 1];
+    constexpr pos_t kInf = (pos_t)~(pos_t)0;
     const uint32_t lane = threadIdx.x & 63;
     const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     if (wave * kLinkRun >= (uint64_t)(r1 - r0)) return;
+    pos_t* const tile = s_stretch[kJump ? threadIdx.x >> 6 : 0];
     const uint32_t run_begin = r0 + (uint32_t)wave * kLinkRun;
     const uint32_t run_end = r1 - run_begin > kLinkRun ? run_begin + kLinkRun : r1;
     uint32_t s_w = wave_seg_find(seg_begin, nseg, run_begin);     // wave-uniform: segment of `base`
     uint32_t seg_end = seg_begin[s_w + 1];
     SegMeta m = sm[s_w], nx = sm[m.next];
+    bool lvl0 = kJump && m.level == 0;                             // wave-uniform: the steps inside this segment find their jumps
+    uint64_t end_len = lvl0 ? qm[m.query].end_len : 0;
     uint32_t hint_seg = kNone, hint = 0;                           // answer of the last lane of the previous step and its segment
     pos_t x_pre = 0, x_pre1 = 0;
     bool have_pre = false, have_pre1 = false;
@@ -556,6 +621,8 @@ __global__ void __launch_bounds__(256) join_link_kernel(const pos_t* __restrict_
             while (seg_begin[s_w + 1] <= base) ++s_w;
             seg_end = seg_begin[s_w + 1];
             m = sm[s_w]; nx = sm[m.next];
+            lvl0 = kJump && m.level == 0;
+            end_len = lvl0 ? qm[m.query].end_len : 0;
             have_pre = false; have_pre1 = false;
         }
         if (run_end - base >= 128 && base + 127 < seg_end) {
@@ -567,8 +634,13 @@ __global__ void __launch_bounds__(256) join_link_kernel(const pos_t* __restrict_
             const uint32_t room = seg_end - base - 128;            // and of the segment
             have_pre = left > 0 && (left < 64 ? left : 64u) <= room;
             have_pre1 = left >= 128 && room >= 128;
-            if (have_pre) x_pre = e0 + 128 < run_end ? P[phys_of(m, e0 + 128)] : (pos_t)0;
-            if (have_pre1) x_pre1 = P[phys_of(m, e1 + 128)];
+            if (lvl0) {                                            // the stretch behind the pair: the next pair's keys where there is one
+                x_pre = e0 + 128 < m.end ? P[phys_of(m, e0 + 128)] : kInf;
+                x_pre1 = e1 + 128 < m.end ? P[phys_of(m, e1 + 128)] : kInf;
+            } else {
+                if (have_pre) x_pre = e0 + 128 < run_end ? P[phys_of(m, e0 + 128)] : (pos_t)0;
+                if (have_pre1) x_pre1 = P[phys_of(m, e1 + 128)];
+            }
             pos_t tlo0, thi0, tlo1, thi1, v0 = 0, v1 = 0;
             const bool want0 = gap_window<pos_t>((uint64_t)x0, nx.lo, nx.hi, tlo0, thi0);
             const bool want1 = gap_window<pos_t>((uint64_t)x1, nx.lo, nx.hi, tlo1, thi1);
@@ -578,10 +650,27 @@ __global__ void __launch_bounds__(256) join_link_kernel(const pos_t* __restrict_
             wave_lower_bound2(P, F, hint, nx.pend, tlo0, want0, tlo1, want1, j0, v0, j1, v1);
             if (!want0) j0 = nx.pend;
             if (!want1) j1 = nx.pend;
-            const bool ok0 = link_finish<pos_t, kLast>(P, nx, fb, e0, want0, j0, v0, thi0, endp, link);
-            const bool ok1 = link_finish<pos_t, kLast>(P, nx, fb, e1, want1, j1, v1, thi1, endp, link);
+            pos_t end0 = 0, end1 = 0;
+            const bool ok0 = link_finish<pos_t, kLast>(P, nx, fb, e0, want0, j0, v0, thi0, endp, link, !lvl0, end0);
+            const bool ok1 = link_finish<pos_t, kLast>(P, nx, fb, e1, want1, j1, v1, thi1, endp, link, !lvl0, end1);
             const unsigned long long okm0 = __ballot(ok0), okm1 = __ballot(ok1);
             if (lane == 0) { fbits_out[base >> 6] = okm0; fbits_out[(base >> 6) + 1] = okm1; }
+            if (kJump) {
+                if (lvl0) {
+                    pos_t key[2] = {0, 0}, unused;
+                    const bool need[2] = {ok0 && gap_window<pos_t>((uint64_t)end0, end_len, end_len, key[0], unused),
+                                          ok1 && gap_window<pos_t>((uint64_t)end1, end_len, end_len, key[1], unused)};
+                    tile[lane] = x0; tile[64 + lane] = x1; tile[128 + lane] = x_pre; tile[192 + lane] = x_pre1;
+                    wave_sync();
+                    uint32_t out[2];
+                    stretch_jump_targets<pos_t, 2>(P, F, m, phys_of(m, base), tile, key, need, out);
+                    wave_sync();                                   // the next step overwrites the stretch
+                    jump[e0] = out[0]; jump[e1] = out[1];
+                } else {
+                    if (e0 >= jlo && e0 < jhi) jump[e0] = kNone;
+                    if (e1 >= jlo && e1 < jhi) jump[e1] = kNone;
+                }
+            }
             hint_seg = s_w;
             hint = __shfl(j1, 63);
             base += 64;                                            // the loop adds the other 64
@@ -604,9 +693,26 @@ __global__ void __launch_bounds__(256) join_link_kernel(const pos_t* __restrict_
             if (hint_seg != s_w) hint = wave_kary_lower_bound(P, F, nx.pbegin, nx.pend, (uint64_t)__shfl(tlo, 0));
             j = wave_lower_bound(P, F, hint, nx.pend, tlo, want, v);
             if (!want) j = nx.pend;
-            const bool ok = link_finish<pos_t, kLast>(P, nx, fb, e, want, j, v, thi, endp, link);
+            pos_t end = 0;
+            const bool ok = link_finish<pos_t, kLast>(P, nx, fb, e, want, j, v, thi, endp, link, !lvl0, end);
             const unsigned long long okm = __ballot(ok);
             if (lane == 0) fbits_out[base >> 6] = okm;
+            if (kJump) {
+                if (lvl0) {                                        // (a run or a list ends here: the stretch is loaded, not carried)
+                    pos_t key[1] = {0}, unused;
+                    const bool need[1] = {ok && gap_window<pos_t>((uint64_t)end, end_len, end_len, key[0], unused)};
+                    tile[lane] = active ? x : (e < m.end ? P[phys_of(m, e)] : kInf);
+#pragma unroll
+                    for (uint32_t r = 1; r < kStretch / 64; ++r) tile[64 * r + lane] = e + 64 * r < m.end ? P[phys_of(m, e + 64 * r)] : kInf;
+                    wave_sync();
+                    uint32_t out[1];
+                    stretch_jump_targets<pos_t, 1>(P, F, m, phys_of(m, base), tile, key, need, out);
+                    wave_sync();
+                    if (active) jump[e] = out[0];
+                } else if (active && e >= jlo && e < jhi) {
+                    jump[e] = kNone;
+                }
+            }
         } else {
             // ---- a segment border inside the step: every lane looks its own segment up ------------------
             have_pre = false;
@@ -619,14 +725,29 @@ __global__ void __launch_bounds__(256) join_link_kernel(const pos_t* __restrict_
                 const uint64_t x = P[phys_of(ml, e)];
                 const uint64_t tlo = sat_add(x, nl.lo), thi = sat_add(x, nl.hi);
                 j = gallop_lower_bound(P, (s == hint_seg) ? hint : nl.pbegin, nl.pend, tlo);
+                const bool first = kJump && ml.level == 0;         // a slot of a first list: its end goes into its jump, not into endp
+                pos_t end = 0;
                 if (e < ml.end) {                                  // padding slots between classes belong to no segment
                     if (kLast) {
                         ok = j < nl.pend && (uint64_t)P[j] <= thi;
-                        if (ok) { if (link) link[e] = j; endp[e] = P[j]; }
+                        if (ok) { if (link) link[e] = j; end = P[j]; if (!first) endp[e] = end; }
                     } else if (j < nl.pend) {
                         const uint32_t ej = next_feasible(fb, (uint64_t)nl.begin + (j - nl.pbegin));
-                        if (ej < nl.end && (uint64_t)P[phys_of(nl, ej)] <= thi) { ok = true; if (link) link[e] = ej; endp[e] = endp[ej]; }
+                        if (ej < nl.end && (uint64_t)P[phys_of(nl, ej)] <= thi) {
+                            ok = true;
+                            if (link) link[e] = ej;
+                            end = endp[ej];
+                            if (!first) endp[e] = end;
+                        }
                     }
+                }
+                if (kJump && e >= jlo && e < jhi) {
+                    uint32_t out = kNone;
+                    if (first && ok) {                             // (a key beyond the positions' range has no element at or after it)
+                        const uint32_t jp = gallop_lower_bound(P, phys_of(ml, e) + 1, ml.pend, sat_add((uint64_t)end, qm[ml.query].end_len));
+                        if (jp < ml.pend) out = ml.begin + (jp - ml.pbegin);
+                    }
+                    jump[e] = out;
                 }
             }
             const unsigned long long okm = __ballot(ok);
@@ -639,13 +760,15 @@ __global__ void __launch_bounds__(256) join_link_kernel(const pos_t* __restrict_
 }
 
 // jump[e] for level-0 elements: first feasible element of list 0 at or after end(e)+end_len (kNone = none);
-// slots of other levels get kNone so the tile pass can treat every slot alike.  Also the start of each chain.
+// slots of other levels get kNone so the tile pass can treat every slot alike.
 // Same walk as the link pass; the list searched is the element's own (the answers lie behind the element itself).
+// The pass of the single-list queries (class 0: every element is feasible and ends at itself, join_init_kernel), and of every
+// class when the workspace option "fuse_jump" is 0; with longer queries the link pass finds the jumps of its level-0 slots itself.
 template <typename pos_t>
 __global__ void __launch_bounds__(256) join_jump_kernel(const pos_t* __restrict__ P, const pos_t* __restrict__ F, const uint32_t* __restrict__ seg_begin, uint32_t nseg,
                                                         const SegMeta* __restrict__ sm, const QueryMeta* __restrict__ qm, uint64_t r0,
                                                         uint64_t r1, FeasRef fb, const pos_t* __restrict__ endp,
-                                                        uint32_t* __restrict__ jump, uint32_t* __restrict__ qstart)
+                                                        uint32_t* __restrict__ jump)
 {
     __shared__ pos_t s_tile[4][kTB];
     const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -669,7 +792,6 @@ __global__ void __launch_bounds__(256) join_jump_kernel(const pos_t* __restrict_
             // ---- long list: blocks of kBlk slots against tiles of the same list ------------------------------
             const uint64_t piece_end = run_end < m.end ? run_end : (uint64_t)m.end;
             const uint64_t end_len = qm[m.query].end_len;
-            if (cur == m.begin && lane == 0) { const uint32_t me = next_feasible(fb, cur); qstart[m.query] = me < m.end ? me : kNone; }
             uint32_t fence = 0;
             for (uint64_t blk0 = cur; blk0 < piece_end; blk0 += kBlk) {
                 const uint64_t blk1 = blk0 + kBlk < piece_end ? blk0 + kBlk : piece_end;
@@ -728,7 +850,6 @@ __global__ void __launch_bounds__(256) join_jump_kernel(const pos_t* __restrict_
                             if (ej < ml.end) out = ej;
                         }
                     }
-                    if ((uint32_t)e == ml.begin) { const uint32_t me = next_feasible(fb, e); qstart[ml.query] = me < ml.end ? me : kNone; }
                 }
                 jump[e] = out;
             }
@@ -744,25 +865,77 @@ __global__ void __launch_bounds__(256) join_jump_kernel(const pos_t* __restrict_
 //           leaving one record per tile visited and the query's match count;
 //   emit  : one lane per record lists the matches inside its tile.
 constexpr uint32_t kTile = 1024;
+constexpr uint32_t kTileFeasWords = 32;     // feasibility words the tile pass stages: the tile's own 16 and as many behind them
 
 // per-slot state of the doubling, one word: [0,10) next element inside the tile, bit 10 = chain left the tile,
 // [11,21) chain elements covered so far minus one, [21,31) last chain element inside the tile
-__global__ void __launch_bounds__(256) chain_tiles_kernel(const uint32_t* __restrict__ jump, uint64_t t0 /* multiple of kTile */,
-                                                          uint64_t r1, uint2* __restrict__ xh)
+//
+// The pass first SETTLES the jump words, in place: the link pass leaves the raw target of a slot, the lower bound of its key in its own
+// list, because the feasibility of that list was still being written when it ran.  The settled word is the first feasible slot at or
+// after the raw one, if that is still a slot of the same segment (padding slots are never feasible, so "below the begin of the next
+// segment" is "below the end of this one"), else kNone.  A word that is settled already -- the separate jump pass writes such -- is a
+// feasible slot of its own segment and stays as it is.
+__global__ void __launch_bounds__(256) chain_tiles_kernel(uint32_t* __restrict__ jump, uint64_t t0 /* multiple of kTile */,
+                                                          uint64_t r1, FeasRef fb, const uint32_t* __restrict__ seg_begin, uint32_t nseg,
+                                                          uint2* __restrict__ xh)
 {
     static_assert(kTile == 1024, "the packed word holds 10-bit tile offsets");
     __shared__ uint32_t s_ext[kTile];
     __shared__ uint32_t s_st[2][kTile];
     constexpr uint32_t kDone = 1u << 10;
+    __shared__ uint64_t s_fb[kTileFeasWords];
     const uint64_t base = t0 + (uint64_t)blockIdx.x * kTile;
     const uint64_t tile_end = base + kTile;
+    // The targets lie a few slots behind their slot: the feasibility words of the tile and of the slots behind it are staged in LDS
+    // by loads that wait for nothing, so a settled word costs no second round trip after the jump word's own.  (every target is a
+    // slot below r1, so no word behind that of r1 - 1 is asked for)
+    uint32_t jw[4];
+#pragma unroll
+    for (uint32_t r = 0; r < 4; ++r) {
+        const uint64_t e = base + threadIdx.x + 256 * r;
+        jw[r] = e < r1 ? jump[e] : kNone;
+    }
+    const uint64_t w_base = base >> 6;
+    if (threadIdx.x < kTileFeasWords) s_fb[threadIdx.x] = w_base + threadIdx.x <= ((r1 - 1) >> 6) ? fb.lvl0[w_base + threadIdx.x] : 0;
+    __syncthreads();
+    uint32_t moved = 0;                                              // bit r: the target of slot r is not the raw one
+#pragma unroll
+    for (uint32_t r = 0; r < 4; ++r) {
+        const uint32_t j = jw[r];
+        if (j != kNone) {
+            const uint64_t wi = ((uint64_t)j >> 6) - w_base;
+            const uint64_t bits = wi < kTileFeasWords ? s_fb[wi] >> (j & 63) : 0;
+            const uint32_t ej = bits ? j + (uint32_t)__ffsll((long long)bits) - 1 : next_feasible(fb, j);
+            moved |= (uint32_t)(ej != j) << r;
+            jw[r] = ej;
+        }
+    }
+    // a target that moved may have left its segment: the segment of the tile's first slot, once per wave that has such a target; the
+    // lanes walk on from it only where a border falls inside the tile
+    if (__any(moved != 0)) {
+        const uint32_t s_t = wave_seg_find(seg_begin, nseg, base);
+        const uint32_t t_next = seg_begin[s_t + 1];                  // begin of the next segment with slots (seg_begin[nseg + 1] = 2^32 - 1)
+#pragma unroll
+        for (uint32_t r = 0; r < 4; ++r) {
+            const uint64_t e = base + threadIdx.x + 256 * r;
+            if ((moved >> r) & 1) {
+                uint32_t lim = t_next;
+                if ((uint64_t)lim < tile_end) {
+                    uint32_t s = s_t;
+                    while (seg_begin[s + 1] <= e) ++s;
+                    lim = seg_begin[s + 1];
+                }
+                if (jw[r] >= lim) jw[r] = kNone;
+                jump[e] = jw[r];
+            }
+        }
+    }
     uint32_t st[4];
     bool open = false;
 #pragma unroll
     for (uint32_t r = 0; r < 4; ++r) {
         const uint32_t li = threadIdx.x + 256 * r;
-        const uint64_t e = base + li;
-        const uint32_t j = e < r1 ? jump[e] : kNone;
+        const uint32_t j = jw[r];
         const bool inside = j != kNone && (uint64_t)j < tile_end;
         s_ext[li] = j;                                   // where the chain goes when this is its last element inside the tile
         st[r] = (inside ? (uint32_t)(j - base) : kDone) | (li << 21);
@@ -795,8 +968,9 @@ __global__ void __launch_bounds__(256) chain_tiles_kernel(const uint32_t* __rest
     }
 }
 
-__global__ void chain_walk_kernel(const SegMeta* __restrict__ sm, const QueryMeta* __restrict__ qm, uint32_t nq,
-                                  const uint32_t* __restrict__ qstart, const uint2* __restrict__ xh, const uint32_t* __restrict__ rec_begin,
+// (a chain starts at the first feasible element of the query's first list)
+__global__ void chain_walk_kernel(const SegMeta* __restrict__ sm, const QueryMeta* __restrict__ qm, uint32_t nq, FeasRef fb,
+                                  const uint2* __restrict__ xh, const uint32_t* __restrict__ rec_begin,
                                   uint2* __restrict__ records, uint32_t* __restrict__ rec_count, unsigned long long* __restrict__ counts)
 {
     uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
@@ -805,9 +979,10 @@ __global__ void chain_walk_kernel(const SegMeta* __restrict__ sm, const QueryMet
     unsigned long long n_match = 0;
     uint32_t nrec = 0;
     if (Q.seg0 != kNone) {
-        const uint32_t mbegin = sm[Q.seg0].begin;
+        const uint32_t mbegin = sm[Q.seg0].begin, mend = sm[Q.seg0].end;
         uint2* rec = records + rec_begin[q];
-        uint32_t cur = qstart[q];
+        uint32_t cur = mbegin < mend ? next_feasible(fb, mbegin) : kNone;
+        if (cur >= mend) cur = kNone;
         while (cur != kNone) {
             uint2 v = xh[cur];
             rec[nrec++] = make_uint2(cur, mbegin + (uint32_t)n_match);

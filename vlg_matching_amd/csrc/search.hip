@@ -80,6 +80,8 @@ struct vlg_workspace {
     bool quad_walk = true;      // locate walks LF on the quad image of an index that has one (lf_walk.hpp: QuadWalk); 0 = the binary walk, for an
                                 // A/B inside one library.  Wide SA indices too: round 0 of their sweep then takes its elements one by one instead of
                                 // in the binary pairs of sweep_first_pair, and still wins (C4, ms per batch: locate 95.4 -> 85.9, batch 353.5 -> 342.6)
+    bool fuse_jump = true;      // the link pass of a class finds the jumps of its level-0 slots itself (join_device.hpp: join_link_kernel<.., kJump>);
+                                // 0 = the separate jump pass over all level-0 slots, for an A/B inside one library (also VLG_FUSE_JUMP=0)
     uint64_t sweep_min = 1ull << 22;    // below this many occurrences the persistent random-access kernel is used
     uint64_t sweep_tail = 1ull << 22;   // stragglers of a sweep are finished one lane each (C3, ms per batch: 2^20 214.0, 2^22 213.4, 2^24 213.7, 2^26 213.8)
     // K3u (kernels.hip): a batch that locates at least unsample_pct per cent of all text positions rebuilds the whole suffix array from
@@ -268,6 +270,7 @@ extern "C" vlg_status vlg_workspace_set_option(vlg_workspace* ws, const char* na
     if (!strcmp(name, "trail")) { ws->trail = value != 0; return VLG_OK; }
     if (!strcmp(name, "quad_walk")) { ws->quad_walk = value != 0; return VLG_OK; }
     if (!strcmp(name, "tuples")) { ws->tuples = value != 0; return VLG_OK; }
+    if (!strcmp(name, "fuse_jump")) { ws->fuse_jump = value != 0; return VLG_OK; }
     if (!strcmp(name, "filter")) { ws->filter = value != 0; return VLG_OK; }
     if (!strcmp(name, "filter_min")) { ws->filter_min = (uint64_t)value; return VLG_OK; }
     if (!strcmp(name, "filter_pivot")) { ws->filter_pivot = value != 0; return VLG_OK; }
@@ -659,7 +662,7 @@ constexpr uint64_t kJoinBytesPerSlot = 4 + 8 + 1;      // any slot: link, endp (
 constexpr uint64_t kJoinBytesPerSlot0 = 4 + 4 + 8 + 1; // slots of list 0: jump, mlist, xh (exit, hops), d_recq + d_rec (chain records)
 // ... and per item of the tables the host builds for a chunk (upper bounds with room to spare):
 constexpr uint64_t kJoinMetaPerSub = sizeof(SegMeta) + 48;      // d_sm; d_segb and compact_survivors' d_tseg, d_tcidx, d_trun0 (20 B)
-constexpr uint64_t kJoinMetaPerQuery = sizeof(QueryMeta) + 96;  // d_qm; d_counts, d_qstart, d_recb, d_recc (20 B)
+constexpr uint64_t kJoinMetaPerQuery = sizeof(QueryMeta) + 96;  // d_qm; d_counts, d_recb, d_recc (16 B)
 constexpr uint64_t kJoinMetaPerRecord = 48;                     // d_recq, d_rec (12 B per chain record)
 // Per-chunk metadata on top of `join_bytes` of join scratch.  Chain records: a first list of n slots overlaps at most n / kTile + 2
 // tiles, and kTile of its slots are more than 8192 B of scratch.  The constant pays for d_fb, the slots of the class alignment and of
@@ -1273,6 +1276,9 @@ vlg_status build_physical(const vlg_index* idx, vlg_workspace* ws, vlg_result* r
 
 namespace {
 
+// VLG_FUSE_JUMP=0: the separate jump pass, whatever the workspace option "fuse_jump" says
+inline bool fuse_jump_env() { static const bool on = [] { const char* e = getenv("VLG_FUSE_JUMP"); return !(e && e[0] == '0'); }(); return on; }
+
 // ---- join of the queries [q0,q1) against the physical lists -------------------------------------------
 // The stages run one after the other (run_join_chunk, below).  The host tables the async copies read are members: they outlive the
 // synchronize that ends gather().
@@ -1290,6 +1296,7 @@ struct JoinChunk {
     const uint32_t nseg = (uint32_t)(s1 - s0), nq = (uint32_t)(q1 - q0);
     ResultPiece piece{q0, q1};
     bool empty = false;                 // no live query, or no slot of a first list: the chunk has no match and launches no join
+    const bool fused = ws->fuse_jump && fuse_jump_env();        // the link passes find the level-0 jumps (link_classes, chain)
     // host tables
     svec<QueryMeta> qm;
     uint32_t kmax = 0, nlive = 0, n_rec = 0;
@@ -1307,7 +1314,7 @@ struct JoinChunk {
     FeasBits fb; uint64_t* lvl_ptr[kBitLevels]; FeasBits* d_fb = nullptr; FeasRef fref{nullptr, nullptr};
     uint32_t* jump = nullptr; uint32_t* mlist = nullptr; uint2* xh = nullptr;
     SegMeta* d_sm = nullptr; QueryMeta* d_qm = nullptr; uint32_t* d_segb = nullptr; unsigned long long* d_counts = nullptr;
-    uint32_t* d_qstart = nullptr; uint32_t* d_recb = nullptr; uint32_t* d_recc = nullptr; uint32_t* d_recq = nullptr; uint2* d_rec = nullptr;
+    uint32_t* d_recb = nullptr; uint32_t* d_recc = nullptr; uint32_t* d_recq = nullptr; uint2* d_rec = nullptr;
 
     // list lengths as the join sees them: the survivors of the window filter where it ran
     uint64_t eo(uint64_t s) const { return fg ? fg->eff[s - fg->sub0] : pl.occ[s]; }
@@ -1467,7 +1474,6 @@ struct JoinChunk {
         d_qm = A.take<QueryMeta>(nq);
         d_segb = A.take<uint32_t>(nlive + 2);
         d_counts = A.take<unsigned long long>(nq);
-        d_qstart = A.take<uint32_t>(nq);
         d_recb = A.take<uint32_t>(nq + 1);
         d_recc = A.take<uint32_t>(nq);
         d_recq = A.take<uint32_t>(n_rec + 1);
@@ -1482,7 +1488,6 @@ struct JoinChunk {
         VLG_HIP_TRY(hipMemcpyAsync(d_fb, &fb, sizeof fb, hipMemcpyHostToDevice, st));
         VLG_HIP_TRY(hipMemcpyAsync(d_recb, rec_begin.data(), (nq + 1) * 4, hipMemcpyHostToDevice, st));
         if (n_rec) VLG_HIP_TRY(hipMemcpyAsync(d_recq, rec_query.data(), n_rec * 4, hipMemcpyHostToDevice, st));
-        VLG_HIP_TRY(hipMemsetAsync(d_qstart, 0xFF, nq * 4, st));
         VLG_HIP_TRY(hipMemcpyAsync(d_sm, sm.data(), (nlive + 1) * sizeof(SegMeta), hipMemcpyHostToDevice, st));
         VLG_HIP_TRY(hipMemcpyAsync(d_segb, seg_begin.data(), (nlive + 2) * 4, hipMemcpyHostToDevice, st));
         VLG_HIP_TRY(hipMemcpyAsync(d_qm, qm.data(), nq * sizeof(QueryMeta), hipMemcpyHostToDevice, st));
@@ -1516,10 +1521,14 @@ struct JoinChunk {
         for (uint32_t dist = 1; dist < kmax; ++dist) {
             const uint64_t b0 = cls_slot_begin[dist], b1 = cls_slot_end[dist];
             if (b1 > b0) {
+                // a class that reaches into the slot range of the chain passes leaves the jump[] of its slots there: the raw targets of
+                // its first lists, kNone for the other levels (what it moves per slot: the position and the end or the jump, as before)
+                const bool jumps = fused && b0 < lvl0_end && b1 > lvl0_begin;
                 Timed t(ws, KS_JOIN_LINK, 8ull * (b1 - b0));
-                const auto kernel = dist == 1 ? join_link_kernel<pos_t, true> : join_link_kernel<pos_t, false>;
+                const auto kernel = jumps ? (dist == 1 ? join_link_kernel<pos_t, true, true> : join_link_kernel<pos_t, false, true>)
+                                          : (dist == 1 ? join_link_kernel<pos_t, true, false> : join_link_kernel<pos_t, false, false>);
                 hipLaunchKernelGGL(kernel, dim3(runs_grid(b1 - b0, kLinkRun)), dim3(256), 0, st, P, F, d_segb, nlive, d_sm, (uint32_t)b0, (uint32_t)b1, fref,
-                                   lvl_ptr[0], endp, link);
+                                   lvl_ptr[0], endp, link, d_qm, (uint32_t)lvl0_begin, (uint32_t)lvl0_end, jump);
             }
             if (vlg_status s = summarize_class(dist)) return s;
         }
@@ -1531,12 +1540,20 @@ struct JoinChunk {
     {
         {
             Timed t(ws, KS_JOIN_CHAIN, 8ull * (lvl0_end - lvl0_begin));
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(join_jump_kernel<pos_t>), dim3(runs_grid(lvl0_end - lvl0_begin)), dim3(256), 0, st, P, F, d_segb, nlive, d_sm,
-                               d_qm, lvl0_begin, lvl0_end, fref, endp, jump, d_qstart);
+            // the jumps the link passes did not leave: all of them (fuse_jump 0), or those of the single-list queries, class 0
+            const uint64_t jb = fused ? std::max(cls_slot_begin[0], lvl0_begin) : lvl0_begin, je = fused ? cls_slot_end[0] : lvl0_end;
+            if (je > jb)
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(join_jump_kernel<pos_t>), dim3(runs_grid(je - jb)), dim3(256), 0, st, P, F, d_segb, nlive, d_sm, d_qm, jb,
+                                   je, fref, endp, jump);
             if (t0 < lvl0_begin) VLG_HIP_TRY(hipMemsetAsync(jump + t0, 0xFF, (lvl0_begin - t0) * 4, st));   // slots of the first tile before the range
-            hipLaunchKernelGGL(chain_tiles_kernel, dim3((uint32_t)((lvl0_end - t0 + kTile - 1) / kTile)), dim3(256), 0, st, jump, t0, lvl0_end, xh);
-            hipLaunchKernelGGL(chain_walk_kernel, dim3((nq + 63) / 64), dim3(64), 0, st, d_sm, d_qm, nq, d_qstart, xh, d_recb, d_rec, d_recc,
-                               d_counts);
+            if (fused)                                              // ... and the <= 63 slots between two classes, which no pass owns
+                for (uint32_t d = 1; d < kmax; ++d) {
+                    const uint64_t p0 = std::max(cls_slot_end[d], lvl0_begin), p1 = std::min(cls_slot_begin[d - 1], lvl0_end);
+                    if (p1 > p0) VLG_HIP_TRY(hipMemsetAsync(jump + p0, 0xFF, (p1 - p0) * 4, st));
+                }
+            hipLaunchKernelGGL(chain_tiles_kernel, dim3((uint32_t)((lvl0_end - t0 + kTile - 1) / kTile)), dim3(256), 0, st, jump, t0, lvl0_end, fref, d_segb,
+                               nlive, xh);
+            hipLaunchKernelGGL(chain_walk_kernel, dim3((nq + 63) / 64), dim3(64), 0, st, d_sm, d_qm, nq, fref, xh, d_recb, d_rec, d_recc, d_counts);
             if (n_rec)
                 hipLaunchKernelGGL(chain_emit_kernel, dim3((n_rec + 3) / 4), dim3(256), 0, st, d_recb, d_recc, d_rec, n_rec, d_recq, jump, xh, lvl0_end, mlist);
         }

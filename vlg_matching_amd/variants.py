@@ -36,7 +36,8 @@ VARIANTS = {
 
 # a run of the default library with the runtime switches that select a second path (none of them masks another)
 ENV_RUNS = {
-    "env_paths": {"VLG_RESOLVE_GROUPED": "0", "VLG_SWEEP_LOOKAHEAD": "0", "VLG_NO_SPECULATIVE_COMPACT": "1", "VLG_WINDOW_SORT": "0"},
+    "env_paths": {"VLG_RESOLVE_GROUPED": "0", "VLG_SWEEP_LOOKAHEAD": "0", "VLG_NO_SPECULATIVE_COMPACT": "1", "VLG_WINDOW_SORT": "0",
+                  "VLG_FUSE_JUMP": "0"},
 }
 
 
