@@ -537,6 +537,33 @@ vlg_status vlg_queries_create_classes(const uint8_t* h_masks, const uint64_t* h_
  * fetch the offsets alone.  A result of any other search gives VLG_E_INVALID. */
 vlg_status vlg_result_class_intervals(const vlg_result* r, uint64_t* h_ivoff, uint64_t* h_l, uint64_t* h_r);
 
+/* Mismatch budgets: a sub-pattern may differ from the text in up to k of its positions (Hamming distance, substitutions only) -- primers
+ * with one or two substitutions for in-silico PCR ("fwd.{100,2000}?rev"), motifs with a tolerated residue.  Expanding a sub-pattern into
+ * its neighbours gives other answers, for the reason given for classes: the left-most, lazy, non-overlapping rule applies to the UNION
+ * of the neighbours' occurrences.
+ * A sub-pattern with the positions S_0 .. S_{m-1} (sets of bytes; one byte each when it is literal) and the budget k OCCURS AT v when
+ * 0 <= v, v + m <= n and #{t : T[v + t] not in S_t} <= k.  m, and with it lo / hi / end_len, stay as parsed; the 0 byte is never
+ * substituted in (the sentinel is not text); k >= m means "every position may differ" and behaves as k = m.  The matches of a query
+ * are the left-most, lazy, non-overlapping ones over these occurrence lists; nothing else about a query changes.
+ *   vlg_queries_set_mismatches  host only, no device, no stream (the contract of vlg_queries_set_windows).  h_k has
+ *     vlg_queries_subpatterns(q) entries in batch order; NULL or all zeros removes the budgets, and the batch is what it was.  Any batch
+ *     of bytes takes them: vlg_queries_parse, _create, _parse_classes, _create_classes.  The query syntax has no form for a budget.
+ *   vlg_queries_get_mismatches  *has (optional) = 1 when a budget > 0 is set; h_k (optional) receives the budgets, zeros when none is set.
+ * VLG_E_UNSUPPORTED, the batch left as it was and no device touched: an integer batch (vlg_queries_parse_int, _parse_int_mapped);
+ * vlg_queries_set_mismatches on a batch that carries windows; vlg_queries_set_windows on a batch that carries budgets.
+ * vlg_search_batch answers a batch with budgets on the road of a batch with classes (byte index, n <= 2^32 + 1): a distinct sub-pattern
+ * is a content AND its effective budget min(k, m); one with budget 0 is searched as without budgets, one with a budget > 0 by a
+ * backward search that branches over every byte the text has and carries the misses so far with each SA interval -- its frontier ends
+ * as one interval per distinct string within the budget that occurs, ascending and disjoint, under the same "class_intervals" cap and
+ * the same VLG_E_WORKSPACE.  The first k steps of such a search are unconstrained: sigma^k intervals at least are needed for them.
+ * Summary and vlg_result_class_intervals as for a batch with classes (the latter for any result of this road, a batch of literal
+ * sub-patterns with budgets included); the kernel-stat class "class_search" counts the budgeted searches too.
+ * Out of scope, refused with VLG_E_UNSUPPORTED before any launch when the batch has budgets: insertions and deletions (there is no
+ * form for them), collective searches, integer-alphabet indexes, vlg_queries_occurrences, vlg_queries_intervals, vlg_wtsa_ranges,
+ * vlg_wtsa_search_batch and vlg_wtsa_search_window_batch. */
+vlg_status vlg_queries_set_mismatches(vlg_queries* q, const uint8_t* h_k);
+vlg_status vlg_queries_get_mismatches(const vlg_queries* q, int* has_mismatches, uint8_t* h_k);
+
 /* ------------------------------------------------------------------------------------------
  * Workspace, fused search, results.
  * ---------------------------------------------------------------------------------------- */

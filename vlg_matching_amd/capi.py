@@ -171,6 +171,8 @@ SYMBOLS = [
     ("vlg_queries_k", _I, [_P, _P]),
     ("vlg_queries_set_windows", _I, [_P, _P, _P]),
     ("vlg_queries_get_windows", _I, [_P, C.POINTER(C.c_int), _P, _P]),
+    ("vlg_queries_set_mismatches", _I, [_P, _P]),
+    ("vlg_queries_get_mismatches", _I, [_P, C.POINTER(C.c_int), _P]),
     ("vlg_queries_destroy", None, [_P]),
     ("vlg_workspace_create", _I, [_U64, _P, C.POINTER(_P)]),
     ("vlg_workspace_destroy", None, [_P]),

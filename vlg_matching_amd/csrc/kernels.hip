@@ -483,6 +483,93 @@ __global__ void __launch_bounds__(256) class_search_kernel(IndexView iv, const u
     }
 }
 
+// K2d: backward search with a budget of substitutions (Hamming distance <= k) per sub-pattern.  Scheduling, scratch layout and the
+// order argument are class_search_kernel's; what differs is what a step deals and what an entry carries.  The symbol list is every
+// byte 1..255 the text has -- the same at every step of every task, so a wave builds it once, in front of its tasks -- and a
+// frontier entry carries the misses e of its string so far in the top byte of its second word (l, r <= 2^33).  For a
+// (symbol c, parent) pair e' = e + !(row_p bit c); a
+// pair with e' > k takes no rank and keeps nothing.  Which pairs are kept does not touch the order: C[c] dominates and within one c
+// the rank is monotone in the parent's l, so the frontier stays ascending and disjoint -- one interval per distinct string within
+// the budget that occurs.  The last step writes its intervals without the miss count, so half 0 reads as class_search_kernel's.
+// task[2 t] = first mask row of the sub-pattern, task[2 t + 1] = its positions, with the budget (1 .. 255) in the top byte.
+template <class BV>
+__global__ void __launch_bounds__(256) approx_search_kernel(IndexView iv, const uint8_t* __restrict__ masks, const uint64_t* __restrict__ task,
+                                                            uint64_t n_tasks, uint32_t cap, ulonglong2* frontier, uint32_t* __restrict__ count,
+                                                            unsigned long long* __restrict__ stat_levels)
+{
+    __shared__ WalkLds<BV> s;
+    __shared__ uint8_t syms[4][256];                       // per wave: the bytes 1..255 of the text, ascending
+    stage_walk(s, iv);
+    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    constexpr uint64_t kEntryMask = (1ull << 56) - 1;
+    uint32_t levels = 0;
+    uint32_t nsym = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < 4; ++j) {
+        const uint32_t c = 64 * j + lane;
+        const bool on = c > 0 && iv.char2comp[c] != 0;
+        const unsigned long long b = __ballot(on);
+        if (on) syms[wv][nsym + (uint32_t)__popcll(b & below)] = (uint8_t)c;
+        nsym += (uint32_t)__popcll(b);
+    }
+    // (the list is read by other lanes of this wave than wrote it)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    for (uint64_t t = (uint64_t)blockIdx.x * 4 + wv; t < n_tasks; t += (uint64_t)gridDim.x * 4) {
+        const uint64_t pos0 = task[2 * t];
+        const uint32_t m = (uint32_t)(task[2 * t + 1] & kEntryMask), k = (uint32_t)(task[2 * t + 1] >> 56);
+        ulonglong2* const half[2] = {frontier + t * cap, frontier + (n_tasks + t) * cap};
+        uint32_t cur = 0, cnt = 1;                         // before the first step: the whole range with no miss, which is not stored
+        bool whole = true, over = false;
+        for (uint32_t p = m; p-- > 0 && cnt && !over;) {
+            const uint8_t* row = masks + (pos0 + p) * 32;
+            const ulonglong2* src = half[cur];
+            ulonglong2* dst = half[cur ^ 1];
+            const uint32_t total = nsym * cnt;             // (255 symbols, cap <= 2^20: fits)
+            uint32_t out = 0;
+            for (uint32_t base = 0; base < total && !over; base += 64) {
+                const uint32_t i = base + lane;
+                bool keep = false;
+                uint64_t nl = 0, nr = 0;
+                uint32_t e = 0;
+                if (i < total) {
+                    const uint32_t si = i / cnt, pi = i - si * cnt;
+                    const uint8_t c = syms[wv][si];
+                    uint64_t l = 0, r = iv.n - 1;
+                    if (!whole) { const ulonglong2 par = src[pi]; l = par.x; r = par.y & kEntryMask; e = (uint32_t)(par.y >> 56); }
+                    e += ((row[c >> 3] >> (c & 7)) & 1u) ^ 1u;
+                    if (e <= k) {                          // a parent at full budget takes its own symbols only
+                        const uint32_t cc = iv.char2comp[c];
+                        const uint64_t c_begin = s.C[cc];
+                        if (l == 0 && r + 1 == iv.n) { nl = c_begin; nr = s.C[cc + 1] - 1; keep = s.C[cc + 1] > c_begin; }      // as backward_search_kernel
+                        else {
+                            const uint64_t path = iv.paths[c];
+                            const uint64_t a = wt_rank_dev(iv, s, path, l, levels), b = wt_rank_dev(iv, s, path, r + 1, levels);
+                            nl = c_begin + a; nr = c_begin + b - 1; keep = b > a;
+                        }
+                    }
+                }
+                const unsigned long long kb = __ballot(keep);
+                const uint32_t at = out + (uint32_t)__popcll(kb & below);
+                out += (uint32_t)__popcll(kb);
+                if (out > cap) over = true;                // (wave-uniform) this turn would pass the cap: none of its lanes writes
+                else if (keep) dst[at] = make_ulonglong2(nl, p ? nr | ((uint64_t)e << 56) : nr);
+            }
+            cnt = out; cur ^= 1; whole = false;
+            __threadfence();                               // the next step's lanes read what other lanes wrote
+        }
+        if (!over && cnt && cur == 1) for (uint32_t i = lane; i < cnt; i += 64) half[0][i] = half[1][i];
+        if (lane == 0) count[t] = over ? kClassSearchOverflow : cnt;
+    }
+    if (stat_levels) {
+        unsigned long long tl = levels;
+        for (int o = 32; o > 0; o >>= 1) tl += __shfl_down(tl, o);
+        if ((threadIdx.x & 63) == 0 && tl) atomicAdd(stat_levels, tl);
+    }
+}
+
 // ---- member bit-vector: which SA indices are elements of the batch, and which (sweep_element explains what for) ----------------
 // bit i = one of the lists [l[d], l[d] + off[d + 1] - off[d]), d < n_lists, holds SA index i; the lists are pairwise disjoint and
 // ascend, and list d owns the slots [off[d], off[d + 1]) -- so the number of set bits before i IS the slot of index i.  Same 256-bit
@@ -1022,6 +1109,19 @@ vlg_status launch_class_search(const IndexView& iv, const uint8_t* d_masks, cons
     const dim3 grid((uint32_t)std::min<uint64_t>((n_tasks + 3) / 4, 16384));
     return on_bv(iv.bv_kind, [&](auto bv) {
         return launch(class_search_kernel<tag_t<decltype(bv)>>, grid, stream, iv, d_masks, d_task, n_tasks, cap, reinterpret_cast<ulonglong2*>(d_frontier), d_count,
+                      d_stat_levels);
+    });
+}
+
+vlg_status launch_approx_search(const IndexView& iv, const uint8_t* d_masks, const uint64_t* d_task, uint64_t n_tasks, uint32_t cap, uint64_t* d_frontier,
+                                uint32_t* d_count, unsigned long long* d_stat_levels, hipStream_t stream)
+{
+    if (!n_tasks) return VLG_OK;
+    if (!cap || cap > kClassIntervalsMax) return fail(VLG_E_INTERNAL, "approximate search: frontier cap out of range");
+    // the grid of launch_class_search
+    const dim3 grid((uint32_t)std::min<uint64_t>((n_tasks + 3) / 4, 16384));
+    return on_bv(iv.bv_kind, [&](auto bv) {
+        return launch(approx_search_kernel<tag_t<decltype(bv)>>, grid, stream, iv, d_masks, d_task, n_tasks, cap, reinterpret_cast<ulonglong2*>(d_frontier), d_count,
                       d_stat_levels);
     });
 }

@@ -17,6 +17,11 @@ constexpr uint32_t kClassIntervalsMax = 1u << 20;
 constexpr uint32_t kClassSearchOverflow = 0xFFFFFFFFu;
 vlg_status launch_class_search(const IndexView& iv, const uint8_t* d_masks, const uint64_t* d_task, uint64_t n_tasks, uint32_t cap, uint64_t* d_frontier,
                                uint32_t* d_count, unsigned long long* d_stat_levels, hipStream_t stream);
+// Mismatch budgets (approx_search_kernel): the same arguments, scratch and result.  d_task[2 t + 1] carries the budget k (1 .. 255, at
+// most the positions) in its top byte; task t's result is one interval per distinct string within Hamming distance k of the rows
+// that occurs in the text.
+vlg_status launch_approx_search(const IndexView& iv, const uint8_t* d_masks, const uint64_t* d_task, uint64_t n_tasks, uint32_t cap, uint64_t* d_frontier,
+                                uint32_t* d_count, unsigned long long* d_stat_levels, hipStream_t stream);
 template <typename pos_t>
 vlg_status launch_expand(const uint64_t* d_l, const uint64_t* d_out_off, uint64_t n_pat, uint64_t total, pos_t* d_io, uint32_t* d_seg,
                          hipStream_t stream);

@@ -539,6 +539,7 @@ extern "C" vlg_status vlg_queries_set_windows(vlg_queries* q, const uint64_t* h_
     if (!q) return fail(VLG_E_INVALID, "null argument");
     if (!h_begin && !h_end) { q->win_begin.clear(); q->win_end.clear(); return VLG_OK; }
     if (q->has_classes()) return fail(VLG_E_UNSUPPORTED, "a batch with character classes takes no text windows");
+    if (q->has_mismatches()) return fail(VLG_E_UNSUPPORTED, "a batch with mismatch budgets takes no text windows");
     // (checked before anything is stored: a refused call keeps the batch's previous windows)
     if (h_begin && h_end)
         for (uint64_t j = 0; j < q->nq; ++j)
@@ -559,6 +560,26 @@ extern "C" vlg_status vlg_queries_get_windows(const vlg_queries* q, int* has_win
         if (h_begin) h_begin[j] = has ? q->win_begin[j] : 0;
         if (h_end) h_end[j] = has ? q->win_end[j] : ~0ull;
     }
+    return VLG_OK;
+}
+extern "C" vlg_status vlg_queries_set_mismatches(vlg_queries* q, const uint8_t* h_k)
+{
+    if (!q) return fail(VLG_E_INVALID, "null argument");
+    bool any = false;
+    for (uint64_t s = 0; h_k && s < q->nsub && !any; ++s) any = h_k[s] != 0;
+    if (!any) { q->sub_k.clear(); return VLG_OK; }                       // (the batch is what it was before it had budgets)
+    if (q->sym_bytes == 4) return fail(VLG_E_UNSUPPORTED, "mismatch budgets are searched on a byte index: an integer batch takes none");
+    if (q->has_windows()) return fail(VLG_E_UNSUPPORTED, "a batch with text windows takes no mismatch budgets");
+    std::vector<uint8_t> k(h_k, h_k + q->nsub);
+    q->sub_k.swap(k);
+    return VLG_OK;
+}
+extern "C" vlg_status vlg_queries_get_mismatches(const vlg_queries* q, int* has_mismatches, uint8_t* h_k)
+{
+    if (!q) return fail(VLG_E_INVALID, "null argument");
+    const bool has = q->has_mismatches();
+    if (has_mismatches) *has_mismatches = has ? 1 : 0;
+    if (h_k) for (uint64_t s = 0; s < q->nsub; ++s) h_k[s] = has ? q->sub_k[s] : 0;
     return VLG_OK;
 }
 extern "C" void vlg_queries_destroy(vlg_queries* q)

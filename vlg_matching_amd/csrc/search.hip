@@ -2299,13 +2299,19 @@ uint64_t fold_checksum(const unsigned long long* stats) { return std::accumulate
 // (literal ones by backward_search_kernel: one interval), the intervals come to the host, and per super-chunk the intervals of a
 // distinct sub-pattern are expanded back to back into ONE list, located by the random-access walks (the stages of vlg_locate_batch),
 // sorted inside itself and joined by plan_joins / run_joins unchanged.
+// Mismatch budgets (queries.cpp: vlg_queries_set_mismatches) take the same road: a sub-pattern with a budget > 0, literal or not, has
+// one interval per distinct string within the budget that occurs (kernels.hip: approx_search_kernel), its effective budget
+// min(k, m) is part of what makes it distinct, and one with budget 0 goes where it went without budgets.
 vlg_status run_class_batch(const vlg_index* idx, const vlg_queries* q, vlg_workspace* ws, vlg_result* res, PhaseTrace& tr)
 {
     hipStream_t st = ws->stream;
     const uint64_t nsub = q->nsub, n = idx->hdr.n;
     const uint32_t cap = ws->class_intervals;
-    // ---- distinct sub-patterns, by content: literal ones by their bytes, the others by their mask rows ---------------------------
+    const bool budgets = q->has_mismatches();
+    const auto literal = [&](uint64_t s) { return !q->has_classes() || q->sub_literal[s] != 0; };
+    // ---- distinct sub-patterns, by content and budget: literal ones by their bytes, the others by their mask rows ------------------
     std::vector<uint32_t> sub_d(nsub, 0);
+    std::vector<uint8_t> sub_kb(nsub, 0);                         // effective budgets
     std::vector<uint64_t> d_sub;                                  // per distinct sub-pattern: the first sub-pattern of the batch that is it
     {
         std::unordered_map<std::string, uint32_t> seen;
@@ -2313,8 +2319,10 @@ vlg_status run_class_batch(const vlg_index* idx, const vlg_queries* q, vlg_works
         std::string key;
         for (uint64_t s = 0; s < nsub; ++s) {
             const uint64_t a = q->suboff[s], b = q->suboff[s + 1];
-            if (q->sub_literal[s]) { key.assign(1, 'L'); key.append(reinterpret_cast<const char*>(q->blob.data() + a), b - a); }
-            else { key.assign(1, 'C'); key.append(reinterpret_cast<const char*>(q->masks.data() + a * 32), (b - a) * 32); }
+            const uint64_t kb = budgets ? std::min<uint64_t>(q->sub_k[s], b - a) : 0;        // k >= m: every position may differ
+            sub_kb[s] = (uint8_t)kb;
+            if (literal(s)) { key.assign(1, 'L'); key.push_back((char)kb); key.append(reinterpret_cast<const char*>(q->blob.data() + a), b - a); }
+            else { key.assign(1, 'C'); key.push_back((char)kb); key.append(reinterpret_cast<const char*>(q->masks.data() + a * 32), (b - a) * 32); }
             const auto it = seen.emplace(key, (uint32_t)d_sub.size());
             if (it.second) d_sub.push_back(s);
             sub_d[s] = it.first->second;
@@ -2322,24 +2330,37 @@ vlg_status run_class_batch(const vlg_index* idx, const vlg_queries* q, vlg_works
     }
     const uint64_t nd = d_sub.size();
     if (nd >= 0xFFFFFFF0ull) return fail(VLG_E_UNSUPPORTED, "too many distinct sub-patterns in one batch");
-    std::vector<uint32_t> lit, cls;                               // distinct ids of either kind
-    for (uint32_t d = 0; d < nd; ++d) (q->sub_literal[d_sub[d]] ? lit : cls).push_back(d);
-    const uint64_t nlit = lit.size(), ncls = cls.size();
-    // ---- device memory of the front: counters, the literal patterns and their intervals, tasks, counts, the frontier -----------------
-    svec<uint8_t> lblob;
-    svec<uint64_t> loff(nlit + 1, 0), task(2 * std::max<uint64_t>(ncls, 1), 0);
+    std::vector<uint32_t> lit, cls, apx;                          // distinct ids: literal and class without a budget, either with one
+    for (uint32_t d = 0; d < nd; ++d) (sub_kb[d_sub[d]] ? apx : literal(d_sub[d]) ? lit : cls).push_back(d);
+    const uint64_t nlit = lit.size(), ncls = cls.size(), napx = apx.size();
+    // ---- device memory of the front: counters, the literal patterns and their intervals, tasks, rows, counts, the frontier -----------
+    svec<uint8_t> lblob, arows;
+    svec<uint64_t> loff(nlit + 1, 0), task(2 * std::max<uint64_t>(ncls + napx, 1), 0);
     for (uint64_t i = 0; i < nlit; ++i) {
         const uint64_t s = d_sub[lit[i]];
         lblob.insert(lblob.end(), q->blob.begin() + q->suboff[s], q->blob.begin() + q->suboff[s + 1]);
         loff[i + 1] = lblob.size();
     }
     for (uint64_t i = 0; i < ncls; ++i) { const uint64_t s = d_sub[cls[i]]; task[2 * i] = q->suboff[s]; task[2 * i + 1] = q->suboff[s + 1] - q->suboff[s]; }
+    // a budgeted sub-pattern reads 256-bit rows: those of the batch, or -- a batch without classes has none -- rows made here, one bit each
+    const bool own_rows = napx && !q->has_classes();
+    for (uint64_t i = 0; i < napx; ++i) {
+        const uint64_t s = d_sub[apx[i]], a = q->suboff[s], m = q->suboff[s + 1] - a;
+        task[2 * (ncls + i)] = own_rows ? arows.size() / 32 : a;
+        task[2 * (ncls + i) + 1] = m | ((uint64_t)sub_kb[s] << 56);
+        if (own_rows) {
+            arows.resize(arows.size() + m * 32, 0);
+            uint8_t* row = arows.data() + arows.size() - m * 32;
+            for (uint64_t p = 0; p < m; ++p) { const uint8_t c = q->blob[a + p]; row[p * 32 + (c >> 3)] = (uint8_t)(1u << (c & 7)); }
+        }
+    }
     const uint64_t kClassScratch = 64ull << 20;                  // the frontiers of one group of tasks
-    const uint64_t group = std::max<uint64_t>(1, std::min<uint64_t>(std::max<uint64_t>(ncls, 1), kClassScratch / (32ull * cap)));
+    const uint64_t group = std::max<uint64_t>(1, std::min<uint64_t>(std::max<uint64_t>(std::max(ncls, napx), 1), kClassScratch / (32ull * cap)));
     const uint64_t st_bytes = align_up(kStatsWords * 8, 256), lb_bytes = align_up(lblob.size() + 16, 256), lo_bytes = align_up((nlit + 1) * 8, 256);
-    const uint64_t tk_bytes = align_up(2 * (ncls + 1) * 8, 256), ct_bytes = align_up(group * 4, 256), fr_bytes = align_up(2 * group * cap * 16, 256);
+    const uint64_t tk_bytes = align_up(2 * (ncls + napx + 1) * 8, 256), ct_bytes = align_up(group * 4, 256), fr_bytes = align_up(2 * group * cap * 16, 256);
+    const uint64_t ar_bytes = align_up(arows.size() + 32, 256);
     uint8_t* head = nullptr;
-    if (vlg_status hs = ws_head(ws, st_bytes + lb_bytes + 3 * lo_bytes + tk_bytes + ct_bytes + fr_bytes, &head)) return hs;
+    if (vlg_status hs = ws_head(ws, st_bytes + lb_bytes + 3 * lo_bytes + tk_bytes + ct_bytes + fr_bytes + ar_bytes, &head)) return hs;
     unsigned long long* d_stats = (unsigned long long*)head;
     uint8_t* d_lblob = head + st_bytes;
     uint64_t* d_loff = (uint64_t*)(d_lblob + lb_bytes);
@@ -2348,6 +2369,7 @@ vlg_status run_class_batch(const vlg_index* idx, const vlg_queries* q, vlg_works
     uint64_t* d_task = (uint64_t*)((uint8_t*)d_lr + lo_bytes);
     uint32_t* d_count = (uint32_t*)((uint8_t*)d_task + tk_bytes);
     uint64_t* d_frontier = (uint64_t*)((uint8_t*)d_count + ct_bytes);
+    uint8_t* d_arows = (uint8_t*)d_frontier + fr_bytes;
     VLG_HIP_TRY(hipMemsetAsync(d_stats, 0, kStatsWords * 8, st));
     ws->sample_reads = 0;
     ws->x_agreed = 0;
@@ -2368,15 +2390,19 @@ vlg_status run_class_batch(const vlg_index* idx, const vlg_queries* q, vlg_works
         for (uint64_t i = 0; i < nlit; ++i)
             if (hr[i] + 1 > hl[i]) { piece_l[lit[i]].push_back(hl[i]); piece_r[lit[i]].push_back(hr[i]); }
     }
-    if (ncls) {
-        VLG_HIP_TRY(hipMemcpyAsync(d_task, task.data(), 2 * ncls * 8, hipMemcpyHostToDevice, st));
+    // the branching searches, a group of tasks at a time: class sub-patterns, then the budgeted ones (either kind: the same tasks,
+    // scratch, count read-back and strided frontier copy)
+    const auto branching = [&](const std::vector<uint32_t>& ids, const uint64_t* d_tk, const uint8_t* d_rows, bool approx) -> vlg_status {
+        const uint64_t nt = ids.size();
         svec<uint32_t> hc(group);
         svec<uint64_t> hf;
-        for (uint64_t g0 = 0; g0 < ncls; g0 += group) {
-            const uint64_t g = std::min<uint64_t>(group, ncls - g0);
+        for (uint64_t g0 = 0; g0 < nt; g0 += group) {
+            const uint64_t g = std::min<uint64_t>(group, nt - g0);
             {
                 Timed t(ws, KS_CLASS_SEARCH, 0);
-                if (vlg_status s = launch_class_search(idx->view, q->d_masks, d_task + 2 * g0, g, cap, d_frontier, d_count, d_stats + 3, st)) return s;
+                if (vlg_status s = approx ? launch_approx_search(idx->view, d_rows, d_tk + 2 * g0, g, cap, d_frontier, d_count, d_stats + 3, st)
+                                          : launch_class_search(idx->view, d_rows, d_tk + 2 * g0, g, cap, d_frontier, d_count, d_stats + 3, st))
+                    return s;
             }
             VLG_HIP_TRY(hipMemcpyAsync(hc.data(), d_count, g * 4, hipMemcpyDeviceToHost, st));
             VLG_HIP_TRY(hipStreamSynchronize(st));
@@ -2384,10 +2410,11 @@ vlg_status run_class_batch(const vlg_index* idx, const vlg_queries* q, vlg_works
             for (uint64_t i = 0; i < g; ++i) {
                 if (hc[i] == kClassSearchOverflow) {
                     // (nothing else is launched: the batch ends here)
-                    const uint64_t s = d_sub[cls[g0 + i]];
+                    const uint64_t s = d_sub[ids[g0 + i]];
                     const uint64_t qi = (uint64_t)(std::upper_bound(q->qsub.begin(), q->qsub.end(), s) - q->qsub.begin()) - 1;
                     return fail(VLG_E_WORKSPACE, "query " + std::to_string(qi) + ", sub-pattern " + std::to_string(s - q->qsub[qi]) + ": more than " +
-                                                     std::to_string(cap) + " SA intervals at one step of its class search (workspace option \"class_intervals\")");
+                                                     std::to_string(cap) + " SA intervals at one step of its " + (approx ? "approximate" : "class") +
+                                                     " search (workspace option \"class_intervals\")");
                 }
                 widest = std::max<uint64_t>(widest, hc[i]);
             }
@@ -2397,11 +2424,18 @@ vlg_status run_class_batch(const vlg_index* idx, const vlg_queries* q, vlg_works
             VLG_HIP_TRY(hipMemcpy2DAsync(hf.data(), widest * 16, d_frontier, (size_t)cap * 16, widest * 16, g, hipMemcpyDeviceToHost, st));
             VLG_HIP_TRY(hipStreamSynchronize(st));
             for (uint64_t i = 0; i < g; ++i) {
-                const uint32_t d = cls[g0 + i];
+                const uint32_t d = ids[g0 + i];
                 piece_l[d].reserve(hc[i]); piece_r[d].reserve(hc[i]);
                 for (uint64_t j = 0; j < hc[i]; ++j) { piece_l[d].push_back(hf[(i * widest + j) * 2]); piece_r[d].push_back(hf[(i * widest + j) * 2 + 1]); }
             }
         }
+        return VLG_OK;
+    };
+    if (ncls + napx) VLG_HIP_TRY(hipMemcpyAsync(d_task, task.data(), 2 * (ncls + napx) * 8, hipMemcpyHostToDevice, st));
+    if (ncls) if (vlg_status s = branching(cls, d_task, q->d_masks, false)) return s;
+    if (napx) {
+        if (own_rows) VLG_HIP_TRY(hipMemcpyAsync(d_arows, arows.data(), arows.size(), hipMemcpyHostToDevice, st));
+        if (vlg_status s = branching(apx, d_task + 2 * ncls, own_rows ? d_arows : q->d_masks, true)) return s;
     }
     tr.mark("class search");
     std::vector<uint64_t> dl_, dr_;
@@ -2557,11 +2591,15 @@ extern "C" vlg_status vlg_search_batch(const vlg_index* idx, const vlg_queries* 
     // (every rank holds the same batch and refuses alike, before anything is launched or exchanged: no rank waits for another)
     if (q->has_windows() && ws->x_ranks > 1) return fail(VLG_E_UNSUPPORTED, "a collective search takes no text windows (vlg_queries_set_windows)");
     // the one branch of a batch with character classes: without them nothing of that path is launched, waited for or copied
-    const bool classes = q->has_classes();
+    const bool classes = q->has_classes() || q->has_mismatches();
     if (classes) {
-        if (idx->is_int) return fail(VLG_E_UNSUPPORTED, "character classes are searched on a byte index");
-        if (ws->x_ranks > 1) return fail(VLG_E_UNSUPPORTED, "a collective search takes no batch with character classes");
-        if (idx->hdr.n > (1ull << 32) + 1) return fail(VLG_E_UNSUPPORTED, "character classes: the text needs 64-bit positions");
+        // (a batch with classes keeps the words it always had)
+        const bool c = q->has_classes();
+        if (idx->is_int) return fail(VLG_E_UNSUPPORTED, c ? "character classes are searched on a byte index" : "mismatch budgets are searched on a byte index");
+        if (ws->x_ranks > 1)
+            return fail(VLG_E_UNSUPPORTED, c ? "a collective search takes no batch with character classes" : "a collective search takes no batch with mismatch budgets");
+        if (idx->hdr.n > (1ull << 32) + 1)
+            return fail(VLG_E_UNSUPPORTED, c ? "character classes: the text needs 64-bit positions" : "mismatch budgets: the text needs 64-bit positions");
     }
     hipStream_t st = ws->stream;
     vlg_result* res = new_result(q->nq, q->qsub);
@@ -2654,6 +2692,7 @@ extern "C" vlg_status vlg_queries_intervals(const vlg_index* idx, const vlg_quer
 {
     if (!idx || !q || (q->nsub && (!h_l || !h_r))) return fail(VLG_E_INVALID, "null argument");
     if (q->has_classes()) return fail(VLG_E_UNSUPPORTED, "a batch with character classes has several SA intervals per sub-pattern (vlg_search_batch + vlg_result_class_intervals)");
+    if (q->has_mismatches()) return fail(VLG_E_UNSUPPORTED, "a batch with mismatch budgets has several SA intervals per sub-pattern (vlg_search_batch + vlg_result_class_intervals)");
     if (idx->is_int != (q->sym_bytes == 4) && q->nsub) return fail(VLG_E_INVALID, "query batch and index are of different alphabets");
     const uint64_t nsub = q->nsub;
     if (!nsub) return VLG_OK;
@@ -2676,6 +2715,7 @@ extern "C" vlg_status vlg_queries_occurrences(const vlg_index* idx, const vlg_qu
 {
     if (!idx || !q || (q->nsub && !h_occ)) return fail(VLG_E_INVALID, "null argument");
     if (q->has_classes()) return fail(VLG_E_UNSUPPORTED, "a batch with character classes has several SA intervals per sub-pattern (vlg_search_batch + vlg_result_class_intervals)");
+    if (q->has_mismatches()) return fail(VLG_E_UNSUPPORTED, "a batch with mismatch budgets has several SA intervals per sub-pattern (vlg_search_batch + vlg_result_class_intervals)");
     std::vector<uint64_t> r(q->nsub + 1);
     if (vlg_status s = vlg_queries_intervals(idx, q, h_occ, r.data(), stream)) return s;
     for (uint64_t i = 0; i < q->nsub; ++i) h_occ[i] = r[i] + 1 - h_occ[i];        // r + 1 - l (suffix_array_algorithm.hpp:325)

@@ -27,4 +27,8 @@ struct vlg_queries {
     std::vector<uint8_t> sub_literal;    // [nsub]: every position of the sub-pattern accepts exactly one byte
     uint8_t* d_masks = nullptr;
     bool has_classes() const { return !masks.empty(); }
+    // mismatch budgets (vlg_queries_set_mismatches): empty = none.  Otherwise sub-pattern s may differ from the text in up to sub_k[s]
+    // of its positions (substitutions only), and at least one budget is > 0.  Host state only, like the windows.
+    std::vector<uint8_t> sub_k;          // [nsub]
+    bool has_mismatches() const { return !sub_k.empty(); }
 };

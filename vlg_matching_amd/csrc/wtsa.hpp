@@ -641,6 +641,7 @@ extern "C" vlg_status vlg_wtsa_ranges(const vlg_wtsa* x, const vlg_queries* q, u
 {
     if (!x || !q || (q->nsub && (!h_sp || !h_ep))) return fail(VLG_E_INVALID, "null argument");
     if (q->has_classes()) return fail(VLG_E_UNSUPPORTED, "a batch with character classes is searched by vlg_search_batch on a byte FM-index only");
+    if (q->has_mismatches()) return fail(VLG_E_UNSUPPORTED, "a batch with mismatch budgets is searched by vlg_search_batch on a byte FM-index only");
     if (!q->nsub) return VLG_OK;
     DevBuf d;
     VLG_HIP_TRY(d.alloc(2 * q->nsub * 8));
@@ -658,6 +659,7 @@ extern "C" vlg_status vlg_wtsa_search_window_batch(const vlg_wtsa* x, const vlg_
     if (!x || !q || !ws || !out) return fail(VLG_E_INVALID, "null argument");
     *out = nullptr;
     if (q->has_classes()) return fail(VLG_E_UNSUPPORTED, "a batch with character classes is searched by vlg_search_batch on a byte FM-index only");
+    if (q->has_mismatches()) return fail(VLG_E_UNSUPPORTED, "a batch with mismatch budgets is searched by vlg_search_batch on a byte FM-index only");
     if (q->has_windows()) return fail(VLG_E_INVALID, "the batch carries text windows (vlg_queries_set_windows): this search takes its windows as arrays");
     hipStream_t st = ws->stream;
     const uint64_t nq = q->nq, nsub = q->nsub;

@@ -452,6 +452,34 @@ class Queries:
         check(lib().vlg_queries_get_windows(self._h, C.byref(has), b.ctypes.data, e.ctypes.data))
         return (b[: self.n], e[: self.n]) if has.value else None
 
+    def set_mismatches(self, k):
+        """Mismatch budgets of the batch (vlg_queries_set_mismatches): VlgIndex.search lets sub-pattern s differ from the text in up
+        to k[s] of its positions (substitutions only).  A scalar for every sub-pattern or one value (0 .. 255) per sub-pattern of the
+        batch, in batch order (subpattern_range); None or all zeros removes the budgets."""
+        nsub = int(lib().vlg_queries_subpatterns(self._h))
+        if k is None:
+            check(lib().vlg_queries_set_mismatches(self._h, None))
+            return
+        a = np.asarray(k)
+        if a.dtype.kind not in "iu":
+            raise ValueError(f"mismatches: budgets are integers, got {a.dtype}")
+        if a.ndim == 0:
+            a = np.full(nsub, a)
+        if a.shape != (nsub,):
+            raise ValueError(f"mismatches: {nsub} sub-patterns, got an array of shape {a.shape}")
+        if len(a) and (a.min() < 0 or a.max() > 255):
+            raise ValueError("mismatches: a budget is 0 .. 255")
+        a = np.ascontiguousarray(np.concatenate([a, [0]]), dtype=np.uint8)
+        check(lib().vlg_queries_set_mismatches(self._h, a.ctypes.data))
+
+    def mismatches(self):
+        """-> the budgets per sub-pattern as they were set, or None for a batch without budgets"""
+        has = C.c_int(0)
+        nsub = int(lib().vlg_queries_subpatterns(self._h))
+        k = np.zeros(max(nsub, 1), np.uint8)
+        check(lib().vlg_queries_get_mismatches(self._h, C.byref(has), k.ctypes.data))
+        return k[:nsub] if has.value else None
+
     @property
     def ks(self):
         """sub-patterns per query (0 for a query that failed to parse)"""
