@@ -2,6 +2,9 @@
 backward search against a suffix array computed here, and whole searches against tests/vlg_brute.py over the occurrence lists of
 tests/vlg_class_brute.py."""
 import ctypes as C
+import hashlib
+import json
+import os
 
 import numpy as np
 import pytest
@@ -398,3 +401,48 @@ def test_refusals(V):
     with pytest.raises(V.VlgError) as e:
         ws.set_option("class_intervals", 0)
     assert e.value.status == V.capi.E_INVALID
+
+
+# ---- recorded behaviour: every counter, interval and match of fixed batches as the commit named in the fixture computed them ---------------
+RECORDED = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "class_batches_recorded.json")
+
+
+def _digest(a):
+    a = np.ascontiguousarray(a)
+    return a.tolist() if a.size <= 32 else {"len": int(a.size), "sha256": hashlib.sha256(a.astype("<u8").tobytes()).hexdigest()}
+
+
+def _observe(res, ws):
+    """everything a batch leaves behind that is a deterministic function of index, batch and options"""
+    off, l, r = res.class_intervals()
+    counts, offsets, first, tuples = res.fetch()
+    return {"summary": dict(res.summary),
+            "class_intervals": {"off": _digest(off), "l": _digest(l), "r": _digest(r)},
+            "fetch": {"counts": _digest(counts), "offsets": _digest(offsets), "first": _digest(first), "tuples": _digest(tuples)},
+            "launches": {k: v["launches"] for k, v in ws.kernel_stats().items()}}
+
+
+def _recorded_cases(V):
+    """name -> a function that runs the batch in a fresh workspace with an explicit cap and observes it"""
+    text = _text("dna3000")
+    regexps = _random_queries(text, np.random.default_rng(11 + len(text)), 48, extra=b"\xf0")      # test_search_matches_brute_force's
+    opts = {"tuples": 1, "filter_min": 0, "filter_stream_min": 0}
+
+    def run(kind):
+        ws = _workspace(opts, cap=1 << 30)
+        return _observe(_index(V, "dna3000", kind).search(V.Queries.from_classes(regexps), workspace=ws), ws)
+    return {"classes/dna3000/" + kind: (lambda kind=kind: run(kind)) for kind in ("plain", "rrr")}
+
+
+def _check_recorded(cases):
+    with open(RECORDED) as f:
+        want = json.load(f)["cases"]
+    for name, run in cases.items():
+        got = run()
+        assert set(got) == set(want[name]), name
+        for part, fields in want[name].items():
+            assert fields and {k: got[part][k] for k in fields} == fields, (name, part)
+
+
+def test_recorded_behaviour(V):
+    _check_recorded(_recorded_cases(V))

@@ -473,3 +473,63 @@ def test_refusals(V):
         ints.search(q, workspace=ws)
     assert e.value.status in (V.capi.E_UNSUPPORTED, V.capi.E_INVALID)
     assert ws.kernel_stats() == before                                      # nothing was launched
+
+
+# ---- 12. the group loop: more tasks than one group of the frontier scratch holds ---------------------------------------------------------------
+GROUP_CAP = 1 << 20                # "class_intervals" at its maximum: 64 MiB of frontier scratch / (32 B x 2^20) = 2 tasks to a group
+
+
+def _group_batch(text):
+    """-> (regexps, budgets): 5 distinct class sub-patterns, 5 distinct budgeted ones (budgets 1 and 2; two of them over classes) and 2
+    literal ones, repeated over 9 queries"""
+    cls = ["[AC]G", "T[CG]A", "[AT][AT]", "[^A]C", "GG[ACT]"]
+    apx = [("ACGT", 1), ("TTGA", 2), ("GGC", 1), ("CA[GT]G", 2), ("[AC]AT", 1)]
+    lit = ["ACG", "TTG"]
+    subs = [(c, 0) for c in cls] + apx + [(x, 0) for x in lit]
+    order = [(0, 5), (1, 6, 10), (2, 7), (3, 8, 11), (4, 9), (0, 9, 1), (5, 10), (6, 2, 8), (11, 7, 3)]
+    regexps = [".{0,40}?".join(subs[i][0] for i in q) for q in order]
+    budgets = [subs[i][1] for q in order for i in q]
+    widths = [max(A.frontier_widths(text, rows, k)) for (rx, k) in subs for rows in B.parse(rx)[0]]
+    assert max(widths) < 1024, widths                                       # the comparison run at the default cap does not overflow
+    assert len(set(order[j][i] for j in range(len(order)) for i in range(len(order[j])))) == 12 < len(budgets)
+    return regexps, budgets
+
+
+def test_task_groups(V):
+    """g0 of the group loop: the tasks, the ids and the rows of the strided frontier copy of every group but the first"""
+    text = _text("dna3000")
+    idx = _index(V, "dna3000")
+    regexps, budgets = _group_batch(text)
+    ws = _workspace({"class_intervals": GROUP_CAP})
+    res, nonempty = _check_search(V, text, idx, regexps, budgets, ws)
+    assert nonempty >= 5
+    _check_intervals("dna3000", regexps, budgets, res)
+    assert ws.kernel_stats()["class_search"]["launches"] == 6               # ceil(5 / 2) for the class kind + ceil(5 / 2) for the budgeted kind
+    ws2 = _workspace()
+    small = idx.search(_batch(V, regexps, budgets), workspace=ws2)
+    assert ws2.kernel_stats()["class_search"]["launches"] == 2              # (one group per kind at the default cap)
+    assert small.summary == res.summary
+    for a, b in zip(res.fetch(), small.fetch()):
+        assert a.tolist() == b.tolist()
+    for a, b in zip(res.class_intervals(), small.class_intervals()):
+        assert a.tolist() == b.tolist()
+
+
+# ---- 13. recorded behaviour (the fixture of tests/test_gpu_query_classes.py) ---------------------------------------------------------------------
+def _recorded_cases(V):
+    text = _text("dna3000")
+    regexps, budgets = _random_queries(text, np.random.default_rng(17 + len(text)), 32, mrange=(4, 8), classes=True)   # test_search_matches_brute_force's
+    opts = {"tuples": 1, "filter_min": 0, "filter_stream_min": 0, "class_intervals": ROOMY}
+    mers = [a + b for a in "ACGT" for b in "ACGT"]
+    chunked = ["%s.{%d,%d}?%s" % (mers[j], 3 + j, 9 + j, mers[(j + 5) % 16]) for j in range(16)]                      # test_super_chunks's
+
+    def run(name, kind, regexps, budgets, opts, cap):
+        ws = _workspace(opts, cap=cap)
+        return K._observe(_index(V, name, kind).search(_batch(V, regexps, budgets), workspace=ws), ws)
+    cases = {"budgets/dna3000/" + kind: (lambda kind=kind: run("dna3000", kind, regexps, budgets, opts, 1 << 30)) for kind in ("plain", "rrr")}
+    cases["budgets/dna40000/super_chunks"] = lambda: run("dna40000", "plain", chunked, 1, None, 17 << 20)
+    return cases
+
+
+def test_recorded_behaviour(V):
+    K._check_recorded(_recorded_cases(V))

@@ -402,129 +402,69 @@ __global__ void __launch_bounds__(256) backward_search_kernel(IndexView iv, cons
     }
 }
 
-// K2c: backward search of sub-patterns whose positions are SETS of bytes (character classes).  One wavefront per sub-pattern.  The
-// frontier -- the SA intervals of the member strings of S_t ... S_{m-1} that occur -- ping-pongs between two halves of `cap` intervals
-// in global scratch: half h of task t is frontier[(h * n_tasks + t) * cap ...].  A step deals the (symbol, parent interval) pairs to
-// the lanes symbol-major, parent-minor -- the new left borders then ascend (C[c] dominates; within one c the rank is monotone in the
-// parent's l), so the frontier stays sorted by l without a sort -- takes the two ranks of backward_search_kernel per pair, and
-// compacts the non-empty results with a ballot and a popcount prefix.  The result ends in half 0; count[t] = its intervals, or
-// kClassSearchOverflow when a step would have kept more than `cap` (nothing is written past the cap; exactly `cap` is legal).
-// task[2 t] = first mask row of the sub-pattern (32 bytes per position, bit c = byte c), task[2 t + 1] = its positions.
-template <class BV>
-__global__ void __launch_bounds__(256) class_search_kernel(IndexView iv, const uint8_t* __restrict__ masks, const uint64_t* __restrict__ task,
-                                                           uint64_t n_tasks, uint32_t cap, ulonglong2* frontier, uint32_t* __restrict__ count,
-                                                           unsigned long long* __restrict__ stat_levels)
+// The symbol list of a step of the branching search into one wave's `list`, ascending -> its length: the bytes 1..255 that the text
+// has and, without a budget, that the class row holds.
+template <bool kBudget>
+__device__ __forceinline__ uint32_t list_symbols(const IndexView& iv, const uint8_t* row, uint8_t* list, uint32_t lane, unsigned long long below)
 {
-    __shared__ WalkLds<BV> s;
-    __shared__ uint8_t syms[4][256];                       // per wave: the members of the step's class that the text has, ascending
-    stage_walk(s, iv);
-    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const unsigned long long below = (1ull << lane) - 1ull;
-    uint32_t levels = 0;
-    for (uint64_t t = (uint64_t)blockIdx.x * 4 + wv; t < n_tasks; t += (uint64_t)gridDim.x * 4) {
-        const uint64_t pos0 = task[2 * t];
-        const uint32_t m = (uint32_t)task[2 * t + 1];
-        ulonglong2* const half[2] = {frontier + t * cap, frontier + (n_tasks + t) * cap};
-        uint32_t cur = 0, cnt = 1;                         // before the first step: the whole range, which is not stored
-        bool whole = true, over = false;
-        for (uint32_t p = m; p-- > 0 && cnt && !over;) {
-            const uint8_t* row = masks + (pos0 + p) * 32;
-            uint32_t nsym = 0;
-#pragma unroll
-            for (uint32_t j = 0; j < 4; ++j) {
-                const uint32_t c = 64 * j + lane;
-                const bool on = c > 0 && ((row[c >> 3] >> (c & 7)) & 1u) && iv.char2comp[c] != 0;
-                const unsigned long long b = __ballot(on);
-                if (on) syms[wv][nsym + (uint32_t)__popcll(b & below)] = (uint8_t)c;
-                nsym += (uint32_t)__popcll(b);
-            }
-            // (the list is read by other lanes of this wave than wrote it)
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            const ulonglong2* src = half[cur];
-            ulonglong2* dst = half[cur ^ 1];
-            const uint32_t total = nsym * cnt;             // (cap <= 2^20: fits)
-            uint32_t out = 0;
-            for (uint32_t base = 0; base < total && !over; base += 64) {
-                const uint32_t i = base + lane;
-                bool keep = false;
-                uint64_t nl = 0, nr = 0;
-                if (i < total) {
-                    const uint32_t si = i / cnt, pi = i - si * cnt;
-                    const uint8_t c = syms[wv][si];
-                    const uint32_t cc = iv.char2comp[c];
-                    const uint64_t c_begin = s.C[cc];
-                    uint64_t l = 0, r = iv.n - 1;
-                    if (!whole) { const ulonglong2 par = src[pi]; l = par.x; r = par.y; }
-                    if (l == 0 && r + 1 == iv.n) { nl = c_begin; nr = s.C[cc + 1] - 1; keep = s.C[cc + 1] > c_begin; }      // as backward_search_kernel
-                    else {
-                        const uint64_t path = iv.paths[c];
-                        const uint64_t a = wt_rank_dev(iv, s, path, l, levels), b = wt_rank_dev(iv, s, path, r + 1, levels);
-                        nl = c_begin + a; nr = c_begin + b - 1; keep = b > a;
-                    }
-                }
-                const unsigned long long kb = __ballot(keep);
-                const uint32_t at = out + (uint32_t)__popcll(kb & below);
-                out += (uint32_t)__popcll(kb);
-                if (out > cap) over = true;                // (wave-uniform) this turn would pass the cap: none of its lanes writes
-                else if (keep) dst[at] = make_ulonglong2(nl, nr);
-            }
-            cnt = out; cur ^= 1; whole = false;
-            __threadfence();                               // the next step's lanes read what other lanes wrote
-        }
-        if (!over && cnt && cur == 1) for (uint32_t i = lane; i < cnt; i += 64) half[0][i] = half[1][i];
-        if (lane == 0) count[t] = over ? kClassSearchOverflow : cnt;
-    }
-    if (stat_levels) {
-        unsigned long long tl = levels;
-        for (int o = 32; o > 0; o >>= 1) tl += __shfl_down(tl, o);
-        if ((threadIdx.x & 63) == 0 && tl) atomicAdd(stat_levels, tl);
-    }
-}
-
-// K2d: backward search with a budget of substitutions (Hamming distance <= k) per sub-pattern.  Scheduling, scratch layout and the
-// order argument are class_search_kernel's; what differs is what a step deals and what an entry carries.  The symbol list is every
-// byte 1..255 the text has -- the same at every step of every task, so a wave builds it once, in front of its tasks -- and a
-// frontier entry carries the misses e of its string so far in the top byte of its second word (l, r <= 2^33).  For a
-// (symbol c, parent) pair e' = e + !(row_p bit c); a
-// pair with e' > k takes no rank and keeps nothing.  Which pairs are kept does not touch the order: C[c] dominates and within one c
-// the rank is monotone in the parent's l, so the frontier stays ascending and disjoint -- one interval per distinct string within
-// the budget that occurs.  The last step writes its intervals without the miss count, so half 0 reads as class_search_kernel's.
-// task[2 t] = first mask row of the sub-pattern, task[2 t + 1] = its positions, with the budget (1 .. 255) in the top byte.
-template <class BV>
-__global__ void __launch_bounds__(256) approx_search_kernel(IndexView iv, const uint8_t* __restrict__ masks, const uint64_t* __restrict__ task,
-                                                            uint64_t n_tasks, uint32_t cap, ulonglong2* frontier, uint32_t* __restrict__ count,
-                                                            unsigned long long* __restrict__ stat_levels)
-{
-    __shared__ WalkLds<BV> s;
-    __shared__ uint8_t syms[4][256];                       // per wave: the bytes 1..255 of the text, ascending
-    stage_walk(s, iv);
-    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const unsigned long long below = (1ull << lane) - 1ull;
-    constexpr uint64_t kEntryMask = (1ull << 56) - 1;
-    uint32_t levels = 0;
     uint32_t nsym = 0;
 #pragma unroll
     for (uint32_t j = 0; j < 4; ++j) {
         const uint32_t c = 64 * j + lane;
-        const bool on = c > 0 && iv.char2comp[c] != 0;
+        bool on = c > 0 && iv.char2comp[c] != 0;
+        if constexpr (!kBudget) on = c > 0 && ((row[c >> 3] >> (c & 7)) & 1u) && iv.char2comp[c] != 0;
         const unsigned long long b = __ballot(on);
-        if (on) syms[wv][nsym + (uint32_t)__popcll(b & below)] = (uint8_t)c;
+        if (on) list[nsym + (uint32_t)__popcll(b & below)] = (uint8_t)c;
         nsym += (uint32_t)__popcll(b);
     }
     // (the list is read by other lanes of this wave than wrote it)
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    return nsym;
+}
+
+// K2c: branching backward search, one wavefront per sub-pattern (task): the SA intervals of every string that the sub-pattern stands
+// for and that occurs.  Without a budget (kBudget = false) the positions are SETS of bytes (character classes) and the strings are the
+// member strings of S_0 ... S_{m-1}; with one (kBudget = true) they are the strings within Hamming distance k of a member string.
+// Scratch: the frontier -- the intervals of the strings of the steps done so far -- ping-pongs between two halves of `cap` intervals
+// in global memory: half h of task t is frontier[(h * n_tasks + t) * cap ...].  The result ends in half 0; count[t] = its intervals,
+// or kClassSearchOverflow when a step would have kept more than `cap` (nothing is written past the cap; exactly `cap` is legal).
+// Order: a step deals the (symbol, parent interval) pairs to the lanes symbol-major, parent-minor, takes the two ranks of
+// backward_search_kernel per pair, and compacts the non-empty results with a ballot and a popcount prefix.  The new left borders
+// ascend (C[c] dominates; within one c the rank is monotone in the parent's l) whichever pairs are kept, so the frontier stays
+// ascending and disjoint without a sort: one interval per distinct string that occurs.
+// Tasks: task[2 t] = first mask row of the sub-pattern (32 bytes per position, bit c = byte c), task[2 t + 1] = its positions.
+// kBudget adds: the budget k (1 .. 255) in the top byte of task[2 t + 1]; a symbol list of every byte 1..255 the text has -- the
+// same at every step of every task, so a wave builds it once, in front of its tasks, where the class search builds the members of
+// the step's row per step; the misses e of an entry's string so far in the top byte of its second word (l, r <= 2^33), with
+// e' = e + !(row_p bit c) for a (symbol c, parent) pair; and the gate e' <= k, without which a pair takes no rank and keeps nothing.
+// The last step writes its intervals without the miss count, so half 0 reads the same for either kind.
+template <class BV, bool kBudget>
+__global__ void __launch_bounds__(256) branching_search_kernel(IndexView iv, const uint8_t* __restrict__ masks, const uint64_t* __restrict__ task,
+                                                               uint64_t n_tasks, uint32_t cap, ulonglong2* frontier, uint32_t* __restrict__ count,
+                                                               unsigned long long* __restrict__ stat_levels)
+{
+    __shared__ WalkLds<BV> s;
+    __shared__ uint8_t syms[4][256];                       // per wave, ascending: the members of the step's class that the text has / its bytes 1..255
+    stage_walk(s, iv);
+    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    constexpr uint64_t kEntryMask = (1ull << 56) - 1;
+    uint32_t levels = 0;
+    uint32_t nsym = 0;
+    if constexpr (kBudget) nsym = list_symbols<true>(iv, nullptr, syms[wv], lane, below);
     for (uint64_t t = (uint64_t)blockIdx.x * 4 + wv; t < n_tasks; t += (uint64_t)gridDim.x * 4) {
         const uint64_t pos0 = task[2 * t];
-        const uint32_t m = (uint32_t)(task[2 * t + 1] & kEntryMask), k = (uint32_t)(task[2 * t + 1] >> 56);
+        const uint32_t m = (uint32_t)(kBudget ? task[2 * t + 1] & kEntryMask : task[2 * t + 1]);
+        [[maybe_unused]] uint32_t k = 0;
+        if constexpr (kBudget) k = (uint32_t)(task[2 * t + 1] >> 56);
         ulonglong2* const half[2] = {frontier + t * cap, frontier + (n_tasks + t) * cap};
-        uint32_t cur = 0, cnt = 1;                         // before the first step: the whole range with no miss, which is not stored
+        uint32_t cur = 0, cnt = 1;                         // before the first step: the whole range (with no miss), which is not stored
         bool whole = true, over = false;
         for (uint32_t p = m; p-- > 0 && cnt && !over;) {
             const uint8_t* row = masks + (pos0 + p) * 32;
+            if constexpr (!kBudget) nsym = list_symbols<false>(iv, row, syms[wv], lane, below);
             const ulonglong2* src = half[cur];
             ulonglong2* dst = half[cur ^ 1];
             const uint32_t total = nsym * cnt;             // (255 symbols, cap <= 2^20: fits)
@@ -533,14 +473,19 @@ __global__ void __launch_bounds__(256) approx_search_kernel(IndexView iv, const 
                 const uint32_t i = base + lane;
                 bool keep = false;
                 uint64_t nl = 0, nr = 0;
-                uint32_t e = 0;
+                [[maybe_unused]] uint32_t e = 0;
                 if (i < total) {
                     const uint32_t si = i / cnt, pi = i - si * cnt;
                     const uint8_t c = syms[wv][si];
                     uint64_t l = 0, r = iv.n - 1;
-                    if (!whole) { const ulonglong2 par = src[pi]; l = par.x; r = par.y & kEntryMask; e = (uint32_t)(par.y >> 56); }
-                    e += ((row[c >> 3] >> (c & 7)) & 1u) ^ 1u;
-                    if (e <= k) {                          // a parent at full budget takes its own symbols only
+                    if (!whole) {
+                        const ulonglong2 par = src[pi];
+                        l = par.x; r = par.y;
+                        if constexpr (kBudget) { r = par.y & kEntryMask; e = (uint32_t)(par.y >> 56); }
+                    }
+                    bool take = true;                      // kBudget: a parent at full budget takes its own symbols only
+                    if constexpr (kBudget) { e += ((row[c >> 3] >> (c & 7)) & 1u) ^ 1u; take = e <= k; }
+                    if (take) {
                         const uint32_t cc = iv.char2comp[c];
                         const uint64_t c_begin = s.C[cc];
                         if (l == 0 && r + 1 == iv.n) { nl = c_begin; nr = s.C[cc + 1] - 1; keep = s.C[cc + 1] > c_begin; }      // as backward_search_kernel
@@ -555,7 +500,7 @@ __global__ void __launch_bounds__(256) approx_search_kernel(IndexView iv, const 
                 const uint32_t at = out + (uint32_t)__popcll(kb & below);
                 out += (uint32_t)__popcll(kb);
                 if (out > cap) over = true;                // (wave-uniform) this turn would pass the cap: none of its lanes writes
-                else if (keep) dst[at] = make_ulonglong2(nl, p ? nr | ((uint64_t)e << 56) : nr);
+                else if (keep) dst[at] = make_ulonglong2(nl, kBudget && p ? nr | ((uint64_t)e << 56) : nr);
             }
             cnt = out; cur ^= 1; whole = false;
             __threadfence();                               // the next step's lanes read what other lanes wrote
@@ -1100,29 +1045,18 @@ vlg_status launch_backward_search(const IndexView& iv, const uint8_t* d_blob, co
     });
 }
 
-vlg_status launch_class_search(const IndexView& iv, const uint8_t* d_masks, const uint64_t* d_task, uint64_t n_tasks, uint32_t cap, uint64_t* d_frontier,
-                               uint32_t* d_count, unsigned long long* d_stat_levels, hipStream_t stream)
+vlg_status launch_branching_search(const IndexView& iv, bool budget, const uint8_t* d_masks, const uint64_t* d_task, uint64_t n_tasks, uint32_t cap,
+                                   uint64_t* d_frontier, uint32_t* d_count, unsigned long long* d_stat_levels, hipStream_t stream)
 {
     if (!n_tasks) return VLG_OK;
-    if (!cap || cap > kClassIntervalsMax) return fail(VLG_E_INTERNAL, "class search: frontier cap out of range");
+    if (!cap || cap > kClassIntervalsMax) return fail(VLG_E_INTERNAL, std::string(budget ? "approximate" : "class") + " search: frontier cap out of range");
     // one wave per task, four to a workgroup; enough workgroups to fill the device, the rest of the tasks in turns
     const dim3 grid((uint32_t)std::min<uint64_t>((n_tasks + 3) / 4, 16384));
     return on_bv(iv.bv_kind, [&](auto bv) {
-        return launch(class_search_kernel<tag_t<decltype(bv)>>, grid, stream, iv, d_masks, d_task, n_tasks, cap, reinterpret_cast<ulonglong2*>(d_frontier), d_count,
-                      d_stat_levels);
-    });
-}
-
-vlg_status launch_approx_search(const IndexView& iv, const uint8_t* d_masks, const uint64_t* d_task, uint64_t n_tasks, uint32_t cap, uint64_t* d_frontier,
-                                uint32_t* d_count, unsigned long long* d_stat_levels, hipStream_t stream)
-{
-    if (!n_tasks) return VLG_OK;
-    if (!cap || cap > kClassIntervalsMax) return fail(VLG_E_INTERNAL, "approximate search: frontier cap out of range");
-    // the grid of launch_class_search
-    const dim3 grid((uint32_t)std::min<uint64_t>((n_tasks + 3) / 4, 16384));
-    return on_bv(iv.bv_kind, [&](auto bv) {
-        return launch(approx_search_kernel<tag_t<decltype(bv)>>, grid, stream, iv, d_masks, d_task, n_tasks, cap, reinterpret_cast<ulonglong2*>(d_frontier), d_count,
-                      d_stat_levels);
+        const auto go = [&](auto kernel) {
+            return launch(kernel, grid, stream, iv, d_masks, d_task, n_tasks, cap, reinterpret_cast<ulonglong2*>(d_frontier), d_count, d_stat_levels);
+        };
+        return budget ? go(branching_search_kernel<tag_t<decltype(bv)>, true>) : go(branching_search_kernel<tag_t<decltype(bv)>, false>);
     });
 }
 

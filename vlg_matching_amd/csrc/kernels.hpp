@@ -9,19 +9,16 @@ namespace vlg {
 
 vlg_status launch_backward_search(const IndexView& iv, const uint8_t* d_blob, const uint64_t* d_off, uint64_t n_pat, uint64_t* d_l,
                                   uint64_t* d_r, unsigned long long* d_stat_levels, hipStream_t stream);
-// Character classes (class_search_kernel): the SA intervals of n_tasks sub-patterns whose positions are sets of bytes.  d_task[2 t] =
-// first row of d_masks (32 bytes per position), d_task[2 t + 1] = positions; d_frontier: 2 x n_tasks x cap intervals (l, r) of
-// scratch, 16-byte aligned -- task t's result is d_frontier[2 (t cap + i)], [.. + 1] for i < d_count[t], ascending and disjoint;
-// d_count[t] = kClassSearchOverflow when the frontier of t would have passed `cap` intervals (nothing is written beyond it).
+// Branching backward search (branching_search_kernel): the SA intervals of n_tasks sub-patterns whose positions are sets of bytes.
+// d_task[2 t] = first row of d_masks (32 bytes per position), d_task[2 t + 1] = positions; d_frontier: 2 x n_tasks x cap intervals
+// (l, r) of scratch, 16-byte aligned -- task t's result is d_frontier[2 (t cap + i)], [.. + 1] for i < d_count[t], ascending and
+// disjoint; d_count[t] = kClassSearchOverflow when the frontier of t would have passed `cap` intervals (nothing is written beyond it).
+// budget: d_task[2 t + 1] carries a mismatch budget k (1 .. 255, at most the positions) in its top byte, and task t's result is one
+// interval per distinct string within Hamming distance k of the rows that occurs in the text; without it, one per member string.
 constexpr uint32_t kClassIntervalsMax = 1u << 20;
 constexpr uint32_t kClassSearchOverflow = 0xFFFFFFFFu;
-vlg_status launch_class_search(const IndexView& iv, const uint8_t* d_masks, const uint64_t* d_task, uint64_t n_tasks, uint32_t cap, uint64_t* d_frontier,
-                               uint32_t* d_count, unsigned long long* d_stat_levels, hipStream_t stream);
-// Mismatch budgets (approx_search_kernel): the same arguments, scratch and result.  d_task[2 t + 1] carries the budget k (1 .. 255, at
-// most the positions) in its top byte; task t's result is one interval per distinct string within Hamming distance k of the rows
-// that occurs in the text.
-vlg_status launch_approx_search(const IndexView& iv, const uint8_t* d_masks, const uint64_t* d_task, uint64_t n_tasks, uint32_t cap, uint64_t* d_frontier,
-                                uint32_t* d_count, unsigned long long* d_stat_levels, hipStream_t stream);
+vlg_status launch_branching_search(const IndexView& iv, bool budget, const uint8_t* d_masks, const uint64_t* d_task, uint64_t n_tasks, uint32_t cap,
+                                   uint64_t* d_frontier, uint32_t* d_count, unsigned long long* d_stat_levels, hipStream_t stream);
 template <typename pos_t>
 vlg_status launch_expand(const uint64_t* d_l, const uint64_t* d_out_off, uint64_t n_pat, uint64_t total, pos_t* d_io, uint32_t* d_seg,
                          hipStream_t stream);

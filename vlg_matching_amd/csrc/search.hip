@@ -93,7 +93,7 @@ struct vlg_workspace {
     uint64_t unsample_min = 1ull << 28;     // ... and at least this many occurrences: ~110 rounds of two launches each are a fixed cost
     uint64_t unsample_tail = 1ull << 20;    // walkers left when the sorted rounds end and the lanes finish them one by one
     uint32_t class_intervals = 1024;        // character classes: SA intervals one sub-pattern may have at any step of its backward search
-                                            // (kernels.hip: class_search_kernel; 32 B of scratch per interval and task of a group)
+                                            // (kernels.hip: branching_search_kernel; 32 B of scratch per interval and task of a group)
     uint64_t sample_reads = 0;              // SA samples read by the locate stage of the batch in work (algorithmic bytes)
     // one process per GPU: a collective search shards the DISTINCT LISTS of a batch over the ranks for locate + sort,
     // exchanges the sorted lists (all-gather) and shards the QUERIES for filter + join
@@ -656,6 +656,28 @@ struct Lists {                      // the sorted occurrence lists the joins rea
     uint64_t* roff = nullptr;       // device: first entry of every level of R
 };
 
+// Plain lists of `total` positions with nothing dead behind them (vlg_join_batch, class_batch.hpp): the room for the survivors of the
+// window filter -- as long as the lists, when the workspace filters at all -- begins at the next multiple of 64, and the fences cover both.
+struct ListRoom {
+    uint64_t pc_first, pc_cap, fence_entries;
+    ListRoom(uint64_t total, bool filter)
+        : pc_first(align_up(total, 64)), pc_cap(filter && total ? std::min<uint64_t>(total, 0xFFFFFF00ull - pc_first) : 0), fence_entries((pc_first + pc_cap) / 64 + 2) {}
+    uint64_t positions() const { return pc_first + pc_cap + 64; }      // what L.P takes
+};
+// L.P holds `total` sorted positions: their fences into F (fence_entries of them), and the room behind them
+template <typename pos_t>
+vlg_status wire_room_and_fences(Lists<pos_t>& L, const ListRoom& room, uint64_t total, pos_t* F, hipStream_t st)
+{
+    if (total >= 64) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(fence_build_kernel<pos_t>), launch_grid(total / 64, 8192), dim3(256), 0, st, L.P, (uint64_t)0, total / 64, F);
+        VLG_HIP_TRY(hipGetLastError());
+    }
+    L.F = total ? F : nullptr;
+    L.Pc = room.pc_cap ? L.P + room.pc_first : nullptr;
+    L.pc_cap = room.pc_cap;
+    return VLG_OK;
+}
+
 template <typename pos_t> constexpr uint64_t kPhysScratchPerElem() { return 20; }   // sweep scratch; the sorted lists reuse it
 // What JoinChunk carves, as the planners count it.  Per slot:
 constexpr uint64_t kJoinBytesPerSlot = 4 + 8 + 1;      // any slot: link, endp (<= 8), lvl_ptr[] (feasibility bits + summaries)
@@ -854,6 +876,22 @@ PhysChoice choose_physical(const vlg_index* idx, const vlg_workspace* ws, uint64
     c.list_sort = sizeof(pos_t) == 4 && ws->list_sort;
     c.global_sort = elems >= ws->global_sort_min && c.pos_bits + bit_width64(n_lists) <= 64;
     return c;
+}
+
+// Few occurrences: the SA intervals d_l (n_lists of them, their places in d_off) expanded and walked one occurrence at a time, in place,
+// in words of word_t -- narrowed into `out` when they are wider than a position.
+template <typename pos_t, typename word_t>
+vlg_status expand_and_walk(vlg_workspace* ws, const IndexView& lview, const uint64_t* d_l, const uint64_t* d_off, uint64_t n_lists, uint64_t total, word_t* io,
+                           pos_t* out, unsigned long long* d_stats)
+{
+    {
+        Timed t(ws, KS_EXPAND, 0);
+        if (vlg_status s = launch_expand<word_t>(d_l, d_off, n_lists, total, io, nullptr, ws->stream)) return s;
+    }
+    Timed t(ws, KS_LOCATE, 0);
+    if (vlg_status s = launch_locate<word_t>(lview, io, total, d_stats, ws->stream)) return s;
+    if constexpr (sizeof(word_t) != sizeof(pos_t)) return launch_narrow<pos_t>(io, out, total, ws->stream);
+    return VLG_OK;
 }
 
 struct SuperChunk {                 // a run of queries [Q0, Q1) whose distinct occurrence lists fit the physical budget
@@ -1057,19 +1095,12 @@ struct PhysicalPass {
         return VLG_OK;
     }
 
-    // few occurrences: one walk per occurrence in place, in words of word_t -- narrowed into Pa when they are wider than a position
+    // few occurrences: the walks, into Pa
     template <typename word_t>
     vlg_status walks(word_t* io, const IndexView& lview)
     {
         if (vlg_status s = plan_sort()) return s;
-        {
-            Timed t(ws, KS_EXPAND, 0);
-            if (vlg_status s = launch_expand<word_t>(d_lh, d_off64, nd, acc, io, nullptr, st)) return s;
-        }
-        Timed t(ws, KS_LOCATE, 0);
-        if (vlg_status s = launch_locate<word_t>(lview, io, acc, d_stats, st)) return s;
-        if constexpr (sizeof(word_t) != sizeof(pos_t)) return launch_narrow<pos_t>(io, Pa, acc, st);
-        return VLG_OK;
+        return expand_and_walk(ws, lview, d_lh, d_off64, nd, acc, io, Pa, d_stats);
     }
 
     // every occurrence list ascending (std::sort, index_sasearch.hpp:80); -> where the sorted share lies
@@ -2223,6 +2254,16 @@ vlg_status plan_on_device(const vlg_queries* q, vlg_workspace* ws, const uint64_
     return run();
 }
 
+// a query with an empty occurrence list has no match: none of its lists is materialised (vlg_index.hpp:315-316 returns at the first
+// empty range).  occ(s): the occurrences of sub-pattern s
+template <class F>
+bool query_live(const vlg_queries* q, uint64_t qi, F&& occ)
+{
+    bool live = q->qsub[qi + 1] > q->qsub[qi];
+    for (uint64_t s = q->qsub[qi]; s < q->qsub[qi + 1] && live; ++s) live = occ(s) > 0;
+    return live;
+}
+
 // The same plan made on the host (no dedup, texts beyond 2^33 or an interval too long for its key on the device): the intervals are
 // copied back and numbered as they come.
 vlg_status plan_on_host(const vlg_queries* q, vlg_workspace* ws, const uint64_t* d_l, const uint64_t* d_r, Plan& pl, uint64_t& logical)
@@ -2235,15 +2276,11 @@ vlg_status plan_on_host(const vlg_queries* q, vlg_workspace* ws, const uint64_t*
         VLG_HIP_TRY(hipMemcpyAsync(r.data(), d_r, nsub * 8, hipMemcpyDeviceToHost, st));
     }
     VLG_HIP_TRY(hipStreamSynchronize(st));
-    // a query with an empty occurrence list has no match: none of its lists is materialised
-    // (vlg_index.hpp:315-316 returns at the first empty range)
     pl.occ.assign(nsub, 0);
     pl.did.assign(nsub, 0);
-    for (uint64_t qi = 0; qi < q->nq; ++qi) {
-        bool live = q->qsub[qi + 1] > q->qsub[qi];
-        for (uint64_t s = q->qsub[qi]; s < q->qsub[qi + 1] && live; ++s) live = (r[s] + 1 - l[s]) > 0;
-        if (live) for (uint64_t s = q->qsub[qi]; s < q->qsub[qi + 1]; ++s) pl.occ[s] = r[s] + 1 - l[s];
-    }
+    for (uint64_t qi = 0; qi < q->nq; ++qi)
+        if (query_live(q, qi, [&](uint64_t s) { return r[s] + 1 - l[s]; }))
+            for (uint64_t s = q->qsub[qi]; s < q->qsub[qi + 1]; ++s) pl.occ[s] = r[s] + 1 - l[s];
     // identical SA intervals are the same occurrence list: locate + sort each distinct one once per
     // super-chunk and let every query that uses it share the sorted list.
     std::vector<uint64_t> order;
@@ -2289,288 +2326,33 @@ vlg_result* new_result(uint64_t n, const std::vector<uint64_t>& qsub)
 // the partial checksums of the gather kernel added up, modulo 2^64 like gm_search.cpp:110-114
 uint64_t fold_checksum(const unsigned long long* stats) { return std::accumulate(stats + kStatsChecksum, stats + kStatsWords, (uint64_t)0); }
 
-
-// =============================================================================================
-// Batches with character classes (queries.cpp: vlg_queries_parse_classes)
-// =============================================================================================
-// A sub-pattern whose positions are sets of bytes has a SET of pairwise disjoint SA intervals, one per member string that occurs
-// (kernels.hip: class_search_kernel).  Everything behind the occurrence lists sees a list as (L.off[s], occ[s]) only, so the batch
-// is assembled as vlg_join_batch assembles one: distinct sub-patterns are found by content on the host, each is searched once
-// (literal ones by backward_search_kernel: one interval), the intervals come to the host, and per super-chunk the intervals of a
-// distinct sub-pattern are expanded back to back into ONE list, located by the random-access walks (the stages of vlg_locate_batch),
-// sorted inside itself and joined by plan_joins / run_joins unchanged.
-// Mismatch budgets (queries.cpp: vlg_queries_set_mismatches) take the same road: a sub-pattern with a budget > 0, literal or not, has
-// one interval per distinct string within the budget that occurs (kernels.hip: approx_search_kernel), its effective budget
-// min(k, m) is part of what makes it distinct, and one with budget 0 goes where it went without budgets.
-vlg_status run_class_batch(const vlg_index* idx, const vlg_queries* q, vlg_workspace* ws, vlg_result* res, PhaseTrace& tr)
+// The device counters of a finished batch, read into hs: the checksum into its summary (all that vlg_join_batch, which searches and
+// locates nothing, takes)
+vlg_status read_checksum(vlg_workspace* ws, vlg_result* res, const unsigned long long* d_stats, unsigned long long (&hs)[kStatsWords])
 {
-    hipStream_t st = ws->stream;
-    const uint64_t nsub = q->nsub, n = idx->hdr.n;
-    const uint32_t cap = ws->class_intervals;
-    const bool budgets = q->has_mismatches();
-    const auto literal = [&](uint64_t s) { return !q->has_classes() || q->sub_literal[s] != 0; };
-    // ---- distinct sub-patterns, by content and budget: literal ones by their bytes, the others by their mask rows ------------------
-    std::vector<uint32_t> sub_d(nsub, 0);
-    std::vector<uint8_t> sub_kb(nsub, 0);                         // effective budgets
-    std::vector<uint64_t> d_sub;                                  // per distinct sub-pattern: the first sub-pattern of the batch that is it
-    {
-        std::unordered_map<std::string, uint32_t> seen;
-        seen.reserve(nsub * 2 + 16);
-        std::string key;
-        for (uint64_t s = 0; s < nsub; ++s) {
-            const uint64_t a = q->suboff[s], b = q->suboff[s + 1];
-            const uint64_t kb = budgets ? std::min<uint64_t>(q->sub_k[s], b - a) : 0;        // k >= m: every position may differ
-            sub_kb[s] = (uint8_t)kb;
-            if (literal(s)) { key.assign(1, 'L'); key.push_back((char)kb); key.append(reinterpret_cast<const char*>(q->blob.data() + a), b - a); }
-            else { key.assign(1, 'C'); key.push_back((char)kb); key.append(reinterpret_cast<const char*>(q->masks.data() + a * 32), (b - a) * 32); }
-            const auto it = seen.emplace(key, (uint32_t)d_sub.size());
-            if (it.second) d_sub.push_back(s);
-            sub_d[s] = it.first->second;
-        }
-    }
-    const uint64_t nd = d_sub.size();
-    if (nd >= 0xFFFFFFF0ull) return fail(VLG_E_UNSUPPORTED, "too many distinct sub-patterns in one batch");
-    std::vector<uint32_t> lit, cls, apx;                          // distinct ids: literal and class without a budget, either with one
-    for (uint32_t d = 0; d < nd; ++d) (sub_kb[d_sub[d]] ? apx : literal(d_sub[d]) ? lit : cls).push_back(d);
-    const uint64_t nlit = lit.size(), ncls = cls.size(), napx = apx.size();
-    // ---- device memory of the front: counters, the literal patterns and their intervals, tasks, rows, counts, the frontier -----------
-    svec<uint8_t> lblob, arows;
-    svec<uint64_t> loff(nlit + 1, 0), task(2 * std::max<uint64_t>(ncls + napx, 1), 0);
-    for (uint64_t i = 0; i < nlit; ++i) {
-        const uint64_t s = d_sub[lit[i]];
-        lblob.insert(lblob.end(), q->blob.begin() + q->suboff[s], q->blob.begin() + q->suboff[s + 1]);
-        loff[i + 1] = lblob.size();
-    }
-    for (uint64_t i = 0; i < ncls; ++i) { const uint64_t s = d_sub[cls[i]]; task[2 * i] = q->suboff[s]; task[2 * i + 1] = q->suboff[s + 1] - q->suboff[s]; }
-    // a budgeted sub-pattern reads 256-bit rows: those of the batch, or -- a batch without classes has none -- rows made here, one bit each
-    const bool own_rows = napx && !q->has_classes();
-    for (uint64_t i = 0; i < napx; ++i) {
-        const uint64_t s = d_sub[apx[i]], a = q->suboff[s], m = q->suboff[s + 1] - a;
-        task[2 * (ncls + i)] = own_rows ? arows.size() / 32 : a;
-        task[2 * (ncls + i) + 1] = m | ((uint64_t)sub_kb[s] << 56);
-        if (own_rows) {
-            arows.resize(arows.size() + m * 32, 0);
-            uint8_t* row = arows.data() + arows.size() - m * 32;
-            for (uint64_t p = 0; p < m; ++p) { const uint8_t c = q->blob[a + p]; row[p * 32 + (c >> 3)] = (uint8_t)(1u << (c & 7)); }
-        }
-    }
-    const uint64_t kClassScratch = 64ull << 20;                  // the frontiers of one group of tasks
-    const uint64_t group = std::max<uint64_t>(1, std::min<uint64_t>(std::max<uint64_t>(std::max(ncls, napx), 1), kClassScratch / (32ull * cap)));
-    const uint64_t st_bytes = align_up(kStatsWords * 8, 256), lb_bytes = align_up(lblob.size() + 16, 256), lo_bytes = align_up((nlit + 1) * 8, 256);
-    const uint64_t tk_bytes = align_up(2 * (ncls + napx + 1) * 8, 256), ct_bytes = align_up(group * 4, 256), fr_bytes = align_up(2 * group * cap * 16, 256);
-    const uint64_t ar_bytes = align_up(arows.size() + 32, 256);
-    uint8_t* head = nullptr;
-    if (vlg_status hs = ws_head(ws, st_bytes + lb_bytes + 3 * lo_bytes + tk_bytes + ct_bytes + fr_bytes + ar_bytes, &head)) return hs;
-    unsigned long long* d_stats = (unsigned long long*)head;
-    uint8_t* d_lblob = head + st_bytes;
-    uint64_t* d_loff = (uint64_t*)(d_lblob + lb_bytes);
-    uint64_t* d_ll = (uint64_t*)((uint8_t*)d_loff + lo_bytes);
-    uint64_t* d_lr = (uint64_t*)((uint8_t*)d_ll + lo_bytes);
-    uint64_t* d_task = (uint64_t*)((uint8_t*)d_lr + lo_bytes);
-    uint32_t* d_count = (uint32_t*)((uint8_t*)d_task + tk_bytes);
-    uint64_t* d_frontier = (uint64_t*)((uint8_t*)d_count + ct_bytes);
-    uint8_t* d_arows = (uint8_t*)d_frontier + fr_bytes;
-    VLG_HIP_TRY(hipMemsetAsync(d_stats, 0, kStatsWords * 8, st));
-    ws->sample_reads = 0;
-    ws->x_agreed = 0;
-    // ---- the intervals of every distinct sub-pattern ------------------------------------------------------------------------------
-    std::vector<uint64_t> doff(nd + 1, 0);                        // per distinct sub-pattern: its intervals inside dl_ / dr_, in two passes
-    std::vector<std::vector<uint64_t>> piece_l(nd), piece_r(nd);
-    if (nlit) {
-        if (!lblob.empty()) VLG_HIP_TRY(hipMemcpyAsync(d_lblob, lblob.data(), lblob.size(), hipMemcpyHostToDevice, st));
-        VLG_HIP_TRY(hipMemcpyAsync(d_loff, loff.data(), (nlit + 1) * 8, hipMemcpyHostToDevice, st));
-        {
-            Timed t(ws, KS_BSEARCH, 0);
-            if (vlg_status s = launch_backward_search(idx->view, d_lblob, d_loff, nlit, d_ll, d_lr, d_stats + 3, st)) return s;
-        }
-        svec<uint64_t> hl(nlit), hr(nlit);
-        VLG_HIP_TRY(hipMemcpyAsync(hl.data(), d_ll, nlit * 8, hipMemcpyDeviceToHost, st));
-        VLG_HIP_TRY(hipMemcpyAsync(hr.data(), d_lr, nlit * 8, hipMemcpyDeviceToHost, st));
-        VLG_HIP_TRY(hipStreamSynchronize(st));
-        for (uint64_t i = 0; i < nlit; ++i)
-            if (hr[i] + 1 > hl[i]) { piece_l[lit[i]].push_back(hl[i]); piece_r[lit[i]].push_back(hr[i]); }
-    }
-    // the branching searches, a group of tasks at a time: class sub-patterns, then the budgeted ones (either kind: the same tasks,
-    // scratch, count read-back and strided frontier copy)
-    const auto branching = [&](const std::vector<uint32_t>& ids, const uint64_t* d_tk, const uint8_t* d_rows, bool approx) -> vlg_status {
-        const uint64_t nt = ids.size();
-        svec<uint32_t> hc(group);
-        svec<uint64_t> hf;
-        for (uint64_t g0 = 0; g0 < nt; g0 += group) {
-            const uint64_t g = std::min<uint64_t>(group, nt - g0);
-            {
-                Timed t(ws, KS_CLASS_SEARCH, 0);
-                if (vlg_status s = approx ? launch_approx_search(idx->view, d_rows, d_tk + 2 * g0, g, cap, d_frontier, d_count, d_stats + 3, st)
-                                          : launch_class_search(idx->view, d_rows, d_tk + 2 * g0, g, cap, d_frontier, d_count, d_stats + 3, st))
-                    return s;
-            }
-            VLG_HIP_TRY(hipMemcpyAsync(hc.data(), d_count, g * 4, hipMemcpyDeviceToHost, st));
-            VLG_HIP_TRY(hipStreamSynchronize(st));
-            uint64_t widest = 0;
-            for (uint64_t i = 0; i < g; ++i) {
-                if (hc[i] == kClassSearchOverflow) {
-                    // (nothing else is launched: the batch ends here)
-                    const uint64_t s = d_sub[ids[g0 + i]];
-                    const uint64_t qi = (uint64_t)(std::upper_bound(q->qsub.begin(), q->qsub.end(), s) - q->qsub.begin()) - 1;
-                    return fail(VLG_E_WORKSPACE, "query " + std::to_string(qi) + ", sub-pattern " + std::to_string(s - q->qsub[qi]) + ": more than " +
-                                                     std::to_string(cap) + " SA intervals at one step of its " + (approx ? "approximate" : "class") +
-                                                     " search (workspace option \"class_intervals\")");
-                }
-                widest = std::max<uint64_t>(widest, hc[i]);
-            }
-            if (!widest) continue;
-            // half 0 of the group's frontiers: `cap` intervals of 16 bytes per task, of which the first `widest` are fetched
-            hf.resize(g * widest * 2);
-            VLG_HIP_TRY(hipMemcpy2DAsync(hf.data(), widest * 16, d_frontier, (size_t)cap * 16, widest * 16, g, hipMemcpyDeviceToHost, st));
-            VLG_HIP_TRY(hipStreamSynchronize(st));
-            for (uint64_t i = 0; i < g; ++i) {
-                const uint32_t d = ids[g0 + i];
-                piece_l[d].reserve(hc[i]); piece_r[d].reserve(hc[i]);
-                for (uint64_t j = 0; j < hc[i]; ++j) { piece_l[d].push_back(hf[(i * widest + j) * 2]); piece_r[d].push_back(hf[(i * widest + j) * 2 + 1]); }
-            }
-        }
-        return VLG_OK;
-    };
-    if (ncls + napx) VLG_HIP_TRY(hipMemcpyAsync(d_task, task.data(), 2 * (ncls + napx) * 8, hipMemcpyHostToDevice, st));
-    if (ncls) if (vlg_status s = branching(cls, d_task, q->d_masks, false)) return s;
-    if (napx) {
-        if (own_rows) VLG_HIP_TRY(hipMemcpyAsync(d_arows, arows.data(), arows.size(), hipMemcpyHostToDevice, st));
-        if (vlg_status s = branching(apx, d_task + 2 * ncls, own_rows ? d_arows : q->d_masks, true)) return s;
-    }
-    tr.mark("class search");
-    std::vector<uint64_t> dl_, dr_;
-    Plan pl;
-    pl.occ.assign(nsub, 0);
-    pl.did.assign(nsub, 0);
-    pl.dl.assign(nd, 0);
-    pl.docc.assign(nd, 0);
-    for (uint64_t d = 0; d < nd; ++d) {
-        doff[d] = dl_.size();
-        dl_.insert(dl_.end(), piece_l[d].begin(), piece_l[d].end());
-        dr_.insert(dr_.end(), piece_r[d].begin(), piece_r[d].end());
-        for (size_t j = 0; j < piece_l[d].size(); ++j) pl.docc[d] += piece_r[d][j] + 1 - piece_l[d][j];
-        pl.dl[d] = piece_l[d].empty() ? 0 : piece_l[d][0];
-    }
-    doff[nd] = dl_.size();
-    piece_l.clear(); piece_r.clear();
-    // what vlg_result_class_intervals returns: per sub-pattern of the batch, the intervals of its distinct sub-pattern
-    res->has_class_intervals = true;
-    res->civ_off.assign(nsub + 1, 0);
-    for (uint64_t s = 0; s < nsub; ++s) res->civ_off[s + 1] = res->civ_off[s] + (doff[sub_d[s] + 1] - doff[sub_d[s]]);
-    res->civ_l.reserve(res->civ_off[nsub]); res->civ_r.reserve(res->civ_off[nsub]);
-    for (uint64_t s = 0; s < nsub; ++s) {
-        res->civ_l.insert(res->civ_l.end(), dl_.begin() + doff[sub_d[s]], dl_.begin() + doff[sub_d[s] + 1]);
-        res->civ_r.insert(res->civ_r.end(), dr_.begin() + doff[sub_d[s]], dr_.begin() + doff[sub_d[s] + 1]);
-    }
-    // a query with an empty occurrence list has no match: none of its lists is materialised (vlg_index.hpp:315-316)
-    for (uint64_t qi = 0; qi < q->nq; ++qi) {
-        bool live = q->qsub[qi + 1] > q->qsub[qi];
-        for (uint64_t s = q->qsub[qi]; s < q->qsub[qi + 1] && live; ++s) live = pl.docc[sub_d[s]] > 0;
-        if (!live) continue;
-        for (uint64_t s = q->qsub[qi]; s < q->qsub[qi + 1]; ++s) { pl.did[s] = sub_d[s]; pl.occ[s] = pl.docc[sub_d[s]]; res->sum.logical_occurrences += pl.occ[s]; }
-    }
-    // ---- super-chunks: whole queries while their distinct lists fit the physical budget (next_super_chunk, as the byte path) ----------
-    const bool wide = idx->hdr.sample_bytes == 8;                 // 33-bit SA indices; the positions still fit 32 bits (n <= 2^32 + 1)
-    const uint64_t fixed = 8ull << 20;
-    if (ws->cap_bytes <= 2 * fixed) return fail(VLG_E_WORKSPACE, "workspace cap too small");
-    const uint64_t budget = ws->cap_bytes - fixed;
-    const uint64_t phys_cap = std::min<uint64_t>(budget / 2 / (sizeof(uint32_t) + kPhysScratchPerElem<uint32_t>() + 1), 0xFFFFFF00ull);
-    const unsigned pos_bits = std::max(1u, bit_width64(n >= 2 ? n - 2 : 0));
-    const IndexView lview = ws->quad_walk ? idx->view : without_quad(idx->view);
-    std::vector<uint32_t> stamp(nd, 0xFFFFFFFFu);
-    uint32_t epoch = 0;
-    Lists<uint32_t> L;
-    L.doff.assign(nd, 0);
-    L.off.assign(nsub, 0);
-    for (uint64_t Q0 = 0; Q0 < q->nq;) {
-        SuperChunk sc;
-        if (vlg_status s = next_super_chunk(q, pl, false, phys_cap, Q0, stamp, epoch, sc)) return s;
-        const uint64_t nl = sc.dlist.size();
-        // the lists of the super-chunk one after the other, and the intervals each of them is made of
-        svec<uint64_t> off64(nl + 1, 0), iv_l, iv_off(1, 0);
-        for (uint64_t i = 0; i < nl; ++i) {
-            const uint32_t d = sc.dlist[i];
-            L.doff[d] = (uint32_t)off64[i];
-            for (uint64_t j = doff[d]; j < doff[d + 1]; ++j) { iv_l.push_back(dl_[j]); iv_off.push_back(iv_off.back() + (dr_[j] + 1 - dl_[j])); }
-            off64[i + 1] = off64[i] + pl.docc[d];
-        }
-        const uint64_t total = off64[nl], niv = iv_l.size();
-        if (total != iv_off.back() || total != sc.phys) return fail(VLG_E_INTERNAL, "class batch: list lengths disagree with their intervals");
-        uint64_t n_long = 0, n_tiles = 0, n_chunks = 0;
-        for (uint64_t i = 0; i < nl; ++i) {
-            const uint64_t len = off64[i + 1] - off64[i];
-            if (len > kSortTile) { const uint64_t t = (len + kSortTile - 1) / kSortTile; ++n_long; n_tiles += t; n_chunks += (t + kSortChunk - 1) / kSortChunk; }
-        }
-        // arena: [lists][room for the survivors of the window filter][walk / sort scratch][tables][fences] | filter state, join scratch
-        const uint64_t pc_first = align_up(total, 64);
-        const uint64_t pc_cap = ws->filter && total ? std::min<uint64_t>(total, 0xFFFFFF00ull - pc_first) : 0;
-        const uint64_t fence_entries = (pc_first + pc_cap) / 64 + 2;
-        const uint64_t list_bytes = align_up((pc_first + pc_cap + 64) * 4, 256) + align_up(total * (wide ? 8 : 4) + 8, 256) + align_up((nl + 1) * 8, 256) +
-                                    align_up((niv + 1) * 8, 256) + align_up((niv + 2) * 8, 256) + align_up(fence_entries * 4, 256) + align_up(nl * 4, 256) +
-                                    kSortClasses * 256 + list_sort_scratch_bytes(n_long, n_tiles, n_chunks) + 16 * 256 + 8192;
-        if (list_bytes >= budget) return fail(VLG_E_WORKSPACE, "the lists of a super-chunk do not fit the workspace cap");
-        JoinPlan jp;
-        if (vlg_status s = plan_joins(q, pl, ws, sc.Q0, sc.Q1, budget - list_bytes, n, jp)) return s;
-        if (vlg_status s = ws_reserve(ws, list_bytes + jp.filter_need + jp.want_bytes + jp.meta + fixed)) return s;
-        Arena A{ws->arena, ws->arena_bytes};
-        L.P = A.take<uint32_t>(pc_first + pc_cap + 64);
-        uint8_t* other = A.take<uint8_t>(total * (wide ? 8 : 4) + 8);
-        uint64_t* d_off = A.take<uint64_t>(nl + 1);
-        uint64_t* d_ivl = A.take<uint64_t>(niv + 1);
-        uint64_t* d_ivoff = A.take<uint64_t>(niv + 2);
-        uint32_t* F = A.take<uint32_t>(fence_entries);
-        if (A.failed) return fail(VLG_E_INTERNAL, "arena carve failed (class lists)");
-        L.Pc = nullptr; L.pc_cap = 0; L.F = nullptr; L.R = nullptr; L.roff = nullptr;
-        if (total) {
-            VLG_HIP_TRY(hipMemcpyAsync(d_off, off64.data(), (nl + 1) * 8, hipMemcpyHostToDevice, st));
-            VLG_HIP_TRY(hipMemcpyAsync(d_ivl, iv_l.data(), niv * 8, hipMemcpyHostToDevice, st));
-            VLG_HIP_TRY(hipMemcpyAsync(d_ivoff, iv_off.data(), (niv + 1) * 8, hipMemcpyHostToDevice, st));
-            ListSortPlan lp;
-            if (vlg_status s = list_sort_prepare(off64, (uint32_t)nl, A, st, lp)) return s;
-            if (wide) {
-                uint64_t* io = reinterpret_cast<uint64_t*>(other);
-                { Timed t(ws, KS_EXPAND, 0); if (vlg_status s = launch_expand<uint64_t>(d_ivl, d_ivoff, niv, total, io, nullptr, st)) return s; }
-                Timed t(ws, KS_LOCATE, 0);
-                if (vlg_status s = launch_locate<uint64_t>(lview, io, total, d_stats, st)) return s;
-                if (vlg_status s = launch_narrow<uint32_t>(io, L.P, total, st)) return s;
-            } else {
-                { Timed t(ws, KS_EXPAND, 0); if (vlg_status s = launch_expand<uint32_t>(d_ivl, d_ivoff, niv, total, L.P, nullptr, st)) return s; }
-                Timed t(ws, KS_LOCATE, 0);
-                if (vlg_status s = launch_locate<uint32_t>(lview, L.P, total, d_stats, st)) return s;
-            }
-            ws->sample_reads += total;
-            res->sum.locate_mode = VLG_LOCATE_WALKS;
-            {
-                Timed t(ws, KS_SORT, 2ull * total * 4);
-                if (vlg_status s = list_sort_enqueue(lp, L.P, reinterpret_cast<uint32_t*>(other), d_off, pos_bits, st, ws->list_sort != 2)) return s;
-            }
-            if (total >= 64) {
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(fence_build_kernel<uint32_t>), launch_grid(total / 64, 8192), dim3(256), 0, st, L.P, (uint64_t)0, total / 64, F);
-                VLG_HIP_TRY(hipGetLastError());
-            }
-            L.F = F;
-            L.Pc = pc_cap ? L.P + pc_first : nullptr;
-            L.pc_cap = pc_cap;
-        }
-        res->sum.located_occurrences += total;
-        tr.mark("class lists: locate + sort");
-        for (uint64_t s = q->qsub[sc.Q0]; s < q->qsub[sc.Q1]; ++s) L.off[s] = pl.occ[s] ? L.doff[pl.did[s]] : 0;
-        if (vlg_status s = run_joins<uint32_t>(n, q, ws, res, pl, L, A, sc.Q0, sc.Q1, jp, d_stats, tr)) return s;
-        Q0 = sc.Q1;
-    }
+    VLG_HIP_TRY(hipMemcpyAsync(hs, d_stats, sizeof hs, hipMemcpyDeviceToHost, ws->stream));
+    VLG_HIP_TRY(hipStreamSynchronize(ws->stream));
+    res->sum.checksum = fold_checksum(hs);
+    return VLG_OK;
+}
+// ... and all of them into the summary and the workspace's statistics.  `searched`: the kernel-stat class whose launches took the tree
+// levels of the backward searches
+vlg_status read_stats(vlg_workspace* ws, vlg_result* res, const unsigned long long* d_stats, const vlg_index* idx, int searched)
+{
     unsigned long long hs[kStatsWords];
-    VLG_HIP_TRY(hipMemcpyAsync(hs, d_stats, sizeof hs, hipMemcpyDeviceToHost, st));
-    VLG_HIP_TRY(hipStreamSynchronize(st));
+    if (vlg_status s = read_checksum(ws, res, d_stats, hs)) return s;
     res->sum.lf_steps = hs[0];
     res->sum.wt_levels_locate = hs[1];
-    res->sum.checksum = fold_checksum(hs);
     res->sum.wt_levels_bsearch = hs[3];
+    // algorithmic bytes: 32 B per super-block read (+ one sample per occurrence)
     ws->stats[KS_LOCATE].algorithmic_bytes += 32ull * hs[1] + (uint64_t)idx->hdr.sample_bytes * ws->sample_reads;
-    ws->stats[KS_CLASS_SEARCH].algorithmic_bytes += 32ull * hs[3];
+    ws->stats[searched].algorithmic_bytes += 32ull * hs[3];
     return VLG_OK;
 }
 
 }  // namespace
+
+#include "class_batch.hpp"
 
 extern "C" vlg_status vlg_result_class_intervals(const vlg_result* r, uint64_t* h_ivoff, uint64_t* h_l, uint64_t* h_r)
 {
@@ -2652,17 +2434,7 @@ extern "C" vlg_status vlg_search_batch(const vlg_index* idx, const vlg_queries* 
         const bool pos64 = wide && (idx->hdr.n > (1ull << 32) + 1 || (f64 && f64[0] == '1'));
         vlg_status s = pos64 ? run_batch<uint64_t>(idx, q, ws, res, pl, d_stats, true) : run_batch<uint32_t>(idx, q, ws, res, pl, d_stats, wide);
         if (s) return s;
-        unsigned long long hs[kStatsWords];
-        VLG_HIP_TRY(hipMemcpyAsync(hs, d_stats, sizeof hs, hipMemcpyDeviceToHost, st));
-        VLG_HIP_TRY(hipStreamSynchronize(st));
-        res->sum.lf_steps = hs[0];
-        res->sum.wt_levels_locate = hs[1];
-        res->sum.checksum = fold_checksum(hs);
-        res->sum.wt_levels_bsearch = hs[3];
-        // algorithmic bytes: 32 B per super-block read (+ one sample per occurrence)
-        ws->stats[KS_LOCATE].algorithmic_bytes += 32ull * hs[1] + (uint64_t)idx->hdr.sample_bytes * ws->sample_reads;
-        ws->stats[KS_BSEARCH].algorithmic_bytes += 32ull * hs[3];
-        return VLG_OK;
+        return read_stats(ws, res, d_stats, idx, KS_BSEARCH);
     };
     vlg_status stt;
     {
@@ -2836,10 +2608,8 @@ extern "C" vlg_status vlg_join_batch(const uint64_t* d_lists, const uint64_t* h_
         if (ws->cap_bytes <= 2 * fixed) return fail(VLG_E_WORKSPACE, "workspace cap too small");
         const uint64_t budget = ws->cap_bytes - fixed;
         // arena: [copy of the lists][room for the survivors of the window filter][filter state][join scratch]
-        const uint64_t pc_first = align_up(total, 64);
-        uint64_t pc_cap = ws->filter && total ? std::min<uint64_t>(total, 0xFFFFFF00ull - pc_first) : 0;
-        const uint64_t fence_entries = (pc_first + pc_cap) / 64 + 2;
-        const uint64_t list_bytes = align_up((pc_first + pc_cap + 64) * 8, 256) + align_up((n_lists + 1) * 8, 256) + align_up(fence_entries * 8, 256) + 4096;
+        const ListRoom room(total, ws->filter);
+        const uint64_t list_bytes = align_up(room.positions() * 8, 256) + align_up((n_lists + 1) * 8, 256) + align_up(room.fence_entries * 8, 256) + 4096;
         if (list_bytes >= budget) return fail(VLG_E_WORKSPACE, "the lists do not fit the workspace cap");
         // the input is checked where it lies (ascending lists, largest position) BEFORE anything is planned: the bound on the
         // positions sizes the block bitmaps of the window filter, so the one plan made below is the one that is executed and the
@@ -2866,25 +2636,15 @@ extern "C" vlg_status vlg_join_batch(const uint64_t* d_lists, const uint64_t* h_
         if (vlg_status s = plan_joins(&qq, pl, ws, 0, n_joins, budget - list_bytes, n_positions, jp)) return s;
         if (vlg_status s = ws_reserve(ws, list_bytes + jp.filter_need + jp.want_bytes + jp.meta + fixed)) return s;
         Arena A{ws->arena, ws->arena_bytes};
-        L.P = A.take<uint64_t>(pc_first + pc_cap + 64);
-        uint64_t* F = A.take<uint64_t>(fence_entries);
+        L.P = A.take<uint64_t>(room.positions());
+        uint64_t* F = A.take<uint64_t>(room.fence_entries);
         if (A.failed) return fail(VLG_E_INTERNAL, "arena carve failed (join lists)");
-        if (total) {
-            VLG_HIP_TRY(hipMemcpyAsync(L.P, d_lists, total * 8, hipMemcpyDeviceToDevice, st));
-            if (total >= 64)
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(fence_build_kernel<uint64_t>), launch_grid(total / 64, 8192), dim3(256), 0, st, L.P, (uint64_t)0, total / 64, F);
-            VLG_HIP_TRY(hipGetLastError());
-            L.F = F;
-        }
-        L.Pc = pc_cap ? L.P + pc_first : nullptr;
-        L.pc_cap = pc_cap;
+        if (total) VLG_HIP_TRY(hipMemcpyAsync(L.P, d_lists, total * 8, hipMemcpyDeviceToDevice, st));
+        if (vlg_status s = wire_room_and_fences(L, room, total, F, st)) return s;
         tr.mark("join lists copied + checked");
         if (vlg_status s = run_joins<uint64_t>(n_positions, &qq, ws, res, pl, L, A, 0, n_joins, jp, d_stats, tr)) return s;
         unsigned long long hs[kStatsWords];
-        VLG_HIP_TRY(hipMemcpyAsync(hs, d_stats, sizeof hs, hipMemcpyDeviceToHost, st));
-        VLG_HIP_TRY(hipStreamSynchronize(st));
-        res->sum.checksum = fold_checksum(hs);
-        return VLG_OK;
+        return read_checksum(ws, res, d_stats, hs);
     };
     vlg_status stt;
     {
