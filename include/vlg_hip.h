@@ -492,6 +492,49 @@ vlg_status vlg_queries_k(const vlg_queries* q, uint32_t* h_k);
  * h_begin reads as zeros, a NULL h_end as UINT64_MAX; a batch without windows gives 0 and UINT64_MAX). */
 vlg_status vlg_queries_set_windows(vlg_queries* q, const uint64_t* h_begin, const uint64_t* h_end);
 vlg_status vlg_queries_get_windows(const vlg_queries* q, int* has_windows, uint64_t* h_begin, uint64_t* h_end);
+
+/* Documents: the indexed text as a collection -- proteins, contigs, lines, files laid end to end -- and searches whose matches never
+ * cross a document boundary.  A vlg_documents is a device-resident handle beside the index, like vlg_text_access and
+ * vlg_select_support: it holds the starts b_0 = 0 < b_1 < ... < b_{d-1} < n_text of the d documents and the sentinel b_d = n_text
+ * (8 bytes each, and one fence per 64 of them, laid out as the fences of the occurrence lists are); document j is [b_j, b_{j+1}).
+ *   vlg_documents_create: h_starts is a host array of n_docs starts, copied.  Checked on the host before a device is asked for: NULL
+ *     starts, n_docs == 0, h_starts[0] != 0, starts that do not strictly ascend, a start >= n_text (so n_text == 0 too) and
+ *     n_docs >= 2^32 - 16 give VLG_E_INVALID; then VLG_E_NO_DEVICE without a device.  Returns when the starts are on the device.
+ *   vlg_documents_locate_batch: doc[j] = the document of positions[j], offset[j] = positions[j] - its start -- what turns a hit into
+ *     (protein, offset).  One lower-bound kernel.  positions, doc and offset (either output may be NULL) are DEVICE arrays of n
+ *     entries, as for vlg_psi_batch.  A position >= n_text gets doc = UINT64_MAX and offset = UINT64_MAX.  Runs on the null stream and
+ *     returns when the results are there (like vlg_quad_lf_batch; neither entry point takes a stream).
+ * vlg_queries_set_documents(q, d) makes every later vlg_search_batch of the batch document-bounded; d == NULL removes the documents and
+ * the batch is what it was.  Host only (no device, no stream), the contract of vlg_queries_set_windows; the handle is borrowed and must
+ * outlive the searches.  Any batch takes documents: byte, integer, character classes, mismatch budgets.  A batch that carries windows
+ * refuses documents and a batch that carries documents refuses windows: VLG_E_UNSUPPORTED, the batch left as it was.
+ * Semantics.  An occurrence of a sub-pattern of m symbols at v lies inside a document iff doc(v) == doc(v + m - 1).  The matches of a
+ * query are, for j ascending, the matches of the same query on the stand-alone text T[b_j, b_{j+1}) with b_j added to every position:
+ * exactly the answer of a windowed batch with one entry (query, b_j, b_{j+1}) per document, concatenated -- counts, first positions,
+ * tuples, n_matches and the checksum follow from it -- but with ONE batch entry per query and every distinct occurrence list located
+ * and sorted once.  This holds in both dialects: a match in one document never delays the first match of the next (the restart key
+ * end + end_len of the non-overlap rule is capped at the next boundary, which matters for the benchmark dialect's end_len = |s_0|).
+ * With the single document [0, n_text) the result is bit-identical to that of the batch without documents.
+ * How: the join's link and jump passes run instantiations that look the next boundary nb(x) of every list element up:
+ * an element whose sub-pattern crosses nb(x) is infeasible, its gap window ends at min(x + hi, nb(x) - m') for a next sub-pattern of m'
+ * symbols.  The window filter, sort, locate and gather are untouched (the filter keeps the uncapped windows: a superset).  A batch
+ * without documents launches exactly the kernels it launched before.  The workspace option "fuse_jump" = 0 is honoured: the separate
+ * jump pass applies the same restart cap.
+ * Road by road:
+ *   vlg_search_batch honours documents on byte and integer indexes (plain or rrr, either sampling) and on batches with classes or
+ *     budgets.  n_text of the handle must be the index's text length (n - 1, without the sentinel): VLG_E_INVALID otherwise, at
+ *     search time, before any launch.  A collective search (more than one rank) of such a batch: VLG_E_UNSUPPORTED before any launch.
+ *   vlg_wtsa_search_batch and vlg_wtsa_search_window_batch refuse a batch with documents: VLG_E_UNSUPPORTED before any launch.
+ *   vlg_join_batch joins caller-built lists and does not look at documents; vlg_queries_occurrences, vlg_queries_intervals and
+ *     vlg_wtsa_ranges answer per sub-pattern and ignore them. */
+typedef struct vlg_documents vlg_documents;
+vlg_status vlg_documents_create(const uint64_t* h_starts, uint64_t n_docs, uint64_t n_text, vlg_documents** out);
+void vlg_documents_destroy(vlg_documents* d);
+uint64_t vlg_documents_count(const vlg_documents* d);
+uint64_t vlg_documents_text_length(const vlg_documents* d);
+vlg_status vlg_documents_locate_batch(const vlg_documents* d, const uint64_t* positions, uint64_t n, uint64_t* doc, uint64_t* offset);
+vlg_status vlg_queries_set_documents(vlg_queries* q, const vlg_documents* d);
+vlg_status vlg_queries_get_documents(const vlg_queries* q, const vlg_documents** out);
 void vlg_queries_destroy(vlg_queries* q);
 
 /* Character classes: a position of a sub-pattern may accept a SET of bytes -- PROSITE motifs (C-x(2,4)-C-x(3)-[LIVMFYWC] is

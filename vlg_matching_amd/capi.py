@@ -171,6 +171,13 @@ SYMBOLS = [
     ("vlg_queries_k", _I, [_P, _P]),
     ("vlg_queries_set_windows", _I, [_P, _P, _P]),
     ("vlg_queries_get_windows", _I, [_P, C.POINTER(C.c_int), _P, _P]),
+    ("vlg_documents_create", _I, [_P, _U64, _U64, C.POINTER(_P)]),
+    ("vlg_documents_destroy", None, [_P]),
+    ("vlg_documents_count", _U64, [_P]),
+    ("vlg_documents_text_length", _U64, [_P]),
+    ("vlg_documents_locate_batch", _I, [_P, _P, _U64, _P, _P]),
+    ("vlg_queries_set_documents", _I, [_P, _P]),
+    ("vlg_queries_get_documents", _I, [_P, C.POINTER(_P)]),
     ("vlg_queries_set_mismatches", _I, [_P, _P]),
     ("vlg_queries_get_mismatches", _I, [_P, C.POINTER(C.c_int), _P]),
     ("vlg_queries_destroy", None, [_P]),

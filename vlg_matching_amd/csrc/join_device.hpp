@@ -1,6 +1,7 @@
 // Device side of the join (K5): search helpers, feasibility bitset, link / jump / chain / gather kernels.
 // Internal to search.hip's translation unit (everything has internal linkage); included exactly once from there.
 #pragma once
+#include "doc_cut.hpp"
 // =============================================================================================
 // Join kernels
 // =============================================================================================
@@ -425,6 +426,72 @@ __device__ __forceinline__ uint32_t wave_seg_find(const uint32_t* __restrict__ s
     return uniform(lb ? lb - 1 : 0u);
 }
 
+// ---- documents (vlg_queries_set_documents; doc_cut.hpp holds the arithmetic) -----------------------------------------------------
+// What the kDocs instantiations of the passes below receive beside their other arguments: the starts of the documents with the
+// sentinel n_text (B[0, nB), ascending), their fences (BF[g] = B[64 g + 63], g < nB >> 6) and, per segment of the chunk, the symbols of
+// its sub-pattern -- beside SegMeta, which the passes without documents read too and which therefore stays as it is.
+struct DocRef { const uint64_t* B; const uint64_t* BF; uint32_t nB; const uint64_t* seg_len; };
+
+// first entry > x, one lane on its own: the fences first (dense lines), then one block of 64
+__device__ __forceinline__ uint64_t doc_next_boundary_dev(const DocRef& d, uint64_t x)
+{
+    const uint64_t g = vlg::doc_upper_bound(d.BF, 0, d.nB >> 6, x);          // first block whose last entry is > x
+    const uint64_t w0 = g << 6, w1 = w0 + 64 < d.nB ? w0 + 64 : d.nB;
+    const uint64_t r = vlg::doc_upper_bound(d.B, w0, w1, x);
+    return d.B[r < d.nB ? r : d.nB - 1];                                     // (x < n_text = B[nB - 1] for every list element)
+}
+
+// The next boundaries of a wave's step.  The keys of a step ascend from lane 0 to lane `last`, and most steps lie inside the document
+// of the step before: the wave keeps that document [c_lo, c_hi) and asks nothing while the step's first and last key fall into it.
+// Otherwise it ranks both among the starts, once per wave (64-ary through the fences, wave-uniform addresses); if they share a
+// document the step shares one boundary, else every lane bisects between the two ranks.
+struct DocWave {
+    uint64_t c_lo = 1, c_hi = 0;        // wave-uniform; empty at first
+    uint32_t r0 = 0, r1 = 0;            // ranks (index of the first entry > key) of the step's first and last key
+    bool shared = false;
+    // (all 64 lanes call it; xf, xl wave-uniform)
+    __device__ __forceinline__ void locate(const DocRef& d, uint64_t xf, uint64_t xl)
+    {
+        shared = xf >= c_lo && xl < c_hi;
+        if (shared) return;
+        const uint32_t top = d.nB - 1;
+        r0 = wave_kary_lower_bound<uint64_t>(d.B, d.BF, 0, d.nB, sat_add(xf, 1));
+        r0 = uniform(r0 < top ? r0 : top);
+        r1 = wave_kary_lower_bound<uint64_t>(d.B, d.BF, r0, d.nB, sat_add(xl, 1));
+        r1 = uniform(r1 < top ? r1 : top);
+        c_hi = d.B[r1];
+        c_lo = r1 ? d.B[r1 - 1] : 0;                                        // the last key's document: the next step most likely starts in it
+        shared = r0 == r1;
+    }
+    __device__ __forceinline__ uint64_t nb(const DocRef& d, uint64_t x) const
+    {
+        if (shared) return c_hi;
+        const uint64_t r = vlg::doc_upper_bound(d.B, r0, r1, x);            // in [r0, r1]: both are entries
+        return d.B[r];
+    }
+};
+
+// gap window of the element at x under documents: false = the element crosses its boundary or no next sub-pattern fits behind it;
+// otherwise the upper end is capped (doc_cut.hpp)
+template <typename pos_t>
+__device__ __forceinline__ bool doc_window(uint64_t x, uint64_t m, uint64_t m_next, uint64_t nb, pos_t& thi)
+{
+    if (x >= nb || vlg::doc_straddles(x, m, nb)) return false;
+    uint64_t t = (uint64_t)thi;
+    if (!vlg::doc_cap_window(x, m_next, nb, t)) return false;
+    thi = (pos_t)t;
+    return true;
+}
+// restart key of a chain that ends at `end`: end + end_len, capped at the boundary nb when kDocs; false = beyond the positions' range
+template <typename pos_t, bool kDocs>
+__device__ __forceinline__ bool restart_key(uint64_t end, uint64_t end_len, uint64_t nb, pos_t& key)
+{
+    if (!kDocs) { pos_t unused; return gap_window<pos_t>(end, end_len, end_len, key, unused); }
+    const uint64_t k = vlg::doc_cap_restart(end, end_len, nb);
+    key = (pos_t)k;
+    return k <= (uint64_t)(pos_t)~(pos_t)0;
+}
+
 // Feasibility of every slot is ONE BIT; "nearest feasible slot at or after j" is a successor query on a hierarchical
 // bitset: level 0 = the feasibility bits, bit i of level l+1 = (word i of level l != 0).  A query reads one word per
 // level it has to climb (almost always just level 0), so the per-level reverse scans of a 4-byte-per-slot array are gone.
@@ -478,10 +545,11 @@ __global__ void bits_summary_kernel(const uint64_t* __restrict__ in, uint64_t in
 }
 
 // single-sub-pattern queries (class dist 0): every element is a feasible chain that ends at itself
-template <typename pos_t>
-__global__ void __launch_bounds__(256) join_init_kernel(const pos_t* __restrict__ P, const uint32_t* __restrict__ seg_begin, uint32_t nseg,
-                                                        const SegMeta* __restrict__ sm, uint64_t r0, uint64_t r1, uint64_t* __restrict__ fbits,
-                                                        pos_t* __restrict__ endp)
+// kDocs: except the elements that cross a document boundary
+template <typename pos_t, bool kDocs>
+__device__ __forceinline__ void join_init_body(const pos_t* __restrict__ P, const uint32_t* __restrict__ seg_begin, uint32_t nseg,
+                                               const SegMeta* __restrict__ sm, uint64_t r0, uint64_t r1, uint64_t* __restrict__ fbits,
+                                               pos_t* __restrict__ endp, const DocRef& dr)
 {
     const uint32_t lane = threadIdx.x & 63;
     const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
@@ -491,17 +559,37 @@ __global__ void __launch_bounds__(256) join_init_kernel(const pos_t* __restrict_
     uint32_t s_w = seg_find(seg_begin, nseg, run_begin);
     for (uint64_t base = run_begin; base < run_end; base += 64) {
         const uint64_t e = base + lane;
+        bool inside = e < run_end;
         if (e < run_end) {
             uint32_t s = s_w;
             while (seg_begin[s + 1] <= e) ++s;
             const SegMeta m = sm[s];
-            endp[e] = P[phys_of(m, (uint32_t)e)];
+            const pos_t x = P[phys_of(m, (uint32_t)e)];
+            endp[e] = x;
+            if (kDocs) {
+                const uint64_t nb = doc_next_boundary_dev(dr, (uint64_t)x);
+                inside = (uint64_t)x < nb && !vlg::doc_straddles((uint64_t)x, dr.seg_len[s], nb);
+            }
             s_w = s;
         }
-        const unsigned long long act = __ballot(e < run_end);
+        const unsigned long long act = __ballot(inside);
         if (lane == 0) fbits[base >> 6] = act;         // class ranges and runs are 64-aligned: one word per step
         s_w = __shfl(s_w, 0);                          // lane 0 is always in range and holds the smallest segment
     }
+}
+template <typename pos_t>
+__global__ void __launch_bounds__(256) join_init_kernel(const pos_t* __restrict__ P, const uint32_t* __restrict__ seg_begin, uint32_t nseg,
+                                                        const SegMeta* __restrict__ sm, uint64_t r0, uint64_t r1, uint64_t* __restrict__ fbits,
+                                                        pos_t* __restrict__ endp)
+{
+    join_init_body<pos_t, false>(P, seg_begin, nseg, sm, r0, r1, fbits, endp, DocRef{});
+}
+template <typename pos_t>
+__global__ void __launch_bounds__(256) join_init_docs_kernel(const pos_t* __restrict__ P, const uint32_t* __restrict__ seg_begin, uint32_t nseg,
+                                                             const SegMeta* __restrict__ sm, uint64_t r0, uint64_t r1, uint64_t* __restrict__ fbits,
+                                                             pos_t* __restrict__ endp, DocRef dr)
+{
+    join_init_body<pos_t, true>(P, seg_begin, nseg, sm, r0, r1, fbits, endp, dr);
 }
 
 // what a slot does with its lower bound j (value v) in the next list: the first FEASIBLE element at or after it, if still
@@ -592,13 +680,19 @@ __device__ __forceinline__ void stretch_jump_targets(const pos_t* __restrict__ P
 // kJump: the pass also leaves jump[] for the slots of the class inside [jlo, jhi), the slot range of the chain passes: the raw target
 // (stretch_jump_targets above) for the slots of a first list, whose endp[] it then does not write -- the jump was its only reader --
 // and kNone for every other level.
-template <typename pos_t, bool kLast, bool kJump>
-__global__ void __launch_bounds__(256) join_link_kernel(const pos_t* __restrict__ P, const pos_t* __restrict__ F /* fences of P, or null */,
-                                                        const uint32_t* __restrict__ seg_begin, uint32_t nseg,
-                                                        const SegMeta* __restrict__ sm, uint32_t r0, uint32_t r1,
-                                                        FeasRef fb, uint64_t* __restrict__ fbits_out,
-                                                        pos_t* __restrict__ endp, uint32_t* __restrict__ link,
-                                                        const QueryMeta* __restrict__ qm, uint32_t jlo, uint32_t jhi, uint32_t* __restrict__ jump)
+// kDocs (a batch with documents, DocRef above): an element whose sub-pattern crosses its next boundary nb(x) links to nothing, the
+// window of the others ends at min(x + hi, nb(x) - symbols of the next sub-pattern), and the restart key of a level-0 slot is capped
+// at nb(x).  The searches themselves are the same: the lower bound of tlo is found for every element and the next step's fence comes
+// from it; only what link_finish may accept changes.  The body is shared; the kernels without documents instantiate it with kDocs =
+// false and are what they were.
+template <typename pos_t, bool kLast, bool kJump, bool kDocs>
+__device__ __forceinline__ void join_link_body(const pos_t* __restrict__ P, const pos_t* __restrict__ F /* fences of P, or null */,
+                                               const uint32_t* __restrict__ seg_begin, uint32_t nseg,
+                                               const SegMeta* __restrict__ sm, uint32_t r0, uint32_t r1,
+                                               FeasRef fb, uint64_t* __restrict__ fbits_out,
+                                               pos_t* __restrict__ endp, uint32_t* __restrict__ link,
+                                               const QueryMeta* __restrict__ qm, uint32_t jlo, uint32_t jhi, uint32_t* __restrict__ jump,
+                                               const DocRef& dr)
 {
     __shared__ pos_t s_stretch[kJump ? 4 : 1][kJump ? kStretch : 1];
     constexpr pos_t kInf = (pos_t)~(pos_t)0;
@@ -613,6 +707,8 @@ __global__ void __launch_bounds__(256) join_link_kernel(const pos_t* __restrict_
     SegMeta m = sm[s_w], nx = sm[m.next];
     bool lvl0 = kJump && m.level == 0;                             // wave-uniform: the steps inside this segment find their jumps
     uint64_t end_len = lvl0 ? qm[m.query].end_len : 0;
+    uint64_t m_len = kDocs ? dr.seg_len[s_w] : 0, m_next = kDocs ? dr.seg_len[m.next] : 0;     // wave-uniform: symbols of the segment's sub-pattern and of the next
+    DocWave dw;
     uint32_t hint_seg = kNone, hint = 0;                           // answer of the last lane of the previous step and its segment
     pos_t x_pre = 0, x_pre1 = 0;
     bool have_pre = false, have_pre1 = false;
@@ -623,6 +719,7 @@ __global__ void __launch_bounds__(256) join_link_kernel(const pos_t* __restrict_
             m = sm[s_w]; nx = sm[m.next];
             lvl0 = kJump && m.level == 0;
             end_len = lvl0 ? qm[m.query].end_len : 0;
+            if (kDocs) { m_len = dr.seg_len[s_w]; m_next = dr.seg_len[m.next]; }
             have_pre = false; have_pre1 = false;
         }
         if (run_end - base >= 128 && base + 127 < seg_end) {
@@ -650,16 +747,24 @@ __global__ void __launch_bounds__(256) join_link_kernel(const pos_t* __restrict_
             wave_lower_bound2(P, F, hint, nx.pend, tlo0, want0, tlo1, want1, j0, v0, j1, v1);
             if (!want0) j0 = nx.pend;
             if (!want1) j1 = nx.pend;
+            bool in0 = want0, in1 = want1;                         // (the searches above ran for every element: j1 is the next step's fence)
+            uint64_t nb0 = 0, nb1 = 0;
+            if (kDocs) {
+                dw.locate(dr, (uint64_t)__shfl(x0, 0), (uint64_t)__shfl(x1, 63));
+                nb0 = dw.nb(dr, (uint64_t)x0); nb1 = dw.nb(dr, (uint64_t)x1);
+                in0 = want0 && doc_window<pos_t>((uint64_t)x0, m_len, m_next, nb0, thi0);
+                in1 = want1 && doc_window<pos_t>((uint64_t)x1, m_len, m_next, nb1, thi1);
+            }
             pos_t end0 = 0, end1 = 0;
-            const bool ok0 = link_finish<pos_t, kLast>(P, nx, fb, e0, want0, j0, v0, thi0, endp, link, !lvl0, end0);
-            const bool ok1 = link_finish<pos_t, kLast>(P, nx, fb, e1, want1, j1, v1, thi1, endp, link, !lvl0, end1);
+            const bool ok0 = link_finish<pos_t, kLast>(P, nx, fb, e0, in0, j0, v0, thi0, endp, link, !lvl0, end0);
+            const bool ok1 = link_finish<pos_t, kLast>(P, nx, fb, e1, in1, j1, v1, thi1, endp, link, !lvl0, end1);
             const unsigned long long okm0 = __ballot(ok0), okm1 = __ballot(ok1);
             if (lane == 0) { fbits_out[base >> 6] = okm0; fbits_out[(base >> 6) + 1] = okm1; }
             if (kJump) {
                 if (lvl0) {
-                    pos_t key[2] = {0, 0}, unused;
-                    const bool need[2] = {ok0 && gap_window<pos_t>((uint64_t)end0, end_len, end_len, key[0], unused),
-                                          ok1 && gap_window<pos_t>((uint64_t)end1, end_len, end_len, key[1], unused)};
+                    pos_t key[2] = {0, 0};
+                    const bool need[2] = {ok0 && restart_key<pos_t, kDocs>((uint64_t)end0, end_len, nb0, key[0]),
+                                          ok1 && restart_key<pos_t, kDocs>((uint64_t)end1, end_len, nb1, key[1])};
                     tile[lane] = x0; tile[64 + lane] = x1; tile[128 + lane] = x_pre; tile[192 + lane] = x_pre1;
                     wave_sync();
                     uint32_t out[2];
@@ -693,14 +798,21 @@ __global__ void __launch_bounds__(256) join_link_kernel(const pos_t* __restrict_
             if (hint_seg != s_w) hint = wave_kary_lower_bound(P, F, nx.pbegin, nx.pend, (uint64_t)__shfl(tlo, 0));
             j = wave_lower_bound(P, F, hint, nx.pend, tlo, want, v);
             if (!want) j = nx.pend;
+            bool in = want;
+            uint64_t nb = 0;
+            if (kDocs) {                                           // (lanes behind the run's end hold no key: the last key is lane step_last's)
+                dw.locate(dr, (uint64_t)__shfl(x, 0), (uint64_t)__shfl(x, (int)(step_last - base)));
+                nb = dw.nb(dr, (uint64_t)x);
+                in = want && doc_window<pos_t>((uint64_t)x, m_len, m_next, nb, thi);
+            }
             pos_t end = 0;
-            const bool ok = link_finish<pos_t, kLast>(P, nx, fb, e, want, j, v, thi, endp, link, !lvl0, end);
+            const bool ok = link_finish<pos_t, kLast>(P, nx, fb, e, in, j, v, thi, endp, link, !lvl0, end);
             const unsigned long long okm = __ballot(ok);
             if (lane == 0) fbits_out[base >> 6] = okm;
             if (kJump) {
                 if (lvl0) {                                        // (a run or a list ends here: the stretch is loaded, not carried)
-                    pos_t key[1] = {0}, unused;
-                    const bool need[1] = {ok && gap_window<pos_t>((uint64_t)end, end_len, end_len, key[0], unused)};
+                    pos_t key[1] = {0};
+                    const bool need[1] = {ok && restart_key<pos_t, kDocs>((uint64_t)end, end_len, nb, key[0])};
                     tile[lane] = active ? x : (e < m.end ? P[phys_of(m, e)] : kInf);
 #pragma unroll
                     for (uint32_t r = 1; r < kStretch / 64; ++r) tile[64 * r + lane] = e + 64 * r < m.end ? P[phys_of(m, e + 64 * r)] : kInf;
@@ -723,11 +835,17 @@ __global__ void __launch_bounds__(256) join_link_kernel(const pos_t* __restrict_
                 const SegMeta ml = sm[s];
                 const SegMeta nl = sm[ml.next];
                 const uint64_t x = P[phys_of(ml, e)];
-                const uint64_t tlo = sat_add(x, nl.lo), thi = sat_add(x, nl.hi);
+                const uint64_t tlo = sat_add(x, nl.lo);
+                uint64_t thi = sat_add(x, nl.hi), nb = 0;
                 j = gallop_lower_bound(P, (s == hint_seg) ? hint : nl.pbegin, nl.pend, tlo);
                 const bool first = kJump && ml.level == 0;         // a slot of a first list: its end goes into its jump, not into endp
                 pos_t end = 0;
-                if (e < ml.end) {                                  // padding slots between classes belong to no segment
+                bool in = e < ml.end;                              // padding slots between classes belong to no segment
+                if (kDocs && in) {
+                    nb = doc_next_boundary_dev(dr, x);
+                    in = doc_window<uint64_t>(x, dr.seg_len[s], dr.seg_len[ml.next], nb, thi);
+                }
+                if (in) {
                     if (kLast) {
                         ok = j < nl.pend && (uint64_t)P[j] <= thi;
                         if (ok) { if (link) link[e] = j; end = P[j]; if (!first) endp[e] = end; }
@@ -744,7 +862,8 @@ __global__ void __launch_bounds__(256) join_link_kernel(const pos_t* __restrict_
                 if (kJump && e >= jlo && e < jhi) {
                     uint32_t out = kNone;
                     if (first && ok) {                             // (a key beyond the positions' range has no element at or after it)
-                        const uint32_t jp = gallop_lower_bound(P, phys_of(ml, e) + 1, ml.pend, sat_add((uint64_t)end, qm[ml.query].end_len));
+                        const uint64_t lim = kDocs ? vlg::doc_cap_restart((uint64_t)end, qm[ml.query].end_len, nb) : sat_add((uint64_t)end, qm[ml.query].end_len);
+                        const uint32_t jp = gallop_lower_bound(P, phys_of(ml, e) + 1, ml.pend, lim);
                         if (jp < ml.pend) out = ml.begin + (jp - ml.pbegin);
                     }
                     jump[e] = out;
@@ -758,17 +877,37 @@ __global__ void __launch_bounds__(256) join_link_kernel(const pos_t* __restrict_
         hint = __shfl(j, (int)(step_last - base));
     }
 }
+template <typename pos_t, bool kLast, bool kJump>
+__global__ void __launch_bounds__(256) join_link_kernel(const pos_t* __restrict__ P, const pos_t* __restrict__ F /* fences of P, or null */,
+                                                        const uint32_t* __restrict__ seg_begin, uint32_t nseg,
+                                                        const SegMeta* __restrict__ sm, uint32_t r0, uint32_t r1,
+                                                        FeasRef fb, uint64_t* __restrict__ fbits_out,
+                                                        pos_t* __restrict__ endp, uint32_t* __restrict__ link,
+                                                        const QueryMeta* __restrict__ qm, uint32_t jlo, uint32_t jhi, uint32_t* __restrict__ jump)
+{
+    join_link_body<pos_t, kLast, kJump, false>(P, F, seg_begin, nseg, sm, r0, r1, fb, fbits_out, endp, link, qm, jlo, jhi, jump, DocRef{});
+}
+template <typename pos_t, bool kLast, bool kJump>
+__global__ void __launch_bounds__(256) join_link_docs_kernel(const pos_t* __restrict__ P, const pos_t* __restrict__ F, const uint32_t* __restrict__ seg_begin,
+                                                             uint32_t nseg, const SegMeta* __restrict__ sm, uint32_t r0, uint32_t r1, FeasRef fb,
+                                                             uint64_t* __restrict__ fbits_out, pos_t* __restrict__ endp, uint32_t* __restrict__ link,
+                                                             const QueryMeta* __restrict__ qm, uint32_t jlo, uint32_t jhi, uint32_t* __restrict__ jump, DocRef dr)
+{
+    join_link_body<pos_t, kLast, kJump, true>(P, F, seg_begin, nseg, sm, r0, r1, fb, fbits_out, endp, link, qm, jlo, jhi, jump, dr);
+}
 
 // jump[e] for level-0 elements: first feasible element of list 0 at or after end(e)+end_len (kNone = none);
 // slots of other levels get kNone so the tile pass can treat every slot alike.
 // Same walk as the link pass; the list searched is the element's own (the answers lie behind the element itself).
 // The pass of the single-list queries (class 0: every element is feasible and ends at itself, join_init_kernel), and of every
 // class when the workspace option "fuse_jump" is 0; with longer queries the link pass finds the jumps of its level-0 slots itself.
-template <typename pos_t>
-__global__ void __launch_bounds__(256) join_jump_kernel(const pos_t* __restrict__ P, const pos_t* __restrict__ F, const uint32_t* __restrict__ seg_begin, uint32_t nseg,
-                                                        const SegMeta* __restrict__ sm, const QueryMeta* __restrict__ qm, uint64_t r0,
-                                                        uint64_t r1, FeasRef fb, const pos_t* __restrict__ endp,
-                                                        uint32_t* __restrict__ jump)
+// kDocs: the restart key is capped at the next boundary of the slot's own element (every lane looks its boundary up on its own: this
+// pass runs for the single-list queries and with "fuse_jump" = 0 only).
+template <typename pos_t, bool kDocs>
+__device__ __forceinline__ void join_jump_body(const pos_t* __restrict__ P, const pos_t* __restrict__ F, const uint32_t* __restrict__ seg_begin, uint32_t nseg,
+                                               const SegMeta* __restrict__ sm, const QueryMeta* __restrict__ qm, uint64_t r0,
+                                               uint64_t r1, FeasRef fb, const pos_t* __restrict__ endp,
+                                               uint32_t* __restrict__ jump, const DocRef& dr)
 {
     __shared__ pos_t s_tile[4][kTB];
     const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -803,8 +942,8 @@ __global__ void __launch_bounds__(256) join_jump_kernel(const pos_t* __restrict_
                     const uint64_t a = blk0 + lane + 64 * i;
                     key[i] = 0;
                     if (a < blk1 && is_feasible(fb, a)) {                                  // feasible start
-                        pos_t unused;
-                        if (gap_window<pos_t>((uint64_t)endp[a], end_len, end_len, key[i], unused)) need |= 1u << i;
+                        const uint64_t nb = kDocs ? doc_next_boundary_dev(dr, (uint64_t)P[phys_of(m, (uint32_t)a)]) : 0;
+                        if (restart_key<pos_t, kDocs>((uint64_t)endp[a], end_len, nb, key[i])) need |= 1u << i;
                     }
                 }
                 const uint32_t own = phys_of(m, (uint32_t)blk0) + 1;                       // every answer lies behind its own element
@@ -843,7 +982,9 @@ __global__ void __launch_bounds__(256) join_jump_kernel(const pos_t* __restrict_
                 uint32_t out = kNone;
                 if (ml.level == 0 && e < ml.end) {
                     if (is_feasible(fb, e)) {
-                        const uint64_t lim = sat_add((uint64_t)endp[e], qm[ml.query].end_len);
+                        const uint64_t lim = kDocs ? vlg::doc_cap_restart((uint64_t)endp[e], qm[ml.query].end_len,
+                                                                          doc_next_boundary_dev(dr, (uint64_t)P[phys_of(ml, (uint32_t)e)]))
+                                                   : sat_add((uint64_t)endp[e], qm[ml.query].end_len);
                         const uint32_t jp = gallop_lower_bound(P, phys_of(ml, (uint32_t)e) + 1, ml.pend, lim);
                         if (jp < ml.pend) {
                             const uint32_t ej = next_feasible(fb, (uint64_t)ml.begin + (jp - ml.pbegin));
@@ -855,6 +996,39 @@ __global__ void __launch_bounds__(256) join_jump_kernel(const pos_t* __restrict_
             }
             cur = grp_end;
         }
+    }
+}
+template <typename pos_t>
+__global__ void __launch_bounds__(256) join_jump_kernel(const pos_t* __restrict__ P, const pos_t* __restrict__ F, const uint32_t* __restrict__ seg_begin, uint32_t nseg,
+                                                        const SegMeta* __restrict__ sm, const QueryMeta* __restrict__ qm, uint64_t r0,
+                                                        uint64_t r1, FeasRef fb, const pos_t* __restrict__ endp,
+                                                        uint32_t* __restrict__ jump)
+{
+    join_jump_body<pos_t, false>(P, F, seg_begin, nseg, sm, qm, r0, r1, fb, endp, jump, DocRef{});
+}
+template <typename pos_t>
+__global__ void __launch_bounds__(256) join_jump_docs_kernel(const pos_t* __restrict__ P, const pos_t* __restrict__ F, const uint32_t* __restrict__ seg_begin,
+                                                             uint32_t nseg, const SegMeta* __restrict__ sm, const QueryMeta* __restrict__ qm, uint64_t r0,
+                                                             uint64_t r1, FeasRef fb, const pos_t* __restrict__ endp, uint32_t* __restrict__ jump, DocRef dr)
+{
+    join_jump_body<pos_t, true>(P, F, seg_begin, nseg, sm, qm, r0, r1, fb, endp, jump, dr);
+}
+
+// positions -> (document, offset): vlg_documents_locate_batch
+__global__ void __launch_bounds__(256) doc_locate_kernel(DocRef dr, const uint64_t* __restrict__ pos, uint64_t n, uint64_t* __restrict__ doc,
+                                                         uint64_t* __restrict__ offset)
+{
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t x = pos[i];
+        uint64_t dj = ~0ull, off = ~0ull;
+        if (x < dr.B[dr.nB - 1]) {
+            const uint64_t g = vlg::doc_upper_bound(dr.BF, 0, dr.nB >> 6, x);
+            const uint64_t w0 = g << 6, w1 = w0 + 64 < dr.nB ? w0 + 64 : dr.nB;
+            dj = vlg::doc_upper_bound(dr.B, w0, w1, x) - 1;              // (B[0] = 0 <= x: the rank is at least 1)
+            off = x - dr.B[dj];
+        }
+        if (doc) doc[i] = dj;
+        if (offset) offset[i] = off;
     }
 }
 

@@ -9,6 +9,7 @@
 #include "common.hpp"
 #include "search_types.hpp"
 #include "class_query.hpp"
+#include "doc_cut.hpp"
 
 using namespace vlg;
 
@@ -540,6 +541,7 @@ extern "C" vlg_status vlg_queries_set_windows(vlg_queries* q, const uint64_t* h_
     if (!h_begin && !h_end) { q->win_begin.clear(); q->win_end.clear(); return VLG_OK; }
     if (q->has_classes()) return fail(VLG_E_UNSUPPORTED, "a batch with character classes takes no text windows");
     if (q->has_mismatches()) return fail(VLG_E_UNSUPPORTED, "a batch with mismatch budgets takes no text windows");
+    if (q->has_documents()) return fail(VLG_E_UNSUPPORTED, "a batch with documents takes no text windows (vlg_queries_set_documents)");
     // (checked before anything is stored: a refused call keeps the batch's previous windows)
     if (h_begin && h_end)
         for (uint64_t j = 0; j < q->nq; ++j)
@@ -560,6 +562,61 @@ extern "C" vlg_status vlg_queries_get_windows(const vlg_queries* q, int* has_win
         if (h_begin) h_begin[j] = has ? q->win_begin[j] : 0;
         if (h_end) h_end[j] = has ? q->win_end[j] : ~0ull;
     }
+    return VLG_OK;
+}
+// ---- documents: the starts of the documents a text is made of (doc_cut.hpp) ------------------------------------------------------
+extern "C" vlg_status vlg_documents_create(const uint64_t* h_starts, uint64_t n_docs, uint64_t n_text, vlg_documents** out)
+{
+    if (!out) return fail(VLG_E_INVALID, "null argument");
+    *out = nullptr;
+    if (!h_starts) return fail(VLG_E_INVALID, "null argument");
+    if (!n_docs) return fail(VLG_E_INVALID, "documents: at least one document");
+    if (n_docs >= 0xFFFFFFF0ull) return fail(VLG_E_INVALID, "documents: more than 2^32 - 16 documents");
+    if (h_starts[0] != 0) return fail(VLG_E_INVALID, "documents: the first document starts at 0");
+    if (const uint64_t bad = doc_starts_invalid(h_starts, n_docs, n_text))
+        return fail(VLG_E_INVALID, "documents: start " + std::to_string(bad - 1) + " is not above its predecessor and below n_text");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(VLG_E_NO_DEVICE, "no HIP device available");
+    vlg_documents* d = nullptr;
+    std::vector<uint64_t> fences;
+    try {
+        d = new vlg_documents;
+        d->n_docs = n_docs; d->n_text = n_text;
+        d->starts.assign(h_starts, h_starts + n_docs);
+        d->starts.push_back(n_text);
+        fences.resize((n_docs + 1) / 64 + 1);
+        for (uint64_t g = 0; g < (n_docs + 1) / 64; ++g) fences[g] = d->starts[64 * g + 63];
+    } catch (const std::bad_alloc&) { delete d; return fail(VLG_E_OOM, "out of host memory for the documents"); }
+    hipError_t e = hipMalloc((void**)&d->d_starts, (n_docs + 1) * 8);
+    if (e == hipSuccess) e = hipMalloc((void**)&d->d_fences, fences.size() * 8);
+    if (e == hipSuccess) e = hipMemcpy(d->d_starts, d->starts.data(), (n_docs + 1) * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d->d_fences, fences.data(), fences.size() * 8, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { vlg_documents_destroy(d); return fail(e == hipErrorOutOfMemory ? VLG_E_OOM : VLG_E_INTERNAL, std::string("documents: ") + hipGetErrorString(e)); }
+    *out = d;
+    return VLG_OK;
+}
+extern "C" void vlg_documents_destroy(vlg_documents* d)
+{
+    if (!d) return;
+    if (d->d_starts) (void)hipFree(d->d_starts);
+    if (d->d_fences) (void)hipFree(d->d_fences);
+    delete d;
+}
+extern "C" uint64_t vlg_documents_count(const vlg_documents* d) { return d ? d->n_docs : 0; }
+extern "C" uint64_t vlg_documents_text_length(const vlg_documents* d) { return d ? d->n_text : 0; }
+
+extern "C" vlg_status vlg_queries_set_documents(vlg_queries* q, const vlg_documents* d)
+{
+    if (!q) return fail(VLG_E_INVALID, "null argument");
+    if (!d) { q->docs = nullptr; return VLG_OK; }                        // (the batch is what it was before it had documents)
+    if (q->has_windows()) return fail(VLG_E_UNSUPPORTED, "a batch with text windows takes no documents (vlg_queries_set_windows)");
+    q->docs = d;
+    return VLG_OK;
+}
+extern "C" vlg_status vlg_queries_get_documents(const vlg_queries* q, const vlg_documents** out)
+{
+    if (!q || !out) return fail(VLG_E_INVALID, "null argument");
+    *out = q->docs;
     return VLG_OK;
 }
 extern "C" vlg_status vlg_queries_set_mismatches(vlg_queries* q, const uint8_t* h_k)

@@ -1328,6 +1328,9 @@ struct JoinChunk {
     ResultPiece piece{q0, q1};
     bool empty = false;                 // no live query, or no slot of a first list: the chunk has no match and launches no join
     const bool fused = ws->fuse_jump && fuse_jump_env();        // the link passes find the level-0 jumps (link_classes, chain)
+    // documents of the batch (vlg_queries_set_documents), or null: then nothing below differs from a batch that never had any
+    const vlg_documents* docs = q->docs;
+    svec<uint64_t> seg_len; uint64_t* d_seglen = nullptr; DocRef dref{};     // symbols of every segment's sub-pattern, beside sm
     // host tables
     svec<QueryMeta> qm;
     uint32_t kmax = 0, nlive = 0, n_rec = 0;
@@ -1413,6 +1416,7 @@ struct JoinChunk {
         }
         for (int d = (int)kmax - 1; d >= 0; --d) { cls_first[d] = nlive; nlive += cls_count[d]; }
         sm.resize(nlive + 1);
+        if (docs) seg_len.assign(nlive + 1, 0);
         seg_begin.assign(nlive + 2, 0);
         std::vector<uint32_t> fill(kmax + 1, 0);
         std::vector<uint32_t> seg_of_sub(nseg, kNone);
@@ -1428,6 +1432,7 @@ struct JoinChunk {
                 SegMeta& m = sm[seg_of_sub[s - s0]];
                 m.level = i; m.dist = k - 1 - i;
                 m.lo = q->lo[s]; m.hi = q->hi[s];
+                if (docs) seg_len[seg_of_sub[s - s0]] = (q->suboff[s + 1] - q->suboff[s]) / q->sym_bytes;
                 if (filtered(s) && fg->speculated) {                 // compacted with its whole group: segment c starts at cpre[c]
                     m.pbegin = (uint32_t)((Pc - P) + fg->cpre[fg->cidx[s - fg->sub0]]);
                 } else if (filtered(s)) {                            // private list of the query: the survivors, compacted behind P
@@ -1504,6 +1509,7 @@ struct JoinChunk {
         d_sm = A.take<SegMeta>(nlive + 1);
         d_qm = A.take<QueryMeta>(nq);
         d_segb = A.take<uint32_t>(nlive + 2);
+        if (docs) d_seglen = A.take<uint64_t>(nlive + 1);
         d_counts = A.take<unsigned long long>(nq);
         d_recb = A.take<uint32_t>(nq + 1);
         d_recc = A.take<uint32_t>(nq);
@@ -1522,6 +1528,10 @@ struct JoinChunk {
         VLG_HIP_TRY(hipMemcpyAsync(d_sm, sm.data(), (nlive + 1) * sizeof(SegMeta), hipMemcpyHostToDevice, st));
         VLG_HIP_TRY(hipMemcpyAsync(d_segb, seg_begin.data(), (nlive + 2) * 4, hipMemcpyHostToDevice, st));
         VLG_HIP_TRY(hipMemcpyAsync(d_qm, qm.data(), nq * sizeof(QueryMeta), hipMemcpyHostToDevice, st));
+        if (docs) {
+            VLG_HIP_TRY(hipMemcpyAsync(d_seglen, seg_len.data(), (nlive + 1) * 8, hipMemcpyHostToDevice, st));
+            dref = DocRef{docs->d_starts, docs->d_fences, (uint32_t)(docs->n_docs + 1), d_seglen};
+        }
         return VLG_OK;
     }
 
@@ -1545,8 +1555,12 @@ struct JoinChunk {
     {
         if (cls_slot_end[0] > cls_slot_begin[0]) {
             Timed t(ws, KS_JOIN_INIT, 0);
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(join_init_kernel<pos_t>), dim3(runs_grid(cls_slot_end[0] - cls_slot_begin[0])), dim3(256), 0, st, P,
-                               d_segb, nlive, d_sm, cls_slot_begin[0], cls_slot_end[0], lvl_ptr[0], endp);
+            if (docs)
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(join_init_docs_kernel<pos_t>), dim3(runs_grid(cls_slot_end[0] - cls_slot_begin[0])), dim3(256), 0, st, P,
+                                   d_segb, nlive, d_sm, cls_slot_begin[0], cls_slot_end[0], lvl_ptr[0], endp, dref);
+            else
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(join_init_kernel<pos_t>), dim3(runs_grid(cls_slot_end[0] - cls_slot_begin[0])), dim3(256), 0, st, P,
+                                   d_segb, nlive, d_sm, cls_slot_begin[0], cls_slot_end[0], lvl_ptr[0], endp);
         }
         if (vlg_status s = summarize_class(0)) return s;
         for (uint32_t dist = 1; dist < kmax; ++dist) {
@@ -1558,8 +1572,15 @@ struct JoinChunk {
                 Timed t(ws, KS_JOIN_LINK, 8ull * (b1 - b0));
                 const auto kernel = jumps ? (dist == 1 ? join_link_kernel<pos_t, true, true> : join_link_kernel<pos_t, false, true>)
                                           : (dist == 1 ? join_link_kernel<pos_t, true, false> : join_link_kernel<pos_t, false, false>);
-                hipLaunchKernelGGL(kernel, dim3(runs_grid(b1 - b0, kLinkRun)), dim3(256), 0, st, P, F, d_segb, nlive, d_sm, (uint32_t)b0, (uint32_t)b1, fref,
-                                   lvl_ptr[0], endp, link, d_qm, (uint32_t)lvl0_begin, (uint32_t)lvl0_end, jump);
+                if (docs) {
+                    const auto dkernel = jumps ? (dist == 1 ? join_link_docs_kernel<pos_t, true, true> : join_link_docs_kernel<pos_t, false, true>)
+                                               : (dist == 1 ? join_link_docs_kernel<pos_t, true, false> : join_link_docs_kernel<pos_t, false, false>);
+                    hipLaunchKernelGGL(dkernel, dim3(runs_grid(b1 - b0, kLinkRun)), dim3(256), 0, st, P, F, d_segb, nlive, d_sm, (uint32_t)b0, (uint32_t)b1,
+                                       fref, lvl_ptr[0], endp, link, d_qm, (uint32_t)lvl0_begin, (uint32_t)lvl0_end, jump, dref);
+                } else {
+                    hipLaunchKernelGGL(kernel, dim3(runs_grid(b1 - b0, kLinkRun)), dim3(256), 0, st, P, F, d_segb, nlive, d_sm, (uint32_t)b0, (uint32_t)b1,
+                                       fref, lvl_ptr[0], endp, link, d_qm, (uint32_t)lvl0_begin, (uint32_t)lvl0_end, jump);
+                }
             }
             if (vlg_status s = summarize_class(dist)) return s;
         }
@@ -1573,7 +1594,10 @@ struct JoinChunk {
             Timed t(ws, KS_JOIN_CHAIN, 8ull * (lvl0_end - lvl0_begin));
             // the jumps the link passes did not leave: all of them (fuse_jump 0), or those of the single-list queries, class 0
             const uint64_t jb = fused ? std::max(cls_slot_begin[0], lvl0_begin) : lvl0_begin, je = fused ? cls_slot_end[0] : lvl0_end;
-            if (je > jb)
+            if (je > jb && docs)
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(join_jump_docs_kernel<pos_t>), dim3(runs_grid(je - jb)), dim3(256), 0, st, P, F, d_segb, nlive, d_sm, d_qm,
+                                   jb, je, fref, endp, jump, dref);
+            else if (je > jb)
                 hipLaunchKernelGGL(HIP_KERNEL_NAME(join_jump_kernel<pos_t>), dim3(runs_grid(je - jb)), dim3(256), 0, st, P, F, d_segb, nlive, d_sm, d_qm, jb,
                                    je, fref, endp, jump);
             if (t0 < lvl0_begin) VLG_HIP_TRY(hipMemsetAsync(jump + t0, 0xFF, (lvl0_begin - t0) * 4, st));   // slots of the first tile before the range
@@ -2364,6 +2388,17 @@ extern "C" vlg_status vlg_result_class_intervals(const vlg_result* r, uint64_t* 
     return VLG_OK;
 }
 
+extern "C" vlg_status vlg_documents_locate_batch(const vlg_documents* d, const uint64_t* positions, uint64_t n, uint64_t* doc, uint64_t* offset)
+{
+    if (!d || (n && !positions)) return fail(VLG_E_INVALID, "null argument");
+    if (!n || (!doc && !offset)) return VLG_OK;
+    hipLaunchKernelGGL(doc_locate_kernel, launch_grid(n, 8192), dim3(256), 0, (hipStream_t) nullptr, DocRef{d->d_starts, d->d_fences, (uint32_t)(d->n_docs + 1), nullptr},
+                       positions, n, doc, offset);
+    VLG_HIP_TRY(hipGetLastError());
+    VLG_HIP_TRY(hipStreamSynchronize(nullptr));
+    return VLG_OK;
+}
+
 extern "C" vlg_status vlg_search_batch(const vlg_index* idx, const vlg_queries* q, vlg_workspace* ws, vlg_result** out)
 {
     if (!idx || !q || !ws || !out) return fail(VLG_E_INVALID, "null argument");
@@ -2372,6 +2407,11 @@ extern "C" vlg_status vlg_search_batch(const vlg_index* idx, const vlg_queries* 
     if (idx->is_int && q->sym_bytes != 4 && q->nsub) return fail(VLG_E_INVALID, "an integer-alphabet index takes query batches parsed by vlg_queries_parse_int");
     // (every rank holds the same batch and refuses alike, before anything is launched or exchanged: no rank waits for another)
     if (q->has_windows() && ws->x_ranks > 1) return fail(VLG_E_UNSUPPORTED, "a collective search takes no text windows (vlg_queries_set_windows)");
+    if (q->has_documents()) {
+        if (ws->x_ranks > 1) return fail(VLG_E_UNSUPPORTED, "a collective search takes no documents (vlg_queries_set_documents)");
+        if (q->docs->n_text != idx->hdr.n - 1)
+            return fail(VLG_E_INVALID, "documents: made for a text of " + std::to_string(q->docs->n_text) + " symbols, the index holds " + std::to_string(idx->hdr.n - 1));
+    }
     // the one branch of a batch with character classes: without them nothing of that path is launched, waited for or copied
     const bool classes = q->has_classes() || q->has_mismatches();
     if (classes) {

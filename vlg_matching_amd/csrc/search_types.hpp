@@ -3,6 +3,15 @@
 #include <cstdint>
 #include <vector>
 
+// The documents of a text (vlg_documents_create): the starts and the sentinel n_text in HBM, and one fence per 64 of them, laid out
+// as the fences of the occurrence lists are (join_device.hpp: F[g] = B[64 g + 63]).  The host copy serves the argument checks.
+struct vlg_documents {
+    uint64_t n_docs = 0, n_text = 0;
+    std::vector<uint64_t> starts;    // [n_docs + 1], starts[n_docs] = n_text
+    uint64_t* d_starts = nullptr;    // [n_docs + 1]
+    uint64_t* d_fences = nullptr;    // [(n_docs + 1) / 64]
+};
+
 struct vlg_queries {
     uint64_t nq = 0, nsub = 0;
     std::vector<uint64_t> qsub;      // [nq+1]
@@ -31,4 +40,7 @@ struct vlg_queries {
     // of its positions (substitutions only), and at least one budget is > 0.  Host state only, like the windows.
     std::vector<uint8_t> sub_k;          // [nsub]
     bool has_mismatches() const { return !sub_k.empty(); }
+    // documents (vlg_queries_set_documents): null = none.  Borrowed: the handle outlives every search of the batch.
+    const vlg_documents* docs = nullptr;
+    bool has_documents() const { return docs != nullptr; }
 };

@@ -661,6 +661,7 @@ extern "C" vlg_status vlg_wtsa_search_window_batch(const vlg_wtsa* x, const vlg_
     if (q->has_classes()) return fail(VLG_E_UNSUPPORTED, "a batch with character classes is searched by vlg_search_batch on a byte FM-index only");
     if (q->has_mismatches()) return fail(VLG_E_UNSUPPORTED, "a batch with mismatch budgets is searched by vlg_search_batch on a byte FM-index only");
     if (q->has_windows()) return fail(VLG_E_INVALID, "the batch carries text windows (vlg_queries_set_windows): this search takes its windows as arrays");
+    if (q->has_documents()) return fail(VLG_E_UNSUPPORTED, "the batch carries documents (vlg_queries_set_documents): vlg_search_batch honours them, this search does not");
     hipStream_t st = ws->stream;
     const uint64_t nq = q->nq, nsub = q->nsub;
     if (nq > 0xFFFFFFF0ull) return fail(VLG_E_UNSUPPORTED, "too many queries in one batch");

@@ -452,6 +452,22 @@ class Queries:
         check(lib().vlg_queries_get_windows(self._h, C.byref(has), b.ctypes.data, e.ctypes.data))
         return (b[: self.n], e[: self.n]) if has.value else None
 
+    def set_documents(self, documents):
+        """Documents of the batch (vlg_queries_set_documents): VlgIndex.search then gives, for every document in turn, the matches
+        the query has on that document alone -- no match crosses a boundary.  A Documents, or None to remove them.  The batch keeps
+        the Documents alive."""
+        if documents is not None and not isinstance(documents, Documents):
+            raise TypeError("a Documents (or None) expected")
+        check(lib().vlg_queries_set_documents(self._h, documents._h if documents is not None else None))
+        self._documents = documents
+
+    def documents(self):
+        """-> the Documents the batch carries, or None"""
+        h = C.c_void_p()
+        check(lib().vlg_queries_get_documents(self._h, C.byref(h)))
+        d = getattr(self, "_documents", None)
+        return d if h.value and d is not None and d._h.value == h.value else None
+
     def set_mismatches(self, k):
         """Mismatch budgets of the batch (vlg_queries_set_mismatches): VlgIndex.search lets sub-pattern s differ from the text in up
         to k[s] of its positions (substitutions only).  A scalar for every sub-pattern or one value (0 .. 255) per sub-pattern of the
@@ -931,6 +947,71 @@ def _u64_batch(a, name, run, *more):
     run(d_i.data_ptr(), d_o.data_ptr(), len(p), *[x.data_ptr() for x in d_more])
     out = d_o.cpu().numpy().view(np.uint64)
     return int(out[0]) if scalar else out
+
+
+class Documents:
+    """The documents a text is made of (vlg_documents): their starts in HBM beside the index.  Queries.set_documents(d) makes a search
+    document-bounded; locate turns positions into (document, offset)."""
+
+    def __init__(self, starts, n_text):
+        self._h = None
+        s = np.asarray(starts)
+        if s.ndim != 1 or (len(s) and s.dtype.kind not in "iu"):
+            raise ValueError("starts: a 1-d array of non-negative integers")
+        if len(s) and s.dtype.kind == "i" and int(s.min()) < 0:
+            raise ValueError("starts: a start is negative")
+        s = np.ascontiguousarray(s, dtype=np.uint64)
+        h = C.c_void_p()
+        check(lib().vlg_documents_create(s.ctypes.data if len(s) else None, len(s), int(n_text), C.byref(h)))
+        self._h = h
+        self.n_text = int(n_text)
+
+    @classmethod
+    def from_starts(cls, starts, n_text):
+        """starts[0] = 0 < starts[1] < ... < n_text: document j is [starts[j], starts[j + 1]), the last one ends at n_text"""
+        return cls(starts, n_text)
+
+    @classmethod
+    def from_separator(cls, text, sep):
+        """One document per `sep`-terminated piece of `text` (bytes or an integer array; sep a byte or a symbol): a document starts at 0
+        and behind every separator, so the separator closes its document."""
+        a = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else np.asarray(text)
+        if isinstance(sep, (bytes, bytearray)):
+            if len(sep) != 1:
+                raise ValueError("sep: one byte")
+            sep = sep[0]
+        after = np.flatnonzero(a == sep).astype(np.uint64) + 1
+        starts = np.concatenate([np.zeros(1, np.uint64), after[after < len(a)]])
+        return cls(starts, len(a))
+
+    def __del__(self):
+        try:
+            if self._h:
+                lib().vlg_documents_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def count(self):
+        return int(lib().vlg_documents_count(self._h))
+
+    def locate_device(self, d_pos_ptr, count, d_doc_ptr, d_offset_ptr):
+        """vlg_documents_locate_batch on device pointers (either output may be None); returns when the results are there"""
+        check(lib().vlg_documents_locate_batch(self._h, d_pos_ptr, int(count), d_doc_ptr, d_offset_ptr))
+
+    def locate(self, positions):
+        """-> (document, offset) of a position (ints) or of an array of positions (np.uint64 arrays); a position >= n_text gives
+        2^64 - 1 twice"""
+        import torch
+        scalar = np.ndim(positions) == 0
+        p = _u64_index_array(positions, "positions")
+        if not len(p):
+            return np.zeros(0, np.uint64), np.zeros(0, np.uint64)
+        d_p = torch.from_numpy(p.view(np.int64)).cuda()
+        d_d, d_o = torch.empty_like(d_p), torch.empty_like(d_p)
+        self.locate_device(d_p.data_ptr(), len(p), d_d.data_ptr(), d_o.data_ptr())
+        doc, off = d_d.cpu().numpy().view(np.uint64), d_o.cpu().numpy().view(np.uint64)
+        return (int(doc[0]), int(off[0])) if scalar else (doc, off)
 
 
 class SelectSupport:
