@@ -537,6 +537,45 @@ vlg_status vlg_queries_set_documents(vlg_queries* q, const vlg_documents* d);
 vlg_status vlg_queries_get_documents(const vlg_queries* q, const vlg_documents** out);
 void vlg_queries_destroy(vlg_queries* q);
 
+/* Document listing: which documents each query of a result matches, and how often -- reduced on the device, where the first positions
+ * already lie sorted per query beside the document starts.  It replaces vlg_result_fetch of every first position (1.2 GB for a result
+ * of the C3 size), a lower bound per position (on the host, or the positions uploaded again for vlg_documents_locate_batch) and a
+ * run-length encoding on the host: what crosses PCIe is one (document, first match) pair per document hit instead of every match.
+ * Semantics.  F_q = the first positions of query q's matches in the order vlg_result_fetch returns them, doc(x) = j with
+ * b_j <= x < b_{j+1}.  The listing of q is the sequence of maximal runs of equal doc(F_q[i]), in order; a run gives
+ *   doc          the document
+ *   count        the length of the run
+ *   first_match  the index of the run's first match in the result's match numbering, offsets[q] + i (offsets of vlg_result_fetch):
+ *                what slices first positions or tuples per document
+ * and df[q] is the number of runs: the documents q matches.  A match belongs to the document of its FIRST position; for a
+ * document-bounded search with the same handle the whole match lies there and count is the number of matches q has on the stand-alone
+ * document.  A run never continues across a query border, even when the neighbouring queries hit the same document.
+ *   vlg_result_list_documents  what = VLG_DOCLIST_PAIRS: df and the pairs.  what = VLG_DOCLIST_DF: only df and the number of pairs (the
+ *     pass that writes the pairs is skipped).  The listing stays on the device until fetched, and borrows neither r nor d once the call
+ *     has returned.  Runs on the null stream and returns when the listing is there (like vlg_documents_locate_batch: no stream, no
+ *     workspace; every search synchronises its stream before it returns its result).  A result without matches gives a listing of zero
+ *     pairs and launches nothing.
+ *     Accepted: every result of vlg_search_batch (byte or integer index, plain or rrr, classes, budgets, windows, documents or none,
+ *     one chunk or several), of vlg_join_batch, of vlg_wtsa_search_batch and of vlg_wtsa_search_window_batch.
+ *     Refused, nothing returned and *out untouched: a NULL argument or an unknown `what` (VLG_E_INVALID); a match whose first position
+ *     is >= vlg_documents_text_length(d), i.e. documents of another text (VLG_E_INVALID); the result of a collective search that holds
+ *     only part of the queries (vlg_result_owned_queries gives ranges: VLG_E_UNSUPPORTED).
+ *   vlg_doc_listing_info   either output may be NULL.
+ *   vlg_doc_listing_fetch  h_df[q], h_offsets (n_queries + 1, exclusive prefix sum of df: query q owns the pairs
+ *     [h_offsets[q], h_offsets[q + 1])), and h_docs / h_counts / h_first_match of n_pairs entries each.  Any pointer may be NULL; one of
+ *     the last three on a VLG_DOCLIST_DF listing gives VLG_E_INVALID.  Documents cross PCIe 4 bytes wide (n_docs < 2^32 - 16), counts
+ *     are taken on the host from consecutive first_match values, closed by the query's end.
+ * How: a head pass in the element-parallel shape of the join passes (matches dealt to waves in runs of VLG_DOCLIST_RUN,
+ * 64 per step: documents through the fences, query borders carried along, one word of head bits per step), a scan of the per-run head
+ * counts, and a pass in which every head writes its pair at its rank.  No search launches anything it did not launch before. */
+typedef struct vlg_doc_listing vlg_doc_listing;
+enum { VLG_DOCLIST_DF = 0, VLG_DOCLIST_PAIRS = 1 };
+vlg_status vlg_result_list_documents(const vlg_result* r, const vlg_documents* d, int what, vlg_doc_listing** out);
+vlg_status vlg_doc_listing_info(const vlg_doc_listing* l, uint64_t* n_queries, uint64_t* n_pairs);
+vlg_status vlg_doc_listing_fetch(const vlg_doc_listing* l, uint64_t* h_df, uint64_t* h_offsets /* n_queries + 1 */,
+                                 uint64_t* h_docs, uint64_t* h_counts, uint64_t* h_first_match /* n_pairs each */);
+void vlg_doc_listing_destroy(vlg_doc_listing* l);
+
 /* Character classes: a position of a sub-pattern may accept a SET of bytes -- PROSITE motifs (C-x(2,4)-C-x(3)-[LIVMFYWC] is
  * "C.{2,4}?C.{3,3}?[LIVMFYWC]"), IUPAC codes (R = [AG]), case-insensitive words ([Tt]he).  Expanding such a query into one query per
  * member string gives other answers: the left-most, lazy, non-overlapping rule applies to the UNION of the alternatives' occurrences.

@@ -9,6 +9,7 @@ _LIB = None
 LOCATE_NONE, LOCATE_WALKS, LOCATE_SWEEP, LOCATE_UNSAMPLE, LOCATE_COPY = range(5)
 OK, E_INVALID, E_NO_DEVICE, E_OOM, E_PARSE, E_ZERO_BYTE, E_UNSUPPORTED, E_WORKSPACE, E_INTERNAL = range(9)
 DIALECT_LIBRARY, DIALECT_BENCHMARK = 0, 1
+DOCLIST_DF, DOCLIST_PAIRS = 0, 1
 
 
 class VlgError(RuntimeError):
@@ -178,6 +179,10 @@ SYMBOLS = [
     ("vlg_documents_locate_batch", _I, [_P, _P, _U64, _P, _P]),
     ("vlg_queries_set_documents", _I, [_P, _P]),
     ("vlg_queries_get_documents", _I, [_P, C.POINTER(_P)]),
+    ("vlg_result_list_documents", _I, [_P, _P, _I, C.POINTER(_P)]),
+    ("vlg_doc_listing_info", _I, [_P, C.POINTER(_U64), C.POINTER(_U64)]),
+    ("vlg_doc_listing_fetch", _I, [_P, _P, _P, _P, _P, _P]),
+    ("vlg_doc_listing_destroy", None, [_P]),
     ("vlg_queries_set_mismatches", _I, [_P, _P]),
     ("vlg_queries_get_mismatches", _I, [_P, C.POINTER(C.c_int), _P]),
     ("vlg_queries_destroy", None, [_P]),

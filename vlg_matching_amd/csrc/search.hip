@@ -2399,6 +2399,8 @@ extern "C" vlg_status vlg_documents_locate_batch(const vlg_documents* d, const u
     return VLG_OK;
 }
 
+#include "doc_list.hpp"
+
 extern "C" vlg_status vlg_search_batch(const vlg_index* idx, const vlg_queries* q, vlg_workspace* ws, vlg_result** out)
 {
     if (!idx || !q || !ws || !out) return fail(VLG_E_INVALID, "null argument");
@@ -2715,6 +2717,7 @@ extern "C" vlg_status vlg_build_constants(vlg_build_constant* out, uint32_t cap,
         {"VLG_SPARSE_TURN", VLG_SPARSE_TURN}, {"VLG_SORT_CLASSES", VLG_SORT_CLASSES}, {"VLG_BUCKET_SORT", VLG_BUCKET_SORT},
         {"VLG_WINDOW_SORT", VLG_WINDOW_SORT}, {"VLG_WINDOWS_PER_TILE", VLG_WINDOWS_PER_TILE}, {"VLG_WINDOW_RANK_LOOP", VLG_WINDOW_RANK_LOOP},
         {"VLG_WINDOW_THREADS", VLG_WINDOW_THREADS}, {"VLG_WINDOW_ITEMS", VLG_WINDOW_ITEMS}, {"VLG_FETCH_THREADS", VLG_FETCH_THREADS},
+        {"VLG_DOCLIST_RUN", VLG_DOCLIST_RUN},
     };
     const uint32_t count = (uint32_t)(sizeof(all) / sizeof(all[0]));
     *n = count;

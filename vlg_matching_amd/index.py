@@ -100,6 +100,13 @@ class SearchResult:
         check(lib().vlg_result_class_intervals(self._h, off.ctypes.data, l.ctypes.data, r.ctypes.data))
         return off, l[: int(off[-1])], r[: int(off[-1])]
 
+    def list_documents(self, documents, pairs=True):
+        """vlg_result_list_documents: which documents each query matches, reduced on the device -> DocListing.  pairs=False computes
+        only df (and the number of pairs)."""
+        h = C.c_void_p()
+        check(lib().vlg_result_list_documents(self._h, documents._h, capi.DOCLIST_PAIRS if pairs else capi.DOCLIST_DF, C.byref(h)))
+        return DocListing(h, bool(pairs))
+
     @property
     def counts(self):
         return self.fetch()[0]
@@ -116,6 +123,57 @@ class SearchResult:
         toff = np.concatenate([[0], np.cumsum(counts * ks)]).astype(np.int64)
         k = int(ks[q])
         return tup[toff[q]: toff[q + 1]].reshape(-1, max(k, 1)) if k else np.zeros((0, 0), np.uint64)
+
+
+class DocListing:
+    """The documents each query of a result matches (vlg_doc_listing), on the device until an attribute asks for it: query q owns the
+    pairs [offsets[q], offsets[q + 1]); pair p says that `counts[p]` consecutive matches of q, from match `first_match[p]` of the
+    result on, begin in document `docs[p]`.  df[q] is the number of pairs of q.  A listing made with pairs=False has df and offsets only."""
+
+    def __init__(self, handle, has_pairs):
+        self._h = handle
+        self.has_pairs = has_pairs
+        nq, npairs = C.c_uint64(), C.c_uint64()
+        check(lib().vlg_doc_listing_info(handle, C.byref(nq), C.byref(npairs)))
+        self.n_queries, self.n_pairs = int(nq.value), int(npairs.value)
+        self._df = self._pairs = None
+
+    def __del__(self):
+        try:
+            if self._h:
+                lib().vlg_doc_listing_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def fetch_into(self, df_ptr, offsets_ptr, docs_ptr, counts_ptr, first_match_ptr):
+        """vlg_doc_listing_fetch into caller-provided host buffers; any pointer may be None."""
+        check(lib().vlg_doc_listing_fetch(self._h, df_ptr, offsets_ptr, docs_ptr, counts_ptr, first_match_ptr))
+
+    def _fetch_df(self):
+        if self._df is None:
+            df, off = np.zeros(max(self.n_queries, 1), np.uint64), np.zeros(self.n_queries + 1, np.uint64)
+            self.fetch_into(df.ctypes.data, off.ctypes.data, None, None, None)
+            self._df = (df[: self.n_queries], off)
+        return self._df
+
+    def _fetch_pairs(self):
+        if self._pairs is None:
+            a = [np.zeros(max(self.n_pairs, 1), np.uint64) for _ in range(3)]
+            self.fetch_into(None, None, a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data)       # (VlgError for a df-only listing)
+            self._pairs = tuple(x[: self.n_pairs] for x in a)
+        return self._pairs
+
+    df = property(lambda self: self._fetch_df()[0])
+    offsets = property(lambda self: self._fetch_df()[1])
+    docs = property(lambda self: self._fetch_pairs()[0])
+    counts = property(lambda self: self._fetch_pairs()[1])
+    first_match = property(lambda self: self._fetch_pairs()[2])
+
+    def of(self, q):
+        """-> (docs, counts, first_match) of query q"""
+        a, b = int(self.offsets[q]), int(self.offsets[q + 1])
+        return self.docs[a:b], self.counts[a:b], self.first_match[a:b]
 
 
 def read_sdsl_file(path, dens=32, rrr=False):
