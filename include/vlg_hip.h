@@ -576,6 +576,54 @@ vlg_status vlg_doc_listing_fetch(const vlg_doc_listing* l, uint64_t* h_df, uint6
                                  uint64_t* h_docs, uint64_t* h_counts, uint64_t* h_first_match /* n_pairs each */);
 void vlg_doc_listing_destroy(vlg_doc_listing* l);
 
+/* Match texts: what every match of a result matched, extracted on the device.  A class position accepts a set of bytes, a budgeted
+ * sub-pattern matches some neighbour of itself, and a gap .{100,2000}? stands for whatever lies between the sub-patterns (for in-silico
+ * PCR that stretch is the amplicon): the positions of a result no longer say what the text holds there.  The first positions and the
+ * tuples, the document starts and a text access are all in HBM; this call composes them without a round trip through the host
+ * (vlg_result_fetch of every tuple, ranges computed and uploaded again, vlg_extract_batch, download).
+ * The rule.  The matches of a result are numbered as vlg_result_fetch returns them.  For match i of query q: p0 its first position, pl
+ * the position of its last sub-pattern (its last tuple value; p0 when k(q) = 1), m_last the number of SYMBOLS of q's last sub-pattern.
+ * The core of the match is [p0, ce), ce = pl + m_last.  The bounds [B0, B1) are [0, n_text) when docs is NULL, otherwise the document of
+ * p0 (a match belongs to the document of its first position, as in the listing).  The extracted range is [b, e):
+ *   b = p0 - min(flank_left, p0 - min(p0, B0))        e = ce + min(flank_right, max(B1, ce) - ce)
+ * The core is never cut, the flanks stop at the text's or the document's ends, and a core that reaches over its document's end (a
+ * result of a search without documents) keeps itself and gets no right flank.  A flank of UINT64_MAX means "to the bound".
+ *   vlg_result_extract_matches  extracts the matches [match_begin, match_end) of the fetch numbering (match_end = UINT64_MAX: to the
+ *     last match), so that a large result can be paged through; the offsets of vlg_result_fetch give the slice of one query.
+ *     max_symbols, when not 0, caps the symbols of the slice: a slice with more is refused BEFORE the symbol buffer is allocated.  The
+ *     texts stay on the device until fetched; the handle borrows none of r, q, t, docs once the call has returned.  Runs on the
+ *     null stream and returns when the texts are there (the listing's contract: no stream, no workspace).  An empty slice or an empty
+ *     result gives a handle with 0 matches and launches nothing.
+ *     Accepted: every result of vlg_search_batch (byte or integer index, plain or rrr, classes, budgets, windows, documents or none, 4-
+ *     or 8-byte positions, one chunk or several), of vlg_join_batch, of vlg_wtsa_search_batch and of vlg_wtsa_search_window_batch; q is
+ *     the batch that was searched (for vlg_join_batch: a batch of the same shape whose last sub-patterns have the joined lengths), t a
+ *     text access of an index of the same text.  A result without tuples (workspace option "tuples" = 0) is accepted iff every query
+ *     with a match in the slice has k = 1.
+ *     Refused, nothing left allocated and *out untouched.  VLG_E_INVALID: a NULL r, q, t or out; match_begin > match_end; match_end
+ *     beyond the matches; a q whose number of queries, or the k of any query, differs from the result's; a byte batch with the text of
+ *     an integer index or the reverse; docs whose text length is not that of t's index; a result without tuples and a k > 1 query with
+ *     a match in the slice; any match whose core is none of the text (ce > n_text, a position behind the text: q, t or docs do not
+ *     belong to this result -- the message says how many, from a counter on the device).  VLG_E_WORKSPACE: more symbols than a
+ *     non-zero max_symbols (the message names both numbers).  VLG_E_UNSUPPORTED: the result of a collective search that holds only
+ *     part of the queries, as the listing refuses it.
+ *   vlg_match_texts_info   any output may be NULL.  symbol_bytes is 1 for a byte index and 4 for an integer one.
+ *   vlg_match_texts_fetch  text i of the slice is h_symbols[h_offsets[i] .. h_offsets[i + 1]) -- uint8_t for a byte index, the ORIGINAL
+ *     uint32_t symbols for an integer one, what vlg_extract_batch writes -- and h_begin[i] is b: a sub-pattern's offset inside its text
+ *     is tuple value - b.  Any pointer may be NULL.
+ * How: a span pass in the shape of the listing's head pass (runs of VLG_DOCLIST_RUN matches per wave, 64 per step; the
+ * query of a lane from the carried offsets, the document of p0 through the fences) writes b, e - 1 and e - b; one scan of the lengths
+ * gives the offsets; vlg_extract_batch walks the ranges.  No search launches anything it did not launch before. */
+typedef struct vlg_match_texts vlg_match_texts;
+vlg_status vlg_result_extract_matches(const vlg_result* r, const vlg_queries* q, const vlg_text_access* t,
+                                      const vlg_documents* docs /* may be NULL */,
+                                      uint64_t flank_left, uint64_t flank_right,
+                                      uint64_t match_begin, uint64_t match_end /* UINT64_MAX: to the last match */,
+                                      uint64_t max_symbols /* 0: no cap */, vlg_match_texts** out);
+vlg_status vlg_match_texts_info(const vlg_match_texts* m, uint64_t* n_matches, uint64_t* n_symbols, uint32_t* symbol_bytes);
+vlg_status vlg_match_texts_fetch(const vlg_match_texts* m, uint64_t* h_offsets /* n_matches + 1 */,
+                                 uint64_t* h_begin /* n_matches: b of every match */, void* h_symbols);
+void vlg_match_texts_destroy(vlg_match_texts* m);
+
 /* Character classes: a position of a sub-pattern may accept a SET of bytes -- PROSITE motifs (C-x(2,4)-C-x(3)-[LIVMFYWC] is
  * "C.{2,4}?C.{3,3}?[LIVMFYWC]"), IUPAC codes (R = [AG]), case-insensitive words ([Tt]he).  Expanding such a query into one query per
  * member string gives other answers: the left-most, lazy, non-overlapping rule applies to the UNION of the alternatives' occurrences.

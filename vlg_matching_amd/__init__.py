@@ -5,4 +5,4 @@ include/vlg_hip.h).  There is no CPU fallback: importing works anywhere, but eve
 VlgError when the library or a HIP device is missing.
 """
 from .capi import VlgError, lib, library_path, build_library  # noqa: F401
-from .index import VlgIndex, WtsaIndex, BitVector, RrrBitVector, SelectSupport, Documents, DocListing, SearchResult, SymbolMap, count, locate, parse_query, parse_class_query, Queries  # noqa: F401
+from .index import VlgIndex, WtsaIndex, BitVector, RrrBitVector, SelectSupport, Documents, DocListing, MatchTexts, SearchResult, SymbolMap, count, locate, parse_query, parse_class_query, Queries  # noqa: F401

@@ -183,6 +183,10 @@ SYMBOLS = [
     ("vlg_doc_listing_info", _I, [_P, C.POINTER(_U64), C.POINTER(_U64)]),
     ("vlg_doc_listing_fetch", _I, [_P, _P, _P, _P, _P, _P]),
     ("vlg_doc_listing_destroy", None, [_P]),
+    ("vlg_result_extract_matches", _I, [_P, _P, _P, _P, _U64, _U64, _U64, _U64, _U64, C.POINTER(_P)]),
+    ("vlg_match_texts_info", _I, [_P, C.POINTER(_U64), C.POINTER(_U64), C.POINTER(C.c_uint32)]),
+    ("vlg_match_texts_fetch", _I, [_P, _P, _P, _P]),
+    ("vlg_match_texts_destroy", None, [_P]),
     ("vlg_queries_set_mismatches", _I, [_P, _P]),
     ("vlg_queries_get_mismatches", _I, [_P, C.POINTER(C.c_int), _P]),
     ("vlg_queries_destroy", None, [_P]),

@@ -299,6 +299,15 @@ struct vlg_index {
     double quad_build_s = 0;
 };
 
+// Text access (kernels.hip: vlg_text_access_create, vlg_extract_batch, vlg_isa_batch; search.hip reads idx for the match texts)
+struct vlg_text_access {
+    const vlg_index* idx = nullptr;
+    uint32_t d = 0;
+    uint32_t isa_bytes = 0;                                        // isa_sample_bytes(n)
+    void* d_isa = nullptr;                                         // ISA[0], ISA[d], ... ((n - 1) / d + 1 entries)
+    uint8_t* d_c2c = nullptr;                                      // byte index: comp2char[256]
+};
+
 namespace vlg {
 // an object under construction: its destroy function takes it, with what it owns by then, unless release() hands it to the caller
 template <class T, void (*Destroy)(T*)> struct DestroyWith { void operator()(T* p) const { Destroy(p); } };

@@ -70,6 +70,32 @@ __device__ __forceinline__ uint32_t doc_of_position(const DocRef& d, uint64_t x)
     return (uint32_t)vlg::doc_upper_bound(d.B, w0, w1, x) - 1;
 }
 
+// The query of the match a wave stands at, carried from step to step (the head pass, and the span pass of match_text.hpp).
+// off[0, nq] are the match offsets of the result's queries; q is a query WITH matches, however many empty ones stand around it.
+struct QueryCarry {
+    uint64_t q = 0, q_end = 0;          // wave-uniform: off[q] <= the match < q_end = off[q + 1]
+    // to the query of match g < off[nq]
+    __device__ __forceinline__ void seek(const uint64_t* __restrict__ off, uint32_t nq, uint64_t g)
+    {
+        q = (uint64_t)uniform(wave_kary_lower_bound<uint64_t>(off, 0, nq + 1, g + 1)) - 1;
+        q_end = off[q + 1];
+    }
+    // to the query of match step_end - 1, 64 offsets at a time; border(v, in) sees every offset the wave passes: lane-wise the
+    // offset v (~0 behind the last) and whether it lies in front of step_end, i.e. whether a query begins at match v of the step
+    template <class F>
+    __device__ __forceinline__ void advance(const uint64_t* __restrict__ off, uint32_t nq, uint32_t lane, uint64_t step_end, F&& border)
+    {
+        while (q_end < step_end) {                                              // wave-uniform; q_end >= the step's first match
+            const uint64_t idx = q + 1 + lane;
+            const uint64_t v = idx <= nq ? off[idx] : ~0ull;
+            const bool in = v < step_end;
+            border(v, in);
+            q += (uint32_t)__popcll(__ballot(in));                              // at least one; off[q] < step_end <= off[nq]
+            q_end = off[q + 1];
+        }
+    }
+};
+
 // One piece of a result as the passes see it: P[0, m) its first positions, `first` the matches of the pieces before it, `pad` its
 // place in the padded numbering (doc_list_math.hpp), n_text the sentinel of the documents.
 template <typename pos_t>
@@ -93,9 +119,9 @@ __global__ void __launch_bounds__(256) doc_heads_kernel(DocListPiece<pos_t> pc, 
 
     // the query of the run's first match: off[q] <= g < off[q + 1] -- a query with matches, however many empty ones stand around it
     const uint64_t g0 = pc.first + run_begin;
-    uint64_t q = (uint64_t)uniform(wave_kary_lower_bound<uint64_t>(off, 0, nq + 1, g0 + 1)) - 1;
-    uint64_t q_end = off[q + 1];
-    const bool first0 = off[q] == g0;
+    QueryCarry qc;
+    qc.seek(off, nq, g0);
+    const bool first0 = off[qc.q] == g0;
 
     DocListWave dw;
     uint32_t carry = ~0u;                                                       // document of the match in front of the step's lane 0
@@ -120,14 +146,7 @@ __global__ void __launch_bounds__(256) doc_heads_kernel(DocListPiece<pos_t> pc, 
         // query borders inside the step: every offset in [gs, step_end) marks its match as the first of a query
         const uint64_t gs = pc.first + s, step_end = gs + (run_end - s < 64 ? run_end - s : 64);
         uint64_t firsts = s == run_begin && first0 ? 1ull : 0ull;
-        while (q_end < step_end) {                                              // wave-uniform; q_end >= gs
-            const uint64_t idx = q + 1 + lane;
-            const uint64_t v = idx <= nq ? off[idx] : ~0ull;
-            const bool in = v < step_end;
-            firsts |= wave_or_u64(in ? 1ull << (v - gs) : 0ull);
-            q += (uint32_t)__popcll(__ballot(in));                              // at least one; off[q] < step_end <= off[nq]
-            q_end = off[q + 1];
-        }
+        qc.advance(off, nq, lane, step_end, [&](uint64_t v, bool in) { firsts |= wave_or_u64(in ? 1ull << (v - gs) : 0ull); });
 
         uint32_t prev = __shfl_up(d, 1);
         if (lane == 0) prev = carry;

@@ -1473,14 +1473,7 @@ extern "C" vlg_status vlg_index_isa_samples(const vlg_index* idx, uint32_t inv_d
 }
 
 // ---- text access: sdsl::extract, csa.text[i], csa.isa[i] (extract.hpp) ----------------------------------------------------------------
-struct vlg_text_access {
-    const vlg_index* idx = nullptr;
-    uint32_t d = 0;
-    uint32_t isa_bytes = 0;                                        // isa_sample_bytes(n)
-    void* d_isa = nullptr;                                         // ISA[0], ISA[d], ... ((n - 1) / d + 1 entries)
-    uint8_t* d_c2c = nullptr;                                      // byte index: comp2char[256]
-};
-
+// (struct vlg_text_access: common.hpp)
 extern "C" vlg_status vlg_text_access_create(const vlg_index* idx, uint32_t inv_dens, void* stream, vlg_text_access** out)
 {
     if (!idx || !out) return fail(VLG_E_INVALID, "null argument");

@@ -2400,6 +2400,7 @@ extern "C" vlg_status vlg_documents_locate_batch(const vlg_documents* d, const u
 }
 
 #include "doc_list.hpp"
+#include "match_text.hpp"
 
 extern "C" vlg_status vlg_search_batch(const vlg_index* idx, const vlg_queries* q, vlg_workspace* ws, vlg_result** out)
 {

@@ -107,6 +107,22 @@ class SearchResult:
         check(lib().vlg_result_list_documents(self._h, documents._h, capi.DOCLIST_PAIRS if pairs else capi.DOCLIST_DF, C.byref(h)))
         return DocListing(h, bool(pairs))
 
+    def extract_matches(self, queries, text_access, flank=0, documents=None, matches=None, max_symbols=0):
+        """vlg_result_extract_matches: the text every match matched, extracted on the device -> MatchTexts.  `queries` is the Queries
+        batch that was searched, `text_access` a TextAccess of an index of the same text.  flank: an int or (left, right), None on a
+        side = to the bound (the text's ends, or the ends of the document of the match's first position when `documents` is given);
+        matches: (begin, end) in the numbering of fetch(), end None = to the last match; max_symbols: refuse a slice with more
+        symbols before they are allocated (0: no cap)."""
+        left, right = flank if isinstance(flank, (tuple, list)) else (flank, flank)
+        left, right = (NO_NEXT if f is None else int(f) for f in (left, right))
+        begin, end = (0, None) if matches is None else matches
+        if left < 0 or right < 0 or int(begin) < 0 or (end is not None and int(end) < 0) or int(max_symbols) < 0:
+            raise ValueError("flank, matches and max_symbols are non-negative")
+        h = C.c_void_p()
+        check(lib().vlg_result_extract_matches(self._h, queries._h, text_access._h, documents._h if documents is not None else None, left, right,
+                                               int(begin), NO_NEXT if end is None else int(end), int(max_symbols), C.byref(h)))
+        return MatchTexts(h)
+
     @property
     def counts(self):
         return self.fetch()[0]
@@ -174,6 +190,47 @@ class DocListing:
         """-> (docs, counts, first_match) of query q"""
         a, b = int(self.offsets[q]), int(self.offsets[q + 1])
         return self.docs[a:b], self.counts[a:b], self.first_match[a:b]
+
+
+class MatchTexts:
+    """The texts of a slice of a result's matches (vlg_match_texts), on the device until fetched: text i of the slice is
+    symbols[offsets[i] : offsets[i + 1]] and begins at text position begin[i] (a sub-pattern's offset inside its text is its tuple
+    value - begin[i]).  Symbols are uint8 for a byte index, the original uint32 symbols for an integer one."""
+
+    def __init__(self, handle):
+        self._h = handle
+        nm, ns, sb = C.c_uint64(), C.c_uint64(), C.c_uint32()
+        check(lib().vlg_match_texts_info(handle, C.byref(nm), C.byref(ns), C.byref(sb)))
+        self.n_matches, self.n_symbols = int(nm.value), int(ns.value)
+        self.symbol_dtype = np.uint32 if sb.value == 4 else np.uint8
+        self._fetched = None
+
+    def __del__(self):
+        try:
+            if self._h:
+                lib().vlg_match_texts_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def fetch_into(self, offsets_ptr, begin_ptr, symbols_ptr):
+        """vlg_match_texts_fetch into caller-provided host buffers; any pointer may be None."""
+        check(lib().vlg_match_texts_fetch(self._h, offsets_ptr, begin_ptr, symbols_ptr))
+
+    def fetch(self):
+        """-> (offsets[n_matches + 1], begin[n_matches], symbols[n_symbols])"""
+        if self._fetched is None:
+            off, beg = np.zeros(self.n_matches + 1, np.uint64), np.zeros(max(self.n_matches, 1), np.uint64)
+            sym = np.zeros(max(self.n_symbols, 1), self.symbol_dtype)
+            self.fetch_into(off.ctypes.data, beg.ctypes.data, sym.ctypes.data)
+            self._fetched = (off, beg[: self.n_matches], sym[: self.n_symbols])
+        return self._fetched
+
+    def of(self, i):
+        """text i of the slice -> bytes (byte index) or np.uint32 array (integer index)"""
+        off, _, sym = self.fetch()
+        s = sym[int(off[i]): int(off[i + 1])]
+        return s if self.symbol_dtype == np.uint32 else s.tobytes()
 
 
 def read_sdsl_file(path, dens=32, rrr=False):
