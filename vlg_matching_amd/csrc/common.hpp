@@ -171,9 +171,9 @@ struct DevBuf {
     template <class T> T* as() const { return reinterpret_cast<T*>(p); }
 };
 // rocPRIM's two calls -- call(nullptr, bytes) asks for the scratch size, call(scratch, bytes) runs -- around a scratch buffer that
-// grows when a call wants more than it holds
-template <class Call>
-hipError_t with_scratch(DevBuf& scratch, Call&& call)
+// grows when a call wants more than it holds: a DevBuf, or any buffer with p, cap and alloc(bytes) (result_passes.hpp: CachedBuf)
+template <class Buf, class Call>
+hipError_t with_scratch(Buf& scratch, Call&& call)
 {
     size_t bytes = 0;
     hipError_t e = call(nullptr, bytes);

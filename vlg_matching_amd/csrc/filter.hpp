@@ -315,7 +315,7 @@ __device__ __forceinline__ void pivot_ranges(const pos_t* __restrict__ P, const 
             fr0[g] = fr1[g] = gh > gl ? gh : gl;
             widest_f = fr0[g] - gl > widest_f ? fr0[g] - gl : widest_f;
         }
-        for (uint32_t w = uniform(wave_max_u32(widest_f)); w; w >>= 1) {
+        for (uint32_t w = uniform(wave_max<uint32_t>(widest_f)); w; w >>= 1) {
             uint64_t v0[G], v1[G];
             uint32_t m0[G], m1[G];
 #pragma unroll
@@ -571,7 +571,7 @@ __global__ void __launch_bounds__(256) filter_pivot_kernel(const pos_t* __restri
                 uint32_t inner = on[g] && below && a1 > from ? a1 - from : 0;    // what every on-element but the first adds
                 for (int o = 32; o > 0; o >>= 1) inner += __shfl_xor(inner, o);
                 const int first = m ? __ffsll((long long)m) - 1 : 0;
-                const uint32_t f0 = __shfl(a0, first), f1 = __shfl(a1, first), top = wave_max_u32(a1);
+                const uint32_t f0 = __shfl(a0, first), f1 = __shfl(a1, first), top = wave_max<uint32_t>(a1);
                 if (lane == 0) {
                     pr.key[rr] = ((uint64_t)seg << 32) | top;
                     pr.first[rr] = make_uint2(f0, f1);

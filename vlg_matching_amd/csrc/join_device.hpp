@@ -273,9 +273,16 @@ __device__ __forceinline__ T wave_min(T v)
     return v;
 }
 
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v)
+template <typename T>
+__device__ __forceinline__ T wave_max(T v)
 {
-    for (int o = 32; o > 0; o >>= 1) { const uint32_t u = __shfl_xor(v, o); v = u > v ? u : v; }
+    for (int o = 32; o > 0; o >>= 1) { const T u = __shfl_xor(v, o); v = u > v ? u : v; }
+    return v;
+}
+template <typename T>
+__device__ __forceinline__ T wave_or(T v)
+{
+    for (int o = 32; o > 0; o >>= 1) v |= __shfl_xor(v, o);
     return v;
 }
 
@@ -432,24 +439,33 @@ __device__ __forceinline__ uint32_t wave_seg_find(const uint32_t* __restrict__ s
 // its sub-pattern -- beside SegMeta, which the passes without documents read too and which therefore stays as it is.
 struct DocRef { const uint64_t* B; const uint64_t* BF; uint32_t nB; const uint64_t* seg_len; };
 
-// first entry > x, one lane on its own: the fences first (dense lines), then one block of 64
-__device__ __forceinline__ uint64_t doc_next_boundary_dev(const DocRef& d, uint64_t x)
+// The rank of x, the index of the first entry > x (nB: none), one lane on its own: the fences first (dense lines), then one block
+// of 64.  Every single-lane lookup goes through it; the document of a position x < n_text = B[nB - 1] is its rank - 1 (B[0] = 0 <= x).
+__device__ __forceinline__ uint64_t doc_rank_dev(const DocRef& d, uint64_t x)
 {
     const uint64_t g = vlg::doc_upper_bound(d.BF, 0, d.nB >> 6, x);          // first block whose last entry is > x
     const uint64_t w0 = g << 6, w1 = w0 + 64 < d.nB ? w0 + 64 : d.nB;
-    const uint64_t r = vlg::doc_upper_bound(d.B, w0, w1, x);
+    return vlg::doc_upper_bound(d.B, w0, w1, x);
+}
+// the first entry > x
+__device__ __forceinline__ uint64_t doc_next_boundary_dev(const DocRef& d, uint64_t x)
+{
+    const uint64_t r = doc_rank_dev(d, x);
     return d.B[r < d.nB ? r : d.nB - 1];                                     // (x < n_text = B[nB - 1] for every list element)
 }
 
-// The next boundaries of a wave's step.  The keys of a step ascend from lane 0 to lane `last`, and most steps lie inside the document
-// of the step before: the wave keeps that document [c_lo, c_hi) and asks nothing while the step's first and last key fall into it.
-// Otherwise it ranks both among the starts, once per wave (64-ary through the fences, wave-uniform addresses); if they share a
-// document the step shares one boundary, else every lane bisects between the two ranks.
+// The documents of a wave's step: the next boundary of every lane's key (nb, the join passes) or its document (doc, the listing and
+// span passes of result_passes.hpp).  Most steps lie inside the document of the step before: the wave keeps that document
+// [c_lo, c_hi) and asks nothing while the step's smallest and largest key fall into it (the keys of a join step ascend from lane 0
+// to lane `last`: its first and last key).  Otherwise it ranks both among the starts, once per wave (64-ary through the fences,
+// wave-uniform addresses); if they share a document the step shares one boundary, else every lane bisects between the two ranks.
+// The keys of the listing and span passes are < n_text = B[nB - 1] (their callers clamp), so their ranks lie in [1, nB - 1]: there
+// sat_add, both clamps and the test of r1 change no value.
 struct DocWave {
     uint64_t c_lo = 1, c_hi = 0;        // wave-uniform; empty at first
-    uint32_t r0 = 0, r1 = 0;            // ranks (index of the first entry > key) of the step's first and last key
+    uint32_t r0 = 0, r1 = 0;            // ranks (index of the first entry > key) of the step's smallest and largest key
     bool shared = false;
-    // (all 64 lanes call it; xf, xl wave-uniform)
+    // (all 64 lanes call it; xf <= xl wave-uniform)
     __device__ __forceinline__ void locate(const DocRef& d, uint64_t xf, uint64_t xl)
     {
         shared = xf >= c_lo && xl < c_hi;
@@ -468,6 +484,11 @@ struct DocWave {
         if (shared) return c_hi;
         const uint64_t r = vlg::doc_upper_bound(d.B, r0, r1, x);            // in [r0, r1]: both are entries
         return d.B[r];
+    }
+    __device__ __forceinline__ uint32_t doc(const DocRef& d, uint64_t x) const
+    {
+        if (shared) return r1 - 1;
+        return (uint32_t)vlg::doc_upper_bound(d.B, r0, r1, x) - 1;          // the rank of x lies in [r0, r1]
     }
 };
 
@@ -582,7 +603,7 @@ __global__ void __launch_bounds__(256) join_init_kernel(const pos_t* __restrict_
                                                         const SegMeta* __restrict__ sm, uint64_t r0, uint64_t r1, uint64_t* __restrict__ fbits,
                                                         pos_t* __restrict__ endp)
 {
-    join_init_body<pos_t, false>(P, seg_begin, nseg, sm, r0, r1, fbits, endp, DocRef{});
+    join_init_body<pos_t, false>(P, seg_begin, nseg, sm, r0, r1, fbits, endp, DocRef());
 }
 template <typename pos_t>
 __global__ void __launch_bounds__(256) join_init_docs_kernel(const pos_t* __restrict__ P, const uint32_t* __restrict__ seg_begin, uint32_t nseg,
@@ -885,7 +906,7 @@ __global__ void __launch_bounds__(256) join_link_kernel(const pos_t* __restrict_
                                                         pos_t* __restrict__ endp, uint32_t* __restrict__ link,
                                                         const QueryMeta* __restrict__ qm, uint32_t jlo, uint32_t jhi, uint32_t* __restrict__ jump)
 {
-    join_link_body<pos_t, kLast, kJump, false>(P, F, seg_begin, nseg, sm, r0, r1, fb, fbits_out, endp, link, qm, jlo, jhi, jump, DocRef{});
+    join_link_body<pos_t, kLast, kJump, false>(P, F, seg_begin, nseg, sm, r0, r1, fb, fbits_out, endp, link, qm, jlo, jhi, jump, DocRef());
 }
 template <typename pos_t, bool kLast, bool kJump>
 __global__ void __launch_bounds__(256) join_link_docs_kernel(const pos_t* __restrict__ P, const pos_t* __restrict__ F, const uint32_t* __restrict__ seg_begin,
@@ -967,7 +988,7 @@ __device__ __forceinline__ void join_jump_body(const pos_t* __restrict__ P, cons
                     }
                 }
                 // ends ascend along a list: the largest answer of this block is a fence for the next one
-                jm = wave_max_u32(jm);
+                jm = wave_max<uint32_t>(jm);
                 fence = jm;
             }
             cur = piece_end;
@@ -1004,7 +1025,7 @@ __global__ void __launch_bounds__(256) join_jump_kernel(const pos_t* __restrict_
                                                         uint64_t r1, FeasRef fb, const pos_t* __restrict__ endp,
                                                         uint32_t* __restrict__ jump)
 {
-    join_jump_body<pos_t, false>(P, F, seg_begin, nseg, sm, qm, r0, r1, fb, endp, jump, DocRef{});
+    join_jump_body<pos_t, false>(P, F, seg_begin, nseg, sm, qm, r0, r1, fb, endp, jump, DocRef());
 }
 template <typename pos_t>
 __global__ void __launch_bounds__(256) join_jump_docs_kernel(const pos_t* __restrict__ P, const pos_t* __restrict__ F, const uint32_t* __restrict__ seg_begin,
@@ -1022,9 +1043,7 @@ __global__ void __launch_bounds__(256) doc_locate_kernel(DocRef dr, const uint64
         const uint64_t x = pos[i];
         uint64_t dj = ~0ull, off = ~0ull;
         if (x < dr.B[dr.nB - 1]) {
-            const uint64_t g = vlg::doc_upper_bound(dr.BF, 0, dr.nB >> 6, x);
-            const uint64_t w0 = g << 6, w1 = w0 + 64 < dr.nB ? w0 + 64 : dr.nB;
-            dj = vlg::doc_upper_bound(dr.B, w0, w1, x) - 1;              // (B[0] = 0 <= x: the rank is at least 1)
+            dj = doc_rank_dev(dr, x) - 1;                                // (B[0] = 0 <= x: the rank is at least 1)
             off = x - dr.B[dj];
         }
         if (doc) doc[i] = dj;

@@ -1,12 +1,13 @@
 // Match texts: what every match of a result matched, extracted on the device -- vlg_result_extract_matches, vlg_match_texts_*
-// (include/vlg_hip.h).  Part of search.hip's translation unit, behind doc_list.hpp; match_span.hpp holds the rule.
+// (include/vlg_hip.h).  Part of search.hip's translation unit: the span kernel, the tuple and last-symbol preparation, the handle and its
+// fetch.  result_passes.hpp holds what the span pass shares with the other consumers of a result, match_span.hpp the rule.
 //
 // The first positions and the tuples of a result lie in HBM beside the document starts, and a text access gives any text range back.
 // Three steps turn the matches [match_begin, match_end) of the fetch numbering into their texts:
-//   spans   : element-parallel in the shape of the listing's head pass -- the matches of the slice that a piece holds are dealt to waves
-//             in runs of kDocListRun, 64 per step.  A lane finds its query (QueryCarry: the wave carries the query of the step's first
+//   spans   : element-parallel -- the matches of the slice that a piece holds are dealt to waves in runs of kDocListRun, 64 per step
+//             (WaveRun).  A lane finds its query (QueryCarry: the wave carries the query of the step's first
 //             match and passes the offsets up to the step's last; a step that leaves its query lets the lanes bisect between the two),
-//             reads p0 and, where k > 1, the match's last tuple value, finds the document of p0 (DocListWave, as the head pass does)
+//             reads p0 and, where k > 1, the match's last tuple value, finds the document of p0 (DocWave, as the listing's head pass does)
 //             and writes b, the inclusive end e - 1 and the length e - b.  A core that is none of the text is counted, not extracted.
 //   scan    : one exclusive scan of the lengths (rocPRIM) gives the out-offsets; its last entry is the number of symbols, read back
 //             once together with the counter.
@@ -15,6 +16,7 @@
 // sub-pattern, tuple base inside the piece) -- from result_alloc, returned.  vlg_extract_batch brings its own: segment counts from
 // hipMalloc / hipFree on every call, a scan, a read-back and two synchronisations of its own (part of the fixed cost).
 #include "match_span.hpp"
+#include "result_passes.hpp"
 
 namespace {
 
@@ -33,19 +35,17 @@ template <typename pos_t>
 __global__ void __launch_bounds__(256) match_span_kernel(SpanPiece<pos_t> pc, SpanQueries sq, DocRef dr, SpanRule rule, uint64_t* __restrict__ begin,
                                                          uint64_t* __restrict__ last, uint64_t* __restrict__ len, unsigned long long* __restrict__ bad)
 {
-    const uint32_t lane = threadIdx.x & 63;
-    const uint64_t run = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (run >= vlg::doclist_runs(pc.b - pc.a, kDocListRun)) return;             // (whole waves leave)
-    const uint64_t run_begin = pc.a + run * kDocListRun;
-    const uint64_t run_end = pc.b - run_begin > kDocListRun ? run_begin + kDocListRun : pc.b;
+    const WaveRun w(pc.a, pc.b);
+    if (w.empty()) return;
+    const uint32_t lane = w.lane;
     const uint64_t top = rule.n_text - 1;                                       // (documents: n_text >= 1)
 
     QueryCarry qc;
-    qc.seek(sq.off, sq.nq, pc.first + run_begin);
-    DocListWave dw;
+    qc.seek(sq.off, sq.nq, pc.first + w.begin);
+    DocWave dw;
     uint32_t n_bad = 0;
-    for (uint64_t s = run_begin; s < run_end; s += 64) {
-        const uint64_t n_step = run_end - s < 64 ? run_end - s : 64;
+    for (uint64_t s = w.begin; s < w.end; s += 64) {
+        const uint64_t n_step = w.end - s < 64 ? w.end - s : 64;
         const bool valid = lane < n_step;
         const uint64_t e = s + (valid ? lane : n_step - 1);                     // (a lane behind the run repeats its last match)
         const uint64_t g = pc.first + e, step_end = pc.first + s + n_step;
@@ -65,7 +65,7 @@ __global__ void __launch_bounds__(256) match_span_kernel(SpanPiece<pos_t> pc, Sp
         uint64_t B0 = 0, B1 = rule.n_text;
         if (dr.B) {                                                             // wave-uniform
             const uint64_t x = p0 < top ? p0 : top;                             // (a position behind the text is not ok anyway)
-            dw.locate(dr, wave_min<uint64_t>(x), wave_max_u64(x));
+            dw.locate(dr, wave_min<uint64_t>(x), wave_max<uint64_t>(x));
             if (dw.shared) { B0 = dw.c_lo; B1 = dw.c_hi; }
             else { const uint32_t d = dw.doc(dr, x); B0 = dr.B[d]; B1 = dr.B[d + 1]; }
         }
@@ -80,17 +80,6 @@ __global__ void __launch_bounds__(256) match_span_kernel(SpanPiece<pos_t> pc, Sp
         n_bad += (uint32_t)__popcll(__ballot(valid && !ok));
     }
     if (n_bad && lane == 0) atomicAdd(bad, (unsigned long long)n_bad);
-}
-
-template <typename pos_t>
-void match_span_launch(const ResultPiece& p, uint64_t first, uint64_t a, uint64_t b, uint64_t out0, const SpanQueries& sq, const vlg_documents* d,
-                       const SpanRule& rule, uint64_t* begin, uint64_t* last, uint64_t* len, unsigned long long* bad)
-{
-    const uint64_t runs = vlg::doclist_runs(b - a, kDocListRun);
-    const DocRef dr = d ? DocRef{d->d_starts, d->d_fences, (uint32_t)(d->n_docs + 1), nullptr} : DocRef{nullptr, nullptr, 0, nullptr};
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(match_span_kernel<pos_t>), dim3((uint32_t)((runs + 3) / 4)), dim3(256), 0, (hipStream_t) nullptr,
-                       SpanPiece<pos_t>{static_cast<const pos_t*>(p.d_first), static_cast<const pos_t*>(p.d_tuples), first, a, b, out0}, sq, dr, rule, begin,
-                       last, len, bad);
 }
 
 }  // namespace
@@ -108,9 +97,11 @@ extern "C" vlg_status vlg_result_extract_matches(const vlg_result* r, const vlg_
 {
     static const char* const fn = "vlg_result_extract_matches: ";
     if (!r || !q || !t || !out) return fail(VLG_E_INVALID, "null argument");
-    if (!r->owned.empty()) return fail(VLG_E_UNSUPPORTED, std::string(fn) + "the result of a collective search holds only part of the queries");
-    const uint64_t nq = r->counts.size();
-    if (nq >= 0xFFFFFFFFull) return fail(VLG_E_UNSUPPORTED, std::string(fn) + "more than 2^32 - 2 queries");
+    ResultView v;
+    if (vlg_status s = v.build(r, "vlg_result_extract_matches")) return s;
+    const uint64_t nq = v.nq, np = v.np, M = v.matches();
+    const uint64_t* const off = v.off.data();
+    const uint64_t* const first = v.lay.data();                                 // [np + 1]
     if (q->nq != nq || q->qsub.size() != nq + 1 || r->k.size() != nq)
         return fail(VLG_E_INVALID, std::string(fn) + "the batch has " + std::to_string(q->nq) + " queries, the result " + std::to_string(nq));
     for (uint64_t i = 0; i < nq; ++i)
@@ -127,35 +118,19 @@ extern "C" vlg_status vlg_result_extract_matches(const vlg_result* r, const vlg_
         return fail(VLG_E_INVALID, std::string(fn) + "documents of a text of " + std::to_string(docs->n_text) + " symbols, the text access has " +
                                        std::to_string(n_text));
 
-    std::vector<uint64_t> off(nq + 1);
-    off[0] = 0;
-    for (uint64_t i = 0; i < nq; ++i) off[i + 1] = off[i] + r->counts[i];
-    const uint64_t M = off[nq];
     if (match_end == ~0ull) match_end = M;
     if (match_begin > match_end) return fail(VLG_E_INVALID, std::string(fn) + "match_begin > match_end");
     if (match_end > M) return fail(VLG_E_INVALID, std::string(fn) + "match_end " + std::to_string(match_end) + " beyond the " + std::to_string(M) + " matches");
     const uint64_t ns = match_end - match_begin;
 
-    // the pieces that hold matches, laid end to end; a piece begins with a query and stores all the tuples of its queries or none
-    std::vector<const ResultPiece*> pieces;
-    std::vector<uint64_t> first;
-    uint64_t acc = 0;
-    for (const auto& p : r->pieces)
-        if (p.matches) { pieces.push_back(&p); first.push_back(acc); acc += p.matches; }
-    const uint64_t np = pieces.size();
-    first.push_back(acc);
-    if (acc != M) return fail(VLG_E_INTERNAL, std::string(fn) + "the pieces of the result do not add up to its counts");
-    for (uint64_t j = 0; j < np; ++j) {
-        if (pieces[j]->width != 4 && pieces[j]->width != 8) return fail(VLG_E_INTERNAL, std::string(fn) + "positions of an unknown width");
-        if (!std::binary_search(off.begin(), off.end(), first[j])) return fail(VLG_E_INTERNAL, std::string(fn) + "a piece of the result begins inside a query");
-    }
+    // a piece stores all the tuples of its queries or none
     std::vector<uint64_t> m_last(nq), tbase(nq);
     for (uint64_t i = 0; i < nq; ++i) m_last[i] = vlg::match_last_symbols(q->suboff.data(), q->qsub[i], q->qsub[i + 1], sym_bytes);
-    vlg::match_tuple_bases(off.data(), r->k.data(), nq, first.data(), np, tbase.data());
+    vlg::match_tuple_bases(off, r->k.data(), nq, first, np, tbase.data());
     for (uint64_t i = 0, j = 0; i < nq; ++i) {                                  // (j: the piece of query i, where it has matches)
         if (off[i + 1] == off[i]) continue;
         while (j + 1 < np && off[i] >= first[j + 1]) ++j;
-        const uint64_t tv = pieces[j]->tuple_vals;
+        const uint64_t tv = v.pieces[j]->tuple_vals;
         if (tv) {
             if (tbase[i] + r->counts[i] * r->k[i] > tv) return fail(VLG_E_INTERNAL, std::string(fn) + "the tuples of a piece are fewer than its counts say");
         } else if (r->k[i] > 1 && off[i] < match_end && off[i + 1] > match_begin)      // (the span pass depends on this refusal: without
@@ -173,13 +148,13 @@ extern "C" vlg_status vlg_result_extract_matches(const vlg_result* r, const vlg_
     // handle: [begin: ns][offsets: ns + 1][counter]; scratch: [last: ns][off: nq + 1][m_last: nq][tbase: nq][k: nq, 4 bytes each]
     const uint64_t o_off = ns, o_bad = o_off + ns + 1;
     const uint64_t s_off = ns, s_ml = s_off + nq + 1, s_tb = s_ml + nq, s_k = s_tb + nq;
-    CachedBuf scratch, scan_tmp;
+    CachedBuf scratch;
     VLG_HIP_TRY(m->meta.alloc((o_bad + 1) * 8));
     VLG_HIP_TRY(scratch.alloc(s_k * 8 + nq * 4));
     uint64_t* const d_meta = m->meta.as<uint64_t>();
     uint64_t* const d_scr = scratch.as<uint64_t>();
     VLG_HIP_TRY(hipMemsetAsync(d_meta + o_off + ns, 0, 16, nullptr));          // the entry behind the last length (the scan makes it the total) and the counter
-    VLG_HIP_TRY(hipMemcpyAsync(d_scr + s_off, off.data(), (nq + 1) * 8, hipMemcpyHostToDevice, nullptr));
+    VLG_HIP_TRY(v.upload_off(d_scr + s_off));
     VLG_HIP_TRY(hipMemcpyAsync(d_scr + s_ml, m_last.data(), nq * 8, hipMemcpyHostToDevice, nullptr));
     VLG_HIP_TRY(hipMemcpyAsync(d_scr + s_tb, tbase.data(), nq * 8, hipMemcpyHostToDevice, nullptr));
     VLG_HIP_TRY(hipMemcpyAsync(d_scr + s_k, r->k.data(), nq * 4, hipMemcpyHostToDevice, nullptr));
@@ -188,24 +163,22 @@ extern "C" vlg_status vlg_result_extract_matches(const vlg_result* r, const vlg_
     const SpanQueries sq{d_scr + s_off, d_scr + s_ml, d_scr + s_tb, reinterpret_cast<const uint32_t*>(d_scr + s_k), (uint32_t)nq};
     const SpanRule rule{n_text, flank_left, flank_right};
     unsigned long long* const d_bad = reinterpret_cast<unsigned long long*>(d_meta + o_bad);
+    const DocRef dr = doc_ref(docs);
     for (uint64_t j = 0; j < np; ++j) {
         const uint64_t a = std::max(match_begin, first[j]), b = std::min(match_end, first[j + 1]);
         if (a >= b) continue;
-        if (pieces[j]->width == 4)
-            match_span_launch<uint32_t>(*pieces[j], first[j], a - first[j], b - first[j], a - match_begin, sq, docs, rule, d_meta, d_scr, d_meta + o_off, d_bad);
-        else
-            match_span_launch<uint64_t>(*pieces[j], first[j], a - first[j], b - first[j], a - match_begin, sq, docs, rule, d_meta, d_scr, d_meta + o_off, d_bad);
+        const ResultPiece& p = *v.pieces[j];
+        with_piece_type(p, [&](auto t) {
+            using pos_t = decltype(t);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(match_span_kernel<pos_t>), run_grid(b - a), dim3(256), 0, (hipStream_t) nullptr,
+                               SpanPiece<pos_t>{static_cast<const pos_t*>(p.d_first), static_cast<const pos_t*>(p.d_tuples), first[j], a - first[j], b - first[j],
+                                                a - match_begin},
+                               sq, dr, rule, d_meta, d_scr, d_meta + o_off, d_bad);
+        });
         VLG_HIP_TRY(hipGetLastError());
     }
-    {
-        size_t tmp_bytes = 0;
-        uint64_t* const d_len = d_meta + o_off;
-        VLG_HIP_TRY(rocprim::exclusive_scan(nullptr, tmp_bytes, d_len, d_len, 0ull, ns + 1, rocprim::plus<uint64_t>(), (hipStream_t) nullptr));
-        VLG_HIP_TRY(scan_tmp.alloc(tmp_bytes));
-        VLG_HIP_TRY(rocprim::exclusive_scan(scan_tmp.p, tmp_bytes, d_len, d_len, 0ull, ns + 1, rocprim::plus<uint64_t>(), (hipStream_t) nullptr));
-    }
-    uint64_t back[2] = {0, 0};                                                  // the number of symbols and the counter, read back together
-    VLG_HIP_TRY(hipMemcpy(back, d_meta + o_off + ns, 16, hipMemcpyDeviceToHost));
+    uint64_t back[2] = {0, 0};                                                  // the number of symbols and the counter
+    if (vlg_status s = scan_with_total(d_meta + o_off, ns, back)) return s;
     if (back[1])
         return fail(VLG_E_INVALID, std::string(fn) + std::to_string(back[1]) + " match(es) of the slice do not end inside the text of " + std::to_string(n_text) +
                                        " symbols (queries or a text access that do not belong to this result)");

@@ -1,6 +1,7 @@
 // Workspace, results and the fused search (backward search -> locate -> sort -> window filter -> join).
 //   queries.cpp      query batches (both dialects parsed on the host, uploaded)
 //   join_device.hpp  the device side of the join: search helpers, feasibility bitset, link / jump / chain / gather kernels
+//   result_passes.hpp  what the passes over a finished result share (doc_list.hpp, match_text.hpp)
 //   filter_shape.hpp how one query is filtered and what that is charged (plain C++, also compiled by a CPU test)
 //   filter.hpp       the window filter before the join (kernels + FilterPass, the driver of one filter group)
 //   kernels.hip      backward search, locate (random access and sorted sweep with shared LF trails)
@@ -599,6 +600,7 @@ extern "C" vlg_status vlg_result_fetch32(const vlg_result* r, uint32_t* h_first,
 }
 
 #include "join_device.hpp"
+#include "result_passes.hpp"
 
 // device counters of a batch: [0] LF steps, [1] tree levels of locate, [3] tree levels of the backward searches, [4..5] flags of
 // vlg_join_batch's input check, [kStatsChecksum ..) partial checksums
@@ -1530,7 +1532,7 @@ struct JoinChunk {
         VLG_HIP_TRY(hipMemcpyAsync(d_qm, qm.data(), nq * sizeof(QueryMeta), hipMemcpyHostToDevice, st));
         if (docs) {
             VLG_HIP_TRY(hipMemcpyAsync(d_seglen, seg_len.data(), (nlive + 1) * 8, hipMemcpyHostToDevice, st));
-            dref = DocRef{docs->d_starts, docs->d_fences, (uint32_t)(docs->n_docs + 1), d_seglen};
+            dref = doc_ref(docs, d_seglen);
         }
         return VLG_OK;
     }
@@ -2392,8 +2394,7 @@ extern "C" vlg_status vlg_documents_locate_batch(const vlg_documents* d, const u
 {
     if (!d || (n && !positions)) return fail(VLG_E_INVALID, "null argument");
     if (!n || (!doc && !offset)) return VLG_OK;
-    hipLaunchKernelGGL(doc_locate_kernel, launch_grid(n, 8192), dim3(256), 0, (hipStream_t) nullptr, DocRef{d->d_starts, d->d_fences, (uint32_t)(d->n_docs + 1), nullptr},
-                       positions, n, doc, offset);
+    hipLaunchKernelGGL(doc_locate_kernel, launch_grid(n, 8192), dim3(256), 0, (hipStream_t) nullptr, doc_ref(d), positions, n, doc, offset);
     VLG_HIP_TRY(hipGetLastError());
     VLG_HIP_TRY(hipStreamSynchronize(nullptr));
     return VLG_OK;
