@@ -944,6 +944,11 @@ vlg_status vlg_workspace_profile(vlg_workspace* ws, int enable);
  * "quad_walk" (default 1): the locate kernels walk LF on the quad image of an index that has one (vlg_index_quad_image) -- two tree
  * levels per dependent read; 0 = the binary tree (an A/B inside one library).  Results do not depend on it, "lf_steps" and
  * "wt_levels_locate" included.
+ * "sweep_compact" (default 1): round 0 of the sorted sweep -- where most walks of a dense batch end -- writes the occurrences that go
+ * on to another round densely and in order, and the round's partition by symbol sorts only them; 0 = a finished occurrence keeps its
+ * place, is carried through the partition into its last bucket and dropped afterwards, as in every later round (an A/B inside one
+ * library).  Results do not depend on it, "lf_steps" and "wt_levels_locate" included.  8 bytes of scratch per VLG_SWEEP_CHUNK (2048)
+ * occurrences of a sweep.
  * "list_sort" (default 1): with 32-bit positions every occurrence list is sorted inside itself (short lists in LDS by value ranges;
  * long ones by two LSD radix passes over the top 16 position bits + one LDS pass over windows of whole groups; 2: four LSD passes
  * over all position bits, what lists with clustered positions take anyway); 0, or 64-bit positions: "global_sort_min" (default 2^20): from this many

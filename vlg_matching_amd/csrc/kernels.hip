@@ -1118,7 +1118,8 @@ vlg_status run_locate_sweep(const SweepKernels& K, const uint64_t* d_l, const ui
                             hipStream_t stream, LaunchTimer* timer, Block* member /* member_blocks(n) super-blocks, or null: no LF step is shared */,
                             uint32_t n_member_lists /* the first so many lists are pairwise disjoint and ascend: they make up `member` */,
                             uint64_t* rec /* total words */,
-                            const std::function<vlg_status()>* while_first_step /* host work to do while the first step runs, or null */)
+                            const std::function<vlg_status()>* while_first_step /* host work to do while the first step runs, or null */,
+                            SweepCompaction compaction)
 {
     bool hook_due = while_first_step != nullptr;
     constexpr uint32_t kShift = kWide ? 33 : 32;
@@ -1126,6 +1127,8 @@ vlg_status run_locate_sweep(const SweepKernels& K, const uint64_t* d_l, const ui
     if (sizeof(pos_t) == 4 && K.n > (1ull << 32) + 1) return fail(VLG_E_INTERNAL, "sorted sweep: positions do not fit 32 bits");
     if (K.sigma >= 0xFFFFu) return fail(VLG_E_INTERNAL, "sorted sweep: alphabet too large for the 16-bit partition key");
     const unsigned bits = bit_width64(K.sigma);             // keys 0..sigma (sigma = finished, sorts last)
+    const unsigned live_bits = std::max(1u, bit_width64(K.sigma ? K.sigma - 1 : 0));      // ... and 0..sigma - 1 where no finished element is sorted
+    unsigned long long* const h_done = compaction.h_done;
     const uint64_t batch_max = sweep_batch_max<kWide>();
     if (member) {
         if (total > 0xFFFFFF00ull) return fail(VLG_E_INTERNAL, "member bit-vector: slots need 32 bits");
@@ -1156,26 +1159,41 @@ vlg_status run_locate_sweep(const SweepKernels& K, const uint64_t* d_l, const ui
         uint32_t step = 0;
         pos_t* out = d_out + t0;
         while (alive > tail_threshold && step < 0xFFFFFFu) {
-            VLG_HIP_TRY(hipMemsetAsync(d_counter, 0, 8, stream));
+            const bool first = fused_first && step == 0;
+            const bool compact = first && h_done != nullptr;        // round 0 leaves its survivors alone, densely (sweep_kernels.hpp: commit_turn)
+            // (compact: n_done, the give-up word, the ticket counter and one status word per turn of this round -- sweep_kernels.hpp)
+            VLG_HIP_TRY(hipMemsetAsync(d_counter, 0, compact ? sweep_control_words(alive) * 8 : 8, stream));
             if (timer) timer->begin(0);
-            const vlg_status ks = fused_first && step == 0 ? K.first(t0, t1, val_a, key_a, out, d_counter, member, rec, ahead, reinterpret_cast<uint32_t*>(val_b))      // round 0 makes the elements' words itself
-                                                           : K.step(val_a, key_a, alive, step, out, d_counter, member, rec, t0, ahead && fused_first && step == 1);
+            const vlg_status ks = first ? K.first(t0, t1, val_a, key_a, out, d_counter, member, rec, ahead, reinterpret_cast<uint32_t*>(val_b), compact)      // round 0 makes the elements' words itself
+                                        : K.step(val_a, key_a, alive, step, out, d_counter, member, rec, t0, ahead && fused_first && step == 1);
             if (timer) timer->end(0);
             if (ks) return ks;
-            size_t tb = temp_bytes;
-            if (timer) timer->begin(1, 20ull * alive);           // key + element read once and written once
-            rocprim::double_buffer<uint16_t> dk(key_a, key_b);
-            rocprim::double_buffer<uint64_t> dv(val_a, val_b);
-            hipError_t se = rocprim::radix_sort_pairs(temp, tb, dk, dv, alive, 0, bits, stream);
-            if (timer) timer->end(1);
-            VLG_HIP_TRY(se);
-            unsigned long long done = 0;
-            VLG_HIP_TRY(hipMemcpyAsync(&done, d_counter, 8, hipMemcpyDeviceToHost, stream));
+            // the stable partition of val_a / key_a [0, count) by symbol; the sorted side becomes val_a / key_a
+            const auto partition = [&](uint64_t count, unsigned key_bits) -> vlg_status {
+                size_t tb = temp_bytes;
+                if (timer) timer->begin(1, 20ull * count);       // key + element read once and written once
+                rocprim::double_buffer<uint16_t> dk(key_a, key_b);
+                rocprim::double_buffer<uint64_t> dv(val_a, val_b);
+                hipError_t se = rocprim::radix_sort_pairs(temp, tb, dk, dv, count, 0, key_bits, stream);
+                if (timer) timer->end(1);
+                VLG_HIP_TRY(se);
+                key_a = dk.current(); key_b = dk.alternate();
+                val_a = dv.current(); val_b = dv.alternate();
+                return VLG_OK;
+            };
+            // not compacting: the partition carries the finished elements (key = sigma) into its last bucket, and runs before `done` is known
+            if (!compact) if (vlg_status ps = partition(alive, bits)) return ps;
+            unsigned long long done_here[2] = {0, 0};
+            unsigned long long* done = compact ? h_done : done_here;
+            VLG_HIP_TRY(hipMemcpyAsync(done, d_counter, compact ? 16 : 8, hipMemcpyDeviceToHost, stream));
             if (hook_due) { hook_due = false; if (vlg_status hs = (*while_first_step)()) return hs; }
             VLG_HIP_TRY(hipStreamSynchronize(stream));
-            key_a = dk.current(); key_b = dk.alternate();
-            val_a = dv.current(); val_b = dv.alternate();
-            alive -= done;
+            if (compact && done[kSweepStalled]) return fail(VLG_E_INTERNAL, "sweep compaction stalled");
+            if (done[kSweepDone] > alive) return fail(VLG_E_INTERNAL, "locate sweep: more elements finished than were walking");
+            alive -= done[kSweepDone];
+            // compacting: the round has left its survivors, and nothing else, in val_a / key_a [0, alive); the next round follows the
+            // partition without another round trip (the stragglers' kernel takes its elements in any order: no partition for it)
+            if (compact && alive > tail_threshold) if (vlg_status ps = partition(alive, live_bits)) return ps;
             ++step;
             if (step > 1u << 20) return fail(VLG_E_INTERNAL, "locate sweep did not converge");
         }
@@ -1219,7 +1237,7 @@ vlg_status run_locate_sweep(const SweepKernels& K, const uint64_t* d_l, const ui
 }
 template vlg_status run_locate_sweep<uint32_t, false>(const SweepKernels&, const uint64_t*, const uint64_t*, uint64_t, uint64_t, uint32_t*, uint64_t*, uint64_t*,
                                                       uint16_t*, uint16_t*, void*, size_t, unsigned long long*, uint64_t, hipStream_t, LaunchTimer*, Block*,
-                                                      uint32_t, uint64_t*, const std::function<vlg_status()>*);
+                                                      uint32_t, uint64_t*, const std::function<vlg_status()>*, SweepCompaction);
 
 // the byte index (IndexView: Huffman-shaped tree, plain or rrr bit-vectors, either sampling) in the sweep
 template <typename pos_t, bool kWide>
@@ -1227,7 +1245,7 @@ vlg_status launch_locate_sweep(const IndexView& iv, const uint64_t* d_l, const u
                                pos_t* d_out, uint64_t* val_a, uint64_t* val_b, uint16_t* key_a, uint16_t* key_b, void* temp,
                                size_t temp_bytes, unsigned long long* d_counter, unsigned long long* d_stats, uint64_t tail_threshold,
                                hipStream_t stream, LaunchTimer* timer, Block* member, uint32_t n_member_lists, uint64_t* rec,
-                               const std::function<vlg_status()>* while_first_step, uint8_t* front)
+                               const std::function<vlg_status()>* while_first_step, uint8_t* front, SweepCompaction compaction)
 {
     if (iv.sample_bytes != (kWide ? 8u : 4u)) return fail(VLG_E_INTERNAL, "sorted sweep: sample width does not match the instantiation");
     const bool text_order = shape(iv).text_order;
@@ -1242,7 +1260,7 @@ vlg_status launch_locate_sweep(const IndexView& iv, const uint64_t* d_l, const u
         const SweepKernels K = bind_sweep<tag_t<decltype(walk)>, ByteSampling<kWide, decltype(to)::value>, pos_t, kWide>(iv, d_l, d_out_off, n_pat, d_stats, stream,
                                                                                                                    rec ? front : nullptr);
         return run_locate_sweep<pos_t, kWide>(K, d_l, d_out_off, n_pat, total, d_out, val_a, val_b, key_a, key_b, temp, temp_bytes, d_counter, tail_threshold, stream, timer,
-                                              member, n_member_lists, rec, while_first_step);
+                                              member, n_member_lists, rec, while_first_step, compaction);
     }); });
 }
 // K3u (above): the whole suffix array into sa_full (n words of 32 bits), then the SA intervals of the lists into d_out.
@@ -1339,7 +1357,7 @@ vlg_status launch_sa_dense_copy(const uint32_t* sa, const uint64_t* d_l, const u
     template vlg_status launch_locate_sweep<P, W>(const IndexView&, const uint64_t*, const uint64_t*, uint64_t, uint64_t, P*, uint64_t*, \
                                                   uint64_t*, uint16_t*, uint16_t*, void*, size_t, unsigned long long*, unsigned long long*, \
                                                   uint64_t, hipStream_t, LaunchTimer*, Block*, uint32_t, uint64_t*,                       \
-                                                  const std::function<vlg_status()>*, uint8_t*);
+                                                  const std::function<vlg_status()>*, uint8_t*, SweepCompaction);
 VLG_SWEEP_INST(uint32_t, false)
 VLG_SWEEP_INST(uint32_t, true)        // n = 2^32 + 1 (BASELINE config 4): 33-bit SA indices, 32-bit text positions
 VLG_SWEEP_INST(uint64_t, true)
@@ -1363,7 +1381,7 @@ template vlg_status launch_widen<uint32_t>(const uint32_t*, uint64_t*, uint64_t,
 // the build-time constants of this translation unit (vlg_build_constants)
 KernelConstants kernel_constants()
 {
-    return KernelConstants{VLG_RESOLVE_HOPS, VLG_RESOLVE_CHUNK, VLG_GROUP_CHUNK, VLG_STAGE_LISTS, VLG_SWEEP_PAIRS};
+    return KernelConstants{VLG_RESOLVE_HOPS, VLG_RESOLVE_CHUNK, VLG_GROUP_CHUNK, VLG_STAGE_LISTS, VLG_SWEEP_PAIRS, VLG_SWEEP_CHUNK};
 }
 
 }  // namespace vlg

@@ -26,7 +26,7 @@ template <typename pos_t>
 vlg_status launch_locate(const IndexView& iv, pos_t* d_io, uint64_t total, unsigned long long* d_stats, hipStream_t stream);
 
 // the build-time constants kernels.hip was compiled with (VLG_RESOLVE_HOPS, ...; reported by vlg_build_constants)
-struct KernelConstants { int64_t resolve_hops, resolve_chunk, group_chunk, stage_lists, sweep_pairs; };
+struct KernelConstants { int64_t resolve_hops, resolve_chunk, group_chunk, stage_lists, sweep_pairs, sweep_chunk; };
 KernelConstants kernel_constants();
 
 // Optional per-launch timing hooks (HIP events on the stream), implemented by the workspace.
@@ -49,6 +49,23 @@ inline LocateSlices locate_slices(uint64_t count, uint64_t min_per_wave = 64 * 1
 }
 
 size_t sweep_temp_bytes(uint64_t total, uint32_t sigma, hipStream_t stream);
+#ifndef VLG_SWEEP_CHUNK
+#define VLG_SWEEP_CHUNK 2048
+#endif
+constexpr uint32_t kSweepChunk = VLG_SWEEP_CHUNK;   // consecutive elements a workgroup of a sweep round takes per turn
+static_assert(kSweepChunk >= 256 && kSweepChunk % 256 == 0, "VLG_SWEEP_CHUNK: whole rows of the 256-thread workgroup");
+static_assert(kSweepChunk <= 4096, "VLG_SWEEP_CHUNK: one wave scans a turn's (row, wave) survivor counts, 64 at most");
+// Control words of a compacting sweep round, in front of the status words of its turns (sweep_kernels.hpp: commit_turn): the
+// round's n_done pointer is the start of this block, which the driver clears before every launch.
+constexpr uint32_t kSweepDone = 0, kSweepStalled = 1, kSweepTicket = 2, kSweepStatus = 4;
+inline uint64_t sweep_turns(uint64_t elements) { return (elements + kSweepChunk - 1) / kSweepChunk; }
+// words of the block for a sweep of `elements` occurrences (a multiple of two: the clearing is a multiple of 16 bytes)
+inline uint64_t sweep_control_words(uint64_t elements) { return kSweepStatus + ((sweep_turns(elements) + 1) & ~1ull); }
+// Round 0 compacts (the workspace option "sweep_compact") when the launcher gets 16 pinned bytes for the round's `done` and give-up
+// word to come back into; the sweep's counter then heads a block of sweep_control_words(elements of one sweep) words.
+struct SweepCompaction {
+    unsigned long long* h_done = nullptr;
+};
 // occurrences one sweep can cover: slots share a 64-bit word with the SA index (32 + 32 bits, or 31 + 33 when SA indices are wide)
 template <bool kWide> constexpr uint64_t sweep_batch_max() { return kWide ? (1ull << 31) : 0xFFFFFF00ull; }
 // kWide: the index keeps 64-bit samples and SA indices may need 33 bits (n > 2^32, or VLG_FORCE_POS64); pos_t is the width of the
@@ -59,10 +76,10 @@ vlg_status launch_locate_sweep(const IndexView& iv, const uint64_t* d_l, const u
                                size_t temp_bytes, unsigned long long* d_counter, unsigned long long* d_stats, uint64_t tail_threshold,
                                hipStream_t stream, LaunchTimer* timer, Block* member, uint32_t n_member_lists, uint64_t* rec,
                                const std::function<vlg_status()>* while_first_step = nullptr,
-                               uint8_t* front = nullptr /* with rec: one byte per element, the symbol in front of it (see SweepKernels) */);
+                               uint8_t* front = nullptr /* with rec: one byte per element, the symbol in front of it (see SweepKernels) */,
+                               SweepCompaction compaction = SweepCompaction());
 // The three launches of a sorted sweep over some index (filled by bind_sweep, sweep_kernels.hpp; each returns the launch's status);
 // run_locate_sweep owns the rounds, the partitions, the member bit-vector, the records and their resolution.  `out` is the sweep's slice of the position array (pos_t*), `rec` null when no LF step is shared.
-constexpr uint32_t kSweepChunk = 2048;          // elements a workgroup of the first round takes per turn
 // the list that holds the first element of every chunk of a sweep [t0, t1): looked up for all chunks at once, in parallel, instead of by
 // one lane of every workgroup in front of its work (a binary search is seventeen dependent loads)
 void launch_sweep_chunk_lists(const uint64_t* d_out_off, uint64_t n_pat, uint64_t t0, uint64_t t1, uint32_t* chunk_list, hipStream_t stream);
@@ -73,8 +90,11 @@ struct SweepKernels {
     uint64_t n = 0;
     uint32_t sigma = 0;                  // partition keys are the symbols 0 .. sigma - 1 (16 bits at most); sigma = finished
     // round 0 of the elements [t0, t1): their words follow from their places (lists l / out_off are the launcher's business)
+    // compact: the survivors are written densely, in order, to the front of val / key and nothing else is (n_done then heads a
+    // cleared block of sweep_control_words); otherwise, and in every later round, an element keeps its place and a finished one gets
+    // key = sigma
     std::function<vlg_status(uint64_t t0, uint64_t t1, uint64_t* val, uint16_t* key, void* out, unsigned long long* n_done, const Block* member, uint64_t* rec, bool ahead,
-                       uint32_t* chunk_list /* scratch, one word per kSweepChunk elements: sweep_chunk_lists_kernel */)> first;
+                       uint32_t* chunk_list /* scratch, one word per kSweepChunk elements: sweep_chunk_lists_kernel */, bool compact)> first;
     // one round of the elements val / key [0, alive)
     std::function<vlg_status(uint64_t* val, uint16_t* key, uint64_t alive, uint32_t step, void* out, unsigned long long* n_done, const Block* member, uint64_t* rec, uint64_t t0,
                        bool probed)> step;
@@ -86,7 +106,8 @@ template <typename pos_t, bool kWide>
 vlg_status run_locate_sweep(const SweepKernels& K, const uint64_t* d_l, const uint64_t* d_out_off, uint64_t n_pat, uint64_t total,
                             pos_t* d_out, uint64_t* val_a, uint64_t* val_b, uint16_t* key_a, uint16_t* key_b, void* temp,
                             size_t temp_bytes, unsigned long long* d_counter, uint64_t tail_threshold, hipStream_t stream, LaunchTimer* timer,
-                            Block* member, uint32_t n_member_lists, uint64_t* rec, const std::function<vlg_status()>* while_first_step = nullptr);
+                            Block* member, uint32_t n_member_lists, uint64_t* rec, const std::function<vlg_status()>* while_first_step = nullptr,
+                            SweepCompaction compaction = SweepCompaction());
 // super-blocks of the member bit-vector over the SA indices of a text of n - 1 characters (kernels.hip: sweep_element)
 inline uint64_t member_blocks(uint64_t n) { return n / kBlockBits + 1; }
 // K3u: the whole suffix array reconstructed from the samples (one LF walker per sample, n LF steps in all) into sa_full (n x 4 B),
@@ -107,7 +128,8 @@ vlg_status launch_int_locate(const IntView& v, uint32_t* d_io, uint64_t total, u
 vlg_status launch_int_locate_sweep(const IntView& v, const uint64_t* d_l, const uint64_t* d_out_off, uint64_t n_pat, uint64_t total, uint32_t* d_out,
                                    uint64_t* val_a, uint64_t* val_b, uint16_t* key_a, uint16_t* key_b, void* temp, size_t temp_bytes, unsigned long long* d_counter,
                                    unsigned long long* d_stats, uint64_t tail_threshold, hipStream_t stream, LaunchTimer* timer, Block* member,
-                                   uint32_t n_member_lists, uint64_t* rec, const std::function<vlg_status()>* while_first_step = nullptr);
+                                   uint32_t n_member_lists, uint64_t* rec, const std::function<vlg_status()>* while_first_step = nullptr,
+                                   SweepCompaction compaction = SweepCompaction());
 // SA-order density 1 (vlg_index_resample): locate copies SA intervals of the samples, which are the suffix array (sa_dense_copy_kernel)
 vlg_status launch_sa_dense_copy(const uint32_t* sa, const uint64_t* d_l, const uint64_t* d_out_off, uint64_t n_pat, uint64_t total, uint32_t* d_out,
                                 hipStream_t stream);

@@ -83,6 +83,8 @@ struct vlg_workspace {
                                 // in the binary pairs of sweep_first_pair, and still wins (C4, ms per batch: locate 95.4 -> 85.9, batch 353.5 -> 342.6)
     bool fuse_jump = true;      // the link pass of a class finds the jumps of its level-0 slots itself (join_device.hpp: join_link_kernel<.., kJump>);
                                 // 0 = the separate jump pass over all level-0 slots, for an A/B inside one library (also VLG_FUSE_JUMP=0)
+    bool sweep_compact = true;  // round 0 of the sorted sweep writes its survivors densely and its partition sorts only them (sweep_kernels.hpp:
+                                // commit_turn); 0 = finished elements are carried through the partition with key = sigma, for an A/B inside one library
     uint64_t sweep_min = 1ull << 22;    // below this many occurrences the persistent random-access kernel is used
     uint64_t sweep_tail = 1ull << 22;   // stragglers of a sweep are finished one lane each (C3, ms per batch: 2^20 214.0, 2^22 213.4, 2^24 213.7, 2^26 213.8)
     // K3u (kernels.hip): a batch that locates at least unsample_pct per cent of all text positions rebuilds the whole suffix array from
@@ -272,6 +274,7 @@ extern "C" vlg_status vlg_workspace_set_option(vlg_workspace* ws, const char* na
     if (!strcmp(name, "quad_walk")) { ws->quad_walk = value != 0; return VLG_OK; }
     if (!strcmp(name, "tuples")) { ws->tuples = value != 0; return VLG_OK; }
     if (!strcmp(name, "fuse_jump")) { ws->fuse_jump = value != 0; return VLG_OK; }
+    if (!strcmp(name, "sweep_compact")) { ws->sweep_compact = value != 0; return VLG_OK; }
     if (!strcmp(name, "filter")) { ws->filter = value != 0; return VLG_OK; }
     if (!strcmp(name, "filter_min")) { ws->filter_min = (uint64_t)value; return VLG_OK; }
     if (!strcmp(name, "filter_pivot")) { ws->filter_pivot = value != 0; return VLG_OK; }
@@ -988,6 +991,9 @@ struct PhysicalPass {
         c = choose_physical<pos_t>(idx, ws, acc, nd, wide, acc, gacc, &cp.c);
     }
 
+    // elements of one sweep of this rank's share
+    uint64_t sweep_cap() const { return std::min<uint64_t>(acc, wide ? sweep_batch_max<true>() : sweep_batch_max<false>()); }
+
     vlg_status carve()
     {
         Pg = A.take<pos_t>(gacc);
@@ -997,7 +1003,8 @@ struct PhysicalPass {
         d_off64 = A.take<uint64_t>(nd + 1);
         d_off32 = A.take<uint32_t>(nd + 1);
         d_lh = A.take<uint64_t>(nd);
-        d_counter = A.take<unsigned long long>(4);                        // [0] the sweep's counter, [1..3] diagnostics (VLG_RESOLVE_STATS)
+        // [0] the sweep's counter, [1..3] diagnostics (VLG_RESOLVE_STATS); a compacting sweep's control block starts here too (kernels.hpp)
+        d_counter = A.take<unsigned long long>(std::max<uint64_t>(4, c.sweep && ws->sweep_compact ? sweep_control_words(sweep_cap()) : 0));
         d_tmp = A.take<uint8_t>(cp.sort_tmp + 256);
         if (A.failed) return fail(VLG_E_INTERNAL, "arena carve failed (physical)");
         Pb = reinterpret_cast<pos_t*>(scratch);
@@ -1051,7 +1058,9 @@ struct PhysicalPass {
             }
             if (!s) bt.mark("  physical: unsampling");
         } else if (c.sweep) {
-            const uint64_t cap = std::min<uint64_t>(acc, wide ? sweep_batch_max<true>() : sweep_batch_max<false>());
+            const uint64_t cap = sweep_cap();
+            svec<unsigned long long> h_round(2, 0);                       // the compacting round's `done` and give-up word come back here
+            const SweepCompaction compaction{ws->sweep_compact ? h_round.data() : nullptr};
             uint64_t* val_a = reinterpret_cast<uint64_t*>(scratch);
             uint64_t* val_b = val_a + cap;
             uint16_t* key_a = reinterpret_cast<uint16_t*>(val_b + cap);
@@ -1062,14 +1071,14 @@ struct PhysicalPass {
             if (idx->is_int) {
                 if constexpr (sizeof(pos_t) == 4)
                     s = launch_int_locate_sweep(idx->iview, d_lh, d_off64, nd, acc, Pa, val_a, val_b, key_a, key_b, d_tmp, cp.sort_tmp, d_counter, d_stats, ws->sweep_tail, st,
-                                                &timer, member, n_member_lists, rec, &hook);
+                                                &timer, member, n_member_lists, rec, &hook, compaction);
                 else s = fail(VLG_E_INTERNAL, "integer-alphabet index with 64-bit positions");
             } else if (wide)
                 s = launch_locate_sweep<pos_t, true>(lview, d_lh, d_off64, nd, acc, Pa, val_a, val_b, key_a, key_b, d_tmp, cp.sort_tmp, d_counter, d_stats,
-                                                     ws->sweep_tail, st, &timer, member, n_member_lists, rec, &hook, front);
+                                                     ws->sweep_tail, st, &timer, member, n_member_lists, rec, &hook, front, compaction);
             else if constexpr (sizeof(pos_t) == 4)                      // (a 64-bit position type always comes with wide indices)
                 s = launch_locate_sweep<uint32_t, false>(lview, d_lh, d_off64, nd, acc, Pa, val_a, val_b, key_a, key_b, d_tmp, cp.sort_tmp, d_counter, d_stats,
-                                                         ws->sweep_tail, st, &timer, member, n_member_lists, rec, &hook, front);
+                                                         ws->sweep_tail, st, &timer, member, n_member_lists, rec, &hook, front, compaction);
             else s = fail(VLG_E_INTERNAL, "64-bit positions with 32-bit SA indices");
             if (!s) bt.mark("  physical: sweep");
         } else if (idx->is_int) {
@@ -1932,7 +1941,9 @@ vlg_status plan_super_chunk(const vlg_index* idx, const vlg_queries* q, const Pl
     // one pass over the lists against two descents per pivot element)
     cp.want_rungs = pivot_elems && (ws->pivot_rungs == 2 || (pivot_elems >= phys / 16 && pivot_elems >= 4096));
     const uint64_t rung_bytes = cp.want_rungs ? rung_layout(phys).entries * sizeof(pos_t) + 8192 : 0;
-    const uint64_t phys_plain = phys * (sizeof(pos_t) + kPhysScratchPerElem<pos_t>()) + cp.sort_tmp + (dlist.size() + 2) * 24 + (8ull << 20) + phys + rung_bytes;
+    // (with the sweep's scratch: the control block of its compacting rounds, 8 B per turn -- kernels.hpp: sweep_control_words)
+    const uint64_t sweep_ctl = cp.c.sweep && ws->sweep_compact ? sweep_control_words(phys) * 8 + 256 : 0;
+    const uint64_t phys_plain = phys * (sizeof(pos_t) + kPhysScratchPerElem<pos_t>()) + sweep_ctl + cp.sort_tmp + (dlist.size() + 2) * 24 + (8ull << 20) + phys + rung_bytes;
     if (trail_bytes) {
         const uint64_t left = budget > phys_plain + trail_bytes ? budget - phys_plain - trail_bytes : 0;
         if (left < std::max<uint64_t>(2 * logical_max_query, budget / 8)) trail_bytes = 0;
@@ -2713,7 +2724,7 @@ extern "C" vlg_status vlg_build_constants(vlg_build_constant* out, uint32_t cap,
     const vlg::KernelConstants kc = vlg::kernel_constants();
     const struct { const char* name; int64_t value; } all[] = {
         {"VLG_LINK_RUN", VLG_LINK_RUN}, {"VLG_COOP_WINDOWS2", VLG_COOP_WINDOWS2}, {"VLG_RUNG_SHIFT", VLG_RUNG_SHIFT},
-        {"VLG_RESOLVE_HOPS", kc.resolve_hops}, {"VLG_RESOLVE_CHUNK", kc.resolve_chunk}, {"VLG_GROUP_CHUNK", kc.group_chunk},
+        {"VLG_RESOLVE_HOPS", kc.resolve_hops}, {"VLG_RESOLVE_CHUNK", kc.resolve_chunk}, {"VLG_GROUP_CHUNK", kc.group_chunk}, {"VLG_SWEEP_CHUNK", kc.sweep_chunk},
         {"VLG_STAGE_LISTS", kc.stage_lists}, {"VLG_SWEEP_PAIRS", kc.sweep_pairs},
         {"VLG_PIVOT_GROUPS", VLG_PIVOT_GROUPS}, {"VLG_PIVOT_TURNS", VLG_PIVOT_TURNS}, {"VLG_COMPACT_RUNS", VLG_COMPACT_RUNS},
         {"VLG_SPARSE_TURN", VLG_SPARSE_TURN}, {"VLG_SORT_CLASSES", VLG_SORT_CLASSES}, {"VLG_BUCKET_SORT", VLG_BUCKET_SORT},

@@ -185,6 +185,182 @@ __device__ __forceinline__ bool stage_lists(ListStage& ls, const uint64_t* __res
     return ls.off[kListStage] >= end;                      // (the same word in every thread: the branch on it is uniform)
 }
 
+// Where a round's elements go.  ArraySink: every element keeps its place e in val / key, a finished one gets key = sigma and is
+// carried through the round's partition into its last bucket (the workspace option "sweep_compact" = 0).
+struct ArraySink {
+    uint64_t* __restrict__ val;
+    uint16_t* __restrict__ key;
+    uint16_t sigma;
+    __device__ __forceinline__ void emit(uint64_t e, uint64_t word, uint32_t c) const { val[e] = word; key[e] = (uint16_t)c; }
+    __device__ __forceinline__ void finish(uint64_t e) const { key[e] = sigma; }
+};
+
+// ---------------------------------------------------------------------------------------------
+// Compaction (round 0, sweep_first_kernel<.., kCompact>): a finished element never reaches the partition -- six in ten of C3's
+// occurrences end in round 0.  A workgroup takes its elements in TURNS of kSweepChunk consecutive
+// ones, row by row (kSweepRows rows of 256); what goes on to another round stays with the thread that walked it, the word in
+// registers and the key in LDS (TurnRegs: the walks exchange nothing), and when the turn's walks are done its survivors are written to
+//     val / key [survivors of all earlier turns + stable rank inside the turn),
+// in the order of the elements themselves (row, then thread): the survivors stay in ascending SA-index order, the round's outcome
+// does not depend on which workgroup ran which turn, and the partition sorts `alive - done` elements instead of `alive`.
+// The survivors of all earlier turns come from a decoupled look-back over one 64-bit status word per turn, tag << 62 | count:
+// tag 1 = the turn's own survivors (stored when its walks are done), tag 2 = the survivors up to and including it (stored when its
+// look-back ends).  The words are written and read with relaxed agent-scope atomics -- the word is its own flag, nothing else is
+// handed from workgroup to workgroup inside the launch -- and one wave looks back, 64 predecessors per load.
+// Turn numbers are drawn from a counter, not taken from blockIdx: the grid is capped and not fully resident, and a workgroup must
+// never wait for a turn that no running workgroup has drawn.  A workgroup that holds turn k is running, so every turn before k has
+// been drawn by a workgroup that is running or done, and each stores its tag-1 word before it waits for anything: the look-back
+// always ends.  Its spins are bounded all the same (kTurnSpins polls per window of 64 turns, all its waits together): on give-up the workgroup raises the word beside
+// n_done, writes nothing further and returns; the driver reads that word with `done`.
+// In place: round 0 reads no words (an element's word follows from its place), so the survivors go to the front of the arrays that
+// the round would have filled anyway; the chunk_list scratch lies in the other buffer.
+// The control block (driver: cleared before every launch): ctl[kSweepDone] = n_done, [kSweepStalled], [kSweepTicket],
+// [kSweepStatus + turn].
+// Why registers: the kernels live on their waves (round 0 of C3: 45 VGPRs, 14.4 KiB of LDS, eight waves per SIMD).  An LDS stage of the
+// turn (10 B per element, 20.5 KB) left four workgroups per CU where there were eight -- DESIGN.md section 9.
+// ---------------------------------------------------------------------------------------------
+constexpr uint32_t kNoKey = 0xFFFF;                        // (keys are symbols < sigma < 0xFFFF: run_locate_sweep)
+constexpr uint32_t kSweepRows = kSweepChunk / 256;
+constexpr uint32_t kTurnSpins = 1u << 21;
+// A thread's elements of one turn: row r is element r * 256 + threadIdx.x of the turn.  The row index is a loop counter at run time
+// (the walks are not unrolled), so a row is written by selects over all rows: the arrays stay registers.
+// kHigh: the high halves of the words are kept too (33-bit indices); without them the word is slot << 32 | low and the slot follows
+// from the element's place.
+struct TurnShared {
+    uint16_t key[kSweepChunk];                             // the turn's keys, each written and read by its own thread; kNoKey: finished, or behind the end
+    uint32_t cnt[kSweepRows * 4];                          // survivors per (row, wave)
+    uint64_t base;
+    uint32_t turn, stalled;
+};
+template <bool kHigh>
+struct TurnRegs {
+    TurnShared& st;
+    uint32_t low[kSweepRows];
+    uint32_t high[kHigh ? kSweepRows : 1];
+    __device__ __forceinline__ void emit(uint64_t row, uint64_t word, uint32_t c)
+    {
+#pragma unroll
+        for (uint32_t r = 0; r < kSweepRows; ++r) {
+            low[r] = row == r ? (uint32_t)word : low[r];
+            if (kHigh) high[r] = row == r ? (uint32_t)(word >> 32) : high[r];
+        }
+        st.key[row * 256 + threadIdx.x] = (uint16_t)c;
+    }
+    __device__ __forceinline__ void finish(uint64_t row) { st.key[row * 256 + threadIdx.x] = (uint16_t)kNoKey; }
+    __device__ __forceinline__ uint32_t key_of(uint32_t r) const { return st.key[r * 256 + threadIdx.x]; }
+};
+using gu64 = __attribute__((address_space(1))) unsigned long long;
+__device__ __forceinline__ void status_store(unsigned long long* p, unsigned long long x)
+{
+    __hip_atomic_store((gu64*)p, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ unsigned long long status_load(unsigned long long* p)
+{
+    return __hip_atomic_load((gu64*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// the next turn of this workgroup
+__device__ __forceinline__ uint32_t draw_turn(TurnShared& st, unsigned long long* ctl)
+{
+    __syncthreads();                                       // (everyone has read what the last turn left in `st`)
+    if (threadIdx.x == 0) st.turn = (uint32_t)atomicAdd(&ctl[kSweepTicket], 1ull);
+    __syncthreads();
+    return __builtin_amdgcn_readfirstlane(st.turn);       // (one word for all: scalar, like everything the turn derives from it)
+}
+
+// The survivors of `turn` to their places; slot_word: the high half's worth of the word of row r where the registers do not hold it
+// (kHigh = false: slot << 32 of the turn's first element + this thread's).  false: the look-back gave up (nothing was written; the
+// whole workgroup returns).
+template <bool kHigh>
+__device__ __forceinline__ bool commit_turn(const TurnRegs<kHigh>& regs, TurnShared& st, unsigned long long* ctl, uint32_t turn, uint64_t first_slot,
+                                            uint64_t* __restrict__ val, uint16_t* __restrict__ key)
+{
+    constexpr unsigned long long kValue = (1ull << 62) - 1;
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (uint32_t r = 0; r < kSweepRows; ++r) {
+        const unsigned long long m = __ballot(regs.key_of(r) != kNoKey);
+        if (lane == 0) st.cnt[r * 4 + wave] = (uint32_t)__popcll(m);
+    }
+    __syncthreads();
+    // every wave scans the counts for itself: lane (row, wave) ends up with the survivors in front of that row of that wave
+    const uint32_t mine = lane < kSweepRows * 4 ? st.cnt[lane] : 0u;
+    uint32_t incl = mine;
+#pragma unroll
+    for (uint32_t o = 1; o < 64; o <<= 1) {
+        const uint32_t y = __shfl_up(incl, o);
+        if (lane >= o) incl += y;
+    }
+    const uint32_t total = __shfl(incl, 63);
+    const uint32_t excl = incl - mine;
+    if (wave == 0) {
+        unsigned long long* status = ctl + kSweepStatus;
+        if (lane == 0) status_store(&status[turn], ((turn ? 1ull : 2ull) << 62) | total);
+        unsigned long long before = 0;
+        bool stalled = false;
+        if (turn) {
+            long long hi = (long long)turn - 1;                                  // the nearest turn not yet counted
+            uint32_t spins = 0;
+            for (;;) {
+                const long long j = hi - (long long)lane;
+                const unsigned long long w = j >= 0 ? status_load(&status[j]) : (2ull << 62);      // (in front of turn 0: nothing)
+                const uint32_t tag = (uint32_t)(w >> 62);
+                const unsigned long long ready = __ballot(tag != 0), prefixed = __ballot(tag == 2);
+                unsigned long long need = ~0ull;                                 // the turns of this window the sum cannot do without
+                if (prefixed) {                                                  // the nearest turn that knows its prefix ends the look-back,
+                    const uint32_t f = (uint32_t)__ffsll((long long)prefixed) - 1;      // once every turn between it and this one has its count
+                    need = f == 63 ? ~0ull : (1ull << (f + 1)) - 1;
+                    if ((ready & need) == need) {
+                        unsigned long long x = lane <= f ? (w & kValue) : 0ull;
+                        for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
+                        before += x;
+                        break;
+                    }
+                } else if (ready == ~0ull) {                                     // 64 turns with their own counts only: take them, look further back
+                    unsigned long long x = w & kValue;
+                    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
+                    before += x;
+                    hi -= 64;
+                    spins = 0;
+                    continue;
+                }
+                // Some of them are still walking.  Turns end roughly in the order they were drawn in, so the nearest of the missing
+                // ones is the last to come: the wave waits on that one word alone -- one 8-byte request per poll instead of 64 from
+                // each of a thousand waiting workgroups, beside the walks' own loads -- and then reads the window again.
+                const long long late = hi - (long long)((uint32_t)__ffsll((long long)(~ready & need)) - 1);
+                // (`spins` counts on from wait to wait and starts again only when the window moves: kTurnSpins bounds a window's waits together)
+                while ((status_load(&status[late]) >> 62) == 0) {
+                    if (++spins > kTurnSpins) { stalled = true; break; }
+                    __builtin_amdgcn_s_sleep(16);
+                }
+                if (stalled) break;
+            }
+            if (lane == 0) {
+                if (stalled) status_store(&ctl[kSweepStalled], 1ull);
+                else status_store(&status[turn], (2ull << 62) | (before + total));
+            }
+        }
+        if (lane == 0) { st.base = before; st.stalled = stalled ? 1u : 0u; }
+    }
+    __syncthreads();
+    if (__builtin_amdgcn_readfirstlane(st.stalled)) return false;
+    const uint64_t base = ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(st.base >> 32)) << 32) | __builtin_amdgcn_readfirstlane((uint32_t)st.base);
+#pragma unroll
+    for (uint32_t r = 0; r < kSweepRows; ++r) {
+        const uint32_t k = regs.key_of(r);
+        const unsigned long long m = __ballot(k != kNoKey);
+        const uint32_t pre = __shfl(excl, r * 4 + wave);
+        if (k != kNoKey) {
+            const uint64_t to = base + pre + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+            const uint64_t high = kHigh ? (uint64_t)regs.high[kHigh ? r : 0] : first_slot + r * 256 + threadIdx.x;
+            val[to] = (high << 32) | regs.low[r];
+            key[to] = (uint16_t)k;
+        }
+        __builtin_amdgcn_sched_barrier(0);                 // (row by row: the rows' addresses side by side cost the walks their registers)
+    }
+    return true;
+}
+
 // kTrail: LF steps are shared inside the batch.  An LF walk from SA index i visits the indices of the text positions SA[i] - 1,
 // SA[i] - 2, ...; when it stands on an index that is ITSELF an element of the batch (the start of another occurrence's walk: text
 // position SA[i] - k is an occurrence too) the rest of the walk is that element's walk, so it stops there and records
@@ -200,9 +376,9 @@ __device__ __forceinline__ bool stage_lists(ListStage& ls, const uint64_t* __res
 // kAhead (round 0): the index an element steps ONTO is looked up at once -- six in ten elements of a dense batch stand next to
 // another occurrence in the text -- so that they leave the sweep before its largest partition instead of after it; `probed` tells
 // round 1 that its elements have been looked up already.
-template <class Walk, class Sampling, typename pos_t, bool kTrail, bool kWide, bool kFirst = false, bool kAhead = false>
+template <class Walk, class Sampling, typename pos_t, bool kTrail, bool kWide, bool kFirst = false, bool kAhead = false, class Sink = ArraySink>
 __device__ __forceinline__ void sweep_element(const Walk& walk, const Sampling& sampling, uint64_t e, uint64_t v64,
-                                              uint64_t* __restrict__ val, uint16_t* __restrict__ key, uint32_t step, pos_t* __restrict__ out,
+                                              Sink& sink, uint32_t step, pos_t* __restrict__ out,
                                               const Block* __restrict__ member, uint64_t* __restrict__ rec, uint64_t slot0,
                                               uint32_t& n_lv, uint32_t& n_lf, uint32_t& n_fin, bool probed = false, uint8_t* __restrict__ front = nullptr)
 {
@@ -217,13 +393,13 @@ __device__ __forceinline__ void sweep_element(const Walk& walk, const Sampling& 
         if (r >= walk.n()) r -= walk.n();                // csa_wt.hpp:343-347
         if (kTrail) rec[slot0 + (v64 >> kShift)] = r;
         else out[v64 >> kShift] = (pos_t)r;
-        key[e] = (uint16_t)walk.sigma();
+        sink.finish(e);
         ++n_fin;
     } else if (kTrail && !kFirst && !probed && member_probe(member, i, owner)) {
         // (round 0: every element stands on its own index.)  Index i is where element `owner` started: same text trail, `step`
         // positions further left
         rec[slot0 + (v64 >> kShift)] = follow_owner<kShift>(rec, owner, step);
-        key[e] = (uint16_t)walk.sigma();
+        sink.finish(e);
         ++n_fin;
     } else {
         if (kTrail && kFirst) rec[slot0 + (v64 >> kShift)] = ~0ull;               // still walking (no pass clears the records beforehand)
@@ -234,12 +410,11 @@ __device__ __forceinline__ void sweep_element(const Walk& walk, const Sampling& 
             // (the owner is in its own round 0 right now: its record reads "still walking" or is not written yet -- either way this
             // element follows it)
             rec[slot0 + (v64 >> kShift)] = ((uint64_t)(step + 1) << kShift) | owner;
-            key[e] = (uint16_t)walk.sigma();
+            sink.finish(e);
             ++n_fin;
             in_front = (uint8_t)c;
         } else {
-            val[e] = (v64 & ~kPosMask) | j;
-            key[e] = (uint16_t)c;
+            sink.emit(e, (v64 & ~kPosMask) | j, c);
         }
     }
     if (kTrail && kFirst && front) front[slot0 + (v64 >> kShift)] = in_front;
@@ -250,6 +425,8 @@ __device__ __forceinline__ void sweep_element(const Walk& walk, const Sampling& 
 #endif
 constexpr bool kSweepPairs = VLG_SWEEP_PAIRS != 0;
 static_assert(VLG_SWEEP_PAIRS == 0 || VLG_SWEEP_PAIRS == 1, "VLG_SWEEP_PAIRS: 0 or 1");
+// The later rounds do not compact (measured on C3, DESIGN.md section 9: the turns cost these kernels 1.5 ms per batch and saved their
+// partitions 0.85 ms): every element keeps its place, and a finished one is carried through the round's partition.
 template <class Walk, class Sampling, typename pos_t, bool kTrail, bool kWide>
 __global__ void __launch_bounds__(256) sweep_step_kernel(typename Walk::View iv, uint64_t* __restrict__ val, uint16_t* __restrict__ key, uint64_t count,
                                                          uint32_t step, pos_t* __restrict__ out,
@@ -262,9 +439,10 @@ __global__ void __launch_bounds__(256) sweep_step_kernel(typename Walk::View iv,
     const Walk walk{iv, s};
     const Sampling sampling(iv);
     uint32_t n_lv = 0, n_lf = 0, n_fin = 0;
+    ArraySink sink{val, key, (uint16_t)walk.sigma()};
     // (pairs of elements as in round 0 -- sweep_first_pair -- were measured here too, on C4: nothing; the later rounds' elements are sparse)
     for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < count; e += (uint64_t)gridDim.x * blockDim.x)
-        sweep_element<Walk, Sampling, pos_t, kTrail, kWide>(walk, sampling, e, val[e], val, key, step, out, member, rec, slot0, n_lv, n_lf, n_fin, probed);
+        sweep_element<Walk, Sampling, pos_t, kTrail, kWide>(walk, sampling, e, val[e], sink, step, out, member, rec, slot0, n_lv, n_lf, n_fin, probed);
     unsigned long long v[3] = {n_lf, n_lv, n_fin};
     unsigned long long* const dst[3] = {&stats[0], &stats[1], n_done};
     block_add<3>(v, dst);
@@ -273,9 +451,9 @@ __global__ void __launch_bounds__(256) sweep_step_kernel(typename Walk::View iv,
 // Two elements of round 0 side by side (plain bit-vectors): every tree level and the look-ahead probe of both are loaded before either
 // is used, so a lane has two dependent chains in flight instead of one (the kernel runs at full occupancy on 46 registers and waits
 // ~1 us per wave-wide dependent load: more waves cannot come, more loads per wave can).  Same outcome as two sweep_element calls.
-template <typename pos_t, bool kTrail, bool kWide, bool kAhead, class Sampling>
+template <typename pos_t, bool kTrail, bool kWide, bool kAhead, class Sampling, class Sink>
 __device__ __forceinline__ void sweep_first_pair(const IndexView& iv, const WalkLds<PlainBV>& s, const Sampling& sampling, bool onA, uint64_t eA, uint64_t wA,
-                                                 bool onB, uint64_t eB, uint64_t wB, uint64_t* __restrict__ val, uint16_t* __restrict__ key,
+                                                 bool onB, uint64_t eB, uint64_t wB, Sink& sink,
                                                  pos_t* __restrict__ out, const Block* __restrict__ member, uint64_t* __restrict__ rec, uint64_t slot0,
                                                  uint32_t& n_lv, uint32_t& n_lf, uint32_t& n_fin, uint8_t* __restrict__ front)
 {
@@ -287,11 +465,11 @@ __device__ __forceinline__ void sweep_first_pair(const IndexView& iv, const Walk
     uint64_t sv = 0;
     if (onA && sampling.probe(iA, sv)) {                                     // csa_wt.hpp:343-347 (round 0: no steps yet)
         if (kTrail) rec[slot0 + (wA >> kShift)] = sv; else out[wA >> kShift] = (pos_t)sv;
-        key[eA] = (uint16_t)iv.sigma; ++n_fin; onA = false;
+        sink.finish(eA); ++n_fin; onA = false;
     }
     if (onB && sampling.probe(iB, sv)) {
         if (kTrail) rec[slot0 + (wB >> kShift)] = sv; else out[wB >> kShift] = (pos_t)sv;
-        key[eB] = (uint16_t)iv.sigma; ++n_fin; onB = false;
+        sink.finish(eB); ++n_fin; onB = false;
     }
     if (kTrail) {                                                            // still walking (no pass clears the records beforehand)
         if (onA) rec[slot0 + (wA >> kShift)] = ~0ull;
@@ -341,12 +519,12 @@ __device__ __forceinline__ void sweep_first_pair(const IndexView& iv, const Walk
         if (onB) { ownB = block_rank_bit(rB, offB, bit); stopB = bit != 0; }
     }
     if (onA) {
-        if (stopA) { rec[slot0 + (wA >> kShift)] = (1ull << kShift) | ownA; key[eA] = (uint16_t)iv.sigma; ++n_fin; }
-        else { val[eA] = (wA & ~kPosMask) | jA; key[eA] = (uint16_t)cA; }
+        if (stopA) { rec[slot0 + (wA >> kShift)] = (1ull << kShift) | ownA; sink.finish(eA); ++n_fin; }
+        else sink.emit(eA, (wA & ~kPosMask) | jA, cA);
     }
     if (onB) {
-        if (stopB) { rec[slot0 + (wB >> kShift)] = (1ull << kShift) | ownB; key[eB] = (uint16_t)iv.sigma; ++n_fin; }
-        else { val[eB] = (wB & ~kPosMask) | jB; key[eB] = (uint16_t)cB; }
+        if (stopB) { rec[slot0 + (wB >> kShift)] = (1ull << kShift) | ownB; sink.finish(eB); ++n_fin; }
+        else sink.emit(eB, (wB & ~kPosMask) | jB, cB);
     }
     if (kTrail && front) {                                                   // the symbol in front of an element that stopped on its first step
         if (hadA) front[slot0 + (wA >> kShift)] = (onA && stopA) ? (uint8_t)cA : (uint8_t)0xFF;
@@ -358,7 +536,9 @@ __device__ __forceinline__ void sweep_first_pair(const IndexView& iv, const Walk
 // follows from its place -- slot t - t0, SA index l[list] + (t - first slot of the list) -- so a workgroup looks its list up once per
 // 2048 consecutive elements (as sweep_init_kernel does) and walks them at once.
 // The pairs are the byte tree's with plain bit-vectors (Walk::kPlainTree); every other walk takes its elements one by one.
-template <class Walk, class Sampling, typename pos_t, bool kTrail, bool kWide, bool kAhead>
+// kCompact: the turns are drawn from the round's counter and their survivors go to the front of val / key (commit_turn; round 0
+// reads no words, so nothing is overwritten that anyone needs).
+template <class Walk, class Sampling, typename pos_t, bool kTrail, bool kWide, bool kAhead, bool kCompact>
 __global__ void __launch_bounds__(256) sweep_first_kernel(typename Walk::View iv, const uint64_t* __restrict__ l, const uint64_t* __restrict__ out_off, uint64_t n_pat,
                                                           uint64_t t0, uint64_t total, uint64_t* __restrict__ val, uint16_t* __restrict__ key,
                                                           pos_t* __restrict__ out, unsigned long long* __restrict__ stats,
@@ -372,10 +552,10 @@ __global__ void __launch_bounds__(256) sweep_first_kernel(typename Walk::View iv
     const Walk walk{iv, s};
     const Sampling sampling(iv);
     constexpr uint32_t kShift = kWide ? 33 : 32;
-    constexpr uint32_t kPer = kSweepChunk / 256;
+    constexpr uint32_t kPer = kSweepRows;
     uint32_t n_lv = 0, n_lf = 0, n_fin = 0;
-    for (uint64_t base = t0 + (uint64_t)blockIdx.x * kSweepChunk; base < total; base += (uint64_t)gridDim.x * kSweepChunk) {
-        __syncthreads();                                                         // (the lists staged for the previous turn have been read)
+    // one turn: the elements [base, base + kSweepChunk) through `sink`, which knows element t by place(t, its row in the turn)
+    auto take_turn = [&](uint64_t base, auto& sink, auto place) {
         uint64_t p = chunk_list[(base - t0) / kSweepChunk];                      // the list of the chunk's first element (sweep_chunk_lists_kernel)
         const uint64_t end = base + 256 * kPer < total ? base + 256 * kPer : total;
         const bool staged = kStage && stage_lists(s_lists, out_off, l, n_pat, p, end);
@@ -394,21 +574,40 @@ __global__ void __launch_bounds__(256) sweep_first_kernel(typename Walk::View iv
         // (measured, round 4: C4 -- 33-bit indices, a deeper tree -- locate 98 -> 93 ms; C3 16.9 -> 17.4 ms: there the kernel has no issue slots
         //  to spare and loses a wave per SIMD to the registers: pairs for wide indices only)
         if constexpr (Walk::kPlainTree && kSweepPairs && kWide) {
-            static_assert(kPer % 2 == 0, "elements are taken in pairs");
+            static_assert(kPer % 2 == 0, "VLG_SWEEP_CHUNK: elements are taken in pairs of rows");
 #pragma unroll 1
             for (uint32_t i = 0; i < kPer; i += 2) {
                 const uint64_t tA = base + i * 256 + threadIdx.x, tB = tA + 256;
                 const bool onA = tA < total, onB = tB < total;
                 const uint64_t wA = onA ? word_of(tA) : 0, wB = onB ? word_of(tB) : 0;
-                sweep_first_pair<pos_t, kTrail, kWide, kAhead>(iv, s, sampling, onA, tA - t0, wA, onB, tB - t0, wB, val, key, out, member, rec, t0, n_lv, n_lf, n_fin, front);
+                if (kCompact) { if (!onA) sink.finish(place(tA, i)); if (!onB) sink.finish(place(tB, i + 1)); }
+                sweep_first_pair<pos_t, kTrail, kWide, kAhead>(iv, s, sampling, onA, place(tA, i), wA, onB, place(tB, i + 1), wB, sink, out, member, rec, t0, n_lv, n_lf, n_fin, front);
             }
         } else {
 #pragma unroll 1
             for (uint32_t i = 0; i < kPer; ++i) {
                 const uint64_t t = base + i * 256 + threadIdx.x;
                 if (t < total)
-                    sweep_element<Walk, Sampling, pos_t, kTrail, kWide, true, kAhead>(walk, sampling, t - t0, word_of(t), val, key, 0u, out, member, rec, t0, n_lv, n_lf, n_fin, false, front);
+                    sweep_element<Walk, Sampling, pos_t, kTrail, kWide, true, kAhead>(walk, sampling, place(t, i), word_of(t), sink, 0u, out, member, rec, t0, n_lv, n_lf, n_fin, false, front);
+                else if (kCompact) sink.finish(place(t, i));
             }
+        }
+    };
+    if constexpr (kCompact) {
+        __shared__ TurnShared st;
+        TurnRegs<kWide> regs{st, {}, {}};                                                  // (32-bit indices: slot << 32 | index, and the slot is the element's place)
+        const uint64_t turns = (total - t0 + kSweepChunk - 1) / kSweepChunk;
+        for (;;) {
+            const uint32_t turn = draw_turn(st, n_done);                         // (and the lists staged for the previous turn have been read)
+            if (turn >= turns) break;
+            take_turn(t0 + (uint64_t)turn * kSweepChunk, regs, [](uint64_t, uint32_t row) -> uint64_t { return row; });
+            if (!commit_turn(regs, st, n_done, turn, (uint64_t)turn * kSweepChunk, val, key)) return;
+        }
+    } else {
+        ArraySink sink{val, key, (uint16_t)walk.sigma()};
+        for (uint64_t base = t0 + (uint64_t)blockIdx.x * kSweepChunk; base < total; base += (uint64_t)gridDim.x * kSweepChunk) {
+            __syncthreads();                                                     // (the lists staged for the previous turn have been read)
+            take_turn(base, sink, [t0](uint64_t t, uint32_t) -> uint64_t { return t - t0; });
         }
     }
     unsigned long long v[3] = {n_lf, n_lv, n_fin};
@@ -427,12 +626,13 @@ SweepKernels bind_sweep(const typename Walk::View& iv, const uint64_t* d_l, cons
     K.sigma = (uint32_t)iv.sigma;
     K.front = front;
     K.first = [=](uint64_t t0, uint64_t t1, uint64_t* val, uint16_t* key, void* out, unsigned long long* counter, const Block* mem, uint64_t* rc, bool ahead,
-                  uint32_t* chunk_list) {
+                  uint32_t* chunk_list, bool compact) {
         launch_sweep_chunk_lists(d_out_off, n_pat, t0, t1, chunk_list, stream);
-        return on_trails_ahead(mem != nullptr, ahead, [&](auto tr, auto ah) {
-            return launch(sweep_first_kernel<Walk, Sampling, pos_t, decltype(tr)::value, kWide, decltype(ah)::value>, launch_grid((t1 - t0 + 7) / 8, 8192), stream, iv,
+        const dim3 grid((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(sweep_turns(t1 - t0), 8192)));
+        return on_trails_ahead(mem != nullptr, ahead, [&](auto tr, auto ah) { return on_flag(compact, [&](auto cm) {
+            return launch(sweep_first_kernel<Walk, Sampling, pos_t, decltype(tr)::value, kWide, decltype(ah)::value, decltype(cm)::value>, grid, stream, iv,
                           d_l, d_out_off, n_pat, t0, t1, val, key, static_cast<pos_t*>(out), d_stats, counter, mem, rc, chunk_list, front);
-        });
+        }); });
     };
     K.step = [=](uint64_t* val, uint16_t* key, uint64_t alive, uint32_t step, void* out, unsigned long long* counter, const Block* mem, uint64_t* rc, uint64_t t0, bool probed) {
         return on_flag(mem != nullptr, [&](auto tr) {
