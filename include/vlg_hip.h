@@ -974,6 +974,10 @@ vlg_status vlg_workspace_profile(vlg_workspace* ws, int enable);
  * "tuples" (default 1): materialise every sub-pattern position of every match (what sdsl::locate returns); 0 = first
  * positions only, which is all the benchmark's gapped_search_result holds (index_sasearch.hpp:58-118): n_tuple_values
  * is 0 and vlg_result_fetch refuses a tuples buffer.
+ * "emit_direct" (default 1; with "tuples" = 0 only): the pass that lists the matches of every chain tile writes their first
+ * positions into the result itself, once the match counts have come back to the host and the result is allocated, and adds them into
+ * the checksum; 0 = it writes the matches' slots into scratch and a gather pass turns them into positions (an A/B inside one library;
+ * with tuples the gather pass runs either way).  Its time is in the kernel class "join_chain"; "gather" then has no launches.
  * Counts, first positions, tuples and the checksum are identical whatever the other options are. */
 vlg_status vlg_workspace_set_option(vlg_workspace* ws, const char* name, int64_t value);
 vlg_status vlg_workspace_kernel_stats(vlg_workspace* ws, vlg_kernel_stat* out, uint32_t cap, uint32_t* n);

@@ -131,14 +131,26 @@ template <typename pos_t> struct alignas(4 * sizeof(pos_t)) RungQuad { pos_t v[4
 // cross-lane reads and then bisects the one block that holds its answer (6 probes inside 256 bytes).  A galloping search
 // would pay ~2 log2(distance) dependent, scattered round trips instead.
 constexpr uint32_t kFarRounds = 4;
+
+// -DVLG_LINK_STATS: path counters of the pair search (wave_lower_bound2 and its far searches), one atomic per wave and event;
+// search.hip prints and clears them behind every link launch.  A diagnostic build: the atomics cost fifty times what the searches do.
+// (the count is formed by every lane -- it may hold a wave-wide vote -- and added by lane 0)
+#ifdef VLG_LINK_STATS
+enum { LS_PAIRS = 0, LS_WINDOWS, LS_PLACED, LS_FAR0, LS_FAR1, LS_FAR_ROUNDS0, LS_FAR_ROUNDS1, LS_COUNT };
+__device__ unsigned long long g_link_stats[LS_COUNT];
+#define VLG_LINK_STAT(i, n) do { const unsigned long long n_ = (unsigned long long)(n); if ((threadIdx.x & 63) == 0 && n_) atomicAdd(&g_link_stats[i], n_); } while (0)
+#else
+#define VLG_LINK_STAT(i, n) do { } while (0)
+#endif
 template <typename pos_t>
 __device__ __forceinline__ void wave_far_lower_bound(const pos_t* __restrict__ P, const pos_t* __restrict__ F, uint32_t wb, uint32_t b, pos_t key,
-                                                     bool need, uint32_t& j, pos_t& val)
+                                                     bool need, uint32_t& j, pos_t& val, uint32_t stat_reg = 2 /* VLG_LINK_STATS: 0 / 1 = a register of a pair */)
 {
     const uint32_t lane = threadIdx.x & 63;
     constexpr pos_t kInf = (pos_t)~(pos_t)0;
     for (uint32_t round = 0; round < kFarRounds && wb < b; ++round) {
         if (!__any(need)) return;
+        if (stat_reg < 2) VLG_LINK_STAT(LS_FAR_ROUNDS0 + stat_reg, 1);
         // without fences the blocks start at wb; with them they are the aligned blocks of the array, the first one cut at wb
         const uint32_t g0 = F ? wb >> 6 : 0;
         pos_t f;
@@ -218,19 +230,38 @@ __device__ __forceinline__ uint32_t wave_lower_bound(const pos_t* __restrict__ P
 static_assert(VLG_COOP_WINDOWS2 >= 1, "VLG_COOP_WINDOWS2: at least one window before the far search");
 constexpr uint32_t kCoopWindows2 = VLG_COOP_WINDOWS2;      // round 3, link class on C3: 3 -> 22.2, 4 -> 21.9, 6 -> 22.5, 9 -> 22.8 ms (flat: the
                                                              // far search is about as cheap per key as a window); round 2:            // measured on C3: 2 -> 35.2, 3 -> 33.8, 4 -> 33.2, 6 -> 31.9, 8..16 -> 33..34 ms
-template <typename pos_t>
+// kEarly: the next window's address is wb + 64 whatever the ranking of this one finds, so its load is issued before the ranking -- six
+// dependent cross-lane reads -- and has come when the loop wants it; a pair that ends in this window has loaded one window for
+// nothing (one coalesced load).  The addresses are those the loop loaded before, each one iteration earlier.  Measured in DESIGN 9
+// (profiles/link_skip.jsonl).  VLG_LINK_EARLY = 0 compiles the loop that loads a window when it turns to it, for an A/B between two builds.
+#ifndef VLG_LINK_EARLY
+#define VLG_LINK_EARLY 1
+#endif
+static_assert(VLG_LINK_EARLY == 0 || VLG_LINK_EARLY == 1, "VLG_LINK_EARLY: 0 or 1");
+template <typename pos_t, bool kEarly>
 __device__ __forceinline__ void wave_lower_bound2(const pos_t* __restrict__ P, const pos_t* __restrict__ F, uint32_t wb, uint32_t b, pos_t key0, bool need0, pos_t key1,
                                                   bool need1, uint32_t& j0, pos_t& v0, uint32_t& j1, pos_t& v1)
 {
     const uint32_t lane = threadIdx.x & 63;
     constexpr pos_t kInf = (pos_t)~(pos_t)0;
     j0 = b; j1 = b;
+    VLG_LINK_STAT(LS_PAIRS, 1);
+    pos_t w_next = kInf;
+    if (kEarly) w_next = wb + lane < b ? P[wb + lane] : kInf;
     for (uint32_t it = 0; it < kCoopWindows2; ++it) {
         if (!__any(need0 || need1)) break;
-        const uint32_t idx = wb + lane;
-        const pos_t w = idx < b ? P[idx] : kInf;
+        pos_t w;
+        if (kEarly) {
+            w = w_next;
+            if (it + 1 < kCoopWindows2) w_next = wb + 64 + lane < b ? P[wb + 64 + lane] : kInf;
+        } else {
+            const uint32_t idx = wb + lane;
+            w = idx < b ? P[idx] : kInf;
+        }
         const pos_t wlast = __shfl(w, 63);
         const bool can0 = need0 && key0 <= wlast, can1 = need1 && key1 <= wlast;
+        VLG_LINK_STAT(LS_WINDOWS, 1);
+        VLG_LINK_STAT(LS_PLACED, (__any(can0) ? 1 : 0) + (__any(can1) ? 1 : 0));
         uint32_t lo0 = 0, lo1 = 0;
 #pragma unroll
         for (uint32_t step = 32; step; step >>= 1) {                 // lo = elements of w[0,63) below the key (w[63] >= key for `can` lanes)
@@ -245,8 +276,10 @@ __device__ __forceinline__ void wave_lower_bound2(const pos_t* __restrict__ P, c
     }
     if (__any(need0 || need1)) {
         wb = wb < b ? wb : b;
-        wave_far_lower_bound(P, F, wb, b, key0, need0, j0, v0);
-        wave_far_lower_bound(P, F, wb, b, key1, need1, j1, v1);
+        VLG_LINK_STAT(LS_FAR0, __any(need0) ? 1 : 0);
+        VLG_LINK_STAT(LS_FAR1, __any(need1) ? 1 : 0);
+        wave_far_lower_bound(P, F, wb, b, key0, need0, j0, v0, 0);
+        wave_far_lower_bound(P, F, wb, b, key1, need1, j1, v1, 1);
     }
 }
 
@@ -765,7 +798,9 @@ __device__ __forceinline__ void join_link_body(const pos_t* __restrict__ P, cons
             uint32_t j0 = nx.pend, j1 = nx.pend;
             if (hint_seg != s_w)                                   // first step of the run in this segment: the smallest key's bound is the fence
                 hint = wave_kary_lower_bound(P, F, nx.pbegin, nx.pend, (uint64_t)__shfl(tlo0, 0));
-            wave_lower_bound2(P, F, hint, nx.pend, tlo0, want0, tlo1, want1, j0, v0, j1, v1);
+            // (the early window load: not with documents and 64-bit positions, where its register costs the kLast pass a wave per SIMD
+            // -- 74 VGPRs against 72, six waves against seven: the resource table of DESIGN 9)
+            wave_lower_bound2<pos_t, VLG_LINK_EARLY != 0 && !(kDocs && sizeof(pos_t) == 8)>(P, F, hint, nx.pend, tlo0, want0, tlo1, want1, j0, v0, j1, v1);
             if (!want0) j0 = nx.pend;
             if (!want1) j1 = nx.pend;
             bool in0 = want0, in1 = want1;                         // (the searches above ran for every element: j1 is the next step's fence)
@@ -1191,57 +1226,96 @@ __global__ void chain_walk_kernel(const SegMeta* __restrict__ sm, const QueryMet
 // left in xh).  The tile's jump targets are staged in LDS as tile-relative 16-bit offsets and the wave builds jump^(2^k) by doubling
 // there; lane r composes the tables selected by the bits of its rank r, so every match is found by <= 10 independent LDS lookups
 // instead of one lane hopping through the whole chain (380 dependent hops per tile on BASELINE config 3).
+// kDirect (first positions only: workspace options "tuples" = 0, "emit_direct" = 1): the wave knows its record's query, the number of that
+// query's first match inside the tile (rc.y - m.begin) and every slot, so it writes the first positions themselves,
+// out_first[Q.out_first + match number] = P[phys_of(m, slot)], and adds them into the checksum as the gather pass does -- no mlist[] and
+// no gather pass behind it.  It then runs after the counts went to the host and qm[].out_first came back.
+template <typename pos_t, bool kDirect>
 __global__ void __launch_bounds__(256) chain_emit_kernel(const uint32_t* __restrict__ rec_begin, const uint32_t* __restrict__ rec_count,
                                                          const uint2* __restrict__ records, uint32_t total_rec_slots,
                                                          const uint32_t* __restrict__ rec_query, const uint32_t* __restrict__ jump,
                                                          const uint2* __restrict__ xh, uint64_t r1 /* end of the slots that have a jump */,
-                                                         uint32_t* __restrict__ mlist)
+                                                         uint32_t* __restrict__ mlist, const pos_t* __restrict__ P, const SegMeta* __restrict__ sm,
+                                                         const QueryMeta* __restrict__ qm, pos_t* __restrict__ out_first,
+                                                         unsigned long long* __restrict__ checksum)
 {
     constexpr uint16_t kOut = 0xFFFFu;                               // the chain leaves the tile
     constexpr uint32_t kPer = kTile / 64;                            // slots (and ranks) per lane
     __shared__ uint16_t s_t[4][2][kTile];
     const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const uint32_t r = uniform((uint32_t)(((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6));
-    if (r >= total_rec_slots) return;
-    const uint32_t q = rec_query[r];                         // slot r belongs to query q; used only if r - rec_begin[q] < rec_count[q]
-    if (r - rec_begin[q] >= rec_count[q]) return;
-    const uint2 rc = records[r];
-    const uint64_t tile_base = (uint64_t)(rc.x / kTile) * kTile;
-    const uint32_t cnt = uniform(xh[rc.x].y);                        // chain elements inside the tile, entry included (1 .. kTile)
-#pragma unroll
-    for (uint32_t i = 0; i < kPer; ++i) {
-        const uint64_t e = tile_base + lane + 64 * i;
-        const uint32_t j = e < r1 ? jump[e] : kNone;
-        s_t[wv][0][lane + 64 * i] = (j != kNone && (uint64_t)j < tile_base + kTile) ? (uint16_t)(j - (uint32_t)tile_base) : kOut;
+    // (wave-uniform; no early return: with kDirect every wave of the workgroup reaches the barriers of the checksum)
+    bool live = r < total_rec_slots;
+    uint32_t q = 0;
+    if (live) {
+        q = rec_query[r];                                    // slot r belongs to query q; used only if r - rec_begin[q] < rec_count[q]
+        live = r - rec_begin[q] < rec_count[q];
     }
-    wave_sync();
-    uint32_t cur[kPer];
-#pragma unroll
-    for (uint32_t i = 0; i < kPer; ++i) cur[i] = rc.x - (uint32_t)tile_base;
-    uint32_t buf = 0;
-    for (uint32_t k = 0; (1u << k) < cnt; ++k) {
-        const uint16_t* __restrict__ T = s_t[wv][buf];
+    unsigned long long local = 0;
+    if (live) {
+        const uint2 rc = records[r];
+        const uint64_t tile_base = (uint64_t)(rc.x / kTile) * kTile;
+        const uint32_t cnt = uniform(xh[rc.x].y);                    // chain elements inside the tile, entry included (1 .. kTile)
 #pragma unroll
         for (uint32_t i = 0; i < kPer; ++i) {
-            const uint32_t rank = lane + 64 * i;
-            if (rank < cnt && ((rank >> k) & 1)) cur[i] = T[cur[i]];         // (rank < cnt: the walk stays inside the tile)
+            const uint64_t e = tile_base + lane + 64 * i;
+            const uint32_t j = e < r1 ? jump[e] : kNone;
+            s_t[wv][0][lane + 64 * i] = (j != kNone && (uint64_t)j < tile_base + kTile) ? (uint16_t)(j - (uint32_t)tile_base) : kOut;
         }
-        if ((2u << k) < cnt) {                                               // jump^(2^(k+1)) for the next round
-            uint16_t* __restrict__ N = s_t[wv][buf ^ 1];
+        wave_sync();
+        uint32_t cur[kPer];
+#pragma unroll
+        for (uint32_t i = 0; i < kPer; ++i) cur[i] = rc.x - (uint32_t)tile_base;
+        uint32_t buf = 0;
+        for (uint32_t k = 0; (1u << k) < cnt; ++k) {
+            const uint16_t* __restrict__ T = s_t[wv][buf];
 #pragma unroll
             for (uint32_t i = 0; i < kPer; ++i) {
-                const uint32_t sl = lane + 64 * i;
-                const uint16_t a = T[sl];
-                N[sl] = a == kOut ? kOut : T[a];
+                const uint32_t rank = lane + 64 * i;
+                if (rank < cnt && ((rank >> k) & 1)) cur[i] = T[cur[i]];     // (rank < cnt: the walk stays inside the tile)
             }
-            wave_sync();
-            buf ^= 1;
+            if ((2u << k) < cnt) {                                           // jump^(2^(k+1)) for the next round
+                uint16_t* __restrict__ N = s_t[wv][buf ^ 1];
+#pragma unroll
+                for (uint32_t i = 0; i < kPer; ++i) {
+                    const uint32_t sl = lane + 64 * i;
+                    const uint16_t a = T[sl];
+                    N[sl] = a == kOut ? kOut : T[a];
+                }
+                wave_sync();
+                buf ^= 1;
+            }
+        }
+        if (kDirect) {
+            const QueryMeta Q = qm[q];
+            const SegMeta m = sm[Q.seg0];
+            pos_t* const out = out_first + Q.out_first + (rc.y - m.begin);   // the record's first match is the query's match rc.y - m.begin
+#pragma unroll
+            for (uint32_t i = 0; i < kPer; ++i) {
+                const uint32_t rank = lane + 64 * i;
+                if (rank < cnt) {
+                    const pos_t first = P[phys_of(m, (uint32_t)tile_base + cur[i])];
+                    out[rank] = first;
+                    local += first;
+                }
+            }
+        } else {
+#pragma unroll
+            for (uint32_t i = 0; i < kPer; ++i) {
+                const uint32_t rank = lane + 64 * i;
+                if (rank < cnt) mlist[rc.y + rank] = (uint32_t)tile_base + cur[i];
+            }
         }
     }
-#pragma unroll
-    for (uint32_t i = 0; i < kPer; ++i) {
-        const uint32_t rank = lane + 64 * i;
-        if (rank < cnt) mlist[rc.y + rank] = (uint32_t)tile_base + cur[i];
+    if (kDirect) {
+        // one atomic per workgroup, spread over kChecksumSlots words, as in join_gather_kernel
+        __shared__ unsigned long long s_sum;
+        if (threadIdx.x == 0) s_sum = 0;
+        __syncthreads();
+        for (int o = 32; o > 0; o >>= 1) local += __shfl_down(local, o);
+        if (lane == 0 && local) atomicAdd(&s_sum, local);
+        __syncthreads();
+        if (threadIdx.x == 0 && s_sum) atomicAdd(checksum + (blockIdx.x % kChecksumSlots), s_sum);
     }
 }
 

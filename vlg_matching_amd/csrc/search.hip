@@ -83,6 +83,9 @@ struct vlg_workspace {
                                 // in the binary pairs of sweep_first_pair, and still wins (C4, ms per batch: locate 95.4 -> 85.9, batch 353.5 -> 342.6)
     bool fuse_jump = true;      // the link pass of a class finds the jumps of its level-0 slots itself (join_device.hpp: join_link_kernel<.., kJump>);
                                 // 0 = the separate jump pass over all level-0 slots, for an A/B inside one library (also VLG_FUSE_JUMP=0)
+    bool emit_direct = true;    // first positions only ("tuples" = 0): the emit pass of the chain writes them itself, after the counts came back, and no
+                                // gather pass runs (join_device.hpp: chain_emit_kernel<.., kDirect>); 0 = emit into mlist[] and gather, for an A/B inside
+                                // one library.  With tuples the gather pass runs whatever this says.
     bool sweep_compact = true;  // round 0 of the sorted sweep writes its survivors densely and its partition sorts only them (sweep_kernels.hpp:
                                 // commit_turn); 0 = finished elements are carried through the partition with key = sigma, for an A/B inside one library
     uint64_t sweep_min = 1ull << 22;    // below this many occurrences the persistent random-access kernel is used
@@ -274,6 +277,7 @@ extern "C" vlg_status vlg_workspace_set_option(vlg_workspace* ws, const char* na
     if (!strcmp(name, "quad_walk")) { ws->quad_walk = value != 0; return VLG_OK; }
     if (!strcmp(name, "tuples")) { ws->tuples = value != 0; return VLG_OK; }
     if (!strcmp(name, "fuse_jump")) { ws->fuse_jump = value != 0; return VLG_OK; }
+    if (!strcmp(name, "emit_direct")) { ws->emit_direct = value != 0; return VLG_OK; }
     if (!strcmp(name, "sweep_compact")) { ws->sweep_compact = value != 0; return VLG_OK; }
     if (!strcmp(name, "filter")) { ws->filter = value != 0; return VLG_OK; }
     if (!strcmp(name, "filter_min")) { ws->filter_min = (uint64_t)value; return VLG_OK; }
@@ -1339,6 +1343,7 @@ struct JoinChunk {
     ResultPiece piece{q0, q1};
     bool empty = false;                 // no live query, or no slot of a first list: the chunk has no match and launches no join
     const bool fused = ws->fuse_jump && fuse_jump_env();        // the link passes find the level-0 jumps (link_classes, chain)
+    const bool direct = !ws->tuples && ws->emit_direct;         // the emit pass writes the first positions (gather), not mlist[] (chain)
     // documents of the batch (vlg_queries_set_documents), or null: then nothing below differs from a batch that never had any
     const vlg_documents* docs = q->docs;
     svec<uint64_t> seg_len; uint64_t* d_seglen = nullptr; DocRef dref{};     // symbols of every segment's sub-pattern, beside sm
@@ -1512,7 +1517,7 @@ struct JoinChunk {
         // arrays that exist for the slots of list 0 only (indexed by absolute slot through an offset pointer)
         const uint64_t n0 = lvl0_end - t0;
         uint32_t* jump_a = A.take<uint32_t>(n0);
-        uint32_t* mlist_a = A.take<uint32_t>(n0);
+        uint32_t* mlist_a = direct ? nullptr : A.take<uint32_t>(n0);      // (the cost formulas still charge for it)
         uint2* xh_a = A.take<uint2>(n0);
         jump = jump_a ? jump_a - t0 : nullptr;
         mlist = mlist_a ? mlist_a - t0 : nullptr;
@@ -1592,6 +1597,14 @@ struct JoinChunk {
                     hipLaunchKernelGGL(kernel, dim3(runs_grid(b1 - b0, kLinkRun)), dim3(256), 0, st, P, F, d_segb, nlive, d_sm, (uint32_t)b0, (uint32_t)b1,
                                        fref, lvl_ptr[0], endp, link, d_qm, (uint32_t)lvl0_begin, (uint32_t)lvl0_end, jump);
                 }
+#ifdef VLG_LINK_STATS
+                unsigned long long ls[LS_COUNT] = {0}, zero[LS_COUNT] = {0};       // (a blocking copy: it waits for the launch)
+                VLG_HIP_TRY(hipMemcpyFromSymbol(ls, HIP_SYMBOL(g_link_stats), sizeof ls));
+                VLG_HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_link_stats), zero, sizeof zero));
+                fprintf(stderr, "[vlg link stats] width %d dist %u slots %llu pairs %llu windows %llu placed %llu far0 %llu far1 %llu "
+                                "far_rounds0 %llu far_rounds1 %llu\n", (int)sizeof(pos_t), dist, (unsigned long long)(b1 - b0), ls[LS_PAIRS],
+                        ls[LS_WINDOWS], ls[LS_PLACED], ls[LS_FAR0], ls[LS_FAR1], ls[LS_FAR_ROUNDS0], ls[LS_FAR_ROUNDS1]);
+#endif
             }
             if (vlg_status s = summarize_class(dist)) return s;
         }
@@ -1620,14 +1633,15 @@ struct JoinChunk {
             hipLaunchKernelGGL(chain_tiles_kernel, dim3((uint32_t)((lvl0_end - t0 + kTile - 1) / kTile)), dim3(256), 0, st, jump, t0, lvl0_end, fref, d_segb,
                                nlive, xh);
             hipLaunchKernelGGL(chain_walk_kernel, dim3((nq + 63) / 64), dim3(64), 0, st, d_sm, d_qm, nq, fref, xh, d_recb, d_rec, d_recc, d_counts);
-            if (n_rec)
-                hipLaunchKernelGGL(chain_emit_kernel, dim3((n_rec + 3) / 4), dim3(256), 0, st, d_recb, d_recc, d_rec, n_rec, d_recq, jump, xh, lvl0_end, mlist);
+            if (n_rec && !direct)                                   // (direct: the emit runs when the result arrays exist, gather())
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(chain_emit_kernel<pos_t, false>), dim3((n_rec + 3) / 4), dim3(256), 0, st, d_recb, d_recc, d_rec, n_rec,
+                                   d_recq, jump, xh, lvl0_end, mlist, nullptr, nullptr, nullptr, nullptr, nullptr);
         }
         VLG_HIP_TRY(hipGetLastError());
         return VLG_OK;
     }
 
-    // sizes of the result, then gather
+    // sizes of the result, then gather -- or, for first positions alone, the emit pass that writes them (its time stays in the chain's class)
     vlg_status gather()
     {
         counts.resize(nq);
@@ -1648,12 +1662,18 @@ struct JoinChunk {
             res->pieces.push_back(piece);
             jt.mark("  chunk: result malloc");
             VLG_HIP_TRY(hipMemcpyAsync(d_qm, qm.data(), nq * sizeof(QueryMeta), hipMemcpyHostToDevice, st));
-            first_of.resize(nq);                                        // where every query's matches start, dense (the counts have been read: their place is free)
-            for (uint32_t i = 0; i < nq; ++i) first_of[i] = qm[i].out_first;
-            VLG_HIP_TRY(hipMemcpyAsync(d_counts, first_of.data(), nq * 8, hipMemcpyHostToDevice, st));
-            Timed t(ws, KS_GATHER, sizeof(pos_t) * (M + TV));
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(join_gather_kernel<pos_t>), dim3(runs_grid(M)), dim3(256), 0, st, P, d_sm, d_qm, d_counts, nq, M, link, mlist,
-                               static_cast<pos_t*>(piece.d_first), static_cast<pos_t*>(piece.d_tuples), d_stats + kStatsChecksum);
+            if (direct) {                                               // (M > 0: the walk left records)
+                Timed t(ws, KS_JOIN_CHAIN, sizeof(pos_t) * M);
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(chain_emit_kernel<pos_t, true>), dim3((n_rec + 3) / 4), dim3(256), 0, st, d_recb, d_recc, d_rec, n_rec,
+                                   d_recq, jump, xh, lvl0_end, nullptr, P, d_sm, d_qm, static_cast<pos_t*>(piece.d_first), d_stats + kStatsChecksum);
+            } else {
+                first_of.resize(nq);                                    // where every query's matches start, dense (the counts have been read: their place is free)
+                for (uint32_t i = 0; i < nq; ++i) first_of[i] = qm[i].out_first;
+                VLG_HIP_TRY(hipMemcpyAsync(d_counts, first_of.data(), nq * 8, hipMemcpyHostToDevice, st));
+                Timed t(ws, KS_GATHER, sizeof(pos_t) * (M + TV));
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(join_gather_kernel<pos_t>), dim3(runs_grid(M)), dim3(256), 0, st, P, d_sm, d_qm, d_counts, nq, M, link,
+                                   mlist, static_cast<pos_t*>(piece.d_first), static_cast<pos_t*>(piece.d_tuples), d_stats + kStatsChecksum);
+            }
             VLG_HIP_TRY(hipGetLastError());
         } else {
             res->pieces.push_back(piece);
@@ -2723,7 +2743,7 @@ extern "C" vlg_status vlg_build_constants(vlg_build_constant* out, uint32_t cap,
     if (!n) return fail(VLG_E_INVALID, "null argument");
     const vlg::KernelConstants kc = vlg::kernel_constants();
     const struct { const char* name; int64_t value; } all[] = {
-        {"VLG_LINK_RUN", VLG_LINK_RUN}, {"VLG_COOP_WINDOWS2", VLG_COOP_WINDOWS2}, {"VLG_RUNG_SHIFT", VLG_RUNG_SHIFT},
+        {"VLG_LINK_RUN", VLG_LINK_RUN}, {"VLG_COOP_WINDOWS2", VLG_COOP_WINDOWS2}, {"VLG_LINK_EARLY", VLG_LINK_EARLY}, {"VLG_RUNG_SHIFT", VLG_RUNG_SHIFT},
         {"VLG_RESOLVE_HOPS", kc.resolve_hops}, {"VLG_RESOLVE_CHUNK", kc.resolve_chunk}, {"VLG_GROUP_CHUNK", kc.group_chunk}, {"VLG_SWEEP_CHUNK", kc.sweep_chunk},
         {"VLG_STAGE_LISTS", kc.stage_lists}, {"VLG_SWEEP_PAIRS", kc.sweep_pairs},
         {"VLG_PIVOT_GROUPS", VLG_PIVOT_GROUPS}, {"VLG_PIVOT_TURNS", VLG_PIVOT_TURNS}, {"VLG_COMPACT_RUNS", VLG_COMPACT_RUNS},
