@@ -712,7 +712,7 @@ vlg_status vlg_search_batch(const vlg_index* idx, const vlg_queries* q, vlg_work
 
 /* K4 stand-alone (std::sort of one occurrence list, benchmark/gapped-matching/include/index_sasearch.hpp:80): every list
  * d_pos[h_off[l], h_off[l + 1]) of 32-bit positions < 2^position_bits is sorted ascending in place by the per-list sort of the batch
- * path.  mode 1: as "list_sort" = 1 above, mode 2: as 2.  n_clustered (may be null) receives the number of long lists whose
+ * path.  mode 1: as "list_sort" = 1 above, mode 2: as 2, mode 3: as 1 with "sort_one_pass" = 0.  n_clustered (may be null) receives the number of long lists whose
  * positions were too clustered for the window pass (they took the four full passes).  Synchronises `stream` before it returns. */
 vlg_status vlg_sort_lists_u32(uint32_t* d_pos, const uint64_t* h_off, uint64_t n_lists, uint32_t position_bits, int mode,
                               uint64_t* n_clustered, void* stream);
@@ -953,6 +953,9 @@ vlg_status vlg_workspace_profile(vlg_workspace* ws, int enable);
  * long ones by two LSD radix passes over the top 16 position bits + one LDS pass over windows of whole groups; 2: four LSD passes
  * over all position bits, what lists with clustered positions take anyway); 0, or 64-bit positions: "global_sort_min" (default 2^20): from this many
  * occurrences on all lists are sorted by one radix sort of (list, position) keys instead of one segmented sort.
+ * "sort_one_pass" (default 1; with "list_sort" = 1): a long list of at most VLG_ONE_PASS_MAX keys (131072) takes one radix pass, over
+ * its top 8 position bits, in front of the window pass -- its groups are short enough for the windows as they are; 0 = every long list
+ * takes the two passes (an A/B inside one library).  Results do not depend on it.
  * "filter" (default 1): before the join drop the list elements whose gap windows hold no element of the neighbouring
  * lists (they are in no match); "filter_min" (default 2^12) = join slots below which a query is joined as it is
  * ("filter_stream_min", default 2^16, for the queries filtered by streaming sweeps);

@@ -243,7 +243,7 @@ struct ClassBatch {
             VLG_HIP_TRY(hipMemcpyAsync(d_off64, off64.data(), (nl + 1) * 8, hipMemcpyHostToDevice, b.st));
             VLG_HIP_TRY(hipMemcpyAsync(d_l, l.data(), niv * 8, hipMemcpyHostToDevice, b.st));
             VLG_HIP_TRY(hipMemcpyAsync(d_off, off.data(), (niv + 1) * 8, hipMemcpyHostToDevice, b.st));
-            return list_sort_prepare(off64, (uint32_t)nl, A, b.st, lp);
+            return list_sort_prepare(off64, (uint32_t)nl, A, b.st, lp, b.ws->sort_one_pass);
         }
         vlg_status locate()
         {

@@ -210,10 +210,15 @@ struct SortList { uint64_t begin; uint32_t len, tile0, chunk0, pad; };      // a
 // digit histogram of every tile: hist[tile][256]
 // (flagged_only, here and in the other pass kernels: a pass over the lists whose SortList::pad is set -- launched with a small grid that
 //  strides over the tiles and leaves at once when *any_flagged is zero, which is the common case: no clustered list in the batch)
+// (split, shift_behind, here and in the scatter kernel: the digit of a tile starts at bit `shift` for the tiles in front of tile `split`
+//  and at bit `shift_behind` from there on -- list_sort_prepare numbers the tiles of the two-pass lists in front of those of the
+//  one-pass lists, so a tile's class is a comparison of its block-uniform number and nothing is loaded for it; a pass with one shift
+//  for all its tiles gives both the same value)
 __global__ void __launch_bounds__(256) list_sort_hist_kernel(const uint32_t* __restrict__ in, const SortList* __restrict__ lists,
                                                              const uint32_t* __restrict__ tile_list, uint32_t n_tiles, uint32_t shift,
                                                              uint32_t mask, uint16_t* __restrict__ hist, bool flagged_only, const uint32_t* __restrict__ any_flagged,
-                                                             const uint2* __restrict__ tile_desc /* {first key in the batch's array, keys} */)
+                                                             const uint2* __restrict__ tile_desc /* {first key in the batch's array, keys} */,
+                                                             uint32_t split, uint32_t shift_behind)
 {
     __shared__ uint32_t h[256];
     if (flagged_only && *any_flagged == 0) return;
@@ -221,13 +226,14 @@ __global__ void __launch_bounds__(256) list_sort_hist_kernel(const uint32_t* __r
         if (flagged_only && !lists[tile_list[t]].pad) continue;
         const uint2 d = tile_desc[t];                                 // one load in front of the keys, not tile -> list -> keys
         const uint32_t cnt = d.y;
+        const uint32_t sh = t < split ? shift : shift_behind;
         h[threadIdx.x] = 0;
         __syncthreads();
         const uint32_t* src = in + d.x;
 #pragma unroll
         for (uint32_t i = 0; i < kSortTile / 256; ++i) {
             const uint32_t e = i * 256 + threadIdx.x;
-            if (e < cnt) atomicAdd(&h[(src[e] >> shift) & mask], 1u);
+            if (e < cnt) atomicAdd(&h[(src[e] >> sh) & mask], 1u);
         }
         __syncthreads();
         hist[(uint64_t)t * 256 + threadIdx.x] = (uint16_t)h[threadIdx.x];      // <= kSortTile = 2^12
@@ -311,7 +317,8 @@ __global__ void __launch_bounds__(256) list_sort_scatter_kernel(const uint32_t* 
                                                                 const SortList* __restrict__ lists, const uint32_t* __restrict__ tile_list,
                                                                 uint32_t n_tiles, uint32_t shift, uint32_t dbits,
                                                                 const uint32_t* __restrict__ pref, bool flagged_only, const uint32_t* __restrict__ any_flagged,
-                                                                const uint2* __restrict__ tile_desc, const uint32_t* __restrict__ tile_base /* where the tile's list starts */)
+                                                                const uint2* __restrict__ tile_desc, const uint32_t* __restrict__ tile_base /* where the tile's list starts */,
+                                                                uint32_t split, uint32_t shift_behind)
 {
     constexpr uint32_t kItems = kSortTile / 256;
     using Rank = rocprim::block_radix_rank<256, 8, rocprim::block_radix_rank_algorithm::match>;
@@ -329,6 +336,7 @@ __global__ void __launch_bounds__(256) list_sort_scatter_kernel(const uint32_t* 
         const uint2 d = tile_desc[t];
         const uint32_t cnt = d.y;
         const uint32_t mask = (1u << dbits) - 1u;
+        const uint32_t sh = t < split ? shift : shift_behind;
         const uint32_t* src = in + d.x;
         const uint32_t wbase = (threadIdx.x >> 6) * (64 * kItems) + (threadIdx.x & 63);
         uint32_t keys[kItems];
@@ -339,7 +347,7 @@ __global__ void __launch_bounds__(256) list_sort_scatter_kernel(const uint32_t* 
             keys[i] = e < cnt ? src[e] : 0xFFFFFFFFu;                            // the padding has the largest digit and stands last: it stays last
         }
         unsigned int prefix[1], counts[1];
-        Rank().rank_keys(keys, ranks, s_rank, [shift, mask](const uint32_t& k) { return (k >> shift) & mask; }, prefix, counts);
+        Rank().rank_keys(keys, ranks, s_rank, [sh, mask](const uint32_t& k) { return (k >> sh) & mask; }, prefix, counts);
         first[threadIdx.x] = prefix[0];                                          // where the tile's keys with digit threadIdx.x start
 #pragma unroll
         for (uint32_t i = 0; i < kItems; ++i) s_keys[ranks[i]] = keys[i];
@@ -350,7 +358,7 @@ __global__ void __launch_bounds__(256) list_sort_scatter_kernel(const uint32_t* 
         for (uint32_t i = 0; i < kItems; ++i) {
             const uint32_t p = i * 256 + threadIdx.x;                            // neighbouring lanes write neighbouring keys of a run
             if (p < cnt) {
-                const uint32_t k = s_keys[p], d = (k >> shift) & mask;
+                const uint32_t k = s_keys[p], d = (k >> sh) & mask;
                 dst[pf[d] + (p - first[d])] = k;
             }
         }
@@ -389,10 +397,27 @@ constexpr uint32_t kWinThreads = VLG_WINDOW_THREADS, kWinItems = VLG_WINDOW_ITEM
 static_assert(kWinCap > kWinSpan && kSortTile % kWinPerTile == 0, "a window holds its span and the group it reaches back for");
 constexpr uint32_t kWinMaxLen = 1u << 25;       // longer lists: groups of the top 16 bits would fill a window by themselves
 
+// One-pass lists: a long list of at most kOnePassMax keys takes ONE ranking pass, over its top 8 bits.  Its groups are then len / 256
+// keys of a spread list -- at the default bound half of kWinReach on average -- so its windows are still made of whole groups found
+// within reach, and the pass over bits [bits - 16, bits - 8) is work its result does not need.  The one pass leaves the list in
+// `other`; its windows read it there and write the sorted keys to P.  A one-pass list the plan kernel flags was never written to in
+// P, and the four full passes sort it from there like any flagged list.  list_sort_prepare numbers the lists, tiles, chunks and
+// windows of the two-pass lists in front of those of the one-pass lists: the second pass is the first one's launches with smaller
+// counts, and the class of a tile or window is a comparison of its number (0 compiles the class out; "sort_one_pass" = 0 and
+// vlg_sort_lists_u32 mode 3 turn it off at run time).
+#ifndef VLG_ONE_PASS_MAX
+#define VLG_ONE_PASS_MAX (256 * (kWinReach / 2))
+#endif
+constexpr uint64_t kOnePassMax = VLG_ONE_PASS_MAX;
+static_assert(kOnePassMax == 0 || (kOnePassMax > kSortTile && kOnePassMax <= 256ull * kWinReach),
+              "VLG_ONE_PASS_MAX: 0, or above a tile and at most 256 groups of a window's reach");
+
 // win[u]: where window u of the batch starts inside its list (u = kWinPerTile * tile + j; the list's length for a window behind its end)
+// (the tiles from `split` on belong to one-pass lists: they lie in in_behind, in groups of shift_behind)
 __global__ void __launch_bounds__(256) list_sort_window_plan_kernel(const uint32_t* __restrict__ in, SortList* __restrict__ lists,
                                                                     const uint32_t* __restrict__ tile_list, uint32_t n_tiles, uint32_t shift,
-                                                                    uint32_t* __restrict__ win, uint32_t* __restrict__ any /* [0]: lists flagged */)
+                                                                    uint32_t* __restrict__ win, uint32_t* __restrict__ any /* [0]: lists flagged */,
+                                                                    uint32_t split, const uint32_t* __restrict__ in_behind, uint32_t shift_behind)
 {
     const uint32_t u = blockIdx.x * blockDim.x + threadIdx.x;
     if (u >= n_tiles * kWinPerTile) return;
@@ -401,6 +426,7 @@ __global__ void __launch_bounds__(256) list_sort_window_plan_kernel(const uint32
     const uint32_t x = (u - L.tile0 * kWinPerTile) * kWinSpan;
     if (x == 0) { win[u] = 0; if (L.len > kWinMaxLen) { lists[m].pad = 1; any[0] = 1; } return; }
     if (x >= L.len) { win[u] = L.len; return; }
+    if (u / kWinPerTile >= split) { in = in_behind; shift = shift_behind; }
     const uint32_t* src = in + L.begin;
     const uint32_t h = src[x] >> shift;
     const uint32_t lo = x > kWinReach ? x - kWinReach : 0;
@@ -427,10 +453,15 @@ __global__ void __launch_bounds__(256) list_sort_window_desc_kernel(const SortLi
 // pass does not carry its registers
 // (measured on 2.7e8 keys: 4 workgroups per CU 1.87 ms, 5 -- what the register cap below buys -- 1.62 ms, 512 threads x 6 keys 1.83 ms:
 //  the pass waits on its dependent loads and barriers, not on its instructions)
+// The windows from `split` on (those of the one-pass lists) read in_behind.  The source is picked per window, in one launch: the
+// window's number is block-uniform, so the choice is a scalar select in front of the descriptor's load and costs the kernel no
+// vector register -- its resource usage is what it was, the fifth workgroup per CU included -- where two launches over the two
+// sub-ranges would drain the CUs once more per batch.
 template <bool kRadix>
 __global__ void __launch_bounds__(kWinThreads) __attribute__((amdgpu_waves_per_eu(5, 8))) list_sort_window_kernel(const uint32_t* in, uint32_t* out /* may be the same array */,
                                                                const uint2* __restrict__ desc, uint32_t n_windows, uint32_t bits,
-                                                               uint8_t* __restrict__ win_flag, uint32_t* __restrict__ any /* [1]: windows flagged */)
+                                                               uint8_t* __restrict__ win_flag, uint32_t* __restrict__ any /* [1]: windows flagged */,
+                                                               uint32_t split, const uint32_t* in_behind)
 {
     using BS = BucketSort<kWinThreads, kWinItems, false, VLG_WINDOW_RANK_LOOP != 0>;
     __shared__ typename std::conditional<kRadix, typename BS::Radix, typename BS::Storage>::type s;
@@ -439,10 +470,11 @@ __global__ void __launch_bounds__(kWinThreads) __attribute__((amdgpu_waves_per_e
     for (uint32_t u = blockIdx.x; u < n_windows; u += gridDim.x) {
         if (kRadix && !win_flag[u]) continue;
         const uint2 d = desc[u];
+        const uint32_t* src = u < split ? in : in_behind;
         if constexpr (kRadix) {
-            BS::radix(in + d.x, out + d.x, d.y, bits, s);
+            BS::radix(src + d.x, out + d.x, d.y, bits, s);
         } else {
-            const bool done = BS::run(in + d.x, out + d.x, d.y, bits, s, misc);
+            const bool done = BS::run(src + d.x, out + d.x, d.y, bits, s, misc);
             if (threadIdx.x == 0) { win_flag[u] = done ? 0 : 1; if (!done) any[1] = 1; }
         }
         __syncthreads();
@@ -470,6 +502,8 @@ struct ListSortPlan {
     uint32_t n_small[kSortClasses] = {};
     uint32_t* d_small[kSortClasses] = {};
     uint32_t n_long = 0, n_tiles = 0, n_chunks = 0;
+    uint32_t n_long_two = 0, n_tiles_two = 0, n_chunks_two = 0;      // of these, the two-pass lists: they are numbered first
+    uint64_t keys_long = 0, keys_one_pass = 0;                       // keys of all long lists, and of the one-pass lists among them
     SortList* d_longs = nullptr;
     uint32_t *d_tile_list = nullptr, *d_chunk_list = nullptr, *d_tot = nullptr, *d_pref = nullptr, *d_win = nullptr;
     uint8_t* d_win_flag = nullptr;
@@ -480,12 +514,30 @@ struct ListSortPlan {
     uint16_t* d_hist = nullptr;
 };
 
-inline vlg_status list_sort_prepare(const svec<uint64_t>& off64, uint32_t nd, Arena& A, hipStream_t st, ListSortPlan& lp)
+// (one_pass: the long lists of up to kOnePassMax keys form the one-pass class; off: every long list takes two passes)
+inline vlg_status list_sort_prepare(const svec<uint64_t>& off64, uint32_t nd, Arena& A, hipStream_t st, ListSortPlan& lp, bool one_pass = true)
 {
     svec<uint32_t> small[kSortClasses];                            // <= kSortClassMax[c] elements
     svec<SortList> longs;
-    svec<uint32_t> tile_list, chunk_list, tile_base;
+    svec<uint32_t> tile_list, chunk_list, tile_base, behind;       // behind: the one-pass lists, numbered after all two-pass lists
     svec<uint2> tile_desc;
+    auto add_long = [&](uint32_t l) -> vlg_status {
+        const uint64_t len = off64[l + 1] - off64[l];
+        if (len > 0xFFFFFFFFull) return fail(VLG_E_INTERNAL, "list sort: list too long");
+        const uint32_t tiles = (uint32_t)((len + kSortTile - 1) / kSortTile), chunks = (tiles + kSortChunk - 1) / kSortChunk;
+        const uint32_t m = (uint32_t)longs.size();
+        longs.push_back(SortList{off64[l], (uint32_t)len, (uint32_t)tile_list.size(), (uint32_t)chunk_list.size(), 0});
+        tile_list.insert(tile_list.end(), tiles, m);
+        if (off64[l] + len > 0xFFFFFFFFull) return fail(VLG_E_INTERNAL, "list sort: more than 2^32 keys");
+        for (uint32_t t = 0; t < tiles; ++t) {
+            const uint32_t first = t * kSortTile;
+            tile_desc.push_back(make_uint2((uint32_t)(off64[l] + first), std::min<uint32_t>((uint32_t)len - first, kSortTile)));
+        }
+        tile_base.insert(tile_base.end(), tiles, (uint32_t)off64[l]);
+        chunk_list.insert(chunk_list.end(), chunks, m);
+        lp.keys_long += len;
+        return VLG_OK;
+    };
     for (uint32_t l = 0; l < nd; ++l) {
         const uint64_t len = off64[l + 1] - off64[l];
         if (len <= 1) continue;
@@ -493,21 +545,15 @@ inline vlg_status list_sort_prepare(const svec<uint64_t>& off64, uint32_t nd, Ar
             uint32_t c = 0;
             while (len > kSortClassMax[c]) ++c;
             small[c].push_back(l);
-        } else {
-            if (len > 0xFFFFFFFFull) return fail(VLG_E_INTERNAL, "list sort: list too long");
-            const uint32_t tiles = (uint32_t)((len + kSortTile - 1) / kSortTile), chunks = (tiles + kSortChunk - 1) / kSortChunk;
-            const uint32_t m = (uint32_t)longs.size();
-            longs.push_back(SortList{off64[l], (uint32_t)len, (uint32_t)tile_list.size(), (uint32_t)chunk_list.size(), 0});
-            tile_list.insert(tile_list.end(), tiles, m);
-            if (off64[l] + len > 0xFFFFFFFFull) return fail(VLG_E_INTERNAL, "list sort: more than 2^32 keys");
-            for (uint32_t t = 0; t < tiles; ++t) {
-                const uint32_t first = t * kSortTile;
-                tile_desc.push_back(make_uint2((uint32_t)(off64[l] + first), std::min<uint32_t>((uint32_t)len - first, kSortTile)));
-            }
-            tile_base.insert(tile_base.end(), tiles, (uint32_t)off64[l]);
-            chunk_list.insert(chunk_list.end(), chunks, m);
-        }
+        } else if (one_pass && len <= kOnePassMax) {
+            behind.push_back(l);
+        } else if (vlg_status s = add_long(l)) return s;
     }
+    lp.n_long_two = (uint32_t)longs.size(); lp.n_tiles_two = (uint32_t)tile_list.size(); lp.n_chunks_two = (uint32_t)chunk_list.size();
+    for (const uint32_t l : behind)
+        if (vlg_status s = add_long(l)) return s;
+    lp.keys_one_pass = lp.keys_long;
+    for (uint32_t m = 0; m < lp.n_long_two; ++m) lp.keys_one_pass -= longs[m].len;
     {   // room for everything, or nothing is carved
         uint64_t need = 4096;
         for (uint32_t c = 0; c < kSortClasses; ++c) need += align_up(small[c].size() * 4, 256);
@@ -563,33 +609,46 @@ inline vlg_status list_sort_enqueue(const ListSortPlan& lp, uint32_t* P, uint32_
     uint32_t* src = P;
     uint32_t* dst = other;
     const uint32_t few = 1024;                                   // blocks of a pass that almost always has nothing to do
-    auto pass = [&](uint32_t shift, uint32_t dbits, bool flagged_only) {
+    // one ranking pass from src to dst over the first n_long lists, n_tiles tiles and n_chunks chunks of the plan: digits of dbits bits
+    // from bit `shift` up, and from bit shift_behind up for the tiles from `split` on
+    auto pass_over = [&](uint32_t n_long, uint32_t n_tiles, uint32_t n_chunks, uint32_t shift, uint32_t dbits, bool flagged_only, uint32_t split, uint32_t shift_behind) {
         const uint32_t mask = (1u << dbits) - 1u;
-        const dim3 gt(flagged_only ? std::min(lp.n_tiles, few) : lp.n_tiles), gc(flagged_only ? std::min(lp.n_chunks, few) : lp.n_chunks);
-        hipLaunchKernelGGL(list_sort_hist_kernel, gt, dim3(256), 0, st, src, lp.d_longs, lp.d_tile_list, lp.n_tiles, shift, mask, lp.d_hist, flagged_only, lp.d_any, lp.d_tile_desc);
-        hipLaunchKernelGGL(list_sort_chunk_kernel, gc, dim3(256), 0, st, lp.d_hist, lp.d_longs, lp.d_chunk_list, lp.n_chunks, lp.d_tot, flagged_only, lp.d_any);
-        hipLaunchKernelGGL(list_sort_scan_kernel, dim3(lp.n_long), dim3(256), 0, st, lp.d_longs, lp.n_long, lp.d_tot, flagged_only, lp.d_any);
-        hipLaunchKernelGGL(list_sort_prefix_kernel, gc, dim3(256), 0, st, lp.d_hist, lp.d_longs, lp.d_chunk_list, lp.n_chunks, lp.d_tot, lp.d_pref, flagged_only, lp.d_any);
-        hipLaunchKernelGGL(list_sort_scatter_kernel, gt, dim3(256), 0, st, src, dst, lp.d_longs, lp.d_tile_list, lp.n_tiles, shift, dbits, lp.d_pref, flagged_only, lp.d_any, lp.d_tile_desc, lp.d_tile_base);
+        const dim3 gt(flagged_only ? std::min(n_tiles, few) : n_tiles), gc(flagged_only ? std::min(n_chunks, few) : n_chunks);
+        hipLaunchKernelGGL(list_sort_hist_kernel, gt, dim3(256), 0, st, src, lp.d_longs, lp.d_tile_list, n_tiles, shift, mask, lp.d_hist, flagged_only, lp.d_any, lp.d_tile_desc, split, shift_behind);
+        hipLaunchKernelGGL(list_sort_chunk_kernel, gc, dim3(256), 0, st, lp.d_hist, lp.d_longs, lp.d_chunk_list, n_chunks, lp.d_tot, flagged_only, lp.d_any);
+        hipLaunchKernelGGL(list_sort_scan_kernel, dim3(n_long), dim3(256), 0, st, lp.d_longs, n_long, lp.d_tot, flagged_only, lp.d_any);
+        hipLaunchKernelGGL(list_sort_prefix_kernel, gc, dim3(256), 0, st, lp.d_hist, lp.d_longs, lp.d_chunk_list, n_chunks, lp.d_tot, lp.d_pref, flagged_only, lp.d_any);
+        hipLaunchKernelGGL(list_sort_scatter_kernel, gt, dim3(256), 0, st, src, dst, lp.d_longs, lp.d_tile_list, n_tiles, shift, dbits, lp.d_pref, flagged_only, lp.d_any, lp.d_tile_desc, lp.d_tile_base, split, shift_behind);
+    };
+    auto pass = [&](uint32_t shift, uint32_t dbits, bool flagged_only) {      // all long lists, one shift
+        pass_over(lp.n_long, lp.n_tiles, lp.n_chunks, shift, dbits, flagged_only, lp.n_tiles, shift);
         std::swap(src, dst);
     };
     static const bool windows = [] { const char* e = getenv("VLG_WINDOW_SORT"); return e ? e[0] != '0' : VLG_WINDOW_SORT != 0; }();
     const bool by_windows = windows && allow_windows && bits >= 17;
     VLG_HIP_TRY(hipMemsetAsync(lp.d_any, 0, 8, st));
     if (by_windows) {
-        pass(bits - 16, 8, false);                                   // the top 16 bits, low digit first; the lists are back in P
-        pass(bits - 8, 8, false);
-        hipLaunchKernelGGL(list_sort_window_plan_kernel, dim3((lp.n_tiles * kWinPerTile + 255) / 256), dim3(256), 0, st, P, lp.d_longs, lp.d_tile_list, lp.n_tiles, bits - 16, lp.d_win, lp.d_any);
-        const uint32_t n_windows = lp.n_tiles * kWinPerTile;
+        // first all long lists from P to `other`: the two-pass lists by the low digit of their top 16 bits, the one-pass lists by their
+        // top 8 bits; then the two-pass lists alone back to P by their top 8 bits (without one-pass lists: the two passes of before)
+        const uint32_t split = lp.n_tiles_two;
+        pass_over(lp.n_long, lp.n_tiles, lp.n_chunks, bits - 16, 8, false, split, bits - 8);
+        std::swap(src, dst);
+        if (split) pass_over(lp.n_long_two, lp.n_tiles_two, lp.n_chunks_two, bits - 8, 8, false, split, bits - 8);
+        std::swap(src, dst);                                         // src is P again, where the four full passes below start from
+        const uint32_t n_windows = lp.n_tiles * kWinPerTile, win_split = split * kWinPerTile;
+        hipLaunchKernelGGL(list_sort_window_plan_kernel, dim3((n_windows + 255) / 256), dim3(256), 0, st, P, lp.d_longs, lp.d_tile_list, lp.n_tiles, bits - 16, lp.d_win, lp.d_any,
+                           split, other, bits - 8);
         hipLaunchKernelGGL(list_sort_window_desc_kernel, dim3((n_windows + 255) / 256), dim3(256), 0, st, lp.d_longs, lp.d_tile_list, lp.n_tiles, lp.d_win, lp.d_win_desc);
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(list_sort_window_kernel<false>), dim3(n_windows), dim3(kWinThreads), 0, st, P, P, lp.d_win_desc, n_windows, bits, lp.d_win_flag, lp.d_any);
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(list_sort_window_kernel<true>), dim3(std::min(n_windows, few)), dim3(kWinThreads), 0, st, P, P, lp.d_win_desc, n_windows, bits, lp.d_win_flag, lp.d_any);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(list_sort_window_kernel<false>), dim3(n_windows), dim3(kWinThreads), 0, st, P, P, lp.d_win_desc, n_windows, bits, lp.d_win_flag, lp.d_any,
+                           win_split, other);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(list_sort_window_kernel<true>), dim3(std::min(n_windows, few)), dim3(kWinThreads), 0, st, P, P, lp.d_win_desc, n_windows, bits, lp.d_win_flag, lp.d_any,
+                           win_split, other);
         VLG_HIP_TRY(hipGetLastError());
     }
     const unsigned passes = bits <= 16 ? 2 : 4;                    // even: the lists come back to P
     const unsigned dbits = (bits + passes - 1) / passes;          // <= 8
-    for (unsigned p = 0; p < passes; ++p) {                        // (by windows: only for the lists the plan kernel flagged)
-        pass(p * dbits, dbits, by_windows);
+    for (unsigned p = 0; p < passes; ++p) {                        // (by windows: only for the lists the plan kernel flagged; a flagged
+        pass(p * dbits, dbits, by_windows);                        //  one-pass list lies in P as it came, a two-pass one permuted there)
         VLG_HIP_TRY(hipGetLastError());
     }
     return VLG_OK;

@@ -77,6 +77,8 @@ struct vlg_workspace {
                                              // (C3, ms for the class: 0 18.2, 64 18.3, 256 16.6, 512 16.8, 1024 19.2, always half words 31.5)
     uint32_t pivot_rungs = 1;   // the pivot filter searches through the ladder (join_device.hpp): 0 never (fences + bisection), 1 when it pays, 2 always
     int list_sort = 1;          // 32-bit positions: every list sorted inside itself (list_sort.hpp; 2: without the window passes); 0: the two rocPRIM paths below
+    bool sort_one_pass = true;  // list_sort.hpp: long lists of up to kOnePassMax keys take one ranking pass in front of their windows, not two;
+                                // 0 = every long list takes two, for an A/B inside one library
     uint64_t global_sort_min = 1ull << 20;  // at least this many occurrences: all lists are sorted by one radix sort of (list, position) keys
     bool quad_walk = true;      // locate walks LF on the quad image of an index that has one (lf_walk.hpp: QuadWalk); 0 = the binary walk, for an
                                 // A/B inside one library.  Wide SA indices too: round 0 of their sweep then takes its elements one by one instead of
@@ -273,6 +275,7 @@ extern "C" vlg_status vlg_workspace_set_option(vlg_workspace* ws, const char* na
     if (!strcmp(name, "sweep_min")) { ws->sweep_min = (uint64_t)value; return VLG_OK; }
     if (!strcmp(name, "global_sort_min")) { ws->global_sort_min = (uint64_t)value; return VLG_OK; }
     if (!strcmp(name, "list_sort")) { ws->list_sort = value > 2 ? 1 : (int)value; return VLG_OK; }
+    if (!strcmp(name, "sort_one_pass")) { ws->sort_one_pass = value != 0; return VLG_OK; }
     if (!strcmp(name, "trail")) { ws->trail = value != 0; return VLG_OK; }
     if (!strcmp(name, "quad_walk")) { ws->quad_walk = value != 0; return VLG_OK; }
     if (!strcmp(name, "tuples")) { ws->tuples = value != 0; return VLG_OK; }
@@ -1030,9 +1033,12 @@ struct PhysicalPass {
     vlg_status plan_sort()
     {
         if (!c.list_sort) return VLG_OK;
-        const vlg_status ls = list_sort_prepare(off64, nd, A, st, lsp);
+        const vlg_status ls = list_sort_prepare(off64, nd, A, st, lsp, ws->sort_one_pass);
         if (ls != VLG_OK && ls != VLG_E_WORKSPACE) return ls;      // no room for its tables: the device-wide sort below
         if (ls != VLG_OK) A.used = sort_mark;
+        else if (getenv("VLG_TRACE"))
+            fprintf(stderr, "[vlg trace] sort: %llu keys in %u long lists, %llu of them in %u one-pass lists\n", (unsigned long long)lsp.keys_long, lsp.n_long,
+                    (unsigned long long)lsp.keys_one_pass, lsp.n_long - lsp.n_long_two);
         return VLG_OK;
     }
 
@@ -2578,7 +2584,7 @@ extern "C" vlg_status vlg_sort_lists_u32(uint32_t* d_pos, const uint64_t* h_off,
                                          uint64_t* n_clustered, void* stream)
 {
     if (!h_off || (n_lists && h_off[n_lists] && !d_pos)) return fail(VLG_E_INVALID, "null argument");
-    if (position_bits < 1 || position_bits > 32 || (mode != 1 && mode != 2)) return fail(VLG_E_INVALID, "position_bits in [1,32], mode 1 or 2");
+    if (position_bits < 1 || position_bits > 32 || mode < 1 || mode > 3) return fail(VLG_E_INVALID, "position_bits in [1,32], mode 1, 2 or 3");
     if (n_lists >= 0xFFFFFFF0ull || h_off[0] != 0) return fail(VLG_E_INVALID, "bad list offsets");
     for (uint64_t l = 0; l < n_lists; ++l) if (h_off[l + 1] < h_off[l]) return fail(VLG_E_INVALID, "list offsets must ascend");
     if (n_clustered) *n_clustered = 0;
@@ -2607,8 +2613,8 @@ extern "C" vlg_status vlg_sort_lists_u32(uint32_t* d_pos, const uint64_t* h_off,
         if (A.failed) return fail(VLG_E_INTERNAL, "arena carve failed (vlg_sort_lists_u32)");
         VLG_HIP_TRY(hipMemcpyAsync(d_off, off64.data(), (n_lists + 1) * 8, hipMemcpyHostToDevice, st));
         ListSortPlan lp;
-        if (vlg_status s = list_sort_prepare(off64, (uint32_t)n_lists, A, st, lp)) return s;
-        if (vlg_status s = list_sort_enqueue(lp, d_pos, other, d_off, position_bits, st, mode == 1)) return s;
+        if (vlg_status s = list_sort_prepare(off64, (uint32_t)n_lists, A, st, lp, mode == 1)) return s;
+        if (vlg_status s = list_sort_enqueue(lp, d_pos, other, d_off, position_bits, st, mode != 2)) return s;
         if (n_clustered && lp.n_long) {
             std::vector<SortList> back(lp.n_long);
             VLG_HIP_TRY(hipMemcpyAsync(back.data(), lp.d_longs, lp.n_long * sizeof(SortList), hipMemcpyDeviceToHost, st));
@@ -2750,7 +2756,7 @@ extern "C" vlg_status vlg_build_constants(vlg_build_constant* out, uint32_t cap,
         {"VLG_SPARSE_TURN", VLG_SPARSE_TURN}, {"VLG_SORT_CLASSES", VLG_SORT_CLASSES}, {"VLG_BUCKET_SORT", VLG_BUCKET_SORT},
         {"VLG_WINDOW_SORT", VLG_WINDOW_SORT}, {"VLG_WINDOWS_PER_TILE", VLG_WINDOWS_PER_TILE}, {"VLG_WINDOW_RANK_LOOP", VLG_WINDOW_RANK_LOOP},
         {"VLG_WINDOW_THREADS", VLG_WINDOW_THREADS}, {"VLG_WINDOW_ITEMS", VLG_WINDOW_ITEMS}, {"VLG_FETCH_THREADS", VLG_FETCH_THREADS},
-        {"VLG_DOCLIST_RUN", VLG_DOCLIST_RUN},
+        {"VLG_DOCLIST_RUN", VLG_DOCLIST_RUN}, {"VLG_ONE_PASS_MAX", (int64_t)kOnePassMax},
     };
     const uint32_t count = (uint32_t)(sizeof(all) / sizeof(all[0]));
     *n = count;
