@@ -189,7 +189,7 @@ struct ClassBatch {
         // super-chunks: whole queries while their distinct lists fit the physical budget (next_super_chunk, as the byte path)
         if (ws->cap_bytes <= 2 * kFixed) return fail(VLG_E_WORKSPACE, "workspace cap too small");
         budget = ws->cap_bytes - kFixed;
-        phys_cap = std::min<uint64_t>(budget / 2 / (sizeof(uint32_t) + kPhysScratchPerElem<uint32_t>() + 1), 0xFFFFFF00ull);
+        phys_cap = std::min<uint64_t>(budget / 2 / (sizeof(uint32_t) + kSweepScratchPerElem + 1), 0xFFFFFF00ull);
         stamp.assign(nd, 0xFFFFFFFFu);
         L.doff.assign(nd, 0);
         L.off.assign(nsub, 0);

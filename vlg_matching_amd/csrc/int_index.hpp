@@ -583,19 +583,14 @@ vlg_status launch_int_backward_search(const IntView& v, const uint8_t* d_blob, c
 }
 
 // the integer index in the sorted sweep (sigma <= 65534: the partition key is 16 bits wide)
-vlg_status launch_int_locate_sweep(const IntView& v, const uint64_t* d_l, const uint64_t* d_out_off, uint64_t n_pat, uint64_t total, uint32_t* d_out,
-                                   uint64_t* val_a, uint64_t* val_b, uint16_t* key_a, uint16_t* key_b, void* temp, size_t temp_bytes, unsigned long long* d_counter,
-                                   unsigned long long* d_stats, uint64_t tail_threshold, hipStream_t stream, LaunchTimer* timer, Block* member,
-                                   uint32_t n_member_lists, uint64_t* rec, const std::function<vlg_status()>* while_first_step, SweepCompaction compaction)
+vlg_status launch_int_locate_sweep(const IntView& v, const SweepJob<uint32_t>& job)
 {
     const bool text_order = shape(v).text_order;
-    if (v.dens == 1 && !text_order && total)                          // the resident suffix array
-        return sweep_dense_copy(timer, while_first_step, [&] { return launch_int_dense_copy(v, d_l, d_out_off, n_pat, total, d_out, stream); });
+    if (v.dens == 1 && !text_order && job.total)                      // the resident suffix array
+        return sweep_dense_copy(job, [&] { return launch_int_dense_copy(v, job.d_l, job.d_out_off, job.n_lists, job.total, job.d_out, job.stream); });
     if (!int_sweep_possible(v)) return fail(VLG_E_INTERNAL, "integer index: not for the sorted sweep");
     return on_bv(v.bv_kind, [&](auto bv) { return on_flag(text_order, [&](auto to) {
-        const SweepKernels K = bind_sweep<IntWalk<tag_t<decltype(bv)>>, IntSampling<decltype(to)::value>, uint32_t, false>(v, d_l, d_out_off, n_pat, d_stats, stream, nullptr);
-        return run_locate_sweep<uint32_t, false>(K, d_l, d_out_off, n_pat, total, d_out, val_a, val_b, key_a, key_b, temp, temp_bytes, d_counter, tail_threshold, stream, timer,
-                                                 member, n_member_lists, rec, while_first_step, compaction);
+        return run_locate_sweep<uint32_t, false>(bind_sweep<IntWalk<tag_t<decltype(bv)>>, IntSampling<decltype(to)::value>, uint32_t, false>(v, job, nullptr), job);
     }); });
 }
 

@@ -1099,11 +1099,6 @@ size_t sweep_temp_bytes(uint64_t total, uint32_t sigma, hipStream_t stream)
     return tb;
 }
 
-// d_l / d_out_off: SA interval starts and output offsets of the n_pat lists; d_out receives SA values (unsorted, SA order).
-// Scratch (caller-provided): val_a, val_b (u64 each), key_a, key_b (u16 each) for min(total, sweep_batch_max<pos_t>()) elements,
-// temp (sweep_temp_bytes), counter (8 B, zeroed here).
-// The sweep's driver: rounds, partitions, records and the stragglers' slices for ANY index that can launch the three kernels of
-// SweepKernels (kernels.hpp) -- the byte index below, the integer-alphabet index in int_index.hpp.
 void launch_sweep_chunk_lists(const uint64_t* d_out_off, uint64_t n_pat, uint64_t t0, uint64_t t1, uint32_t* chunk_list, hipStream_t stream)
 {
     const uint64_t chunks = (t1 - t0 + kSweepChunk - 1) / kSweepChunk;
@@ -1111,206 +1106,203 @@ void launch_sweep_chunk_lists(const uint64_t* d_out_off, uint64_t n_pat, uint64_
     hipLaunchKernelGGL(sweep_chunk_lists_kernel, dim3((uint32_t)((chunks + 255) / 256)), dim3(256), 0, stream, d_out_off, n_pat, t0, t1, chunk_list);
 }
 
+struct SweepSwitches { bool grouped_resolve, lookahead, resolve_stats; };      // the runtime switches of a sweep, read once per run
+static bool env_is(const char* name, char c) { const char* e = getenv(name); return e && e[0] == c; }
+
+// What the sweep and K3u share while they run: the val / key pair as it stands, the partition that swaps it, and the host hook.
+struct SweepState {
+    SweepScratch buf;                                   // val[0] / key[0]: the elements as they stand
+    hipStream_t stream; LaunchTimer* timer;
+    const std::function<vlg_status()>* hook;            // null once it has run
+    template <typename pos_t> explicit SweepState(const SweepJob<pos_t>& job) : buf(job.scratch), stream(job.stream), timer(job.timer), hook(job.while_first_step) {}
+    // the stable partition of val[0] / key[0] [0, count) by symbol; the sorted side becomes val[0] / key[0]
+    vlg_status partition(uint64_t count, unsigned key_bits)
+    {
+        size_t tb = buf.temp_bytes;
+        rocprim::double_buffer<uint16_t> dk(buf.key[0], buf.key[1]);
+        rocprim::double_buffer<uint64_t> dv(buf.val[0], buf.val[1]);
+        const auto sort = [&]() -> vlg_status { VLG_HIP_TRY(rocprim::radix_sort_pairs(buf.temp, tb, dk, dv, count, 0, key_bits, stream)); return VLG_OK; };
+        if (vlg_status s = timed(timer, 1, kSweepScratchPerElem * count, sort)) return s;      // key + element read once and written once
+        buf.key[0] = dk.current(); buf.key[1] = dk.alternate();
+        buf.val[0] = dv.current(); buf.val[1] = dv.alternate();
+        return VLG_OK;
+    }
+    // the host work to do while the first step runs: where it is first due, and never again
+    vlg_status hook_once() { const auto* due = hook; hook = nullptr; return due ? (*due)() : VLG_OK; }
+};
+
+// The sweep's driver: rounds, partitions, records and the stragglers' slices for ANY index that can launch the three kernels of
+// SweepKernels (kernels.hpp) -- the byte index below, the integer-alphabet index in int_index.hpp.
 template <typename pos_t, bool kWide>
-vlg_status run_locate_sweep(const SweepKernels& K, const uint64_t* d_l, const uint64_t* d_out_off, uint64_t n_pat, uint64_t total,
-                            pos_t* d_out, uint64_t* val_a, uint64_t* val_b, uint16_t* key_a, uint16_t* key_b, void* temp,
-                            size_t temp_bytes, unsigned long long* d_counter, uint64_t tail_threshold,
-                            hipStream_t stream, LaunchTimer* timer, Block* member /* member_blocks(n) super-blocks, or null: no LF step is shared */,
-                            uint32_t n_member_lists /* the first so many lists are pairwise disjoint and ascend: they make up `member` */,
-                            uint64_t* rec /* total words */,
-                            const std::function<vlg_status()>* while_first_step /* host work to do while the first step runs, or null */,
-                            SweepCompaction compaction)
-{
-    bool hook_due = while_first_step != nullptr;
-    constexpr uint32_t kShift = kWide ? 33 : 32;
-    if (K.n > (1ull << kShift)) return fail(VLG_E_UNSUPPORTED, "sorted sweep: text too long for the packed position");
-    if (sizeof(pos_t) == 4 && K.n > (1ull << 32) + 1) return fail(VLG_E_INTERNAL, "sorted sweep: positions do not fit 32 bits");
-    if (K.sigma >= 0xFFFFu) return fail(VLG_E_INTERNAL, "sorted sweep: alphabet too large for the 16-bit partition key");
-    const unsigned bits = bit_width64(K.sigma);             // keys 0..sigma (sigma = finished, sorts last)
-    const unsigned live_bits = std::max(1u, bit_width64(K.sigma ? K.sigma - 1 : 0));      // ... and 0..sigma - 1 where no finished element is sorted
-    unsigned long long* const h_done = compaction.h_done;
-    const uint64_t batch_max = sweep_batch_max<kWide>();
-    if (member) {
-        if (total > 0xFFFFFF00ull) return fail(VLG_E_INTERNAL, "member bit-vector: slots need 32 bits");
-        if (timer) timer->begin(0);
-        hipLaunchKernelGGL(member_build_kernel, launch_grid(member_blocks(K.n), 16384), dim3(256), 0, stream, d_l, d_out_off, n_member_lists,
-                           member_blocks(K.n), member);
-        if (timer) timer->end(0);
-        VLG_HIP_TRY(hipGetLastError());
+struct SweepRun : SweepState {
+    static constexpr uint32_t kShift = kWide ? 33 : 32;
+    const SweepKernels& K; const SweepJob<pos_t>& job;
+    const SweepSwitches sw{!env_is("VLG_RESOLVE_GROUPED", '0'), !env_is("VLG_SWEEP_LOOKAHEAD", '0'), env_is("VLG_RESOLVE_STATS", '1')};
+    // bits of the keys 0..sigma (sigma = finished, sorts last), and of 0..sigma - 1 where no finished element is sorted
+    const unsigned bits = bit_width64(K.sigma), live_bits = std::max(1u, bit_width64(K.sigma ? K.sigma - 1 : 0));
+    bool front_valid = K.front != nullptr && sw.grouped_resolve;       // front[] holds what the grouped resolve reads
+    // the sweep [t0, t1) under way: `alive` elements still walk, in val[0] / key[0] [0, alive), after `step` rounds
+    uint64_t t0 = 0, t1 = 0, alive = 0; uint32_t step = 0; bool fused_first = false;
+    SweepRun(const SweepKernels& K, const SweepJob<pos_t>& job) : SweepState(job), K(K), job(job) {}
+    pos_t* out() const { return job.d_out + t0; }
+    vlg_status run()
+    {
+        if (vlg_status s = check()) return s;
+        if (vlg_status s = build_member()) return s;
+        for (t0 = 0; t0 < job.total; t0 += sweep_batch_max<kWide>()) {
+            t1 = std::min(job.total, t0 + sweep_batch_max<kWide>());
+            if (vlg_status s = seed()) return s;
+            while (alive > job.tail_threshold && step < 0xFFFFFFu)
+                if (vlg_status s = round(fused_first && step == 0)) return s;
+            if (vlg_status s = stragglers()) return s;
+        }
+        if (vlg_status s = hook_once()) return s;
+        return job.member ? resolve() : VLG_OK;
+    }
+    vlg_status check()
+    {
+        if (K.n > (1ull << kShift)) return fail(VLG_E_UNSUPPORTED, "sorted sweep: text too long for the packed position");
+        if (sizeof(pos_t) == 4 && K.n > (1ull << 32) + 1) return fail(VLG_E_INTERNAL, "sorted sweep: positions do not fit 32 bits");
+        if (K.sigma >= 0xFFFFu) return fail(VLG_E_INTERNAL, "sorted sweep: alphabet too large for the 16-bit partition key");
+        if (job.member && job.total > 0xFFFFFF00ull) return fail(VLG_E_INTERNAL, "member bit-vector: slots need 32 bits");
+        return VLG_OK;
+    }
+    vlg_status build_member()
+    {
+        if (!job.member) return VLG_OK;
+        const auto build = [&] { return launch(member_build_kernel, launch_grid(member_blocks(K.n), 16384), stream, job.d_l, job.d_out_off, job.n_member_lists, member_blocks(K.n), job.member); };
+        if (vlg_status s = timed(timer, 0, 0, build)) return s;
         // more than one sweep: an element may stop at an element of a LATER sweep, whose record must read "still walking" until then
-        if (total > batch_max) VLG_HIP_TRY(hipMemsetAsync(rec, 0xFF, total * 8, stream));
+        if (job.total > sweep_batch_max<kWide>()) VLG_HIP_TRY(hipMemsetAsync(job.rec, 0xFF, job.total * 8, stream));
+        return VLG_OK;
     }
-    bool front_valid = K.front != nullptr && [] { const char* e = getenv("VLG_RESOLVE_GROUPED"); return !(e && e[0] == '0'); }();
-    for (uint64_t t0 = 0; t0 < total; t0 += batch_max) {
-        const uint64_t t1 = std::min(total, t0 + batch_max);
-        // (a sweep too short for a single round hands its elements to the stragglers' kernel, which reads their words)
-        // (rounds always start with the fused first round: the switch VLG_NO_FUSED_FIRST_ROUND that ran them behind sweep_init_kernel
-        // returned wrong positions and was removed -- DESIGN.md section 5)
-        const bool fused_first = t1 - t0 > tail_threshold;
-        if (!fused_first) front_valid = false;                   // (front[] is written by the fused first round only)
-        static const bool ahead = [] { const char* e = getenv("VLG_SWEEP_LOOKAHEAD"); return !(e && e[0] == '0'); }();
-        if (!fused_first) {
-            if (member) VLG_HIP_TRY(hipMemsetAsync(rec + t0, 0xFF, (t1 - t0) * 8, stream));     // "still walking" (the first-round kernel writes it itself)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(sweep_init_kernel<kShift>), launch_grid((t1 - t0 + 7) / 8, 32768), dim3(256), 0, stream, d_l, d_out_off, n_pat,
-                               t0, t1, val_a);
-        }
-        VLG_HIP_TRY(hipGetLastError());
-        uint64_t alive = t1 - t0;
-        uint32_t step = 0;
-        pos_t* out = d_out + t0;
-        while (alive > tail_threshold && step < 0xFFFFFFu) {
-            const bool first = fused_first && step == 0;
-            const bool compact = first && h_done != nullptr;        // round 0 leaves its survivors alone, densely (sweep_kernels.hpp: commit_turn)
-            // (compact: n_done, the give-up word, the ticket counter and one status word per turn of this round -- sweep_kernels.hpp)
-            VLG_HIP_TRY(hipMemsetAsync(d_counter, 0, compact ? sweep_control_words(alive) * 8 : 8, stream));
-            if (timer) timer->begin(0);
-            const vlg_status ks = first ? K.first(t0, t1, val_a, key_a, out, d_counter, member, rec, ahead, reinterpret_cast<uint32_t*>(val_b), compact)      // round 0 makes the elements' words itself
-                                        : K.step(val_a, key_a, alive, step, out, d_counter, member, rec, t0, ahead && fused_first && step == 1);
-            if (timer) timer->end(0);
-            if (ks) return ks;
-            // the stable partition of val_a / key_a [0, count) by symbol; the sorted side becomes val_a / key_a
-            const auto partition = [&](uint64_t count, unsigned key_bits) -> vlg_status {
-                size_t tb = temp_bytes;
-                if (timer) timer->begin(1, 20ull * count);       // key + element read once and written once
-                rocprim::double_buffer<uint16_t> dk(key_a, key_b);
-                rocprim::double_buffer<uint64_t> dv(val_a, val_b);
-                hipError_t se = rocprim::radix_sort_pairs(temp, tb, dk, dv, count, 0, key_bits, stream);
-                if (timer) timer->end(1);
-                VLG_HIP_TRY(se);
-                key_a = dk.current(); key_b = dk.alternate();
-                val_a = dv.current(); val_b = dv.alternate();
-                return VLG_OK;
-            };
-            // not compacting: the partition carries the finished elements (key = sigma) into its last bucket, and runs before `done` is known
-            if (!compact) if (vlg_status ps = partition(alive, bits)) return ps;
-            unsigned long long done_here[2] = {0, 0};
-            unsigned long long* done = compact ? h_done : done_here;
-            VLG_HIP_TRY(hipMemcpyAsync(done, d_counter, compact ? 16 : 8, hipMemcpyDeviceToHost, stream));
-            if (hook_due) { hook_due = false; if (vlg_status hs = (*while_first_step)()) return hs; }
-            VLG_HIP_TRY(hipStreamSynchronize(stream));
-            if (compact && done[kSweepStalled]) return fail(VLG_E_INTERNAL, "sweep compaction stalled");
-            if (done[kSweepDone] > alive) return fail(VLG_E_INTERNAL, "locate sweep: more elements finished than were walking");
-            alive -= done[kSweepDone];
-            // compacting: the round has left its survivors, and nothing else, in val_a / key_a [0, alive); the next round follows the
-            // partition without another round trip (the stragglers' kernel takes its elements in any order: no partition for it)
-            if (compact && alive > tail_threshold) if (vlg_status ps = partition(alive, live_bits)) return ps;
-            ++step;
-            if (step > 1u << 20) return fail(VLG_E_INTERNAL, "locate sweep did not converge");
-        }
-        if (alive) {
-            const LocateSlices sl = locate_slices(alive);
-            if (timer) timer->begin(0);
-            const vlg_status ks = K.tail(out, alive, sl.per_wave, val_a, step, member ? rec : nullptr, t0, member, sl.blocks);
-            if (timer) timer->end(0);
-            if (ks) return ks;
-        }
+    // a sweep too short for a single round hands its words to the stragglers' kernel; rounds start with the fused first round, which makes them itself
+    vlg_status seed()
+    {
+        alive = t1 - t0; step = 0;
+        fused_first = alive > job.tail_threshold;
+        if (fused_first) return VLG_OK;
+        front_valid = false;                   // (front[] is written by the fused first round only)
+        if (job.member) VLG_HIP_TRY(hipMemsetAsync(job.rec + t0, 0xFF, alive * 8, stream));     // "still walking" (the first-round kernel writes it itself)
+        return launch(sweep_init_kernel<kShift>, launch_grid((alive + 7) / 8, 32768), stream, job.d_l, job.d_out_off, job.n_lists, t0, t1, buf.val[0]);
     }
-    if (hook_due) { hook_due = false; if (vlg_status hs = (*while_first_step)()) return hs; }
-    if (member) {
-        // every element has a record now; jump pointers until all of them are positions
-        static const bool diag = [] { const char* e = getenv("VLG_RESOLVE_STATS"); return e && e[0] == '1'; }();
-        for (uint32_t round = 0;; ++round) {
-            VLG_HIP_TRY(hipMemsetAsync(d_counter, 0, diag ? 32 : 8, stream));
-            if (timer) timer->begin(2, round == 0 ? total * (8ull + sizeof(pos_t)) : 0);     // every record read, every position written
-            if (round == 0 && front_valid && !diag)
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(trail_resolve_grouped_kernel<pos_t, kWide>), dim3((uint32_t)std::min<uint64_t>((total + kGroupChunk - 1) / kGroupChunk, 1u << 20)),
-                                   dim3(256), 0, stream, rec, total, d_out, K.front, d_counter);
-            else
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(trail_resolve_kernel<pos_t, kWide>), dim3((uint32_t)std::min<uint64_t>((total + kResolveChunk - 1) / kResolveChunk, 65536)),
-                                   dim3(256), 0, stream, rec, total, d_out, d_counter, round, diag);
-            if (timer) timer->end(2);
-            VLG_HIP_TRY(hipGetLastError());
+    vlg_status round(bool first)
+    {
+        const bool compact = first && job.h_round != nullptr;        // round 0 leaves its survivors alone, densely (sweep_kernels.hpp: commit_turn)
+        VLG_HIP_TRY(hipMemsetAsync(buf.control, 0, sweep_control_bytes(alive, compact), stream));
+        if (vlg_status ks = timed(timer, 0, 0, [&] {
+                return first ? K.first(t0, t1, buf.val[0], buf.key[0], out(), buf.control, job.member, job.rec, sw.lookahead, buf.chunk_list(), compact)      // round 0 makes the elements' words itself
+                             : K.step(buf.val[0], buf.key[0], alive, step, out(), buf.control, job.member, job.rec, t0, sw.lookahead && fused_first && step == 1);
+            })) return ks;
+        // not compacting: the partition carries the finished elements (key = sigma) into its last bucket, and runs before `done` is known
+        if (!compact) if (vlg_status ps = partition(alive, bits)) return ps;
+        unsigned long long done_here[2] = {0, 0};
+        unsigned long long* done = compact ? job.h_round : done_here;
+        VLG_HIP_TRY(hipMemcpyAsync(done, buf.control, compact ? 16 : 8, hipMemcpyDeviceToHost, stream));
+        if (vlg_status hs = hook_once()) return hs;
+        VLG_HIP_TRY(hipStreamSynchronize(stream));
+        if (compact && done[kSweepStalled]) return fail(VLG_E_INTERNAL, "sweep compaction stalled");
+        if (done[kSweepDone] > alive) return fail(VLG_E_INTERNAL, "locate sweep: more elements finished than were walking");
+        alive -= done[kSweepDone];
+        // compacting: the round has left its survivors, and nothing else, in val[0] / key[0] [0, alive); the next round follows the
+        // partition without another round trip (the stragglers' kernel takes its elements in any order: no partition for it)
+        if (compact && alive > job.tail_threshold) if (vlg_status ps = partition(alive, live_bits)) return ps;
+        ++step;
+        if (step > 1u << 20) return fail(VLG_E_INTERNAL, "locate sweep did not converge");
+        return VLG_OK;
+    }
+    vlg_status stragglers()
+    {
+        if (!alive) return VLG_OK;
+        const LocateSlices sl = locate_slices(alive);
+        return timed(timer, 0, 0, [&] { return K.tail(out(), alive, sl.per_wave, buf.val[0], step, job.member ? job.rec : nullptr, t0, job.member, sl.blocks); });
+    }
+    // every element has a record now; jump pointers until all of them are positions
+    vlg_status resolve()
+    {
+        const bool diag = sw.resolve_stats;
+        for (uint32_t pass = 0;; ++pass) {
+            VLG_HIP_TRY(hipMemsetAsync(buf.control, 0, diag ? 32 : 8, stream));
+            if (vlg_status ks = timed(timer, 2, pass == 0 ? job.total * (8ull + sizeof(pos_t)) : 0, [&] {     // every record read, every position written
+                if (pass == 0 && front_valid && !diag)
+                    return launch(trail_resolve_grouped_kernel<pos_t, kWide>, dim3((uint32_t)std::min<uint64_t>((job.total + kGroupChunk - 1) / kGroupChunk, 1u << 20)), stream,
+                                  job.rec, job.total, job.d_out, K.front, buf.control);
+                return launch(trail_resolve_kernel<pos_t, kWide>, dim3((uint32_t)std::min<uint64_t>((job.total + kResolveChunk - 1) / kResolveChunk, 65536)), stream, job.rec,
+                              job.total, job.d_out, buf.control, pass, diag);
+            })) return ks;
             unsigned long long open = 0;
-            VLG_HIP_TRY(hipMemcpyAsync(&open, d_counter, 8, hipMemcpyDeviceToHost, stream));
+            VLG_HIP_TRY(hipMemcpyAsync(&open, buf.control, 8, hipMemcpyDeviceToHost, stream));
             VLG_HIP_TRY(hipStreamSynchronize(stream));
-            if (diag) {
-                unsigned long long c[4] = {0, 0, 0, 0};
-                VLG_HIP_TRY(hipMemcpy(c, d_counter, 32, hipMemcpyDeviceToHost));
-                fprintf(stderr, "[vlg resolve] round %u: %llu records, %llu pointers, %llu hops, %llu distinct lines (per wave-wide hop), %llu still open\n", round,
-                        (unsigned long long)total, c[3], c[1], c[2], c[0]);
-            }
+            if (diag) if (vlg_status s = trace_resolve(pass)) return s;
             if (!open) break;
-            if (round > 64) return fail(VLG_E_INTERNAL, "trail records did not resolve");
+            if (pass > 64) return fail(VLG_E_INTERNAL, "trail records did not resolve");
         }
+        return VLG_OK;
     }
-    return VLG_OK;
-}
-template vlg_status run_locate_sweep<uint32_t, false>(const SweepKernels&, const uint64_t*, const uint64_t*, uint64_t, uint64_t, uint32_t*, uint64_t*, uint64_t*,
-                                                      uint16_t*, uint16_t*, void*, size_t, unsigned long long*, uint64_t, hipStream_t, LaunchTimer*, Block*,
-                                                      uint32_t, uint64_t*, const std::function<vlg_status()>*, SweepCompaction);
+    // VLG_RESOLVE_STATS=1: what the pass's kernel counted behind the counter
+    vlg_status trace_resolve(uint32_t pass)
+    {
+        unsigned long long c[4] = {0, 0, 0, 0};
+        VLG_HIP_TRY(hipMemcpy(c, buf.control, 32, hipMemcpyDeviceToHost));
+        fprintf(stderr, "[vlg resolve] round %u: %llu records, %llu pointers, %llu hops, %llu distinct lines (per wave-wide hop), %llu still open\n", pass,
+                (unsigned long long)job.total, c[3], c[1], c[2], c[0]);
+        return VLG_OK;
+    }
+};
+template <typename pos_t, bool kWide>
+vlg_status run_locate_sweep(const SweepKernels& K, const SweepJob<pos_t>& job) { return SweepRun<pos_t, kWide>(K, job).run(); }
+template vlg_status run_locate_sweep<uint32_t, false>(const SweepKernels&, const SweepJob<uint32_t>&);
 
 // the byte index (IndexView: Huffman-shaped tree, plain or rrr bit-vectors, either sampling) in the sweep
 template <typename pos_t, bool kWide>
-vlg_status launch_locate_sweep(const IndexView& iv, const uint64_t* d_l, const uint64_t* d_out_off, uint64_t n_pat, uint64_t total,
-                               pos_t* d_out, uint64_t* val_a, uint64_t* val_b, uint16_t* key_a, uint16_t* key_b, void* temp,
-                               size_t temp_bytes, unsigned long long* d_counter, unsigned long long* d_stats, uint64_t tail_threshold,
-                               hipStream_t stream, LaunchTimer* timer, Block* member, uint32_t n_member_lists, uint64_t* rec,
-                               const std::function<vlg_status()>* while_first_step, uint8_t* front, SweepCompaction compaction)
+vlg_status launch_locate_sweep(const IndexView& iv, const SweepJob<pos_t>& job)
 {
     if (iv.sample_bytes != (kWide ? 8u : 4u)) return fail(VLG_E_INTERNAL, "sorted sweep: sample width does not match the instantiation");
     const bool text_order = shape(iv).text_order;
-    if (iv.dens == 1 && !text_order && total) {
+    if (iv.dens == 1 && !text_order && job.total) {
         using sample_t = typename std::conditional<kWide, uint64_t, uint32_t>::type;
-        return sweep_dense_copy(timer, while_first_step, [&] {
-            return launch(sa_dense_copy_kernel<pos_t, sample_t>, launch_grid((total + 7) / 8, 32768), stream, reinterpret_cast<const sample_t*>(iv.samples), d_l, d_out_off,
-                          n_pat, total, d_out);
+        return sweep_dense_copy(job, [&] {
+            return launch(sa_dense_copy_kernel<pos_t, sample_t>, launch_grid((job.total + 7) / 8, 32768), job.stream, reinterpret_cast<const sample_t*>(iv.samples), job.d_l,
+                          job.d_out_off, job.n_lists, job.total, job.d_out);
         });
     }
     return on_byte_walk<kWide>(iv, [&](auto walk) { return on_flag(text_order, [&](auto to) {
-        const SweepKernels K = bind_sweep<tag_t<decltype(walk)>, ByteSampling<kWide, decltype(to)::value>, pos_t, kWide>(iv, d_l, d_out_off, n_pat, d_stats, stream,
-                                                                                                                   rec ? front : nullptr);
-        return run_locate_sweep<pos_t, kWide>(K, d_l, d_out_off, n_pat, total, d_out, val_a, val_b, key_a, key_b, temp, temp_bytes, d_counter, tail_threshold, stream, timer,
-                                              member, n_member_lists, rec, while_first_step, compaction);
+        return run_locate_sweep<pos_t, kWide>(bind_sweep<tag_t<decltype(walk)>, ByteSampling<kWide, decltype(to)::value>, pos_t, kWide>(iv, job, job.rec ? job.front : nullptr), job);
     }); });
 }
-// K3u (above): the whole suffix array into sa_full (n words of 32 bits), then the SA intervals of the lists into d_out.
-// val / key buffers for n_samples walkers; temp as for the sweep.  Rounds are enqueued kUnsampleSync at a time: the count of walkers
-// still on their way is read back only then (the kernels skip the ones that have arrived, which the partition keeps at the end).
+// K3u (above): the whole suffix array into sa_full (n words of 32 bits), then the SA intervals of the lists into d_out.  Rounds are enqueued kUnsampleSync
+// at a time: the count of walkers still on their way is read back only then (the kernels skip the ones that have arrived, which the partition keeps at the end).
 constexpr uint32_t kUnsampleSync = 4;
 template <bool kWide>
-vlg_status launch_unsample(const IndexView& iv, const uint64_t* d_l, const uint64_t* d_out_off, uint64_t n_pat, uint64_t total, uint32_t* d_out,
-                           uint32_t* sa_full, uint64_t* val_a, uint64_t* val_b, uint16_t* key_a, uint16_t* key_b, void* temp, size_t temp_bytes,
-                           unsigned long long* d_counter, unsigned long long* h_done /* 8 pinned bytes */, unsigned long long* d_stats, uint64_t tail_threshold,
-                           hipStream_t stream, LaunchTimer* timer, const std::function<vlg_status()>* while_first_step)
+vlg_status launch_unsample(const IndexView& iv, const SweepJob<uint32_t>& job, uint32_t* sa_full, unsigned long long* h_done)
 {
-    bool hook_due = while_first_step != nullptr;
+    SweepState st(job);
+    const hipStream_t stream = job.stream;
     if (iv.sampling != kSamplingSaOrder || iv.dens < 2) return fail(VLG_E_INTERNAL, "unsampling needs SA-order samples of density >= 2");
     if (iv.sample_bytes != (kWide ? 8u : 4u)) return fail(VLG_E_INTERNAL, "unsampling: sample width does not match the instantiation");
     if (iv.n > (1ull << 32) + 1 || (!kWide && iv.n > (1ull << 32))) return fail(VLG_E_UNSUPPORTED, "unsampling: text too long for 32-bit positions");
     if (iv.sigma >= 0x7FFFu) return fail(VLG_E_INTERNAL, "unsampling: alphabet too large for the key");
     const unsigned bits = bit_width64(iv.sigma);            // keys 0 .. sigma - 1, dead = all ones in these bits too (sorts last)
-    uint64_t alive = iv.n_samples, done_total = 0;
-    // one round of the walkers val_a / key_a [0, alive) as they stand when it is called; the first one makes their words
+    uint64_t alive = iv.n_samples;
+    // one round of the walkers val[0] / key[0] [0, alive) as they stand when it is called; the first one makes their words
     const auto step_round = [&](bool first) {
-        if (timer) timer->begin(0);
-        const vlg_status ks = on_bv(iv.bv_kind, [&](auto bv) { return on_flag(first, [&](auto f) {
-            return launch(unsample_step_kernel<tag_t<decltype(bv)>, kWide, decltype(f)::value>, launch_grid(alive, 8192), stream, iv, val_a, key_a, alive, sa_full, d_stats,
-                          d_counter);
-        }); });
-        if (timer) timer->end(0);
-        return ks;
+        return timed(st.timer, 0, 0, [&] { return on_bv(iv.bv_kind, [&](auto bv) { return on_flag(first, [&](auto f) {
+            return launch(unsample_step_kernel<tag_t<decltype(bv)>, kWide, decltype(f)::value>, launch_grid(alive, 8192), stream, iv, st.buf.val[0], st.buf.key[0], alive,
+                          sa_full, job.d_stats, st.buf.control);
+        }); }); });
     };
-    VLG_HIP_TRY(hipMemsetAsync(d_counter, 0, 8, stream));
+    VLG_HIP_TRY(hipMemsetAsync(st.buf.control, 0, 8, stream));
     uint32_t round = 0;
-    while (alive > tail_threshold) {
+    while (alive > job.tail_threshold) {
         for (uint32_t r = 0; r < kUnsampleSync; ++r, ++round) {
             if (vlg_status ks = step_round(round == 0)) return ks;
-            size_t tb = temp_bytes;
-            if (timer) timer->begin(1, 20ull * alive);
-            rocprim::double_buffer<uint16_t> dk(key_a, key_b);
-            rocprim::double_buffer<uint64_t> dv(val_a, val_b);
-            const hipError_t se = rocprim::radix_sort_pairs(temp, tb, dk, dv, alive, 0, bits, stream);
-            if (timer) timer->end(1);
-            VLG_HIP_TRY(se);
-            key_a = dk.current(); key_b = dk.alternate();
-            val_a = dv.current(); val_b = dv.alternate();
-            if (hook_due) { hook_due = false; if (vlg_status hs = (*while_first_step)()) return hs; }
+            if (vlg_status ps = st.partition(alive, bits)) return ps;
+            if (vlg_status hs = st.hook_once()) return hs;
         }
-        VLG_HIP_TRY(hipMemcpyAsync(h_done, d_counter, 8, hipMemcpyDeviceToHost, stream));
+        VLG_HIP_TRY(hipMemcpyAsync(h_done, st.buf.control, 8, hipMemcpyDeviceToHost, stream));
         VLG_HIP_TRY(hipStreamSynchronize(stream));
-        done_total = *h_done;
-        if (done_total > iv.n_samples) return fail(VLG_E_INTERNAL, "unsampling: more walkers arrived than were started");
-        alive = iv.n_samples - done_total;
+        if (*h_done > iv.n_samples) return fail(VLG_E_INTERNAL, "unsampling: more walkers arrived than were started");
+        alive = iv.n_samples - *h_done;
         if (round > (1u << 20)) return fail(VLG_E_INTERNAL, "unsampling did not converge");
     }
     if (round == 0 && iv.n_samples) {
@@ -1318,32 +1310,21 @@ vlg_status launch_unsample(const IndexView& iv, const uint64_t* d_l, const uint6
         if (vlg_status ks = step_round(true)) return ks;
         ++round;
     }
-    if (hook_due) { hook_due = false; if (vlg_status hs = (*while_first_step)()) return hs; }
+    if (vlg_status hs = st.hook_once()) return hs;
     if (alive || round == 1) {
         // (after an unsorted round 0 the dead are anywhere: the tail looks at all of them)
         const uint64_t span = round == 1 ? iv.n_samples : alive;
         const LocateSlices sl = locate_slices(span, 64 * 4);
-        if (timer) timer->begin(0);
-        const vlg_status ks = on_bv(iv.bv_kind, [&](auto bv) {
-            return launch(unsample_tail_kernel<tag_t<decltype(bv)>, kWide>, dim3(sl.blocks), stream, iv, val_a, key_a, span, sl.per_wave, sa_full, d_stats);
-        });
-        if (timer) timer->end(0);
+        const vlg_status ks = timed(st.timer, 0, 0, [&] { return on_bv(iv.bv_kind, [&](auto bv) {
+            return launch(unsample_tail_kernel<tag_t<decltype(bv)>, kWide>, dim3(sl.blocks), stream, iv, st.buf.val[0], st.buf.key[0], span, sl.per_wave, sa_full, job.d_stats);
+        }); });
         if (ks) return ks;
     }
-    if (total) {
-        if (timer) timer->begin(0);
-        const vlg_status ks = launch_sa_dense_copy(sa_full, d_l, d_out_off, n_pat, total, d_out, stream);
-        if (timer) timer->end(0);
-        if (ks) return ks;
-    }
-    return VLG_OK;
+    if (!job.total) return VLG_OK;
+    return timed(st.timer, 0, 0, [&] { return launch_sa_dense_copy(sa_full, job.d_l, job.d_out_off, job.n_lists, job.total, job.d_out, stream); });
 }
-template vlg_status launch_unsample<false>(const IndexView&, const uint64_t*, const uint64_t*, uint64_t, uint64_t, uint32_t*, uint32_t*, uint64_t*, uint64_t*,
-                                           uint16_t*, uint16_t*, void*, size_t, unsigned long long*, unsigned long long*, unsigned long long*, uint64_t, hipStream_t,
-                                           LaunchTimer*, const std::function<vlg_status()>*);
-template vlg_status launch_unsample<true>(const IndexView&, const uint64_t*, const uint64_t*, uint64_t, uint64_t, uint32_t*, uint32_t*, uint64_t*, uint64_t*,
-                                          uint16_t*, uint16_t*, void*, size_t, unsigned long long*, unsigned long long*, unsigned long long*, uint64_t, hipStream_t,
-                                          LaunchTimer*, const std::function<vlg_status()>*);
+template vlg_status launch_unsample<false>(const IndexView&, const SweepJob<uint32_t>&, uint32_t*, unsigned long long*);
+template vlg_status launch_unsample<true>(const IndexView&, const SweepJob<uint32_t>&, uint32_t*, unsigned long long*);
 
 // the copy on its own, for the integer index (int_index.hpp: an SA-order index of density 1 keeps the suffix array as its samples)
 vlg_status launch_sa_dense_copy(const uint32_t* sa, const uint64_t* d_l, const uint64_t* d_out_off, uint64_t n_pat, uint64_t total, uint32_t* d_out,
@@ -1353,15 +1334,9 @@ vlg_status launch_sa_dense_copy(const uint32_t* sa, const uint64_t* d_l, const u
     return launch(sa_dense_copy_kernel<uint32_t, uint32_t>, launch_grid((total + 7) / 8, 32768), stream, sa, d_l, d_out_off, n_pat, total, d_out);
 }
 
-#define VLG_SWEEP_INST(P, W)                                                                                                          \
-    template vlg_status launch_locate_sweep<P, W>(const IndexView&, const uint64_t*, const uint64_t*, uint64_t, uint64_t, P*, uint64_t*, \
-                                                  uint64_t*, uint16_t*, uint16_t*, void*, size_t, unsigned long long*, unsigned long long*, \
-                                                  uint64_t, hipStream_t, LaunchTimer*, Block*, uint32_t, uint64_t*,                       \
-                                                  const std::function<vlg_status()>*, uint8_t*, SweepCompaction);
-VLG_SWEEP_INST(uint32_t, false)
-VLG_SWEEP_INST(uint32_t, true)        // n = 2^32 + 1 (BASELINE config 4): 33-bit SA indices, 32-bit text positions
-VLG_SWEEP_INST(uint64_t, true)
-#undef VLG_SWEEP_INST
+template vlg_status launch_locate_sweep<uint32_t, false>(const IndexView&, const SweepJob<uint32_t>&);
+template vlg_status launch_locate_sweep<uint32_t, true>(const IndexView&, const SweepJob<uint32_t>&);        // n = 2^32 + 1 (BASELINE config 4): 33-bit SA indices, 32-bit text positions
+template vlg_status launch_locate_sweep<uint64_t, true>(const IndexView&, const SweepJob<uint64_t>&);
 
 template <typename T>
 vlg_status launch_narrow(const uint64_t* d_in, T* d_out, uint64_t count, hipStream_t stream)

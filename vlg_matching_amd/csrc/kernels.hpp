@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <functional>
 #include "common.hpp"
+#include "sweep_scratch.hpp"
 
 namespace vlg {
 
@@ -35,6 +36,13 @@ struct LaunchTimer {
     virtual void begin(int which, uint64_t algorithmic_bytes = 0) = 0;     // which: 0 = LF step kernel, 1 = stable partition by symbol, 2 = trail record resolution
     virtual void end(int which) = 0;
 };
+template <class F> vlg_status timed(LaunchTimer* timer, int which, uint64_t algorithmic_bytes, const F& launch)    // `launch` between the timer's two events
+{
+    if (timer) timer->begin(which, algorithmic_bytes);
+    const vlg_status s = launch();
+    if (timer) timer->end(which);
+    return s;
+}
 
 // The slices the refilling-lane kernels (locate_kernel, unsample_tail_kernel) cut `count` elements into, one per wave: enough waves to
 // fill 256 CUs x 32 waves several times over, but slices long enough (min_per_wave) that the drain tail -- the slowest element of a
@@ -49,40 +57,28 @@ inline LocateSlices locate_slices(uint64_t count, uint64_t min_per_wave = 64 * 1
 }
 
 size_t sweep_temp_bytes(uint64_t total, uint32_t sigma, hipStream_t stream);
-#ifndef VLG_SWEEP_CHUNK
-#define VLG_SWEEP_CHUNK 2048
-#endif
-constexpr uint32_t kSweepChunk = VLG_SWEEP_CHUNK;   // consecutive elements a workgroup of a sweep round takes per turn
-static_assert(kSweepChunk >= 256 && kSweepChunk % 256 == 0, "VLG_SWEEP_CHUNK: whole rows of the 256-thread workgroup");
-static_assert(kSweepChunk <= 4096, "VLG_SWEEP_CHUNK: one wave scans a turn's (row, wave) survivor counts, 64 at most");
-// Control words of a compacting sweep round, in front of the status words of its turns (sweep_kernels.hpp: commit_turn): the
-// round's n_done pointer is the start of this block, which the driver clears before every launch.
-constexpr uint32_t kSweepDone = 0, kSweepStalled = 1, kSweepTicket = 2, kSweepStatus = 4;
-inline uint64_t sweep_turns(uint64_t elements) { return (elements + kSweepChunk - 1) / kSweepChunk; }
-// words of the block for a sweep of `elements` occurrences (a multiple of two: the clearing is a multiple of 16 bytes)
-inline uint64_t sweep_control_words(uint64_t elements) { return kSweepStatus + ((sweep_turns(elements) + 1) & ~1ull); }
-// Round 0 compacts (the workspace option "sweep_compact") when the launcher gets 16 pinned bytes for the round's `done` and give-up
-// word to come back into; the sweep's counter then heads a block of sweep_control_words(elements of one sweep) words.
-struct SweepCompaction {
-    unsigned long long* h_done = nullptr;
-};
 // occurrences one sweep can cover: slots share a 64-bit word with the SA index (32 + 32 bits, or 31 + 33 when SA indices are wide)
 template <bool kWide> constexpr uint64_t sweep_batch_max() { return kWide ? (1ull << 31) : 0xFFFFFF00ull; }
+template <typename pos_t> struct SweepJob {      // what a sorted sweep is asked to do
+    // lists: SA interval starts and output offsets of the n_lists lists; d_out receives their `total` positions (unsorted, SA order)
+    const uint64_t* d_l = nullptr; const uint64_t* d_out_off = nullptr; uint64_t n_lists = 0, total = 0; pos_t* d_out = nullptr;
+    SweepScratch scratch{};     // for min(total, sweep_batch_max) elements (sweep_scratch.hpp)
+    // sharing LF steps, all null or zero when none is shared: member_blocks(n) super-blocks, made up of the first n_member_lists lists
+    // (pairwise disjoint, ascending); rec: `total` words; front: a byte per element, the symbol in front of it (SweepKernels; byte index)
+    Block* member = nullptr; uint32_t n_member_lists = 0; uint64_t* rec = nullptr; uint8_t* front = nullptr;
+    // run: at most tail_threshold elements go to the stragglers' kernel.  h_round: 16 pinned bytes for the `done` and give-up word of a
+    // compacting round 0 (workspace option "sweep_compact"), null: round 0 does not compact.  while_first_step: host work, or null
+    uint64_t tail_threshold = 0; unsigned long long* h_round = nullptr; unsigned long long* d_stats = nullptr;
+    hipStream_t stream = nullptr; LaunchTimer* timer = nullptr; const std::function<vlg_status()>* while_first_step = nullptr;
+};
 // kWide: the index keeps 64-bit samples and SA indices may need 33 bits (n > 2^32, or VLG_FORCE_POS64); pos_t is the width of the
 // text positions written -- uint32_t whenever the text has at most 2^32 characters, whatever the width of the SA indices.
-template <typename pos_t, bool kWide>
-vlg_status launch_locate_sweep(const IndexView& iv, const uint64_t* d_l, const uint64_t* d_out_off, uint64_t n_pat, uint64_t total,
-                               pos_t* d_out, uint64_t* val_a, uint64_t* val_b, uint16_t* key_a, uint16_t* key_b, void* temp,
-                               size_t temp_bytes, unsigned long long* d_counter, unsigned long long* d_stats, uint64_t tail_threshold,
-                               hipStream_t stream, LaunchTimer* timer, Block* member, uint32_t n_member_lists, uint64_t* rec,
-                               const std::function<vlg_status()>* while_first_step = nullptr,
-                               uint8_t* front = nullptr /* with rec: one byte per element, the symbol in front of it (see SweepKernels) */,
-                               SweepCompaction compaction = SweepCompaction());
-// The three launches of a sorted sweep over some index (filled by bind_sweep, sweep_kernels.hpp; each returns the launch's status);
-// run_locate_sweep owns the rounds, the partitions, the member bit-vector, the records and their resolution.  `out` is the sweep's slice of the position array (pos_t*), `rec` null when no LF step is shared.
+template <typename pos_t, bool kWide> vlg_status launch_locate_sweep(const IndexView& iv, const SweepJob<pos_t>& job);
 // the list that holds the first element of every chunk of a sweep [t0, t1): looked up for all chunks at once, in parallel, instead of by
 // one lane of every workgroup in front of its work (a binary search is seventeen dependent loads)
 void launch_sweep_chunk_lists(const uint64_t* d_out_off, uint64_t n_pat, uint64_t t0, uint64_t t1, uint32_t* chunk_list, hipStream_t stream);
+// The three launches of a sorted sweep over some index (filled by bind_sweep, sweep_kernels.hpp; each returns the launch's status); run_locate_sweep
+// owns the rounds, the partitions, the member bit-vector, the records and their resolution.  `out` is the sweep's slice of the position array (pos_t*).
 struct SweepKernels {
     // front[slot] (optional, with records): the compact symbol read in front of an element that stopped on its first step, 0xFF otherwise
     // -- what the resolve regroups a workgroup's records by, so that the first hop of neighbouring lanes reads neighbouring records
@@ -91,7 +87,7 @@ struct SweepKernels {
     uint32_t sigma = 0;                  // partition keys are the symbols 0 .. sigma - 1 (16 bits at most); sigma = finished
     // round 0 of the elements [t0, t1): their words follow from their places (lists l / out_off are the launcher's business)
     // compact: the survivors are written densely, in order, to the front of val / key and nothing else is (n_done then heads a
-    // cleared block of sweep_control_words); otherwise, and in every later round, an element keeps its place and a finished one gets
+    // cleared block of sweep_control_bytes); otherwise, and in every later round, an element keeps its place and a finished one gets
     // key = sigma
     std::function<vlg_status(uint64_t t0, uint64_t t1, uint64_t* val, uint16_t* key, void* out, unsigned long long* n_done, const Block* member, uint64_t* rec, bool ahead,
                        uint32_t* chunk_list /* scratch, one word per kSweepChunk elements: sweep_chunk_lists_kernel */, bool compact)> first;
@@ -102,22 +98,13 @@ struct SweepKernels {
     std::function<vlg_status(void* out, uint64_t alive, uint32_t per_wave, const uint64_t* val, uint32_t step, uint64_t* rec_or_null, uint64_t t0, const Block* member,
                        uint32_t blocks)> tail;
 };
-template <typename pos_t, bool kWide>
-vlg_status run_locate_sweep(const SweepKernels& K, const uint64_t* d_l, const uint64_t* d_out_off, uint64_t n_pat, uint64_t total,
-                            pos_t* d_out, uint64_t* val_a, uint64_t* val_b, uint16_t* key_a, uint16_t* key_b, void* temp,
-                            size_t temp_bytes, unsigned long long* d_counter, uint64_t tail_threshold, hipStream_t stream, LaunchTimer* timer,
-                            Block* member, uint32_t n_member_lists, uint64_t* rec, const std::function<vlg_status()>* while_first_step = nullptr,
-                            SweepCompaction compaction = SweepCompaction());
+template <typename pos_t, bool kWide> vlg_status run_locate_sweep(const SweepKernels& K, const SweepJob<pos_t>& job);
 // super-blocks of the member bit-vector over the SA indices of a text of n - 1 characters (kernels.hip: sweep_element)
 inline uint64_t member_blocks(uint64_t n) { return n / kBlockBits + 1; }
 // K3u: the whole suffix array reconstructed from the samples (one LF walker per sample, n LF steps in all) into sa_full (n x 4 B),
 // then the SA intervals of the lists copied into d_out.  For batches that locate a large part of all text positions.
-// Scratch: val_a / val_b (8 B) and key_a / key_b (2 B) for n_samples walkers, temp as for the sweep, counter 8 B.
-template <bool kWide>
-vlg_status launch_unsample(const IndexView& iv, const uint64_t* d_l, const uint64_t* d_out_off, uint64_t n_pat, uint64_t total, uint32_t* d_out,
-                           uint32_t* sa_full, uint64_t* val_a, uint64_t* val_b, uint16_t* key_a, uint16_t* key_b, void* temp, size_t temp_bytes,
-                           unsigned long long* d_counter, unsigned long long* h_done /* 8 pinned bytes */, unsigned long long* d_stats, uint64_t tail_threshold,
-                           hipStream_t stream, LaunchTimer* timer, const std::function<vlg_status()>* while_first_step = nullptr);
+// job.scratch: UnsampleScratch's walkers (n_samples of them); h_done: 8 pinned bytes.
+template <bool kWide> vlg_status launch_unsample(const IndexView& iv, const SweepJob<uint32_t>& job, uint32_t* sa_full, unsigned long long* h_done);
 template <typename T> vlg_status launch_narrow(const uint64_t* d_in, T* d_out, uint64_t count, hipStream_t stream);
 template <typename T> vlg_status launch_widen(const T* d_in, uint64_t* d_out, uint64_t count, hipStream_t stream);
 
@@ -125,11 +112,7 @@ template <typename T> vlg_status launch_widen(const T* d_in, uint64_t* d_out, ui
 vlg_status launch_int_backward_search(const IntView& v, const uint8_t* d_blob, const uint64_t* d_off, uint64_t n_pat, uint64_t* d_l, uint64_t* d_r,
                                       unsigned long long* d_stat_levels, hipStream_t st);
 vlg_status launch_int_locate(const IntView& v, uint32_t* d_io, uint64_t total, unsigned long long* d_stats, hipStream_t st);
-vlg_status launch_int_locate_sweep(const IntView& v, const uint64_t* d_l, const uint64_t* d_out_off, uint64_t n_pat, uint64_t total, uint32_t* d_out,
-                                   uint64_t* val_a, uint64_t* val_b, uint16_t* key_a, uint16_t* key_b, void* temp, size_t temp_bytes, unsigned long long* d_counter,
-                                   unsigned long long* d_stats, uint64_t tail_threshold, hipStream_t stream, LaunchTimer* timer, Block* member,
-                                   uint32_t n_member_lists, uint64_t* rec, const std::function<vlg_status()>* while_first_step = nullptr,
-                                   SweepCompaction compaction = SweepCompaction());
+vlg_status launch_int_locate_sweep(const IntView& v, const SweepJob<uint32_t>& job);
 // SA-order density 1 (vlg_index_resample): locate copies SA intervals of the samples, which are the suffix array (sa_dense_copy_kernel)
 vlg_status launch_sa_dense_copy(const uint32_t* sa, const uint64_t* d_l, const uint64_t* d_out_off, uint64_t n_pat, uint64_t total, uint32_t* d_out,
                                 hipStream_t stream);

@@ -690,7 +690,6 @@ vlg_status wire_room_and_fences(Lists<pos_t>& L, const ListRoom& room, uint64_t 
     return VLG_OK;
 }
 
-template <typename pos_t> constexpr uint64_t kPhysScratchPerElem() { return 20; }   // sweep scratch; the sorted lists reuse it
 // What JoinChunk carves, as the planners count it.  Per slot:
 constexpr uint64_t kJoinBytesPerSlot = 4 + 8 + 1;      // any slot: link, endp (<= 8), lvl_ptr[] (feasibility bits + summaries)
 constexpr uint64_t kJoinBytesPerSlot0 = 4 + 4 + 8 + 1; // slots of list 0: jump, mlist, xh (exit, hops), d_recq + d_rec (chain records)
@@ -863,7 +862,7 @@ struct PhysChoice {
 };
 
 // `elems` occurrences in `n_lists` lists.  K3u (kernels.hip: the whole suffix array rebuilt from the samples -- n LF steps, no trails,
-// no records) is judged on `unsample_elems` and needs its arrays (n x 4 B + 20 B per sample) inside the sweep scratch of
+// no records) is judged on `unsample_elems` and needs its arrays (sweep_scratch.hpp: unsample_scratch_bytes) inside the sweep scratch of
 // `scratch_elems` (0: not tested).  `sized` is the choice the arena was planned for (null: this is that plan): the pass unsamples and
 // shares LF steps only where the plan made room for it.
 template <typename pos_t>
@@ -881,7 +880,7 @@ PhysChoice choose_physical(const vlg_index* idx, const vlg_workspace* ws, uint64
     const bool unsample = c.sweep && sizeof(pos_t) == 4 && ws->unsample_pct && ws->trail && ws->dedup && !idx->is_int && h.sampling == kSamplingSaOrder &&
                           h.dens >= 2 && h.n <= (1ull << 32) + 1 && h.sigma < 0x7FFFu && unsample_elems >= ws->sweep_min && unsample_elems >= ws->unsample_min &&
                           (__uint128_t)unsample_elems * 100 >= (__uint128_t)h.n * ws->unsample_pct &&
-                          (!scratch_elems || align_up(h.n * 4, 256) + n_walkers * 20 + 1024 <= scratch_elems * kPhysScratchPerElem<pos_t>()) &&
+                          (!scratch_elems || unsample_scratch_bytes(h.n, n_walkers) <= scratch_elems * kSweepScratchPerElem) &&
                           (!sized || sized->locate == VLG_LOCATE_UNSAMPLE);
     c.locate = !c.sweep ? (idx->is_int && dense ? VLG_LOCATE_COPY : VLG_LOCATE_WALKS) : unsample ? VLG_LOCATE_UNSAMPLE : dense ? VLG_LOCATE_COPY : VLG_LOCATE_SWEEP;
     c.share_steps = c.sweep && !unsample && ws->trail && ws->dedup && !dense && elems <= 0xFFFFFF00ull && (!sized || sized->share_steps);
@@ -1004,14 +1003,14 @@ struct PhysicalPass {
     vlg_status carve()
     {
         Pg = A.take<pos_t>(gacc);
-        scratch = A.take<uint8_t>(gacc * kPhysScratchPerElem<pos_t>());   // the sweep's scratch (20 B per element); the sorted lists Pb reuse it
+        scratch = A.take<uint8_t>(gacc * kSweepScratchPerElem);   // the sweep's scratch (20 B per element); the sorted lists Pb reuse it
         Pa = Pg ? Pg + goff64[sl] : nullptr;
         d_goff64 = (ws->x_ranks > 1) ? A.take<uint64_t>(gnd + 1) : nullptr;
         d_off64 = A.take<uint64_t>(nd + 1);
         d_off32 = A.take<uint32_t>(nd + 1);
         d_lh = A.take<uint64_t>(nd);
-        // [0] the sweep's counter, [1..3] diagnostics (VLG_RESOLVE_STATS); a compacting sweep's control block starts here too (kernels.hpp)
-        d_counter = A.take<unsigned long long>(std::max<uint64_t>(4, c.sweep && ws->sweep_compact ? sweep_control_words(sweep_cap()) : 0));
+        // the sweep's control block (sweep_scratch.hpp): the counter, diagnostics behind it, and what a compacting round 0 adds
+        d_counter = A.take<unsigned long long>(std::max(kSweepControlFloor, sweep_control_bytes(sweep_cap(), c.sweep && ws->sweep_compact)) / 8);
         d_tmp = A.take<uint8_t>(cp.sort_tmp + 256);
         if (A.failed) return fail(VLG_E_INTERNAL, "arena carve failed (physical)");
         Pb = reinterpret_cast<pos_t*>(scratch);
@@ -1050,47 +1049,35 @@ struct PhysicalPass {
         vlg_status s = VLG_OK;
         // the view the locate kernels walk: with the quad image or without it (shape_dispatch.hpp: on_byte_walk)
         const IndexView lview = ws->quad_walk ? idx->view : without_quad(idx->view);
-        if (c.locate == VLG_LOCATE_UNSAMPLE) {
-            // K3u: the whole suffix array from the samples, inside the sweep's scratch (n x 4 B + 20 B per sample <= 20 B per occurrence)
-            uint32_t* sa_full = reinterpret_cast<uint32_t*>(scratch);
-            uint64_t* val_a = reinterpret_cast<uint64_t*>(scratch + align_up(idx->hdr.n * 4, 256));
-            uint64_t* val_b = val_a + n_walkers;
-            uint16_t* key_a = reinterpret_cast<uint16_t*>(val_b + n_walkers);
-            uint16_t* key_b = key_a + n_walkers;
-            svec<unsigned long long> h_done(1, 0);
+        if (c.sweep) {
+            // the sorted sweep, or K3u inside the sweep's scratch (choose_physical saw to it that it fits): one job, with another scratch and tail
             SweepTimer timer(ws);
+            SweepJob<pos_t> job;
+            job.d_l = d_lh; job.d_out_off = d_off64; job.n_lists = nd; job.total = acc; job.d_out = Pa;
+            job.d_stats = d_stats; job.stream = st; job.timer = &timer; job.while_first_step = &hook;
             bt.mark("  physical: tables + sort plan");
-            if constexpr (sizeof(pos_t) == 4) {
-                if (wide) s = launch_unsample<true>(idx->view, d_lh, d_off64, nd, acc, Pa, sa_full, val_a, val_b, key_a, key_b, d_tmp, cp.sort_tmp, d_counter, h_done.data(),
-                                                    d_stats, ws->unsample_tail, st, &timer, &hook);
-                else s = launch_unsample<false>(idx->view, d_lh, d_off64, nd, acc, Pa, sa_full, val_a, val_b, key_a, key_b, d_tmp, cp.sort_tmp, d_counter, h_done.data(),
-                                                d_stats, ws->unsample_tail, st, &timer, &hook);
+            if (c.locate == VLG_LOCATE_UNSAMPLE) {
+                const UnsampleScratch u = UnsampleScratch::over(scratch, idx->hdr.n, n_walkers, d_tmp, cp.sort_tmp, d_counter);
+                job.scratch = u.walkers; job.tail_threshold = ws->unsample_tail;
+                svec<unsigned long long> h_done(1, 0);
+                if constexpr (sizeof(pos_t) == 4) s = wide ? launch_unsample<true>(idx->view, job, u.sa_full, h_done.data()) : launch_unsample<false>(idx->view, job, u.sa_full, h_done.data());
+                if (!s) bt.mark("  physical: unsampling");
+            } else {
+                svec<unsigned long long> h_round(2, 0);                   // the compacting round's `done` and give-up word come back here
+                job.scratch = SweepScratch::over(scratch, sweep_cap(), d_tmp, cp.sort_tmp, d_counter);
+                job.member = member; job.rec = rec; job.front = front;
+                job.n_member_lists = n_outer > sl ? std::min(n_outer - sl, nd) : 0u;      // this rank's outer lists: a prefix of its share
+                job.tail_threshold = ws->sweep_tail; job.h_round = ws->sweep_compact ? h_round.data() : nullptr;
+                if (idx->is_int) {
+                    if constexpr (sizeof(pos_t) == 4) s = launch_int_locate_sweep(idx->iview, job);
+                    else s = fail(VLG_E_INTERNAL, "integer-alphabet index with 64-bit positions");
+                } else if (wide)
+                    s = launch_locate_sweep<pos_t, true>(lview, job);
+                else if constexpr (sizeof(pos_t) == 4)                      // (a 64-bit position type always comes with wide indices)
+                    s = launch_locate_sweep<uint32_t, false>(lview, job);
+                else s = fail(VLG_E_INTERNAL, "64-bit positions with 32-bit SA indices");
+                if (!s) bt.mark("  physical: sweep");
             }
-            if (!s) bt.mark("  physical: unsampling");
-        } else if (c.sweep) {
-            const uint64_t cap = sweep_cap();
-            svec<unsigned long long> h_round(2, 0);                       // the compacting round's `done` and give-up word come back here
-            const SweepCompaction compaction{ws->sweep_compact ? h_round.data() : nullptr};
-            uint64_t* val_a = reinterpret_cast<uint64_t*>(scratch);
-            uint64_t* val_b = val_a + cap;
-            uint16_t* key_a = reinterpret_cast<uint16_t*>(val_b + cap);
-            uint16_t* key_b = key_a + cap;
-            const uint32_t n_member_lists = n_outer > sl ? std::min(n_outer - sl, nd) : 0u;      // this rank's outer lists: a prefix of its share
-            SweepTimer timer(ws);
-            bt.mark("  physical: tables + sort plan");
-            if (idx->is_int) {
-                if constexpr (sizeof(pos_t) == 4)
-                    s = launch_int_locate_sweep(idx->iview, d_lh, d_off64, nd, acc, Pa, val_a, val_b, key_a, key_b, d_tmp, cp.sort_tmp, d_counter, d_stats, ws->sweep_tail, st,
-                                                &timer, member, n_member_lists, rec, &hook, compaction);
-                else s = fail(VLG_E_INTERNAL, "integer-alphabet index with 64-bit positions");
-            } else if (wide)
-                s = launch_locate_sweep<pos_t, true>(lview, d_lh, d_off64, nd, acc, Pa, val_a, val_b, key_a, key_b, d_tmp, cp.sort_tmp, d_counter, d_stats,
-                                                     ws->sweep_tail, st, &timer, member, n_member_lists, rec, &hook, front, compaction);
-            else if constexpr (sizeof(pos_t) == 4)                      // (a 64-bit position type always comes with wide indices)
-                s = launch_locate_sweep<uint32_t, false>(lview, d_lh, d_off64, nd, acc, Pa, val_a, val_b, key_a, key_b, d_tmp, cp.sort_tmp, d_counter, d_stats,
-                                                         ws->sweep_tail, st, &timer, member, n_member_lists, rec, &hook, front, compaction);
-            else s = fail(VLG_E_INTERNAL, "64-bit positions with 32-bit SA indices");
-            if (!s) bt.mark("  physical: sweep");
         } else if (idx->is_int) {
             // integer-alphabet index (int_index.hpp): one lane per occurrence on the wavelet matrix of the BWT -- or, with the suffix array
             // resident (SA order, density 1), a copy of the SA intervals whatever the alphabet or the size of the batch
@@ -1261,7 +1248,7 @@ struct PhysicalPass {
     // room for the survivors of the window filter behind the sorted lists (the dead scratch), the fences of both and the ladder
     vlg_status fences_and_ladder()
     {
-        const uint64_t dead_bytes = (L.P == Pb ? 0 : (uint64_t)(scratch - reinterpret_cast<uint8_t*>(Pg))) + gacc * kPhysScratchPerElem<pos_t>() - gacc * sizeof(pos_t);
+        const uint64_t dead_bytes = (L.P == Pb ? 0 : (uint64_t)(scratch - reinterpret_cast<uint8_t*>(Pg))) + gacc * kSweepScratchPerElem - gacc * sizeof(pos_t);
         const uint64_t pc_first = align_up(gacc, 64);
         if (dead_bytes > (pc_first - gacc + 64) * sizeof(pos_t) && pc_first < 0xFFFFFF00ull) {
             L.Pc = L.P + pc_first;
@@ -1967,9 +1954,9 @@ vlg_status plan_super_chunk(const vlg_index* idx, const vlg_queries* q, const Pl
     // one pass over the lists against two descents per pivot element)
     cp.want_rungs = pivot_elems && (ws->pivot_rungs == 2 || (pivot_elems >= phys / 16 && pivot_elems >= 4096));
     const uint64_t rung_bytes = cp.want_rungs ? rung_layout(phys).entries * sizeof(pos_t) + 8192 : 0;
-    // (with the sweep's scratch: the control block of its compacting rounds, 8 B per turn -- kernels.hpp: sweep_control_words)
-    const uint64_t sweep_ctl = cp.c.sweep && ws->sweep_compact ? sweep_control_words(phys) * 8 + 256 : 0;
-    const uint64_t phys_plain = phys * (sizeof(pos_t) + kPhysScratchPerElem<pos_t>()) + sweep_ctl + cp.sort_tmp + (dlist.size() + 2) * 24 + (8ull << 20) + phys + rung_bytes;
+    // (with the sweep's scratch: the control block of its compacting rounds, 8 B per turn -- sweep_scratch.hpp)
+    const uint64_t sweep_ctl = cp.c.sweep && ws->sweep_compact ? sweep_control_bytes(phys, true) + kSweepControlSlack : 0;
+    const uint64_t phys_plain = phys * (sizeof(pos_t) + kSweepScratchPerElem) + sweep_ctl + cp.sort_tmp + (dlist.size() + 2) * 24 + (8ull << 20) + phys + rung_bytes;
     if (trail_bytes) {
         const uint64_t left = budget > phys_plain + trail_bytes ? budget - phys_plain - trail_bytes : 0;
         if (left < std::max<uint64_t>(2 * logical_max_query, budget / 8)) trail_bytes = 0;
@@ -2146,7 +2133,7 @@ vlg_status run_batch(const vlg_index* idx, const vlg_queries* q, vlg_workspace* 
     if (ws->cap_bytes <= 2 * fixed) return fail(VLG_E_WORKSPACE, "workspace cap too small");
     const uint64_t budget = ws->cap_bytes - fixed;
     // physical lists take at most half of the budget (two buffers during the sort)
-    const uint64_t phys_cap = std::min<uint64_t>(budget / 2 / (sizeof(pos_t) + kPhysScratchPerElem<pos_t>() + 1), 0xFFFFFF00ull);
+    const uint64_t phys_cap = std::min<uint64_t>(budget / 2 / (sizeof(pos_t) + kSweepScratchPerElem + 1), 0xFFFFFF00ull);
     std::vector<uint32_t> stamp(pl.dl.size(), 0xFFFFFFFFu);
     Lists<pos_t> L;
     L.doff.assign(pl.dl.size(), 0);

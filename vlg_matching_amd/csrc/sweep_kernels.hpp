@@ -618,9 +618,10 @@ __global__ void __launch_bounds__(256) sweep_first_kernel(typename Walk::View iv
 // The sweep's launches over one walk and one sampling.  run_locate_sweep calls them after this frame has gone, so they hold the view
 // and everything else by value.  front: null unless the resolve regroups by it (SweepKernels).
 template <class Walk, class Sampling, typename pos_t, bool kWide>
-SweepKernels bind_sweep(const typename Walk::View& iv, const uint64_t* d_l, const uint64_t* d_out_off, uint64_t n_pat, unsigned long long* d_stats,
-                        hipStream_t stream, uint8_t* front)
+SweepKernels bind_sweep(const typename Walk::View& iv, const SweepJob<pos_t>& job, uint8_t* front)
 {
+    const uint64_t* const d_l = job.d_l; const uint64_t* const d_out_off = job.d_out_off; const uint64_t n_pat = job.n_lists;      // (of the job, the launches hold these five)
+    unsigned long long* const d_stats = job.d_stats; const hipStream_t stream = job.stream;
     SweepKernels K;
     K.n = iv.n;
     K.sigma = (uint32_t)iv.sigma;
@@ -647,14 +648,11 @@ SweepKernels bind_sweep(const typename Walk::View& iv, const uint64_t* d_l, cons
 }
 
 // Every SA index is sampled (SA-order samples of density 1): no walk, no trails, no records -- the sweep is `copy`, one launch
-template <class Copy>
-vlg_status sweep_dense_copy(LaunchTimer* timer, const std::function<vlg_status()>* while_first_step, const Copy& copy)
+template <typename pos_t, class Copy>
+vlg_status sweep_dense_copy(const SweepJob<pos_t>& job, const Copy& copy)
 {
-    if (timer) timer->begin(0);
-    const vlg_status s = copy();
-    if (timer) timer->end(0);
-    if (s) return s;
-    return while_first_step ? (*while_first_step)() : VLG_OK;
+    if (vlg_status s = timed(job.timer, 0, 0, copy)) return s;
+    return job.while_first_step ? (*job.while_first_step)() : VLG_OK;
 }
 
 }  // namespace vlg
