@@ -981,6 +981,12 @@ vlg_status vlg_workspace_profile(vlg_workspace* ws, int enable);
  * positions into the result itself, once the match counts have come back to the host and the result is allocated, and adds them into
  * the checksum; 0 = it writes the matches' slots into scratch and a gather pass turns them into positions (an A/B inside one library;
  * with tuples the gather pass runs either way).  Its time is in the kernel class "join_chain"; "gather" then has no launches.
+ * "tile_scan" (default 1): the pass that resolves the match chain inside tiles of 1024 first-list elements finishes every element by
+ * one backward scan of its tile in two levels (32 blocks of 32), half a wave per tile; 0 = pointer doubling, a workgroup per tile
+ * (an A/B inside one library).  Both leave the same words.
+ * "walk_wave" (default 1): a query whose first list spans at least 64 such tiles is walked from tile to tile by a whole wave, which
+ * fetches the first 16 words of the next four tiles together with the current one and hops through them without another round trip;
+ * 0 = one lane per query for all queries (an A/B inside one library).  Both leave the same records and counts.
  * Counts, first positions, tuples and the checksum are identical whatever the other options are. */
 vlg_status vlg_workspace_set_option(vlg_workspace* ws, const char* name, int64_t value);
 vlg_status vlg_workspace_kernel_stats(vlg_workspace* ws, vlg_kernel_stat* out, uint32_t cap, uint32_t* n);

@@ -1103,9 +1103,8 @@ constexpr uint32_t kTileFeasWords = 32;     // feasibility words the tile pass s
 // after the raw one, if that is still a slot of the same segment (padding slots are never feasible, so "below the begin of the next
 // segment" is "below the end of this one"), else kNone.  A word that is settled already -- the separate jump pass writes such -- is a
 // feasible slot of its own segment and stays as it is.
-__global__ void __launch_bounds__(256) chain_tiles_kernel(uint32_t* __restrict__ jump, uint64_t t0 /* multiple of kTile */,
-                                                          uint64_t r1, FeasRef fb, const uint32_t* __restrict__ seg_begin, uint32_t nseg,
-                                                          uint2* __restrict__ xh)
+__device__ __forceinline__ void chain_tiles_doubling(uint32_t* __restrict__ jump, uint64_t t0, uint64_t r1, const FeasRef& fb,
+                                                     const uint32_t* __restrict__ seg_begin, uint32_t nseg, uint2* __restrict__ xh)
 {
     static_assert(kTile == 1024, "the packed word holds 10-bit tile offsets");
     __shared__ uint32_t s_ext[kTile];
@@ -1196,13 +1195,222 @@ __global__ void __launch_bounds__(256) chain_tiles_kernel(uint32_t* __restrict__
     }
 }
 
-// (a chain starts at the first feasible element of the query's first list)
-__global__ void chain_walk_kernel(const SegMeta* __restrict__ sm, const QueryMeta* __restrict__ qm, uint32_t nq, FeasRef fb,
-                                  const uint2* __restrict__ xh, const uint32_t* __restrict__ rec_begin,
-                                  uint2* __restrict__ records, uint32_t* __restrict__ rec_count, unsigned long long* __restrict__ counts)
+// The same words by one backward scan (workspace option "tile_scan", the default).  jump[e] > e: the chains of a tile form an ORDERED
+// forest, every target lies behind its slot, so a slot is finished by one look-up once everything behind it is.  Two levels keep that
+// parallel: the tile is 32 blocks of 32 slots,
+//   phase 1 : a lane per block walks it from its last slot to its first; a slot whose target lies inside the block takes the target's
+//             state (final for the block already), one whose target lies outside keeps its own;
+//   phase 2 : the blocks from the last to the first, a lane per slot; a slot whose chain leaves its block composes with the slot it
+//             lands on, which lies in a later block and is final.
+// 32 + 32 dependent LDS steps whatever the chains look like, against up to 10 rounds over all slots.  A tile belongs to HALF a wave
+// (32 lanes, 32 slots each; a wave takes two tiles, a workgroup eight), so nothing here waits for a workgroup barrier.  The state
+// word is the doubling's.  The state array is padded by one word per block: in phase 1 lane l addresses slot 32 l + k, word 33 l + k,
+// and the 32 lanes of a tile hit 32 different banks; in phase 2 the lanes address consecutive words.  The two tiles of a wave lie in
+// different lane groups of an LDS access and never meet.  The settled jump words stay in registers through the scan and go into the
+// state array when it is done, where `last` finds the exit: 4.2 KB of LDS per tile.
+constexpr uint32_t kScanBlock = 32;                                  // slots of a block, and blocks of a tile
+constexpr uint32_t kScanTiles = 8;                                   // tiles of a workgroup: two per wave
+constexpr uint32_t kScanWords = kTile + kTile / kScanBlock;          // state words of a tile, padded
+__device__ __forceinline__ uint32_t scan_word(uint32_t li) { return li + li / kScanBlock; }
+
+__device__ __forceinline__ void chain_tiles_scan(uint32_t* __restrict__ jump, uint64_t t0, uint64_t r1, const FeasRef& fb,
+                                                 const uint32_t* __restrict__ seg_begin, uint32_t nseg, uint2* __restrict__ xh)
 {
-    uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+    static_assert(kTile == 1024 && kScanBlock * kScanBlock == kTile, "the packed word holds 10-bit tile offsets; 32 blocks of 32 slots");
+    __shared__ uint32_t s_st[kScanTiles][kScanWords];
+    __shared__ uint64_t s_fb[kScanTiles][kTileFeasWords];
+    constexpr uint32_t kDone = 1u << 10;
+    constexpr uint32_t kPer = kTile / 32;                            // slots per lane
+    const uint32_t l = threadIdx.x & 31, tl = threadIdx.x >> 5;      // lane of the tile, tile of the workgroup
+    uint32_t* const S = s_st[tl];
+    const uint64_t base = t0 + ((uint64_t)blockIdx.x * kScanTiles + tl) * kTile;       // (may lie at or behind r1: such a tile writes nothing)
+    const uint64_t wave_base = uniform(t0 + ((uint64_t)blockIdx.x * kScanTiles + (tl & ~1u)) * kTile);
+    const uint64_t tile_end = base + kTile;
+    // ---- settling, as in the doubling kernel: a lane holds slots l + 32 r of its tile ------------------------------------------------
+    uint32_t jw[kPer];
+#pragma unroll
+    for (uint32_t r = 0; r < kPer; ++r) {
+        const uint64_t e = base + l + 32 * r;
+        jw[r] = e < r1 ? jump[e] : kNone;
+    }
+    const uint64_t w_base = base >> 6;
+    s_fb[tl][l] = w_base + l <= ((r1 - 1) >> 6) ? fb.lvl0[w_base + l] : 0;             // (kTileFeasWords = 32: a word per lane)
+    static_assert(kTileFeasWords == 32, "one feasibility word per lane of the tile");
+    wave_sync();
+    uint32_t moved = 0;                                              // bit r: the target of slot r is not the raw one
+#pragma unroll
+    for (uint32_t r = 0; r < kPer; ++r) {
+        const uint32_t j = jw[r];
+        if (j != kNone) {
+            const uint64_t wi = ((uint64_t)j >> 6) - w_base;
+            const uint64_t bits = wi < kTileFeasWords ? s_fb[tl][wi] >> (j & 63) : 0;
+            const uint32_t ej = bits ? j + (uint32_t)__ffsll((long long)bits) - 1 : next_feasible(fb, j);
+            moved |= (uint32_t)(ej != j) << r;
+            jw[r] = ej;
+        }
+    }
+    // the segment of the wave's first slot, once per wave that has a moved target; the lanes walk on from it only where a border falls
+    // before the end of their tile
+    if (__any(moved != 0)) {
+        const uint32_t s_t = wave_seg_find(seg_begin, nseg, wave_base);
+        const uint32_t t_next = seg_begin[s_t + 1];                  // begin of the next segment with slots (seg_begin[nseg + 1] = 2^32 - 1)
+#pragma unroll
+        for (uint32_t r = 0; r < kPer; ++r) {
+            const uint64_t e = base + l + 32 * r;
+            if ((moved >> r) & 1) {
+                uint32_t lim = t_next;
+                if ((uint64_t)lim < tile_end) {
+                    uint32_t s = s_t;
+                    while (seg_begin[s + 1] <= e) ++s;
+                    lim = seg_begin[s + 1];
+                }
+                if (jw[r] >= lim) jw[r] = kNone;
+                jump[e] = jw[r];
+            }
+        }
+    }
+#pragma unroll
+    for (uint32_t r = 0; r < kPer; ++r) {
+        const uint32_t li = l + 32 * r;
+        const uint32_t j = jw[r];
+        const bool inside = j != kNone && (uint64_t)j < tile_end;
+        S[li + r] = (inside ? (uint32_t)(j - base) : kDone) | (li << 21);                // (scan_word(li) = li + r)
+    }
+    wave_sync();
+    // ---- phase 1: lane l owns block l, words 33 l + k; it reads and writes no other block ---------------------------------------------
+    {
+        uint32_t* const B = S + l * (kScanBlock + 1);
+        uint32_t v = B[kScanBlock - 1];
+        for (uint32_t k = kScanBlock; k-- > 0;) {
+            const uint32_t below = k ? B[k - 1] : 0;                 // (asked for before slot k is written: slot k - 1 does not wait for it)
+            const uint32_t t = v & 1023u;
+            if (!(v & kDone) && t / kScanBlock == l) {
+                const uint32_t nx = S[scan_word(t)];
+                const uint32_t hops = ((v >> 11) & 1023u) + ((nx >> 11) & 1023u) + 1;
+                B[k] = (nx & 0x7FFu) | (hops << 11) | (nx & (1023u << 21));
+            }
+            v = below;
+        }
+    }
+    wave_sync();
+    // ---- phase 2: block b, lane l takes slot 32 b + l, word 33 b + l; an open slot lands in a block that is final -----------------------
+    {
+        uint32_t v = S[(kScanBlock - 1) * (kScanBlock + 1) + l];
+        for (uint32_t b = kScanBlock; b-- > 0;) {
+            const uint32_t below = b ? S[(b - 1) * (kScanBlock + 1) + l] : 0;          // (block b - 1 is written in its own step only)
+            if (!(v & kDone)) {
+                const uint32_t nx = S[scan_word(v & 1023u)];
+                const uint32_t hops = ((v >> 11) & 1023u) + ((nx >> 11) & 1023u) + 1;
+                S[b * (kScanBlock + 1) + l] = kDone | (hops << 11) | (nx & (1023u << 21));
+            }
+            wave_sync();
+            v = below;
+        }
+    }
+    // ---- the exits: the states leave the array, the settled jump words take their place -------------------------------------------------
+    uint32_t st[kPer];
+#pragma unroll
+    for (uint32_t r = 0; r < kPer; ++r) st[r] = S[l + 33 * r];
+    wave_sync();
+#pragma unroll
+    for (uint32_t r = 0; r < kPer; ++r) S[l + 33 * r] = jw[r];
+    wave_sync();
+#pragma unroll
+    for (uint32_t r = 0; r < kPer; ++r) {
+        const uint64_t e = base + l + 32 * r;
+        if (e < r1) xh[e] = make_uint2(S[scan_word(st[r] >> 21)], ((st[r] >> 11) & 1023u) + 1);
+    }
+}
+
+template <bool kScan>
+__global__ void __launch_bounds__(256) chain_tiles_kernel(uint32_t* __restrict__ jump, uint64_t t0 /* multiple of kTile */,
+                                                          uint64_t r1, FeasRef fb, const uint32_t* __restrict__ seg_begin, uint32_t nseg,
+                                                          uint2* __restrict__ xh)
+{
+    if constexpr (kScan) chain_tiles_scan(jump, t0, r1, fb, seg_begin, nseg, xh);
+    else chain_tiles_doubling(jump, t0, r1, fb, seg_begin, nseg, xh);
+}
+
+// (a chain starts at the first feasible element of the query's first list)
+//
+// A lane that walks a heavy query pays one dependent xh[] round trip per tile while the other 63 lanes of its wave have long finished.
+// Queries whose level-0 segment overlaps at least `wave_tiles` tiles (workspace option "walk_wave"; layout() lists them in `heavy`) are
+// therefore walked by a wave each, the first n_heavy waves of the launch, in rounds: together with xh[cur] the wave asks for the first
+// kWalkHeadSlots words of the next kWalkHeadTiles tiles, one word per lane, clipped to the segment.  A chain's exit lands a few slots
+// into a following tile, so the entry's word is usually one of these heads: the wave hops exit to entry through them by cross-lane
+// reads, a record per tile visited, and one latency covers up to kWalkHeadTiles + 1 tiles.  The first entry the heads do not hold opens
+// the next round.  Records, record counts and match counts are those of the lane loop, in the same order.
+constexpr uint32_t kWalkWaveTiles = 64;      // tiles of a level-0 segment from which a wave walks it
+constexpr uint32_t kWalkHeadTiles = 4, kWalkHeadSlots = 16;
+static_assert(kWalkHeadTiles * kWalkHeadSlots == 64, "one head word per lane");
+// -DVLG_WALK_STATS: rounds of the heavy waves, tiles they visited, and entries that lay outside the fetched heads (each opens a round);
+// search.hip prints and clears them behind every walk launch.  A diagnostic build.
+#ifdef VLG_WALK_STATS
+enum { WS_QUERIES = 0, WS_ROUNDS, WS_TILES, WS_MISSES, WS_COUNT };
+__device__ unsigned long long g_walk_stats[WS_COUNT];
+#define VLG_WALK_STAT(i, n) do { const unsigned long long n_ = (unsigned long long)(n); if ((threadIdx.x & 63) == 0 && n_) atomicAdd(&g_walk_stats[i], n_); } while (0)
+#else
+#define VLG_WALK_STAT(i, n) do { } while (0)
+#endif
+__global__ void __launch_bounds__(64) chain_walk_kernel(const SegMeta* __restrict__ sm, const QueryMeta* __restrict__ qm, uint32_t nq, FeasRef fb,
+                                                        const uint2* __restrict__ xh, const uint32_t* __restrict__ rec_begin,
+                                                        uint2* __restrict__ records, uint32_t* __restrict__ rec_count,
+                                                        unsigned long long* __restrict__ counts, const uint32_t* __restrict__ heavy,
+                                                        uint32_t n_heavy, uint32_t wave_tiles /* 2^32 - 1: no query is heavy */)
+{
+    if (blockIdx.x < n_heavy) {
+        // ---- a wave per heavy query (its segment is not empty) -------------------------------------------------------------------
+        const uint32_t lane = threadIdx.x;
+        const uint32_t q = heavy[blockIdx.x];
+        const uint32_t seg0 = qm[q].seg0;
+        const uint32_t mbegin = sm[seg0].begin, mend = sm[seg0].end;
+        const uint32_t n_tiles = rec_begin[q + 1] - rec_begin[q];    // tiles the segment overlaps: no chain visits more
+        uint2* rec = records + rec_begin[q];
+        uint32_t cur = uniform(next_feasible(fb, mbegin));
+        if (cur >= mend) cur = kNone;
+        unsigned long long n_match = 0;
+        uint32_t nrec = 0;
+        VLG_WALK_STAT(WS_QUERIES, 1);
+        // The records wait in the lanes, the n-th since the last store in lane n, and are stored 60 or more at a time: loads and stores
+        // leave one counter in issue order, so a store per hop in front of the next round's loads would be waited for with them.
+        uint2 pend = make_uint2(0, 0);
+        uint32_t pend_at = 0, pend_n = 0;
+        while (cur != kNone && nrec < n_tiles) {                     // a round; every hop below leaves a record, so this ends
+            if (pend_n > 64 - (kWalkHeadTiles + 1)) {                // (a round leaves at most kWalkHeadTiles + 1 records)
+                if (lane < pend_n) rec[pend_at + lane] = pend;
+                pend_at = nrec; pend_n = 0;
+            }
+            const uint64_t first = (uint64_t)(cur / kTile + 1) * kTile;          // first slot of the tile behind cur's
+            const uint64_t hs = first + (uint64_t)(lane / kWalkHeadSlots) * kTile + lane % kWalkHeadSlots;
+            uint2 head = make_uint2(kNone, 0);
+            if (hs < mend) head = xh[hs];
+            uint2 v = xh[cur];
+            v.x = uniform(v.x); v.y = uniform(v.y);
+            VLG_WALK_STAT(WS_ROUNDS, 1);
+            while (nrec < n_tiles) {
+                if (lane == pend_n) pend = make_uint2(cur, mbegin + (uint32_t)n_match);
+                ++pend_n;
+                ++nrec;
+                n_match += v.y;
+                cur = v.x;
+                VLG_WALK_STAT(WS_TILES, 1);
+                if (cur == kNone) break;
+                // the entry: head word (tile i behind the round's first, slot j) if i and j are small enough.  (cur < mend: a settled
+                // target is a slot of its own segment, so a head that was clipped is never asked for)
+                const uint64_t i = ((uint64_t)cur - first) / kTile;
+                const uint32_t j = cur % kTile;
+                if (i >= kWalkHeadTiles || j >= kWalkHeadSlots) { VLG_WALK_STAT(WS_MISSES, 1); break; }
+                const uint32_t src = (uint32_t)i * kWalkHeadSlots + j;
+                v.x = uniform(__shfl(head.x, src)); v.y = uniform(__shfl(head.y, src));
+            }
+        }
+        if (lane < pend_n) rec[pend_at + lane] = pend;
+        if (lane == 0) { rec_count[q] = nrec; counts[q] = n_match; }
+        return;
+    }
+    uint32_t q = (blockIdx.x - n_heavy) * blockDim.x + threadIdx.x;
     if (q >= nq) return;
+    if (rec_begin[q + 1] - rec_begin[q] >= wave_tiles) return;      // a heavy query: a wave above walks it
     const QueryMeta Q = qm[q];
     unsigned long long n_match = 0;
     uint32_t nrec = 0;

@@ -88,6 +88,10 @@ struct vlg_workspace {
     bool emit_direct = true;    // first positions only ("tuples" = 0): the emit pass of the chain writes them itself, after the counts came back, and no
                                 // gather pass runs (join_device.hpp: chain_emit_kernel<.., kDirect>); 0 = emit into mlist[] and gather, for an A/B inside
                                 // one library.  With tuples the gather pass runs whatever this says.
+    bool tile_scan = true;      // the tile pass of the chain resolves a tile by one two-level backward scan, half a wave per tile (join_device.hpp:
+                                // chain_tiles_scan); 0 = pointer doubling, a workgroup per tile, for an A/B inside one library.  xh[] is the same
+    bool walk_wave = true;      // queries whose level-0 segment spans at least kWalkWaveTiles chain tiles are walked by a wave each, which looks
+                                // ahead over the heads of the next tiles (join_device.hpp: chain_walk_kernel); 0 = a lane per query for all
     bool sweep_compact = true;  // round 0 of the sorted sweep writes its survivors densely and its partition sorts only them (sweep_kernels.hpp:
                                 // commit_turn); 0 = finished elements are carried through the partition with key = sigma, for an A/B inside one library
     uint64_t sweep_min = 1ull << 22;    // below this many occurrences the persistent random-access kernel is used
@@ -281,6 +285,8 @@ extern "C" vlg_status vlg_workspace_set_option(vlg_workspace* ws, const char* na
     if (!strcmp(name, "tuples")) { ws->tuples = value != 0; return VLG_OK; }
     if (!strcmp(name, "fuse_jump")) { ws->fuse_jump = value != 0; return VLG_OK; }
     if (!strcmp(name, "emit_direct")) { ws->emit_direct = value != 0; return VLG_OK; }
+    if (!strcmp(name, "tile_scan")) { ws->tile_scan = value != 0; return VLG_OK; }
+    if (!strcmp(name, "walk_wave")) { ws->walk_wave = value != 0; return VLG_OK; }
     if (!strcmp(name, "sweep_compact")) { ws->sweep_compact = value != 0; return VLG_OK; }
     if (!strcmp(name, "filter")) { ws->filter = value != 0; return VLG_OK; }
     if (!strcmp(name, "filter_min")) { ws->filter_min = (uint64_t)value; return VLG_OK; }
@@ -1350,14 +1356,14 @@ struct JoinChunk {
     std::vector<uint64_t> cls_slot_begin, cls_slot_end;
     svec<SegMeta> sm; svec<uint32_t> seg_begin;
     uint64_t T = 0, lvl0_begin = 0, lvl0_end = 0, t0 = 0;
-    svec<uint32_t> rec_begin, rec_query;
+    svec<uint32_t> rec_begin, rec_query, heavy;                     // heavy: the queries a wave walks (chain_walk_kernel)
     svec<unsigned long long> counts, first_of;
     // device arrays
     uint32_t* link = nullptr; pos_t* endp = nullptr;
     FeasBits fb; uint64_t* lvl_ptr[kBitLevels]; FeasBits* d_fb = nullptr; FeasRef fref{nullptr, nullptr};
     uint32_t* jump = nullptr; uint32_t* mlist = nullptr; uint2* xh = nullptr;
     SegMeta* d_sm = nullptr; QueryMeta* d_qm = nullptr; uint32_t* d_segb = nullptr; unsigned long long* d_counts = nullptr;
-    uint32_t* d_recb = nullptr; uint32_t* d_recc = nullptr; uint32_t* d_recq = nullptr; uint2* d_rec = nullptr;
+    uint32_t* d_recb = nullptr; uint32_t* d_recc = nullptr; uint32_t* d_recq = nullptr; uint2* d_rec = nullptr; uint32_t* d_heavy = nullptr;
 
     // list lengths as the join sees them: the survivors of the window filter where it ran
     uint64_t eo(uint64_t s) const { return fg ? fg->eff[s - fg->sub0] : pl.occ[s]; }
@@ -1488,6 +1494,7 @@ struct JoinChunk {
             }
             rec_begin[i + 1] = rec_begin[i] + cnt;
             rec_query.insert(rec_query.end(), cnt, i);
+            if (ws->walk_wave && cnt >= kWalkWaveTiles) heavy.push_back(i);
         }
         n_rec = rec_begin[nq];
         empty = lvl0_end <= lvl0_begin;
@@ -1524,6 +1531,7 @@ struct JoinChunk {
         d_recc = A.take<uint32_t>(nq);
         d_recq = A.take<uint32_t>(n_rec + 1);
         d_rec = A.take<uint2>(n_rec + 1);
+        d_heavy = A.take<uint32_t>(heavy.size() + 1);
         if (A.failed) return fail(VLG_E_INTERNAL, "arena carve failed (join)");
         return VLG_OK;
     }
@@ -1534,6 +1542,7 @@ struct JoinChunk {
         VLG_HIP_TRY(hipMemcpyAsync(d_fb, &fb, sizeof fb, hipMemcpyHostToDevice, st));
         VLG_HIP_TRY(hipMemcpyAsync(d_recb, rec_begin.data(), (nq + 1) * 4, hipMemcpyHostToDevice, st));
         if (n_rec) VLG_HIP_TRY(hipMemcpyAsync(d_recq, rec_query.data(), n_rec * 4, hipMemcpyHostToDevice, st));
+        if (!heavy.empty()) VLG_HIP_TRY(hipMemcpyAsync(d_heavy, heavy.data(), heavy.size() * 4, hipMemcpyHostToDevice, st));
         VLG_HIP_TRY(hipMemcpyAsync(d_sm, sm.data(), (nlive + 1) * sizeof(SegMeta), hipMemcpyHostToDevice, st));
         VLG_HIP_TRY(hipMemcpyAsync(d_segb, seg_begin.data(), (nlive + 2) * 4, hipMemcpyHostToDevice, st));
         VLG_HIP_TRY(hipMemcpyAsync(d_qm, qm.data(), nq * sizeof(QueryMeta), hipMemcpyHostToDevice, st));
@@ -1623,9 +1632,22 @@ struct JoinChunk {
                     const uint64_t p0 = std::max(cls_slot_end[d], lvl0_begin), p1 = std::min(cls_slot_begin[d - 1], lvl0_end);
                     if (p1 > p0) VLG_HIP_TRY(hipMemsetAsync(jump + p0, 0xFF, (p1 - p0) * 4, st));
                 }
-            hipLaunchKernelGGL(chain_tiles_kernel, dim3((uint32_t)((lvl0_end - t0 + kTile - 1) / kTile)), dim3(256), 0, st, jump, t0, lvl0_end, fref, d_segb,
-                               nlive, xh);
-            hipLaunchKernelGGL(chain_walk_kernel, dim3((nq + 63) / 64), dim3(64), 0, st, d_sm, d_qm, nq, fref, xh, d_recb, d_rec, d_recc, d_counts);
+            const uint32_t n_tiles = (uint32_t)((lvl0_end - t0 + kTile - 1) / kTile);
+            if (ws->tile_scan)
+                hipLaunchKernelGGL(chain_tiles_kernel<true>, dim3((n_tiles + kScanTiles - 1) / kScanTiles), dim3(256), 0, st, jump, t0, lvl0_end, fref,
+                                   d_segb, nlive, xh);
+            else
+                hipLaunchKernelGGL(chain_tiles_kernel<false>, dim3(n_tiles), dim3(256), 0, st, jump, t0, lvl0_end, fref, d_segb, nlive, xh);
+            const uint32_t n_heavy = (uint32_t)heavy.size();        // (empty with walk_wave 0: then no query counts as heavy)
+            hipLaunchKernelGGL(chain_walk_kernel, dim3(n_heavy + (nq + 63) / 64), dim3(64), 0, st, d_sm, d_qm, nq, fref, xh, d_recb, d_rec, d_recc, d_counts,
+                               d_heavy, n_heavy, ws->walk_wave ? kWalkWaveTiles : 0xFFFFFFFFu);
+#ifdef VLG_WALK_STATS
+            unsigned long long wst[WS_COUNT] = {0}, wzero[WS_COUNT] = {0};         // (a blocking copy: it waits for the launch)
+            VLG_HIP_TRY(hipMemcpyFromSymbol(wst, HIP_SYMBOL(g_walk_stats), sizeof wst));
+            VLG_HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_walk_stats), wzero, sizeof wzero));
+            fprintf(stderr, "[vlg walk stats] queries %u heavy %llu rounds %llu tiles %llu misses %llu\n", nq, wst[WS_QUERIES], wst[WS_ROUNDS],
+                    wst[WS_TILES], wst[WS_MISSES]);
+#endif
             if (n_rec && !direct)                                   // (direct: the emit runs when the result arrays exist, gather())
                 hipLaunchKernelGGL(HIP_KERNEL_NAME(chain_emit_kernel<pos_t, false>), dim3((n_rec + 3) / 4), dim3(256), 0, st, d_recb, d_recc, d_rec, n_rec,
                                    d_recq, jump, xh, lvl0_end, mlist, nullptr, nullptr, nullptr, nullptr, nullptr);
